@@ -14,25 +14,30 @@ One step = one frame through the reference's call protocol (`cl_wrap_output(rayg
 What `--gpus N` measures (one process per GPU, no data-path collective while tracing, GLOBAL work-item ids, so the
 assembled frame is bit-identical to a single-GPU render).  The HEADLINE is BASELINE.json's metric:
   strong  the FIXED 1920x1080 frame cut into N contiguous row strips (north_star's row-strip split)   <- value / ms_per_step
-and the same JSON line carries, as named legs under "legs" (each with value, value_per_gpu, ms_per_step, transport):
+and, with `--full`, the same JSON line carries, as named legs under "legs" (each with value, value_per_gpu, ms_per_step, transport):
   weak    every GPU keeps a 1920x1080 share of ONE 1920 x (1080*N) frame -- rank r owns every N-th 8-row band;
   c5      BASELINE config 5: 8192x8192, depth 4, N row strips, the single PNG written by rank 0 after the timed
           region (its time is reported separately).
 At N = 1 strong and weak are the same single-GPU frame.  `--scaling weak` / `--config c5` make that leg the headline instead;
-`--legs` picks which legs run.  Each step ends with ONE gather of the rows (packed to RGB888) into rank 0's frame buffer:
+`--legs` picks which legs `--full` runs.  Each step ends with ONE gather of the rows (packed to RGB888) into rank 0's frame buffer:
 `--transport rccl-gather` (default: torch.distributed.gather on the nccl backend = RCCL's gather) or `--transport peer`
 (every rank stores its share straight into rank 0's peer-mapped buffer; distributed.FrameGatherer), on a side stream and
 double-buffered so it overlaps the next frame's trace.
 
-Timing.  W warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides, max over ranks -- and, because K
-frames of 0.1 ms are a 2 ms region, that K-step loop is REPEATED until at least 50 ms have been timed: `ms_per_step` is the
-median repeat's time / K (min / max of the repeats beside it).  The kernel's own duration is hipEvent-timed around EVERY
-launch of one extra, untimed pass of K steps.
+Timing.  W warm-up steps (repeated until 50 ms have been spent warming), then EXACTLY K steps between barrier + synchronize
+on both sides, max over ranks: `ms_per_step` is that region's time / K.  With `--full` the K-step loop is then REPEATED until
+at least 50 ms have been timed (median / min / max of the repeats beside the headline), and the kernel's own duration is
+hipEvent-timed around EVERY launch of one extra, untimed pass of K steps.
 
 rays = path segments + shadow rays as the REFERENCE casts them, counted by the counting build of the kernel
 outside the timed region; `rays_traced` / `value_traced` leave out the shadow rays the kernel draws but does not trace
-(surfaces whose light terms are exactly zero).  rank 0 prints ONE JSON line; at N = 1 it also carries the strict (bit-exact
-parity) build timed on the same workload, the kernel's roofline figures and the CPU baseline (the oracle on the host cores).
+(surfaces whose light terms are exactly zero).  rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs (`--dump-outputs DIR`:
+the last timed step's frame as DIR/frame_rgb.npy, float32 [H, W, 3] in 0..255, or a fixed sample of it above 64 MB) and print
+the line.  `--full` adds everything else: the repeats and the kernel pass above, the other legs, and at N = 1 the PCIe-inclusive
+and moving-camera frame rates, the strict (bit-exact parity) build timed on the same workload, the reference driver's own
+800x600 depth-15 configuration, the kernel's roofline figures and the CPU baseline (the oracle on the host cores).
 """
 from __future__ import annotations
 
@@ -60,8 +65,10 @@ HBM_PEAK_GBPS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s
 VALU_PEAK_TFLOPS = 157.3        # MI355X_MICROARCH.md: peak fp32 vector
 VALU_CYCLES, TRANS_CYCLES = 2.0, 8.0   # MI355X_MICROARCH.md cycle constants: v_fma_f32 wave64 2 cycles per SIMD, transcendentals 8
 CLOCK_GHZ, SIMDS = 2.4, 1024
-MIN_TIMED_S = 0.05              # the K-step loop is repeated until this much has been timed
+MIN_TIMED_S = 0.05              # --full: the K-step loop is repeated until this much has been timed
 MAX_REPEATS = 200
+MIN_WARM_S = 0.05               # the W warm-up steps are repeated until this much has been spent warming
+DUMP_LIMIT = 64 << 20           # --dump-outputs: bytes written at most
 # fp32 operations of the reference's expression trees (DESIGN.md section "flop model")
 FLOP = dict(sphere_test=34, plane_test=14, shadow_ray=40, light_shade=94, shaded_hit=73, sky=20, texel=25)
 
@@ -226,35 +233,57 @@ class Leg:
         self.rays, self.rays_traced = int(tot[0].item()), int(tot[4].item())
         self.lane_util = float(tot[2].item() / max(tot[3].item(), 1.0))
 
+    def warm(self, warmup):
+        """`warmup` steps, repeated as a round until MIN_WARM_S have been spent warming, so that the timed steps meet a GPU
+        in its steady state (a first loop straight after a few warm-up steps runs some 5 % slow); every rank takes the same count."""
+        ctx, spent = self.ctx, 0.0
+        while warmup > 0 and spent < MIN_WARM_S:
+            t0 = time.perf_counter()
+            for k in range(warmup):
+                self.step(k)
+            self.gat.drain()
+            torch.cuda.synchronize()
+            t = torch.tensor([spent + time.perf_counter() - t0], dtype=torch.float64, device=ctx.dev)
+            if ctx.world > 1:
+                torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+            spent = float(t.item())
+
     def run(self, steps, warmup):
-        """-> dict of this leg's results (the same on every rank)."""
+        """Count, warm up, time EXACTLY `steps` steps once -> dict of this leg's results (the same on every rank)."""
         ctx = self.ctx
         self.count()
         for r in self.rr:
             r.w.set_timing_every(0)
-        for k in range(warmup):
-            self.step(k)
-        self.gat.drain()
-        times = [self.timed(steps)]
-        # repeat the K-step loop until MIN_TIMED_S have been timed; every rank takes the same count (the first time is a max over ranks)
-        reps = min(MAX_REPEATS, max(1, math.ceil(MIN_TIMED_S / max(times[0], 1e-6))))
-        for _ in range(reps - 1):
-            times.append(self.timed(steps))
-        el = statistics.median(times)
-        k_ms, launches = self.kernel_pass(steps)
+        self.warm(warmup)
+        self.times = [self.timed(steps)]
+        el = self.times[0]
         world = ctx.world
         sharding = ("single GPU" if world == 1 else
                     (f"{world} contiguous row strips" if self.layout == "strips" else f"interleaved 8-row bands x{world}") +
                     f" + one gather of RGB888 rows into rank 0 per frame ({'rccl-gather' if self.gat.transport == 'gather' else self.gat.transport})")
         return dict(mode=self.mode, frame=f"{self.W}x{self.H}", value=round(self.rays * steps / el / 1e6, 1), unit="Mrays/s",
                     value_per_gpu=round(self.rays * steps / el / 1e6 / world, 1), ms_per_step=round(el / steps * 1e3, 4),
-                    ms_per_step_min=round(min(times) / steps * 1e3, 4), ms_per_step_max=round(max(times) / steps * 1e3, 4),
-                    repeats=len(times), steps=steps, timed_s=round(sum(times), 4),
+                    ms_per_step_min=round(el / steps * 1e3, 4), ms_per_step_max=round(el / steps * 1e3, 4),
+                    repeats=1, steps=steps, timed_s=round(el, 4),
                     frames_per_s=round(steps / el, 1), rays=self.rays, rays_traced=self.rays_traced,
                     value_traced=round(self.rays_traced * steps / el / 1e6, 1), rays_per_pixel=round(self.rays / (self.W * self.H), 4),
-                    trace_kernel_ms=round(k_ms, 4), trace_launches_timed=launches, lane_utilisation=round(self.lane_util, 4),
+                    lane_utilisation=round(self.lane_util, 4),
                     transport="none" if world == 1 else ("rccl-gather" if self.gat.transport == "gather" else self.gat.transport),
-                    sharding=sharding, scaling="weak" if self.mode == "weak" else "strong", elapsed_median_s=el)
+                    sharding=sharding, scaling="weak" if self.mode == "weak" else "strong")
+
+    def extras(self, res, steps):
+        """--full, after run(): repeat the K-step loop until MIN_TIMED_S have been timed, then the hipEvent kernel pass -> res updated.
+        The headline `ms_per_step` stays the first loop's; the repeats (that loop included) give median / min / max beside it."""
+        times = self.times
+        # every rank takes the same count (the first time is a max over ranks)
+        reps = min(MAX_REPEATS, max(1, math.ceil(MIN_TIMED_S / max(times[0], 1e-6))))
+        for _ in range(reps - 1):
+            times.append(self.timed(steps))
+        k_ms, launches = self.kernel_pass(steps)
+        res.update(ms_per_step_median=round(statistics.median(times) / steps * 1e3, 4),
+                   ms_per_step_min=round(min(times) / steps * 1e3, 4), ms_per_step_max=round(max(times) / steps * 1e3, 4),
+                   repeats=len(times), timed_s=round(sum(times), 4), trace_kernel_ms=round(k_ms, 4), trace_launches_timed=launches)
+        return res
 
     def last_frame(self, steps):
         """rank 0: the frame of the last step as uint32 [H * W]"""
@@ -262,6 +291,22 @@ class Leg:
         if self.ctx.world == 1:
             return self.fbs[s][:self.px_rank].cpu().numpy().view(np.uint32)
         return self.gat.assemble(s).cpu().numpy().view(np.uint32)
+
+
+def dump_outputs(d, frame, W, H):
+    """The frame a caller of the timed path receives (packed 0x00RRGGBB) as float32 R, G, B in 0..255 -> DIR/frame_rgb.npy [H, W, 3];
+    a frame above DUMP_LIMIT as every stride-th pixel (a fixed sample, the same in every run) plus the pixels' indices."""
+    os.makedirs(d, exist_ok=True)
+    n = W * H
+    stride = math.ceil(n * (3 * 4 + 8) / (DUMP_LIMIT // 2)) if n * 3 * 4 > DUMP_LIMIT else 1   # 12 B of colour + 8 B of index
+    idx = np.arange(0, n, stride, dtype=np.int64) if stride > 1 else None
+    px = frame[:n] if idx is None else frame[idx]
+    rgb = np.stack([(px >> 16) & 255, (px >> 8) & 255, px & 255], -1).astype(np.float32)
+    if idx is None:
+        np.save(os.path.join(d, "frame_rgb.npy"), rgb.reshape(H, W, 3))
+    else:
+        np.save(os.path.join(d, "frame_rgb_sample.npy"), rgb)
+        np.save(os.path.join(d, "frame_sample_index.npy"), idx.astype(np.float64))
 
 
 def main():
@@ -273,7 +318,7 @@ def main():
                     help="which sharding the HEADLINE is: strong = the fixed 1920x1080 frame in row strips (default, BASELINE.json's metric); "
                          "weak = 1920x1080 per GPU of a taller frame.  The other one is reported as a leg")
     ap.add_argument("--config", choices=("c2", "c5"), default="c2", help="c5: the 8192x8192 depth-4 row-strip leg (+ the single PNG) is the headline")
-    ap.add_argument("--legs", default="all", help="comma list of strong,weak,c5 (or all / none): the legs reported beside the headline")
+    ap.add_argument("--legs", default="all", help="comma list of strong,weak,c5 (or all / none): the legs --full reports beside the headline")
     ap.add_argument("--strict", type=int, default=0, help="1: the headline itself runs the strict arithmetic build")
     ap.add_argument("--transport", choices=("rccl-gather", "gather", "peer", "auto"), default=os.environ.get("BENCH_TRANSPORT", "rccl-gather"),
                     help="how shares reach rank 0 (N > 1): ONE torch.distributed.gather per frame (RCCL's gather on the nccl backend; the default), "
@@ -287,6 +332,13 @@ def main():
     ap.add_argument("--rehearse-device-tensors", action="store_true",
                     help="with --rehearse: hand the GPU tensors to gloo directly (exercises the side-stream packing path)")
     ap.add_argument("--dump-png", default=None, help="rank 0 writes the headline leg's assembled frame here")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the frame of the last timed step to DIR/frame_rgb.npy (float32 [H, W, 3], 0..255; above "
+                         f"{DUMP_LIMIT >> 20} MB a fixed sample: DIR/frame_rgb_sample.npy [n, 3] + DIR/frame_sample_index.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: repeats of the K-step loop, the kernel pass, the other legs "
+                         "and, at N = 1, read-back and moving-camera rates, the strict build, the reference configuration, roofline "
+                         "figures and the CPU baseline (a plain run does only the headline)")
     args = ap.parse_args()
     if args.transport == "gather":
         args.transport = "rccl-gather"
@@ -317,7 +369,7 @@ def main():
     if world == 1 and head_mode == "weak":
         head_mode = "strong"                    # the same single-GPU frame
     want = ["strong", "weak", "c5"] if args.legs == "all" else ([] if args.legs in ("none", "") else args.legs.split(","))
-    want = [m for m in want if m in ("strong", "weak", "c5")]
+    want = [m for m in want if m in ("strong", "weak", "c5")] if args.full else []
 
     # ---- the headline leg
     head = Leg(ctx, head_mode, strict=bool(args.strict))
@@ -325,13 +377,22 @@ def main():
     legs = {head_mode: res}
     c5 = head_mode == "c5"
 
-    png = None
-    if rank == 0 and (args.dump_png or c5):
-        path = args.dump_png or os.path.join(ROOT, "gpurun_out", "c5.png")
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    if args.full:
+        head.extras(res, args.steps)           # more passes of the same K steps: the frame slots end as the timed loop left them
+
+    # the last step's frame, fetched once (assembling a gathered frame releases its slot)
+    full = t_host = None
+    if rank == 0 and (args.dump_outputs or args.dump_png or (c5 and args.full)):
         t = time.perf_counter()
         full = head.last_frame(args.steps)
         t_host = time.perf_counter() - t
+    if full is not None and args.dump_outputs:
+        dump_outputs(args.dump_outputs, full, head.W, head.H)
+
+    png = None
+    if rank == 0 and (args.dump_png or (c5 and args.full)):
+        path = args.dump_png or os.path.join(ROOT, "gpurun_out", "c5.png")
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         t = time.perf_counter()
         api.write_png(path, full, head.W, head.H)
         t_png = time.perf_counter() - t
@@ -344,7 +405,7 @@ def main():
     rr, px_rank, W, H = head.rr, head.px_rank, head.W, head.H
     host = np.empty(px_rank, np.uint32)
     rb, moving, strict_leg = [], None, None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         rr[0].w.set_async(False)
         for _ in range(5):
             tt = time.perf_counter()
@@ -384,10 +445,10 @@ def main():
                 r.look(**pkg.CAMERA_RAYPNG)
     cnt = head.cnt
     head.release()
-    if world == 1 and not args.strict and not args.no_strict_leg and not c5:
+    if args.full and world == 1 and not args.strict and not args.no_strict_leg and not c5:
         sl = Leg(ctx, head_mode, strict=True)
         n = max(min(args.steps, 100), 2)
-        sres = sl.run(n, 6)
+        sres = sl.extras(sl.run(n, 6), n)
         strict_leg = dict(ms_per_step=sres["ms_per_step"], ms_per_step_min=sres["ms_per_step_min"], ms_per_step_max=sres["ms_per_step_max"],
                           value=sres["value"], value_traced=sres["value_traced"], unit="Mrays/s", steps=n, repeats=sres["repeats"],
                           trace_kernel_ms=sres["trace_kernel_ms"], rays_traced=sres["rays_traced"],
@@ -397,7 +458,7 @@ def main():
     # ---- the reference driver's OWN configuration (800x600, MAX_DEPTH 15: raypng.c:6-7, raytracing.cl:8): a deep launch, bound by the refraction
     #      trees of a few tiles -- with the tree-parallel tail (csrc/whitted_tpt.inc) and, beside it, with the per-lane loop alone (variant 16)
     ref_leg = None
-    if rank == 0 and world == 1 and not args.strict and not c5 and not args.no_strict_leg:
+    if args.full and rank == 0 and world == 1 and not args.strict and not c5 and not args.no_strict_leg:
         from example_gui_opencl_raytracer_amd.renderer import Renderer
         r = Renderer(ctx.sc, ctx.tex, ctx.sky, 800, 600, depth=15, strict=False)
         r.look(**pkg.CAMERA_RAYPNG)
@@ -432,20 +493,12 @@ def main():
             continue
         n = max(2, min(args.steps, 20 if m == "c5" else 100))
         leg = Leg(ctx, m, strict=bool(args.strict))
-        legs[m] = leg.run(n, min(args.warmup, 5))
+        legs[m] = leg.extras(leg.run(n, min(args.warmup, 5)), n)
         leg.release()
         ctx.barrier()
 
     if rank == 0:
-        k_ms = res["trace_kernel_ms"]
-        # algorithmic HBM bytes of ONE trace launch on this rank: the 4-byte packed pixel per
-        # work-item + one 4-byte texel per texture / skybox fetch + the prepared geometry once
-        bytes_launch = 4 * px_rank + 4 * (cnt["texel_fetches"] + cnt["sky_fetches"]) + 16 * (4 + 2 * 2 + 2 * 3)
-        ach = bytes_launch / (k_ms * 1e-3) / 1e9
         single_c2 = world == 1 and not c5
-        khash = api.kernel_source_hash()
-        fe, wr = (profiled("FETCH_SIZE"), profiled("WRITE_SIZE")) if single_c2 and not args.strict else (None, None)
-        traffic = int((fe[0] + wr[0]) * 1024) if fe and wr else None
         strong = res["scaling"] == "strong"
         workload = ("C5: scenes/render.map 8192x8192 depth 4" if c5 else "C2: scenes/render.map (regenerated), camera raypng.c:17-21, 1920x1080"
                     + (" per GPU" if not strong else "") + ", depth 4, 2 soft-shadow samples, 4x256^2 textures + 4096x3072 skybox (procedural)")
@@ -463,18 +516,29 @@ def main():
             "value_per_gpu": res["value_per_gpu"],
             "rays": res["rays"], "rays_traced": res["rays_traced"], "value_traced": res["value_traced"],
             "frames_per_s": res["frames_per_s"],
-            "frames_per_s_with_readback": round(1.0 / statistics.median(rb), 1) if rb else None,
-            "trace_kernel_ms": k_ms, "trace_launches_timed": res["trace_launches_timed"],
             "lane_utilisation": res["lane_utilisation"],
-            "kernel_source_sha256_16": khash,
-            "legs": {m: {k: v for k, v in leg.items() if k != "elapsed_median_s"} for m, leg in legs.items()},
-            "roofline": {"bound": "hbm", "achieved": round(ach, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(ach / HBM_PEAK_GBPS, 5), "traffic": traffic,
-                         "algorithmic_bytes": bytes_launch, "traffic_source": fe[1] if traffic else None,
-                         "traffic_note": None if traffic or not single_c2 else "no committed rocprofv3 summary was taken from the loaded kernels (kernel_source_sha256_16)",
-                         "note": "algorithmic bytes/launch = 4 B x pixels + 4 B x texel fetches + geometry; the path is "
-                                 "VALU-bound (723-byte scene), see roofline_valu / roofline_valu_issue"},
+            "kernel_source_sha256_16": api.kernel_source_hash(),
+            "legs": legs,
         }
+        if args.full:
+            k_ms = res["trace_kernel_ms"]
+            # algorithmic HBM bytes of ONE trace launch on this rank: the 4-byte packed pixel per
+            # work-item + one 4-byte texel per texture / skybox fetch + the prepared geometry once
+            bytes_launch = 4 * px_rank + 4 * (cnt["texel_fetches"] + cnt["sky_fetches"]) + 16 * (4 + 2 * 2 + 2 * 3)
+            ach = bytes_launch / (k_ms * 1e-3) / 1e9
+            fe, wr = (profiled("FETCH_SIZE"), profiled("WRITE_SIZE")) if single_c2 and not args.strict else (None, None)
+            traffic = int((fe[0] + wr[0]) * 1024) if fe and wr else None
+            line.update({
+                "ms_per_step_median": res["ms_per_step_median"],
+                "frames_per_s_with_readback": round(1.0 / statistics.median(rb), 1) if rb else None,
+                "trace_kernel_ms": k_ms, "trace_launches_timed": res["trace_launches_timed"],
+                "roofline": {"bound": "hbm", "achieved": round(ach, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                             "frac": round(ach / HBM_PEAK_GBPS, 5), "traffic": traffic,
+                             "algorithmic_bytes": bytes_launch, "traffic_source": fe[1] if traffic else None,
+                             "traffic_note": None if traffic or not single_c2 else "no committed rocprofv3 summary was taken from the loaded kernels (kernel_source_sha256_16)",
+                             "note": "algorithmic bytes/launch = 4 B x pixels + 4 B x texel fetches + geometry; the path is "
+                                     "VALU-bound (723-byte scene), see roofline_valu / roofline_valu_issue"},
+            })
         if strict_leg:
             line["strict"] = strict_leg
         if moving:
@@ -483,7 +547,7 @@ def main():
             line["reference_config"] = ref_leg
         if png:
             line["png"] = png
-        vi, vt = (profiled("SQ_INSTS_VALU"), profiled("SQ_INSTS_VALU_TRANS_F32")) if single_c2 and not args.strict else (None, None)
+        vi, vt = (profiled("SQ_INSTS_VALU"), profiled("SQ_INSTS_VALU_TRANS_F32")) if args.full and single_c2 and not args.strict else (None, None)
         if vi:
             # VALU issue bound from the guide's cycle constants: a wave64 VALU instruction occupies its SIMD for 2 cycles,
             # a transcendental (v_rcp/rsq/sqrt/sin/cos/log/exp) for 8; 1 024 SIMDs at 2.4 GHz
@@ -495,7 +559,7 @@ def main():
                                            "issue_floor_ms": round(floor_ms, 4), "valu_instructions_per_launch": int(vi[0]),
                                            "transcendental_per_launch": int(trans), "cycles_plain": VALU_CYCLES, "cycles_transcendental": TRANS_CYCLES,
                                            "source": vi[1]}
-        if single_c2 and not args.no_cpu_baseline:
+        if args.full and single_c2 and not args.no_cpu_baseline:
             base, oc = cpu_baseline(ctx.sc, ctx.tex, ctx.sky, W, H)
             line["cpu_baseline"] = base
             flops = (FLOP["sphere_test"] * oc.sphere_tests + FLOP["plane_test"] * oc.plane_tests + FLOP["shadow_ray"] * oc.shadow_rays

@@ -62,9 +62,10 @@ def test_two_rank_weak_scaling_assembles_the_single_gpu_frame(demo_scene, tex, t
 
 def test_two_rank_default_is_the_fixed_frame_in_row_strips_with_all_three_legs(demo_scene, tex, tmp_path):
     """`bench.py --gpus N` with no further flags measures BASELINE.json's metric: the FIXED 1920x1080 frame in contiguous row
-    strips (536 + 544 rows here), ONE torch.distributed.gather per frame, and carries the weak-scaling and C5 results as named legs."""
+    strips (536 + 544 rows here), ONE torch.distributed.gather per frame; with `--full` it carries the weak-scaling and C5
+    results as named legs."""
     png = str(tmp_path / "strips.png")
-    line = _run_bench(["--steps", "4", "--warmup", "2"], png)
+    line = _run_bench(["--steps", "4", "--warmup", "2", "--full"], png)
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["config"]["frame"] == "1920x1080"
     assert "2 contiguous row strips" in line["config"]["sharding"] and "rccl-gather" in line["config"]["sharding"]
     assert 13.8 < line["config"]["rays_per_pixel"] < 13.95
@@ -137,3 +138,24 @@ def test_two_rank_c5_writes_the_single_png(demo_scene, tex, tmp_path):
     got = _png_frame(png)
     want = _single_gpu_frame(demo_scene, tex, 8192, 8192)
     assert np.array_equal(got, want)
+
+
+def test_plain_single_gpu_run_times_the_steps_and_dumps_the_frame(demo_scene, tex, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: exactly one K-step timed region, only the headline figures,
+    and the last step's frame as float32 R, G, B -- the single-GPU render."""
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 3 and line["repeats"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["timed_s"] == pytest.approx(line["ms_per_step"] * 3 / 1e3, rel=1e-2, abs=2e-4)
+    assert set(line["legs"]) == {"strong"}
+    assert not {"strict", "cpu_baseline", "reference_config", "moving_camera", "roofline"} & set(line)
+    assert sorted(os.listdir(out)) == ["frame_rgb.npy"]
+    got = np.load(out / "frame_rgb.npy")
+    assert got.shape == (1080, 1920, 3) and got.dtype == np.float32
+    want = _single_gpu_frame(demo_scene, tex, 1920, 1080).reshape(1080, 1920)
+    assert np.array_equal(got, np.stack([(want >> 16) & 255, (want >> 8) & 255, want & 255], -1).astype(np.float32))

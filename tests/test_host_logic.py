@@ -7,7 +7,7 @@ import re
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, CAM, REFERENCE_ROOT, ROOT
+from conftest import GOLDEN, CAM, ROOT
 from example_gui_opencl_raytracer_amd import api, scene as S, textures as T
 from example_gui_opencl_raytracer_amd.renderer import strip_rows
 
@@ -38,10 +38,10 @@ def test_one_byte_counts_limit():
         big.to_bytes()
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_ROOT), reason="reference tree absent")
 def test_regenerated_scene_equals_committed_render_map(demo_scene):
-    """Field by field (the committed file has uninitialised bytes in the struct padding)."""
-    ref = S.Scene.load(os.path.join(REFERENCE_ROOT, "scenes", "render.map"))
+    """Field by field (the committed file has uninitialised bytes in the struct padding).  The reference's scenes/render.map
+    is read from its copy in tests/golden/reference_scene/ (test_reference_fixture.py pins the copies)."""
+    ref = S.Scene.load(os.path.join(GOLDEN, "reference_scene", "render.map"))
     assert ref.counts == demo_scene.counts == (4, 2, 3)
 
     def fields(a):
@@ -195,11 +195,11 @@ def test_png_reader_rejects_sizes_that_overflow(tmp_path):
         api.read_png(str(tmp_path / "len.png"))
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_ROOT), reason="reference tree absent")
 def test_png_reader_on_the_reference_assets():
+    """The reference's asset PNGs, from their copies in tests/golden/reference_scene/."""
     from PIL import Image
     for name in ("check.png", "cobblestone.png", "sand.png", "grass.png"):
-        path = os.path.join(REFERENCE_ROOT, "assets", name)
+        path = os.path.join(GOLDEN, "reference_scene", name)
         mine = api.read_png(path)
         assert mine.shape == (256, 256, 4)
         assert np.array_equal(mine[..., :3], np.asarray(Image.open(path).convert("RGB")))
@@ -263,3 +263,26 @@ def test_library_exports_every_declared_symbol():
 def test_struct_mirror_matches_header():
     assert C.sizeof(api.cl_wrap) == 8 + 4 + 4 * 16 + 4 * 16 * 32 + 4 + 8 * 16 * 32   # impl, num, nums, ids, (pad), handles
     assert api.cl_wrap.buffers.offset % 8 == 0
+
+
+# ------------------------------------------------------------------ bench.py --dump-outputs
+def test_bench_dump_outputs_whole_frame_and_fixed_sample(tmp_path, monkeypatch):
+    """A frame within the byte limit is written whole as float32 [H, W, 3]; a larger one as the same fixed sample in every run,
+    within the limit."""
+    import bench
+    W, H = 64, 48
+    frame = (np.arange(W * H, dtype=np.uint32) * 2654435761 & 0xFFFFFF).astype(np.uint32)
+    rgb = np.stack([(frame >> 16) & 255, (frame >> 8) & 255, frame & 255], -1).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), frame, W, H)
+    got = np.load(tmp_path / "a" / "frame_rgb.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, rgb.reshape(H, W, 3))
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 16 << 10)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), frame, W, H)
+    assert sorted(os.listdir(tmp_path / "b")) == ["frame_rgb_sample.npy", "frame_sample_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 16 << 10
+    idx = np.load(tmp_path / "b" / "frame_sample_index.npy")
+    sample = np.load(tmp_path / "b" / "frame_rgb_sample.npy")
+    assert idx.dtype == np.float64 and sample.dtype == np.float32 and len(idx) == len(sample) > 100
+    assert np.array_equal(sample, rgb[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "frame_sample_index.npy"))

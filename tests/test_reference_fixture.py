@@ -54,14 +54,16 @@ def check_fixture_bar(st, what):
 
 
 def test_fixture_files_are_the_references_own():
-    """Where the reference tree is present: the committed copies are byte-identical to the reference's files."""
-    from conftest import REFERENCE_ROOT
-    if not os.path.isdir(REFERENCE_ROOT):
-        pytest.skip("reference tree absent")
+    """The committed copies are byte-identical to the reference's files: their SHA-256 digests equal the ones recorded from the
+    reference tree in tests/golden/reference_files_sha256.json."""
+    import hashlib
+    import json
+    recorded = json.load(open(os.path.join(GOLDEN, "reference_files_sha256.json")))
     pairs = {"scene.png": "out/scene.png", "render.map": "scenes/render.map", "stormydays.png": "assets/bg/stormydays.png"}
     pairs.update({n + ".png": f"assets/{n}.png" for n in ("cobblestone", "sand", "check", "grass")})
+    assert set(recorded) == set(pairs.values())
     for mine, theirs in pairs.items():
-        assert open(os.path.join(FIX, mine), "rb").read() == open(os.path.join(REFERENCE_ROOT, theirs), "rb").read(), mine
+        assert hashlib.sha256(open(os.path.join(FIX, mine), "rb").read()).hexdigest() == recorded[theirs], mine
 
 
 def test_oracle_reproduces_the_references_committed_render(oracle):
