@@ -40,7 +40,10 @@ extern "C" hipError_t wt_fast_launch_sched(const unsigned*, unsigned*, unsigned,
 
 namespace {
 
-enum { F_COUNT = 1, F_DEEP = 2, F_GEOM_LDS = 4, F_RAYS = 8, F_GRID = 16, F_OCC = 32, F_D8 = 64, F_D16 = 128 }; /* = WT_F_* of whitted_trace.inc */
+enum { F_COUNT = 1, F_DEEP = 2, F_GEOM_LDS = 4, F_RAYS = 8, F_GRID = 16, F_OCC = 32, F_D8 = 64, F_D16 = 128, F_SHAPE = 256 }; /* = WT_F_* of whitted_trace.inc */
+/* shallow fast launches of small LDS-geometry scenes run a kernel with the scene's counts compiled in (wt_shape of whitted_trace.inc): the
+ * counts whitted_launch.inc instantiates -- 1..SHAPE_MAX_SPHERES spheres, 0..SHAPE_MAX_PLANES planes, SHAPE_LIGHTS lights */
+constexpr uint32_t SHAPE_MAX_SPHERES = 4, SHAPE_MAX_PLANES = 2, SHAPE_LIGHTS = 3;
 /* deep launches of at least OCC_TILES_PER_DEPTH x depth wavefronts take the high-occupancy flavour: the serial tail of
  * the deepest refraction trees grows with the depth, the throughput part with the tile count (tools/occ_sweep.py on
  * render.map: wins 12-14 % at 2560x1440 depth 6 and 3840x2160 depth 6-8, loses 2-5 % at 1920x1080 and at depth 15) */
@@ -140,6 +143,7 @@ struct Impl {
     int fuse = 1;
     int async = 0;
     int variant = 0;
+    int last_trace_flags = -1;    /* the kernel flavour (WT_F_* flags) of the latest trace launch; -1 = none yet */
     int counting = 0;
     float through = 0.8f;  /* primitives.cl:7 TRANSPERENT_THROUGH; CLWRAP_THROUGH / clw_ext_set_shadow_through */
     int stamps = 0;        /* CLWRAP_STAMPS=1: hand the counter block to the (diagnostic) stamp build of the kernel */
@@ -635,6 +639,12 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
     }
     /* deep launches: the scratch part of the DFS stack is sized for the launch's depth (7 / 15 / 31 parents) */
     if ((flags & F_DEEP) && !(flags & F_COUNT) && !(I->variant & 2048)) flags |= I->depth <= 8 ? F_D8 : (I->depth <= 16 ? F_D16 : 0);
+    /* a small scene of the shallow fast build: its counts compiled in (the shaped kernel assumes the side table whenever there are planes);
+     * variant 8192 = the generic kernel */
+    if (!I->strict && flags == F_GEOM_LDS && P.ns >= 1u && P.ns <= SHAPE_MAX_SPHERES && P.np <= SHAPE_MAX_PLANES && P.nl == SHAPE_LIGHTS &&
+        (P.np == 0u || P.lpt) && !(I->variant & 8192))
+        flags |= F_SHAPE | (int)(P.ns << 9 | P.np << 12 | P.nl << 14);
+    I->last_trace_flags = flags;
     if (tail_wanted) {
         const uint64_t nslots = tpt_nslots, slice = tpt_slice, cap = tpt_cap;
         if (cap >= TPT_MIN_CAP) {
@@ -1016,6 +1026,7 @@ void clw_ext_set_shadow_through(cl_wrap* wrap, float factor) { impl_of(wrap)->th
 void clw_ext_set_grid(cl_wrap* wrap, int on) { impl_of(wrap)->use_grid = on ? 1 : 0; }
 void clw_ext_set_tile_sched(cl_wrap* wrap, int on) { Impl* I = impl_of(wrap); I->sched = on ? 1 : 0; for (auto& sc : I->scheds) sc.reset(); }
 void clw_ext_set_variant(cl_wrap* wrap, int variant) { impl_of(wrap)->variant = variant; }
+int clw_ext_last_trace_flags(cl_wrap* wrap) { return impl_of(wrap)->last_trace_flags; }
 void clw_ext_set_tpt(cl_wrap* wrap, int max_lanes, int min_paths, int pool_mb) {
     Impl* I = impl_of(wrap);
     if (max_lanes >= 0) I->tpt_max = (unsigned)std::min(max_lanes, 64);

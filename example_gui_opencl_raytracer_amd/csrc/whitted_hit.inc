@@ -56,8 +56,8 @@
                     }
                 }
             };
-            for (unsigned base = 0; base < P.nl; base += 4u) {
-                const unsigned left = P.nl - base;
+            for (unsigned base = 0; base < SH::nl(P); base += 4u) {
+                const unsigned left = SH::nl(P) - base;
                 if (left >= 4u) probe_chunk(wt_int<4>{}, base);
                 else if (left == 3u) probe_chunk(wt_int<3>{}, base);
                 else if (left == 2u) probe_chunk(wt_int<2>{}, base);
@@ -68,13 +68,13 @@
                     if (GRID) {
                         if (wt_grid_occluded(P, r, tl)) lit = false;
                     }
-                    for (unsigned i = 0; !GRID && i < P.ns; i++) {
+                    for (unsigned i = 0; !GRID && i < SH::ns(P); i++) {
                         float4 s = wt_geom<GEOM_LDS>(P, sg, i);
                         float t;
                         bool hit = wt_sphere(r, s, t);
                         if (hit && t <= tl && !(__float_as_uint(s.w) >> 31)) lit = false;
                     }
-                    for (unsigned i = 0; i < P.np; i++) {
+                    for (unsigned i = 0; i < SH::np(P); i++) {
                         float4 n = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * i);
                         float4 p0 = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * i + 1);
                         float t;
@@ -96,14 +96,14 @@
                 if (GRID) {
                     best = wt_grid_nearest(P, r, tbest);
                 } else {
-                    for (unsigned base = 0; base < P.ns; base += 4u) {      /* four spheres at a time, see the light probe */
+                    for (unsigned base = 0; base < SH::ns(P); base += 4u) {      /* four spheres at a time, see the light probe */
                         float4 s4[4]; float bq[4], Dq[4]; bool ok[4]; bool any = false;
 #pragma unroll
-                        for (int k = 0; k < 4; k++) s4[k] = wt_geom<GEOM_LDS>(P, sg, min(base + k, P.ns - 1u));
+                        for (int k = 0; k < 4; k++) s4[k] = wt_geom<GEOM_LDS>(P, sg, min(base + k, SH::ns(P) - 1u));
 #pragma unroll
                         for (int k = 0; k < 4; k++) {
                             const sph_pre pre = wt_sphere_pre(r.o, s4[k]);
-                            ok[k] = wt_sphere_disc(pre, r.d, r.a4, bq[k], Dq[k]) && (base + k < P.ns);
+                            ok[k] = wt_sphere_disc(pre, r.d, r.a4, bq[k], Dq[k]) && (base + k < SH::ns(P));
                             any |= ok[k];
                         }
                         if (__builtin_amdgcn_ballot_w64(any)) {
@@ -117,12 +117,12 @@
                         }
                     }
                 }
-                for (unsigned i = 0; i < P.np; i++) {
+                for (unsigned i = 0; i < SH::np(P); i++) {
                     float4 n = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * i);
                     float4 p0 = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * i + 1);
                     float t;
                     bool hit = wt_plane(r, n, p0, t);
-                    if (hit && !(t >= tbest)) { tbest = t; best = (int)(P.ns + i); }
+                    if (hit && !(t >= tbest)) { tbest = t; best = (int)(SH::ns(P) + i); }
                 }
                 WT_STAMP(WT_ST_NEAREST);
                 if (best < 0) {
@@ -134,11 +134,11 @@
                     ip = wt_madd3(d, tbest, o);
                     prim = (unsigned)best;
                     textured = false;
-                    if ((unsigned)best < P.ns) {
+                    if ((unsigned)best < SH::ns(P)) {
                         float4 s = wt_geom<GEOM_LDS>(P, sg, (unsigned)best);
                         nrm = wt_normalize(ip - mk3(s.x, s.y, s.z));
                     } else {
-                        unsigned pi = (unsigned)best - P.ns;
+                        unsigned pi = (unsigned)best - SH::ns(P);
                         float4 n = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * pi);
                         nrm = mk3(n.x, n.y, n.z);               /* never flipped toward the ray */
                         if (n.w != 0.0f) {                       /* texture_id >= 0 */
@@ -148,11 +148,11 @@
                         }
                     }
                     /* material of the winner, gathered from the raw arrays */
-                    wt_mat_set_b(m, wt_mat_f4(P, prim, 1u));
+                    wt_mat_set_b(m, wt_mat_f4(P, prim, 1u, SH::ns(P)));
                     {
-                        const float4 a_ = wt_mat_f4(P, prim, 0u);
+                        const float4 a_ = wt_mat_f4(P, prim, 0u, SH::ns(P));
                         m.rgb = mk3(a_.x, a_.y, a_.z);
-                        wt_mat_set_c(m, wt_mat_f4(P, prim, 2u));
+                        wt_mat_set_c(m, wt_mat_f4(P, prim, 2u, SH::ns(P)));
                     }
                     ip = wt_madd3(nrm, WT_EPSILON, ip);
                     cost += 3u;

@@ -12,6 +12,20 @@ static hipError_t wt_launch_one(const whitted_params* P, unsigned grid, size_t d
 
 extern "C" hipError_t WT_LAUNCH_TRACE(const whitted_params* P, int flags, unsigned grid, size_t dyn_lds,
                                       hipStream_t s) {
+#if !WT_STRICT
+    using WT_NS::WT_F_GEOM_LDS; using WT_NS::WT_F_SHAPE;
+    if (flags & WT_F_SHAPE) {
+        /* the shaped flavour (wt_shape): exactly these counts are compiled -- 1..4 spheres, 0..2 planes, 3 lights; the shim asks for no other */
+        switch (flags) {
+#define WT_SHAPE_CASE(ns, np) case WT_SHAPE_FLAGS(ns, np, 3): return wt_launch_one<WT_SHAPE_FLAGS(ns, np, 3)>(P, grid, dyn_lds, s);
+#define WT_SHAPE_CASES(ns) WT_SHAPE_CASE(ns, 0) WT_SHAPE_CASE(ns, 1) WT_SHAPE_CASE(ns, 2)
+            WT_SHAPE_CASES(1) WT_SHAPE_CASES(2) WT_SHAPE_CASES(3) WT_SHAPE_CASES(4)
+#undef WT_SHAPE_CASES
+#undef WT_SHAPE_CASE
+        }
+        return hipErrorInvalidValue;
+    }
+#endif
     switch (flags & 255) {
 #define WT_CASE(F) case F: return wt_launch_one<F>(P, grid, dyn_lds, s);
         WT_CASE(0) WT_CASE(1) WT_CASE(2) WT_CASE(3) WT_CASE(4) WT_CASE(5) WT_CASE(6) WT_CASE(7)

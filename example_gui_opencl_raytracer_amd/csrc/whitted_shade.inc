@@ -71,14 +71,14 @@
                 }
                 WT_STAMP(WT_ST_SHADOW);     /* samples, walks and the lights' terms of a grid build, all under "shadow" */
             } else
-            for (unsigned lb = 0; lb < P.nl; lb += LCH) {
+            for (unsigned lb = 0; lb < SH::nl(P); lb += LCH) {
                 f3 rd[NR];
                 float tl[NR], a4[NR], a2[NR], op[NR], dl[LCH], spec[LCH], diff[LCH], opu[LCH];
                 bool needk[LCH], known[LCH];
 #pragma unroll
                 for (int k = 0; k < LCH; k++) {
                     dl[k] = 1.0f; spec[k] = 0.0f; diff[k] = 0.0f; needk[k] = false; known[k] = false; opu[k] = 1.0f;
-                    if (lb + k < P.nl) {                                   /* wave-uniform */
+                    if (lb + k < SH::nl(P)) {                                   /* wave-uniform */
                         const float4 l0 = wt_geom<GEOM_LDS>(P, sg, g_lgt + 2 * (lb + k));
                         const light_terms L = wt_light_terms(l0, ip, nrm, view, m.shininess, ks, kd);
                         dl[k] = L.dl; spec[k] = L.spec; diff[k] = L.diff; needk[k] = L.need;
@@ -119,7 +119,7 @@
                 bool any_sample = false;
 #pragma unroll
                 for (int k = 0; k < LCH; k++) {
-                    const bool ex = lb + k < P.nl;                     /* wave-uniform */
+                    const bool ex = lb + k < SH::nl(P);                     /* wave-uniform */
                     const bool sample = needk[k] && !known[k];
                     const bool wave_sample = __builtin_amdgcn_ballot_w64(sample) != 0;
                     any_sample |= wave_sample;
@@ -147,11 +147,11 @@
                 WT_STAMP(WT_ST_LIGHTS);
                 /* (not in the high-occupancy deep flavour: its register cap turns the table's four values into spills, +3 % at C3) */
                 if (any_sample)
-                    wt_shadow_batch<GEOM_LDS, NR, !(DEEP && wt_cfg<FLAGS>::occ), SPHCULL>(P, sg, g_pln, ip, rd, tl, a4, a2, op, LCH == 3 ? lb / 3u : ~0u, dl, cand);
+                    wt_shadow_batch<GEOM_LDS, NR, !(DEEP && wt_cfg<FLAGS>::occ), SPHCULL, FLAGS>(P, sg, g_pln, ip, rd, tl, a4, a2, op, LCH == 3 ? lb / 3u : ~0u, dl, cand);
                 WT_STAMP(WT_ST_SHADOW);
 #pragma unroll
                 for (int k = 0; k < LCH; k++) {
-                    if (lb + k < P.nl) {
+                    if (lb + k < SH::nl(P)) {
                         const float4 l1 = wt_geom<GEOM_LDS>(P, sg, g_lgt + 2 * (lb + k) + 1);
                         float soft = 0.0f;
 #pragma unroll

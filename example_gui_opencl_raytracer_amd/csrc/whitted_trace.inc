@@ -455,8 +455,8 @@ struct mat_t {
 };
 /* float4 k (0: rgb | 1: ambient, diffuse, specular, shininess | 2: transparent, dielectric, n, reflectivity) of the
  * material of primitive `prim` (sphere index, or ns + plane index), gathered from the raw arrays for the winner only. */
-__device__ __forceinline__ float4 wt_mat_f4(const whitted_params& P, unsigned prim, unsigned k) {
-    const uint8_t* raw = prim < P.ns ? P.spheres_raw + 96 * (size_t)prim : P.planes_raw + 96 * (size_t)(prim - P.ns);
+__device__ __forceinline__ float4 wt_mat_f4(const whitted_params& P, unsigned prim, unsigned k, unsigned ns) {   /* ns = P.ns */
+    const uint8_t* raw = prim < ns ? P.spheres_raw + 96 * (size_t)prim : P.planes_raw + 96 * (size_t)(prim - ns);
     return ((const float4*)(raw + 32))[k];
 }
 __device__ __forceinline__ void wt_mat_set_b(mat_t& m, float4 b) {
@@ -646,6 +646,30 @@ __device__ __forceinline__ float4 wt_geom(const whitted_params& P, const float4*
     if (GEOM_LDS) return sg[i];
     return ((const float4*)P.geom)[i];
 }
+
+
+enum { WT_F_COUNT = 1, WT_F_DEEP = 2, WT_F_GEOM_LDS = 4, WT_F_RAYS = 8, WT_F_GRID = 16,
+       WT_F_OCC = 32 /* deep builds only: the high-occupancy flavour (see WT_LDS_LEVELS above) */,
+       WT_F_D8 = 64, WT_F_D16 = 128 /* deep builds only: the launch's depth is <= 8 / <= 16, so the DFS stack holds at most 7 / 15 parents and the
+                                       part of it kept in scratch is sized for that instead of for CLW_MAX_DEPTH */,
+       WT_F_SHAPE = 256 /* shallow fast LDS-geometry build only: the scene's counts are compiled in (wt_shape) */ };
+
+/* ---- the scene's primitive counts: launch parameters, or compile-time constants (FLAGS & WT_F_SHAPE) ----------------------------
+ * A small scene's loops over 4 spheres, 2 planes and 3 lights are mostly loop control, guards and selects around little arithmetic.
+ * The shaped flavour carries ns, np and nl in FLAGS bits 9-11, 12-13 and 14-16: every sphere, plane and light loop of the hot path
+ * unrolls, the geometry offsets and the early-out ballots' positions become constants, and the side-table branch folds (the shim
+ * launches it only when the light / plane side table is on or there are no planes).  Same operations in the same order: the frame is
+ * the generic kernel's, bit for bit.  (WT_SHAPE_FLAGS: hip_wrap.cpp picks the kernel from the prepared scene.) */
+#define WT_SHAPE_FLAGS(ns, np, nl) (WT_F_GEOM_LDS | WT_F_SHAPE | ((ns) << 9) | ((np) << 12) | ((nl) << 14))
+template <int FLAGS>
+struct wt_shape {
+    static constexpr bool on = (FLAGS & WT_F_SHAPE) != 0;
+    static constexpr unsigned cns = ((unsigned)FLAGS >> 9) & 7u, cnp = ((unsigned)FLAGS >> 12) & 3u, cnl = ((unsigned)FLAGS >> 14) & 7u;
+    static __device__ __forceinline__ unsigned ns(const whitted_params& P) { return on ? cns : P.ns; }
+    static __device__ __forceinline__ unsigned np(const whitted_params& P) { return on ? cnp : P.np; }
+    static __device__ __forceinline__ unsigned nl(const whitted_params& P) { return on ? cnl : P.nl; }
+    static __device__ __forceinline__ bool lpt(const whitted_params& P) { return on ? true : P.lpt != 0u; }
+};
 
 
 /* ---- uniform-grid traversal over the spheres (big scenes; FLAGS & WT_F_GRID) ------------------------------
@@ -1158,13 +1182,14 @@ __device__ __forceinline__ unsigned long long wt_sphere_candidates(const whitted
  * light sphere lie on the same side of the plane, with margins ten times the rounding involved, so the reference's
  * predicate `b != 0 && 0 < num/b < tl` (primitives.cl:422-437) is false whatever the sample.  In render.map no plane
  * ever lies between a surface and a light: 12 of the 36 tests of a shaded hit go. */
-template <bool GEOM_LDS, int NR, bool CULL, bool MASKED = false>
+template <bool GEOM_LDS, int NR, bool CULL, bool MASKED = false, int SHF = 0>
 __device__ __forceinline__ void wt_shadow_batch(const whitted_params& P, const float4* sg, unsigned g_pln, f3 ip,
                                                 const f3 (&rd)[NR], const float (&tl)[NR], const float (&a4)[NR],
                                                 const float (&a2)[NR], float (&op)[NR], unsigned chunk,
                                                 const float (&dlc)[NR / WT_SOFT], const unsigned long long cand = ~0ull) {
     /* `cand` (wave-uniform; scenes of <= 64 spheres): bit i clear = no ray of this batch, from any lane, can meet sphere i in front of its
      * sample (wt_sphere_candidates): the sphere is not tested.  Which spheres are tested never changes a factor: a skipped test could only fail. */
+    typedef wt_shape<SHF> SH;                                /* SHF: the caller's FLAGS (compile-time counts, wt_shape) */
     const bool masked = MASKED && P.ns <= 64u;               /* (MASKED: deep builds; the other builds keep exactly the plain loop below) */
     unsigned long long todo = !masked ? 0ull : ((P.ns == 64u ? ~0ull : ((1ull << P.ns) - 1ull)) & cand);
     for (unsigned n = 0; todo != 0ull; n++) {
@@ -1192,7 +1217,7 @@ __device__ __forceinline__ void wt_shadow_batch(const whitted_params& P, const f
             }
         }
     }
-    for (unsigned i = 0; !masked && i < P.ns; i++) {
+    for (unsigned i = 0; !masked && i < SH::ns(P); i++) {
         if ((i & 3u) == 3u) {   /* every fourth sphere: is any ray of any lane still undecided? */
             /* op >= 0: all six are zero iff the OR of their bit patterns is */
             unsigned live = 0u;
@@ -1216,7 +1241,7 @@ __device__ __forceinline__ void wt_shadow_batch(const whitted_params& P, const f
             }
         }
     }
-    for (unsigned i = 0; i < P.np; i++) {
+    for (unsigned i = 0; i < SH::np(P); i++) {
         if ((i & 3u) == 0u) {   /* after the spheres, then every fourth plane */
             unsigned live = 0u;
 #pragma unroll
@@ -1229,8 +1254,8 @@ __device__ __forceinline__ void wt_shadow_batch(const whitted_params& P, const f
         bool skip[NR / WT_SOFT];
 #pragma unroll
         for (int k = 0; k < NR / WT_SOFT; k++) skip[k] = false;
-        if (CULL && P.lpt && chunk != ~0u) {                               /* wave-uniform */
-            const float4 mu = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * P.np + 2 * P.nl + chunk * P.np + i);
+        if (CULL && SH::lpt(P) && chunk != ~0u) {                          /* wave-uniform */
+            const float4 mu = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * SH::np(P) + 2 * SH::nl(P) + chunk * SH::np(P) + i);
             const float mus[3] = {mu.x, mu.y, mu.z};
             const float an = 1e-5f * fabsf(num) * mu.w;                    /* |num| in units of distance, x 1e-5 */
 #pragma unroll
@@ -1254,11 +1279,6 @@ __device__ __forceinline__ void wt_stage_scene(const whitted_params& P, float4* 
     for (unsigned i = tid; i < P.geom_f4; i += nthreads) s_geom[i] = ((const float4*)P.geom)[i];
     __syncthreads();
 }
-
-enum { WT_F_COUNT = 1, WT_F_DEEP = 2, WT_F_GEOM_LDS = 4, WT_F_RAYS = 8, WT_F_GRID = 16,
-       WT_F_OCC = 32 /* deep builds only: the high-occupancy flavour (see WT_LDS_LEVELS above) */,
-       WT_F_D8 = 64, WT_F_D16 = 128 /* deep builds only: the launch's depth is <= 8 / <= 16, so the DFS stack holds at most 7 / 15 parents and the
-                                       part of it kept in scratch is sized for that instead of for CLW_MAX_DEPTH */ };
 
 #include "whitted_terms.inc"
 
@@ -1397,7 +1417,9 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
     unsigned c_known = 0, c_visbad = 0; /* lights whose samples were decided by their visibility class; verification build: ... wrongly */
     unsigned c_tptrun = 0, c_tptfail = 0, c_tptnodes = 0;   /* tiles finished by the tree-parallel tail / that it gave up on; nodes it traced */
 
-    const unsigned g_pln = P.ns, g_lgt = P.ns + 2 * P.np;
+    /* the scene's counts (compile-time constants in the shaped flavour, wt_shape) and the offsets of planes and lights in the geometry */
+    typedef wt_shape<FLAGS> SH;
+    const unsigned g_pln = SH::ns(P), g_lgt = SH::ns(P) + 2 * SH::np(P);
 
     /* scheduling hint for the next frame's dispatch order.  Small scenes: per lane 1 per loop iteration, +3 when it shades;
      * the tile reports its most expensive pixel (the serial chain of a refraction tree is what makes a tile late).  Grid
@@ -1741,6 +1763,7 @@ __global__ void __launch_bounds__(64) wt_unit_scene(const whitted_params P, int 
     constexpr bool UNIT_CT = false;                         /* the unit-test kernel takes rays as given */
     if (GEOM_LDS) wt_stage_scene(P, s_geom, tid, 64u);
     const float4* sg = s_geom;
+    typedef wt_shape<0> SH;                               /* (the counts as whitted_hit.inc reads them: the launch's) */
     const unsigned g_pln = P.ns, g_lgt = P.ns + 2 * P.np;
     const unsigned i = blockIdx.x * 64 + tid;
     if (i >= n) return;

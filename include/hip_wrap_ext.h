@@ -159,12 +159,16 @@ void clw_ext_unit_scene(cl_wrap* wrap, cl_uint kernel_id, int op, const float* i
  * order, 8 no uniform grid, 16 no tree-parallel tail (deep launches run their per-lane loop to the end), 64 never the high-occupancy flavour of the deep build,
  * 128 no light / plane side table (every shadow ray tests every plane), 256 no visibility classes (every needed shadow ray is traced),
  * 4096 heavy tiles of deep launches are not split over several wavefronts,
+ * 8192 small scenes of the shallow fast build run the generic trace kernel instead of the one with the scene's counts compiled in,
  * 2048 deep launches always carry the full-depth (31-parent) scratch stack instead of one sized for their depth,
  * 1024 (with clw_ext_enable_counters) VERIFICATION of the visibility classes: lights are classified AND traced, counter word 9 =
  * lights classified, word 28 = lights whose traced factors differ from their class's (must read 0),
  * 512 DIAGNOSTIC builds only (-DWT_TIMELINE=1, tools/timeline.py): the tile-cost buffer receives when each tile's wave ran inside the launch
  * (CLWRAP_TIMELINE_SHIFT = tick of 10 ns << shift; CLWRAP_TIMELINE_EDGES = 1 / 2: its prologue and epilogue instead); no effect otherwise. */
 void clw_ext_set_variant(cl_wrap* wrap, int variant);
+/* The kernel flavour of the latest trace launch: its WT_F_* flags (csrc/whitted_trace.inc; bit 256 = the scene's counts compiled in,
+ * ns | np << 3 | nl << 5 in bits 9..16), -1 before the first launch.  For tests and A/B runs. */
+int clw_ext_last_trace_flags(cl_wrap* wrap);
 
 /* The tree-parallel tail of deep launches (depth > 4; csrc/whitted_tpt.inc): once at most `max_lanes` lanes of a tile's wavefront are
  * alive and they hold at least `min_paths` pending paths (current segments + continuations on their stacks), the rest of the tile is
