@@ -525,6 +525,7 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
     bind_scene(w, I, kid, P, flags, dyn_lds);
     P.n_items = (uint32_t)n64;
     P.depth = I->depth;
+    P.untrimmed = (I->variant & 16384) ? 1u : 0u;
     P.out = (uint32_t*)out->dptr;
     P.out_rgb = I->debug_rgb;
     P.diag = (I->variant & 512) ? (env_int("CLWRAP_TIMELINE_EDGES", 0) ? 255u + (uint32_t)env_int("CLWRAP_TIMELINE_EDGES", 0) : 1u + (uint32_t)env_int("CLWRAP_TIMELINE_SHIFT", 0)) : 0u;

@@ -2,6 +2,13 @@
  * textually included twice by whitted_trace.inc.  WT_BOUNCE_PUSH(rec) takes the parent record (the reflected continuation): the per-lane
  * loop stores it on the lane's DFS stack, the tree-parallel tail makes it a node of its own. */
             /* ---- Fresnel, reflection, refraction child (raytracing.cl:139-179) --- */
+            /* On a path's last level (WT_BOUNCE_LAST: depth >= D after the step below) no child is pushed, and whitted_pop.inc then overwrites
+             * o, d, depth, n1 and f from the parent's record or ends the lane: nothing the block computes is read again, and a wave none of whose
+             * lanes goes further branches over it.  (`o = ip` stays in front of the branch: the old origin then dies on both paths; with the move
+             * inside the block the shaped kernel spilled five more registers, one of them inside the loop.) */
+            o = ip;
+            depth++;
+            if (!(WT_BOUNCE_LAST)) {
             const f3 incident = d;
             float n2 = (n1 == WT_DEFAULT_N) ? m.n : WT_DEFAULT_N;   /* binary media model */
             float ra = m.reflectivity;
@@ -9,8 +16,6 @@
             const float old_f = f;
             f *= ra;
             d = wt_reflect(d, nrm);
-            o = ip;
-            depth++;
             /* a child pushed at depth == D would end at once and add nothing: skip it */
             if (m.transparent && sp + 1 < D && ra < 1.0f && depth < D) {
                 f3 co = o, cn = nrm;
@@ -27,4 +32,4 @@
                     n1 = n2; f = old_f * (1.0f - ra);
                 }
             }
-        
+            }

@@ -54,6 +54,8 @@ typedef struct {
     uint32_t tpt_clock;    /* DIAGNOSTIC: 1 = the tail books its phases' durations into counter words 10-25 (`counters` must be set) */
     uint32_t cost_sum;     /* 1: a tile's cost is the SUM over its lanes (and over the wavefronts that share the tile), added atomically to a zeroed tile_cost; 0: the maximum over its lanes, stored */
     int32_t depth;         /* reference MAX_DEPTH                                     */
+    uint32_t untrimmed;    /* A/B and equivalence tests (variant 16384): 1 = the bounce block also runs on a path's last level and the tile cost is
+                              reduced by the shuffle butterfly, as before both were trimmed (whitted_bounce.inc, wt_wave_reduce); same image, same costs */
     /* scene */
     const float* geom;     /* float4 stream, layout above                             */
     const float* ptex;     /* float4 x 2 per plane                                    */

@@ -198,6 +198,8 @@
 #undef WT_HIT_COLOUR
 #undef WT_HIT_AMBIENT
 #undef WT_BOUNCE_PUSH
+#undef WT_BOUNCE_LAST
+#define WT_BOUNCE_LAST false            /* the tail runs the whole bounce on every node, as before */
 #define WT_HIT_COLOUR(c) t_col = (c)
 #define WT_HIT_AMBIENT(cf, a) do { t_col = (cf); t_ambk = (a); } while (0)
 #define WT_BOUNCE_PUSH(rec) do { t_pushed = true; _Pragma("unroll") for (int w_ = 0; w_ < WT_REC; w_++) t_prec[w_] = (rec)[w_]; } while (0)

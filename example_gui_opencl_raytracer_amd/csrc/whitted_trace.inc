@@ -1290,6 +1290,24 @@ struct wt_cfg {
     static constexpr int max_levels = !deep ? 3 : ((FLAGS & 64) ? 7 : ((FLAGS & 128) ? 15 : CLW_MAX_DEPTH - 1));
     static constexpr int min_waves = deep ? (occ ? WT_OCC_WAVES : WT_MIN_WAVES) : ((grid && !WT_STRICT) ? WT_GRID_SHALLOW_WAVES : WT_SHALLOW_WAVES);
 };
+/* Sum (SUM) or maximum of `c` over the 64 lanes of a full wave, uniform in every lane: DPP row shifts fold each row of 16 into its lane 15,
+ * two row broadcasts fold the four rows into lane 63, one v_readlane fetches it -- a handful of VALU instructions, where the __shfl_xor
+ * butterfly is six ds_bpermute_b32 round trips through the LDS crossbar with a wait each.  Lanes a shift or broadcast does not reach
+ * take 0, the identity of both operations on unsigned values; integer sums and maxima are exact in any order. */
+template <bool SUM>
+__device__ __forceinline__ unsigned wt_wave_reduce(unsigned c) {
+#define WT_DPP_STEP(ctrl, rows) do { const unsigned t_ = (unsigned)__builtin_amdgcn_update_dpp(0, (int)c, ctrl, rows, 0xF, false); \
+                                     c = SUM ? c + t_ : max(c, t_); } while (0)
+    WT_DPP_STEP(0x111, 0xF);    /* row_shr:1 */
+    WT_DPP_STEP(0x112, 0xF);    /* row_shr:2 */
+    WT_DPP_STEP(0x114, 0xF);    /* row_shr:4 */
+    WT_DPP_STEP(0x118, 0xF);    /* row_shr:8 */
+    WT_DPP_STEP(0x142, 0xA);    /* row_bcast:15 into rows 1 and 3 */
+    WT_DPP_STEP(0x143, 0xC);    /* row_bcast:31 into rows 2 and 3 */
+#undef WT_DPP_STEP
+    return (unsigned)__builtin_amdgcn_readlane((int)c, 63);
+}
+
 /* One tile (tiled launches) or one block of work-items: the whole trace of its pixels.  `wg` is the workgroup's number in
  * the launch's dispatch order (blockIdx.x). */
 typedef const __attribute__((address_space(4))) whitted_params* wt_kparams_t;
@@ -1492,8 +1510,12 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
     if (P.tiled && P.tile_cost) {       /* wave-uniform branch */
         unsigned c = cost;
         if (GRID || WT_COST_LIFETIME) c = (unsigned)min((__builtin_amdgcn_s_memtime() - t_begin) >> 8, 0xFFFFFFFFull);
-        else if (P.cost_sum) for (int off = 32; off > 0; off >>= 1) c += (unsigned)__shfl_xor((int)c, off);   /* the wave's total work */
-        else for (int off = 32; off > 0; off >>= 1) c = max(c, (unsigned)__shfl_xor((int)c, off));
+        else if (P.untrimmed) {             /* variant 16384: the butterfly this reduction was before wt_wave_reduce */
+            if (P.cost_sum) for (int off = 32; off > 0; off >>= 1) c += (unsigned)__shfl_xor((int)c, off);
+            else for (int off = 32; off > 0; off >>= 1) c = max(c, (unsigned)__shfl_xor((int)c, off));
+        }
+        else if (P.cost_sum) c = wt_wave_reduce<true>(c);      /* the wave's total work */
+        else c = wt_wave_reduce<false>(c);
 #if WT_TIMELINE     /* DIAGNOSTIC: when in the launch did this wave run? (tools/timeline.py) */
         if (P.diag && P.diag < 256u) c = ((unsigned)((tl_begin >> (P.diag - 1u)) & 0xFFFFull) << 16) | (unsigned)((__builtin_amdgcn_s_memrealtime() >> (P.diag - 1u)) & 0xFFFFull);
         tl_end = __builtin_amdgcn_s_memrealtime();

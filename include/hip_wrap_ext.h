@@ -160,6 +160,8 @@ void clw_ext_unit_scene(cl_wrap* wrap, cl_uint kernel_id, int op, const float* i
  * 128 no light / plane side table (every shadow ray tests every plane), 256 no visibility classes (every needed shadow ray is traced),
  * 4096 heavy tiles of deep launches are not split over several wavefronts,
  * 8192 small scenes of the shallow fast build run the generic trace kernel instead of the one with the scene's counts compiled in,
+ * 16384 the trace loop runs the Fresnel / reflection block on a path's last level too, where nothing reads its results, and the tile cost is
+ * reduced over the wave by the shuffle butterfly instead of DPP row operations (the kernel as it was before both were trimmed),
  * 2048 deep launches always carry the full-depth (31-parent) scratch stack instead of one sized for their depth,
  * 1024 (with clw_ext_enable_counters) VERIFICATION of the visibility classes: lights are classified AND traced, counter word 9 =
  * lights classified, word 28 = lights whose traced factors differ from their class's (must read 0),

@@ -1,5 +1,6 @@
 """When does each tile's wave run inside one launch?  (DIAGNOSTIC build -DWT_TIMELINE=1, variant bit 512.)
-   CLWRAP_LIB=.../libopencl_wrap_hip_tl.so python tools/timeline.py c2  -> busy wave slots per 5 % of the launch"""
+   CLWRAP_LIB=.../libopencl_wrap_hip_tl.so python tools/timeline.py c2 [--variant V]  -> busy wave slots per 5 % of the launch
+   (--variant: further variant bits for the stamped launch and the ones before it, e.g. 16384 = the untrimmed trace loop)"""
 import json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,6 +12,7 @@ cfg = sys.argv[1] if len(sys.argv) > 1 else "c2"
 shift = int(os.environ.get("CLWRAP_TIMELINE_SHIFT", "0"))      # ticks of 10 ns << shift (16 bits per stamp: 655 us at shift 0)
 tick_us = 0.01 * (1 << shift)
 strict = "--strict" in sys.argv
+variant = int(sys.argv[sys.argv.index("--variant") + 1]) if "--variant" in sys.argv else 0
 cam = pkg.CAMERA_RAYPNG
 if cfg == "c2":
     sc, W, H, depth = scene.render_map_scene(), 1920, 1080, 4
@@ -25,10 +27,11 @@ else:
 r = Renderer(sc, textures.texture_layers(), textures.skybox_cross(4096), W, H, depth=depth, strict=strict)
 r.look(**cam)
 if "--tpt" in sys.argv: r.w.set_tpt(int(sys.argv[sys.argv.index("--tpt") + 1]), -1, -1)
+r.w.set_variant(variant)
 for _ in range(6):
     r.render(readback=False)
 r.w.sync()
-r.w.set_variant(512)
+r.w.set_variant(512 | variant)
 r.w.timing_reset(); r.render(readback=False); r.w.sync(); n, ms = r.w.timing_get(1)
 c = r.w.read_tile_costs().astype(np.int64)
 if os.environ.get("CLWRAP_TIMELINE_EDGES") == "2":   # the prologue in three parts: staging | tile and pixel mapping | primary ray + loop set-up
