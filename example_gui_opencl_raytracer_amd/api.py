@@ -38,6 +38,7 @@ SYMBOLS = [
     "clw_ext_last_trace_flags", "clw_ext_set_shadow_through", "clw_ext_set_tpt", "clw_ext_invalidate_scene", "clw_ext_read_counters_ex", "clw_ext_unit_scene",
     "clw_host_perspective", "clw_host_write_png", "clw_host_write_png_rgba", "clw_host_read_png",
     "clw_host_free", "clw_ext_version",
+    "clw_ext_set_supersample", "clw_ext_get_supersample",
 ]
 
 
@@ -110,6 +111,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.clw_ext_device_ptr.argtypes = [W, u32, u32]
     L.clw_ext_device_ptr.restype = vp
     L.clw_ext_set_debug_rgb.argtypes = [W, vp]
+    if hasattr(L, "clw_ext_set_supersample") or not os.environ.get("CLWRAP_LIB"):      # (an older A/B build may lack it)
+        L.clw_ext_set_supersample.argtypes = [W, C.c_int]
+        L.clw_ext_get_supersample.argtypes = [W]
+        L.clw_ext_get_supersample.restype = C.c_int
     L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
     L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
     L.clw_ext_read_tile_costs.restype = u32
@@ -279,6 +284,8 @@ class ClWrap:
 
     def device_ptr(self, kernel_id, arg_id): return self.L.clw_ext_device_ptr(C.byref(self.w), kernel_id, arg_id)
     def set_debug_rgb(self, ptr): self.L.clw_ext_set_debug_rgb(C.byref(self.w), C.c_void_p(ptr))
+    def set_supersample(self, n): self.L.clw_ext_set_supersample(C.byref(self.w), int(n))
+    def get_supersample(self): return int(self.L.clw_ext_get_supersample(C.byref(self.w)))
     def enable_counters(self, on): self.L.clw_ext_enable_counters(C.byref(self.w), int(on))
 
     def read_counters(self):

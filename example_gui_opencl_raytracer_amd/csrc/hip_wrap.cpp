@@ -36,11 +36,11 @@ extern "C" hipError_t wt_fast_launch_unit(int, const float*, float*, unsigned, u
 extern "C" hipError_t wt_strict_launch_unit(int, const float*, float*, unsigned, unsigned, unsigned, unsigned, hipStream_t);
 extern "C" hipError_t wt_fast_launch_unit_scene(const whitted_params*, int, int, const float*, float*, unsigned, unsigned, unsigned, size_t, hipStream_t);
 extern "C" hipError_t wt_strict_launch_unit_scene(const whitted_params*, int, int, const float*, float*, unsigned, unsigned, unsigned, size_t, hipStream_t);
-extern "C" hipError_t wt_fast_launch_sched(const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
+extern "C" hipError_t wt_fast_launch_sched(const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
 
 namespace {
 
-enum { F_COUNT = 1, F_DEEP = 2, F_GEOM_LDS = 4, F_RAYS = 8, F_GRID = 16, F_OCC = 32, F_D8 = 64, F_D16 = 128, F_SHAPE = 256 }; /* = WT_F_* of whitted_trace.inc */
+enum { F_COUNT = 1, F_DEEP = 2, F_GEOM_LDS = 4, F_RAYS = 8, F_GRID = 16, F_OCC = 32, F_D8 = 64, F_D16 = 128, F_SHAPE = 256, F_SS = 1 << 17 }; /* = WT_F_* of whitted_trace.inc */
 /* shallow fast launches of small LDS-geometry scenes run a kernel with the scene's counts compiled in (wt_shape of whitted_trace.inc): the
  * counts whitted_launch.inc instantiates -- 1..SHAPE_MAX_SPHERES spheres, 0..SHAPE_MAX_PLANES planes, SHAPE_LIGHTS lights */
 constexpr uint32_t SHAPE_MAX_SPHERES = 4, SHAPE_MAX_PLANES = 2, SHAPE_LIGHTS = 3;
@@ -149,6 +149,7 @@ struct Impl {
     int stamps = 0;        /* CLWRAP_STAMPS=1: hand the counter block to the (diagnostic) stamp build of the kernel */
     uint64_t id_offset = 0;
     uint32_t band_stride = 1, band_phase = 0;
+    int supersample = 1;   /* n x n samples per pixel, resolved in the trace kernel (clw_ext_set_supersample / CLWRAP_SUPERSAMPLE): 1, 2, 4 or 8 */
     float* debug_rgb = nullptr;
     /* prepared scene cache */
     const Buffer *prep_s = nullptr, *prep_p = nullptr, *prep_l = nullptr;
@@ -174,7 +175,8 @@ struct Impl {
         bool have[2] = {false, false};                /* order[i] holds / will hold a schedule */
         int wr = 0;                                   /* cost buffer the next trace writes */
         hipEvent_t traced = nullptr;
-        uint32_t w = 0, rows = 0, cap = 0;           /* frame the buffers were sized for; dispatch entries per XCD share */
+        uint32_t w = 0, rows = 0, cap = 0;           /* frame the buffers were sized for (the virtual frame of a supersampled launch); dispatch entries per XCD share */
+        int ss = 1;                                   /* supersampling factor its orders were built for: it caps how far a tile is split */
         RaygenArgs sig{}; int sig_depth = 0; uint64_t sig_scene = 0; bool sig_valid = false; int sig_age = 0, newest = 0; uint64_t frame = 0, newest_frame = 0;   /* what the newest order was built for, frames since */
         void reset() { have[0] = have[1] = false; sig_valid = false; newest = 0; }
         void free_all() {
@@ -530,6 +532,7 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
     P.out_rgb = I->debug_rgb;
     P.diag = (I->variant & 512) ? (env_int("CLWRAP_TIMELINE_EDGES", 0) ? 255u + (uint32_t)env_int("CLWRAP_TIMELINE_EDGES", 0) : 1u + (uint32_t)env_int("CLWRAP_TIMELINE_SHIFT", 0)) : 0u;
 
+    const int ss = I->supersample;
     const bool fused = I->fuse && rays->gen_valid && !rays->exposed;   /* (a buffer whose pointer was handed out is read, not regenerated) */
     RaygenArgs g{};
     if (fused) {
@@ -548,10 +551,28 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
         if (P.n_items > g.n_items) P.n_items = g.n_items; /* rays past the generated range are undefined in the reference */
         if (P.n_items == 0) return;
         P.tiled = (g.id_offset % g.width == 0 || g.band_stride > 1) && (P.n_items % g.width == 0) && !(I->variant & 2);
+        if (ss > 1) {
+            /* the launch traces the virtual frame of ss x as many columns and rows that the same camera gives (for a power of two bit for bit
+             * what rgen_perspective returns for it) and stores one resolved pixel per ss x ss samples; ids -- the RNG seeds -- are the virtual
+             * frame's.  Everything the caller sized stays in output pixels: the range above, `out`, the ray buffer, the strips. */
+            if (g.band_stride > 1) die("Supersampling does not support interleaved row bands");
+            if (I->variant & 2) die("Supersampling does not support linear work-item ids (variant 2)");
+            if (!P.tiled) die("Supersampling needs a launch range of whole rows");
+            if ((uint64_t)g.width * g.height * (uint64_t)(ss * ss) >= (1ull << 32)) die("Supersampling: the %d x %d samples of this frame exceed 32-bit ids", ss, ss);
+            const uint32_t out_rows = P.n_items / g.width, row0 = (uint32_t)(g.id_offset / g.width);
+            g.w_factor /= (float)ss; g.h_factor /= (float)ss;
+            g.width *= (uint32_t)ss; g.height *= (uint32_t)ss;
+            g.id_offset = (uint64_t)row0 * (uint32_t)ss * g.width;
+            g.n_items = out_rows * (uint32_t)ss * g.width;
+            P.w_factor = g.w_factor; P.h_factor = g.h_factor; P.width = g.width; P.height = g.height;
+            P.id_offset = g.id_offset; P.n_items = g.n_items;
+            P.ss_lg = ss == 2 ? 1u : (ss == 4 ? 2u : 3u);
+        }
         P.rows = P.n_items / g.width;
         P.row_offset = (uint32_t)(g.id_offset / g.width);
         P.unit_dirs = P.ns <= GRID_MIN_SPHERES ? 1u : 0u;      /* primary rays are generated (and normalised) in the kernel */
     } else {
+        if (ss > 1) die("Supersampling needs the fused raygen + trace launch (CLWRAP_FUSE=1, rays generated by this library and not rewritten)");
         materialise_rays(I, rays);
         ensure_allocated(I, rays);
         if ((uint64_t)P.n_items * 64 > rays->size) die("Couldn't run the kernel");
@@ -601,12 +622,14 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
     const uint64_t tpt_cap = std::min<uint64_t>(tpt_slice > tpt_fixed ? ((tpt_slice - tpt_fixed) / tpt_per_node) & ~(uint64_t)63 : 0, 64960u);   /* whole blocks of 64 nodes; node ids are 16 bits */
     const bool tail_wanted = (flags & F_DEEP) && !(flags & F_OCC) && !(I->variant & 16) && I->tpt_max != 0u && tpt_cap >= TPT_MIN_CAP;
     bool split = false;
+    const unsigned split_max_lg = ss == 1 ? 4u : (ss == 2 ? 2u : (ss == 4 ? 1u : 0u));
     if (P.tiled) {
         if (I->sched && !(I->variant & 4) && trows <= 0xFFFu && tpr <= 0xFFFu) {   /* the order packs (tile column | row << 12 | parts) */
-            split = tail_wanted && !(flags & F_GRID) && I->split_min_quota != 0u && !(I->variant & 4096);
+            /* a part of a split tile owns 8 >> lg whole tile rows; a supersampled launch needs ss of them in one wavefront (ss = 8: no split) */
+            split = tail_wanted && !(flags & F_GRID) && I->split_min_quota != 0u && !(I->variant & 4096) && split_max_lg != 0u;
             if (split) { per_share_cap = per_share + SPLIT_EXTRA_PER_SHARE; grid = 8 * per_share_cap; }
             P.cost_sum = (tail_wanted && !(flags & F_GRID)) ? 1u : 0u;
-            if (S.w != P.width || S.rows != P.rows || S.cap != per_share_cap || !S.cost[0]) {
+            if (S.w != P.width || S.rows != P.rows || S.cap != per_share_cap || S.ss != ss || !S.cost[0]) {
                 S.free_all();
                 for (int i = 0; i < 2; i++) {
                     HIP_OK(hipMalloc((void**)&S.cost[i], (size_t)trows * tpr * 4), "Couldn't allocate device memory");
@@ -614,7 +637,7 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
                     HIP_OK(hipEventCreateWithFlags(&S.built[i], hipEventDisableTiming), "Couldn't create a timing event");
                 }
                 HIP_OK(hipEventCreateWithFlags(&S.traced, hipEventDisableTiming), "Couldn't create a timing event");
-                S.w = P.width; S.rows = P.rows; S.cap = per_share_cap; S.wr = 0;
+                S.w = P.width; S.rows = P.rows; S.cap = per_share_cap; S.ss = ss; S.wr = 0;
             }
             const int wr = S.wr;
             P.tile_cost = S.cost[wr];
@@ -645,6 +668,7 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
     if (!I->strict && flags == F_GEOM_LDS && P.ns >= 1u && P.ns <= SHAPE_MAX_SPHERES && P.np <= SHAPE_MAX_PLANES && P.nl == SHAPE_LIGHTS &&
         (P.np == 0u || P.lpt) && !(I->variant & 8192))
         flags |= F_SHAPE | (int)(P.ns << 9 | P.np << 12 | P.nl << 14);
+    if (P.ss_lg) flags |= F_SS;      /* every fused flavour has a supersampled twin, whose epilogue resolves the samples */
     I->last_trace_flags = flags;
     if (tail_wanted) {
         const uint64_t nslots = tpt_nslots, slice = tpt_slice, cap = tpt_cap;
@@ -683,7 +707,7 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
             HIP_OK(hipEventRecord(S.traced, I->stream), "Couldn't run the kernel");
             HIP_OK(hipStreamWaitEvent(I->sched_stream, S.traced, 0), "Couldn't run the kernel");
             if (wt_fast_launch_sched(S.cost[wr], S.order[wr], tpr, trows, per_share, (flags & F_GRID) ? 1u : 0u, per_share_cap,
-                                     split ? I->split_slots : 0u, I->split_min_quota, I->sched_stream) != hipSuccess)
+                                     split ? I->split_slots : 0u, I->split_min_quota, split_max_lg, I->sched_stream) != hipSuccess)
                 die("Couldn't run the kernel");
             HIP_OK(hipEventRecord(S.built[wr], I->sched_stream), "Couldn't run the kernel");
             S.have[wr] = true; S.newest = wr; S.newest_frame = S.frame - 1;
@@ -804,6 +828,8 @@ void cl_wrap_init(cl_wrap* wrap, cl_device_type type, ...) {
     I->timing_every = (uint32_t)env_int("CLWRAP_TIMING_EVERY", 1);
     if (I->timing_every == 0) I->timing_every = 1;
     I->pipeline = env_int("CLWRAP_PIPELINE", 1) ? 1 : 0;
+    I->supersample = env_int("CLWRAP_SUPERSAMPLE", 1);
+    if (I->supersample != 1 && I->supersample != 2 && I->supersample != 4 && I->supersample != 8) die("CLWRAP_SUPERSAMPLE (supersampling factor) must be 1, 2, 4 or 8");
     I->stamps = env_int("CLWRAP_STAMPS", 0) ? 1 : 0;
     if (const char* th = getenv("CLWRAP_THROUGH")) { if (*th) I->through = (float)atof(th); }
     I->occ_tiles_per_depth = (unsigned)env_int("CLWRAP_OCC_TILES_PER_DEPTH", (int)OCC_TILES_PER_DEPTH);
@@ -1035,6 +1061,11 @@ void clw_ext_set_tpt(cl_wrap* wrap, int max_lanes, int min_paths, int pool_mb) {
     if (pool_mb >= 0) I->tpt_pool_mb = (unsigned)pool_mb;
 }
 void clw_ext_set_debug_rgb(cl_wrap* wrap, void* p) { impl_of(wrap)->debug_rgb = (float*)p; }
+void clw_ext_set_supersample(cl_wrap* wrap, int n) {
+    if (n != 1 && n != 2 && n != 4 && n != 8) die("The supersampling factor must be 1, 2, 4 or 8");
+    impl_of(wrap)->supersample = n;
+}
+int clw_ext_get_supersample(const cl_wrap* wrap) { return impl_of(wrap)->supersample; }
 
 void clw_ext_set_pipeline(cl_wrap* wrap, int on) { impl_of(wrap)->pipeline = on ? 1 : 0; }
 void clw_ext_set_timing_every(cl_wrap* wrap, uint32_t n) { Impl* I = impl_of(wrap); I->timing_every = n ? n : 1; I->timing_tick = 0; I->timing_on = n != 0; }

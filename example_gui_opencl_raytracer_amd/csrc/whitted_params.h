@@ -87,6 +87,10 @@ typedef struct {
     uint32_t* out;         /* packed 0x00RRGGBB per work-item                         */
     float* out_rgb;        /* optional float radiance, 3 per work-item                */
     unsigned long long* counters; /* counting build only: CLW_NUM_COUNTERS words          */
+    /* n x n supersampling, n = 1 << ss_lg (tiled launches; 0 = off): the camera, width, rows, row_offset, id_offset, n_items and the tile
+     * buffers above describe the VIRTUAL frame of n x as many columns and rows; the n x n samples of an output pixel sit in adjacent lanes
+     * of one wavefront and are resolved in registers (wt_ss_resolve); out / out_rgb hold one entry per OUTPUT pixel, width >> ss_lg per row */
+    uint32_t ss_lg;
 } whitted_params;
 
 typedef struct {

@@ -652,7 +652,8 @@ enum { WT_F_COUNT = 1, WT_F_DEEP = 2, WT_F_GEOM_LDS = 4, WT_F_RAYS = 8, WT_F_GRI
        WT_F_OCC = 32 /* deep builds only: the high-occupancy flavour (see WT_LDS_LEVELS above) */,
        WT_F_D8 = 64, WT_F_D16 = 128 /* deep builds only: the launch's depth is <= 8 / <= 16, so the DFS stack holds at most 7 / 15 parents and the
                                        part of it kept in scratch is sized for that instead of for CLW_MAX_DEPTH */,
-       WT_F_SHAPE = 256 /* shallow fast LDS-geometry build only: the scene's counts are compiled in (wt_shape) */ };
+       WT_F_SHAPE = 256 /* shallow fast LDS-geometry build only: the scene's counts are compiled in (wt_shape) */,
+       WT_F_SS = 1 << 17 /* n x n supersampling, fused tiled launches only (bits 9-16: the counts of WT_SHAPE_FLAGS) */ };
 
 /* ---- the scene's primitive counts: launch parameters, or compile-time constants (FLAGS & WT_F_SHAPE) ----------------------------
  * A small scene's loops over 4 spheres, 2 planes and 3 lights are mostly loop control, guards and selects around little arithmetic.
@@ -1308,6 +1309,32 @@ __device__ __forceinline__ unsigned wt_wave_reduce(unsigned c) {
     return (unsigned)__builtin_amdgcn_readlane((int)c, 63);
 }
 
+/* Supersampling resolve (whitted_params.h: ss_lg): the sum of `v` over the n x n lane group of this lane, n = 1 << lg, with the lanes of a
+ * tile laid out x = lane & 7, y = lane >> 3 -- the butterfly xor 1, 2, 4 along x, then xor 8, 16, 32 along y, cut to lg steps per axis.
+ * Every step is one plain fp32 add of the lane's value and its partner's, and a + b == b + a bit for bit, so all lanes of a group end with the
+ * same bits (the order is part of the image's definition: x first, adjacent pairs).  All in registers: DPP inside a row of 16 lanes, the
+ * gfx950 half-row / half-wave swaps across rows.  Call with the WHOLE wave active: a DPP read of a disabled lane does not return its value.
+ *   xor 1, 2: quad_perm.  xor 4: row_half_mirror reads lane ^ 7, which sits in the quad of lane ^ 4 -- a quad is uniform after xor 1 and 2,
+ *   and xor 4 only runs after both (n = 8).  xor 8: row_ror:8.  xor 16 / 32: v_permlane16_swap / v_permlane32_swap of two copies of the value
+ *   leave (own, partner) in one order or the other depending on the lane's half; their sum is the same either way. */
+__device__ __forceinline__ float wt_ss_resolve(float v, const unsigned lg) {
+#define WT_SS_DPP(ctrl) v = v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xF, 0xF, false))
+    WT_SS_DPP(0xB1);                    /* quad_perm:[1,0,3,2] */
+    if (lg >= 2u) WT_SS_DPP(0x4E);      /* quad_perm:[2,3,0,1] */
+    if (lg >= 3u) WT_SS_DPP(0x141);     /* row_half_mirror */
+    WT_SS_DPP(0x128);                   /* row_ror:8 */
+#undef WT_SS_DPP
+    if (lg >= 2u) {
+        const auto p = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+        v = __uint_as_float(p[0]) + __uint_as_float(p[1]);
+    }
+    if (lg >= 3u) {
+        const auto p = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+        v = __uint_as_float(p[0]) + __uint_as_float(p[1]);
+    }
+    return v;
+}
+
 /* One tile (tiled launches) or one block of work-items: the whole trace of its pixels.  `wg` is the workgroup's number in
  * the launch's dispatch order (blockIdx.x). */
 typedef const __attribute__((address_space(4))) whitted_params* wt_kparams_t;
@@ -1318,6 +1345,7 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
     constexpr bool GEOM_LDS = (FLAGS & WT_F_GEOM_LDS) != 0;
     constexpr bool FROM_RAYS = (FLAGS & WT_F_RAYS) != 0;
     constexpr bool GRID = (FLAGS & WT_F_GRID) != 0;     /* spheres through the uniform grid (big scenes) */
+    constexpr bool SS = (FLAGS & WT_F_SS) != 0;         /* supersampled launch: the epilogue resolves n x n samples per stored pixel */
     constexpr bool UNIT_CT = !WT_STRICT && GEOM_LDS && !FROM_RAYS && !GRID;   /* see whitted_hit.inc */
     /* The lights' visibility classes (wt_light_vis) are compiled into the STRICT build's small-scene kernels only: there the samples they
      * save cost an fp64 product and a libm sin / cos each (-13 % at C2).  Measured for the fast build, whose samples are two hardware
@@ -1527,6 +1555,25 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
     }
 
 
+    /* ---- supersampled launches: the n x n clamped samples of an output pixel are averaged across their lanes, one lane packs and stores.
+     * n divides 8 and the virtual sizes are multiples of n, so a lane group is valid or invalid as a whole (a part of a split tile owns whole
+     * tile rows, at least n of them: the shim caps the split); the cross-lane steps run with every lane active, only the store is predicated.
+     * A flavour of its own (WT_F_SS), so that the 1-sample kernels are the code they were. */
+    if (SS) {
+        const unsigned lg = P.ss_lg, m = (1u << lg) - 1u;
+        const float inv = __uint_as_float((127u - 2u * lg) << 23);      /* 1 / n^2, exact */
+        const float mr = wt_ss_resolve(fminf(fmaxf(rgb.x, 0.0f), 1.0f), lg) * inv;
+        const float mg = wt_ss_resolve(fminf(fmaxf(rgb.y, 0.0f), 1.0f), lg) * inv;
+        const float mb = wt_ss_resolve(fminf(fmaxf(rgb.z, 0.0f), 1.0f), lg) * inv;
+        if (valid && (lane & (m | (m << 3))) == 0u) {
+            const size_t px = (size_t)(y >> lg) * (P.width >> lg) + (x >> lg);
+            if (P.out_rgb) {
+                float* q = P.out_rgb + 3 * px;
+                q[0] = mr; q[1] = mg; q[2] = mb;
+            }
+            P.out[px] = ((unsigned)(mr * 255.0f) << 16) | ((unsigned)(mg * 255.0f) << 8) | (unsigned)(mb * 255.0f);
+        }
+    } else
     /* ---- pack (raytracing.cl:193-194): clamp, *255, truncate ---------------------------- */
     if (valid) {
         if (P.out_rgb) {
@@ -1619,7 +1666,7 @@ __global__ void __launch_bounds__(WT_RG_BLOCK) wt_raygen(const raygen_params P) 
  *      quota doubles until the parts fit. ------------ */
 __global__ void __launch_bounds__(256) wt_sched_build(const unsigned* __restrict__ cost, unsigned* __restrict__ order,
                                                       unsigned tpr, unsigned trows, unsigned per_share, unsigned clamp_outliers,
-                                                      unsigned per_share_cap, unsigned split_slots, unsigned min_quota) {
+                                                      unsigned per_share_cap, unsigned split_slots, unsigned min_quota, unsigned max_lg) {
     __shared__ unsigned hist[256];
     __shared__ unsigned base[256];
     __shared__ unsigned s_max, s_cnt, s_entries;
@@ -1636,7 +1683,8 @@ __global__ void __launch_bounds__(256) wt_sched_build(const unsigned* __restrict
     }
     atomicAdd(&s_sum, sum); atomicAdd(&s_cnt, cnt);
     __syncthreads();
-    /* parts per tile: the smallest power of two that brings cost / parts under the quota, at most 16 */
+    /* parts per tile: the smallest power of two that brings cost / parts under the quota, at most 2^max_lg (16; fewer in supersampled launches,
+     * where a part must hold whole n x n sample groups: 8 >> lg tile rows >= n) */
     unsigned quota = 0xFFFFFFFFu;
     if (split_slots != 0u) {
         const unsigned long long q = s_sum / split_slots;
@@ -1649,7 +1697,7 @@ __global__ void __launch_bounds__(256) wt_sched_build(const unsigned* __restrict
             unsigned e = 0u;
             for (unsigned j = tid; j < per_share; j += 256) {
                 const unsigned trow = (j / tpr) * 8u + k;
-                if (trow < trows) { unsigned lg = 0u; const unsigned c = cost[trow * tpr + (j % tpr)]; while (lg < 4u && (c >> lg) > quota) lg++; e += 1u << lg; }
+                if (trow < trows) { unsigned lg = 0u; const unsigned c = cost[trow * tpr + (j % tpr)]; while (lg < max_lg && (c >> lg) > quota) lg++; e += 1u << lg; }
             }
             atomicAdd(&s_entries, e);
             __syncthreads();
@@ -1659,7 +1707,7 @@ __global__ void __launch_bounds__(256) wt_sched_build(const unsigned* __restrict
             quota = quota > 0x3FFFFFFFu ? 0xFFFFFFFFu : quota * 2u;      /* (ends at "never split": cnt <= per_share <= per_share_cap) */
         }
     }
-    auto parts_lg = [&](unsigned c) { unsigned lg = 0u; while (lg < 4u && (c >> lg) > quota) lg++; return lg; };
+    auto parts_lg = [&](unsigned c) { unsigned lg = 0u; while (lg < max_lg && (c >> lg) > quota) lg++; return lg; };
     /* costs are iteration counts, total work or wave durations (any range): 256 bins scaled by the share's maximum.  Durations have
      * outliers (a wave of a cold first frame can live a hundred times longer than the rest, which would squeeze every other
      * tile into bin 0 = no order at all): with `clamp_outliers` the scale stops at 16x the share's mean. */

@@ -8,6 +8,9 @@ collective.  The one exchange is a single gather of the finished rows (packed to
 storing its share straight into rank 0's frame buffer (peer-mapped through a HIP IPC handle, one device-to-device copy
 per rank and frame, a one-word all-reduce as the completion signal).  Work-item ids stay GLOBAL (renderer.Renderer /
 clw_ext_set_id_offset / clw_ext_set_row_bands) so the assembled image is bit-identical to a single-GPU render.
+Supersampled renderers (`Renderer(..., supersample=n)`) compose the same way in the "strips" layout: a strip of output rows is n x as many rows
+of the sampled frame and the sample ids stay global (tests/test_gpu_supersample.py); the gather moves W x H pixels as before.  Interleaved
+bands are not supersampled (the shim refuses them).
 """
 from __future__ import annotations
 

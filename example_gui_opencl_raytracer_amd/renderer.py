@@ -9,6 +9,10 @@ by value and 8 = ray buffer; kernel 1 ("raytracer") argument 0 = the 8-byte hand
 Row strips (multi-GPU): a renderer may own rows ``[first_row, first_row + rows)`` of the
 frame; work-item ids, and with them ``id % W``, ``id / W`` and the RNG seed, stay global
 (SURVEY.md 8(e)), so a strip is bit-identical to the same rows of a full-frame render.
+
+``supersample=n`` (2, 4, 8): every pixel is the mean of n x n samples traced and resolved inside the
+kernel (include/hip_wrap_ext.h, clw_ext_set_supersample); ``render()`` and ``render_rgb()`` still
+return W*H entries, and strips compose as before.
 """
 from __future__ import annotations
 
@@ -35,7 +39,7 @@ class Renderer:
     def __init__(self, scene: Scene, tex: np.ndarray, sky: np.ndarray, width: int, height: int, *,
                  depth: int = 15, strict: bool = False, fuse: bool = True, first_row: int = 0,
                  rows: int | None = None, bands: tuple[int, int] | None = None, framebuffer_ptr: int | None = None, wide_counts: bool | None = None,
-                 texture_paths=None, skybox_path=None):
+                 texture_paths=None, skybox_path=None, supersample: int = 1):
         self.width, self.height = width, height
         self.first_row = first_row
         self.rows = height - first_row if rows is None else rows
@@ -49,6 +53,8 @@ class Renderer:
         w.set_strict(strict)
         w.set_fuse(fuse)
         w.set_id_offset(first_row * width)
+        if supersample != 1:      # n x n samples per pixel, resolved in the trace kernel: sizes, rows and strips here stay in output pixels
+            w.set_supersample(supersample)
         if bands is not None:
             w.set_row_bands(*bands)
 

@@ -12,6 +12,7 @@
  *
  * Environment variables read once by cl_wrap_init (same meaning as the setters):
  *   CLWRAP_DEPTH=<1..32>   CLWRAP_STRICT=<0|1>   CLWRAP_FUSE=<0|1>   CLWRAP_DEVICE=<ordinal>   CLWRAP_PIPELINE=<0|1>   CLWRAP_THROUGH=<float>
+ *   CLWRAP_SUPERSAMPLE=<1|2|4|8>
  * Tuning / experiment knobs (defaults are the measured optima): CLWRAP_GRID_MIN, CLWRAP_GRID_DENSITY (uniform grid),
  *   CLWRAP_OCC_TILES_PER_DEPTH (deep launches of >= this x depth tiles take the high-occupancy kernel flavour),
  *   CLWRAP_TIMING_EVERY, CLWRAP_VARIANT (bit mask of clw_ext_set_variant).
@@ -99,6 +100,21 @@ void* clw_ext_device_ptr(cl_wrap* wrap, cl_uint kernel_id, cl_uint arg_id);
 /* Optional float radiance output of the trace kernel: 3 floats per work-item, written
  * before the 8-bit pack (reference raytracing.cl:193).  NULL disables. */
 void clw_ext_set_debug_rgb(cl_wrap* wrap, void* device_ptr_f32x3);
+
+/* n x n supersampling (anti-aliasing) inside the trace kernel; n = 1 (default), 2, 4 or 8; env CLWRAP_SUPERSAMPLE.
+ * With n > 1 a fused trace launch of W x H pixels (or a strip of whole rows of it) traces the n*W x n*H frame the same
+ * camera gives -- same im_corner, origin, up and right, w_factor / n, h_factor / n, work-item ids (the RNG seeds) of
+ * that frame: bit for bit the samples of a 1-sample render of n*W x n*H -- and writes W x H pixels.  Each sample is
+ * clamped to [0, 1] like raytracing.cl:193; the n x n samples of a pixel are added in float32, adjacent pairs along x
+ * (log2 n rounds), then adjacent pairs along y, times 1 / n^2, and the mean is packed as usual; the float debug output,
+ * when bound, receives the mean (3 floats per OUTPUT pixel).  The samples of a pixel are traced by neighbouring lanes of
+ * one wavefront and added in registers: the large frame never exists in memory.  Everything the caller sizes --
+ * framebuffer, `pixels` argument, ray buffer (which keeps its one-ray-per-pixel W x H meaning when read back), id
+ * offset, row strips -- stays in output pixels.  Work counters and clw_ext_read_tile_costs describe the n*W x n*H frame.
+ * Refused with an error and exit(1): launches that are not fused (CLWRAP_FUSE=0, caller-written rays), ranges that
+ * are not whole rows, interleaved row bands, linear ids (variant 2), n * n * W * H >= 2^32. */
+void clw_ext_set_supersample(cl_wrap* wrap, int n);
+int clw_ext_get_supersample(const cl_wrap* wrap);
 
 /* Work counters of the trace kernel.  enable=1 selects the counting build of the kernel
  * for subsequent launches (slower); read returns and clears

@@ -1,6 +1,9 @@
 """Time one BASELINE.json configuration through the C-ABI (kernel-only, frames back to back) and print JSON.
-   python tools/run_config.py c2|c3|c4|c5strip [--strict 1] [--frames N] [--variant V] [--depth D]"""
-import argparse, json, os, sys, time
+   python tools/run_config.py c2|c3|c4|c5strip|ref800 [--strict 1] [--frames N] [--variant V] [--depth D] [--size WxH] [--supersample N]
+   --supersample N: n x n samples per pixel resolved in the kernel (the frame stays WxH); --size: another frame size for the configuration's
+   scene and camera -- e.g. the n*W x n*H frame a supersampled launch traces, to time the same work without the resolve.
+   --repeats R: the N-frame loop R times (0 = until 50 ms have been timed, as bench.py --full does), median / min / max of the repeats."""
+import argparse, json, math, os, statistics, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -15,6 +18,9 @@ ap.add_argument("--frames", type=int, default=20)
 ap.add_argument("--variant", type=int, default=0)
 ap.add_argument("--depth", type=int, default=None)
 ap.add_argument("--png", default=None)
+ap.add_argument("--size", default=None)
+ap.add_argument("--supersample", type=int, default=1)
+ap.add_argument("--repeats", type=int, default=1)
 a = ap.parse_args()
 tex, sky = textures.texture_layers(), textures.skybox_cross(4096)
 cam = pkg.CAMERA_RAYPNG
@@ -35,23 +41,35 @@ elif a.config == "ref800":  # the reference driver's own configuration: 800x600,
 else:
     raise SystemExit("unknown config")
 depth = a.depth or depth
+if a.size:
+    W, H = (int(v) for v in a.size.lower().split("x"))
+if a.supersample != 1:
+    kw["supersample"] = a.supersample
 r = Renderer(sc, tex, sky, W, H, depth=depth, strict=bool(a.strict), **kw)
 r.w.set_variant(a.variant)
 r.look(**cam)
 r.render(readback=False); r.render(readback=False)
 r.w.enable_counters(1); r.render(readback=False); c = r.w.read_counters(); r.w.enable_counters(0)
-r.w.timing_reset(); r.w.set_async(1)
-t = time.perf_counter()
-for _ in range(a.frames):
-    r.render(readback=False)
-r.w.sync()
-wall = (time.perf_counter() - t) / a.frames
-n, ms = r.w.timing_get(1)
+r.w.set_async(1)
+kms, walls, reps = [], [], a.repeats
+while len(kms) < max(reps, 1):
+    r.w.timing_reset()
+    t = time.perf_counter()
+    for _ in range(a.frames):
+        r.render(readback=False)
+    r.w.sync()
+    walls.append((time.perf_counter() - t) / a.frames)
+    n, ms = r.w.timing_get(1)
+    kms.append(ms / n)
+    if reps == 0:
+        reps = min(200, max(1, math.ceil(0.05 / max(walls[0] * a.frames, 1e-6))))
+wall, ms, n = statistics.median(walls), statistics.median(kms), 1
 r.w.set_async(0)
 img = r.render()
 rays = c["segments"] + c["shadow_rays"]
 px = r.pixels
-print(json.dumps(dict(config=a.config, frame=f"{W}x{H}", pixels=px, depth=depth, strict=a.strict, variant=a.variant, kernel_ms=round(ms / n, 4),
+print(json.dumps(dict(config=a.config, frame=f"{W}x{H}", pixels=px, depth=depth, strict=a.strict, variant=a.variant, supersample=a.supersample, kernel_ms=round(ms / n, 4),
+                      kernel_ms_min=round(min(kms), 4), kernel_ms_max=round(max(kms), 4), repeats=len(kms),
                       wall_ms_per_frame=round(wall * 1e3, 4), rays_per_px=round(rays / px, 3), Mrays_s=round(rays / (ms / n) / 1e3, 1),
                       lane_util=round(c["lane_iters"] / max(c["wave_iters_x64"], 1), 4), counters=c)), flush=True)
 if a.png:
