@@ -39,6 +39,7 @@ SYMBOLS = [
     "clw_host_perspective", "clw_host_write_png", "clw_host_write_png_rgba", "clw_host_read_png",
     "clw_host_free", "clw_ext_version",
     "clw_ext_set_supersample", "clw_ext_get_supersample",
+    "clw_ext_set_sample_cameras", "clw_ext_get_sample_cameras", "clw_ext_set_lens", "clw_host_lens_cameras", "clw_host_shutter_cameras",
 ]
 
 
@@ -66,6 +67,11 @@ class clw_camera(C.Structure):
     _fields_ = [("im_corner", C.c_float * 3), ("origin", C.c_float * 3), ("up", C.c_float * 3),
                 ("right", C.c_float * 3), ("w_factor", C.c_float), ("h_factor", C.c_float),
                 ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class clw_sample_camera(C.Structure):
+    """One entry of a table of sample cameras (48 bytes): row k of the float32 [n*n, 12] arrays below."""
+    _fields_ = [("im_corner", C.c_float * 3), ("origin", C.c_float * 3), ("up", C.c_float * 3), ("right", C.c_float * 3)]
 
 
 _lib = None
@@ -115,6 +121,15 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         L.clw_ext_set_supersample.argtypes = [W, C.c_int]
         L.clw_ext_get_supersample.argtypes = [W]
         L.clw_ext_get_supersample.restype = C.c_int
+    if hasattr(L, "clw_ext_set_sample_cameras") or not os.environ.get("CLWRAP_LIB"):      # (an older A/B build may lack them)
+        L.clw_ext_set_sample_cameras.argtypes = [W, vp, u32]
+        L.clw_ext_get_sample_cameras.argtypes = [W, vp, u32]
+        L.clw_ext_get_sample_cameras.restype = u32
+        L.clw_ext_set_lens.argtypes = [W, C.c_float, C.c_float]
+        L.clw_host_lens_cameras.argtypes = [C.POINTER(clw_camera), C.c_float, C.c_float, u32, vp]
+        L.clw_host_lens_cameras.restype = C.c_int
+        L.clw_host_shutter_cameras.argtypes = [C.POINTER(clw_camera), C.POINTER(clw_camera), u32, vp]
+        L.clw_host_shutter_cameras.restype = C.c_int
     L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
     L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
     L.clw_ext_read_tile_costs.restype = u32
@@ -154,6 +169,22 @@ def perspective(origin, look, fov, focal, width, height) -> clw_camera:
     if not ok:
         raise ValueError("rgen_perspective rejects this camera (cpu_ray.c:58-63)")
     return cam
+
+
+def lens_cameras(cam: clw_camera, aperture: float, focus: float, n: int) -> np.ndarray:
+    """clw_host_lens_cameras: the thin-lens table of `cam` -> float32 [n*n, 12], rows {im_corner, origin, up, right} in sy * n + sx order."""
+    out = np.zeros((max(int(n), 0) ** 2 or 1, 12), np.float32)
+    if not load_library().clw_host_lens_cameras(C.byref(cam), aperture, focus, n, _ptr(out)):
+        raise ValueError("clw_host_lens_cameras rejects these arguments (n in 2, 4, 8; aperture >= 0; focus > 0)")
+    return out
+
+
+def shutter_cameras(cam0: clw_camera, cam1: clw_camera, n: int) -> np.ndarray:
+    """clw_host_shutter_cameras: the n*n cameras of a shutter open from `cam0` to `cam1` -> float32 [n*n, 12]."""
+    out = np.zeros((max(int(n), 0) ** 2 or 1, 12), np.float32)
+    if not load_library().clw_host_shutter_cameras(C.byref(cam0), C.byref(cam1), n, _ptr(out)):
+        raise ValueError("clw_host_shutter_cameras rejects these arguments (n in 2, 4, 8; cameras of one size and one pair of factors)")
+    return out
 
 
 def write_png(path: str, xrgb: np.ndarray, width: int, height: int) -> None:
@@ -286,6 +317,26 @@ class ClWrap:
     def set_debug_rgb(self, ptr): self.L.clw_ext_set_debug_rgb(C.byref(self.w), C.c_void_p(ptr))
     def set_supersample(self, n): self.L.clw_ext_set_supersample(C.byref(self.w), int(n))
     def get_supersample(self): return int(self.L.clw_ext_get_supersample(C.byref(self.w)))
+
+    def set_sample_cameras(self, cams):
+        """float32 [n*n, 12] ({im_corner, origin, up, right} per sample, sy * n + sx order), copied; None / empty = no table."""
+        if cams is None or len(cams) == 0:
+            self.L.clw_ext_set_sample_cameras(C.byref(self.w), None, 0)
+            return
+        cams = np.ascontiguousarray(cams, np.float32)
+        assert cams.ndim == 2 and cams.shape[1] == 12
+        self.L.clw_ext_set_sample_cameras(C.byref(self.w), _ptr(cams), cams.shape[0])
+
+    def get_sample_cameras(self) -> np.ndarray:
+        """The table the last trace launch used -> float32 [count, 12] (count 0 = none)."""
+        n = self.L.clw_ext_get_sample_cameras(C.byref(self.w), None, 0)
+        out = np.zeros((n, 12), np.float32)
+        if n:
+            self.L.clw_ext_get_sample_cameras(C.byref(self.w), _ptr(out), n)
+        return out
+
+    def set_lens(self, aperture, focus): self.L.clw_ext_set_lens(C.byref(self.w), float(aperture), float(focus))
+
     def enable_counters(self, on): self.L.clw_ext_enable_counters(C.byref(self.w), int(on))
 
     def read_counters(self):

@@ -36,6 +36,7 @@ extern "C" hipError_t wt_fast_launch_unit(int, const float*, float*, unsigned, u
 extern "C" hipError_t wt_strict_launch_unit(int, const float*, float*, unsigned, unsigned, unsigned, unsigned, hipStream_t);
 extern "C" hipError_t wt_fast_launch_unit_scene(const whitted_params*, int, int, const float*, float*, unsigned, unsigned, unsigned, size_t, hipStream_t);
 extern "C" hipError_t wt_strict_launch_unit_scene(const whitted_params*, int, int, const float*, float*, unsigned, unsigned, unsigned, size_t, hipStream_t);
+extern "C" hipError_t wt_fast_launch_cams(const wt_cam_table*, float*, hipStream_t);
 extern "C" hipError_t wt_fast_launch_sched(const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
 
 namespace {
@@ -151,6 +152,17 @@ struct Impl {
     uint32_t band_stride = 1, band_phase = 0;
     int supersample = 1;   /* n x n samples per pixel, resolved in the trace kernel (clw_ext_set_supersample / CLWRAP_SUPERSAMPLE): 1, 2, 4 or 8 */
     float* debug_rgb = nullptr;
+    /* per-sample cameras of supersampled launches (clw_ext_set_sample_cameras / clw_ext_set_lens: alternatives, the later call clears the
+     * other).  The device copy is laid out per lane of a tile's wavefront (whitted_params.h: ss_cams) and is rewritten, only when it changed,
+     * by a small kernel on the launch stream that carries the table as its argument: stream order keeps it behind every queued launch that
+     * reads the previous table, and no host memory has to outlive the call.  A change of stream (clw_ext_set_stream) records cams_fence on
+     * the old stream, which the next launch with a table waits for on the new one. */
+    std::vector<clw_sample_camera> cams;         /* the explicit table, sy * n + sx order; empty = none */
+    float aperture = 0.0f, focus = 1.0f;         /* thin lens: the table is derived at every launch from the latched camera; aperture 0 = pinhole */
+    std::vector<clw_sample_camera> cams_used;    /* the table of the latest trace launch (clw_ext_get_sample_cameras) */
+    float* d_cams = nullptr;
+    wt_cam_table cams_dev{}; bool cams_dev_valid = false;   /* what d_cams holds once the stream gets there */
+    hipEvent_t cams_fence = nullptr; bool cams_fence_pending = false, cams_in_flight = false;
     /* prepared scene cache */
     const Buffer *prep_s = nullptr, *prep_p = nullptr, *prep_l = nullptr;
     uint32_t prep_ns = 0, prep_np = 0, prep_nl = 0;
@@ -177,6 +189,7 @@ struct Impl {
         hipEvent_t traced = nullptr;
         uint32_t w = 0, rows = 0, cap = 0;           /* frame the buffers were sized for (the virtual frame of a supersampled launch); dispatch entries per XCD share */
         int ss = 1;                                   /* supersampling factor its orders were built for: it caps how far a tile is split */
+        wt_cam_table sig_cams{}; bool sig_has_cams = false;   /* the sample cameras belong to the signature below */
         RaygenArgs sig{}; int sig_depth = 0; uint64_t sig_scene = 0; bool sig_valid = false; int sig_age = 0, newest = 0; uint64_t frame = 0, newest_frame = 0;   /* what the newest order was built for, frames since */
         void reset() { have[0] = have[1] = false; sig_valid = false; newest = 0; }
         void free_all() {
@@ -372,6 +385,14 @@ int env_int(const char* name, int dflt) {
     const char* s = getenv(name);
     return (s && *s) ? atoi(s) : dflt;
 }
+/* a float from the environment; anything that is not a number reads as NaN, which every caller refuses */
+float env_float(const char* name, float dflt) {
+    const char* s = getenv(name);
+    if (!s || !*s) return dflt;
+    char* end = nullptr;
+    const float v = strtof(s, &end);
+    return (end == s || *end) ? NAN : v;
+}
 
 /* xorshift32 (primitives.cl:116-125) is linear over GF(2): a step is a 32x32 bit matrix T (column b = the step applied to 1 << b), the 4 nl numbers
  * a shaded hit draws are M = T^(4 nl), and the state k hits on is M^k times the state now.  out[i] = M^(2^i), i = 0..6, as columns: the tail's xorshift
@@ -533,6 +554,13 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
     P.diag = (I->variant & 512) ? (env_int("CLWRAP_TIMELINE_EDGES", 0) ? 255u + (uint32_t)env_int("CLWRAP_TIMELINE_EDGES", 0) : 1u + (uint32_t)env_int("CLWRAP_TIMELINE_SHIFT", 0)) : 0u;
 
     const int ss = I->supersample;
+    if (I->aperture > 0.0f && ss == 1) die("A lens needs samples: aperture %g with supersampling factor 1 (clw_ext_set_supersample / CLWRAP_SUPERSAMPLE)", (double)I->aperture);
+    if (!I->cams.empty() && (ss == 1 || I->cams.size() != (size_t)(ss * ss)))
+        die("Sample cameras: the table holds %u cameras, but supersampling factor %d %s", (unsigned)I->cams.size(), ss,
+            ss == 1 ? "takes none (set a factor of 2, 4 or 8)" : (ss == 2 ? "needs 4" : (ss == 4 ? "needs 16" : "needs 64")));
+    bool have_cams = false;
+    wt_cam_table cam_table;
+    I->cams_used.clear();
     const bool fused = I->fuse && rays->gen_valid && !rays->exposed;   /* (a buffer whose pointer was handed out is read, not regenerated) */
     RaygenArgs g{};
     if (fused) {
@@ -567,6 +595,27 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
             P.w_factor = g.w_factor; P.h_factor = g.h_factor; P.width = g.width; P.height = g.height;
             P.id_offset = g.id_offset; P.n_items = g.n_items;
             P.ss_lg = ss == 2 ? 1u : (ss == 4 ? 2u : 3u);
+            if (I->aperture > 0.0f) {   /* the lens table of the camera the raygen launch latched (the W x H one) */
+                clw_camera base;
+                memcpy(base.im_corner, rays->gen.corner, 12); memcpy(base.origin, rays->gen.origin, 12);
+                memcpy(base.up, rays->gen.up, 12); memcpy(base.right, rays->gen.right, 12);
+                base.w_factor = rays->gen.w_factor; base.h_factor = rays->gen.h_factor; base.width = rays->gen.width; base.height = rays->gen.height;
+                I->cams_used.resize((size_t)(ss * ss));
+                if (!clw_host_lens_cameras(&base, I->aperture, I->focus, (uint32_t)ss, I->cams_used.data())) die("A lens cannot be derived from this camera (its image plane passes through its origin)");
+            } else I->cams_used = I->cams;
+            if (!I->cams_used.empty()) {
+                have_cams = true;
+                for (unsigned lane = 0; lane < 64; lane++)   /* a tile's lane (lane & 7, lane >> 3) traces sub-sample (sx, sy) = both mod n */
+                    memcpy(cam_table.v + 12 * lane, &I->cams_used[(size_t)((lane >> 3) & (unsigned)(ss - 1)) * ss + ((lane & 7u) & (unsigned)(ss - 1))], 48);
+                if (!I->d_cams) HIP_OK(hipMalloc((void**)&I->d_cams, sizeof(wt_cam_table)), "Couldn't allocate device memory");
+                if (I->cams_fence_pending) { HIP_OK(hipStreamWaitEvent(I->stream, I->cams_fence, 0), "Couldn't run the kernel"); I->cams_fence_pending = false; }
+                if (!I->cams_dev_valid || memcmp(&cam_table, &I->cams_dev, sizeof cam_table)) {
+                    if (wt_fast_launch_cams(&cam_table, I->d_cams, I->stream) != hipSuccess) die("Couldn't run the kernel");
+                    I->cams_dev = cam_table; I->cams_dev_valid = true;
+                }
+                I->cams_in_flight = true;
+                P.ss_cams = I->d_cams;
+            }
         }
         P.rows = P.n_items / g.width;
         P.row_offset = (uint32_t)(g.id_offset / g.width);
@@ -651,10 +700,11 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
             if (rd >= 0 && rd != wr) HIP_OK(hipStreamWaitEvent(I->stream, S.built[rd], 0), "Couldn't run the kernel");
             P.tile_order = rd >= 0 ? S.order[rd] : nullptr;
             /* the costs can only change when the camera, the depth or the scene did */
-            sched_rebuild = !S.sig_valid || !same_raygen(g, S.sig) || S.sig_depth != I->depth || S.sig_scene != I->scene_generation;
+            sched_rebuild = !S.sig_valid || !same_raygen(g, S.sig) || S.sig_depth != I->depth || S.sig_scene != I->scene_generation ||
+                            S.sig_has_cams != have_cams || (have_cams && memcmp(&S.sig_cams, &cam_table, sizeof cam_table));
             /* (costs that add up: the buffer starts at zero; the build that read it two frames ago has been waited for above) */
             if (P.cost_sum) HIP_OK(hipMemsetAsync(S.cost[wr], 0, (size_t)trows * tpr * 4, I->stream), "Couldn't run the kernel");
-            if (sched_rebuild) { S.sig = g; S.sig_depth = I->depth; S.sig_scene = I->scene_generation; S.sig_valid = true; S.sig_age = 0; }
+            if (sched_rebuild) { S.sig_has_cams = have_cams; if (have_cams) S.sig_cams = cam_table; S.sig = g; S.sig_depth = I->depth; S.sig_scene = I->scene_generation; S.sig_valid = true; S.sig_age = 0; }
             /* Grid builds measure a tile by its wave's lifetime, which depends on the company it ran in: the order built
              * from the first (unsorted, often cold) frame is refined once from the first sorted one. */
             else if ((flags & F_GRID) && S.sig_age < 2) sched_rebuild = true;
@@ -830,6 +880,10 @@ void cl_wrap_init(cl_wrap* wrap, cl_device_type type, ...) {
     I->pipeline = env_int("CLWRAP_PIPELINE", 1) ? 1 : 0;
     I->supersample = env_int("CLWRAP_SUPERSAMPLE", 1);
     if (I->supersample != 1 && I->supersample != 2 && I->supersample != 4 && I->supersample != 8) die("CLWRAP_SUPERSAMPLE (supersampling factor) must be 1, 2, 4 or 8");
+    I->aperture = env_float("CLWRAP_APERTURE", 0.0f);
+    I->focus = env_float("CLWRAP_FOCUS", 1.0f);
+    if (!(I->aperture >= 0.0f) || !std::isfinite(I->aperture)) die("CLWRAP_APERTURE (lens aperture) must be a finite number >= 0");
+    if (!(I->focus > 0.0f) || !std::isfinite(I->focus)) die("CLWRAP_FOCUS (lens focus distance) must be a finite number > 0");
     I->stamps = env_int("CLWRAP_STAMPS", 0) ? 1 : 0;
     if (const char* th = getenv("CLWRAP_THROUGH")) { if (*th) I->through = (float)atof(th); }
     I->occ_tiles_per_depth = (unsigned)env_int("CLWRAP_OCC_TILES_PER_DEPTH", (int)OCC_TILES_PER_DEPTH);
@@ -962,6 +1016,8 @@ void cl_wrap_release(cl_wrap* wrap) {
     if (I->d_tpt_pool) (void)hipFree(I->d_tpt_pool);
     if (I->d_tpt_flags) (void)hipFree(I->d_tpt_flags);
     if (I->d_tpt_jump) (void)hipFree(I->d_tpt_jump);
+    if (I->d_cams) (void)hipFree(I->d_cams);
+    if (I->cams_fence) (void)hipEventDestroy(I->cams_fence);
     for (uint32_t* q : {I->d_grid_start, I->d_grid_items, I->d_grid_box}) if (q) (void)hipFree(q);
     if (I->d_grid_geom) (void)hipFree(I->d_grid_geom);
     if (I->sched_stream) (void)hipStreamSynchronize(I->sched_stream);
@@ -994,7 +1050,14 @@ void clw_ext_set_async(cl_wrap* wrap, int async) { impl_of(wrap)->async = async 
 void clw_ext_sync(cl_wrap* wrap) { Impl* I = impl_of(wrap); use_device(I); finish(I); }
 void clw_ext_set_stream(cl_wrap* wrap, void* hip_stream) {
     Impl* I = impl_of(wrap);
-    I->stream = hip_stream ? (hipStream_t)hip_stream : I->own_stream;
+    hipStream_t next = hip_stream ? (hipStream_t)hip_stream : I->own_stream;
+    if (next != I->stream && I->cams_in_flight) {   /* the sample-camera table was written / is read in the old stream's order: fence it */
+        use_device(I);
+        if (!I->cams_fence) HIP_OK(hipEventCreateWithFlags(&I->cams_fence, hipEventDisableTiming), "Couldn't create a timing event");
+        HIP_OK(hipEventRecord(I->cams_fence, I->stream), "Couldn't run the kernel");
+        I->cams_fence_pending = true; I->cams_in_flight = false;
+    }
+    I->stream = next;
 }
 void clw_ext_unit(cl_wrap* wrap, int op, const float* in, uint32_t stride_in, float* out, uint32_t stride_out, uint32_t n,
                   uint32_t aux) {
@@ -1066,6 +1129,24 @@ void clw_ext_set_supersample(cl_wrap* wrap, int n) {
     impl_of(wrap)->supersample = n;
 }
 int clw_ext_get_supersample(const cl_wrap* wrap) { return impl_of(wrap)->supersample; }
+void clw_ext_set_sample_cameras(cl_wrap* wrap, const clw_sample_camera* cams, uint32_t count) {
+    Impl* I = impl_of(wrap);
+    if (cams && count) I->cams.assign(cams, cams + count); else I->cams.clear();
+    I->aperture = 0.0f;     /* the table and the lens are alternatives: the later call wins */
+}
+uint32_t clw_ext_get_sample_cameras(const cl_wrap* wrap, clw_sample_camera* out, uint32_t cap) {
+    const Impl* I = impl_of(wrap);
+    const uint32_t n = (uint32_t)I->cams_used.size();
+    if (out && n && cap >= n) memcpy(out, I->cams_used.data(), (size_t)n * sizeof(clw_sample_camera));
+    return n;
+}
+void clw_ext_set_lens(cl_wrap* wrap, float aperture, float focus) {
+    if (!(aperture >= 0.0f) || !std::isfinite(aperture)) die("The lens aperture must be a finite number >= 0");
+    if (!(focus > 0.0f) || !std::isfinite(focus)) die("The lens focus distance must be a finite number > 0");
+    Impl* I = impl_of(wrap);
+    I->aperture = aperture; I->focus = focus;
+    I->cams.clear();
+}
 
 void clw_ext_set_pipeline(cl_wrap* wrap, int on) { impl_of(wrap)->pipeline = on ? 1 : 0; }
 void clw_ext_set_timing_every(cl_wrap* wrap, uint32_t n) { Impl* I = impl_of(wrap); I->timing_every = n ? n : 1; I->timing_tick = 0; I->timing_on = n != 0; }

@@ -11,6 +11,7 @@
 #include "../../include/hip_wrap_ext.h"
 #include <float.h>
 #include <math.h>
+#include <string.h>
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -47,6 +48,72 @@ int clw_host_perspective(const float origin[3], const float look[3], float fov, 
         out->right[k] = right[k];
         out->up[k] = up[k];
         out->im_corner[k] = centre - right[k] * image_w / 2 + up[k] * image_h / 2;
+    }
+    return 1;
+}
+
+/* ---- tables of n x n sample cameras (hip_wrap_ext.h: clw_ext_set_sample_cameras) ---------------------------------- */
+
+static int sample_factor_lg(uint32_t n) { return n == 2 ? 1 : (n == 4 ? 2 : (n == 8 ? 3 : 0)); }
+
+/* sample k = sy * n + sx -> lens cell / shutter slot j: k with its 2 log2 n bits reversed */
+static uint32_t sample_slot(uint32_t k, int lg) {
+    uint32_t j = 0;
+    for (int b = 0; b < 2 * lg; b++) j |= ((k >> b) & 1u) << (2 * lg - 1 - b);
+    return j;
+}
+
+int clw_host_lens_cameras(const clw_camera* base, float aperture, float focus, uint32_t n, clw_sample_camera* out) {
+    const int lg = sample_factor_lg(n);
+    if (!base || !out || !lg || !(aperture >= 0.0f) || !isfinite(aperture) || !(focus > 0.0f) || !isfinite(focus)) return 0;
+    /* image-plane centre relative to the origin, its length (the focal distance), and q = focal / focus: double, q stored to float */
+    double c2 = 0;
+    for (int a = 0; a < 3; a++) {
+        double c = (double)base->im_corner[a] + (double)base->right[a] * ((double)base->w_factor * base->width / 2)
+                                              - (double)base->up[a] * ((double)base->h_factor * base->height / 2);
+        c2 += c * c;
+    }
+    const double focal = sqrt(c2);
+    if (!(focal > 0) || !isfinite(focal)) return 0;
+    const float q = (float)(focal / (double)focus);
+    if (!isfinite(q)) return 0;
+    for (uint32_t k = 0; k < n * n; k++) {
+        clw_sample_camera* o = out + k;
+        memcpy(o->im_corner, base->im_corner, 12); memcpy(o->origin, base->origin, 12);
+        memcpy(o->up, base->up, 12); memcpy(o->right, base->right, 12);
+        if (aperture == 0.0f) continue;                /* the pinhole: the base camera, bit for bit */
+        const uint32_t j = sample_slot(k, lg);
+        /* centre of lens cell (j mod n, j div n) in [-1, 1]^2 -> unit disk, concentric map (Shirley & Chiu 1997): double, stored to float */
+        const double a = (2.0 * (j % n) + 1.0) / n - 1.0, b = (2.0 * (j / n) + 1.0) / n - 1.0;
+        double r, phi;
+        if (fabs(a) > fabs(b)) { r = a; phi = (M_PI / 4) * (b / a); }
+        else { r = b; phi = M_PI / 2 - (M_PI / 4) * (a / b); }      /* (n is even: no cell centre at 0, 0) */
+        const float lx = (float)(r * cos(phi)), ly = (float)(r * sin(phi));
+        const float ax = aperture * lx, ay = aperture * ly;
+        for (int i = 0; i < 3; i++) {
+            const float delta = base->right[i] * ax + base->up[i] * ay;
+            o->origin[i] = base->origin[i] + delta;
+            o->im_corner[i] = base->im_corner[i] - delta * q;
+        }
+    }
+    return 1;
+}
+
+static float shutter_mix(float a, float b, float t) { return a == b ? a : a + (b - a) * t; }
+
+int clw_host_shutter_cameras(const clw_camera* open, const clw_camera* close, uint32_t n, clw_sample_camera* out) {
+    const int lg = sample_factor_lg(n);
+    if (!open || !close || !out || !lg) return 0;
+    if (open->width != close->width || open->height != close->height ||
+        memcmp(&open->w_factor, &close->w_factor, 4) || memcmp(&open->h_factor, &close->h_factor, 4)) return 0;
+    for (uint32_t k = 0; k < n * n; k++) {
+        const float t = ((float)sample_slot(k, lg) + 0.5f) / (float)(n * n);      /* exact */
+        for (int i = 0; i < 3; i++) {
+            out[k].im_corner[i] = shutter_mix(open->im_corner[i], close->im_corner[i], t);
+            out[k].origin[i] = shutter_mix(open->origin[i], close->origin[i], t);
+            out[k].up[i] = shutter_mix(open->up[i], close->up[i], t);
+            out[k].right[i] = shutter_mix(open->right[i], close->right[i], t);
+        }
     }
     return 1;
 }

@@ -66,6 +66,11 @@ extern "C" hipError_t WT_LAUNCH_SCHED(const unsigned* cost, unsigned* order, uns
     return hipGetLastError();
 }
 
+extern "C" hipError_t WT_LAUNCH_CAMS(const wt_cam_table* T, float* dst, hipStream_t s) {
+    hipLaunchKernelGGL(WT_NS::wt_cams_store, dim3(1), dim3(64), 0, s, *T, (float4*)dst);
+    return hipGetLastError();
+}
+
 extern "C" hipError_t WT_LAUNCH_UNIT(int op, const float* in, float* out, unsigned n, unsigned stride_in,
                                      unsigned stride_out, unsigned aux, hipStream_t s) {
     hipLaunchKernelGGL(WT_NS::wt_unit, dim3((n + 63) / 64), dim3(64), 0, s, op, in, out, n, stride_in, stride_out, aux);

@@ -91,7 +91,14 @@ typedef struct {
      * buffers above describe the VIRTUAL frame of n x as many columns and rows; the n x n samples of an output pixel sit in adjacent lanes
      * of one wavefront and are resolved in registers (wt_ss_resolve); out / out_rgb hold one entry per OUTPUT pixel, width >> ss_lg per row */
     uint32_t ss_lg;
+    /* sample cameras of a supersampled launch (NULL = every sample looks through the launch camera above): WT_CAM_TABLE_FLOATS floats,
+     * 12 per LANE of a tile's wavefront -- { im_corner, origin, up, right } of the camera of sub-sample ((lane & 7) mod n, (lane >> 3) mod n);
+     * w_factor, h_factor, width, height stay the launch's (16-byte aligned) */
+    const float* ss_cams;
 } whitted_params;
+
+#define WT_CAM_TABLE_FLOATS (64 * 12)
+typedef struct { float v[WT_CAM_TABLE_FLOATS]; } wt_cam_table;   /* the table as a by-value kernel argument (wt_cams_store) */
 
 typedef struct {
     float corner[3], origin[3], up[3], right[3];

@@ -261,6 +261,17 @@ __device__ __forceinline__ f3 wt_primary_dir_xy(const float* corner, const float
     float len = sqrtf(vx * vx + vy * vy + vz * vz);
     return mk3(vx / len, vy / len, vz / len);
 }
+/* the same with a camera of the lane's own (the sample cameras of a supersampled launch): the same operations in the same order */
+__device__ __forceinline__ f3 wt_primary_dir_xy(f3 corner, f3 right, f3 up, float w_factor, float h_factor, unsigned px, unsigned py) {
+#pragma clang fp contract(off)
+    const float w = (float)px;
+    const float h = (float)py;
+    float vx = corner.x + right.x * w_factor * w - up.x * h_factor * h;
+    float vy = corner.y + right.y * w_factor * w - up.y * h_factor * h;
+    float vz = corner.z + right.z * w_factor * w - up.z * h_factor * h;
+    float len = sqrtf(vx * vx + vy * vy + vz * vz);
+    return mk3(vx / len, vy / len, vz / len);
+}
 
 /* (int)f as AMD hardware converts it: saturating, NaN -> 0 (v_cvt_i32_f32) */
 __device__ __forceinline__ int wt_f2i(float f) { return (int)f; }
@@ -1446,6 +1457,14 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
             float4 ro = rr[0], rd = rr[1], rc = rr[2];
             o = mk3(ro.x, ro.y, ro.z); d = mk3(rd.x, rd.y, rd.z); rgb = mk3(rc.x, rc.y, rc.z);
             depth = __float_as_int(rr[3].x);
+        } else if (SS && P.ss_cams) {
+            /* a table of sample cameras (wave-uniform branch, supersampled flavours only): the lane's sub-sample is fixed by its number --
+             * ((lane & 7) mod n, (lane >> 3) mod n), the virtual row offset being a multiple of n -- so the shim lays the table out per lane:
+             * 12 floats { im_corner, origin, up, right }, three coalesced 16-byte loads, once per wave */
+            const float4* c = (const float4*)P.ss_cams + 3u * lane;
+            const float4 c0 = c[0], c1 = c[1], c2 = c[2];
+            d = wt_primary_dir_xy(mk3(c0.x, c0.y, c0.z), mk3(c2.y, c2.z, c2.w), mk3(c1.z, c1.w, c2.x), P.w_factor, P.h_factor, x, gy);
+            o = mk3(c0.w, c1.x, c1.y);
         } else {
             if (P.tiled || P.band_stride > 1u) d = wt_primary_dir_xy(P.corner, P.right, P.up, P.w_factor, P.h_factor, x, gy);
             else d = wt_primary_dir(P.corner, P.right, P.up, P.w_factor, P.h_factor, (unsigned)gid, P.width);
@@ -1618,6 +1637,16 @@ template <int FLAGS>
 __global__ void __launch_bounds__(WT_BLOCK, wt_cfg<FLAGS>::min_waves) wt_trace(const whitted_params P_arg) {
     const wt_kparams_t Pk = (wt_kparams_t)__builtin_amdgcn_kernarg_segment_ptr();     /* = &P_arg */
     wt_trace_body<FLAGS>(Pk, blockIdx.x);
+}
+
+/* ---- the per-lane table of sample cameras (whitted_params.h: ss_cams) travels as a by-value kernel argument and is written by the launch
+ *      stream itself: ordered behind the launches that read the previous table, no host memory to keep alive, no host wait. ---- */
+__global__ void __launch_bounds__(64) wt_cams_store(const wt_cam_table T_arg, float4* __restrict__ dst) {
+    typedef const __attribute__((address_space(4))) float4* kargs_t;
+    const float4* src = (const float4*)(kargs_t)__builtin_amdgcn_kernarg_segment_ptr();   /* = &T_arg */
+    (void)T_arg;
+#pragma unroll
+    for (unsigned k = 0; k < WT_CAM_TABLE_FLOATS / 4u / 64u; k++) dst[k * 64u + threadIdx.x] = src[k * 64u + threadIdx.x];
 }
 
 #define WT_RG_BLOCK 256

@@ -10,7 +10,9 @@ per rank and frame, a one-word all-reduce as the completion signal).  Work-item 
 clw_ext_set_id_offset / clw_ext_set_row_bands) so the assembled image is bit-identical to a single-GPU render.
 Supersampled renderers (`Renderer(..., supersample=n)`) compose the same way in the "strips" layout: a strip of output rows is n x as many rows
 of the sampled frame and the sample ids stay global (tests/test_gpu_supersample.py); the gather moves W x H pixels as before.  Interleaved
-bands are not supersampled (the shim refuses them).
+bands are not supersampled (the shim refuses them).  Sample cameras -- a lens (`Renderer(..., lens=(aperture, focus))`) or an explicit
+table (`set_sample_cameras`) -- need nothing new here: the table is derived from the W x H camera, not from the strip, so it is the same on
+every rank (tests/test_gpu_sample_cameras.py).
 """
 from __future__ import annotations
 

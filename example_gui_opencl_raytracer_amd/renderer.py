@@ -13,6 +13,10 @@ frame; work-item ids, and with them ``id % W``, ``id / W`` and the RNG seed, sta
 ``supersample=n`` (2, 4, 8): every pixel is the mean of n x n samples traced and resolved inside the
 kernel (include/hip_wrap_ext.h, clw_ext_set_supersample); ``render()`` and ``render_rgb()`` still
 return W*H entries, and strips compose as before.
+
+``lens=(aperture, focus)`` (with ``supersample`` > 1): the n x n samples of a pixel look through n x n points of a thin lens focused at
+distance ``focus`` (clw_ext_set_lens); ``set_sample_cameras`` hands the kernel any table of n x n cameras instead, e.g.
+``api.shutter_cameras`` for camera motion blur.
 """
 from __future__ import annotations
 
@@ -39,7 +43,8 @@ class Renderer:
     def __init__(self, scene: Scene, tex: np.ndarray, sky: np.ndarray, width: int, height: int, *,
                  depth: int = 15, strict: bool = False, fuse: bool = True, first_row: int = 0,
                  rows: int | None = None, bands: tuple[int, int] | None = None, framebuffer_ptr: int | None = None, wide_counts: bool | None = None,
-                 texture_paths=None, skybox_path=None, supersample: int = 1):
+                 texture_paths=None, skybox_path=None, supersample: int = 1,
+                 lens: tuple[float, float] | None = None):
         self.width, self.height = width, height
         self.first_row = first_row
         self.rows = height - first_row if rows is None else rows
@@ -55,6 +60,8 @@ class Renderer:
         w.set_id_offset(first_row * width)
         if supersample != 1:      # n x n samples per pixel, resolved in the trace kernel: sizes, rows and strips here stay in output pixels
             w.set_supersample(supersample)
+        if lens is not None:      # (aperture, focus): depth of field from the samples of a pixel
+            w.set_lens(*lens)
         if bands is not None:
             w.set_row_bands(*bands)
 
@@ -98,6 +105,10 @@ class Renderer:
         w.load_single_data(0, 3, f3(cam.right))
         w.load_single_data(0, 4, np.float32(cam.w_factor))
         w.load_single_data(0, 5, np.float32(cam.h_factor))
+
+    def set_sample_cameras(self, cams) -> None:
+        """float32 [n*n, 12]: sample k = sy * n + sx of every pixel looks through camera k (None = the launch camera); replaces a lens."""
+        self.w.set_sample_cameras(cams)
 
     def look(self, origin, look, fov=90.0, focal=1.0):
         cam = api.perspective(origin, look, fov, focal, self.width, self.height)

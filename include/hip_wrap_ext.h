@@ -12,7 +12,7 @@
  *
  * Environment variables read once by cl_wrap_init (same meaning as the setters):
  *   CLWRAP_DEPTH=<1..32>   CLWRAP_STRICT=<0|1>   CLWRAP_FUSE=<0|1>   CLWRAP_DEVICE=<ordinal>   CLWRAP_PIPELINE=<0|1>   CLWRAP_THROUGH=<float>
- *   CLWRAP_SUPERSAMPLE=<1|2|4|8>
+ *   CLWRAP_SUPERSAMPLE=<1|2|4|8>   CLWRAP_APERTURE=<float >= 0>   CLWRAP_FOCUS=<float > 0>   (thin lens: clw_ext_set_lens)
  * Tuning / experiment knobs (defaults are the measured optima): CLWRAP_GRID_MIN, CLWRAP_GRID_DENSITY (uniform grid),
  *   CLWRAP_OCC_TILES_PER_DEPTH (deep launches of >= this x depth tiles take the high-occupancy kernel flavour),
  *   CLWRAP_TIMING_EVERY, CLWRAP_VARIANT (bit mask of clw_ext_set_variant).
@@ -116,6 +116,26 @@ void clw_ext_set_debug_rgb(cl_wrap* wrap, void* device_ptr_f32x3);
 void clw_ext_set_supersample(cl_wrap* wrap, int n);
 int clw_ext_get_supersample(const cl_wrap* wrap);
 
+/* Per-sample cameras: with supersampling factor n in {2, 4, 8} and a table cams[0 .. n*n) in effect, the sample at virtual pixel
+ * (vx, vy) -- sub-sample (sx, sy) = (vx mod n, vy mod n) of output pixel (vx div n, vy div n) -- is pixel (vx, vy) of a 1-sample
+ * render of the n*W x n*H frame with im_corner, origin, up and right of cams[sy * n + sx] and the launch's w_factor / n, h_factor / n:
+ * same primary-ray arithmetic, same ids (RNG seeds), same clamp, resolve and pack as plain supersampling.  A table whose entries all
+ * equal the launch camera gives the plain supersampled frame bit for bit.  The ray buffer keeps its meaning (one ray per OUTPUT pixel
+ * through the launch camera).  `cams` is copied; count 0 or NULL = no table (and it clears a lens).  Refused at the next trace launch
+ * with an error and exit(1): a table whose count is not n * n of the factor then in effect (any table with factor 1 included). */
+typedef struct clw_sample_camera { float im_corner[3], origin[3], up[3], right[3]; } clw_sample_camera;   /* 48 bytes */
+void     clw_ext_set_sample_cameras(cl_wrap* wrap, const clw_sample_camera* cams, uint32_t count);
+/* The table the LAST trace launch used (explicit or lens-derived), in sy * n + sx order -> its count (0 = none); copies the entries
+ * if `cap` suffices. */
+uint32_t clw_ext_get_sample_cameras(const cl_wrap* wrap, clw_sample_camera* out, uint32_t cap);
+
+/* Thin lens (depth of field) on top of the table: with aperture > 0 every fused trace launch derives its table with
+ * clw_host_lens_cameras from the camera latched by the raygen launch (the W x H one), so a driver that moves its camera every frame
+ * gets the lens for free.  aperture 0 (default) = pinhole; env CLWRAP_APERTURE, CLWRAP_FOCUS (default focus 1).  An explicit table
+ * and the lens are alternatives: the later call wins and clears the other.  Errors (print + exit(1)): aperture negative or not
+ * finite, focus <= 0 or not finite; at launch, aperture > 0 with supersampling factor 1 (a lens needs samples). */
+void clw_ext_set_lens(cl_wrap* wrap, float aperture, float focus);
+
 /* Work counters of the trace kernel.  enable=1 selects the counting build of the kernel
  * for subsequent launches (slower); read returns and clears
  *   out[0] path segments  out[1] shadow rays  out[2] light probes  out[3] skybox fetches
@@ -208,6 +228,22 @@ typedef struct clw_camera {
 } clw_camera;
 int clw_host_perspective(const float origin[3], const float look[3], float fov, float focal,
                          uint32_t width, uint32_t height, clw_camera* out);
+
+/* Host helper: THE definition of the lens table, n in {2, 4, 8}; returns 0 on bad arguments (n, aperture < 0 or not finite,
+ * focus <= 0 or not finite, a camera whose image plane passes through its origin), else 1 and n * n entries in sy * n + sx order.
+ *   image-plane centre (im_corner is relative to the origin)  c = im_corner + right (w_factor W / 2) - up (h_factor H / 2),
+ *   focal = |c|, q = focal / focus                                      [double; q rounded to float]
+ *   sample k = sy n + sx takes lens cell j = k with its 2 log2 n bits reversed, cell (j mod n, j div n); the cell's centre in
+ *   [-1, 1]^2 goes to the unit disk by the concentric (Shirley-Chiu) map -> (lx, ly)          [double; lx, ly rounded to float]
+ *   delta = right (aperture lx) + up (aperture ly);  origin_k = origin + delta;  im_corner_k = im_corner - delta q;  up, right unchanged
+ *                                                                       [float32, one rounding per operation, no contraction]
+ * Every camera sees a point of the plane at axial distance `focus` at the same virtual pixel position.  aperture 0 returns n * n
+ * copies of the base camera, bit for bit. */
+int clw_host_lens_cameras(const clw_camera* base, float aperture, float focus, uint32_t n, clw_sample_camera* out);
+/* Host helper: an open shutter between two cameras (camera motion blur; set the result with clw_ext_set_sample_cameras).  Sample k
+ * looks through the camera at time t = (j + 1/2) / n^2, j as above, each of the four vectors a + (b - a) t in float32 (a where
+ * a == b).  Returns 0 when n is not 2, 4 or 8 or the two cameras differ in width, height, w_factor or h_factor. */
+int clw_host_shutter_cameras(const clw_camera* open, const clw_camera* close, uint32_t n, clw_sample_camera* out);
 
 /* Host helpers: PNG files without libpng (reference png_dump, src/cpu_ray.c:108-165, and the
  * decode step of cl_wrap_load_images).  Return 0 on success. */

@@ -4,12 +4,13 @@
  * reference drivers hard-code 800x600 and a cl_uint byte count that overflows at 8192x8192).
  * Host code is C99 and talks to the GPU only through include/opencl_wrap.h + include/hip_wrap_ext.h.
  *
- *   raybench [-w W] [-h H] [-d depth] [-n frames] [-s scene.map] [-a assets_dir] [-o out.png] [-r] [-S] [--supersample N]
+ *   raybench [-w W] [-h H] [-d depth] [-n frames] [-s scene.map] [-a assets_dir] [-o out.png] [-r] [-S] [--supersample N] [--aperture A --focus F]
  *     -s  scene archive: the reference's render.map format or the extended wide-count format (scene.py)
  *     -a  directory holding cobblestone.png sand.png check.png grass.png bg/stormydays.png (raypng.c:74-81)
  *     -r  include the blocking framebuffer read-back in every frame (what rayinteractive's loop does)
  *     -S  strict arithmetic build
  *     --supersample N  n x n samples per pixel, resolved in the trace kernel (clw_ext_set_supersample); the frame stays W x H
+ *     --aperture A --focus F  thin lens over those samples (clw_ext_set_lens): depth of field, focused at distance F
  * Prints one JSON line with kernel-only and per-frame wall times.
  */
 #include <stdio.h>
@@ -50,6 +51,7 @@ static int load_scene(const char* path, void** sph, uint32_t* ns, void** pln, ui
 int main(int argc, char** argv) {
     uint32_t W = 1920, H = 1080;
     int depth = 4, frames = 100, readback = 0, strict = 0, supersample = 1;
+    float aperture = 0.0f, focus = 1.0f;
     const char *scene = "scenes/render.map", *assets = "assets", *out = NULL;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-w") && i + 1 < argc) W = (uint32_t)atoi(argv[++i]);
@@ -62,7 +64,9 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "-r")) readback = 1;
         else if (!strcmp(argv[i], "-S")) strict = 1;
         else if (!strcmp(argv[i], "--supersample") && i + 1 < argc) supersample = atoi(argv[++i]);
-        else { fprintf(stderr, "usage: raybench [-w W] [-h H] [-d depth] [-n frames] [-s scene] [-a assets] [-o out.png] [-r] [-S] [--supersample N]\n"); return 2; }
+        else if (!strcmp(argv[i], "--aperture") && i + 1 < argc) aperture = (float)atof(argv[++i]);
+        else if (!strcmp(argv[i], "--focus") && i + 1 < argc) focus = (float)atof(argv[++i]);
+        else { fprintf(stderr, "usage: raybench [-w W] [-h H] [-d depth] [-n frames] [-s scene] [-a assets] [-o out.png] [-r] [-S] [--supersample N] [--aperture A --focus F]\n"); return 2; }
     }
     void *sph, *pln, *lgt;
     uint32_t ns, np, nl;
@@ -77,6 +81,7 @@ int main(int argc, char** argv) {
     clw_ext_set_depth(&w, depth);
     clw_ext_set_strict(&w, strict);
     if (supersample != 1) clw_ext_set_supersample(&w, supersample);
+    if (aperture != 0.0f) clw_ext_set_lens(&w, aperture, focus);
 
     const size_t pixels = (size_t)W * H;                 /* size_t: 64 B x 8192^2 overflows cl_uint (raypng.c:44) */
     const size_t buffer_size = pixels * sizeof(cl_uint);
@@ -130,8 +135,8 @@ int main(int argc, char** argv) {
     cl_wrap_output(&w, pixels, 0, 0, 0, 0, NULL);
     cl_wrap_output(&w, pixels, buffer_size, 1, 1, 10, buffer);
     printf("{\"driver\": \"raybench.c\", \"frame\": \"%ux%u\", \"depth\": %d, \"spheres\": %u, \"planes\": %u, \"lights\": %u, "
-           "\"frames\": %d, \"readback\": %d, \"strict\": %d, \"supersample\": %d, \"trace_kernel_ms\": %.4f, \"wall_ms_per_frame\": %.4f, \"frames_per_s\": %.1f}\n",
-           W, H, depth, ns, np, nl, frames, readback, strict, supersample, kms / (launches ? launches : 1), wall, 1e3 / wall);
+           "\"frames\": %d, \"readback\": %d, \"strict\": %d, \"supersample\": %d, \"aperture\": %g, \"focus\": %g, \"trace_kernel_ms\": %.4f, \"wall_ms_per_frame\": %.4f, \"frames_per_s\": %.1f}\n",
+           W, H, depth, ns, np, nl, frames, readback, strict, supersample, (double)aperture, (double)focus, kms / (launches ? launches : 1), wall, 1e3 / wall);
     if (out && clw_host_write_png(out, buffer, W, H) != 0) fprintf(stderr, "cannot write %s\n", out);
     cl_wrap_release(&w);
     free(sph); free(pln); free(lgt); free(buffer);

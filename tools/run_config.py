@@ -1,7 +1,9 @@
 """Time one BASELINE.json configuration through the C-ABI (kernel-only, frames back to back) and print JSON.
-   python tools/run_config.py c2|c3|c4|c5strip|ref800 [--strict 1] [--frames N] [--variant V] [--depth D] [--size WxH] [--supersample N]
+   python tools/run_config.py c2|c3|c4|c5strip|ref800 [--strict 1] [--frames N] [--variant V] [--depth D] [--size WxH] [--supersample N] [--aperture A --focus F | --copies]
    --supersample N: n x n samples per pixel resolved in the kernel (the frame stays WxH); --size: another frame size for the configuration's
    scene and camera -- e.g. the n*W x n*H frame a supersampled launch traces, to time the same work without the resolve.
+   --aperture A --focus F: a thin lens over the samples (clw_ext_set_lens); --copies: an explicit table of n*n copies of the launch camera
+   (clw_ext_set_sample_cameras) -- the plain supersampled image through the table path, to time the mechanism alone.
    --repeats R: the N-frame loop R times (0 = until 50 ms have been timed, as bench.py --full does), median / min / max of the repeats."""
 import argparse, json, math, os, statistics, sys, time
 import numpy as np
@@ -21,6 +23,9 @@ ap.add_argument("--png", default=None)
 ap.add_argument("--size", default=None)
 ap.add_argument("--supersample", type=int, default=1)
 ap.add_argument("--repeats", type=int, default=1)
+ap.add_argument("--aperture", type=float, default=0.0)
+ap.add_argument("--focus", type=float, default=1.0)
+ap.add_argument("--copies", action="store_true")
 a = ap.parse_args()
 tex, sky = textures.texture_layers(), textures.skybox_cross(4096)
 cam = pkg.CAMERA_RAYPNG
@@ -47,7 +52,11 @@ if a.supersample != 1:
     kw["supersample"] = a.supersample
 r = Renderer(sc, tex, sky, W, H, depth=depth, strict=bool(a.strict), **kw)
 r.w.set_variant(a.variant)
-r.look(**cam)
+camera = r.look(**cam)
+if a.aperture:
+    r.w.set_lens(a.aperture, a.focus)
+elif a.copies:
+    r.set_sample_cameras(np.tile(np.concatenate([np.asarray(v, np.float32) for v in (camera.im_corner, camera.origin, camera.up, camera.right)]), (a.supersample ** 2, 1)))
 r.render(readback=False); r.render(readback=False)
 r.w.enable_counters(1); r.render(readback=False); c = r.w.read_counters(); r.w.enable_counters(0)
 r.w.set_async(1)
@@ -68,7 +77,7 @@ r.w.set_async(0)
 img = r.render()
 rays = c["segments"] + c["shadow_rays"]
 px = r.pixels
-print(json.dumps(dict(config=a.config, frame=f"{W}x{H}", pixels=px, depth=depth, strict=a.strict, variant=a.variant, supersample=a.supersample, kernel_ms=round(ms / n, 4),
+print(json.dumps(dict(config=a.config, frame=f"{W}x{H}", pixels=px, depth=depth, strict=a.strict, variant=a.variant, supersample=a.supersample, aperture=a.aperture, focus=a.focus, copies=int(a.copies), kernel_ms=round(ms / n, 4),
                       kernel_ms_min=round(min(kms), 4), kernel_ms_max=round(max(kms), 4), repeats=len(kms),
                       wall_ms_per_frame=round(wall * 1e3, 4), rays_per_px=round(rays / px, 3), Mrays_s=round(rays / (ms / n) / 1e3, 1),
                       lane_util=round(c["lane_iters"] / max(c["wave_iters_x64"], 1), 4), counters=c)), flush=True)
