@@ -40,6 +40,7 @@ SYMBOLS = [
     "clw_host_free", "clw_ext_version",
     "clw_ext_set_supersample", "clw_ext_get_supersample",
     "clw_ext_set_sample_cameras", "clw_ext_get_sample_cameras", "clw_ext_set_lens", "clw_host_lens_cameras", "clw_host_shutter_cameras",
+    "clw_ext_set_sphere_motion", "clw_ext_get_sample_times", "clw_host_sample_times", "clw_host_spheres_at",
 ]
 
 
@@ -130,6 +131,14 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         L.clw_host_lens_cameras.restype = C.c_int
         L.clw_host_shutter_cameras.argtypes = [C.POINTER(clw_camera), C.POINTER(clw_camera), u32, vp]
         L.clw_host_shutter_cameras.restype = C.c_int
+    if hasattr(L, "clw_ext_set_sphere_motion") or not os.environ.get("CLWRAP_LIB"):       # (an older A/B build may lack them)
+        L.clw_ext_set_sphere_motion.argtypes = [W, vp, u32, vp, u32]
+        L.clw_ext_get_sample_times.argtypes = [W, vp, u32]
+        L.clw_ext_get_sample_times.restype = u32
+        L.clw_host_sample_times.argtypes = [u32, vp]
+        L.clw_host_sample_times.restype = C.c_int
+        L.clw_host_spheres_at.argtypes = [vp, u32, vp, C.c_float, vp]
+        L.clw_host_spheres_at.restype = C.c_int
     L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
     L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
     L.clw_ext_read_tile_costs.restype = u32
@@ -184,6 +193,27 @@ def shutter_cameras(cam0: clw_camera, cam1: clw_camera, n: int) -> np.ndarray:
     out = np.zeros((max(int(n), 0) ** 2 or 1, 12), np.float32)
     if not load_library().clw_host_shutter_cameras(C.byref(cam0), C.byref(cam1), n, _ptr(out)):
         raise ValueError("clw_host_shutter_cameras rejects these arguments (n in 2, 4, 8; cameras of one size and one pair of factors)")
+    return out
+
+
+def sample_times(n: int) -> np.ndarray:
+    """clw_host_sample_times: the default scene times of the n*n samples of a pixel (the shutter's clock) -> float32 [n*n], sy * n + sx order."""
+    out = np.zeros(max(int(n), 0) ** 2 or 1, np.float32)
+    if not load_library().clw_host_sample_times(n, _ptr(out)):
+        raise ValueError("clw_host_sample_times rejects this factor (n in 2, 4, 8)")
+    return out
+
+
+def spheres_at(spheres: np.ndarray, disp, t: float) -> np.ndarray:
+    """clw_host_spheres_at: the 96-byte sphere records of the scene at time t -- centre i = fma(t, disp[i], centre i) in float32, every
+    other byte copied -> a new record array of the same dtype."""
+    spheres = np.ascontiguousarray(spheres)
+    assert spheres.dtype.itemsize == 96
+    disp = np.ascontiguousarray(disp, np.float32).reshape(-1, 3)
+    assert len(disp) == len(spheres)
+    out = spheres.copy()
+    if not load_library().clw_host_spheres_at(_ptr(spheres), len(spheres), _ptr(disp), float(t), _ptr(out)):
+        raise ValueError("clw_host_spheres_at rejects these arguments")
     return out
 
 
@@ -336,6 +366,24 @@ class ClWrap:
         return out
 
     def set_lens(self, aperture, focus): self.L.clw_ext_set_lens(C.byref(self.w), float(aperture), float(focus))
+
+    def set_sphere_motion(self, disp, times=None):
+        """disp float32 [spheres, 3] (the movement of each centre while the shutter is open), times float32 [n*n] or None (the shutter
+        times); both copied.  disp None / empty = no table."""
+        if disp is None or len(disp) == 0:
+            self.L.clw_ext_set_sphere_motion(C.byref(self.w), None, 0, None, 0)
+            return
+        disp = np.ascontiguousarray(disp, np.float32).reshape(-1, 3)
+        times = None if times is None else np.ascontiguousarray(times, np.float32).reshape(-1)
+        self.L.clw_ext_set_sphere_motion(C.byref(self.w), _ptr(disp), disp.shape[0], None if times is None else _ptr(times), 0 if times is None else times.size)
+
+    def get_sample_times(self) -> np.ndarray:
+        """The sample times the last trace launch used -> float32 [count] (count 0 = the scene stood still)."""
+        n = self.L.clw_ext_get_sample_times(C.byref(self.w), None, 0)
+        out = np.zeros(n, np.float32)
+        if n:
+            self.L.clw_ext_get_sample_times(C.byref(self.w), _ptr(out), n)
+        return out
 
     def enable_counters(self, on): self.L.clw_ext_enable_counters(C.byref(self.w), int(on))
 

@@ -41,7 +41,7 @@ extern "C" hipError_t wt_fast_launch_sched(const unsigned*, unsigned*, unsigned,
 
 namespace {
 
-enum { F_COUNT = 1, F_DEEP = 2, F_GEOM_LDS = 4, F_RAYS = 8, F_GRID = 16, F_OCC = 32, F_D8 = 64, F_D16 = 128, F_SHAPE = 256, F_SS = 1 << 17 }; /* = WT_F_* of whitted_trace.inc */
+enum { F_COUNT = 1, F_DEEP = 2, F_GEOM_LDS = 4, F_RAYS = 8, F_GRID = 16, F_OCC = 32, F_D8 = 64, F_D16 = 128, F_SHAPE = 256, F_SS = 1 << 17, F_MOVE = 1 << 18 }; /* = WT_F_* of whitted_trace.inc */
 /* shallow fast launches of small LDS-geometry scenes run a kernel with the scene's counts compiled in (wt_shape of whitted_trace.inc): the
  * counts whitted_launch.inc instantiates -- 1..SHAPE_MAX_SPHERES spheres, 0..SHAPE_MAX_PLANES planes, SHAPE_LIGHTS lights */
 constexpr uint32_t SHAPE_MAX_SPHERES = 4, SHAPE_MAX_PLANES = 2, SHAPE_LIGHTS = 3;
@@ -77,6 +77,11 @@ constexpr size_t GRID_MAX_PAIRS = (size_t)1 << 25;   /* 20 B per cell-list entry
     va_end(ap);
     fflush(stdout);
     exit(1);
+}
+
+/* the same floats bit for bit (+0 and -0 differ, a NaN equals itself): "the device table is unchanged" is decided on what it holds */
+bool same_bits(const std::vector<float>& a, const std::vector<float>& b) {
+    return a.size() == b.size() && (a.empty() || !memcmp(a.data(), b.data(), a.size() * sizeof(float)));
 }
 
 #define HIP_OK(call, what)                                                        \
@@ -163,6 +168,15 @@ struct Impl {
     float* d_cams = nullptr;
     wt_cam_table cams_dev{}; bool cams_dev_valid = false;   /* what d_cams holds once the stream gets there */
     hipEvent_t cams_fence = nullptr; bool cams_fence_pending = false, cams_in_flight = false;
+    /* moving spheres of supersampled launches (clw_ext_set_sphere_motion).  The device copy -- 64 per-lane times, then a float4 per sphere
+     * (whitted_params.h: ss_times, ss_disp) -- is written like the camera table: only when it changed, in pieces of one wt_cam_table by the
+     * same small kernel on the launch stream, and behind the same fence when the stream changes. */
+    std::vector<float> motion_disp;              /* 3 per sphere; empty = the scene stands still (an all-zero table is stored as none) */
+    std::vector<float> motion_times;             /* explicit sample times, sy * n + sx order (only when motion_explicit_times) */
+    bool motion_explicit_times = false;          /* the caller gave times (of any count: the launch checks it); false = the shutter times of the launch's factor */
+    std::vector<float> times_used;               /* the times of the latest trace launch (clw_ext_get_sample_times) */
+    float* d_motion = nullptr;
+    std::vector<float> motion_dev;               /* what d_motion holds once the stream gets there; empty = nothing yet */
     /* prepared scene cache */
     const Buffer *prep_s = nullptr, *prep_p = nullptr, *prep_l = nullptr;
     uint32_t prep_ns = 0, prep_np = 0, prep_nl = 0;
@@ -190,6 +204,7 @@ struct Impl {
         uint32_t w = 0, rows = 0, cap = 0;           /* frame the buffers were sized for (the virtual frame of a supersampled launch); dispatch entries per XCD share */
         int ss = 1;                                   /* supersampling factor its orders were built for: it caps how far a tile is split */
         wt_cam_table sig_cams{}; bool sig_has_cams = false;   /* the sample cameras belong to the signature below */
+        std::vector<float> sig_motion;                        /* ... and so do the moving spheres' device table (empty = none) */
         RaygenArgs sig{}; int sig_depth = 0; uint64_t sig_scene = 0; bool sig_valid = false; int sig_age = 0, newest = 0; uint64_t frame = 0, newest_frame = 0;   /* what the newest order was built for, frames since */
         void reset() { have[0] = have[1] = false; sig_valid = false; newest = 0; }
         void free_all() {
@@ -561,6 +576,23 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
     bool have_cams = false;
     wt_cam_table cam_table;
     I->cams_used.clear();
+    const bool moving = !I->motion_disp.empty();
+    std::vector<float> motion_table;             /* the device layout: 64 per-lane times, a float4 per sphere, padded to whole wt_cam_tables */
+    I->times_used.clear();
+    if (moving) {
+        if (ss == 1) die("Moving spheres need samples: a displacement table with supersampling factor 1 (clw_ext_set_supersample / CLWRAP_SUPERSAMPLE)");
+        if (I->motion_explicit_times && I->motion_times.size() != (size_t)(ss * ss))
+            die("Moving spheres: %u sample times, but supersampling factor %d needs %d", (unsigned)I->motion_times.size(), ss, ss * ss);
+        if (I->motion_disp.size() != 3 * (size_t)P.ns)
+            die("Moving spheres: the displacement table is for %u spheres, the scene has %u", (unsigned)(I->motion_disp.size() / 3), (unsigned)P.ns);
+        if ((flags & F_GRID) || P.ns > GRID_MIN_SPHERES)
+            die("Moving spheres: scenes of more than %u spheres (the uniform grid is built for one set of centres) are not supported", (unsigned)GRID_MIN_SPHERES);
+        /* the 16 KiB staging rule counts the table: a scene it pushes over the limit reads both from global memory */
+        if (flags & F_GEOM_LDS) {
+            if (I->geom_f4 + P.ns <= GEOM_LDS_MAX_F4) dyn_lds += (size_t)P.ns * 16;
+            else { flags &= ~F_GEOM_LDS; dyn_lds = 0; }
+        }
+    }
     const bool fused = I->fuse && rays->gen_valid && !rays->exposed;   /* (a buffer whose pointer was handed out is read, not regenerated) */
     RaygenArgs g{};
     if (fused) {
@@ -616,6 +648,27 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
                 I->cams_in_flight = true;
                 P.ss_cams = I->d_cams;
             }
+            if (moving) {
+                if (!I->motion_explicit_times) { I->times_used.resize((size_t)(ss * ss)); clw_host_sample_times((uint32_t)ss, I->times_used.data()); }
+                else I->times_used = I->motion_times;
+                const size_t pieces = (64 + 4 * (size_t)P.ns + WT_CAM_TABLE_FLOATS - 1) / WT_CAM_TABLE_FLOATS;      /* <= 2: ns <= 256 */
+                motion_table.assign(pieces * WT_CAM_TABLE_FLOATS, 0.0f);
+                for (unsigned lane = 0; lane < 64; lane++)   /* as the camera table: lane (lane & 7, lane >> 3) traces sub-sample (sx, sy) = both mod n */
+                    motion_table[lane] = I->times_used[(size_t)((lane >> 3) & (unsigned)(ss - 1)) * ss + ((lane & 7u) & (unsigned)(ss - 1))];
+                for (uint32_t i = 0; i < P.ns; i++) memcpy(&motion_table[64 + 4 * (size_t)i], &I->motion_disp[3 * (size_t)i], 12);
+                if (!I->d_motion) HIP_OK(hipMalloc((void**)&I->d_motion, 2 * sizeof(wt_cam_table)), "Couldn't allocate device memory");
+                if (I->cams_fence_pending) { HIP_OK(hipStreamWaitEvent(I->stream, I->cams_fence, 0), "Couldn't run the kernel"); I->cams_fence_pending = false; }
+                if (!same_bits(I->motion_dev, motion_table)) {
+                    for (size_t c = 0; c < pieces; c++) {
+                        wt_cam_table piece;
+                        memcpy(piece.v, &motion_table[c * WT_CAM_TABLE_FLOATS], sizeof piece);
+                        if (wt_fast_launch_cams(&piece, I->d_motion + c * WT_CAM_TABLE_FLOATS, I->stream) != hipSuccess) die("Couldn't run the kernel");
+                    }
+                    I->motion_dev = motion_table;
+                }
+                I->cams_in_flight = true;
+                P.ss_times = I->d_motion; P.ss_disp = I->d_motion + 64;
+            }
         }
         P.rows = P.n_items / g.width;
         P.row_offset = (uint32_t)(g.id_offset / g.width);
@@ -669,7 +722,8 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
     const uint64_t tpt_nslots = 8u * (uint64_t)TPT_SLOTS_PER_XCC;
     const uint64_t tpt_slice = std::min<uint64_t>(TPT_SLICE_WORDS_MAX, ((uint64_t)I->tpt_pool_mb << 18) / tpt_nslots) & ~(uint64_t)63;
     const uint64_t tpt_cap = std::min<uint64_t>(tpt_slice > tpt_fixed ? ((tpt_slice - tpt_fixed) / tpt_per_node) & ~(uint64_t)63 : 0, 64960u);   /* whole blocks of 64 nodes; node ids are 16 bits */
-    const bool tail_wanted = (flags & F_DEEP) && !(flags & F_OCC) && !(I->variant & 16) && I->tpt_max != 0u && tpt_cap >= TPT_MIN_CAP;
+    /* (not for moving spheres: a tail node is traced by whichever lane takes it, which would need the owning pixel's time; with it goes the split of heavy tiles) */
+    const bool tail_wanted = (flags & F_DEEP) && !(flags & F_OCC) && !(I->variant & 16) && I->tpt_max != 0u && tpt_cap >= TPT_MIN_CAP && !moving;
     bool split = false;
     const unsigned split_max_lg = ss == 1 ? 4u : (ss == 2 ? 2u : (ss == 4 ? 1u : 0u));
     if (P.tiled) {
@@ -701,10 +755,10 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
             P.tile_order = rd >= 0 ? S.order[rd] : nullptr;
             /* the costs can only change when the camera, the depth or the scene did */
             sched_rebuild = !S.sig_valid || !same_raygen(g, S.sig) || S.sig_depth != I->depth || S.sig_scene != I->scene_generation ||
-                            S.sig_has_cams != have_cams || (have_cams && memcmp(&S.sig_cams, &cam_table, sizeof cam_table));
+                            S.sig_has_cams != have_cams || (have_cams && memcmp(&S.sig_cams, &cam_table, sizeof cam_table)) || !same_bits(S.sig_motion, motion_table);
             /* (costs that add up: the buffer starts at zero; the build that read it two frames ago has been waited for above) */
             if (P.cost_sum) HIP_OK(hipMemsetAsync(S.cost[wr], 0, (size_t)trows * tpr * 4, I->stream), "Couldn't run the kernel");
-            if (sched_rebuild) { S.sig_has_cams = have_cams; if (have_cams) S.sig_cams = cam_table; S.sig = g; S.sig_depth = I->depth; S.sig_scene = I->scene_generation; S.sig_valid = true; S.sig_age = 0; }
+            if (sched_rebuild) { S.sig_motion = motion_table; S.sig_has_cams = have_cams; if (have_cams) S.sig_cams = cam_table; S.sig = g; S.sig_depth = I->depth; S.sig_scene = I->scene_generation; S.sig_valid = true; S.sig_age = 0; }
             /* Grid builds measure a tile by its wave's lifetime, which depends on the company it ran in: the order built
              * from the first (unsorted, often cold) frame is refined once from the first sorted one. */
             else if ((flags & F_GRID) && S.sig_age < 2) sched_rebuild = true;
@@ -719,6 +773,7 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
         (P.np == 0u || P.lpt) && !(I->variant & 8192))
         flags |= F_SHAPE | (int)(P.ns << 9 | P.np << 12 | P.nl << 14);
     if (P.ss_lg) flags |= F_SS;      /* every fused flavour has a supersampled twin, whose epilogue resolves the samples */
+    if (P.ss_lg && P.ss_disp) flags |= F_MOVE;      /* ... and the twin (not the grid builds') a flavour whose sphere reads take the lane's scene time */
     I->last_trace_flags = flags;
     if (tail_wanted) {
         const uint64_t nslots = tpt_nslots, slice = tpt_slice, cap = tpt_cap;
@@ -1017,6 +1072,7 @@ void cl_wrap_release(cl_wrap* wrap) {
     if (I->d_tpt_flags) (void)hipFree(I->d_tpt_flags);
     if (I->d_tpt_jump) (void)hipFree(I->d_tpt_jump);
     if (I->d_cams) (void)hipFree(I->d_cams);
+    if (I->d_motion) (void)hipFree(I->d_motion);
     if (I->cams_fence) (void)hipEventDestroy(I->cams_fence);
     for (uint32_t* q : {I->d_grid_start, I->d_grid_items, I->d_grid_box}) if (q) (void)hipFree(q);
     if (I->d_grid_geom) (void)hipFree(I->d_grid_geom);
@@ -1051,7 +1107,7 @@ void clw_ext_sync(cl_wrap* wrap) { Impl* I = impl_of(wrap); use_device(I); finis
 void clw_ext_set_stream(cl_wrap* wrap, void* hip_stream) {
     Impl* I = impl_of(wrap);
     hipStream_t next = hip_stream ? (hipStream_t)hip_stream : I->own_stream;
-    if (next != I->stream && I->cams_in_flight) {   /* the sample-camera table was written / is read in the old stream's order: fence it */
+    if (next != I->stream && I->cams_in_flight) {   /* the sample-camera / moving-sphere tables were written / are read in the old stream's order: fence them */
         use_device(I);
         if (!I->cams_fence) HIP_OK(hipEventCreateWithFlags(&I->cams_fence, hipEventDisableTiming), "Couldn't create a timing event");
         HIP_OK(hipEventRecord(I->cams_fence, I->stream), "Couldn't run the kernel");
@@ -1138,6 +1194,25 @@ uint32_t clw_ext_get_sample_cameras(const cl_wrap* wrap, clw_sample_camera* out,
     const Impl* I = impl_of(wrap);
     const uint32_t n = (uint32_t)I->cams_used.size();
     if (out && n && cap >= n) memcpy(out, I->cams_used.data(), (size_t)n * sizeof(clw_sample_camera));
+    return n;
+}
+void clw_ext_set_sphere_motion(cl_wrap* wrap, const float* disp, uint32_t ns, const float* times, uint32_t count) {
+    Impl* I = impl_of(wrap);
+    bool any = false;
+    if (disp) for (size_t i = 0; i < 3 * (size_t)ns; i++) {
+        if (!std::isfinite(disp[i])) die("Moving spheres: displacement %u of sphere %u is not finite", (unsigned)(i % 3), (unsigned)(i / 3));
+        any |= disp[i] != 0.0f;
+    }
+    if (times) for (uint32_t k = 0; k < count; k++) if (!std::isfinite(times[k])) die("Moving spheres: sample time %u is not finite", (unsigned)k);
+    I->motion_disp.clear(); I->motion_times.clear(); I->motion_explicit_times = false;
+    if (!any) return;                            /* no table, or nothing moves: the plain launch */
+    I->motion_disp.assign(disp, disp + 3 * (size_t)ns);
+    if (times) { I->motion_times.assign(times, times + count); I->motion_explicit_times = true; }   /* a count that is not n * n, 0 included, is refused at the launch */
+}
+uint32_t clw_ext_get_sample_times(const cl_wrap* wrap, float* out, uint32_t cap) {
+    const Impl* I = impl_of(wrap);
+    const uint32_t n = (uint32_t)I->times_used.size();
+    if (out && n && cap >= n) memcpy(out, I->times_used.data(), (size_t)n * sizeof(float));
     return n;
 }
 void clw_ext_set_lens(cl_wrap* wrap, float aperture, float focus) {

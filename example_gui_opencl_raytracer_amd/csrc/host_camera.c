@@ -117,3 +117,24 @@ int clw_host_shutter_cameras(const clw_camera* open, const clw_camera* close, ui
     }
     return 1;
 }
+
+/* ---- moving spheres (hip_wrap_ext.h: clw_ext_set_sphere_motion) --------------------------------------------------- */
+
+int clw_host_sample_times(uint32_t n, float* out) {
+    const int lg = sample_factor_lg(n);
+    if (!out || !lg) return 0;
+    for (uint32_t k = 0; k < n * n; k++) out[k] = ((float)sample_slot(k, lg) + 0.5f) / (float)(n * n);      /* exact */
+    return 1;
+}
+
+int clw_host_spheres_at(const void* rspheres, uint32_t ns, const float* disp, float t, void* out) {
+    if (ns && (!rspheres || !disp || !out)) return 0;
+    if (out != rspheres) memmove(out, rspheres, 96 * (size_t)ns);
+    for (uint32_t i = 0; i < ns; i++) {
+        float c[3];
+        memcpy(c, (const unsigned char*)out + 96 * (size_t)i, 12);
+        for (int a = 0; a < 3; a++) c[a] = fmaf(t, disp[3 * (size_t)i + a], c[a]);      /* one rounding, as the kernel's v_fma_f32 */
+        memcpy((unsigned char*)out + 96 * (size_t)i, c, 12);
+    }
+    return 1;
+}

@@ -5,7 +5,8 @@
  * What a segment ADDS to its path's radiance goes through two macros, so that the tree-parallel tail (whitted_tpt.inc) can record
  * the terms instead and add them later, in the reference's order:
  *   WT_HIT_COLOUR(c)      a light sphere seen / the skybox texel of a miss:  rgb = c * f + rgb
- *   WT_HIT_AMBIENT(cf, a) the ambient term of a hit (cf = colour x throughput): rgb = cf * a + rgb */
+ *   WT_HIT_AMBIENT(cf, a) the ambient term of a hit (cf = colour x throughput): rgb = cf * a + rgb
+ * Spheres are read through wt_sphere_at with WT_MOTION: the lane's own scene time in the per-lane loop, none in the tail (whitted_terms.inc). */
             cost++;
             if (COUNT) {
                 c_iter++;   /* lane-iterations; the first live lane books 64 per wave-iteration */
@@ -69,7 +70,7 @@
                         if (wt_grid_occluded(P, r, tl)) lit = false;
                     }
                     for (unsigned i = 0; !GRID && i < SH::ns(P); i++) {
-                        float4 s = wt_geom<GEOM_LDS>(P, sg, i);
+                        float4 s = wt_sphere_at<GEOM_LDS>(P, sg, i, WT_MOTION);
                         float t;
                         bool hit = wt_sphere(r, s, t);
                         if (hit && t <= tl && !(__float_as_uint(s.w) >> 31)) lit = false;
@@ -99,7 +100,7 @@
                     for (unsigned base = 0; base < SH::ns(P); base += 4u) {      /* four spheres at a time, see the light probe */
                         float4 s4[4]; float bq[4], Dq[4]; bool ok[4]; bool any = false;
 #pragma unroll
-                        for (int k = 0; k < 4; k++) s4[k] = wt_geom<GEOM_LDS>(P, sg, min(base + k, SH::ns(P) - 1u));
+                        for (int k = 0; k < 4; k++) s4[k] = wt_sphere_at<GEOM_LDS>(P, sg, min(base + k, SH::ns(P) - 1u), WT_MOTION);
 #pragma unroll
                         for (int k = 0; k < 4; k++) {
                             const sph_pre pre = wt_sphere_pre(r.o, s4[k]);
@@ -135,7 +136,7 @@
                     prim = (unsigned)best;
                     textured = false;
                     if ((unsigned)best < SH::ns(P)) {
-                        float4 s = wt_geom<GEOM_LDS>(P, sg, (unsigned)best);
+                        float4 s = wt_sphere_at<GEOM_LDS>(P, sg, (unsigned)best, WT_MOTION);
                         nrm = wt_normalize(ip - mk3(s.x, s.y, s.z));
                     } else {
                         unsigned pi = (unsigned)best - SH::ns(P);

@@ -12,14 +12,15 @@ static hipError_t wt_launch_one(const whitted_params* P, unsigned grid, size_t d
 
 extern "C" hipError_t WT_LAUNCH_TRACE(const whitted_params* P, int flags, unsigned grid, size_t dyn_lds,
                                       hipStream_t s) {
-    using WT_NS::WT_F_SS;
+    using WT_NS::WT_F_SS; using WT_NS::WT_F_MOVE;
 #if !WT_STRICT
     using WT_NS::WT_F_GEOM_LDS; using WT_NS::WT_F_SHAPE;
     if (flags & WT_F_SHAPE) {
         /* the shaped flavour (wt_shape): exactly these counts are compiled -- 1..4 spheres, 0..2 planes, 3 lights; the shim asks for no other */
         switch (flags) {
 #define WT_SHAPE_CASE(ns, np) case WT_SHAPE_FLAGS(ns, np, 3): return wt_launch_one<WT_SHAPE_FLAGS(ns, np, 3)>(P, grid, dyn_lds, s); \
-                              case WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS: return wt_launch_one<WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS>(P, grid, dyn_lds, s);
+                              case WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS: return wt_launch_one<WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS>(P, grid, dyn_lds, s); \
+                              case WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS | WT_F_MOVE: return wt_launch_one<WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS | WT_F_MOVE>(P, grid, dyn_lds, s);
 #define WT_SHAPE_CASES(ns) WT_SHAPE_CASE(ns, 0) WT_SHAPE_CASE(ns, 1) WT_SHAPE_CASE(ns, 2)
             WT_SHAPE_CASES(1) WT_SHAPE_CASES(2) WT_SHAPE_CASES(3) WT_SHAPE_CASES(4)
 #undef WT_SHAPE_CASES
@@ -28,24 +29,27 @@ extern "C" hipError_t WT_LAUNCH_TRACE(const whitted_params* P, int flags, unsign
         return hipErrorInvalidValue;
     }
 #endif
-    switch (flags & (255 | WT_F_SS)) {
+    switch (flags & (255 | WT_F_SS | WT_F_MOVE)) {
 #define WT_CASE(F) case F: return wt_launch_one<F>(P, grid, dyn_lds, s);
 /* F and its supersampled twin (fused launches only: no twin for the ray-buffer flavours, bit 3) */
 #define WT_CASE2(F) WT_CASE(F) WT_CASE((F) | WT_F_SS)
-        WT_CASE2(0) WT_CASE2(1) WT_CASE2(2) WT_CASE2(3) WT_CASE2(4) WT_CASE2(5) WT_CASE2(6) WT_CASE2(7)
+/* ... and the twin's moving-spheres flavour (not the grid builds) */
+#define WT_CASE3(F) WT_CASE2(F) WT_CASE((F) | WT_F_SS | WT_F_MOVE)
+        WT_CASE3(0) WT_CASE3(1) WT_CASE3(2) WT_CASE3(3) WT_CASE3(4) WT_CASE3(5) WT_CASE3(6) WT_CASE3(7)
         WT_CASE(8) WT_CASE(9) WT_CASE(10) WT_CASE(11) WT_CASE(12) WT_CASE(13) WT_CASE(14) WT_CASE(15)
         /* grid builds: geometry from global memory only (bit 2 clear) */
         WT_CASE2(16) WT_CASE2(17) WT_CASE2(18) WT_CASE2(19) WT_CASE(24) WT_CASE(25) WT_CASE(26) WT_CASE(27)
         /* deep builds whose depth is <= 8 (bit 6) / <= 16 (bit 7): a smaller scratch part of the DFS stack (not the counting builds) */
-        WT_CASE2(66) WT_CASE2(70) WT_CASE(74) WT_CASE(78) WT_CASE2(82) WT_CASE(90)
-        WT_CASE2(130) WT_CASE2(134) WT_CASE(138) WT_CASE(142) WT_CASE2(146) WT_CASE(154)
+        WT_CASE3(66) WT_CASE3(70) WT_CASE(74) WT_CASE(78) WT_CASE2(82) WT_CASE(90)
+        WT_CASE3(130) WT_CASE3(134) WT_CASE(138) WT_CASE(142) WT_CASE2(146) WT_CASE(154)
 #if !WT_STRICT
-        WT_CASE2(98) WT_CASE2(102) WT_CASE(106) WT_CASE(110) WT_CASE2(114) WT_CASE(122)
-        WT_CASE2(162) WT_CASE2(166) WT_CASE(170) WT_CASE(174) WT_CASE2(178) WT_CASE(186)
+        WT_CASE3(98) WT_CASE3(102) WT_CASE(106) WT_CASE(110) WT_CASE2(114) WT_CASE(122)
+        WT_CASE3(162) WT_CASE3(166) WT_CASE(170) WT_CASE(174) WT_CASE2(178) WT_CASE(186)
         /* deep builds, high-occupancy flavour (bit 5 on top of bit 1) */
-        WT_CASE2(34) WT_CASE2(35) WT_CASE2(38) WT_CASE2(39) WT_CASE(42) WT_CASE(43) WT_CASE(46) WT_CASE(47)
+        WT_CASE3(34) WT_CASE3(35) WT_CASE3(38) WT_CASE3(39) WT_CASE(42) WT_CASE(43) WT_CASE(46) WT_CASE(47)
         WT_CASE2(50) WT_CASE2(51) WT_CASE(58) WT_CASE(59)
 #endif
+#undef WT_CASE3
 #undef WT_CASE2
 #undef WT_CASE
     }

@@ -12,6 +12,7 @@
  *   geom[ns + 2np + 2nl + c*np + p]  (only if lpt != 0) light chunk c, plane p: { mu0, mu1, mu2, 1/|n| } -- the signed
  *                                            distance of the three lights of the chunk from the plane, less radius and
  *                                            slack (scene_prep.c): lets a wave skip plane tests no shadow ray can fail
+ *   (LDS copy only) [geom_f4 + i] sphere i : { dx, dy, dz, 0 } of a moving launch's displacement table (ss_disp below), staged behind the stream
  *   ptex[2p], ptex[2p+1]          plane p  : { b0x, b0y, b0z, texture_scale }, { b1x, b1y, b1z, bits(texture_id) }
  *                                            (tangent basis of reference primitives.cl:226-236)
  * Materials stay in the raw arrays and are gathered for the winning primitive only.
@@ -95,6 +96,12 @@ typedef struct {
      * 12 per LANE of a tile's wavefront -- { im_corner, origin, up, right } of the camera of sub-sample ((lane & 7) mod n, (lane >> 3) mod n);
      * w_factor, h_factor, width, height stay the launch's (16-byte aligned) */
     const float* ss_cams;
+    /* moving spheres of a supersampled launch (NULL = the scene stands still): ss_disp = float4 { dx, dy, dz, 0 } per sphere, the movement of
+     * its centre while the shutter is open; ss_times = 64 floats, the scene time of the sub-sample each LANE of a tile's wavefront traces (laid
+     * out like ss_cams).  A lane sees sphere i at fmaf(t_lane, d_i, c_i) per component (wt_sphere_at); radius, planes and lights stand still.
+     * Small non-grid scenes only (ns <= 256); LDS-geometry kernels stage the table behind the prepared stream (geom_f4 + ns <= 1024 float4) */
+    const float* ss_disp;
+    const float* ss_times;
 } whitted_params;
 
 #define WT_CAM_TABLE_FLOATS (64 * 12)

@@ -94,7 +94,7 @@
 #pragma unroll
                     for (int k = 0; k < LCH; k++) anyw |= needk[k];
                     if (__builtin_amdgcn_ballot_w64(anyw) != 0)
-                        wt_light_vis<GEOM_LDS, LCH>(P, sg, g_pln, g_lgt, lb, ip, needk, LCH == 3 ? lb / 3u : ~0u, known, opu);
+                        wt_light_vis<GEOM_LDS, LCH>(P, sg, g_pln, g_lgt, lb, ip, needk, LCH == 3 ? lb / 3u : ~0u, known, opu, WT_MOTION);
                     if (COUNT) {
 #pragma unroll
                         for (int k = 0; k < LCH; k++) if (known[k]) c_known++;
@@ -106,7 +106,8 @@
                 }
                 /* which spheres can this wave's rays of the batch meet at all (wt_sphere_candidates)?  Asked BEFORE the samples exist: fewer registers are live here */
                 unsigned long long cand = ~0ull;
-                if (SPHCULL && P.ns >= WT_CULL_MIN_SPHERES && P.ns <= 64u) {                 /* wave-uniform: C3's 64 spheres, not render.map's 4 */
+                /* (not in a moving launch: the choice is made per WAVE from centres that are then per-lane values; testing every sphere gives the same factors) */
+                if (SPHCULL && !WT_MOTION.on && P.ns >= WT_CULL_MIN_SPHERES && P.ns <= 64u) {  /* wave-uniform: C3's 64 spheres, not render.map's 4 */
                     bool part = false;
 #pragma unroll
                     for (int k = 0; k < LCH; k++) part |= needk[k] && !known[k];
@@ -147,7 +148,7 @@
                 WT_STAMP(WT_ST_LIGHTS);
                 /* (not in the high-occupancy deep flavour: its register cap turns the table's four values into spills, +3 % at C3) */
                 if (any_sample)
-                    wt_shadow_batch<GEOM_LDS, NR, !(DEEP && wt_cfg<FLAGS>::occ), SPHCULL, FLAGS>(P, sg, g_pln, ip, rd, tl, a4, a2, op, LCH == 3 ? lb / 3u : ~0u, dl, cand);
+                    wt_shadow_batch<GEOM_LDS, NR, !(DEEP && wt_cfg<FLAGS>::occ), SPHCULL, FLAGS>(P, sg, g_pln, ip, rd, tl, a4, a2, op, LCH == 3 ? lb / 3u : ~0u, dl, cand, WT_MOTION);
                 WT_STAMP(WT_ST_SHADOW);
 #pragma unroll
                 for (int k = 0; k < LCH; k++) {

@@ -7,6 +7,8 @@
 #undef WT_SHADE_ADD
 #undef WT_BOUNCE_PUSH
 #undef WT_BOUNCE_LAST
+#undef WT_MOTION
+#define WT_MOTION mv        /* the scene time spheres are read at (wt_sphere_at): the lane's own; the tail, which moving launches do not enter, reads them unmoved */
 #define WT_HIT_COLOUR(c) rgb = wt_madd3((c), f, rgb)
 #define WT_HIT_AMBIENT(cf, a) rgb = wt_madd3((cf), (a), rgb)
 #define WT_SHADE_ADD(li, l1, soft, dl, spec, diff) rgb = wt_light_add(rgb, (l1), (soft), (dl), (spec), (diff), ks, kd)

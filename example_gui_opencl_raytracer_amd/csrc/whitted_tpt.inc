@@ -200,6 +200,8 @@
 #undef WT_BOUNCE_PUSH
 #undef WT_BOUNCE_LAST
 #define WT_BOUNCE_LAST false            /* the tail runs the whole bounce on every node, as before */
+#undef WT_MOTION
+#define WT_MOTION (wt_motion{false, 0.0f, 0u})   /* moving launches never enter the tail (the shim sets tpt_cap = 0): a node is traced by whichever lane takes it */
 #define WT_HIT_COLOUR(c) t_col = (c)
 #define WT_HIT_AMBIENT(cf, a) do { t_col = (cf); t_ambk = (a); } while (0)
 #define WT_BOUNCE_PUSH(rec) do { t_pushed = true; _Pragma("unroll") for (int w_ = 0; w_ < WT_REC; w_++) t_prec[w_] = (rec)[w_]; } while (0)
@@ -406,6 +408,8 @@
 
     T_PHASE(3);
     /* ---- D: shading, one hit per lane; the lights' factors go where the replay will look for them: at the hit's position -------------- */
+#undef WT_MOTION
+#define WT_MOTION (wt_motion{false, 0.0f, 0u})
 #undef WT_SHADE_ADD
 #if WT_STRICT
 #define WT_SHADE_ADD(li, l1, soft, dl, spec, diff) do { const unsigned w_ = T_W + 4u * (li); (void)(l1); \

@@ -657,6 +657,22 @@ __device__ __forceinline__ float4 wt_geom(const whitted_params& P, const float4*
     if (GEOM_LDS) return sg[i];
     return ((const float4*)P.geom)[i];
 }
+/* ---- moving spheres (whitted_params.h: ss_disp, ss_times): EVERY read of a sphere's float4 goes through wt_sphere_at, which returns the sphere as
+ * the lane's sub-sample sees it -- centre fmaf(t, d_i, c_i) per component, one rounding in both builds (the host's clw_host_spheres_at does the
+ * same), radius and the transparency bit untouched.  `on` is a compile-time constant: true in the WT_F_MOVE flavours only, false in every other kernel,
+ * whose code is then the plain fetch it was; the displacement is an LDS broadcast read behind the staged geometry (or a uniform global load).
+ * A moving sphere's centre is a per-lane value: every ballot around a sphere test is an early-out over per-lane predicates (no lane's result
+ * depends on what another lane's test gave), and the one wave-level decision that reads centres, wt_sphere_candidates, is skipped. */
+struct wt_motion { bool on; float t; unsigned off; };   /* off: float4 index of the staged table in the LDS stream (= geom_f4) */
+template <bool GEOM_LDS>
+__device__ __forceinline__ float4 wt_sphere_at(const whitted_params& P, const float4* sg, unsigned i, const wt_motion& mv) {
+    float4 s = wt_geom<GEOM_LDS>(P, sg, i);
+    if (mv.on) {
+        const float4 dd = GEOM_LDS ? sg[mv.off + i] : ((const float4*)P.ss_disp)[i];
+        s.x = __builtin_fmaf(mv.t, dd.x, s.x); s.y = __builtin_fmaf(mv.t, dd.y, s.y); s.z = __builtin_fmaf(mv.t, dd.z, s.z);
+    }
+    return s;
+}
 
 
 enum { WT_F_COUNT = 1, WT_F_DEEP = 2, WT_F_GEOM_LDS = 4, WT_F_RAYS = 8, WT_F_GRID = 16,
@@ -664,7 +680,9 @@ enum { WT_F_COUNT = 1, WT_F_DEEP = 2, WT_F_GEOM_LDS = 4, WT_F_RAYS = 8, WT_F_GRI
        WT_F_D8 = 64, WT_F_D16 = 128 /* deep builds only: the launch's depth is <= 8 / <= 16, so the DFS stack holds at most 7 / 15 parents and the
                                        part of it kept in scratch is sized for that instead of for CLW_MAX_DEPTH */,
        WT_F_SHAPE = 256 /* shallow fast LDS-geometry build only: the scene's counts are compiled in (wt_shape) */,
-       WT_F_SS = 1 << 17 /* n x n supersampling, fused tiled launches only (bits 9-16: the counts of WT_SHAPE_FLAGS) */ };
+       WT_F_SS = 1 << 17 /* n x n supersampling, fused tiled launches only (bits 9-16: the counts of WT_SHAPE_FLAGS) */,
+       WT_F_MOVE = 1 << 18 /* on top of WT_F_SS, not the grid builds: moving spheres (wt_sphere_at) -- a flavour of its own, so that the plain
+                              supersampled kernels are the code they were */ };
 
 /* ---- the scene's primitive counts: launch parameters, or compile-time constants (FLAGS & WT_F_SHAPE) ----------------------------
  * A small scene's loops over 4 spheres, 2 planes and 3 lights are mostly loop control, guards and selects around little arithmetic.
@@ -1039,7 +1057,8 @@ __device__ __forceinline__ void wt_grid_shadow_pair(const whitted_params& P, f3 
 #endif
 template <bool GEOM_LDS, int LCH>
 __device__ __forceinline__ void wt_light_vis(const whitted_params& P, const float4* sg, unsigned g_pln, unsigned g_lgt, unsigned lb,
-                                             f3 ip, const bool (&want)[LCH], unsigned chunk, bool (&known)[LCH], float (&opu)[LCH]) {
+                                             f3 ip, const bool (&want)[LCH], unsigned chunk, bool (&known)[LCH], float (&opu)[LCH],
+                                             const wt_motion mv = wt_motion{false, 0.0f, 0u}) {
     f3 lv[LCH];
     float rs[LCH], dl[LCH], rho[LCH], sa[LCH], ca2[LCH];
     bool live[LCH], unk[LCH], blk[LCH], pok[LCH];
@@ -1082,7 +1101,7 @@ __device__ __forceinline__ void wt_light_vis(const whitted_params& P, const floa
         }
     }
     for (unsigned i = 0; i < P.ns; i++) {
-        const float4 s4 = wt_geom<GEOM_LDS>(P, sg, i);
+        const float4 s4 = wt_sphere_at<GEOM_LDS>(P, sg, i, mv);
         const f3 w = mk3(s4.x, s4.y, s4.z) - ip;                 /* = -(from - centre) of primitives.cl:173, exactly */
         const float ww = dot3(w, w), R2 = fabsf(s4.w);
         const float slack = __builtin_fmaf(1e-5f, ww, 1e-30f);
@@ -1158,7 +1177,7 @@ __device__ __forceinline__ unsigned long long wt_sphere_candidates(const whitted
     if (!(rho < 1e30f)) return ~0ull;                             /* a NaN or infinite shading point: everything is tested */
     const unsigned nact = (unsigned)__builtin_popcountll(act), rank = (unsigned)__builtin_popcountll(act & ((1ull << lane) - 1ull));
     for (unsigned i = rank; i < P.ns; i += nact) {                /* the spheres dealt over the active lanes */
-        const float4 s = wt_geom<GEOM_LDS>(P, sg, i);
+        const float4 s = wt_geom<GEOM_LDS>(P, sg, i);             /* the UNMOVED centre, not wt_sphere_at: one mask serves every lane, so a launch with sphere motion must not call this (whitted_shade.inc asks !WT_MOTION.on first) */
         const f3 c = mk3(s.x, s.y, s.z);
         const float R = sqrtf(fabsf(s.w));
         bool near_ = false;
@@ -1198,7 +1217,8 @@ template <bool GEOM_LDS, int NR, bool CULL, bool MASKED = false, int SHF = 0>
 __device__ __forceinline__ void wt_shadow_batch(const whitted_params& P, const float4* sg, unsigned g_pln, f3 ip,
                                                 const f3 (&rd)[NR], const float (&tl)[NR], const float (&a4)[NR],
                                                 const float (&a2)[NR], float (&op)[NR], unsigned chunk,
-                                                const float (&dlc)[NR / WT_SOFT], const unsigned long long cand = ~0ull) {
+                                                const float (&dlc)[NR / WT_SOFT], const unsigned long long cand = ~0ull,
+                                                const wt_motion mv = wt_motion{false, 0.0f, 0u}) {
     /* `cand` (wave-uniform; scenes of <= 64 spheres): bit i clear = no ray of this batch, from any lane, can meet sphere i in front of its
      * sample (wt_sphere_candidates): the sphere is not tested.  Which spheres are tested never changes a factor: a skipped test could only fail. */
     typedef wt_shape<SHF> SH;                                /* SHF: the caller's FLAGS (compile-time counts, wt_shape) */
@@ -1213,7 +1233,7 @@ __device__ __forceinline__ void wt_shadow_batch(const whitted_params& P, const f
             for (int q = 0; q < NR; q++) live |= __float_as_uint(op[q]);
             if (__builtin_amdgcn_ballot_w64(live != 0u) == 0) break;
         }
-        const float4 s = wt_geom<GEOM_LDS>(P, sg, i);
+        const float4 s = wt_sphere_at<GEOM_LDS>(P, sg, i, mv);
         const sph_pre pre = wt_shadow_pre(ip, s);
         const float through = (__float_as_uint(s.w) >> 31) ? P.through : 0.0f;   /* x0.8 or blocked */
         float bq[NR], Dq[NR];
@@ -1237,7 +1257,7 @@ __device__ __forceinline__ void wt_shadow_batch(const whitted_params& P, const f
             for (int q = 0; q < NR; q++) live |= __float_as_uint(op[q]);
             if (__builtin_amdgcn_ballot_w64(live != 0u) == 0) break;
         }
-        const float4 s = wt_geom<GEOM_LDS>(P, sg, i);
+        const float4 s = wt_sphere_at<GEOM_LDS>(P, sg, i, mv);
         const sph_pre pre = wt_shadow_pre(ip, s);
         const float through = (__float_as_uint(s.w) >> 31) ? P.through : 0.0f;   /* x0.8 or blocked */
         float bq[NR], Dq[NR];
@@ -1287,8 +1307,11 @@ __device__ __forceinline__ void wt_shadow_batch(const whitted_params& P, const f
 }
 
 /* The prepared geometry stream of a small scene (whitted_params.h), staged in LDS once per workgroup */
+/* (moving launches -- the WT_F_MOVE flavours -- stage the displacement table behind it: wt_sphere_at) */
+template <bool MOVE = false>
 __device__ __forceinline__ void wt_stage_scene(const whitted_params& P, float4* s_geom, unsigned tid, unsigned nthreads) {
     for (unsigned i = tid; i < P.geom_f4; i += nthreads) s_geom[i] = ((const float4*)P.geom)[i];
+    if (MOVE) for (unsigned i = tid; i < P.ns; i += nthreads) s_geom[P.geom_f4 + i] = ((const float4*)P.ss_disp)[i];
     __syncthreads();
 }
 
@@ -1357,6 +1380,7 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
     constexpr bool FROM_RAYS = (FLAGS & WT_F_RAYS) != 0;
     constexpr bool GRID = (FLAGS & WT_F_GRID) != 0;     /* spheres through the uniform grid (big scenes) */
     constexpr bool SS = (FLAGS & WT_F_SS) != 0;         /* supersampled launch: the epilogue resolves n x n samples per stored pixel */
+    constexpr bool MOVE = SS && !GRID && (FLAGS & WT_F_MOVE) != 0;   /* moving spheres: every sphere read takes the lane's scene time */
     constexpr bool UNIT_CT = !WT_STRICT && GEOM_LDS && !FROM_RAYS && !GRID;   /* see whitted_hit.inc */
     /* The lights' visibility classes (wt_light_vis) are compiled into the STRICT build's small-scene kernels only: there the samples they
      * save cost an fp64 product and a libm sin / cos each (-13 % at C2).  Measured for the fast build, whose samples are two hardware
@@ -1384,7 +1408,7 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
 #endif
 
     /* ---- stage the prepared geometry in LDS ------------------------------------------------------------------- */
-    if (GEOM_LDS) wt_stage_scene(P, s_geom, threadIdx.x, WT_BLOCK);
+    if (GEOM_LDS) wt_stage_scene<MOVE>(P, s_geom, threadIdx.x, WT_BLOCK);
     const float4* sg = s_geom;
 #if WT_TIMELINE
     const unsigned long long tl_staged = __builtin_amdgcn_s_memrealtime();
@@ -1471,6 +1495,10 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
             o = mk3(P.origin[0], P.origin[1], P.origin[2]);
         }
     }
+    /* moving spheres (the WT_F_MOVE flavours: supersampled, and not the grid builds, whose cell lists are built for one set of centres):
+     * the lane's sub-sample fixes its scene time, one coalesced load per wave */
+    wt_motion mv = {false, 0.0f, 0u};
+    if (MOVE) { mv.on = true; mv.t = P.ss_times[lane]; mv.off = P.geom_f4; }
     float n1 = WT_DEFAULT_N, f = 1.0f;
     int sp = 0;                         /* parents on the stack */
     unsigned rng = (unsigned)gid;       /* raytracing.cl:33: id 0 is the xorshift fixed point */
@@ -1871,6 +1899,7 @@ __global__ void __launch_bounds__(64) wt_unit_scene(const whitted_params P, int 
     WT_STAMP_DECL
     constexpr bool COUNT = false, FROM_RAYS = false;    /* like the fused kernel: the test rows carry unit directions */
     unsigned cost = 0, c_iter = 0, c_witer = 0, c_probe = 0, c_seg = 0, c_sky = 0, c_tex = 0;
+    const wt_motion mv = {false, 0.0f, 0u};             /* the unit-test kernel sees the scene as it stands */
     (void)lane; (void)c_iter; (void)c_witer; (void)c_probe; (void)c_seg; (void)c_sky; (void)c_tex;
     if (op == WT_US_HIT) {
         f3 o = mk3(a[0], a[1], a[2]), d = mk3(a[3], a[4], a[5]), rgb = mk3(0, 0, 0);

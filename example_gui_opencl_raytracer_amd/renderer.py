@@ -17,6 +17,9 @@ return W*H entries, and strips compose as before.
 ``lens=(aperture, focus)`` (with ``supersample`` > 1): the n x n samples of a pixel look through n x n points of a thin lens focused at
 distance ``focus`` (clw_ext_set_lens); ``set_sample_cameras`` hands the kernel any table of n x n cameras instead, e.g.
 ``api.shutter_cameras`` for camera motion blur.
+
+``motion=disp`` (float32 [spheres, 3], with ``supersample`` > 1): object motion blur -- sphere i moves by ``disp[i]`` while the shutter is
+open and every sample sees the scene at its own time (clw_ext_set_sphere_motion; ``set_sphere_motion(disp, times)`` to change it).
 """
 from __future__ import annotations
 
@@ -44,7 +47,7 @@ class Renderer:
                  depth: int = 15, strict: bool = False, fuse: bool = True, first_row: int = 0,
                  rows: int | None = None, bands: tuple[int, int] | None = None, framebuffer_ptr: int | None = None, wide_counts: bool | None = None,
                  texture_paths=None, skybox_path=None, supersample: int = 1,
-                 lens: tuple[float, float] | None = None):
+                 lens: tuple[float, float] | None = None, motion=None):
         self.width, self.height = width, height
         self.first_row = first_row
         self.rows = height - first_row if rows is None else rows
@@ -62,6 +65,8 @@ class Renderer:
             w.set_supersample(supersample)
         if lens is not None:      # (aperture, focus): depth of field from the samples of a pixel
             w.set_lens(*lens)
+        if motion is not None:    # float32 [spheres, 3]: how far each sphere moves while the shutter is open
+            w.set_sphere_motion(motion)
         if bands is not None:
             w.set_row_bands(*bands)
 
@@ -109,6 +114,11 @@ class Renderer:
     def set_sample_cameras(self, cams) -> None:
         """float32 [n*n, 12]: sample k = sy * n + sx of every pixel looks through camera k (None = the launch camera); replaces a lens."""
         self.w.set_sample_cameras(cams)
+
+    def set_sphere_motion(self, disp, times=None) -> None:
+        """float32 [spheres, 3]: sample k of every pixel sees sphere i at centre + times[k] * disp[i] (None = the shutter times of
+        api.sample_times); disp None / empty / all zero = the scene stands still."""
+        self.w.set_sphere_motion(disp, times)
 
     def look(self, origin, look, fov=90.0, focal=1.0):
         cam = api.perspective(origin, look, fov, focal, self.width, self.height)

@@ -136,6 +136,27 @@ uint32_t clw_ext_get_sample_cameras(const cl_wrap* wrap, clw_sample_camera* out,
  * finite, focus <= 0 or not finite; at launch, aperture > 0 with supersampling factor 1 (a lens needs samples). */
 void clw_ext_set_lens(cl_wrap* wrap, float aperture, float focus);
 
+/* Moving spheres (object motion blur): with supersampling factor n in {2, 4, 8}, a displacement table disp[0 .. ns) -- three floats per
+ * sphere, the movement of its centre while the shutter is open -- and sample times t[0 .. n*n) in effect, let S(t) be the scene whose
+ * sphere i has centre fmaf(t, disp[i], c[i]) per component (float32, one rounding; clw_host_spheres_at), radius, material, planes and
+ * lights unchanged.  The sample at virtual pixel (vx, vy), k = (vy mod n) * n + (vx mod n), is pixel (vx, vy) of the 1-sample render of
+ * the n*W x n*H frame of S(t[k]) -- through the launch camera, or through cams[k] when a table of sample cameras or a lens is in
+ * effect; w_factor / n, h_factor / n, ids (RNG seeds), clamp, resolve and pack as plain supersampling.  times == NULL: the times of
+ * clw_host_sample_times for the factor in effect at the launch (`count` is then ignored) -- the clock of clw_host_shutter_cameras, so a
+ * sphere and a shutter-blurred camera move together.  Both arrays are copied.  disp == NULL or ns == 0 clears the table, and a table
+ * whose entries are all zero IS no table: frame, kernel flavour, tile costs and counters are those of the plain launch.
+ * Moving launches of deep traces run without the tree-parallel tail and without splitting heavy tiles (a tail node is traced by
+ * whichever lane takes it, which would need the owning pixel's time): same image, the tail's speed-up is lost.  The table is staged
+ * into LDS behind the prepared geometry and counts in the 16 KiB staging rule: a scene the table pushes over it runs the kernels that
+ * read the geometry (and the table) from global memory instead -- same image, another kernel family and its speed.
+ * Errors (print + exit(1)): at the call, a displacement or time that is not finite; at the next trace launch, a table with factor 1,
+ * count != n * n of the factor then in effect, ns != the scene's sphere count, a scene of more than 256 spheres (the uniform grid's
+ * cell lists are built for one set of centres), and whatever plain supersampling refuses. */
+void     clw_ext_set_sphere_motion(cl_wrap* wrap, const float* disp /* 3 per sphere */, uint32_t ns, const float* times /* NULL = shutter times */, uint32_t count);
+/* The sample times the LAST trace launch used, in sy * n + sx order -> their count (0 = the scene stood still); copies them if `cap`
+ * suffices. */
+uint32_t clw_ext_get_sample_times(const cl_wrap* wrap, float* out, uint32_t cap);
+
 /* Work counters of the trace kernel.  enable=1 selects the counting build of the kernel
  * for subsequent launches (slower); read returns and clears
  *   out[0] path segments  out[1] shadow rays  out[2] light probes  out[3] skybox fetches
@@ -244,6 +265,13 @@ int clw_host_lens_cameras(const clw_camera* base, float aperture, float focus, u
  * looks through the camera at time t = (j + 1/2) / n^2, j as above, each of the four vectors a + (b - a) t in float32 (a where
  * a == b).  Returns 0 when n is not 2, 4 or 8 or the two cameras differ in width, height, w_factor or h_factor. */
 int clw_host_shutter_cameras(const clw_camera* open, const clw_camera* close, uint32_t n, clw_sample_camera* out);
+/* Host helper: the default sample times of moving spheres, the ones clw_host_shutter_cameras uses: t[k] = (j + 1/2) / n^2, j = k with its
+ * 2 log2 n bits reversed (exact in float32).  Returns 0 when n is not 2, 4 or 8, else 1 and n * n times in sy * n + sx order. */
+int clw_host_sample_times(uint32_t n, float* out);
+/* Host helper: THE definition of the moved scene S(t): copies the ns 96-byte rsphere records to `out` and replaces each centre (the
+ * first three floats) by fmaf(t, disp[3 i + a], c[a]); every other byte -- radius, material, padding -- is copied as it is.  `out` may
+ * be `rspheres` itself.  Returns 0 on a NULL argument (with ns > 0), else 1. */
+int clw_host_spheres_at(const void* rspheres, uint32_t ns, const float* disp, float t, void* out);
 
 /* Host helpers: PNG files without libpng (reference png_dump, src/cpu_ray.c:108-165, and the
  * decode step of cl_wrap_load_images).  Return 0 on success. */

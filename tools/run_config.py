@@ -1,9 +1,12 @@
 """Time one BASELINE.json configuration through the C-ABI (kernel-only, frames back to back) and print JSON.
-   python tools/run_config.py c2|c3|c4|c5strip|ref800 [--strict 1] [--frames N] [--variant V] [--depth D] [--size WxH] [--supersample N] [--aperture A --focus F | --copies]
+   python tools/run_config.py c2|c3|c4|c5strip|ref800 [--strict 1] [--frames N] [--variant V] [--depth D] [--size WxH] [--supersample N] [--aperture A --focus F | --copies] [--motion move|equal] [--no-tail]
    --supersample N: n x n samples per pixel resolved in the kernel (the frame stays WxH); --size: another frame size for the configuration's
    scene and camera -- e.g. the n*W x n*H frame a supersampled launch traces, to time the same work without the resolve.
    --aperture A --focus F: a thin lens over the samples (clw_ext_set_lens); --copies: an explicit table of n*n copies of the launch camera
    (clw_ext_set_sample_cameras) -- the plain supersampled image through the table path, to time the mechanism alone.
+   --motion move: every third sphere of the scene moves by (0.5, 0, -0.3) while the shutter is open (clw_ext_set_sphere_motion); --motion equal:
+   the same table with every sample time 0.5 -- the per-test fma and table read without the extra divergence; --no-tail: the tree-parallel tail
+   off (clw_ext_set_tpt), as a moving deep launch runs.
    --repeats R: the N-frame loop R times (0 = until 50 ms have been timed, as bench.py --full does), median / min / max of the repeats."""
 import argparse, json, math, os, statistics, sys, time
 import numpy as np
@@ -26,6 +29,8 @@ ap.add_argument("--repeats", type=int, default=1)
 ap.add_argument("--aperture", type=float, default=0.0)
 ap.add_argument("--focus", type=float, default=1.0)
 ap.add_argument("--copies", action="store_true")
+ap.add_argument("--motion", choices=["move", "equal"], default=None)
+ap.add_argument("--no-tail", action="store_true")
 a = ap.parse_args()
 tex, sky = textures.texture_layers(), textures.skybox_cross(4096)
 cam = pkg.CAMERA_RAYPNG
@@ -57,6 +62,12 @@ if a.aperture:
     r.w.set_lens(a.aperture, a.focus)
 elif a.copies:
     r.set_sample_cameras(np.tile(np.concatenate([np.asarray(v, np.float32) for v in (camera.im_corner, camera.origin, camera.up, camera.right)]), (a.supersample ** 2, 1)))
+if a.motion:
+    disp = np.zeros((len(sc.spheres), 3), np.float32)
+    disp[1::3] = (0.5, 0.0, -0.3)
+    r.set_sphere_motion(disp, np.full(a.supersample ** 2, 0.5, np.float32) if a.motion == "equal" else None)
+if a.no_tail:
+    r.w.set_tpt(max_lanes=0)
 r.render(readback=False); r.render(readback=False)
 r.w.enable_counters(1); r.render(readback=False); c = r.w.read_counters(); r.w.enable_counters(0)
 r.w.set_async(1)
@@ -77,7 +88,7 @@ r.w.set_async(0)
 img = r.render()
 rays = c["segments"] + c["shadow_rays"]
 px = r.pixels
-print(json.dumps(dict(config=a.config, frame=f"{W}x{H}", pixels=px, depth=depth, strict=a.strict, variant=a.variant, supersample=a.supersample, aperture=a.aperture, focus=a.focus, copies=int(a.copies), kernel_ms=round(ms / n, 4),
+print(json.dumps(dict(config=a.config, frame=f"{W}x{H}", pixels=px, depth=depth, strict=a.strict, variant=a.variant, supersample=a.supersample, aperture=a.aperture, focus=a.focus, copies=int(a.copies), motion=a.motion, no_tail=int(a.no_tail), kernel_ms=round(ms / n, 4),
                       kernel_ms_min=round(min(kms), 4), kernel_ms_max=round(max(kms), 4), repeats=len(kms),
                       wall_ms_per_frame=round(wall * 1e3, 4), rays_per_px=round(rays / px, 3), Mrays_s=round(rays / (ms / n) / 1e3, 1),
                       lane_util=round(c["lane_iters"] / max(c["wave_iters_x64"], 1), 4), counters=c)), flush=True)
