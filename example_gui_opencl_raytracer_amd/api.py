@@ -41,6 +41,7 @@ SYMBOLS = [
     "clw_ext_set_supersample", "clw_ext_get_supersample",
     "clw_ext_set_sample_cameras", "clw_ext_get_sample_cameras", "clw_ext_set_lens", "clw_host_lens_cameras", "clw_host_shutter_cameras",
     "clw_ext_set_sphere_motion", "clw_ext_get_sample_times", "clw_host_sample_times", "clw_host_spheres_at",
+    "clw_ext_set_adaptive", "clw_ext_get_adaptive", "clw_ext_read_refine_mask", "clw_host_refine_mask",
 ]
 
 
@@ -139,6 +140,14 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         L.clw_host_sample_times.restype = C.c_int
         L.clw_host_spheres_at.argtypes = [vp, u32, vp, C.c_float, vp]
         L.clw_host_spheres_at.restype = C.c_int
+    if hasattr(L, "clw_ext_set_adaptive") or not os.environ.get("CLWRAP_LIB"):            # (an older A/B build may lack them)
+        L.clw_ext_set_adaptive.argtypes = [W, C.c_int]
+        L.clw_ext_get_adaptive.argtypes = [W]
+        L.clw_ext_get_adaptive.restype = C.c_int
+        L.clw_ext_read_refine_mask.argtypes = [W, vp, u32]
+        L.clw_ext_read_refine_mask.restype = u32
+        L.clw_host_refine_mask.argtypes = [vp, u32, u32, u32, C.c_int, vp]
+        L.clw_host_refine_mask.restype = C.c_int
     L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
     L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
     L.clw_ext_read_tile_costs.restype = u32
@@ -214,6 +223,20 @@ def spheres_at(spheres: np.ndarray, disp, t: float) -> np.ndarray:
     out = spheres.copy()
     if not load_library().clw_host_spheres_at(_ptr(spheres), len(spheres), _ptr(disp), float(t), _ptr(out)):
         raise ValueError("clw_host_spheres_at rejects these arguments")
+    return out
+
+
+def refine_mask(xrgb, width: int, rows: int, n: int, threshold: int) -> np.ndarray:
+    """clw_host_refine_mask: the blocks of b x b pixels (b = 8 / n) of a packed width x rows frame that adaptive supersampling refines at this
+    contrast threshold -> uint8 [ceil(rows / b), ceil(width / b)] of 0 / 1."""
+    xrgb = np.ascontiguousarray(xrgb, np.uint32).reshape(-1)
+    width, rows, n = int(width), int(rows), int(n)
+    if n not in (2, 4, 8) or width <= 0 or rows <= 0 or xrgb.size != width * rows:
+        raise ValueError("clw_host_refine_mask rejects these arguments (n in 2, 4, 8; a frame of width * rows pixels)")
+    b = 8 // n
+    out = np.zeros((-(-rows // b), -(-width // b)), np.uint8)
+    if not load_library().clw_host_refine_mask(_ptr(xrgb), width, rows, n, int(threshold), _ptr(out)):
+        raise ValueError("clw_host_refine_mask rejects these arguments (threshold in [0, 256])")
     return out
 
 
@@ -347,6 +370,17 @@ class ClWrap:
     def set_debug_rgb(self, ptr): self.L.clw_ext_set_debug_rgb(C.byref(self.w), C.c_void_p(ptr))
     def set_supersample(self, n): self.L.clw_ext_set_supersample(C.byref(self.w), int(n))
     def get_supersample(self): return int(self.L.clw_ext_get_supersample(C.byref(self.w)))
+
+    def set_adaptive(self, threshold): self.L.clw_ext_set_adaptive(C.byref(self.w), int(threshold))
+    def get_adaptive(self): return int(self.L.clw_ext_get_adaptive(C.byref(self.w)))
+
+    def read_refine_mask(self) -> np.ndarray:
+        """The block mask of the last trace launch if it was adaptive -> uint8 [blocks], row-major (empty = it was not)."""
+        n = self.L.clw_ext_read_refine_mask(C.byref(self.w), None, 0)
+        out = np.zeros(n, np.uint8)
+        if n:
+            self.L.clw_ext_read_refine_mask(C.byref(self.w), _ptr(out), n)
+        return out
 
     def set_sample_cameras(self, cams):
         """float32 [n*n, 12] ({im_corner, origin, up, right} per sample, sy * n + sx order), copied; None / empty = no table."""

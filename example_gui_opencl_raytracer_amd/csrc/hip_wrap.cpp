@@ -37,11 +37,12 @@ extern "C" hipError_t wt_strict_launch_unit(int, const float*, float*, unsigned,
 extern "C" hipError_t wt_fast_launch_unit_scene(const whitted_params*, int, int, const float*, float*, unsigned, unsigned, unsigned, size_t, hipStream_t);
 extern "C" hipError_t wt_strict_launch_unit_scene(const whitted_params*, int, int, const float*, float*, unsigned, unsigned, unsigned, size_t, hipStream_t);
 extern "C" hipError_t wt_fast_launch_cams(const wt_cam_table*, float*, hipStream_t);
+extern "C" hipError_t wt_fast_launch_classify(const unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned char*, unsigned*, unsigned*, unsigned, hipStream_t);
 extern "C" hipError_t wt_fast_launch_sched(const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
 
 namespace {
 
-enum { F_COUNT = 1, F_DEEP = 2, F_GEOM_LDS = 4, F_RAYS = 8, F_GRID = 16, F_OCC = 32, F_D8 = 64, F_D16 = 128, F_SHAPE = 256, F_SS = 1 << 17, F_MOVE = 1 << 18 }; /* = WT_F_* of whitted_trace.inc */
+enum { F_COUNT = 1, F_DEEP = 2, F_GEOM_LDS = 4, F_RAYS = 8, F_GRID = 16, F_OCC = 32, F_D8 = 64, F_D16 = 128, F_SHAPE = 256, F_SS = 1 << 17, F_MOVE = 1 << 18, F_LIST = 1 << 19 }; /* = WT_F_* of whitted_trace.inc */
 /* shallow fast launches of small LDS-geometry scenes run a kernel with the scene's counts compiled in (wt_shape of whitted_trace.inc): the
  * counts whitted_launch.inc instantiates -- 1..SHAPE_MAX_SPHERES spheres, 0..SHAPE_MAX_PLANES planes, SHAPE_LIGHTS lights */
 constexpr uint32_t SHAPE_MAX_SPHERES = 4, SHAPE_MAX_PLANES = 2, SHAPE_LIGHTS = 3;
@@ -157,17 +158,30 @@ struct Impl {
     uint32_t band_stride = 1, band_phase = 0;
     int supersample = 1;   /* n x n samples per pixel, resolved in the trace kernel (clw_ext_set_supersample / CLWRAP_SUPERSAMPLE): 1, 2, 4 or 8 */
     float* debug_rgb = nullptr;
+    /* adaptive supersampling (clw_ext_set_adaptive / CLWRAP_ADAPTIVE): a trace launch becomes a 1-sample base pass, the classifier
+     * (wt_refine_classify) and a supersampled pass over the blocks it listed, all three on the launch stream and none waited for.  The
+     * buffers follow the launch range and the factor; a change of stream fences them like the camera table (tables_fence). */
+    int adaptive = -1;            /* contrast threshold, 0..256; -1 = off */
+    struct Adaptive {
+        uint8_t* mask = nullptr; uint32_t* order = nullptr; uint32_t* count = nullptr;
+        uint32_t w = 0, rows = 0; int ss = 0;     /* output pixels of the range the buffers were sized for, and the factor */
+        uint32_t blocks = 0;                      /* blocks of the LAST trace launch when it was adaptive, else 0 (clw_ext_read_refine_mask) */
+        void free_all() {
+            for (void* q : {(void*)mask, (void*)order, (void*)count}) if (q) (void)hipFree(q);
+            mask = nullptr; order = nullptr; count = nullptr; w = rows = 0; ss = 0;
+        }
+    } adapt;
     /* per-sample cameras of supersampled launches (clw_ext_set_sample_cameras / clw_ext_set_lens: alternatives, the later call clears the
      * other).  The device copy is laid out per lane of a tile's wavefront (whitted_params.h: ss_cams) and is rewritten, only when it changed,
      * by a small kernel on the launch stream that carries the table as its argument: stream order keeps it behind every queued launch that
-     * reads the previous table, and no host memory has to outlive the call.  A change of stream (clw_ext_set_stream) records cams_fence on
+     * reads the previous table, and no host memory has to outlive the call.  A change of stream (clw_ext_set_stream) records tables_fence on
      * the old stream, which the next launch with a table waits for on the new one. */
     std::vector<clw_sample_camera> cams;         /* the explicit table, sy * n + sx order; empty = none */
     float aperture = 0.0f, focus = 1.0f;         /* thin lens: the table is derived at every launch from the latched camera; aperture 0 = pinhole */
     std::vector<clw_sample_camera> cams_used;    /* the table of the latest trace launch (clw_ext_get_sample_cameras) */
     float* d_cams = nullptr;
     wt_cam_table cams_dev{}; bool cams_dev_valid = false;   /* what d_cams holds once the stream gets there */
-    hipEvent_t cams_fence = nullptr; bool cams_fence_pending = false, cams_in_flight = false;
+    hipEvent_t tables_fence = nullptr; bool tables_fence_pending = false, tables_in_flight = false;   /* one fence for every device table written and read in stream order: sample cameras, moving spheres, an adaptive launch's mask / list / counters */
     /* moving spheres of supersampled launches (clw_ext_set_sphere_motion).  The device copy -- 64 per-lane times, then a float4 per sphere
      * (whitted_params.h: ss_times, ss_disp) -- is written like the camera table: only when it changed, in pieces of one wt_cam_table by the
      * same small kernel on the launch stream, and behind the same fence when the stream changes. */
@@ -306,7 +320,7 @@ std::pair<hipEvent_t, hipEvent_t> take_events(Impl* I) {
 
 struct LaunchTimer {
     Impl* I; cl_uint kernel; bool on; std::pair<hipEvent_t, hipEvent_t> ev;
-    LaunchTimer(Impl* I_, cl_uint k) : I(I_), kernel(k), on(I_->timing_on && I_->timing.size() < 16384 && (I_->timing_tick++ % I_->timing_every) == 0) {
+    LaunchTimer(Impl* I_, cl_uint k, bool wanted = true) : I(I_), kernel(k), on(wanted && I_->timing_on && I_->timing.size() < 16384 && (I_->timing_tick++ % I_->timing_every) == 0) {
         if (on) { ev = take_events(I); HIP_OK(hipEventRecord(ev.first, I->stream), "Couldn't run the kernel"); }
     }
     void done() {
@@ -536,8 +550,13 @@ void bind_scene(cl_wrap* w, Impl* I, cl_uint kid, whitted_params& P, int& flags,
 /* one strip of a frame: rows [row0, row0 + rows) of the launch range, scheduling state in scheds[slot] */
 struct Strip { uint32_t row0, rows; int slot; };
 
-void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Strip* strip = nullptr) {
+/* what a trace launch is: the whole thing, or one of the two passes of an adaptive launch (run_raytracer) -- its 1-sample base pass, which is
+ * the factor-1 launch in everything (scheduling state included), or its refine pass, the supersampled launch served from the classifier's list */
+enum TracePass { PASS_PLAIN = 0, PASS_BASE = 1, PASS_REFINE = 2 };
+
+void trace_launch(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Strip* strip, TracePass pass) {
     Kernel& k = I->kernels[kid];
+    const char* who = pass == PASS_PLAIN ? "Supersampling" : "Adaptive supersampling";
     /* arg 0: the ray buffer, passed by value as the 8 bytes of a handle (raypng.c:61) or bound as a buffer */
     Buffer* rays = nullptr;
     if (is_registered(w, kid, 0)) rays = (Buffer*)w->buffers[kid][0];
@@ -568,7 +587,7 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
     P.out_rgb = I->debug_rgb;
     P.diag = (I->variant & 512) ? (env_int("CLWRAP_TIMELINE_EDGES", 0) ? 255u + (uint32_t)env_int("CLWRAP_TIMELINE_EDGES", 0) : 1u + (uint32_t)env_int("CLWRAP_TIMELINE_SHIFT", 0)) : 0u;
 
-    const int ss = I->supersample;
+    const int ss = pass == PASS_BASE ? 1 : I->supersample;
     if (I->aperture > 0.0f && ss == 1) die("A lens needs samples: aperture %g with supersampling factor 1 (clw_ext_set_supersample / CLWRAP_SUPERSAMPLE)", (double)I->aperture);
     if (!I->cams.empty() && (ss == 1 || I->cams.size() != (size_t)(ss * ss)))
         die("Sample cameras: the table holds %u cameras, but supersampling factor %d %s", (unsigned)I->cams.size(), ss,
@@ -615,10 +634,10 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
             /* the launch traces the virtual frame of ss x as many columns and rows that the same camera gives (for a power of two bit for bit
              * what rgen_perspective returns for it) and stores one resolved pixel per ss x ss samples; ids -- the RNG seeds -- are the virtual
              * frame's.  Everything the caller sized stays in output pixels: the range above, `out`, the ray buffer, the strips. */
-            if (g.band_stride > 1) die("Supersampling does not support interleaved row bands");
-            if (I->variant & 2) die("Supersampling does not support linear work-item ids (variant 2)");
-            if (!P.tiled) die("Supersampling needs a launch range of whole rows");
-            if ((uint64_t)g.width * g.height * (uint64_t)(ss * ss) >= (1ull << 32)) die("Supersampling: the %d x %d samples of this frame exceed 32-bit ids", ss, ss);
+            if (g.band_stride > 1) die("%s does not support interleaved row bands", who);
+            if (I->variant & 2) die("%s does not support linear work-item ids (variant 2)", who);
+            if (!P.tiled) die("%s needs a launch range of whole rows", who);
+            if ((uint64_t)g.width * g.height * (uint64_t)(ss * ss) >= (1ull << 32)) die("%s: the %d x %d samples of this frame exceed 32-bit ids", who, ss, ss);
             const uint32_t out_rows = P.n_items / g.width, row0 = (uint32_t)(g.id_offset / g.width);
             g.w_factor /= (float)ss; g.h_factor /= (float)ss;
             g.width *= (uint32_t)ss; g.height *= (uint32_t)ss;
@@ -640,12 +659,12 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
                 for (unsigned lane = 0; lane < 64; lane++)   /* a tile's lane (lane & 7, lane >> 3) traces sub-sample (sx, sy) = both mod n */
                     memcpy(cam_table.v + 12 * lane, &I->cams_used[(size_t)((lane >> 3) & (unsigned)(ss - 1)) * ss + ((lane & 7u) & (unsigned)(ss - 1))], 48);
                 if (!I->d_cams) HIP_OK(hipMalloc((void**)&I->d_cams, sizeof(wt_cam_table)), "Couldn't allocate device memory");
-                if (I->cams_fence_pending) { HIP_OK(hipStreamWaitEvent(I->stream, I->cams_fence, 0), "Couldn't run the kernel"); I->cams_fence_pending = false; }
+                if (I->tables_fence_pending) { HIP_OK(hipStreamWaitEvent(I->stream, I->tables_fence, 0), "Couldn't run the kernel"); I->tables_fence_pending = false; }
                 if (!I->cams_dev_valid || memcmp(&cam_table, &I->cams_dev, sizeof cam_table)) {
                     if (wt_fast_launch_cams(&cam_table, I->d_cams, I->stream) != hipSuccess) die("Couldn't run the kernel");
                     I->cams_dev = cam_table; I->cams_dev_valid = true;
                 }
-                I->cams_in_flight = true;
+                I->tables_in_flight = true;
                 P.ss_cams = I->d_cams;
             }
             if (moving) {
@@ -657,7 +676,7 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
                     motion_table[lane] = I->times_used[(size_t)((lane >> 3) & (unsigned)(ss - 1)) * ss + ((lane & 7u) & (unsigned)(ss - 1))];
                 for (uint32_t i = 0; i < P.ns; i++) memcpy(&motion_table[64 + 4 * (size_t)i], &I->motion_disp[3 * (size_t)i], 12);
                 if (!I->d_motion) HIP_OK(hipMalloc((void**)&I->d_motion, 2 * sizeof(wt_cam_table)), "Couldn't allocate device memory");
-                if (I->cams_fence_pending) { HIP_OK(hipStreamWaitEvent(I->stream, I->cams_fence, 0), "Couldn't run the kernel"); I->cams_fence_pending = false; }
+                if (I->tables_fence_pending) { HIP_OK(hipStreamWaitEvent(I->stream, I->tables_fence, 0), "Couldn't run the kernel"); I->tables_fence_pending = false; }
                 if (!same_bits(I->motion_dev, motion_table)) {
                     for (size_t c = 0; c < pieces; c++) {
                         wt_cam_table piece;
@@ -666,7 +685,7 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
                     }
                     I->motion_dev = motion_table;
                 }
-                I->cams_in_flight = true;
+                I->tables_in_flight = true;
                 P.ss_times = I->d_motion; P.ss_disp = I->d_motion + 64;
             }
         }
@@ -674,7 +693,7 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
         P.row_offset = (uint32_t)(g.id_offset / g.width);
         P.unit_dirs = P.ns <= GRID_MIN_SPHERES ? 1u : 0u;      /* primary rays are generated (and normalised) in the kernel */
     } else {
-        if (ss > 1) die("Supersampling needs the fused raygen + trace launch (CLWRAP_FUSE=1, rays generated by this library and not rewritten)");
+        if (ss > 1) die("%s needs the fused raygen + trace launch (CLWRAP_FUSE=1, rays generated by this library and not rewritten)", who);
         materialise_rays(I, rays);
         ensure_allocated(I, rays);
         if ((uint64_t)P.n_items * 64 > rays->size) die("Couldn't run the kernel");
@@ -726,7 +745,28 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
     const bool tail_wanted = (flags & F_DEEP) && !(flags & F_OCC) && !(I->variant & 16) && I->tpt_max != 0u && tpt_cap >= TPT_MIN_CAP && !moving;
     bool split = false;
     const unsigned split_max_lg = ss == 1 ? 4u : (ss == 2 ? 2u : (ss == 4 ? 1u : 0u));
-    if (P.tiled) {
+    if (pass == PASS_REFINE) {
+        /* the refine pass: its order is the classifier's list, eight per-XCD lists of up to per_share entries whose lengths only the device knows --
+         * the grid covers full lists, and the list-driven flavour sends the waves beyond a list's end home.  No costs, no split of heavy tiles;
+         * the tail, the high-occupancy flavour and the grid are chosen above and below as the plain supersampled launch chooses them. */
+        if (trows > 0xFFFu || tpr > 0xFFFu) die("Adaptive supersampling: %u x %u blocks are more than a tile list can address (4095 each way)", tpr, trows);
+        const uint32_t ow = P.width >> P.ss_lg, orows = P.rows >> P.ss_lg;
+        Impl::Adaptive& A = I->adapt;
+        if (A.w != ow || A.rows != orows || A.ss != ss || !A.mask) {
+            A.free_all();
+            HIP_OK(hipMalloc((void**)&A.mask, (size_t)trows * tpr), "Couldn't allocate device memory");
+            HIP_OK(hipMalloc((void**)&A.order, (size_t)grid * 4), "Couldn't allocate device memory");
+            HIP_OK(hipMalloc((void**)&A.count, 8 * WT_LIST_COUNT_STRIDE * 4), "Couldn't allocate device memory");
+            A.w = ow; A.rows = orows; A.ss = ss;
+        }
+        if (I->tables_fence_pending) { HIP_OK(hipStreamWaitEvent(I->stream, I->tables_fence, 0), "Couldn't run the kernel"); I->tables_fence_pending = false; }
+        HIP_OK(hipMemsetAsync(A.count, 0, 8 * WT_LIST_COUNT_STRIDE * 4, I->stream), "Couldn't run the kernel");
+        if (wt_fast_launch_classify(P.out, ow, orows, 3u - P.ss_lg, (unsigned)I->adaptive, A.mask, A.order, A.count, per_share, I->stream) != hipSuccess)
+            die("Couldn't run the kernel");
+        I->tables_in_flight = true;
+        A.blocks = trows * tpr;
+        P.tile_order = A.order; P.list_count = A.count;
+    } else if (P.tiled) {
         if (I->sched && !(I->variant & 4) && trows <= 0xFFFu && tpr <= 0xFFFu) {   /* the order packs (tile column | row << 12 | parts) */
             /* a part of a split tile owns 8 >> lg whole tile rows; a supersampled launch needs ss of them in one wavefront (ss = 8: no split) */
             split = tail_wanted && !(flags & F_GRID) && I->split_min_quota != 0u && !(I->variant & 4096) && split_max_lg != 0u;
@@ -774,6 +814,7 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
         flags |= F_SHAPE | (int)(P.ns << 9 | P.np << 12 | P.nl << 14);
     if (P.ss_lg) flags |= F_SS;      /* every fused flavour has a supersampled twin, whose epilogue resolves the samples */
     if (P.ss_lg && P.ss_disp) flags |= F_MOVE;      /* ... and the twin (not the grid builds') a flavour whose sphere reads take the lane's scene time */
+    if (pass == PASS_REFINE) flags |= F_LIST;       /* ... and one that asks the device how long its tile list is */
     I->last_trace_flags = flags;
     if (tail_wanted) {
         const uint64_t nslots = tpt_nslots, slice = tpt_slice, cap = tpt_cap;
@@ -800,7 +841,7 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
             }
         }
     }
-    LaunchTimer t(I, kid);
+    LaunchTimer t(I, kid, pass == PASS_PLAIN);      /* (an adaptive launch is timed as one: run_raytracer) */
     hipError_t e = I->strict ? wt_strict_launch_trace(&P, flags, grid, dyn_lds, I->stream)
                              : wt_fast_launch_trace(&P, flags, grid, dyn_lds, I->stream);
     if (e != hipSuccess) die("Couldn't run the kernel");
@@ -821,6 +862,21 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
     }
 }
 
+void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Strip* strip = nullptr) {
+    I->adapt.blocks = 0;
+    if (I->adaptive < 0) { trace_launch(w, I, kid, array_size, strip, PASS_PLAIN); return; }
+    /* Adaptive supersampling (hip_wrap_ext.h: clw_ext_set_adaptive).  Per-sample cameras and moving spheres change every pixel of the frame, so
+     * the contrast of a 1-sample frame says nothing about where their samples matter: refused. */
+    if (I->supersample == 1) die("Adaptive supersampling needs samples: threshold %d with supersampling factor 1 (clw_ext_set_supersample / CLWRAP_SUPERSAMPLE)", I->adaptive);
+    if (I->aperture > 0.0f) die("Adaptive supersampling does not combine with a lens (clw_ext_set_lens): every pixel of such a frame needs its samples");
+    if (!I->cams.empty()) die("Adaptive supersampling does not combine with a table of sample cameras (clw_ext_set_sample_cameras): every pixel of such a frame needs its samples");
+    if (!I->motion_disp.empty()) die("Adaptive supersampling does not combine with moving spheres (clw_ext_set_sphere_motion): every pixel of such a frame needs its samples");
+    LaunchTimer t(I, kid);
+    trace_launch(w, I, kid, array_size, strip, PASS_BASE);
+    trace_launch(w, I, kid, array_size, strip, PASS_REFINE);
+    t.done();
+}
+
 /* cl_wrap_output of a big frame with read-back (what rayinteractive.c does every frame, :183-191): the launch is cut
  * into strips of whole tile rows, and strip c travels to the host while strip c+1 renders.  Same pixels (strips
  * keep their global ids), same blocking semantics -- the call returns when the whole frame is in `host_output`.
@@ -828,6 +884,7 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
 bool pipelined_output(cl_wrap* w, Impl* I, size_t array_size, size_t output_size, cl_uint kid, cl_uint out_kernel,
                       cl_int out_arg, void* host_output) {
     if (!I->pipeline || I->async || !host_output || !I->fuse || I->counting || I->debug_rgb || (I->variant & 2)) return false;
+    if (I->adaptive >= 0) return false;      /* a strip's edge rows would be classified without their neighbours in the next strip: another frame */
     if (out_kernel != kid || out_arg != 10 || !is_registered(w, kid, 10)) return false;
     Kernel& k = I->kernels[kid];
     Buffer* rays = nullptr;
@@ -935,6 +992,14 @@ void cl_wrap_init(cl_wrap* wrap, cl_device_type type, ...) {
     I->pipeline = env_int("CLWRAP_PIPELINE", 1) ? 1 : 0;
     I->supersample = env_int("CLWRAP_SUPERSAMPLE", 1);
     if (I->supersample != 1 && I->supersample != 2 && I->supersample != 4 && I->supersample != 8) die("CLWRAP_SUPERSAMPLE (supersampling factor) must be 1, 2, 4 or 8");
+    if (const char* ad = getenv("CLWRAP_ADAPTIVE")) {
+        if (*ad) {
+            char* end = nullptr;
+            const long v = strtol(ad, &end, 10);
+            if (end == ad || *end || v < 0 || v > 256) die("CLWRAP_ADAPTIVE (adaptive supersampling: contrast threshold) must be an integer in [0, 256]");
+            I->adaptive = (int)v;
+        }
+    }
     I->aperture = env_float("CLWRAP_APERTURE", 0.0f);
     I->focus = env_float("CLWRAP_FOCUS", 1.0f);
     if (!(I->aperture >= 0.0f) || !std::isfinite(I->aperture)) die("CLWRAP_APERTURE (lens aperture) must be a finite number >= 0");
@@ -1073,7 +1138,8 @@ void cl_wrap_release(cl_wrap* wrap) {
     if (I->d_tpt_jump) (void)hipFree(I->d_tpt_jump);
     if (I->d_cams) (void)hipFree(I->d_cams);
     if (I->d_motion) (void)hipFree(I->d_motion);
-    if (I->cams_fence) (void)hipEventDestroy(I->cams_fence);
+    I->adapt.free_all();
+    if (I->tables_fence) (void)hipEventDestroy(I->tables_fence);
     for (uint32_t* q : {I->d_grid_start, I->d_grid_items, I->d_grid_box}) if (q) (void)hipFree(q);
     if (I->d_grid_geom) (void)hipFree(I->d_grid_geom);
     if (I->sched_stream) (void)hipStreamSynchronize(I->sched_stream);
@@ -1107,11 +1173,11 @@ void clw_ext_sync(cl_wrap* wrap) { Impl* I = impl_of(wrap); use_device(I); finis
 void clw_ext_set_stream(cl_wrap* wrap, void* hip_stream) {
     Impl* I = impl_of(wrap);
     hipStream_t next = hip_stream ? (hipStream_t)hip_stream : I->own_stream;
-    if (next != I->stream && I->cams_in_flight) {   /* the sample-camera / moving-sphere tables were written / are read in the old stream's order: fence them */
+    if (next != I->stream && I->tables_in_flight) {   /* the sample-camera / moving-sphere tables and an adaptive launch's tile list were written / are read in the old stream's order: fence them */
         use_device(I);
-        if (!I->cams_fence) HIP_OK(hipEventCreateWithFlags(&I->cams_fence, hipEventDisableTiming), "Couldn't create a timing event");
-        HIP_OK(hipEventRecord(I->cams_fence, I->stream), "Couldn't run the kernel");
-        I->cams_fence_pending = true; I->cams_in_flight = false;
+        if (!I->tables_fence) HIP_OK(hipEventCreateWithFlags(&I->tables_fence, hipEventDisableTiming), "Couldn't create a timing event");
+        HIP_OK(hipEventRecord(I->tables_fence, I->stream), "Couldn't run the kernel");
+        I->tables_fence_pending = true; I->tables_in_flight = false;
     }
     I->stream = next;
 }
@@ -1185,6 +1251,19 @@ void clw_ext_set_supersample(cl_wrap* wrap, int n) {
     impl_of(wrap)->supersample = n;
 }
 int clw_ext_get_supersample(const cl_wrap* wrap) { return impl_of(wrap)->supersample; }
+void clw_ext_set_adaptive(cl_wrap* wrap, int threshold) {
+    if (threshold < -1 || threshold > 256) die("The adaptive supersampling threshold must be in [0, 256], or -1 for off");
+    impl_of(wrap)->adaptive = threshold;
+}
+int clw_ext_get_adaptive(const cl_wrap* wrap) { return impl_of(wrap)->adaptive; }
+uint32_t clw_ext_read_refine_mask(cl_wrap* wrap, uint8_t* out, uint32_t cap) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    finish(I);
+    const uint32_t n = I->adapt.blocks;
+    if (out && n && cap >= n) HIP_OK(hipMemcpy(out, I->adapt.mask, n, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
+    return n;
+}
 void clw_ext_set_sample_cameras(cl_wrap* wrap, const clw_sample_camera* cams, uint32_t count) {
     Impl* I = impl_of(wrap);
     if (cams && count) I->cams.assign(cams, cams + count); else I->cams.clear();

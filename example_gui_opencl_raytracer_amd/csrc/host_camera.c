@@ -138,3 +138,33 @@ int clw_host_spheres_at(const void* rspheres, uint32_t ns, const float* disp, fl
     }
     return 1;
 }
+
+/* ---- adaptive supersampling (hip_wrap_ext.h: clw_ext_set_adaptive) ------------------------------------------------- */
+
+static uint32_t channel_contrast(uint32_t p, uint32_t q) {
+    uint32_t c = 0;
+    for (int s = 0; s < 24; s += 8) {
+        const int d = (int)((p >> s) & 255u) - (int)((q >> s) & 255u);
+        const uint32_t a = (uint32_t)(d < 0 ? -d : d);
+        if (a > c) c = a;
+    }
+    return c;
+}
+
+int clw_host_refine_mask(const uint32_t* xrgb, uint32_t width, uint32_t rows, uint32_t n, int threshold, uint8_t* out) {
+    const int lg = sample_factor_lg(n);
+    if (!xrgb || !out || !lg || threshold < 0 || threshold > 256 || !width || !rows) return 0;
+    const uint32_t b = 8u / n, bc = (width + b - 1) / b, br = (rows + b - 1) / b;
+    memset(out, 0, (size_t)bc * br);
+    for (uint32_t y = 0; y < rows; y++)
+        for (uint32_t x = 0; x < width; x++) {
+            const uint32_t* p = xrgb + (size_t)y * width + x;
+            uint32_t c = 0, v;
+            if (x > 0 && (v = channel_contrast(*p, p[-1])) > c) c = v;
+            if (x + 1 < width && (v = channel_contrast(*p, p[1])) > c) c = v;
+            if (y > 0 && (v = channel_contrast(*p, *(p - width))) > c) c = v;
+            if (y + 1 < rows && (v = channel_contrast(*p, p[width])) > c) c = v;
+            if ((int)c >= threshold) out[(size_t)(y / b) * bc + x / b] = 1;
+        }
+    return 1;
+}

@@ -14,6 +14,7 @@
 #define WT_LAUNCH_RAYGEN wt_fast_launch_raygen
 #define WT_LAUNCH_SCHED wt_fast_launch_sched
 #define WT_LAUNCH_CAMS wt_fast_launch_cams
+#define WT_LAUNCH_CLASSIFY wt_fast_launch_classify
 #define WT_LAUNCH_UNIT wt_fast_launch_unit
 #define WT_LAUNCH_UNIT_SCENE wt_fast_launch_unit_scene
 #include "whitted_launch.inc"

@@ -12,7 +12,7 @@ static hipError_t wt_launch_one(const whitted_params* P, unsigned grid, size_t d
 
 extern "C" hipError_t WT_LAUNCH_TRACE(const whitted_params* P, int flags, unsigned grid, size_t dyn_lds,
                                       hipStream_t s) {
-    using WT_NS::WT_F_SS; using WT_NS::WT_F_MOVE;
+    using WT_NS::WT_F_SS; using WT_NS::WT_F_MOVE; using WT_NS::WT_F_LIST;
 #if !WT_STRICT
     using WT_NS::WT_F_GEOM_LDS; using WT_NS::WT_F_SHAPE;
     if (flags & WT_F_SHAPE) {
@@ -20,6 +20,7 @@ extern "C" hipError_t WT_LAUNCH_TRACE(const whitted_params* P, int flags, unsign
         switch (flags) {
 #define WT_SHAPE_CASE(ns, np) case WT_SHAPE_FLAGS(ns, np, 3): return wt_launch_one<WT_SHAPE_FLAGS(ns, np, 3)>(P, grid, dyn_lds, s); \
                               case WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS: return wt_launch_one<WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS>(P, grid, dyn_lds, s); \
+                              case WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS | WT_F_LIST: return wt_launch_one<WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS | WT_F_LIST>(P, grid, dyn_lds, s); \
                               case WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS | WT_F_MOVE: return wt_launch_one<WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS | WT_F_MOVE>(P, grid, dyn_lds, s);
 #define WT_SHAPE_CASES(ns) WT_SHAPE_CASE(ns, 0) WT_SHAPE_CASE(ns, 1) WT_SHAPE_CASE(ns, 2)
             WT_SHAPE_CASES(1) WT_SHAPE_CASES(2) WT_SHAPE_CASES(3) WT_SHAPE_CASES(4)
@@ -29,10 +30,10 @@ extern "C" hipError_t WT_LAUNCH_TRACE(const whitted_params* P, int flags, unsign
         return hipErrorInvalidValue;
     }
 #endif
-    switch (flags & (255 | WT_F_SS | WT_F_MOVE)) {
+    switch (flags & (255 | WT_F_SS | WT_F_MOVE | WT_F_LIST)) {
 #define WT_CASE(F) case F: return wt_launch_one<F>(P, grid, dyn_lds, s);
-/* F and its supersampled twin (fused launches only: no twin for the ray-buffer flavours, bit 3) */
-#define WT_CASE2(F) WT_CASE(F) WT_CASE((F) | WT_F_SS)
+/* F, its supersampled twin (fused launches only: no twin for the ray-buffer flavours, bit 3) and the twin's list-driven flavour (adaptive launches) */
+#define WT_CASE2(F) WT_CASE(F) WT_CASE((F) | WT_F_SS) WT_CASE((F) | WT_F_SS | WT_F_LIST)
 /* ... and the twin's moving-spheres flavour (not the grid builds) */
 #define WT_CASE3(F) WT_CASE2(F) WT_CASE((F) | WT_F_SS | WT_F_MOVE)
         WT_CASE3(0) WT_CASE3(1) WT_CASE3(2) WT_CASE3(3) WT_CASE3(4) WT_CASE3(5) WT_CASE3(6) WT_CASE3(7)
@@ -69,6 +70,19 @@ extern "C" hipError_t WT_LAUNCH_SCHED(const unsigned* cost, unsigned* order, uns
                        split_slots, min_quota, max_lg);
     return hipGetLastError();
 }
+
+#if !WT_STRICT   /* integer work: one copy, in the fast unit, serves both builds */
+extern "C" hipError_t WT_LAUNCH_CLASSIFY(const unsigned* frame, unsigned width, unsigned rows, unsigned lgb, unsigned threshold,
+                                         unsigned char* mask, unsigned* order, unsigned* count, unsigned cap, hipStream_t s) {
+    const unsigned b = 1u << lgb, nbc = (width + b - 1u) / b, nbr = (rows + b - 1u) / b;
+    const unsigned per_wave = 64u >> (2u * lgb), wpr = (nbc + per_wave - 1u) / per_wave;      /* blocks a wave owns; waves per block row */
+    const unsigned long long waves = (unsigned long long)nbr * wpr;
+    if (lgb > 2u || waves == 0ull || waves > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(WT_NS::wt_refine_classify, dim3((unsigned)((waves + 3ull) / 4ull)), dim3(256), 0, s, frame, width, rows, lgb, threshold, nbc, nbr,
+                       wpr, mask, order, count, cap);
+    return hipGetLastError();
+}
+#endif
 
 extern "C" hipError_t WT_LAUNCH_CAMS(const wt_cam_table* T, float* dst, hipStream_t s) {
     hipLaunchKernelGGL(WT_NS::wt_cams_store, dim3(1), dim3(64), 0, s, *T, (float4*)dst);

@@ -102,8 +102,14 @@ typedef struct {
      * Small non-grid scenes only (ns <= 256); LDS-geometry kernels stage the table behind the prepared stream (geom_f4 + ns <= 1024 float4) */
     const float* ss_disp;
     const float* ss_times;
+    /* the refine pass of an adaptive supersampled launch (the WT_F_LIST flavours; wt_refine_classify wrote both): tile_order holds eight lists
+     * interleaved as order[8 * j + k], list k -- the refined tiles of the tile rows r = 8m + k -- being list_count[WT_LIST_COUNT_STRIDE * k]
+     * entries long (a cache line per counter); the grid is sized for full lists, and workgroup b leaves at once unless b / 8 is below the
+     * length of list b % 8 */
+    const uint32_t* list_count;
 } whitted_params;
 
+#define WT_LIST_COUNT_STRIDE 32
 #define WT_CAM_TABLE_FLOATS (64 * 12)
 typedef struct { float v[WT_CAM_TABLE_FLOATS]; } wt_cam_table;   /* the table as a by-value kernel argument (wt_cams_store) */
 

@@ -682,7 +682,9 @@ enum { WT_F_COUNT = 1, WT_F_DEEP = 2, WT_F_GEOM_LDS = 4, WT_F_RAYS = 8, WT_F_GRI
        WT_F_SHAPE = 256 /* shallow fast LDS-geometry build only: the scene's counts are compiled in (wt_shape) */,
        WT_F_SS = 1 << 17 /* n x n supersampling, fused tiled launches only (bits 9-16: the counts of WT_SHAPE_FLAGS) */,
        WT_F_MOVE = 1 << 18 /* on top of WT_F_SS, not the grid builds: moving spheres (wt_sphere_at) -- a flavour of its own, so that the plain
-                              supersampled kernels are the code they were */ };
+                              supersampled kernels are the code they were */,
+       WT_F_LIST = 1 << 19 /* on top of WT_F_SS, not with WT_F_MOVE: the refine pass of an adaptive launch -- a wave first asks the device-side length of
+                              its list (whitted_params.h: list_count) whether it has a tile at all; again a flavour of its own */ };
 
 /* ---- the scene's primitive counts: launch parameters, or compile-time constants (FLAGS & WT_F_SHAPE) ----------------------------
  * A small scene's loops over 4 spheres, 2 planes and 3 lights are mostly loop control, guards and selects around little arithmetic.
@@ -1381,6 +1383,7 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
     constexpr bool GRID = (FLAGS & WT_F_GRID) != 0;     /* spheres through the uniform grid (big scenes) */
     constexpr bool SS = (FLAGS & WT_F_SS) != 0;         /* supersampled launch: the epilogue resolves n x n samples per stored pixel */
     constexpr bool MOVE = SS && !GRID && (FLAGS & WT_F_MOVE) != 0;   /* moving spheres: every sphere read takes the lane's scene time */
+    constexpr bool LIST = SS && (FLAGS & WT_F_LIST) != 0;            /* the refine pass of an adaptive launch: the tile list's length is on the device */
     constexpr bool UNIT_CT = !WT_STRICT && GEOM_LDS && !FROM_RAYS && !GRID;   /* see whitted_hit.inc */
     /* The lights' visibility classes (wt_light_vis) are compiled into the STRICT build's small-scene kernels only: there the samples they
      * save cost an fp64 product and a libm sin / cos each (-13 % at C2).  Measured for the fast build, whose samples are two hardware
@@ -1406,6 +1409,9 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
 #if WT_TIMELINE
     const unsigned long long tl_entry = __builtin_amdgcn_s_memrealtime();   /* first instructions of the wave */
 #endif
+    /* list-driven launches are sized for the case that every tile is refined: a wave beyond the end of its XCD's list (most of them, in a
+     * frame with flat regions) leaves before it stages anything -- one scalar load and a compare */
+    if (LIST) { if ((wg >> 3) >= P.list_count[WT_LIST_COUNT_STRIDE * (wg & 7u)]) return; }
 
     /* ---- stage the prepared geometry in LDS ------------------------------------------------------------------- */
     if (GEOM_LDS) wt_stage_scene<MOVE>(P, s_geom, threadIdx.x, WT_BLOCK);
@@ -1806,6 +1812,63 @@ __global__ void __launch_bounds__(256) wt_sched_build(const unsigned* __restrict
     }
     for (unsigned j = nvalid + tid; j < per_share_cap; j += 256) order[8u * j + k] = 0xFFFFFFFFu;
 }
+
+/* ---- adaptive supersampling: the classifier between the 1-sample base pass and the list-driven refine pass (WT_F_LIST).
+ *      frame = the packed base frame of the launch range, width x rows OUTPUT pixels.  A pixel is flagged when one of its R, G, B channels
+ *      differs by at least `threshold` from the same channel of one of its 4-neighbours inside the range; a block of b x b pixels, b = 1 << lgb
+ *      = 8 / n -- one 8x8 tile of the virtual frame -- is refined when any of its pixels is flagged (host definition: clw_host_refine_mask).
+ *      A wave owns 64 / b^2 blocks of ONE block row, block g in the b^2 adjacent lanes g b^2 .. -- so a block's flag is a field of the
+ *      wave's ballot, and all its blocks go to the same list: block (= virtual tile) row r belongs to XCD r mod 8, as in wt_sched_build, the
+ *      eight lists interleaved as order[8 j + k].  One append per wave: the ballot of the refined blocks, one atomic add of its population
+ *      count by the first of their lanes, the lanes' ranks from mbcnt.  mask[block] = 0 / 1 for every block; count[WT_LIST_COUNT_STRIDE * k]
+ *      (zeroed by the shim) ends as the length of list k.  The order inside a list depends on which wave came first; mask and lengths do not.
+ *      cap = entries per list: what every block of a share refined gives, so the guard below never fires. ------------ */
+#if !WT_STRICT   /* integer work, the same in both arithmetic builds: compiled into the fast unit only (the shim launches that copy) */
+__device__ __forceinline__ unsigned wt_px_contrast(unsigned p, unsigned q) {
+    unsigned c = 0u;
+#pragma unroll
+    for (int s = 0; s < 24; s += 8) {
+        const int d = (int)((p >> s) & 255u) - (int)((q >> s) & 255u);
+        c = max(c, (unsigned)(d < 0 ? -d : d));
+    }
+    return c;
+}
+__global__ void __launch_bounds__(256) wt_refine_classify(const unsigned* __restrict__ frame, unsigned width, unsigned rows, unsigned lgb,
+                                                          unsigned threshold, unsigned nbc, unsigned nbr, unsigned wpr,
+                                                          unsigned char* __restrict__ mask, unsigned* __restrict__ order,
+                                                          unsigned* __restrict__ count, unsigned cap) {
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (wave >= nbr * wpr) return;                                  /* wave-uniform */
+    const unsigned br = wave / wpr, wc = wave % wpr;                /* the wave's block row, and which 64 / b^2 blocks of it */
+    const unsigned b = 1u << lgb, sub = lane & (b * b - 1u);
+    const unsigned bc = wc * (64u >> (2u * lgb)) + (lane >> (2u * lgb));
+    const unsigned x = bc * b + (sub & (b - 1u)), y = br * b + (sub >> lgb);
+    const bool in = x < width && y < rows;
+    unsigned c = 0u;
+    if (in) {                                                       /* the one-pixel halo, cut at the range's edges */
+        const unsigned* p = frame + (size_t)y * width + x;
+        const unsigned v = p[0];
+        if (x > 0u) c = max(c, wt_px_contrast(v, p[-1]));
+        if (x + 1u < width) c = max(c, wt_px_contrast(v, p[1]));
+        if (y > 0u) c = max(c, wt_px_contrast(v, p[-(ptrdiff_t)width]));
+        if (y + 1u < rows) c = max(c, wt_px_contrast(v, p[width]));
+    }
+    const unsigned long long flagged = __builtin_amdgcn_ballot_w64(in && c >= threshold);
+    const bool lead = sub == 0u && in;                              /* a block's first pixel is inside the range iff the block is */
+    const bool refined = lead && ((flagged >> lane) & ((1ull << (b * b)) - 1ull)) != 0ull;     /* b^2 <= 16 */
+    if (lead) mask[(size_t)br * nbc + bc] = refined ? 1 : 0;
+    const unsigned long long app = __builtin_amdgcn_ballot_w64(refined);
+    if (app != 0ull) {
+        const unsigned k = br & 7u, first = (unsigned)__builtin_ctzll(app);
+        unsigned base = 0u;
+        if (lane == first) base = atomicAdd(count + WT_LIST_COUNT_STRIDE * k, (unsigned)__builtin_popcountll(app));
+        base = (unsigned)__builtin_amdgcn_readlane((int)base, (int)first);
+        const unsigned j = base + __builtin_amdgcn_mbcnt_hi((unsigned)(app >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)app, 0u));
+        if (refined && j < cap) order[8u * j + k] = bc | (br << 12);
+    }
+}
+#endif
 
 /* ---- unit-test kernel: the device helpers one by one, one input row per thread (tests/test_gpu_functions.py
  *      feeds it the golden vectors produced by the reference's own functions).  Rows are `stride_in` floats in,

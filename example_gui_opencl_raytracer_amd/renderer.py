@@ -20,6 +20,11 @@ distance ``focus`` (clw_ext_set_lens); ``set_sample_cameras`` hands the kernel a
 
 ``motion=disp`` (float32 [spheres, 3], with ``supersample`` > 1): object motion blur -- sphere i moves by ``disp[i]`` while the shutter is
 open and every sample sees the scene at its own time (clw_ext_set_sphere_motion; ``set_sphere_motion(disp, times)`` to change it).
+
+``adaptive=T`` (0..256, with ``supersample`` > 1, without lens, sample cameras or motion): only the blocks of 8/n x 8/n pixels in which the
+1-sample frame shows a contrast of at least T between neighbouring pixels take their n x n samples, the others keep the 1-sample value
+(clw_ext_set_adaptive; ``w.read_refine_mask()`` tells which).  A strip is classified on its own rows, so its edge rows may differ from the
+full frame's.
 """
 from __future__ import annotations
 
@@ -47,7 +52,7 @@ class Renderer:
                  depth: int = 15, strict: bool = False, fuse: bool = True, first_row: int = 0,
                  rows: int | None = None, bands: tuple[int, int] | None = None, framebuffer_ptr: int | None = None, wide_counts: bool | None = None,
                  texture_paths=None, skybox_path=None, supersample: int = 1,
-                 lens: tuple[float, float] | None = None, motion=None):
+                 lens: tuple[float, float] | None = None, motion=None, adaptive: int | None = None):
         self.width, self.height = width, height
         self.first_row = first_row
         self.rows = height - first_row if rows is None else rows
@@ -67,6 +72,8 @@ class Renderer:
             w.set_lens(*lens)
         if motion is not None:    # float32 [spheres, 3]: how far each sphere moves while the shutter is open
             w.set_sphere_motion(motion)
+        if adaptive is not None:  # contrast threshold 0..256: the samples only where the 1-sample frame shows that much contrast
+            w.set_adaptive(adaptive)
         if bands is not None:
             w.set_row_bands(*bands)
 

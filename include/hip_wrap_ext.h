@@ -157,6 +157,34 @@ void     clw_ext_set_sphere_motion(cl_wrap* wrap, const float* disp /* 3 per sph
  * suffices. */
 uint32_t clw_ext_get_sample_times(const cl_wrap* wrap, float* out, uint32_t cap);
 
+/* Adaptive supersampling: the n x n samples only where the 1-sample frame shows contrast.  threshold T in [0, 256] turns it on, -1 (the
+ * default) off; also CLWRAP_ADAPTIVE=<0..256> in the environment of cl_wrap_init.  It applies to what clw_ext_set_supersample applies to --
+ * a fused, tiled trace launch of W x H output pixels, or a strip of whole rows of it -- with a factor n of 2, 4 or 8, and is exact:
+ *   1. the base frame B is the launch range traced as the factor-1 launch traces it (camera, ids, RNG seeds, clamp, pack);
+ *   2. c(p) = the largest |ch(p) - ch(q)| over the channels R, G, B and the 4-neighbours q of p INSIDE the launch range, on the packed 8-bit
+ *      channels of B; p is flagged iff c(p) >= T (T = 0 flags every pixel, T = 256 none);
+ *   3. the range is cut into blocks of b x b output pixels, b = 8 / n, from its first row and column 0 (edge blocks are partial) -- the 8x8 tiles
+ *      of the virtual frame; a block is refined iff one of its pixels is flagged (clw_host_refine_mask below is THE definition of 2 and 3);
+ *   4. the pixels of refined blocks take the value the plain supersampled launch of that range gives them, all others keep B; the float debug
+ *      output likewise (un-clamped radiance in kept pixels, the resolved mean in refined ones).
+ * One launch is three on the launch stream, none waited for (clw_ext_set_async holds): the base pass -- an ordinary 1-sample launch, which keeps
+ * the cost-sorted dispatch and whose costs clw_ext_read_tile_costs returns --, the classifier, which writes the mask and appends the refined tiles
+ * to eight per-XCD lists on the device, and the refine pass: the supersampled kernel in its list-driven flavour (clw_ext_last_trace_flags: WT_F_SS |
+ * WT_F_LIST, 1 << 19), its grid sized for full lists, a wavefront beyond its list's end leaving at once.  The refine pass keeps the tree-parallel
+ * tail, the high-occupancy flavour and the uniform grid as the plain supersampled launch of the frame chooses them; heavy tiles are not split.
+ * Work counters add up over both passes; the launch timer brackets all three as one launch.  The pipelined read-back of cl_wrap_output declines
+ * while the mode is on.  A strip is defined on its OWN range: the pixels of its first and last row have no neighbour beyond it, so those rows may
+ * differ from the same rows of the full frame (the strips of a multi-GPU frame do not compose bit for bit; each equals the definition above).
+ * Errors (print + exit(1)): at the call, T outside [-1, 256]; at the next trace launch, the mode with factor 1, with a table of sample cameras, a
+ * lens or moving spheres (they change every pixel: a 1-sample contrast test says nothing), a range of more than 4095 blocks either way (a list entry
+ * packs block column and row in 12 bits each: at most 16380 pixels per row and rows per range with n = 2, 8190 with n = 4, 4095 with n = 8 -- narrower
+ * than what plain supersampling accepts), and whatever plain supersampling refuses; at cl_wrap_init, a CLWRAP_ADAPTIVE that is not such an integer. */
+void     clw_ext_set_adaptive(cl_wrap* wrap, int threshold);
+int      clw_ext_get_adaptive(const cl_wrap* wrap);
+/* The block mask of the LAST trace launch if it was adaptive: one byte (0 / 1) per block, row-major, ceil(rows / b) x ceil(W / b) -> their count
+ * (0 = the last launch was not adaptive); copies them if `cap` suffices.  Waits for the launch. */
+uint32_t clw_ext_read_refine_mask(cl_wrap* wrap, uint8_t* out, uint32_t cap);
+
 /* Work counters of the trace kernel.  enable=1 selects the counting build of the kernel
  * for subsequent launches (slower); read returns and clears
  *   out[0] path segments  out[1] shadow rays  out[2] light probes  out[3] skybox fetches
@@ -272,6 +300,11 @@ int clw_host_sample_times(uint32_t n, float* out);
  * first three floats) by fmaf(t, disp[3 i + a], c[a]); every other byte -- radius, material, padding -- is copied as it is.  `out` may
  * be `rspheres` itself.  Returns 0 on a NULL argument (with ns > 0), else 1. */
 int clw_host_spheres_at(const void* rspheres, uint32_t ns, const float* disp, float t, void* out);
+
+/* Host helper: THE definition of the refine mask of adaptive supersampling (steps 2 and 3 of clw_ext_set_adaptive): `xrgb` = width x rows packed
+ * pixels (the top byte is ignored), n in {2, 4, 8}, threshold in [0, 256]; writes one byte (0 / 1) per block of b x b pixels, b = 8 / n, row-major,
+ * ceil(rows / b) x ceil(width / b) of them.  Returns 0 on bad arguments (n, threshold, a NULL pointer, an empty frame), else 1. */
+int clw_host_refine_mask(const uint32_t* xrgb, uint32_t width, uint32_t rows, uint32_t n, int threshold, uint8_t* out);
 
 /* Host helpers: PNG files without libpng (reference png_dump, src/cpu_ray.c:108-165, and the
  * decode step of cl_wrap_load_images).  Return 0 on success. */

@@ -1,0 +1,81 @@
+"""Shared by test_adaptive_host.py and test_gpu_adaptive.py: the numpy side of the definition of adaptive supersampling
+(include/hip_wrap_ext.h, clw_ext_set_adaptive).
+
+With factor n and threshold T, the contrast c(p) of pixel p of the packed 1-sample frame B of the launch range is the largest |ch(p) - ch(q)|
+over R, G, B and the 4-neighbours q of p inside the range; p is flagged iff c(p) >= T; the range is cut into blocks of b x b pixels, b = 8 / n,
+from its first row and column 0, and a block is refined iff one of its pixels is flagged (`refine_mask_np`).  The adaptive frame is the plain
+supersampled frame in the refined blocks and B elsewhere (`composite`)."""
+import numpy as np
+
+from conftest import CAM
+
+
+def contrast_np(xrgb, W, rows):
+    """c(p) for every pixel -> int32 [rows, W]"""
+    a = np.asarray(xrgb, np.uint32).reshape(rows, W)
+    ch = np.stack([(a >> 16) & 255, (a >> 8) & 255, a & 255], -1).astype(np.int32)
+    c = np.zeros((rows, W), np.int32)
+    dx = np.abs(ch[:, 1:] - ch[:, :-1]).max(-1)          # between (x, x + 1)
+    dy = np.abs(ch[1:] - ch[:-1]).max(-1)                # between (y, y + 1)
+    c[:, 1:] = np.maximum(c[:, 1:], dx)
+    c[:, :-1] = np.maximum(c[:, :-1], dx)
+    c[1:] = np.maximum(c[1:], dy)
+    c[:-1] = np.maximum(c[:-1], dy)
+    return c
+
+
+def refine_mask_np(xrgb, W, rows, n, T):
+    """-> uint8 [ceil(rows / b), ceil(W / b)], b = 8 / n: 1 = the block holds a pixel whose contrast is >= T"""
+    b = 8 // n
+    flag = contrast_np(xrgb, W, rows) >= T
+    br, bc = -(-rows // b), -(-W // b)
+    pad = np.zeros((br * b, bc * b), bool)
+    pad[:rows, :W] = flag
+    return pad.reshape(br, b, bc, b).any((1, 3)).astype(np.uint8)
+
+
+def pixel_mask(mask, W, rows, n):
+    """the block mask spread over the pixels -> bool [rows * W]"""
+    b = 8 // n
+    return np.repeat(np.repeat(np.asarray(mask, bool), b, 0), b, 1)[:rows, :W].reshape(-1)
+
+
+def composite(mask, W, rows, n, base, fine):
+    """where(refined, plain supersampled frame, 1-sample frame), for packed [rows * W] or float [rows * W, 3] frames"""
+    m = pixel_mask(mask, W, rows, n)
+    return np.where(m if base.ndim == 1 else m[:, None], fine, base)
+
+
+# ---- copies of the helpers of test_gpu_supersample.py (a test module is not importable from another) ---------------------------------
+def resolve(rgb, W, H, n):                      # rgb: float32 [n*H * n*W, 3], virtual-frame order
+    s = np.clip(rgb.reshape(H * n, W * n, 3), np.float32(0), np.float32(1))
+    k = n
+    while k > 1: s = s[:, 0::2] + s[:, 1::2]; k //= 2
+    k = n
+    while k > 1: s = s[0::2] + s[1::2]; k //= 2
+    s = s * np.float32(1.0 / (n * n))
+    c = (s * np.float32(255.0)).astype(np.uint32)
+    return ((c[..., 0] << 16) | (c[..., 1] << 8) | c[..., 2]).reshape(-1), s.reshape(-1, 3)
+
+
+def frames(R, sc, tex, sky, W, H, depth, strict, n=1, count=1, setup=None, rgb=True, **kw):
+    """`count` frames in a row from one renderer -> ([(packed, float) ...], flags of the last trace launch); **kw goes to the Renderer"""
+    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, **kw)
+    try:
+        if setup:
+            setup(r.w)
+        r.look(**CAM)
+        out = []
+        for _ in range(count):
+            if rgb:
+                p, f = r.render_rgb()
+                out.append((p.copy(), f.copy()))
+            else:
+                out.append((r.render().copy(), None))
+        return out, r.w.last_trace_flags()
+    finally:
+        r.release()
+
+
+def same_floats(a, b):
+    return np.array_equal(a.view(np.uint32), b.view(np.uint32))

@@ -1,0 +1,134 @@
+"""Adaptive supersampling without a GPU: the C ABI and the host helper that IS the definition of the refine mask (clw_host_refine_mask),
+held to the numpy restatement of adaptive_common.py."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from adaptive_common import composite, contrast_np, pixel_mask, refine_mask_np
+from conftest import ROOT
+from example_gui_opencl_raytracer_amd import api
+
+NEW = ["clw_ext_set_adaptive", "clw_ext_get_adaptive", "clw_ext_read_refine_mask", "clw_host_refine_mask"]
+SHAPES = [(101, 75, 2), (200, 152, 4), (96, 64, 8), (1, 1, 2), (1, 1, 8), (37, 1, 4), (1, 9, 2)]      # (W, rows, n)
+THRESHOLDS = [0, 1, 16, 255, 256]
+
+
+def random_frame(W, rows, seed):
+    """packed pixels with flat regions, gentle ramps and hard edges, so that every threshold splits the blocks (and a top byte to ignore)"""
+    rng = np.random.default_rng(seed)
+    base = rng.integers(0, 256, (-(-rows // 7), -(-W // 9), 3), dtype=np.int64)
+    img = np.repeat(np.repeat(base, 7, 0), 9, 1)[:rows, :W]
+    noise = rng.integers(0, 3, (rows, W, 3)) * (rng.random((rows, W, 1)) < 0.05)
+    img = np.clip(img + noise, 0, 255).astype(np.uint32)
+    if rows > 1:
+        img[rows // 2:, : W // 2] = img[rows // 2, 0]      # one big flat region
+    top = rng.integers(0, 256, (rows, W), dtype=np.uint32) << 24
+    return ((img[..., 0] << 16) | (img[..., 1] << 8) | img[..., 2] | top).reshape(-1)
+
+
+# ------------------------------------------------------------------ 1. the ABI
+def test_header_library_and_mirror_agree_on_the_new_symbols():
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hip_wrap_ext.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b((?:clw_ext|clw_host)_\w+)\s*\(", text))
+    L = api.load_library()
+    for name in NEW:
+        assert name in declared and name in api.SYMBOLS and hasattr(L, name), name
+
+
+def test_renderer_and_wrapper_take_a_threshold():
+    import inspect
+    from example_gui_opencl_raytracer_amd.renderer import Renderer
+    assert "adaptive" in inspect.signature(Renderer.__init__).parameters
+    assert callable(api.ClWrap.set_adaptive) and callable(api.ClWrap.get_adaptive) and callable(api.ClWrap.read_refine_mask)
+    assert callable(api.refine_mask)
+
+
+# ------------------------------------------------------------------ 2. the mask
+@pytest.mark.parametrize("W,rows,n", SHAPES)
+def test_mask_of_random_frames_is_the_numpy_restatement(W, rows, n):
+    b = 8 // n
+    for seed in range(3):
+        frame = random_frame(W, rows, 1000 * seed + W + rows + n)
+        shares = []
+        for T in THRESHOLDS:
+            got = api.refine_mask(frame, W, rows, n, T)
+            assert got.dtype == np.uint8 and got.shape == (-(-rows // b), -(-W // b))
+            assert np.array_equal(got, refine_mask_np(frame, W, rows, n, T)), (W, rows, n, T, seed)
+            shares.append(float(got.mean()))
+            if T == 0:
+                assert got.all()
+            if T == 256:
+                assert not got.any()
+        assert shares == sorted(shares, reverse=True)                  # a higher threshold never refines more
+        if W * rows >= 64 * 64:
+            assert 0.0 < shares[2] < 1.0                               # T = 16 splits these frames
+
+
+def test_the_top_byte_is_ignored():
+    W, rows, n = 40, 24, 4
+    frame = random_frame(W, rows, 7)
+    for T in (1, 16):
+        assert np.array_equal(api.refine_mask(frame, W, rows, n, T), api.refine_mask(frame & np.uint32(0xFFFFFF), W, rows, n, T))
+
+
+def test_contrast_is_per_channel_and_over_the_four_neighbours_only():
+    W, rows = 16, 16
+    frame = np.zeros((rows, W), np.uint32)
+    frame[5, 6] = (10 << 16) | (40 << 8) | 20            # one pixel: contrast 40 to its 4 neighbours, and theirs to it
+    c = contrast_np(frame, W, rows)
+    assert c[5, 6] == 40 and c[4, 6] == c[6, 6] == c[5, 5] == c[5, 7] == 40 and c[4, 5] == c[6, 7] == 0 and c.sum() == 5 * 40
+    for n in (2, 4, 8):
+        b = 8 // n
+        want = np.zeros((rows // b, W // b), np.uint8)
+        for (y, x) in ((5, 6), (4, 6), (6, 6), (5, 5), (5, 7)):
+            want[y // b, x // b] = 1
+        assert np.array_equal(api.refine_mask(frame, W, rows, n, 40), want)
+        assert not api.refine_mask(frame, W, rows, n, 41).any()
+
+
+@pytest.mark.parametrize("key,W,H", [("render_map_160x120_d4", 160, 120), ("render_map_320x240_d4", 320, 240), ("render_map_160x120_d15", 160, 120)])
+def test_mask_of_golden_frames(golden_frames, key, W, H):
+    frame = golden_frames[key]
+    for n in (2, 4, 8):
+        for T in THRESHOLDS:
+            assert np.array_equal(api.refine_mask(frame, W, H, n, T), refine_mask_np(frame, W, H, n, T)), (key, n, T)
+        share = float(api.refine_mask(frame, W, H, n, 16).mean())
+        print(f"{key} n={n} T=16: {share * 100:.1f} % of the blocks refined")
+        assert 0.0 < share < 1.0
+    # a strip is classified on its own rows: its mask is the mask of those rows alone
+    r0, rows = 40, 44
+    part = frame.reshape(H, W)[r0:r0 + rows].reshape(-1)
+    assert np.array_equal(api.refine_mask(part, W, rows, 2, 16), refine_mask_np(part, W, rows, 2, 16))
+
+
+def test_bad_arguments_return_zero():
+    L = api.load_library()
+    frame = np.zeros(64, np.uint32)
+    out = np.full(64, 7, np.uint8)
+    ok = lambda *a: L.clw_host_refine_mask(*a)
+    assert ok(api._ptr(frame), 8, 8, 2, 16, api._ptr(out)) == 1
+    for n in (0, 1, 3, 5, 16):
+        assert ok(api._ptr(frame), 8, 8, n, 16, api._ptr(out)) == 0
+    for T in (-1, 257, 300, -2 ** 31):
+        assert ok(api._ptr(frame), 8, 8, 2, T, api._ptr(out)) == 0
+    assert ok(None, 8, 8, 2, 16, api._ptr(out)) == 0 and ok(api._ptr(frame), 8, 8, 2, 16, None) == 0
+    with pytest.raises(ValueError):
+        api.refine_mask(frame, 8, 8, 3, 16)
+    with pytest.raises(ValueError):
+        api.refine_mask(frame, 8, 8, 2, 300)
+    with pytest.raises(ValueError):
+        api.refine_mask(frame, 8, 9, 2, 16)
+
+
+def test_composite_takes_refined_blocks_from_the_fine_frame():
+    W, rows, n = 10, 6, 2                                # blocks of 4 x 4, partial on both edges
+    mask = np.array([[1, 0, 1], [0, 1, 0]], np.uint8)
+    m = pixel_mask(mask, W, rows, n).reshape(rows, W)
+    assert m[:4, :4].all() and not m[:4, 4:8].any() and m[:4, 8:].all() and not m[4:, :4].any() and m[4:, 4:8].all() and not m[4:, 8:].any()
+    base, fine = np.zeros(W * rows, np.uint32), np.ones(W * rows, np.uint32)
+    assert np.array_equal(composite(mask, W, rows, n, base, fine), m.reshape(-1).astype(np.uint32))
+    fb, ff = np.zeros((W * rows, 3), np.float32), np.ones((W * rows, 3), np.float32)
+    assert np.array_equal(composite(mask, W, rows, n, fb, ff)[:, 1], m.reshape(-1).astype(np.float32))

@@ -1,0 +1,380 @@
+"""Adaptive supersampling (clw_ext_set_adaptive, Renderer(supersample=n, adaptive=T)) on a real GPU.
+
+The definition every test uses (adaptive_common.py): the adaptive frame is, per block of 8/n x 8/n pixels, the plain supersampled frame where
+the block's 1-sample pixels show a contrast of at least T, and the 1-sample frame elsewhere -- bit for bit, packed and float.  The 1-sample
+frame, the plain supersampled frame and the mask are the GPU's own (the mask through api.refine_mask = clw_host_refine_mask, and read back
+with read_refine_mask); one test holds the strict build to the CPU oracle's frames."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from adaptive_common import composite, frames, pixel_mask, resolve, same_floats
+from conftest import CAM, ROOT
+
+pytestmark = pytest.mark.gpu
+
+F_DEEP, F_GRID, F_OCC, F_SHAPE, F_SS, F_LIST = 2, 16, 32, 256, 1 << 17, 1 << 19      # WT_F_* of csrc/whitted_trace.inc (clw_ext_last_trace_flags)
+SHAPES = [(320, 240, 2), (200, 152, 4), (96, 64, 8), (101, 75, 2)]
+COUNTED = ("segments", "shadow_rays", "light_probes", "sky_fetches", "texel_fetches", "pushes")
+
+
+@pytest.fixture(scope="module")
+def R():
+    import torch  # noqa: F401
+    from example_gui_opencl_raytracer_amd.renderer import Renderer
+    return Renderer
+
+
+@pytest.fixture(scope="module")
+def api():
+    import torch  # noqa: F401  (before the shim is loaded: both then share the ROCm runtime torch ships)
+    from example_gui_opencl_raytracer_amd import api
+    return api
+
+
+_refs = {}
+
+
+def refs(R, name, sc, tex, sky, W, H, n, depth, strict, **kw):
+    """(1-sample packed, float, plain supersampled packed, float, its flags) of a configuration, rendered once per module"""
+    key = (name, W, H, n, depth, strict, tuple(sorted(kw.items())))
+    if key not in _refs:
+        ((bp, bf),), _ = frames(R, sc, tex, sky, W, H, depth, strict, **kw)
+        ((fp, ff),), flags = frames(R, sc, tex, sky, W, H, depth, strict, n=n, **kw)
+        for a in (bp, bf, fp, ff):
+            a.setflags(write=False)
+        _refs[key] = (bp, bf, fp, ff, flags)
+    return _refs[key]
+
+
+def adaptive(R, sc, tex, sky, W, H, depth, strict, n, T, count=1, setup=None, **kw):
+    """`count` adaptive frames in a row from one renderer -> ([(packed, float, mask) ...], flags of the last trace launch)"""
+    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, adaptive=T, **kw)
+    try:
+        if setup:
+            setup(r.w)
+        r.look(**CAM)
+        out = []
+        for _ in range(count):
+            p, f = r.render_rgb()
+            out.append((p.copy(), f.copy(), r.w.read_refine_mask()))
+        return out, r.w.last_trace_flags()
+    finally:
+        r.release()
+
+
+def check_composite(api, ref, got, W, rows, n, T, what):
+    """every frame of `got` == where(mask, fine, base) with mask = the host definition on the GPU's own base frame -> the mask"""
+    bp, bf, fp, ff, _ = ref
+    mask = api.refine_mask(bp, W, rows, n, T)
+    want_p, want_f = composite(mask, W, rows, n, bp, fp), composite(mask, W, rows, n, bf, ff)
+    for k, (p, f, m) in enumerate(got):
+        print(f"{what} frame {k}: {mask.mean() * 100:.1f} % of {mask.size} blocks refined, {int((m != mask.reshape(-1)).sum())} mask bytes differ, "
+              f"{int((p != want_p).sum())} packed pixels differ, {int((f.view(np.uint32) != want_f.view(np.uint32)).any(1).sum())} float")
+        assert np.array_equal(m, mask.reshape(-1)), (what, k)
+        assert np.array_equal(p, want_p), (what, k)
+        assert same_floats(f, want_f), (what, k)
+    return mask
+
+
+# ------------------------------------------------------------------ the setter
+def test_get_returns_what_set_and_the_environment_set(api):
+    w = api.ClWrap()
+    assert w.get_adaptive() == -1
+    for T in (0, 16, 256, -1, 64):
+        w.set_adaptive(T)
+        assert w.get_adaptive() == T
+    assert w.read_refine_mask().size == 0
+    w.release()
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "from example_gui_opencl_raytracer_amd import api\n"
+            "w = api.ClWrap(); print('adaptive', w.get_adaptive()); w.release()\n" % ROOT)
+    for T in ("0", "16", "256"):
+        p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, CLWRAP_ADAPTIVE=T), timeout=300)
+        assert p.returncode == 0 and f"adaptive {T}" in p.stdout, p.stdout + p.stderr
+
+
+# ------------------------------------------------------------------ 1. the composite, exact, both builds
+@pytest.mark.parametrize("strict", [True, False], ids=["strict", "fast"])
+@pytest.mark.parametrize("W,H,n", SHAPES)
+def test_frame_is_the_composite_of_the_gpus_own_frames(R, api, demo_scene, tex, sky, W, H, n, strict):
+    ref = refs(R, "demo", demo_scene, tex, sky, W, H, n, 4, strict)
+    got, flags = adaptive(R, demo_scene, tex, sky, W, H, 4, strict, n, 16)
+    assert flags & F_SS and flags & F_LIST and not flags & F_DEEP and flags == ref[4] | F_LIST
+    if not strict:
+        assert flags & F_SHAPE
+    mask = check_composite(api, ref, got, W, H, n, 16, f"{W}x{H} n={n} strict={int(strict)}")
+    assert 0 < mask.sum() < mask.size                      # (the oracle gives 58-79 % at these shapes)
+    assert not np.array_equal(got[0][0], ref[0]) and not np.array_equal(got[0][0], ref[2])
+
+
+# ------------------------------------------------------------------ 2. the two ends of the threshold
+@pytest.mark.parametrize("strict", [True, False], ids=["strict", "fast"])
+@pytest.mark.parametrize("W,H,n", SHAPES)
+def test_threshold_0_is_the_supersampled_frame_and_256_the_one_sample_frame(R, demo_scene, tex, sky, W, H, n, strict):
+    bp, bf, fp, ff, _ = refs(R, "demo", demo_scene, tex, sky, W, H, n, 4, strict)
+    ((p, f, m),), flags = adaptive(R, demo_scene, tex, sky, W, H, 4, strict, n, 0)
+    assert flags & F_LIST and m.size == (-(-H * n // 8)) * (-(-W * n // 8)) and m.all()
+    assert np.array_equal(p, fp) and same_floats(f, ff)
+    ((p, f, m),), flags = adaptive(R, demo_scene, tex, sky, W, H, 4, strict, n, 256)
+    assert flags & F_LIST and not m.any()
+    assert np.array_equal(p, bp) and same_floats(f, bf)
+
+
+# ------------------------------------------------------------------ 3. deep launches: the tail on the list-driven flavour, the base pass on its sorted order
+@pytest.mark.parametrize("strict", [True, False], ids=["strict", "fast"])
+def test_deep_frames(R, api, demo_scene, tex, sky, strict):
+    W, H, n, depth = 400, 300, 2, 15
+    ref = refs(R, "demo", demo_scene, tex, sky, W, H, n, depth, strict)
+    ways = dict(default=None, tail_off=lambda w: w.set_tpt(0), unsorted=lambda w: w.set_tile_sched(0))
+    for name, setup in ways.items():
+        got, flags = adaptive(R, demo_scene, tex, sky, W, H, depth, strict, n, 16, count=3, setup=setup)
+        assert flags & F_DEEP and flags & F_LIST and not flags & F_OCC
+        mask = check_composite(api, ref, got, W, H, n, 16, f"deep {name} strict={int(strict)}")
+        assert 0 < mask.sum() < mask.size
+
+
+# ------------------------------------------------------------------ 4. the uniform grid
+@pytest.mark.parametrize("strict", [True, False], ids=["strict", "fast"])
+def test_uniform_grid_scene(R, api, tex, sky, strict):
+    from example_gui_opencl_raytracer_amd import scene
+    sc = scene.sphere_grid_scene(24, 24)          # 576 spheres
+    W, H, n = 160, 120, 2
+    for depth in (4, 6):
+        ref = refs(R, "grid", sc, tex, sky, W, H, n, depth, strict)
+        got, flags = adaptive(R, sc, tex, sky, W, H, depth, strict, n, 16, count=2)
+        assert flags & F_GRID and flags & F_LIST and bool(flags & F_DEEP) == (depth == 6)
+        mask = check_composite(api, ref, got, W, H, n, 16, f"grid depth {depth} strict={int(strict)}")
+        assert 0 < mask.sum() < mask.size
+
+
+# ------------------------------------------------------------------ 5. the strict build against the oracle
+@pytest.mark.parametrize("W,H,n,depth", [(200, 152, 4, 4), (320, 240, 2, 4)])
+def test_strict_frame_is_the_composite_of_the_oracles_frames(R, api, oracle, demo_scene, tex, sky, W, H, n, depth):
+    """The strict build differs from glibc on isolated 1-ulp sinf / cosf / powf inputs (profiles/r03_libm_divergence.jsonl).  A base pixel that
+    differs changes its own contrast and its 4-neighbours', so the blocks that hold such a pixel in themselves or in the one-pixel ring around
+    them are left out, and so are the blocks whose footprint holds a virtual pixel that differs: at most 4 pixels of either kind."""
+    b = 8 // n
+    cam = oracle.camera(CAM["origin"], CAM["look"], CAM["fov"], CAM["focal"], W, H)
+    want_base, _, _ = oracle.render(cam, demo_scene, tex, sky, depth)
+    cam = oracle.camera(CAM["origin"], CAM["look"], CAM["fov"], CAM["focal"], n * W, n * H)
+    want_virt_p, want_virt_f, _ = oracle.render(cam, demo_scene, tex, sky, depth, want_rgb=True)
+    want_fine, _ = resolve(want_virt_f, W, H, n)
+    bp = refs(R, "demo", demo_scene, tex, sky, W, H, n, depth, True)[0]
+    (virt,), _ = frames(R, demo_scene, tex, sky, n * W, n * H, depth, True, rgb=False)
+    base_differs, virt_differs = (bp != want_base).reshape(H, W), (virt[0] != want_virt_p).reshape(n * H, n * W)
+    print(f"{W}x{H} n={n} depth {depth}: {int(base_differs.sum())} base pixels and {int(virt_differs.sum())} virtual pixels differ from the oracle's")
+    assert base_differs.sum() <= 4 and virt_differs.sum() <= 4
+    near = np.zeros((H + 2, W + 2), bool)                  # a differing base pixel and the ring around it
+    for dy in range(3):
+        for dx in range(3):
+            near[dy:dy + H, dx:dx + W] |= base_differs
+    br, bc = -(-H // b), -(-W // b)
+    bpad = np.zeros((br * b, bc * b), bool)
+    bpad[:H, :W] = near[1:H + 1, 1:W + 1]                  # = some pixel of this pixel's 3 x 3 neighbourhood differs
+    out = bpad.reshape(br, b, bc, b).any((1, 3))           # = the block or its one-pixel ring holds a differing pixel
+    vpad = np.zeros((br * 8, bc * 8), bool)
+    vpad[:n * H, :n * W] = virt_differs
+    out |= vpad.reshape(br, 8, bc, 8).any((1, 3))
+    keep = ~pixel_mask(out, W, H, n)
+    print(f"  {int(out.sum())} of {out.size} blocks left out")
+    mask = api.refine_mask(want_base, W, H, n, 16)
+    want = composite(mask, W, H, n, want_base, want_fine)
+    ((p, _, m),), flags = adaptive(R, demo_scene, tex, sky, W, H, depth, True, n, 16)
+    assert flags & F_LIST
+    print(f"  {int((p[keep] != want[keep]).sum())} kept pixels differ, {int((m.reshape(br, bc)[~out] != mask[~out]).sum())} kept mask bytes")
+    assert np.array_equal(m.reshape(br, bc)[~out], mask[~out])
+    assert np.array_equal(p[keep], want[keep])
+    assert 0 < mask.sum() < mask.size
+
+
+# ------------------------------------------------------------------ 6. one wrapper across frames
+@pytest.mark.parametrize("strict", [True, False], ids=["strict", "fast"])
+def test_changing_threshold_and_factor_between_frames(R, demo_scene, tex, sky, strict):
+    """One wrapper, threshold and factor changed between frames of a deep launch: the scheduling state switches between the base pass's W x H
+    tiles and the plain launch's virtual ones, the list buffers follow the factor.  Packed and float frames, flags, mask; the tile costs of
+    the frames with the mode off."""
+    W, H, depth = 160, 120, 15
+    seq = [(2, 16), (2, 16), (2, 256), (2, 0), (2, -1), (8, 16), (8, -1), (4, 16), (4, 0), (4, -1), (2, 16)]      # (n, T)
+    want = {}
+    for n, T in set(seq):
+        r = R(demo_scene, tex, sky, W, H, depth=depth, strict=strict, supersample=n, adaptive=None if T < 0 else T)
+        r.look(**CAM)
+        p, f = r.render_rgb()
+        want[n, T] = (p.copy(), f.copy(), r.w.last_trace_flags(), r.w.read_tile_costs(), r.w.read_refine_mask())
+        r.release()
+    r = R(demo_scene, tex, sky, W, H, depth=depth, strict=strict)
+    r.look(**CAM)
+    for n, T in seq:
+        r.w.set_supersample(n)
+        r.w.set_adaptive(T)
+        p, f = r.render_rgb()
+        frame, rgb, flags, costs, mask = want[n, T]
+        assert np.array_equal(p, frame) and same_floats(f, rgb), (n, T)
+        assert r.w.last_trace_flags() == flags and bool(flags & F_LIST) == (T >= 0), (n, T)
+        assert np.array_equal(r.w.read_refine_mask(), mask) and (mask.size != 0) == (T >= 0), (n, T)
+        got_costs = r.w.read_tile_costs()
+        if T < 0:                     # the plain supersampled launch, on scheduling state of its own: the virtual frame's tiles
+            assert np.array_equal(got_costs, costs), (n, T)
+        else:                         # the base pass's: an ordinary 1-sample launch of W x H
+            assert got_costs.size == costs.size == (-(-W // 8)) * (-(-H // 8)), (n, T)
+    r.release()
+    (plain,), pflags = frames(R, demo_scene, tex, sky, W, H, depth, strict, n=2)
+    assert np.array_equal(want[2, -1][0], plain[0]) and same_floats(want[2, -1][1], plain[1]) and want[2, -1][2] == pflags
+    assert np.array_equal(want[2, 0][0], plain[0]) and same_floats(want[2, 0][1], plain[1])
+    assert len({v[0].tobytes() for k, v in want.items() if k[0] == 2}) == 3          # T = 16, 256 and (0 = off) differ
+
+
+# ------------------------------------------------------------------ 7. strips: each is the composite of its own range
+@pytest.mark.parametrize("strict", [True, False], ids=["strict", "fast"])
+def test_row_strips_are_composites_of_their_own_range(R, api, demo_scene, tex, sky, strict):
+    from example_gui_opencl_raytracer_amd.renderer import strip_rows
+    W, H, n, depth, T = 400, 300, 4, 4, 16
+    bp, bf, fp, ff, _ = refs(R, "demo", demo_scene, tex, sky, W, H, n, depth, strict)
+    full, _ = adaptive(R, demo_scene, tex, sky, W, H, depth, strict, n, T)
+    parts = []
+    for rank in range(3):
+        r0, rows = strip_rows(H, 3, rank)
+        cut = lambda a: a[r0 * W:(r0 + rows) * W]
+        got, flags = adaptive(R, demo_scene, tex, sky, W, H, depth, strict, n, T, first_row=r0, rows=rows)
+        assert flags & F_LIST and got[0][0].shape == (rows * W,)
+        check_composite(api, (cut(bp), cut(bf), cut(fp), cut(ff), 0), got, W, rows, n, T, f"strip {rank} strict={int(strict)}")
+        parts.append(got[0][0])
+    differ = np.flatnonzero(np.concatenate(parts) != full[0][0]) // W
+    print(f"rows where the strips differ from the full frame: {sorted(set(differ.tolist()))}")
+    edges = {r for rank in range(3) for r0, rows in [strip_rows(H, 3, rank)] for r in (r0, r0 + 1, r0 + rows - 2, r0 + rows - 1)}
+    assert set(differ.tolist()) <= edges                   # only the blocks at a strip's boundary can see another neighbourhood
+
+
+# ------------------------------------------------------------------ 8. counters: the sum of both passes
+@pytest.mark.parametrize("W,H,n", [(200, 152, 4), (101, 75, 2)])
+def test_counters_add_up_over_both_passes(R, api, demo_scene, tex, sky, W, H, n):
+    depth, b = 4, 8 // n
+
+    def counted(k, T):
+        r = R(demo_scene, tex, sky, W, H, depth=depth, strict=True, supersample=k, adaptive=T)
+        r.look(**CAM)
+        r.w.enable_counters(1)
+        p = r.render().copy()
+        c = r.w.read_counters()
+        mask = r.w.read_refine_mask()
+        r.release()
+        return p, {x: c[x] for x in COUNTED}, mask
+
+    base_p, base_c, _ = counted(1, None)
+    _, fine_c, _ = counted(n, None)
+    _, c0, m0 = counted(n, 0)
+    assert m0.all() and c0 == {x: base_c[x] + fine_c[x] for x in COUNTED}
+    _, c256, m256 = counted(n, 256)
+    assert not m256.any() and c256 == base_c
+    _, c16, m16 = counted(n, 16)
+    mask = api.refine_mask(base_p, W, H, n, 16)
+    assert np.array_equal(m16, mask.reshape(-1))
+    full = mask[:H // b, :W // b]                          # blocks that lie wholly inside the frame: 64 samples each
+    print(f"{W}x{H} n={n}: segments {c16['segments']} (base {base_c['segments']}, plain {fine_c['segments']}), {int(full.sum())} full blocks refined")
+    assert c16["segments"] >= W * H + 64 * int(full.sum())
+    for x in COUNTED:
+        assert base_c[x] <= c16[x] <= c0[x], x
+
+
+# ------------------------------------------------------------------ 9. async: queued behind each other on the caller's stream, one timed launch per frame
+def test_async_frames_on_a_side_stream(R, api, demo_scene, tex, sky):
+    import torch
+    W, H, n, depth = 320, 240, 2, 4
+    bp, _, fp, _, _ = refs(R, "demo", demo_scene, tex, sky, W, H, n, depth, False)
+    Ts = [16, 256, 0, 16, 64]
+    want = {T: composite(api.refine_mask(bp, W, H, n, T), W, H, n, bp, fp) for T in set(Ts)}
+    fb = torch.zeros(W * H, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    r = R(demo_scene, tex, sky, W, H, depth=depth, supersample=n, framebuffer_ptr=fb.data_ptr())
+    r.w.set_stream(side.cuda_stream)
+    r.w.set_async(True)
+    r.look(**CAM)
+    r.w.timing_reset()
+    outs = []
+    for T in Ts:
+        r.w.set_adaptive(T)
+        r.render(readback=False)
+        with torch.cuda.stream(side):
+            outs.append(fb.clone())
+    r.w.sync()
+    launches, ms = r.w.timing_get(1)
+    assert launches == len(Ts) and 0.0 < ms < 1000.0       # base + classify + refine are timed as one launch
+    for T, o in zip(Ts, outs):
+        assert np.array_equal(o.cpu().numpy().view(np.uint32), want[T]), T
+    assert np.array_equal(r.w.read_refine_mask(), api.refine_mask(bp, W, H, n, Ts[-1]).reshape(-1))
+    r.w.set_stream(0)                                       # the lists are fenced when the stream changes
+    r.w.set_adaptive(16)
+    r.render(readback=False)
+    r.w.sync()
+    assert np.array_equal(fb.cpu().numpy().view(np.uint32), want[16])
+    r.release()
+
+
+# ------------------------------------------------------------------ 10. refusals: message + exit(1)
+def _run(snippet, env=None):
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "import numpy as np\n"
+            "import torch\n"
+            "from example_gui_opencl_raytracer_amd import api, scene, textures\n"
+            "from example_gui_opencl_raytracer_amd.renderer import Renderer\n"
+            "CAM = %r\n"
+            "sc, tex, sky = scene.render_map_scene(), textures.texture_layers(), textures.skybox_cross(64)\n" % (ROOT, CAM)) + snippet
+    return subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
+
+
+REFUSED = {
+    "factor_1": "r = Renderer(sc, tex, sky, 64, 48, depth=2, adaptive=16); r.look(**CAM); r.render()",
+    "lens": "r = Renderer(sc, tex, sky, 64, 48, depth=2, supersample=2, lens=(0.1, 8.0), adaptive=16); r.look(**CAM); r.render()",
+    "camera_table": ("r = Renderer(sc, tex, sky, 64, 48, depth=2, supersample=2, adaptive=16); cam = r.look(**CAM)\n"
+                     "r.set_sample_cameras(api.lens_cameras(cam, 0.1, 8.0, 2)); r.render()"),
+    "moving_spheres": ("r = Renderer(sc, tex, sky, 64, 48, depth=2, supersample=2, adaptive=16, motion=np.full((4, 3), 0.1, np.float32))\n"
+                       "r.look(**CAM); r.render()"),
+    "two_kernel_path": "r = Renderer(sc, tex, sky, 64, 48, depth=2, fuse=False, supersample=2, adaptive=16); r.look(**CAM); r.render()",
+    "more_than_4095_blocks": "r = Renderer(sc, tex, sky, 4096, 8, depth=1, supersample=8, adaptive=16); r.look(**CAM); r.render(readback=False)",
+    "threshold_300": "w = api.ClWrap(); w.set_adaptive(300)",
+    "threshold_minus_2": "w = api.ClWrap(); w.set_adaptive(-2)",
+}
+
+
+@pytest.mark.parametrize("case", sorted(REFUSED))
+def test_unsupported_combinations_exit_with_a_message(case):
+    p = _run(REFUSED[case] + "\nprint('unreachable')")
+    assert p.returncode == 1 and "ERROR:\t" in p.stdout and "daptive" in p.stdout and "unreachable" not in p.stdout, p.stdout + p.stderr
+
+
+@pytest.mark.parametrize("value", ["abc", "300", "-1", "16x"])
+def test_bad_environment_value_exits(value):
+    p = _run("api.ClWrap()\nprint('unreachable')", env=dict(os.environ, CLWRAP_ADAPTIVE=value))
+    assert p.returncode == 1 and "ERROR:\t" in p.stdout and "CLWRAP_ADAPTIVE" in p.stdout and "daptive" in p.stdout and "unreachable" not in p.stdout, p.stdout + p.stderr
+
+
+# ------------------------------------------------------------------ 11. default untouched
+@pytest.mark.parametrize("n", [1, 2])
+def test_mode_off_set_explicitly_is_the_default(R, demo_scene, tex, sky, n):
+    from example_gui_opencl_raytracer_amd.renderer import Renderer
+    W, H, depth = 1280, 720, 4
+    for strict in (False, True):
+        res = []
+        for explicit in (False, True):
+            r = Renderer(demo_scene, tex, sky, W, H, depth=depth, strict=strict, supersample=n)
+            if explicit:
+                r.w.set_adaptive(-1)
+            r.look(**CAM)
+            frame = r.render().copy()
+            frame2 = r.render().copy()
+            flags = r.w.last_trace_flags()
+            costs = r.w.read_tile_costs()
+            assert r.w.read_refine_mask().size == 0 and r.w.get_adaptive() == -1
+            r.w.enable_counters(1)
+            r.render()
+            c = r.w.read_counters()
+            r.release()
+            res.append((frame, frame2, costs, [c[k] for k in COUNTED], flags))
+        assert not res[0][4] & F_LIST and bool(res[0][4] & F_SS) == (n > 1) and res[0][4] == res[1][4]
+        assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1])
+        assert np.array_equal(res[0][2], res[1][2]) and res[0][3] == res[1][3]
