@@ -42,6 +42,8 @@ SYMBOLS = [
     "clw_ext_set_sample_cameras", "clw_ext_get_sample_cameras", "clw_ext_set_lens", "clw_host_lens_cameras", "clw_host_shutter_cameras",
     "clw_ext_set_sphere_motion", "clw_ext_get_sample_times", "clw_host_sample_times", "clw_host_spheres_at",
     "clw_ext_set_adaptive", "clw_ext_get_adaptive", "clw_ext_read_refine_mask", "clw_host_refine_mask",
+    "clw_ext_set_seed_offset", "clw_ext_get_seed_offset", "clw_ext_set_accumulate", "clw_ext_get_accumulated", "clw_ext_reset_accumulation",
+    "clw_host_frame_seed", "clw_host_jitter_camera",
 ]
 
 
@@ -148,6 +150,18 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         L.clw_ext_read_refine_mask.restype = u32
         L.clw_host_refine_mask.argtypes = [vp, u32, u32, u32, C.c_int, vp]
         L.clw_host_refine_mask.restype = C.c_int
+    if hasattr(L, "clw_ext_set_accumulate") or not os.environ.get("CLWRAP_LIB"):          # (an older A/B build may lack them)
+        L.clw_ext_set_seed_offset.argtypes = [W, u32]
+        L.clw_ext_get_seed_offset.argtypes = [W]
+        L.clw_ext_get_seed_offset.restype = u32
+        L.clw_ext_set_accumulate.argtypes = [W, C.c_int, C.c_int]
+        L.clw_ext_get_accumulated.argtypes = [W]
+        L.clw_ext_get_accumulated.restype = u32
+        L.clw_ext_reset_accumulation.argtypes = [W]
+        L.clw_host_frame_seed.argtypes = [u32]
+        L.clw_host_frame_seed.restype = u32
+        L.clw_host_jitter_camera.argtypes = [C.POINTER(clw_camera), u32, u32, C.POINTER(clw_camera)]
+        L.clw_host_jitter_camera.restype = C.c_int
     L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
     L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
     L.clw_ext_read_tile_costs.restype = u32
@@ -237,6 +251,20 @@ def refine_mask(xrgb, width: int, rows: int, n: int, threshold: int) -> np.ndarr
     out = np.zeros((-(-rows // b), -(-width // b)), np.uint8)
     if not load_library().clw_host_refine_mask(_ptr(xrgb), width, rows, n, int(threshold), _ptr(out)):
         raise ValueError("clw_host_refine_mask rejects these arguments (threshold in [0, 256])")
+    return out
+
+
+def frame_seed(f: int) -> int:
+    """clw_host_frame_seed: the seed offset frame f of an accumulated view adds (0 for frame 0, distinct for every frame of a run)."""
+    return int(load_library().clw_host_frame_seed(int(f) & 0xFFFFFFFF))
+
+
+def jitter_camera(cam: clw_camera, f: int, n: int = 1) -> clw_camera:
+    """clw_host_jitter_camera: the camera frame f of an accumulated view looks through -- `cam` moved by the frame's Halton (2, 3) point inside
+    the cell of a sample of supersampling factor n (1, 2, 4, 8); frame 0 is `cam` itself."""
+    out = clw_camera()
+    if not load_library().clw_host_jitter_camera(C.byref(cam), int(f), int(n), C.byref(out)):
+        raise ValueError("clw_host_jitter_camera rejects these arguments (n in 1, 2, 4, 8)")
     return out
 
 
@@ -370,6 +398,12 @@ class ClWrap:
     def set_debug_rgb(self, ptr): self.L.clw_ext_set_debug_rgb(C.byref(self.w), C.c_void_p(ptr))
     def set_supersample(self, n): self.L.clw_ext_set_supersample(C.byref(self.w), int(n))
     def get_supersample(self): return int(self.L.clw_ext_get_supersample(C.byref(self.w)))
+
+    def set_seed_offset(self, s): self.L.clw_ext_set_seed_offset(C.byref(self.w), int(s) & 0xFFFFFFFF)
+    def get_seed_offset(self): return int(self.L.clw_ext_get_seed_offset(C.byref(self.w)))
+    def set_accumulate(self, max_frames, jitter=True): self.L.clw_ext_set_accumulate(C.byref(self.w), int(max_frames), int(jitter))
+    def get_accumulated(self): return int(self.L.clw_ext_get_accumulated(C.byref(self.w)))
+    def reset_accumulation(self): self.L.clw_ext_reset_accumulation(C.byref(self.w))
 
     def set_adaptive(self, threshold): self.L.clw_ext_set_adaptive(C.byref(self.w), int(threshold))
     def get_adaptive(self): return int(self.L.clw_ext_get_adaptive(C.byref(self.w)))

@@ -42,7 +42,7 @@ extern "C" hipError_t wt_fast_launch_sched(const unsigned*, unsigned*, unsigned,
 
 namespace {
 
-enum { F_COUNT = 1, F_DEEP = 2, F_GEOM_LDS = 4, F_RAYS = 8, F_GRID = 16, F_OCC = 32, F_D8 = 64, F_D16 = 128, F_SHAPE = 256, F_SS = 1 << 17, F_MOVE = 1 << 18, F_LIST = 1 << 19 }; /* = WT_F_* of whitted_trace.inc */
+enum { F_COUNT = 1, F_DEEP = 2, F_GEOM_LDS = 4, F_RAYS = 8, F_GRID = 16, F_OCC = 32, F_D8 = 64, F_D16 = 128, F_SHAPE = 256, F_SS = 1 << 17, F_MOVE = 1 << 18, F_LIST = 1 << 19, F_ACC = 1 << 20 }; /* = WT_F_* of whitted_trace.inc */
 /* shallow fast launches of small LDS-geometry scenes run a kernel with the scene's counts compiled in (wt_shape of whitted_trace.inc): the
  * counts whitted_launch.inc instantiates -- 1..SHAPE_MAX_SPHERES spheres, 0..SHAPE_MAX_PLANES planes, SHAPE_LIGHTS lights */
 constexpr uint32_t SHAPE_MAX_SPHERES = 4, SHAPE_MAX_PLANES = 2, SHAPE_LIGHTS = 3;
@@ -191,6 +191,29 @@ struct Impl {
     std::vector<float> times_used;               /* the times of the latest trace launch (clw_ext_get_sample_times) */
     float* d_motion = nullptr;
     std::vector<float> motion_dev;               /* what d_motion holds once the stream gets there; empty = nothing yet */
+    /* the seed offset of every trace launch (clw_ext_set_seed_offset / CLWRAP_SEED_OFFSET): a work-item's xorshift state starts at id + seed_offset */
+    uint32_t seed_offset = 0;
+    /* progressive frame accumulation (clw_ext_set_accumulate / CLWRAP_ACCUMULATE, CLWRAP_ACC_JITTER): frame f = K of a still view is traced with
+     * seed offset seed_offset + clw_host_frame_seed(f) through clw_host_jitter_camera(latched camera, f, n) and folded into `sum` by the trace
+     * kernel's epilogue (whitted_params.h: acc_sum); the key is everything that defines the image -- a launch whose key differs from the previous
+     * one's starts again at frame 0.  `sum` follows the launch range and is fenced across a change of stream like the tables (tables_fence). */
+    int acc_max = 0, acc_jitter = 1;          /* frames a still view accumulates (0 = the mode is off); per-frame sub-pixel offset on / off */
+    struct AccKey {
+        RaygenArgs gen{}; uint64_t n_out = 0; uint32_t total = 0;
+        int depth = 0, strict = 0, fuse = 0, ss = 0, max_frames = 0, jitter = 0;
+        float through = 0.0f; uint32_t seed = 0;
+        const Buffer* buf[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   /* rays, spheres, planes, lights, textures, skybox, framebuffer */
+        const void* dptr[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t size[7] = {0, 0, 0, 0, 0, 0, 0};
+        uint32_t counts[3] = {0, 0, 0}, img[5] = {0, 0, 0, 0, 0};
+        uint64_t epoch = 0;
+    };
+    struct Accum {
+        float* sum = nullptr; size_t pixels = 0;      /* 3 floats per output pixel of the launch range */
+        uint32_t K = 0;                               /* frames in the sum */
+        int frame = -1;                               /* the frame the trace launch under way folds in; -1 = not an accumulated launch */
+        uint64_t epoch = 0;                           /* bumped by whatever changes the image behind the key's back (uploads, invalidate, reset) */
+        bool key_valid = false; AccKey key;
+    } acc;
     /* prepared scene cache */
     const Buffer *prep_s = nullptr, *prep_p = nullptr, *prep_l = nullptr;
     uint32_t prep_ns = 0, prep_np = 0, prep_nl = 0;
@@ -254,6 +277,13 @@ struct Impl {
     uint32_t timing_every = 1, timing_tick = 0;   /* events around every n-th launch only */
     std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
 };
+
+bool same_acc_key(const Impl::AccKey& a, const Impl::AccKey& b) {
+    return same_raygen(a.gen, b.gen) && a.n_out == b.n_out && a.total == b.total && a.depth == b.depth && a.strict == b.strict && a.fuse == b.fuse &&
+           a.ss == b.ss && a.max_frames == b.max_frames && a.jitter == b.jitter && !memcmp(&a.through, &b.through, 4) && a.seed == b.seed &&
+           !memcmp(a.buf, b.buf, sizeof a.buf) && !memcmp(a.dptr, b.dptr, sizeof a.dptr) && !memcmp(a.size, b.size, sizeof a.size) &&
+           !memcmp(a.counts, b.counts, sizeof a.counts) && !memcmp(a.img, b.img, sizeof a.img) && a.epoch == b.epoch;
+}
 
 Impl* impl_of(const cl_wrap* w) {
     if (!w || !w->impl) die("cl_wrap is not initialised");
@@ -554,7 +584,8 @@ struct Strip { uint32_t row0, rows; int slot; };
  * the factor-1 launch in everything (scheduling state included), or its refine pass, the supersampled launch served from the classifier's list */
 enum TracePass { PASS_PLAIN = 0, PASS_BASE = 1, PASS_REFINE = 2 };
 
-void trace_launch(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Strip* strip, TracePass pass) {
+/* -> whether a kernel was launched (an empty range launches none) */
+bool trace_launch(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Strip* strip, TracePass pass) {
     Kernel& k = I->kernels[kid];
     const char* who = pass == PASS_PLAIN ? "Supersampling" : "Adaptive supersampling";
     /* arg 0: the ray buffer, passed by value as the 8 bytes of a handle (raypng.c:61) or bound as a buffer */
@@ -573,7 +604,7 @@ void trace_launch(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Str
     uint64_t n64 = rounded < total ? rounded : total;      /* guard `id >= total_size` (raytracing.cl:24) */
     ensure_allocated(I, out);
     if (n64 > out->size / 4) n64 = out->size / 4;          /* never write past the framebuffer */
-    if (n64 == 0) return;
+    if (n64 == 0) return false;
     if (n64 > 0xFFFFFFFFull) die("Couldn't run the kernel");
 
     whitted_params P{};
@@ -585,6 +616,7 @@ void trace_launch(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Str
     P.untrimmed = (I->variant & 16384) ? 1u : 0u;
     P.out = (uint32_t*)out->dptr;
     P.out_rgb = I->debug_rgb;
+    P.seed_offset = I->seed_offset;
     P.diag = (I->variant & 512) ? (env_int("CLWRAP_TIMELINE_EDGES", 0) ? 255u + (uint32_t)env_int("CLWRAP_TIMELINE_EDGES", 0) : 1u + (uint32_t)env_int("CLWRAP_TIMELINE_SHIFT", 0)) : 0u;
 
     const int ss = pass == PASS_BASE ? 1 : I->supersample;
@@ -628,7 +660,32 @@ void trace_launch(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Str
         P.id_offset = g.id_offset;
         P.band_stride = g.band_stride; P.band_phase = g.band_phase;
         if (P.n_items > g.n_items) P.n_items = g.n_items; /* rays past the generated range are undefined in the reference */
-        if (P.n_items == 0) return;
+        if (P.n_items == 0) return false;
+        if (I->acc.frame >= 0) {
+            /* frame f of an accumulated view (run_raytracer): its own seeds, its own sub-pixel offset, folded into the running sum by the kernel's
+             * epilogue.  Only the trace's camera words move: `g` -- the ray buffer's meaning, the scheduling signature -- stays the latched camera,
+             * so the tile order built for the still view keeps serving it (the offset moves a tile's content by less than a pixel). */
+            Impl::Accum& A = I->acc;
+            const uint32_t f = (uint32_t)A.frame;
+            P.seed_offset = I->seed_offset + clw_host_frame_seed(f);
+            if (I->acc_jitter) {
+                clw_camera base, jit;
+                memcpy(base.im_corner, g.corner, 12); memcpy(base.origin, g.origin, 12); memcpy(base.up, g.up, 12); memcpy(base.right, g.right, 12);
+                base.w_factor = g.w_factor; base.h_factor = g.h_factor; base.width = g.width; base.height = g.height;
+                if (!clw_host_jitter_camera(&base, f, (uint32_t)ss, &jit)) die("Couldn't run the kernel");
+                memcpy(P.corner, jit.im_corner, 12);
+            }
+            if (A.pixels != (size_t)P.n_items || !A.sum) {
+                if (f != 0) die("Couldn't run the kernel");      /* (the range is part of the key: a new range starts at frame 0) */
+                if (A.sum) { finish(I); (void)hipFree(A.sum); A.sum = nullptr; }
+                HIP_OK(hipMalloc((void**)&A.sum, (size_t)P.n_items * 12), "Couldn't allocate device memory");
+                A.pixels = P.n_items;
+            }
+            if (I->tables_fence_pending) { HIP_OK(hipStreamWaitEvent(I->stream, I->tables_fence, 0), "Couldn't run the kernel"); I->tables_fence_pending = false; }
+            I->tables_in_flight = true;
+            P.acc_sum = A.sum;      /* indexed like `out` (whole-range launches only: the pipelined read-back declines in the mode) */
+            P.acc_scale = 1.0f / (float)(f + 1u);
+        }
         P.tiled = (g.id_offset % g.width == 0 || g.band_stride > 1) && (P.n_items % g.width == 0) && !(I->variant & 2);
         if (ss > 1) {
             /* the launch traces the virtual frame of ss x as many columns and rows that the same camera gives (for a power of two bit for bit
@@ -815,6 +872,8 @@ void trace_launch(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Str
     if (P.ss_lg) flags |= F_SS;      /* every fused flavour has a supersampled twin, whose epilogue resolves the samples */
     if (P.ss_lg && P.ss_disp) flags |= F_MOVE;      /* ... and the twin (not the grid builds') a flavour whose sphere reads take the lane's scene time */
     if (pass == PASS_REFINE) flags |= F_LIST;       /* ... and one that asks the device how long its tile list is */
+    /* the strict build's shallow counting and grid kernels read the seed offset and accumulate only as their WT_F_ACC twin (wt_acc_flagged) */
+    if (I->strict && !(flags & F_DEEP) && (flags & (F_COUNT | F_GRID)) && (P.seed_offset != 0u || P.acc_sum)) flags |= F_ACC;
     I->last_trace_flags = flags;
     if (tail_wanted) {
         const uint64_t nslots = tpt_nslots, slice = tpt_slice, cap = tpt_cap;
@@ -826,7 +885,11 @@ void trace_launch(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Str
                 if (I->d_tpt_flags) (void)hipFree(I->d_tpt_flags);
                 I->d_tpt_pool = nullptr; I->d_tpt_flags = nullptr; I->tpt_pool_bytes = 0;
                 if (hipMalloc((void**)&I->d_tpt_pool, need) == hipSuccess && hipMalloc((void**)&I->d_tpt_flags, nslots * 4u) == hipSuccess) {
-                    HIP_OK(hipMemset(I->d_tpt_flags, 0, nslots * 4u), "Couldn't allocate device memory");
+                    /* on the LAUNCH stream: it does not synchronise with the null stream (hipStreamNonBlocking), and a hipMemset of device memory may
+                     * return before it has run -- cleared there, the flags could still be garbage when the first waves take their slots, or be
+                     * zeroed under a wave that holds one, and two tiles would share a slot (seen as an occasional wrong first frame of a deep
+                     * launch whose tiles all enter the tail at once, clw_ext_set_tpt(64)) */
+                    HIP_OK(hipMemsetAsync(I->d_tpt_flags, 0, nslots * 4u, I->stream), "Couldn't allocate device memory");
                     I->tpt_pool_bytes = need;
                 } else {                                /* no room: the launch runs without the tail */
                     (void)hipGetLastError();
@@ -860,10 +923,58 @@ void trace_launch(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Str
         }
         S.wr = wr ^ 1;
     }
+    return true;
+}
+
+Buffer* rays_of(cl_wrap* w, Impl* I, cl_uint kid) {
+    Kernel& k = I->kernels[kid];
+    if (is_registered(w, kid, 0)) return (Buffer*)w->buffers[kid][0];
+    const ArgValue& v = need_value(k, 0, sizeof(cl_mem), sizeof(cl_mem));
+    void* h; memcpy(&h, v.bytes, sizeof h);
+    Buffer* rays = lookup_handle(I, h);
+    if (!rays) die("Couldn't run the kernel");
+    return rays;
+}
+
+/* A trace launch with progressive accumulation on (hip_wrap_ext.h: clw_ext_set_accumulate): refuses what the mode does not combine with, restarts
+ * the sum when the key of the image changed, holds a converged view (no launch at all), else traces frame K and folds it in. */
+void run_accumulated(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Strip* strip) {
+    Kernel& k = I->kernels[kid];
+    Buffer* rays = rays_of(w, I, kid);
+    /* the shim must own the camera: it moves it by a sub-pixel per frame, and the seeds are the frame's */
+    if (!(I->fuse && rays->gen_valid && !rays->exposed))
+        die("Frame accumulation needs the fused raygen + trace launch (CLWRAP_FUSE=1, rays generated by this library and not rewritten)");
+    /* per-frame decorrelated lens and time samples are not built: a frame of these would repeat its lens points and times for ever */
+    if (!I->cams.empty()) die("Frame accumulation does not combine with a table of sample cameras (clw_ext_set_sample_cameras)");
+    if (I->aperture > 0.0f) die("Frame accumulation does not combine with a lens (clw_ext_set_lens)");
+    if (!I->motion_disp.empty()) die("Frame accumulation does not combine with moving spheres (clw_ext_set_sphere_motion)");
+    if (I->adaptive >= 0) die("Frame accumulation does not combine with adaptive supersampling (clw_ext_set_adaptive)");
+    Impl::Accum& A = I->acc;
+    Impl::AccKey key;
+    key.gen = rays->gen;
+    uint32_t total; memcpy(&total, need_value(k, 7, 4, 4).bytes, 4);
+    key.total = total; key.n_out = (uint64_t)array_size;
+    key.depth = I->depth; key.strict = I->strict; key.fuse = I->fuse; key.ss = I->supersample; key.max_frames = I->acc_max; key.jitter = I->acc_jitter;
+    key.through = I->through; key.seed = I->seed_offset;
+    const cl_uint args[6] = {1, 2, 3, 8, 9, 10};
+    key.buf[0] = rays; key.size[0] = rays->size;
+    /* (a lazily created buffer -- the framebuffer -- gets its memory here, not inside the first launch: its address is part of the key) */
+    for (int a = 0; a < 6; a++) { Buffer* b = buffer_arg(w, kid, args[a]); ensure_allocated(I, b); key.buf[1 + a] = b; key.dptr[1 + a] = b->dptr; key.size[1 + a] = b->size; }
+    for (int a = 0; a < 3; a++) key.counts[a] = read_count(k, 4 + (cl_uint)a);
+    { const Buffer* t = key.buf[4]; const Buffer* s = key.buf[5]; key.img[0] = t->w; key.img[1] = t->h; key.img[2] = t->layers; key.img[3] = s->w; key.img[4] = s->h; }
+    key.epoch = A.epoch;
+    if (!A.key_valid || !same_acc_key(key, A.key)) { A.K = 0; A.key = key; A.key_valid = true; }
+    if (A.K >= (uint32_t)I->acc_max) return;      /* converged: framebuffer, sum, tile costs, timing log and flavour stay as the last frame left them */
+    A.frame = (int)A.K;
+    const bool launched = trace_launch(w, I, kid, array_size, strip, PASS_PLAIN);
+    A.frame = -1;
+    if (launched) A.K++;      /* (an empty launch range traces nothing and adds no frame) */
 }
 
 void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Strip* strip = nullptr) {
     I->adapt.blocks = 0;
+    if (I->acc_max > 0) { run_accumulated(w, I, kid, array_size, strip); return; }
+    I->acc.key_valid = false;      /* a launch outside the mode: the next accumulated one starts at frame 0 */
     if (I->adaptive < 0) { trace_launch(w, I, kid, array_size, strip, PASS_PLAIN); return; }
     /* Adaptive supersampling (hip_wrap_ext.h: clw_ext_set_adaptive).  Per-sample cameras and moving spheres change every pixel of the frame, so
      * the contrast of a 1-sample frame says nothing about where their samples matter: refused. */
@@ -884,6 +995,7 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
 bool pipelined_output(cl_wrap* w, Impl* I, size_t array_size, size_t output_size, cl_uint kid, cl_uint out_kernel,
                       cl_int out_arg, void* host_output) {
     if (!I->pipeline || I->async || !host_output || !I->fuse || I->counting || I->debug_rgb || (I->variant & 2)) return false;
+    if (I->acc_max > 0) return false;        /* an accumulated view is one launch per frame, or none at all once it has converged */
     if (I->adaptive >= 0) return false;      /* a strip's edge rows would be classified without their neighbours in the next strip: another frame */
     if (out_kernel != kid || out_arg != 10 || !is_registered(w, kid, 10)) return false;
     Kernel& k = I->kernels[kid];
@@ -1000,6 +1112,18 @@ void cl_wrap_init(cl_wrap* wrap, cl_device_type type, ...) {
             I->adaptive = (int)v;
         }
     }
+    if (const char* so = getenv("CLWRAP_SEED_OFFSET")) {
+        if (*so) {
+            char* end = nullptr;
+            const unsigned long long v = strtoull(so, &end, 0);
+            if (end == so || *end || *so == '-' || v > 0xFFFFFFFFull) die("CLWRAP_SEED_OFFSET (seed offset of every trace launch) must be an integer in [0, 4294967295]");
+            I->seed_offset = (uint32_t)v;
+        }
+    }
+    I->acc_max = env_int("CLWRAP_ACCUMULATE", 0);
+    if (I->acc_max < 0 || I->acc_max > 65536) die("CLWRAP_ACCUMULATE (frames a still view accumulates) must be in [0, 65536]");
+    I->acc_jitter = env_int("CLWRAP_ACC_JITTER", 1);
+    if (I->acc_jitter != 0 && I->acc_jitter != 1) die("CLWRAP_ACC_JITTER (sub-pixel offset per accumulated frame) must be 0 or 1");
     I->aperture = env_float("CLWRAP_APERTURE", 0.0f);
     I->focus = env_float("CLWRAP_FOCUS", 1.0f);
     if (!(I->aperture >= 0.0f) || !std::isfinite(I->aperture)) die("CLWRAP_APERTURE (lens aperture) must be a finite number >= 0");
@@ -1026,6 +1150,7 @@ void cl_wrap_load_global_data(cl_wrap* wrap, cl_uint kernel_id, cl_uint arg_id, 
     precheck_buffer_arg(wrap, kernel_id, arg_id);
     Buffer* b = new_buffer(I);
     b->size = size;
+    if (kernel_id < I->kernels.size() && I->kernels[kernel_id].kind == K_RAYTRACER && arg_id >= 1 && arg_id <= 9) I->acc.epoch++;
     if (data) {
         ensure_allocated(I, b);
         if (size) {
@@ -1046,6 +1171,7 @@ void cl_wrap_load_single_data(cl_wrap* wrap, cl_uint kernel_id, cl_uint arg_id, 
     if (arg_id >= __MAX_BUFFERS || !data || obj_size == 0 || obj_size > sizeof(ArgValue::bytes))
         die("Couldn't pass the data argument to the kernel");
     ArgValue& v = I->kernels[kernel_id].values[arg_id];
+    if (I->kernels[kernel_id].kind == K_RAYTRACER && arg_id >= 1 && arg_id <= 9) I->acc.epoch++;      /* (an accumulated view starts again) */
     memcpy(v.bytes, data, obj_size); /* copied at call time, like clSetKernelArg */
     v.size = obj_size;
     v.set = true;
@@ -1060,6 +1186,7 @@ static void install_images(cl_wrap* wrap, Impl* I, cl_uint kernel_id, cl_uint ar
     ensure_allocated(I, b);
     if (hipMemcpy(b->dptr, rgba, b->size, hipMemcpyHostToDevice) != hipSuccess)
         die("Couldn't create an image array %d", -1);
+    if (I->kernels[kernel_id].kind == K_RAYTRACER && arg_id >= 1 && arg_id <= 9) I->acc.epoch++;
     register_buffer(wrap, kernel_id, arg_id, b);
 }
 
@@ -1138,6 +1265,7 @@ void cl_wrap_release(cl_wrap* wrap) {
     if (I->d_tpt_jump) (void)hipFree(I->d_tpt_jump);
     if (I->d_cams) (void)hipFree(I->d_cams);
     if (I->d_motion) (void)hipFree(I->d_motion);
+    if (I->acc.sum) (void)hipFree(I->acc.sum);
     I->adapt.free_all();
     if (I->tables_fence) (void)hipEventDestroy(I->tables_fence);
     for (uint32_t* q : {I->d_grid_start, I->d_grid_items, I->d_grid_box}) if (q) (void)hipFree(q);
@@ -1302,6 +1430,17 @@ void clw_ext_set_lens(cl_wrap* wrap, float aperture, float focus) {
     I->cams.clear();
 }
 
+void clw_ext_set_seed_offset(cl_wrap* wrap, uint32_t s) { impl_of(wrap)->seed_offset = s; }
+uint32_t clw_ext_get_seed_offset(const cl_wrap* wrap) { return impl_of(wrap)->seed_offset; }
+void clw_ext_set_accumulate(cl_wrap* wrap, int max_frames, int jitter) {
+    if (max_frames < 0 || max_frames > 65536) die("Frame accumulation: the number of frames must be in [0, 65536] (0 = off)");
+    if (jitter != 0 && jitter != 1) die("Frame accumulation: jitter must be 0 or 1");
+    Impl* I = impl_of(wrap);
+    I->acc_max = max_frames; I->acc_jitter = jitter;
+}
+uint32_t clw_ext_get_accumulated(cl_wrap* wrap) { Impl* I = impl_of(wrap); return I->acc_max > 0 ? I->acc.K : 0u; }
+void clw_ext_reset_accumulation(cl_wrap* wrap) { impl_of(wrap)->acc.epoch++; }
+
 void clw_ext_set_pipeline(cl_wrap* wrap, int on) { impl_of(wrap)->pipeline = on ? 1 : 0; }
 void clw_ext_set_timing_every(cl_wrap* wrap, uint32_t n) { Impl* I = impl_of(wrap); I->timing_every = n ? n : 1; I->timing_tick = 0; I->timing_on = n != 0; }
 
@@ -1346,12 +1485,14 @@ void clw_ext_bind_device_buffer(cl_wrap* wrap, cl_uint kernel_id, cl_uint arg_id
     if (!device_ptr) die("Couldn't pass the data argument to the kernel");
     Buffer* b = new_buffer(I);
     b->dptr = device_ptr; b->size = size; b->owned = false;
+    if (I->kernels[kernel_id].kind == K_RAYTRACER && arg_id >= 1 && arg_id <= 10) I->acc.epoch++;      /* scene arrays, images, the framebuffer */
     register_buffer(wrap, kernel_id, arg_id, b);
 }
 
 void clw_ext_invalidate_scene(cl_wrap* wrap) {
     Impl* I = impl_of(wrap);
     I->prep_s = I->prep_p = I->prep_l = nullptr;
+    I->acc.epoch++;
     /* a scene buffer rewritten in place on the device no longer matches its host copy */
     for (Buffer* b : I->live) if (!b->image) b->shadow.clear();
 }

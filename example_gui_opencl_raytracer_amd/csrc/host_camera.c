@@ -99,6 +99,34 @@ int clw_host_lens_cameras(const clw_camera* base, float aperture, float focus, u
     return 1;
 }
 
+/* ---- progressive frame accumulation (hip_wrap_ext.h: clw_ext_set_accumulate) -------------------------------------- */
+
+uint32_t clw_host_frame_seed(uint32_t f) { return f * 0x9E3779B1u; }      /* odd multiplier: a bijection mod 2^32, 0 for frame 0 */
+
+/* the radical inverse of f in `base`: the usual digit loop, double */
+static double radical_inverse(uint32_t f, uint32_t base) {
+    const double inv = 1.0 / (double)base;
+    double w = inv, r = 0.0;
+    while (f) { r += (double)(f % base) * w; f /= base; w *= inv; }
+    return r;
+}
+
+int clw_host_jitter_camera(const clw_camera* base, uint32_t f, uint32_t n, clw_camera* out) {
+    if (!base || !out || (n != 1 && n != 2 && n != 4 && n != 8)) return 0;
+    if (out != base) memcpy(out, base, sizeof *out);
+    if (f == 0) return 1;                                /* frame 0: the base camera, byte for byte */
+    /* the Halton point (2, 3) of the frame, centred: double, stored to float; everything after it in float32, one rounding per operation */
+    const float jx = (float)(radical_inverse(f, 2) - 0.5), jy = (float)(radical_inverse(f, 3) - 0.5);
+    const float cw = base->w_factor / (float)n, ch = base->h_factor / (float)n;      /* the cell of a sample */
+    const float ax = cw * jx, ay = ch * jy;
+    for (int i = 0; i < 3; i++) {
+        const float rx = base->right[i] * ax, uy = base->up[i] * ay;
+        const float c = base->im_corner[i] + rx;
+        out->im_corner[i] = c - uy;
+    }
+    return 1;
+}
+
 static float shutter_mix(float a, float b, float t) { return a == b ? a : a + (b - a) * t; }
 
 int clw_host_shutter_cameras(const clw_camera* open, const clw_camera* close, uint32_t n, clw_sample_camera* out) {

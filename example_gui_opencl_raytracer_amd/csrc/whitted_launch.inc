@@ -12,7 +12,7 @@ static hipError_t wt_launch_one(const whitted_params* P, unsigned grid, size_t d
 
 extern "C" hipError_t WT_LAUNCH_TRACE(const whitted_params* P, int flags, unsigned grid, size_t dyn_lds,
                                       hipStream_t s) {
-    using WT_NS::WT_F_SS; using WT_NS::WT_F_MOVE; using WT_NS::WT_F_LIST;
+    using WT_NS::WT_F_SS; using WT_NS::WT_F_MOVE; using WT_NS::WT_F_LIST; using WT_NS::WT_F_ACC;
 #if !WT_STRICT
     using WT_NS::WT_F_GEOM_LDS; using WT_NS::WT_F_SHAPE;
     if (flags & WT_F_SHAPE) {
@@ -30,7 +30,7 @@ extern "C" hipError_t WT_LAUNCH_TRACE(const whitted_params* P, int flags, unsign
         return hipErrorInvalidValue;
     }
 #endif
-    switch (flags & (255 | WT_F_SS | WT_F_MOVE | WT_F_LIST)) {
+    switch (flags & (255 | WT_F_SS | WT_F_MOVE | WT_F_LIST | WT_F_ACC)) {
 #define WT_CASE(F) case F: return wt_launch_one<F>(P, grid, dyn_lds, s);
 /* F, its supersampled twin (fused launches only: no twin for the ray-buffer flavours, bit 3) and the twin's list-driven flavour (adaptive launches) */
 #define WT_CASE2(F) WT_CASE(F) WT_CASE((F) | WT_F_SS) WT_CASE((F) | WT_F_SS | WT_F_LIST)
@@ -43,6 +43,11 @@ extern "C" hipError_t WT_LAUNCH_TRACE(const whitted_params* P, int flags, unsign
         /* deep builds whose depth is <= 8 (bit 6) / <= 16 (bit 7): a smaller scratch part of the DFS stack (not the counting builds) */
         WT_CASE3(66) WT_CASE3(70) WT_CASE(74) WT_CASE(78) WT_CASE2(82) WT_CASE(90)
         WT_CASE3(130) WT_CASE3(134) WT_CASE(138) WT_CASE(142) WT_CASE2(146) WT_CASE(154)
+#if WT_STRICT
+        /* the shallow counting and grid kernels (wt_acc_flagged): their twins that read the seed offset and accumulate */
+        WT_CASE3(1 | WT_F_ACC) WT_CASE3(5 | WT_F_ACC) WT_CASE(9 | WT_F_ACC) WT_CASE(13 | WT_F_ACC)
+        WT_CASE2(16 | WT_F_ACC) WT_CASE2(17 | WT_F_ACC) WT_CASE(24 | WT_F_ACC) WT_CASE(25 | WT_F_ACC)
+#endif
 #if !WT_STRICT
         WT_CASE3(98) WT_CASE3(102) WT_CASE(106) WT_CASE(110) WT_CASE2(114) WT_CASE(122)
         WT_CASE3(162) WT_CASE3(166) WT_CASE(170) WT_CASE(174) WT_CASE2(178) WT_CASE(186)

@@ -107,6 +107,15 @@ typedef struct {
      * entries long (a cache line per counter); the grid is sized for full lists, and workgroup b leaves at once unless b / 8 is below the
      * length of list b % 8 */
     const uint32_t* list_count;
+    /* progressive frame accumulation (NULL = off; hip_wrap_ext.h: clw_ext_set_accumulate): acc_sum holds 3 floats per OUTPUT pixel, indexed like
+     * out -- the running sum of the clamped (1 sample) or resolved (supersampled) value the plain launch would pack; the lane that packs a pixel
+     * stores its value (acc_scale == 1.0f: the first frame, a store with no read) or adds it, and packs fminf(sum * acc_scale, 1.0f), acc_scale
+     * = 1 / frames, correctly rounded by the host; out_rgb, when bound, receives that mean */
+    float* acc_sum;
+    float acc_scale;
+    /* added mod 2^32 to the global id that seeds a work-item's xorshift state (clw_ext_set_seed_offset; an accumulated frame adds its own);
+     * nothing else reads it: pixel positions, buffers and guards keep the id */
+    uint32_t seed_offset;
 } whitted_params;
 
 #define WT_LIST_COUNT_STRIDE 32

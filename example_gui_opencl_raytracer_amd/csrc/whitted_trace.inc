@@ -684,7 +684,15 @@ enum { WT_F_COUNT = 1, WT_F_DEEP = 2, WT_F_GEOM_LDS = 4, WT_F_RAYS = 8, WT_F_GRI
        WT_F_MOVE = 1 << 18 /* on top of WT_F_SS, not the grid builds: moving spheres (wt_sphere_at) -- a flavour of its own, so that the plain
                               supersampled kernels are the code they were */,
        WT_F_LIST = 1 << 19 /* on top of WT_F_SS, not with WT_F_MOVE: the refine pass of an adaptive launch -- a wave first asks the device-side length of
-                              its list (whitted_params.h: list_count) whether it has a tile at all; again a flavour of its own */ };
+                              its list (whitted_params.h: list_count) whether it has a tile at all; again a flavour of its own */,
+       WT_F_ACC = 1 << 20 /* the seed offset and progressive accumulation (whitted_params.h: seed_offset, acc_sum) are one more scalar word and a wave-uniform
+                              run-time branch of the epilogue in every flavour but the few whose register allocation they disturbed (wt_acc_flagged:
+                              the strict build's shallow counting and grid kernels, which sit on their 128-VGPR cap): those read neither unless
+                              they are this twin, so that they are the code they were; the shim asks for the twin when the launch has a seed
+                              offset or accumulates */ };
+/* the flavours that take the seed offset and the accumulation branch only as their WT_F_ACC twin (tools/kernel_stats.py against the parent:
+ * profiles/r10_ab_experiments.txt) */
+constexpr bool wt_acc_flagged(int flags) { return WT_STRICT != 0 && (flags & WT_F_DEEP) == 0 && (flags & (WT_F_COUNT | WT_F_GRID)) != 0; }
 
 /* ---- the scene's primitive counts: launch parameters, or compile-time constants (FLAGS & WT_F_SHAPE) ----------------------------
  * A small scene's loops over 4 spheres, 2 planes and 3 lights are mostly loop control, guards and selects around little arithmetic.
@@ -1371,6 +1379,17 @@ __device__ __forceinline__ float wt_ss_resolve(float v, const unsigned lg) {
     return v;
 }
 
+/* Progressive accumulation (whitted_params.h: acc_sum): the pixel's value of this frame -- r, g, b in [0, 1] -- joins its 12-byte record of
+ * running sums, and the running mean comes back in its place.  scale = 1 / frames; 1.0f is the first frame, which stores without reading
+ * (the buffer is never cleared).  One owner lane per output pixel and launch: plain loads and stores, no atomics; every operation rounds
+ * once (the units are built without contraction), so a numpy fold of the constituent frames gives the same bits. */
+__device__ __forceinline__ void wt_acc_fold(float* __restrict__ s, const float scale, float& r, float& g, float& b) {
+    float sr = r, sg = g, sb = b;
+    if (scale != 1.0f) { sr = s[0] + r; sg = s[1] + g; sb = s[2] + b; }
+    s[0] = sr; s[1] = sg; s[2] = sb;
+    r = fminf(sr * scale, 1.0f); g = fminf(sg * scale, 1.0f); b = fminf(sb * scale, 1.0f);
+}
+
 /* One tile (tiled launches) or one block of work-items: the whole trace of its pixels.  `wg` is the workgroup's number in
  * the launch's dispatch order (blockIdx.x). */
 typedef const __attribute__((address_space(4))) whitted_params* wt_kparams_t;
@@ -1384,6 +1403,8 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
     constexpr bool SS = (FLAGS & WT_F_SS) != 0;         /* supersampled launch: the epilogue resolves n x n samples per stored pixel */
     constexpr bool MOVE = SS && !GRID && (FLAGS & WT_F_MOVE) != 0;   /* moving spheres: every sphere read takes the lane's scene time */
     constexpr bool LIST = SS && (FLAGS & WT_F_LIST) != 0;            /* the refine pass of an adaptive launch: the tile list's length is on the device */
+    constexpr bool SEEDED = !wt_acc_flagged(FLAGS) || (FLAGS & WT_F_ACC) != 0;   /* the kernel reads the seed offset ... */
+    constexpr bool ACC = SEEDED && !FROM_RAYS;                                   /* ... and its epilogue carries the accumulation branch (fused launches only) */
     constexpr bool UNIT_CT = !WT_STRICT && GEOM_LDS && !FROM_RAYS && !GRID;   /* see whitted_hit.inc */
     /* The lights' visibility classes (wt_light_vis) are compiled into the STRICT build's small-scene kernels only: there the samples they
      * save cost an fp64 product and a libm sin / cos each (-13 % at C2).  Measured for the fast build, whose samples are two hardware
@@ -1508,6 +1529,7 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
     float n1 = WT_DEFAULT_N, f = 1.0f;
     int sp = 0;                         /* parents on the stack */
     unsigned rng = (unsigned)gid;       /* raytracing.cl:33: id 0 is the xorshift fixed point */
+    if (SEEDED) rng += P.seed_offset;   /* (0 = the reference's seeds) */
     const int D = P.depth;
     bool active = valid && depth < D;
 
@@ -1620,15 +1642,21 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
         const float mb = wt_ss_resolve(fminf(fmaxf(rgb.z, 0.0f), 1.0f), lg) * inv;
         if (valid && (lane & (m | (m << 3))) == 0u) {
             const size_t px = (size_t)(y >> lg) * (P.width >> lg) + (x >> lg);
+            float vr = mr, vg = mg, vb = mb;
+            if (ACC && P.acc_sum) wt_acc_fold(P.acc_sum + 3 * px, P.acc_scale, vr, vg, vb);      /* wave-uniform: the running mean of a still view */
             if (P.out_rgb) {
                 float* q = P.out_rgb + 3 * px;
-                q[0] = mr; q[1] = mg; q[2] = mb;
+                q[0] = vr; q[1] = vg; q[2] = vb;
             }
-            P.out[px] = ((unsigned)(mr * 255.0f) << 16) | ((unsigned)(mg * 255.0f) << 8) | (unsigned)(mb * 255.0f);
+            P.out[px] = ((unsigned)(vr * 255.0f) << 16) | ((unsigned)(vg * 255.0f) << 8) | (unsigned)(vb * 255.0f);
         }
     } else
     /* ---- pack (raytracing.cl:193-194): clamp, *255, truncate ---------------------------- */
     if (valid) {
+        if (ACC && P.acc_sum) {      /* wave-uniform: the clamped sample joins the running sum, and the mean (in [0, 1]: the clamp below keeps it) takes its place */
+            rgb = mk3(fminf(fmaxf(rgb.x, 0.0f), 1.0f), fminf(fmaxf(rgb.y, 0.0f), 1.0f), fminf(fmaxf(rgb.z, 0.0f), 1.0f));
+            wt_acc_fold(P.acc_sum + 3 * (size_t)item, P.acc_scale, rgb.x, rgb.y, rgb.z);
+        }
         if (P.out_rgb) {
             float* q = P.out_rgb + 3 * (size_t)item;
             q[0] = rgb.x; q[1] = rgb.y; q[2] = rgb.z;

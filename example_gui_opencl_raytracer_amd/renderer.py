@@ -25,6 +25,12 @@ open and every sample sees the scene at its own time (clw_ext_set_sphere_motion;
 1-sample frame shows a contrast of at least T between neighbouring pixels take their n x n samples, the others keep the 1-sample value
 (clw_ext_set_adaptive; ``w.read_refine_mask()`` tells which).  A strip is classified on its own rows, so its edge rows may differ from the
 full frame's.
+
+``accumulate=N`` (1..65536; without lens, sample cameras, motion or adaptive): progressive accumulation -- while nothing that defines the image
+changes, every ``render()`` traces the view once more with its own random numbers and (``jitter=True``) its own sub-pixel offset and returns the
+running mean of the frames so far, until N frames are in; then it returns that mean without tracing (clw_ext_set_accumulate).  ``accumulated``
+tells how many frames the mean holds, ``reset_accumulation()`` starts again.  ``seed_offset=s`` shifts the random seed of every pixel
+(clw_ext_set_seed_offset).  ``render_rgb()`` returns the mean (clamped to [0, 1]) while the mode is on.
 """
 from __future__ import annotations
 
@@ -52,7 +58,8 @@ class Renderer:
                  depth: int = 15, strict: bool = False, fuse: bool = True, first_row: int = 0,
                  rows: int | None = None, bands: tuple[int, int] | None = None, framebuffer_ptr: int | None = None, wide_counts: bool | None = None,
                  texture_paths=None, skybox_path=None, supersample: int = 1,
-                 lens: tuple[float, float] | None = None, motion=None, adaptive: int | None = None):
+                 lens: tuple[float, float] | None = None, motion=None, adaptive: int | None = None,
+                 accumulate: int = 0, jitter: bool = True, seed_offset: int = 0):
         self.width, self.height = width, height
         self.first_row = first_row
         self.rows = height - first_row if rows is None else rows
@@ -74,6 +81,11 @@ class Renderer:
             w.set_sphere_motion(motion)
         if adaptive is not None:  # contrast threshold 0..256: the samples only where the 1-sample frame shows that much contrast
             w.set_adaptive(adaptive)
+        if seed_offset:           # added to the id that seeds a pixel's random numbers
+            w.set_seed_offset(seed_offset)
+        self.accumulate = int(accumulate)
+        if self.accumulate:       # frames a still view accumulates; each with its own seeds and (jitter) sub-pixel offset
+            w.set_accumulate(self.accumulate, jitter)
         if bands is not None:
             w.set_row_bands(*bands)
 
@@ -143,16 +155,29 @@ class Renderer:
         return out
 
     def render_rgb(self):
-        """-> (packed uint32[n], float32[n,3] un-clamped radiance): the optional float debug output."""
+        """-> (packed uint32[n], float32[n,3]): the optional float debug output -- un-clamped radiance of a 1-sample launch, the resolved mean of a
+        supersampled one, the running mean (in [0, 1]) while a view accumulates."""
         if self._rgb_dev is None:
             self.w.load_global_data(1, 31, None, 12 * self.pixels, api.CL_MEM_WRITE_ONLY)  # spare arg slot
             self._rgb_dev = self.w.device_ptr(1, 31)
         self.w.set_debug_rgb(self._rgb_dev)
         out = self.render()
         rgb = np.empty((self.pixels, 3), np.float32)
-        self.w.output(self.pixels, rgb.nbytes, 1, 1, 31, rgb)
+        # cl_wrap_output reads a buffer back only behind a launch: the trace launch again -- but while a view accumulates that would be its next
+        # frame, so then the raygen launch, which in fused mode only latches the camera again; equal camera values do not restart the sum
+        # (hip_wrap_ext.h, clw_ext_set_accumulate: the key compares them by value)
+        accumulating = hasattr(self.w.L, "clw_ext_get_accumulated") and self.accumulated > 0      # (set here or by CLWRAP_ACCUMULATE)
+        self.w.output(self.pixels, rgb.nbytes, 0 if accumulating else 1, 1, 31, rgb)
         self.w.set_debug_rgb(0)
         return out, rgb
+
+    @property
+    def accumulated(self) -> int:
+        """Frames in the running mean after the last render (0 = the mode is off)."""
+        return self.w.get_accumulated()
+
+    def reset_accumulation(self) -> None:
+        self.w.reset_accumulation()
 
     def read_rays(self) -> np.ndarray:
         """The 64-B rray records of buffers[0][8] (materialised on demand in fused mode)."""

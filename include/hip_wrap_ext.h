@@ -13,6 +13,7 @@
  * Environment variables read once by cl_wrap_init (same meaning as the setters):
  *   CLWRAP_DEPTH=<1..32>   CLWRAP_STRICT=<0|1>   CLWRAP_FUSE=<0|1>   CLWRAP_DEVICE=<ordinal>   CLWRAP_PIPELINE=<0|1>   CLWRAP_THROUGH=<float>
  *   CLWRAP_SUPERSAMPLE=<1|2|4|8>   CLWRAP_APERTURE=<float >= 0>   CLWRAP_FOCUS=<float > 0>   (thin lens: clw_ext_set_lens)
+ *   CLWRAP_ADAPTIVE=<0..256>   CLWRAP_SEED_OFFSET=<uint32>   CLWRAP_ACCUMULATE=<0..65536>   CLWRAP_ACC_JITTER=<0|1>   (clw_ext_set_accumulate)
  * Tuning / experiment knobs (defaults are the measured optima): CLWRAP_GRID_MIN, CLWRAP_GRID_DENSITY (uniform grid),
  *   CLWRAP_OCC_TILES_PER_DEPTH (deep launches of >= this x depth tiles take the high-occupancy kernel flavour),
  *   CLWRAP_TIMING_EVERY, CLWRAP_VARIANT (bit mask of clw_ext_set_variant).
@@ -185,6 +186,51 @@ int      clw_ext_get_adaptive(const cl_wrap* wrap);
  * (0 = the last launch was not adaptive); copies them if `cap` suffices.  Waits for the launch. */
 uint32_t clw_ext_read_refine_mask(cl_wrap* wrap, uint8_t* out, uint32_t cap);
 
+/* Seed offset: the xorshift state of a work-item of every following trace launch starts at (uint32_t)(id + s), `id` being the global id that
+ * seeds it otherwise (reference raytracing.cl:33; the VIRTUAL frame's id in a supersampled launch).  Nothing else reads s: pixel positions,
+ * buffers and the `pixels` guard keep the id.  It applies to every launch flavour of both arithmetic builds -- fused and caller-written rays,
+ * tiled, linear and banded ranges, supersampled, moving and list-driven launches, the uniform grid, the tree-parallel tail.  The work-item with
+ * id + s = 0 (mod 2^32) has the stuck generator that id 0 has in the reference.  Default 0 = the reference's seeds; env CLWRAP_SEED_OFFSET=<0..4294967295> (anything else is an error at cl_wrap_init).
+ * (The strict build's shallow counting and grid kernels take the offset, and the accumulation below, as a twin flavour -- bit 1 << 20 of
+ * clw_ext_last_trace_flags, WT_F_ACC -- which such a launch runs only when s != 0 or it accumulates.) */
+void     clw_ext_set_seed_offset(cl_wrap* wrap, uint32_t s);
+uint32_t clw_ext_get_seed_offset(const cl_wrap* wrap);
+
+/* Progressive frame accumulation: a still view converges over frames at the price of a plain frame each.  max_frames 0 (default) = off,
+ * 1 .. 65536 = on; jitter 0 / 1 = every frame looks through the latched camera / through its own sub-pixel offset.  Env CLWRAP_ACCUMULATE=<0..65536>,
+ * CLWRAP_ACC_JITTER=<0|1> (default 1).  The shim keeps, per cl_wrap, a count K (0 at first) and a device buffer `sum` of 3 floats per OUTPUT pixel
+ * of the launch range.  A fused trace launch with the mode on and K < max_frames, exactly:
+ *   1. is frame f = K: traced as the plain launch would be, but with seed offset s + clw_host_frame_seed(f) (s = clw_ext_set_seed_offset's, the sum
+ *      mod 2^32) and, with jitter on, through clw_host_jitter_camera(latched camera, f, n), n the supersampling factor.  Only the trace's camera
+ *      words change: the ray buffer keeps its meaning (one ray per output pixel through the latched camera);
+ *   2. c_f, per output pixel and channel, is what the plain launch would pack: the sample clamped to [0, 1], or with supersampling the resolved mean;
+ *   3. sum = c_0 for f = 0 (a store, no read: the buffer is never cleared), else sum = sum + c_f (float32, one rounding);
+ *   4. mean = fminf(sum * r, 1.0f), r = 1.0f / (float)(f + 1) rounded on the host;
+ *   5. the framebuffer receives mean packed as usual, (unsigned)(v * 255.0f) per channel;
+ *   6. the float debug output, when bound, receives mean;
+ *   7. K becomes f + 1.
+ * Frame 0 is the plain frame bit for bit, packed and float -- except that the float output of a 1-SAMPLE launch is the CLAMPED value while the mode
+ * is on (the un-clamped radiance otherwise); supersampled launches' float output is bit-equal.
+ * Holding: with K == max_frames no trace launch is issued -- framebuffer, sum, tile costs, timing log and clw_ext_last_trace_flags stay as the last
+ * frame left them; a cl_wrap_output that asks for a read-back still copies.  A converged view costs nothing.  (To read a buffer back WITHOUT
+ * adding a frame, ride the read-back on the raygen launch: cl_wrap_output(run = the raygen kernel, read = the buffer); in fused mode that launch
+ * only latches the camera again, and equal values do not restart the sum.  Renderer.render_rgb reads the float output that way.)
+ * Restart: K := 0 at the next trace launch whenever the key of the image differs from the previous trace launch's -- the eight latched raygen
+ * values (by value: a driver that re-uploads equal bytes does not restart), id offset, range, rows and bands; depth, strict, fuse; the
+ * supersampling factor; the shadow `through` factor; the seed offset; max_frames and jitter; identity and sizes of the scene, count, texture and
+ * skybox arguments and of the framebuffer; any cl_wrap_load_* on raytracer arguments 1-9; clw_ext_invalidate_scene; clw_ext_bind_device_buffer on
+ * the framebuffer; clw_ext_reset_accumulation; a trace launch with the mode off in between.  Pure scheduling knobs do not restart it (the image is
+ * the same): variant, grid, tile order, the tail's thresholds, counters, the stream (the sum is fenced across clw_ext_set_stream).
+ * The tile order of a still view keeps serving its frames: the offset moves what a tile shows by less than a pixel.
+ * Errors (print + exit(1)): at the call, max_frames outside [0, 65536] or jitter not 0 / 1; at the next trace launch, the mode together with
+ * caller-written rays or CLWRAP_FUSE=0 (the shim must own the camera), a table of sample cameras, a lens, moving spheres (their per-frame
+ * decorrelated lens points and times are not built) or adaptive supersampling.  The pipelined read-back of cl_wrap_output declines while the mode is on. */
+void     clw_ext_set_accumulate(cl_wrap* wrap, int max_frames, int jitter);
+/* K, the number of frames in the sum after the last trace launch; 0 = the mode is off. */
+uint32_t clw_ext_get_accumulated(cl_wrap* wrap);
+/* The next trace launch starts the sum again at frame 0. */
+void     clw_ext_reset_accumulation(cl_wrap* wrap);
+
 /* Work counters of the trace kernel.  enable=1 selects the counting build of the kernel
  * for subsequent launches (slower); read returns and clears
  *   out[0] path segments  out[1] shadow rays  out[2] light probes  out[3] skybox fetches
@@ -300,6 +346,17 @@ int clw_host_sample_times(uint32_t n, float* out);
  * first three floats) by fmaf(t, disp[3 i + a], c[a]); every other byte -- radius, material, padding -- is copied as it is.  `out` may
  * be `rspheres` itself.  Returns 0 on a NULL argument (with ns > 0), else 1. */
 int clw_host_spheres_at(const void* rspheres, uint32_t ns, const float* disp, float t, void* out);
+
+/* Host helpers: THE definition of what makes frame f of an accumulated view its own (clw_ext_set_accumulate).
+ *   clw_host_frame_seed(f) = f * 0x9E3779B1 mod 2^32: 0 for frame 0; the multiplier is odd, so the frames of a run get distinct offsets.
+ *   clw_host_jitter_camera(base, f, n), n in {1, 2, 4, 8}: f = 0 copies `base` byte for byte; for f >= 1
+ *     jx = radical inverse of f in base 2, less 1/2;  jy = radical inverse of f in base 3, less 1/2     [double, the digit loop; rounded to float]
+ *     ax = (w_factor / n) jx;  ay = (h_factor / n) jy;  im_corner[i] = (im_corner[i] + right[i] ax) - up[i] ay
+ *                                                                       [float32, one rounding per operation, no contraction]
+ *   and everything else copied: an offset of at most half a sample cell either way, so the running mean is a box filter over the cell of a pixel
+ *   (of a sub-sample when n > 1).  Returns 0 on a NULL pointer or an n that is not 1, 2, 4 or 8, else 1.  `out` may be `base`. */
+uint32_t clw_host_frame_seed(uint32_t f);
+int clw_host_jitter_camera(const clw_camera* base, uint32_t f, uint32_t n, clw_camera* out);
 
 /* Host helper: THE definition of the refine mask of adaptive supersampling (steps 2 and 3 of clw_ext_set_adaptive): `xrgb` = width x rows packed
  * pixels (the top byte is ignored), n in {2, 4, 8}, threshold in [0, 256]; writes one byte (0 / 1) per block of b x b pixels, b = 8 / n, row-major,

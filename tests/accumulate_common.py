@@ -1,0 +1,73 @@
+"""Shared by test_accumulate_host.py and test_gpu_accumulate.py: the numpy restatement of progressive frame accumulation
+(include/hip_wrap_ext.h, clw_ext_set_accumulate).
+
+Frame K-1 of an accumulated view is `fold` of K constituent frames c_0 .. c_{K-1}: per output pixel and channel the values the plain launch
+would pack (clamped to [0, 1]), added one after the other in float32, times float32(1 / K), capped at 1, packed with (unsigned)(v * 255).
+Constituent frame f is the plain frame with seed offset `frame_seed(f)` through the camera `jittered(cam, f, n)`."""
+import numpy as np
+
+F32 = np.float32
+GOLDEN_RATIO_ODD = 0x9E3779B1
+
+
+def frame_seed(f):
+    return (int(f) * GOLDEN_RATIO_ODD) & 0xFFFFFFFF
+
+
+def pack(v):
+    c = (np.asarray(v, F32) * F32(255.0)).astype(np.uint32)
+    return ((c[..., 0] << 16) | (c[..., 1] << 8) | c[..., 2]).reshape(-1)
+
+
+def fold(cs):
+    """cs: K float32 [pixels, 3] frames (radiance or resolved means; clamped here) -> (packed uint32 [pixels], float32 mean [pixels, 3])"""
+    cs = [np.clip(np.asarray(c, F32), F32(0), F32(1)) for c in cs]
+    s = cs[0].copy()
+    for c in cs[1:]:
+        s = s + c                                          # float32, one rounding
+    r = F32(1.0) / F32(len(cs))                            # correctly rounded
+    mean = np.minimum(s * r, F32(1.0))
+    return pack(mean), mean
+
+
+def radical_inverse(f, base):
+    inv = 1.0 / base                                       # Python floats are doubles: the C digit loop, operation for operation
+    w, r = inv, 0.0
+    while f:
+        r += float(f % base) * w
+        f //= base
+        w *= inv
+    return r
+
+
+def halton(f):
+    """-> (jx, jy) float32: the Halton (2, 3) point of frame f, centred on 0"""
+    return F32(radical_inverse(f, 2) - 0.5), F32(radical_inverse(f, 3) - 0.5)
+
+
+def camera_rows(cam):
+    """clw_camera / oracle Camera -> (im_corner, origin, up, right) float32 [3] each"""
+    return tuple(np.array(list(v), F32) for v in (cam.im_corner, cam.origin, cam.up, cam.right))
+
+
+def jittered(cam, f, n, cls=None):
+    """The camera of frame f (a `cls` structure, default type(cam)): im_corner = (im_corner + right ax) - up ay in float32, the rest copied."""
+    out = (cls or type(cam))()
+    corner, origin, up, right = camera_rows(cam)
+    if f:
+        jx, jy = halton(f)
+        ax = (F32(cam.w_factor) / F32(n)) * jx
+        ay = (F32(cam.h_factor) / F32(n)) * jy
+        corner = (corner + right * ax) - up * ay
+    for name, v in (("im_corner", corner), ("origin", origin), ("up", up), ("right", right)):
+        for i in range(3):
+            getattr(out, name)[i] = float(v[i])
+    out.w_factor, out.h_factor = float(F32(cam.w_factor)), float(F32(cam.h_factor))
+    out.width, out.height = cam.width, cam.height
+    return out
+
+
+def camera_bytes(cam):
+    corner, origin, up, right = camera_rows(cam)
+    return np.concatenate([corner, origin, up, right, np.array([cam.w_factor, cam.h_factor], F32)]).tobytes() + \
+        np.array([cam.width, cam.height], np.uint32).tobytes()

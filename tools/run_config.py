@@ -1,5 +1,5 @@
 """Time one BASELINE.json configuration through the C-ABI (kernel-only, frames back to back) and print JSON.
-   python tools/run_config.py c2|c3|c4|c5strip|ref800 [--strict 1] [--frames N] [--variant V] [--depth D] [--size WxH] [--supersample N] [--aperture A --focus F | --copies] [--motion move|equal] [--no-tail]
+   python tools/run_config.py c2|c3|c4|c5strip|ref800 [--strict 1] [--frames N] [--variant V] [--depth D] [--size WxH] [--supersample N] [--aperture A --focus F | --copies] [--motion move|equal] [--no-tail] [--accumulate N [--no-jitter]]
    --supersample N: n x n samples per pixel resolved in the kernel (the frame stays WxH); --size: another frame size for the configuration's
    scene and camera -- e.g. the n*W x n*H frame a supersampled launch traces, to time the same work without the resolve.
    --aperture A --focus F: a thin lens over the samples (clw_ext_set_lens); --copies: an explicit table of n*n copies of the launch camera
@@ -7,6 +7,9 @@
    --motion move: every third sphere of the scene moves by (0.5, 0, -0.3) while the shutter is open (clw_ext_set_sphere_motion); --motion equal:
    the same table with every sample time 0.5 -- the per-test fma and table read without the extra divergence; --no-tail: the tree-parallel tail
    off (clw_ext_set_tpt), as a moving deep launch runs.
+   --accumulate N [--no-jitter]: progressive accumulation over N frames (clw_ext_set_accumulate), every frame with its own seeds and, unless
+   --no-jitter, sub-pixel offset; the sum starts again before every timed loop, so N >= --frames times launches that all trace (a converged
+   view issues none).
    --repeats R: the N-frame loop R times (0 = until 50 ms have been timed, as bench.py --full does), median / min / max of the repeats."""
 import argparse, json, math, os, statistics, sys, time
 import numpy as np
@@ -31,6 +34,8 @@ ap.add_argument("--focus", type=float, default=1.0)
 ap.add_argument("--copies", action="store_true")
 ap.add_argument("--motion", choices=["move", "equal"], default=None)
 ap.add_argument("--no-tail", action="store_true")
+ap.add_argument("--accumulate", type=int, default=0)
+ap.add_argument("--no-jitter", action="store_true")
 a = ap.parse_args()
 tex, sky = textures.texture_layers(), textures.skybox_cross(4096)
 cam = pkg.CAMERA_RAYPNG
@@ -55,6 +60,10 @@ if a.size:
     W, H = (int(v) for v in a.size.lower().split("x"))
 if a.supersample != 1:
     kw["supersample"] = a.supersample
+if a.accumulate:
+    if a.accumulate < a.frames:
+        raise SystemExit("--accumulate N needs N >= --frames: a converged view issues no launch to time")
+    kw.update(accumulate=a.accumulate, jitter=not a.no_jitter)
 r = Renderer(sc, tex, sky, W, H, depth=depth, strict=bool(a.strict), **kw)
 r.w.set_variant(a.variant)
 camera = r.look(**cam)
@@ -73,6 +82,8 @@ r.w.enable_counters(1); r.render(readback=False); c = r.w.read_counters(); r.w.e
 r.w.set_async(1)
 kms, walls, reps = [], [], a.repeats
 while len(kms) < max(reps, 1):
+    if a.accumulate:
+        r.reset_accumulation()
     r.w.timing_reset()
     t = time.perf_counter()
     for _ in range(a.frames):
@@ -88,7 +99,7 @@ r.w.set_async(0)
 img = r.render()
 rays = c["segments"] + c["shadow_rays"]
 px = r.pixels
-print(json.dumps(dict(config=a.config, frame=f"{W}x{H}", pixels=px, depth=depth, strict=a.strict, variant=a.variant, supersample=a.supersample, aperture=a.aperture, focus=a.focus, copies=int(a.copies), motion=a.motion, no_tail=int(a.no_tail), kernel_ms=round(ms / n, 4),
+print(json.dumps(dict(config=a.config, frame=f"{W}x{H}", pixels=px, depth=depth, strict=a.strict, variant=a.variant, supersample=a.supersample, aperture=a.aperture, focus=a.focus, copies=int(a.copies), motion=a.motion, no_tail=int(a.no_tail), accumulate=a.accumulate, jitter=int(not a.no_jitter), kernel_ms=round(ms / n, 4),
                       kernel_ms_min=round(min(kms), 4), kernel_ms_max=round(max(kms), 4), repeats=len(kms),
                       wall_ms_per_frame=round(wall * 1e3, 4), rays_per_px=round(rays / px, 3), Mrays_s=round(rays / (ms / n) / 1e3, 1),
                       lane_util=round(c["lane_iters"] / max(c["wave_iters_x64"], 1), 4), counters=c)), flush=True)
