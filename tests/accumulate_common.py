@@ -6,6 +6,8 @@ would pack (clamped to [0, 1]), added one after the other in float32, times floa
 Constituent frame f is the plain frame with seed offset `frame_seed(f)` through the camera `jittered(cam, f, n)`."""
 import numpy as np
 
+from conftest import CAM
+
 F32 = np.float32
 GOLDEN_RATIO_ODD = 0x9E3779B1
 
@@ -71,3 +73,56 @@ def camera_bytes(cam):
     corner, origin, up, right = camera_rows(cam)
     return np.concatenate([corner, origin, up, right, np.array([cam.w_factor, cam.h_factor], F32)]).tobytes() + \
         np.array([cam.width, cam.height], np.uint32).tobytes()
+
+
+# ---- the GPU side (R = renderer.Renderer, api = the api module; `cam`: the view, conftest.CAM unless given; `setup(w)`: knobs set on the wrapper)
+def base_camera(api, W, H, cam=CAM):
+    return api.perspective(cam["origin"], cam["look"], cam["fov"], cam["focal"], W, H)
+
+
+def plain(R, sc, tex, sky, W, H, depth, strict, cam, n=1, seed=0, setup=None, **kw):
+    """one frame of a fresh renderer with the mode off -> (packed, float)"""
+    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, seed_offset=seed, **kw)
+    try:
+        if setup:
+            setup(r.w)
+        r.set_camera(cam)
+        p, f = r.render_rgb()
+        return p.copy(), f.copy()
+    finally:
+        r.release()
+
+
+_own = {}
+
+
+def own_frames(R, api, sc, tex, sky, W, H, n, depth, strict, jitter, count, cam=CAM, name=None, setup=None):
+    """the constituent frames 0 .. count-1 of a view, each from a fresh renderer, rendered once per process (`name` tells scenes, cameras and
+    set-ups apart)"""
+    key = (W, H, n, depth, strict, jitter, name)
+    have = _own.setdefault(key, [])
+    cam = base_camera(api, W, H, cam)
+    while len(have) < count:
+        f = len(have)
+        p, c = plain(R, sc, tex, sky, W, H, depth, strict, api.jitter_camera(cam, f, n) if jitter else cam, n=n, seed=api.frame_seed(f), setup=setup)
+        p.setflags(write=False); c.setflags(write=False)
+        have.append((p, c))
+    return have[:count]
+
+
+def accumulated(R, api, sc, tex, sky, W, H, n, depth, strict, jitter, count, max_frames=64, cam=CAM, setup=None, flags=None, **kw):
+    """`count` frames in a row of one accumulating renderer -> [(packed, float, K) ...]; the flags of the last trace launch are appended to `flags`"""
+    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, accumulate=max_frames, jitter=jitter, **kw)
+    try:
+        if setup:
+            setup(r.w)
+        r.set_camera(base_camera(api, W, H, cam))
+        out = []
+        for _ in range(count):
+            p, f = r.render_rgb()
+            out.append((p.copy(), f.copy(), r.accumulated))
+        if flags is not None:
+            flags.append(r.w.last_trace_flags())
+        return out
+    finally:
+        r.release()

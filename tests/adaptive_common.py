@@ -58,13 +58,13 @@ def resolve(rgb, W, H, n):                      # rgb: float32 [n*H * n*W, 3], v
     return ((c[..., 0] << 16) | (c[..., 1] << 8) | c[..., 2]).reshape(-1), s.reshape(-1, 3)
 
 
-def frames(R, sc, tex, sky, W, H, depth, strict, n=1, count=1, setup=None, rgb=True, **kw):
+def frames(R, sc, tex, sky, W, H, depth, strict, n=1, count=1, setup=None, rgb=True, cam=CAM, **kw):
     """`count` frames in a row from one renderer -> ([(packed, float) ...], flags of the last trace launch); **kw goes to the Renderer"""
     r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, **kw)
     try:
         if setup:
             setup(r.w)
-        r.look(**CAM)
+        r.look(**cam)
         out = []
         for _ in range(count):
             if rgb:
@@ -79,3 +79,34 @@ def frames(R, sc, tex, sky, W, H, depth, strict, n=1, count=1, setup=None, rgb=T
 
 def same_floats(a, b):
     return np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+# ---- the adaptive launch and its check (api = the api module; `cam`: the view, conftest.CAM unless given)
+def adaptive(R, sc, tex, sky, W, H, depth, strict, n, T, count=1, setup=None, cam=CAM, **kw):
+    """`count` adaptive frames in a row from one renderer -> ([(packed, float, mask) ...], flags of the last trace launch)"""
+    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, adaptive=T, **kw)
+    try:
+        if setup:
+            setup(r.w)
+        r.look(**cam)
+        out = []
+        for _ in range(count):
+            p, f = r.render_rgb()
+            out.append((p.copy(), f.copy(), r.w.read_refine_mask()))
+        return out, r.w.last_trace_flags()
+    finally:
+        r.release()
+
+
+def check_composite(api, ref, got, W, rows, n, T, what):
+    """every frame of `got` == where(mask, fine, base) with mask = the host definition on the GPU's own base frame -> the mask"""
+    bp, bf, fp, ff, _ = ref
+    mask = api.refine_mask(bp, W, rows, n, T)
+    want_p, want_f = composite(mask, W, rows, n, bp, fp), composite(mask, W, rows, n, bf, ff)
+    for k, (p, f, m) in enumerate(got):
+        print(f"{what} frame {k}: {mask.mean() * 100:.1f} % of {mask.size} blocks refined, {int((m != mask.reshape(-1)).sum())} mask bytes differ, "
+              f"{int((p != want_p).sum())} packed pixels differ, {int((f.view(np.uint32) != want_f.view(np.uint32)).any(1).sum())} float")
+        assert np.array_equal(m, mask.reshape(-1)), (what, k)
+        assert np.array_equal(p, want_p), (what, k)
+        assert same_floats(f, want_f), (what, k)
+    return mask

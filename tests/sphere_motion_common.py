@@ -6,6 +6,13 @@ the 1-sample render of the n*W x n*H frame of the scene S(t[(vy mod n) * n + (vx
 (api.spheres_at = clw_host_spheres_at); clamp, add and scale as plain supersampling (sample_cameras_common.resolve)."""
 import numpy as np
 
+from conftest import CAM
+from sample_cameras_common import composed, rows_of, virtual_camera
+
+F_SS = 1 << 17      # WT_F_SS of csrc/whitted_trace.inc (clw_ext_last_trace_flags)
+LENS = (0.2, 8.0)
+CAM2 = dict(origin=(1.6, 3.1, -6.5), look=(0.05, -0.15, 1.0), fov=90.0, focal=1.0)      # the other end of a camera shutter
+
 # the demo scene (scene.render_map_scene): sphere 0 (red plastic) and 3 (green glass) stand still, 1 (blue plastic, opaque) and 2 (glass) move
 # by a few tenths of a unit while the shutter is open
 DISP = np.array([[0.0, 0.0, 0.0], [0.5, 0.0, -0.3], [-0.4, 0.2, 0.0], [0.0, 0.0, 0.0]], np.float32)
@@ -37,3 +44,88 @@ def fma32(t, d, c):
     toward = np.where(err > 0, np.inf, -np.inf)
     s = np.where((err != 0) & ~odd, np.nextafter(s, toward), s)
     return s.astype(np.float32)
+
+
+# ---- the GPU side of the definition (R = renderer.Renderer, api = the api module; `cam`, `cam2`: the launch camera and the shutter's other end)
+def same_floats(a, b):
+    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def camera_table(api, W, H, n, kind, cam=CAM, cam2=CAM2):
+    """kind None: n*n copies of the launch camera; (aperture, focus): the lens table; "shutter": cam -> cam2 -> (base camera, float32 [n*n, 12])"""
+    base = api.perspective(**cam, width=W, height=H)
+    if kind is None:
+        return base, np.tile(rows_of(base), (n * n, 1))
+    if kind == "shutter":
+        return base, api.shutter_cameras(base, api.perspective(**cam2, width=W, height=H), n)
+    return base, api.lens_cameras(base, kind[0], kind[1], n)
+
+
+def gpu_virtual(R, api, sc, tex, sky, disp, t, base, row, n, depth, strict, what="rgb", setup=None):
+    """the GPU's own 1-sample render of the n*W x n*H frame of S(t) through the camera `row` of a table"""
+    r = R(moved_scene(api, sc, disp, float(t)), tex, sky, n * base.width, n * base.height, depth=depth, strict=strict)
+    try:
+        if setup:
+            setup(r.w)
+        r.set_camera(virtual_camera(api.clw_camera, row, base, n))
+        out = r.render_rgb()[1] if what == "rgb" else r.render().copy()
+        return out, r.w.last_trace_flags()
+    finally:
+        r.release()
+
+
+def gpu_composed(R, api, sc, tex, sky, disp, times, W, H, n, depth, strict, cams=None, setup=None, cam=CAM, cam2=CAM2):
+    """`composed` over the GPU's own 1-sample virtual frames of the moved scenes -> (packed, float)"""
+    base, table = camera_table(api, W, H, n, cams, cam, cam2)
+
+    def render_virtual(k):
+        f, flags = gpu_virtual(R, api, sc, tex, sky, disp, times[k], base, table[k], n, depth, strict, setup=setup)
+        assert not flags & F_SS
+        return f
+    return composed(render_virtual, table, W, H, n)
+
+
+def moving(R, sc, tex, sky, W, H, n, depth, strict, disp, times=None, cams=None, count=1, setup=None, rgb=True, cam=CAM, **kw):
+    """`count` frames of one supersampled renderer with a displacement table (None = none), optional explicit times and a lens
+    (cams = (aperture, focus)) or a table of cameras (cams = float32 [n*n, 12]) -> [(packed, float)], flags, the times the last launch used"""
+    lens = cams if isinstance(cams, tuple) else None
+    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, lens=lens, motion=disp if times is None else None, **kw)
+    try:
+        if setup:
+            setup(r.w)
+        if times is not None:
+            r.set_sphere_motion(disp, times)
+        if cams is not None and lens is None:
+            r.set_sample_cameras(cams)
+        r.look(**cam)
+        out = []
+        for _ in range(count):
+            if rgb:
+                p, f = r.render_rgb()
+                out.append((p.copy(), f.copy()))
+            else:
+                out.append((r.render().copy(), None))
+        return out, r.w.last_trace_flags(), r.w.get_sample_times()
+    finally:
+        r.release()
+
+
+def check_self_consistent(R, api, sc, tex, sky, W, H, n, depth, strict, disp=DISP, times=None, cams=None, count=1, setup=None, cam=CAM, cam2=CAM2):
+    used_times = api.sample_times(n) if times is None else np.asarray(times, np.float32)
+    want_p, want_f = gpu_composed(R, api, sc, tex, sky, disp, used_times, W, H, n, depth, strict, cams=cams, setup=setup, cam=cam, cam2=cam2)
+    table = None if cams is None or isinstance(cams, tuple) else camera_table(api, W, H, n, cams, cam, cam2)[1]
+    got, flags, used = moving(R, sc, tex, sky, W, H, n, depth, strict, disp, times=times, cams=cams if table is None else table, count=count, setup=setup, cam=cam)
+    assert flags & F_SS
+    assert used.tobytes() == used_times.tobytes()
+    for k, (p, f) in enumerate(got):
+        assert p.shape == (W * H,) and f.shape == (W * H, 3)
+        bad = int((p != want_p).sum())
+        print(f"{W}x{H} n={n} depth {depth} strict={int(strict)} cams={cams} frame {k}: {bad} packed pixels differ, "
+              f"{int((f.view(np.uint32) != want_f.view(np.uint32)).any(1).sum())} float pixels differ")
+        assert np.array_equal(p, want_p), (W, H, n, depth, strict, k, bad)
+        assert same_floats(f, want_f), (W, H, n, depth, strict, k)
+    # and the moving frame is not the static supersampled one
+    static = moving(R, sc, tex, sky, W, H, n, depth, strict, None, cams=cams if table is None else table, rgb=False, setup=setup, cam=cam)[0][0][0]
+    print(f"  {100 * float((static != want_p).mean()):.1f} % of the pixels differ from the static supersampled frame")
+    assert not np.array_equal(static, want_p)
+    return flags, want_p

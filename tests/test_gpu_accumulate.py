@@ -11,7 +11,7 @@ import sys
 import numpy as np
 import pytest
 
-from accumulate_common import fold, jittered
+from accumulate_common import accumulated, base_camera, fold, jittered, own_frames, plain
 from conftest import CAM, ROOT
 from sample_cameras_common import resolve, rows_of, virtual_camera
 
@@ -34,53 +34,6 @@ def api():
     import torch  # noqa: F401  (before the shim is loaded: both then share the ROCm runtime torch ships)
     from example_gui_opencl_raytracer_amd import api
     return api
-
-
-def base_camera(api, W, H):
-    return api.perspective(CAM["origin"], CAM["look"], CAM["fov"], CAM["focal"], W, H)
-
-
-def plain(R, sc, tex, sky, W, H, depth, strict, cam, n=1, seed=0, setup=None, **kw):
-    """one frame of a fresh renderer with the mode off -> (packed, float)"""
-    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, seed_offset=seed, **kw)
-    try:
-        if setup:
-            setup(r.w)
-        r.set_camera(cam)
-        p, f = r.render_rgb()
-        return p.copy(), f.copy()
-    finally:
-        r.release()
-
-
-_own = {}
-
-
-def own_frames(R, api, sc, tex, sky, W, H, n, depth, strict, jitter, count):
-    """the constituent frames 0 .. count-1 of a view, each from a fresh renderer, rendered once per module"""
-    key = (W, H, n, depth, strict, jitter)
-    have = _own.setdefault(key, [])
-    cam = base_camera(api, W, H)
-    while len(have) < count:
-        f = len(have)
-        p, c = plain(R, sc, tex, sky, W, H, depth, strict, api.jitter_camera(cam, f, n) if jitter else cam, n=n, seed=api.frame_seed(f))
-        p.setflags(write=False); c.setflags(write=False)
-        have.append((p, c))
-    return have[:count]
-
-
-def accumulated(R, api, sc, tex, sky, W, H, n, depth, strict, jitter, count, max_frames=64, **kw):
-    """`count` frames in a row of one accumulating renderer -> [(packed, float, K) ...]"""
-    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, accumulate=max_frames, jitter=jitter, **kw)
-    try:
-        r.set_camera(base_camera(api, W, H))
-        out = []
-        for _ in range(count):
-            p, f = r.render_rgb()
-            out.append((p.copy(), f.copy(), r.accumulated))
-        return out
-    finally:
-        r.release()
 
 
 def oracle_frame(oracle, cam, sc, tex, sky, depth, seed):

@@ -11,7 +11,7 @@ import sys
 import numpy as np
 import pytest
 
-from adaptive_common import composite, frames, pixel_mask, resolve, same_floats
+from adaptive_common import adaptive, check_composite, composite, frames, pixel_mask, resolve, same_floats
 from conftest import CAM, ROOT
 
 pytestmark = pytest.mark.gpu
@@ -48,36 +48,6 @@ def refs(R, name, sc, tex, sky, W, H, n, depth, strict, **kw):
             a.setflags(write=False)
         _refs[key] = (bp, bf, fp, ff, flags)
     return _refs[key]
-
-
-def adaptive(R, sc, tex, sky, W, H, depth, strict, n, T, count=1, setup=None, **kw):
-    """`count` adaptive frames in a row from one renderer -> ([(packed, float, mask) ...], flags of the last trace launch)"""
-    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, adaptive=T, **kw)
-    try:
-        if setup:
-            setup(r.w)
-        r.look(**CAM)
-        out = []
-        for _ in range(count):
-            p, f = r.render_rgb()
-            out.append((p.copy(), f.copy(), r.w.read_refine_mask()))
-        return out, r.w.last_trace_flags()
-    finally:
-        r.release()
-
-
-def check_composite(api, ref, got, W, rows, n, T, what):
-    """every frame of `got` == where(mask, fine, base) with mask = the host definition on the GPU's own base frame -> the mask"""
-    bp, bf, fp, ff, _ = ref
-    mask = api.refine_mask(bp, W, rows, n, T)
-    want_p, want_f = composite(mask, W, rows, n, bp, fp), composite(mask, W, rows, n, bf, ff)
-    for k, (p, f, m) in enumerate(got):
-        print(f"{what} frame {k}: {mask.mean() * 100:.1f} % of {mask.size} blocks refined, {int((m != mask.reshape(-1)).sum())} mask bytes differ, "
-              f"{int((p != want_p).sum())} packed pixels differ, {int((f.view(np.uint32) != want_f.view(np.uint32)).any(1).sum())} float")
-        assert np.array_equal(m, mask.reshape(-1)), (what, k)
-        assert np.array_equal(p, want_p), (what, k)
-        assert same_floats(f, want_f), (what, k)
-    return mask
 
 
 # ------------------------------------------------------------------ the setter

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import CAM, channel_diff, frame_mask
+from parity_common import check_exact, report
 
 pytestmark = pytest.mark.gpu
 
@@ -31,14 +32,6 @@ def gpu_frame(R, sc, tex, sky, w, h, depth, strict, cam=CAM, rgb=False, **kw):
     out = r.render_rgb() if rgb else r.render()
     r.release()
     return out
-
-
-def check_exact(got, want, what="", allow=0):
-    """The strict build's bar: every pixel equal.  (At the multi-megapixel sizes a handful of pixels differ where the device libm and the
-    oracle's glibc round one sinf / cosf / powf value differently: those frames go through pin_strict_residual instead.)"""
-    bad = int((got != want).sum())
-    report(dict(test=what, pixels=int(got.size), differing=bad, allowed=allow))
-    assert got.shape == want.shape and bad <= allow, f"{what}: {bad} of {got.size} pixels differ from the oracle (allowed {allow})"
 
 
 def device_libm_rows(w, log):
@@ -102,17 +95,6 @@ def pin_strict_residual(w, got, want, oracle, cam, sc, tex, sky, depth, what, li
         with open(os.path.join(d, "libm_divergence.jsonl"), "a") as f:
             for r in found:
                 f.write(json.dumps(r) + "\n")
-
-
-def report(rec):
-    """Append one JSON line of measured parity figures to gpurun_out/parity_report.jsonl (copied to profiles/)."""
-    import json
-    import os
-    from conftest import ROOT
-    d = os.path.join(ROOT, "gpurun_out")
-    if os.path.isdir(d):
-        with open(os.path.join(d, "parity_report.jsonl"), "a") as f:
-            f.write(json.dumps(rec) + "\n")
 
 
 def check(got, want, exact_min, le1_min=None):
@@ -580,16 +562,10 @@ def test_ragged_sizes(R, oracle, demo_scene, tex, sky, w, h):
 
 
 def test_empty_primitive_lists(R, oracle, demo_scene, tex, sky):
-    from example_gui_opencl_raytracer_amd.scene import Scene
+    from shape_common import empty_list_scenes
     w, h = 96, 64
     cam = oracle.camera(CAM["origin"], CAM["look"], 90.0, 1.0, w, h)
-    cases = {
-        "no spheres": Scene(demo_scene.spheres[:0], demo_scene.planes, demo_scene.lights),
-        "no planes": Scene(demo_scene.spheres, demo_scene.planes[:0], demo_scene.lights),
-        "no lights": Scene(demo_scene.spheres, demo_scene.planes, demo_scene.lights[:0]),
-        "sky only": Scene(demo_scene.spheres[:0], demo_scene.planes[:0], demo_scene.lights[:0]),
-    }
-    for name, sc in cases.items():
+    for name, sc in empty_list_scenes(demo_scene).items():
         want, _, _ = oracle.render(cam, sc, tex, sky, 4)
         got = gpu_frame(R, sc, tex, sky, w, h, 4, True)
         check_exact(got, want, name)

@@ -11,13 +11,12 @@ import numpy as np
 import pytest
 
 from conftest import CAM, ROOT
-from sample_cameras_common import composed, pick, resolve, rows_of, virtual_camera
+from sample_cameras_common import CAM2, composed, gpu_composed, make_table, pick, resolve, rows_of, same_floats, sampled, virtual_camera
 
 pytestmark = pytest.mark.gpu
 
 F_DEEP, F_GRID, F_OCC, F_SHAPE, F_SS = 2, 16, 32, 256, 1 << 17      # WT_F_* of csrc/whitted_trace.inc (clw_ext_last_trace_flags)
 LENS = (0.2, 8.0)
-CAM2 = dict(origin=(1.6, 3.1, -6.5), look=(0.05, -0.15, 1.0), fov=90.0, focal=1.0)      # a clearly different camera (the shutter's other end)
 COUNTED = ("segments", "shadow_rays", "light_probes", "sky_fetches", "texel_fetches", "pushes")
 
 
@@ -32,56 +31,6 @@ def R():
 def api():
     from example_gui_opencl_raytracer_amd import api
     return api
-
-
-def same_floats(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def make_table(api, W, H, n, kind, cam=CAM):
-    """kind: (aperture, focus) = the lens table, "shutter" = an open shutter from CAM to CAM2 -> (base camera, float32 [n*n, 12])"""
-    base = api.perspective(**cam, width=W, height=H)
-    if kind == "shutter":
-        return base, api.shutter_cameras(base, api.perspective(**CAM2, width=W, height=H), n)
-    return base, api.lens_cameras(base, kind[0], kind[1], n)
-
-
-def gpu_composed(R, api, sc, tex, sky, base, table, W, H, n, depth, strict, setup=None):
-    """`composed` over the GPU's own 1-sample virtual frames (one renderer, camera re-set per table entry) -> (packed, float), flags"""
-    r = R(sc, tex, sky, n * W, n * H, depth=depth, strict=strict)
-    try:
-        if setup:
-            setup(r.w)
-
-        def render_virtual(k):
-            r.set_camera(virtual_camera(api.clw_camera, table[k], base, n))
-            return r.render_rgb()[1]
-        want = composed(render_virtual, table, W, H, n)
-        return want, r.w.last_trace_flags()
-    finally:
-        r.release()
-
-
-def sampled(R, sc, tex, sky, W, H, n, depth, strict, kind, table=None, count=1, setup=None, cam=CAM, rgb=True, **kw):
-    """`count` frames of one supersampled renderer with a lens (kind = (aperture, focus)), an explicit table (kind "shutter" / "table") or
-    neither (kind None) -> [(packed, float)], flags, the table the last launch used"""
-    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, lens=kind if isinstance(kind, tuple) else None, **kw)
-    try:
-        if setup:
-            setup(r.w)
-        if kind in ("shutter", "table"):
-            r.set_sample_cameras(table)
-        r.look(**cam)
-        out = []
-        for _ in range(count):
-            if rgb:
-                p, f = r.render_rgb()
-                out.append((p.copy(), f.copy()))
-            else:
-                out.append((r.render().copy(), None))
-        return out, r.w.last_trace_flags(), r.w.get_sample_cameras()
-    finally:
-        r.release()
 
 
 def check_self_consistent(R, api, sc, tex, sky, W, H, n, depth, strict, kind=LENS, count=1, setup=None):

@@ -1,38 +1,21 @@
 """The shaped trace kernel: small LDS-geometry scenes of the shallow fast build run a kernel with the scene's sphere, plane and light
-counts compiled in (wt_shape in csrc/whitted_trace.inc; 1-4 spheres, 0-2 planes, 3 lights).  It must give the generic kernel's frame
-bit for bit, and every other scene must keep the generic kernel.  Variant 8192 forces the generic kernel, so both run in one process.
+counts compiled in (wt_shape in csrc/whitted_trace.inc).  It must give the generic kernel's frame bit for bit, and every other scene must keep
+the generic kernel.  This module holds the bench-sized frames and the scenes just outside the compiled set; every compiled count pair, in every
+sampling mode, is swept by tests/test_gpu_shape_modes.py.  Variant 8192 forces the generic kernel, so both run in one process.
 (The strict build has no shaped flavour: its small scenes always take the generic kernel, checked below.)"""
 import numpy as np
 import pytest
 
 from conftest import CAM
+from shape_common import F_DEEP, F_GEOM_LDS, F_SHAPE, V_GENERIC, frame, shape_of
 
 pytestmark = pytest.mark.gpu
-
-F_DEEP, F_GEOM_LDS, F_SHAPE, V_GENERIC = 2, 4, 256, 8192
-
 
 @pytest.fixture(scope="module")
 def R():
     import torch  # noqa: F401  (the shim then shares torch's ROCm runtime)
     from example_gui_opencl_raytracer_amd.renderer import Renderer
     return Renderer
-
-
-def frame(R, sc, tex, sky, w, h, depth, variant, cam=CAM, strict=False):
-    """-> (packed frame, float radiance, flags of the trace launch)"""
-    r = R(sc, tex, sky, w, h, depth=depth, strict=strict)
-    try:
-        r.w.set_variant(variant)
-        r.look(**cam)
-        out, rgb = r.render_rgb()
-        return out, rgb, r.w.last_trace_flags()
-    finally:
-        r.release()
-
-
-def shape_of(flags):
-    return (flags >> 9) & 7, (flags >> 12) & 3, (flags >> 14) & 7
 
 
 def check_pair(R, sc, tex, sky, w, h, depth, cam=CAM, shaped=True):
@@ -74,7 +57,9 @@ def _variants(sc):
     from example_gui_opencl_raytracer_amd.scene import Scene
     s, p, l = sc.spheres, sc.planes, sc.lights
     inside = {"1 sphere": Scene(s[:1], p, l), "2 spheres": Scene(s[:2], p, l), "3 spheres": Scene(s[1:], p, l),
-              "1 plane": Scene(s, p[1:], l), "no planes": Scene(s, p[:0], l), "3 spheres 1 plane": Scene(s[:3], p[:1], l)}
+              "1 plane": Scene(s, p[1:], l), "no planes": Scene(s, p[:0], l), "3 spheres 1 plane": Scene(s[:3], p[:1], l),
+              "1 sphere 1 plane": Scene(s[2:3], p[:1], l), "2 spheres no planes": Scene(s[1:3], p[:0], l), "2 spheres 1 plane": Scene(s[2:], p[1:], l),
+              "3 spheres no planes": Scene(s[:3], p[:0], l)}
     s5 = np.concatenate([s, s[:1]])
     s5[4]["origin"] = (-3.0, 0.6, 2.0)
     l4 = np.concatenate([l, l[:1]])
