@@ -44,6 +44,7 @@ SYMBOLS = [
     "clw_ext_set_adaptive", "clw_ext_get_adaptive", "clw_ext_read_refine_mask", "clw_host_refine_mask",
     "clw_ext_set_seed_offset", "clw_ext_get_seed_offset", "clw_ext_set_accumulate", "clw_ext_get_accumulated", "clw_ext_reset_accumulation",
     "clw_host_frame_seed", "clw_host_jitter_camera",
+    "clw_ext_set_split", "clw_ext_get_split", "clw_ext_get_tpt", "clw_ext_read_tile_order", "clw_ext_unit_sched",
 ]
 
 
@@ -165,6 +166,13 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
     L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
     L.clw_ext_read_tile_costs.restype = u32
+    L.clw_ext_set_split.argtypes = [W, C.c_int, C.c_int]
+    L.clw_ext_get_split.argtypes = [W, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    L.clw_ext_get_tpt.argtypes = [W, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    L.clw_ext_read_tile_order.argtypes = [W, vp, u32, C.POINTER(u32)]
+    L.clw_ext_read_tile_order.restype = u32
+    L.clw_ext_unit_sched.argtypes = [W, vp, u32, u32, C.c_int, u32, u32, u32, u32, vp, u32]
+    L.clw_ext_unit_sched.restype = u32
     L.clw_ext_read_counters.argtypes = [W, C.POINTER(C.c_uint64 * 8)]
     L.clw_ext_read_counters_ex.argtypes = [W, C.POINTER(C.c_uint64 * 32), u32]
     L.clw_ext_invalidate_scene.argtypes = [W]
@@ -370,6 +378,39 @@ class ClWrap:
             self.L.clw_ext_read_tile_costs(C.byref(self.w), _ptr(out), n)
         return out
 
+    def read_tile_order(self):
+        """(order words [8 * per_share_cap], per_share_cap) the last tiled launch read; (empty, 0) = it ran in the default order."""
+        cap = C.c_uint32()
+        n = self.L.clw_ext_read_tile_order(C.byref(self.w), None, 0, C.byref(cap))
+        out = np.zeros(n, np.uint32)
+        if n:
+            self.L.clw_ext_read_tile_order(C.byref(self.w), _ptr(out), n, C.byref(cap))
+        return out, int(cap.value)
+
+    def unit_sched(self, cost: np.ndarray, tpr: int, trows: int, clamp_outliers: int, per_share_cap: int, split_slots: int, min_quota: int,
+                   max_lg: int) -> np.ndarray:
+        """Run wt_sched_build once on a cost table (see clw_ext_unit_sched) -> the whole sentinel-filled buffer, uint32."""
+        cost = np.ascontiguousarray(cost, np.uint32).reshape(-1)
+        assert cost.size == tpr * trows
+        a = (int(tpr), int(trows), int(clamp_outliers), int(per_share_cap), int(split_slots), int(min_quota), int(max_lg))
+        n = self.L.clw_ext_unit_sched(C.byref(self.w), _ptr(cost), *a, None, 0)
+        out = np.zeros(n, np.uint32)
+        self.L.clw_ext_unit_sched(C.byref(self.w), _ptr(cost), *a, _ptr(out), n)
+        return out
+
+    def get_split(self):
+        """(split_slots, min_quota, extra entries per share of a launch that may split) in effect."""
+        v = [C.c_uint32() for _ in range(3)]
+        self.L.clw_ext_get_split(C.byref(self.w), *[C.byref(x) for x in v])
+        return tuple(int(x.value) for x in v)
+
+    def get_tpt(self):
+        """(max_lanes, min_paths, pool_mb) of the tree-parallel tail in effect."""
+        v = [C.c_uint32() for _ in range(3)]
+        self.L.clw_ext_get_tpt(C.byref(self.w), *[C.byref(x) for x in v])
+        return tuple(int(x.value) for x in v)
+
+    def set_split(self, slots=-1, min_quota=-1): self.L.clw_ext_set_split(C.byref(self.w), int(slots), int(min_quota))
     def set_shadow_through(self, f): self.L.clw_ext_set_shadow_through(C.byref(self.w), float(f))
     def set_grid(self, on): self.L.clw_ext_set_grid(C.byref(self.w), int(on))
     def set_tile_sched(self, on): self.L.clw_ext_set_tile_sched(C.byref(self.w), int(on))

@@ -240,10 +240,11 @@ struct Impl {
         hipEvent_t traced = nullptr;
         uint32_t w = 0, rows = 0, cap = 0;           /* frame the buffers were sized for (the virtual frame of a supersampled launch); dispatch entries per XCD share */
         int ss = 1;                                   /* supersampling factor its orders were built for: it caps how far a tile is split */
+        int last_rd = -1;                             /* order[] the last tiled launch read; -1 = it ran in the default order (clw_ext_read_tile_order) */
         wt_cam_table sig_cams{}; bool sig_has_cams = false;   /* the sample cameras belong to the signature below */
         std::vector<float> sig_motion;                        /* ... and so do the moving spheres' device table (empty = none) */
         RaygenArgs sig{}; int sig_depth = 0; uint64_t sig_scene = 0; bool sig_valid = false; int sig_age = 0, newest = 0; uint64_t frame = 0, newest_frame = 0;   /* what the newest order was built for, frames since */
-        void reset() { have[0] = have[1] = false; sig_valid = false; newest = 0; }
+        void reset() { have[0] = have[1] = false; sig_valid = false; newest = 0; last_rd = -1; }
         void free_all() {
             for (int i = 0; i < 2; i++) {
                 if (cost[i]) (void)hipFree(cost[i]);
@@ -824,6 +825,7 @@ bool trace_launch(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Str
         A.blocks = trows * tpr;
         P.tile_order = A.order; P.list_count = A.count;
     } else if (P.tiled) {
+        if (!strip) S.last_rd = -1;
         if (I->sched && !(I->variant & 4) && trows <= 0xFFFu && tpr <= 0xFFFu) {   /* the order packs (tile column | row << 12 | parts) */
             /* a part of a split tile owns 8 >> lg whole tile rows; a supersampled launch needs ss of them in one wavefront (ss = 8: no split) */
             split = tail_wanted && !(flags & F_GRID) && I->split_min_quota != 0u && !(I->variant & 4096) && split_max_lg != 0u;
@@ -850,6 +852,7 @@ bool trace_launch(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Str
             if (S.have[wr]) HIP_OK(hipStreamWaitEvent(I->stream, S.built[wr], 0), "Couldn't run the kernel");
             if (rd >= 0 && rd != wr) HIP_OK(hipStreamWaitEvent(I->stream, S.built[rd], 0), "Couldn't run the kernel");
             P.tile_order = rd >= 0 ? S.order[rd] : nullptr;
+            if (!strip) S.last_rd = rd;
             /* the costs can only change when the camera, the depth or the scene did */
             sched_rebuild = !S.sig_valid || !same_raygen(g, S.sig) || S.sig_depth != I->depth || S.sig_scene != I->scene_generation ||
                             S.sig_has_cams != have_cams || (have_cams && memcmp(&S.sig_cams, &cam_table, sizeof cam_table)) || !same_bits(S.sig_motion, motion_table);
@@ -1362,6 +1365,56 @@ uint32_t clw_ext_read_tile_costs(cl_wrap* wrap, uint32_t* out, uint32_t capacity
     if (out && capacity >= n) HIP_OK(hipMemcpy(out, S.cost[S.wr ^ 1], (size_t)n * 4, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
     return n;
 }
+uint32_t clw_ext_read_tile_order(cl_wrap* wrap, uint32_t* out, uint32_t capacity, uint32_t* per_share_cap) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    finish(I);
+    if (I->sched_stream) HIP_OK(hipStreamSynchronize(I->sched_stream), "The device kernel failed");
+    const Impl::Sched& S = I->scheds[0];
+    if (per_share_cap) *per_share_cap = 0;
+    if (S.last_rd < 0 || !S.order[S.last_rd]) return 0;
+    if (per_share_cap) *per_share_cap = S.cap;
+    const uint32_t n = 8u * S.cap;
+    if (out && capacity >= n) HIP_OK(hipMemcpy(out, S.order[S.last_rd], (size_t)n * 4, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
+    return n;
+}
+uint32_t clw_ext_unit_sched(cl_wrap* wrap, const uint32_t* cost, uint32_t tpr, uint32_t trows, int clamp_outliers, uint32_t per_share_cap,
+                            uint32_t split_slots, uint32_t min_quota, uint32_t max_lg, uint32_t* out, uint32_t out_words) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    if (tpr == 0 || trows == 0 || tpr > 0xFFFu || trows > 0xFFFu || max_lg > 4u) die("clw_ext_unit_sched: %u x %u tiles, max_lg %u", tpr, trows, max_lg);
+    const uint32_t per_share = ((trows + 7u) / 8u) * tpr;
+    if (per_share_cap < per_share) die("clw_ext_unit_sched: per_share_cap %u is below the %u tiles of a share", per_share_cap, per_share);
+    const uint64_t words = 8ull * ((uint64_t)per_share << max_lg) + 8ull * per_share_cap;
+    if (words > 0xFFFFFFFFull) die("clw_ext_unit_sched: the table is too large");
+    if (!out || out_words < words) return (uint32_t)words;
+    const size_t ntiles = (size_t)trows * tpr;
+    unsigned *dcost = nullptr, *dorder = nullptr;
+    HIP_OK(hipMalloc((void**)&dcost, ntiles * 4), "Couldn't allocate device memory");
+    HIP_OK(hipMalloc((void**)&dorder, (size_t)words * 4), "Couldn't allocate device memory");
+    HIP_OK(hipMemcpy(dcost, cost, ntiles * 4, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+    std::vector<uint32_t> fill((size_t)words, CLW_SCHED_SENTINEL);
+    HIP_OK(hipMemcpy(dorder, fill.data(), (size_t)words * 4, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+    HIP_OK(hipDeviceSynchronize(), "The device kernel failed");
+    if (wt_fast_launch_sched(dcost, dorder, tpr, trows, per_share, clamp_outliers ? 1u : 0u, per_share_cap, split_slots, min_quota, max_lg, I->stream) != hipSuccess)
+        die("Couldn't run the kernel");
+    finish(I);
+    HIP_OK(hipMemcpy(out, dorder, (size_t)words * 4, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
+    (void)hipFree(dcost); (void)hipFree(dorder);
+    return (uint32_t)words;
+}
+void clw_ext_set_split(cl_wrap* wrap, int slots, int min_quota) {
+    Impl* I = impl_of(wrap);
+    if (slots >= 0) I->split_slots = (unsigned)std::max(1, slots);
+    if (min_quota >= 0) I->split_min_quota = (unsigned)min_quota;
+    for (auto& sc : I->scheds) sc.reset();
+}
+void clw_ext_get_split(const cl_wrap* wrap, uint32_t* slots, uint32_t* min_quota, uint32_t* extra_per_share) {
+    const Impl* I = impl_of(wrap);
+    if (slots) *slots = I->split_slots;
+    if (min_quota) *min_quota = I->split_min_quota;
+    if (extra_per_share) *extra_per_share = SPLIT_EXTRA_PER_SHARE;
+}
 void clw_ext_set_shadow_through(cl_wrap* wrap, float factor) { impl_of(wrap)->through = factor; }
 void clw_ext_set_grid(cl_wrap* wrap, int on) { impl_of(wrap)->use_grid = on ? 1 : 0; }
 void clw_ext_set_tile_sched(cl_wrap* wrap, int on) { Impl* I = impl_of(wrap); I->sched = on ? 1 : 0; for (auto& sc : I->scheds) sc.reset(); }
@@ -1372,6 +1425,12 @@ void clw_ext_set_tpt(cl_wrap* wrap, int max_lanes, int min_paths, int pool_mb) {
     if (max_lanes >= 0) I->tpt_max = (unsigned)std::min(max_lanes, 64);
     if (min_paths >= 0) I->tpt_min = (unsigned)min_paths;
     if (pool_mb >= 0) I->tpt_pool_mb = (unsigned)pool_mb;
+}
+void clw_ext_get_tpt(const cl_wrap* wrap, uint32_t* max_lanes, uint32_t* min_paths, uint32_t* pool_mb) {
+    const Impl* I = impl_of(wrap);
+    if (max_lanes) *max_lanes = I->tpt_max;
+    if (min_paths) *min_paths = I->tpt_min;
+    if (pool_mb) *pool_mb = I->tpt_pool_mb;
 }
 void clw_ext_set_debug_rgb(cl_wrap* wrap, void* p) { impl_of(wrap)->debug_rgb = (float*)p; }
 void clw_ext_set_supersample(cl_wrap* wrap, int n) {

@@ -1782,6 +1782,7 @@ __global__ void __launch_bounds__(256) wt_sched_build(const unsigned* __restrict
         quota = (unsigned)(q > 0x7FFFFFFFull ? 0x7FFFFFFFull : q);
         if (quota < min_quota) quota = min_quota;
         if (quota == 0u) quota = 1u;
+        bool fitted = false;
         for (int trial = 0; trial < 24; trial++) {
             if (tid == 0) s_entries = 0u;
             __syncthreads();
@@ -1794,9 +1795,12 @@ __global__ void __launch_bounds__(256) wt_sched_build(const unsigned* __restrict
             __syncthreads();
             const bool fits = s_entries <= per_share_cap;
             __syncthreads();
-            if (fits) break;
-            quota = quota > 0x3FFFFFFFu ? 0xFFFFFFFFu : quota * 2u;      /* (ends at "never split": cnt <= per_share <= per_share_cap) */
+            if (fits) { fitted = true; break; }
+            quota = quota > 0x3FFFFFFFu ? 0xFFFFFFFFu : quota * 2u;
         }
+        /* the doubling reaches "never split" by itself only from a quota of 2^8 or more: a smaller one with huge costs gets there here, so
+         * that the scatter below always stays inside the list (cnt <= per_share <= per_share_cap) */
+        if (!fitted) quota = 0xFFFFFFFFu;
     }
     auto parts_lg = [&](unsigned c) { unsigned lg = 0u; while (lg < max_lg && (c >> lg) > quota) lg++; return lg; };
     /* costs are iteration counts, total work or wave durations (any range): 256 bins scaled by the share's maximum.  Durations have
@@ -1816,7 +1820,7 @@ __global__ void __launch_bounds__(256) wt_sched_build(const unsigned* __restrict
         const unsigned trow = (j / tpr) * 8u + k;
         if (trow < trows) {
             const unsigned c0 = cost[trow * tpr + (j % tpr)], lg = parts_lg(c0);
-            const unsigned c = min((unsigned)((float)(c0 >> lg) * scale), 255u);
+            const unsigned c = (unsigned)fminf((float)(c0 >> lg) * scale, 255.0f);   /* (clamped as a float: with `clamp_outliers` the product can pass 2^32) */
             atomicAdd(&hist[255u - c], 1u << lg);
         }
     }
@@ -1833,7 +1837,7 @@ __global__ void __launch_bounds__(256) wt_sched_build(const unsigned* __restrict
         if (trow < trows) {
             const unsigned tcol = j % tpr, t = trow * tpr + tcol;
             const unsigned lg = parts_lg(cost[t]);
-            const unsigned c = min((unsigned)((float)(cost[t] >> lg) * scale), 255u);
+            const unsigned c = (unsigned)fminf((float)(cost[t] >> lg) * scale, 255.0f);
             const unsigned pos = atomicAdd(&base[255u - c], 1u << lg);
             for (unsigned q = 0; q < (1u << lg); q++) order[8u * (pos + q) + k] = tcol | (trow << 12) | (lg << 24) | (q << 27);
         }

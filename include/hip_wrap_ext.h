@@ -274,6 +274,33 @@ uint32_t clw_ext_read_tile_costs(cl_wrap* wrap, uint32_t* out, uint32_t capacity
 void clw_ext_unit(cl_wrap* wrap, int op, const float* in, uint32_t stride_in, float* out, uint32_t stride_out,
                   uint32_t n, uint32_t aux);
 
+/* Runs the dispatch-order builder (wt_sched_build, csrc/whitted_trace.inc) ONCE on a caller's cost table -- `cost` = trows x tpr words, row-major
+ * 8x8 tiles, as clw_ext_read_tile_costs returns them -- with exactly the arguments the shim gives it, per_share = ceil(trows / 8) * tpr:
+ *   clamp_outliers 0 / 1 (1 = the scale of the 256 bins stops at 16x the share's mean: grid builds), per_share_cap >= per_share = entries per
+ *   XCD share, split_slots (0 = no tile is split), min_quota, max_lg in 0..4 (a tile is served by at most 2^max_lg wavefronts).
+ * The order is order[8 * pos + k] = entry `pos` of share k (the tiles of tile rows = k mod 8), heaviest first; an entry is
+ *   tile column | tile row << 12 | lg << 24 | part << 27, or 0xFFFFFFFF = none.
+ * The device buffer is allocated for the worst case, 8 * (per_share << max_lg) + 8 * per_share_cap words, pre-filled with CLW_SCHED_SENTINEL
+ * (neither an entry nor 0xFFFFFFFF) and returned WHOLE: a builder that writes beyond its 8 * per_share_cap words shows as overwritten sentinels,
+ * never as an access outside an allocation.  Returns that number of words; copies them if `out_words` suffices (else nothing is launched).
+ * Errors (print + exit(1)): an empty table, more than 4095 tiles either way, max_lg > 4, per_share_cap < per_share.  For tests. */
+#define CLW_SCHED_SENTINEL 0xA5A5A5A5u
+uint32_t clw_ext_unit_sched(cl_wrap* wrap, const uint32_t* cost, uint32_t tpr, uint32_t trows, int clamp_outliers, uint32_t per_share_cap,
+                            uint32_t split_slots, uint32_t min_quota, uint32_t max_lg, uint32_t* out, uint32_t out_words);
+/* The order buffer the LAST tiled launch of a whole range (not a strip of the pipelined read-back) actually read, 8 * per_share_cap words laid
+ * out as above -> their count, and per_share_cap through the pointer (may be NULL); 0 = that launch ran in the default order (no order built
+ * yet, tile order off, variant 4) or there was none.  Copies the words if `capacity` suffices.  Waits for the launch and for a build behind it.
+ * The shim remembers WHICH of its two buffers the launch read; a launch that also rebuilds (its camera, depth or scene changed) may have that
+ * buffer rewritten behind it, so pair the call with a still view: the order is then the one built from the first frame's costs.  For tests. */
+uint32_t clw_ext_read_tile_order(cl_wrap* wrap, uint32_t* out, uint32_t capacity, uint32_t* per_share_cap);
+/* How heavy tiles of deep launches are split: the quota of a share is its total cost over `slots` wavefronts (default 512, at least 1; env
+ * CLWRAP_SPLIT_SLOTS), and at least `min_quota` (default 1500; 0 = no tile is split; env CLWRAP_SPLIT_MIN_QUOTA).  A negative argument keeps the
+ * current value.  Same image whatever the settings.  The orders built so far are dropped, as by clw_ext_set_tile_sched: the next launch runs in
+ * the default order and the one after it in an order built with the new values. */
+void clw_ext_set_split(cl_wrap* wrap, int slots, int min_quota);
+/* The values in effect, and how many entries a share's list has beyond its tiles in a launch that may split (any pointer may be NULL). */
+void clw_ext_get_split(const cl_wrap* wrap, uint32_t* slots, uint32_t* min_quota, uint32_t* extra_per_share);
+
 /* The same for the helpers that need the SCENE: runs on the scene bound to raytracer kernel `kernel_id` (its args 1-6,
  * 8, 9), through the code the trace kernel itself runs (its hit phase and its batched shadow traversal).
  * op: 0 hit phase {o,d -> lit, light rgb[3], solid hit, point[3], normal[3], material rgb[3], ambient, diffuse, specular,
@@ -311,6 +338,8 @@ int clw_ext_last_trace_flags(cl_wrap* wrap);
  * CLWRAP_TPT_MAX / CLWRAP_TPT_MIN / CLWRAP_TPT_POOL_MB.  Counting build: counter words 29 / 30 / 31 = tiles the tail gave up on (slice
  * full: finished by the per-lane loop) / tiles it finished / nodes it traced. */
 void clw_ext_set_tpt(cl_wrap* wrap, int max_lanes, int min_paths, int pool_mb);
+/* The values in effect (any pointer may be NULL). */
+void clw_ext_get_tpt(const cl_wrap* wrap, uint32_t* max_lanes, uint32_t* min_paths, uint32_t* pool_mb);
 
 /* Host helper: camera -> the eight by-value raygen arguments, with the reference's exact
  * mixed float/double arithmetic (rinit_camera + rgen_perspective, src/cpu_ray.c:8-35, 42-106).
