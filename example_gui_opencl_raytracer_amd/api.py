@@ -45,7 +45,31 @@ SYMBOLS = [
     "clw_ext_set_seed_offset", "clw_ext_get_seed_offset", "clw_ext_set_accumulate", "clw_ext_get_accumulated", "clw_ext_reset_accumulation",
     "clw_host_frame_seed", "clw_host_jitter_camera",
     "clw_ext_set_split", "clw_ext_get_split", "clw_ext_get_tpt", "clw_ext_read_tile_order", "clw_ext_unit_sched",
+    "clw_ext_render_gbuffer", "clw_ext_read_gbuffer", "clw_ext_gbuffer_device_ptr", "clw_ext_pick",
 ]
+
+# the channels of the primary-hit pass (hip_wrap_ext.h: CLW_GB_*), the id of a miss and the pass's id in the timing log
+GB_DEPTH, GB_ID, GB_NORMAL, GB_POINT, GB_ALBEDO, GB_ALL = 1, 2, 4, 8, 16, 31
+ID_NONE = 0xFFFFFFFF
+ID_SPHERE, ID_PLANE, ID_LIGHT = 0, 1, 2
+TIMING_GBUFFER = 0x47425546
+GB_CHANNELS = {"depth": (GB_DEPTH, np.float32, 1), "id": (GB_ID, np.uint32, 1), "normal": (GB_NORMAL, np.float32, 3),
+               "point": (GB_POINT, np.float32, 3), "albedo": (GB_ALBEDO, np.float32, 3)}     # name -> (bit, dtype, entries per work-item)
+
+
+def id_kind(ids):
+    """Kind of the entries of an id channel (0 sphere, 1 plane, 2 light; 3 for ID_NONE)."""
+    return np.asarray(ids, np.uint32) >> np.uint32(30)
+
+
+def id_index(ids):
+    """Index into the caller's sphere / plane / light array of the entries of an id channel (meaningless for ID_NONE)."""
+    return np.asarray(ids, np.uint32) & np.uint32(0x3FFFFFFF)
+
+
+def make_id(kind, index):
+    """kind << 30 | index, as the id channel stores it."""
+    return (np.asarray(kind, np.uint32) << np.uint32(30)) | np.asarray(index, np.uint32)
 
 
 def library_version() -> str:
@@ -77,6 +101,11 @@ class clw_camera(C.Structure):
 class clw_sample_camera(C.Structure):
     """One entry of a table of sample cameras (48 bytes): row k of the float32 [n*n, 12] arrays below."""
     _fields_ = [("im_corner", C.c_float * 3), ("origin", C.c_float * 3), ("up", C.c_float * 3), ("right", C.c_float * 3)]
+
+
+class clw_pick(C.Structure):
+    """What clw_ext_pick returns (44 bytes): the entries of one pixel in the channels of the primary-hit pass."""
+    _fields_ = [("id", C.c_uint32), ("depth", C.c_float), ("point", C.c_float * 3), ("normal", C.c_float * 3), ("albedo", C.c_float * 3)]
 
 
 _lib = None
@@ -163,6 +192,15 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         L.clw_host_frame_seed.restype = u32
         L.clw_host_jitter_camera.argtypes = [C.POINTER(clw_camera), u32, u32, C.POINTER(clw_camera)]
         L.clw_host_jitter_camera.restype = C.c_int
+    if hasattr(L, "clw_ext_render_gbuffer") or not os.environ.get("CLWRAP_LIB"):          # (an older A/B build may lack them)
+        L.clw_ext_render_gbuffer.argtypes = [W, u32]
+        L.clw_ext_render_gbuffer.restype = u32
+        L.clw_ext_read_gbuffer.argtypes = [W, u32, vp, u32]
+        L.clw_ext_read_gbuffer.restype = u32
+        L.clw_ext_gbuffer_device_ptr.argtypes = [W, u32]
+        L.clw_ext_gbuffer_device_ptr.restype = vp
+        L.clw_ext_pick.argtypes = [W, u32, u32, C.POINTER(clw_pick)]
+        L.clw_ext_pick.restype = C.c_int
     L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
     L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
     L.clw_ext_read_tile_costs.restype = u32
@@ -445,6 +483,28 @@ class ClWrap:
     def set_accumulate(self, max_frames, jitter=True): self.L.clw_ext_set_accumulate(C.byref(self.w), int(max_frames), int(jitter))
     def get_accumulated(self): return int(self.L.clw_ext_get_accumulated(C.byref(self.w)))
     def reset_accumulation(self): self.L.clw_ext_reset_accumulation(C.byref(self.w))
+
+    def render_gbuffer(self, channels=GB_ALL) -> int:
+        """Launch the primary-hit pass over the range the next trace launch would cover -> work-items (0 = no camera latched / no known channel)."""
+        return int(self.L.clw_ext_render_gbuffer(C.byref(self.w), int(channels)))
+
+    def read_gbuffer(self, channel) -> np.ndarray:
+        """One channel (a GB_* bit) of the last pass -> float32 [n] / uint32 [n] / float32 [n, 3]; empty for a channel it did not write."""
+        _, dtype, per = next(v for v in GB_CHANNELS.values() if v[0] == channel)
+        nbytes = int(self.L.clw_ext_read_gbuffer(C.byref(self.w), int(channel), None, 0))
+        out = np.zeros(nbytes // 4, dtype)
+        if nbytes:
+            assert self.L.clw_ext_read_gbuffer(C.byref(self.w), int(channel), _ptr(out), nbytes) == nbytes
+        return out.reshape(-1, 3) if per == 3 else out
+
+    def gbuffer_device_ptr(self, channel):
+        """Device address of one channel of the last pass (None for a channel it did not write)."""
+        return self.L.clw_ext_gbuffer_device_ptr(C.byref(self.w), int(channel))
+
+    def pick(self, x, y):
+        """clw_ext_pick: the clw_pick of frame pixel (x, y), or None (no camera latched, or the pixel is not one of this wrapper's)."""
+        p = clw_pick()
+        return p if self.L.clw_ext_pick(C.byref(self.w), int(x), int(y), C.byref(p)) else None
 
     def set_adaptive(self, threshold): self.L.clw_ext_set_adaptive(C.byref(self.w), int(threshold))
     def get_adaptive(self): return int(self.L.clw_ext_get_adaptive(C.byref(self.w)))

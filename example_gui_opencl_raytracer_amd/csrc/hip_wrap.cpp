@@ -36,6 +36,8 @@ extern "C" hipError_t wt_fast_launch_unit(int, const float*, float*, unsigned, u
 extern "C" hipError_t wt_strict_launch_unit(int, const float*, float*, unsigned, unsigned, unsigned, unsigned, hipStream_t);
 extern "C" hipError_t wt_fast_launch_unit_scene(const whitted_params*, int, int, const float*, float*, unsigned, unsigned, unsigned, size_t, hipStream_t);
 extern "C" hipError_t wt_strict_launch_unit_scene(const whitted_params*, int, int, const float*, float*, unsigned, unsigned, unsigned, size_t, hipStream_t);
+extern "C" hipError_t wt_fast_launch_gbuffer(const whitted_params*, int, unsigned, size_t, float*, unsigned*, float*, float*, float*, hipStream_t);
+extern "C" hipError_t wt_strict_launch_gbuffer(const whitted_params*, int, unsigned, size_t, float*, unsigned*, float*, float*, float*, hipStream_t);
 extern "C" hipError_t wt_fast_launch_cams(const wt_cam_table*, float*, hipStream_t);
 extern "C" hipError_t wt_fast_launch_classify(const unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned char*, unsigned*, unsigned*, unsigned, hipStream_t);
 extern "C" hipError_t wt_fast_launch_sched(const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
@@ -214,6 +216,17 @@ struct Impl {
         uint64_t epoch = 0;                           /* bumped by whatever changes the image behind the key's back (uploads, invalidate, reset) */
         bool key_valid = false; AccKey key;
     } acc;
+    /* the primary-hit pass (clw_ext_render_gbuffer / clw_ext_pick; whitted_gbuffer.inc): planar channel buffers indexed like the framebuffer, one per
+     * CLW_GB_* bit, allocated when a pass first asks for them and sized for the pass's range; `done` is recorded behind every pass on the stream it
+     * ran on, so a read-back waits for the pass whatever the launch stream is by then */
+    struct GBuffer {
+        void* chan[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   /* depth, id, normal, point, albedo */
+        uint32_t n = 0;                 /* work-items the buffers are sized for */
+        uint32_t written = 0;           /* the channels of the last pass */
+        uint32_t* pick = nullptr;       /* the 11 words of one clw_pick: a pick is the pass on a one-pixel range, its channels laid out as the struct */
+        hipEvent_t done = nullptr;
+        void free_channels() { for (void*& q : chan) { if (q) (void)hipFree(q); q = nullptr; } n = 0; written = 0; }
+    } gb;
     /* prepared scene cache */
     const Buffer *prep_s = nullptr, *prep_p = nullptr, *prep_l = nullptr;
     uint32_t prep_ns = 0, prep_np = 0, prep_nl = 0;
@@ -1057,6 +1070,57 @@ void run_raygen(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size) {
     }
 }
 
+/* ---- the primary-hit pass -------------------------------------------------------------------------------------------------------- */
+constexpr uint32_t GB_WORDS[5] = {1, 1, 3, 3, 3};      /* 4-byte words per work-item of the channels depth, id, normal, point, albedo */
+
+/* The pass's launch parameters over the range the next trace launch would cover: the camera and range the raygen launch latched, clipped by
+ * the raytracer's `pixels` argument, bands included; the scene as bind_scene binds it.  false (nothing filled in) when there is no raytracer
+ * kernel, no latched camera or no bound scene yet -- the callers return 0 then, they do not terminate the process. */
+bool gbuffer_params(cl_wrap* w, Impl* I, whitted_params& P, int& flags, size_t& dyn_lds) {
+    cl_uint kid = 0;
+    while (kid < I->kernels.size() && I->kernels[kid].kind != K_RAYTRACER) kid++;
+    if (kid >= I->kernels.size()) return false;
+    const Kernel& k = I->kernels[kid];
+    Buffer* rays = nullptr;
+    if (is_registered(w, kid, 0)) rays = (Buffer*)w->buffers[kid][0];
+    else if (k.values[0].set && k.values[0].size == sizeof(cl_mem)) { void* h; memcpy(&h, k.values[0].bytes, sizeof h); rays = lookup_handle(I, h); }
+    if (!rays || !rays->gen_valid) return false;
+    for (cl_uint a : {1u, 2u, 3u, 8u, 9u}) if (!is_registered(w, kid, a)) return false;
+    for (cl_uint a : {4u, 5u, 6u}) if (!k.values[a].set) return false;
+    if (!k.values[7].set || k.values[7].size != 4) return false;
+    uint32_t total; memcpy(&total, k.values[7].bytes, 4);
+    const RaygenArgs& g = rays->gen;
+    const uint32_t n = g.n_items < total ? g.n_items : total;
+    if (n == 0) return false;
+    bind_scene(w, I, kid, P, flags, dyn_lds);
+    memcpy(P.corner, g.corner, 12); memcpy(P.origin, g.origin, 12); memcpy(P.up, g.up, 12); memcpy(P.right, g.right, 12);
+    P.w_factor = g.w_factor; P.h_factor = g.h_factor; P.width = g.width; P.height = g.height;
+    P.id_offset = g.id_offset; P.n_items = n;
+    P.band_stride = g.band_stride; P.band_phase = g.band_phase;
+    P.tiled = ((g.id_offset % g.width == 0 || g.band_stride > 1) && n % g.width == 0) ? 1u : 0u;
+    P.rows = n / g.width;
+    P.row_offset = (uint32_t)(g.id_offset / g.width);
+    P.unit_dirs = P.ns <= GRID_MIN_SPHERES ? 1u : 0u;      /* as the fused trace launch: the rays are this library's own */
+    P.vis = 0;
+    return true;
+}
+
+void launch_gbuffer(Impl* I, const whitted_params& P, int flags, size_t dyn_lds, void* const chan[5], bool timed) {
+    unsigned grid;
+    if (P.tiled) grid = 8u * (((P.rows + 7u) / 8u + 7u) / 8u) * ((P.width + 7u) / 8u);      /* as trace_launch: tile rows dealt to the 8 XCDs */
+    else grid = (P.n_items + TRACE_BLOCK - 1) / TRACE_BLOCK;
+    LaunchTimer t(I, CLW_TIMING_GBUFFER, timed);
+    hipError_t e = (I->strict ? wt_strict_launch_gbuffer : wt_fast_launch_gbuffer)(&P, flags, grid, dyn_lds, (float*)chan[0], (unsigned*)chan[1], (float*)chan[2],
+                                                                                   (float*)chan[3], (float*)chan[4], I->stream);
+    if (e != hipSuccess) die("Couldn't run the kernel");
+    t.done();
+}
+
+/* index of a single CLW_GB_* bit, -1 for anything else */
+int gbuffer_channel(uint32_t channel) {
+    for (int c = 0; c < 5; c++) if (channel == (1u << c)) return c;
+    return -1;
+}
 
 } /* namespace */
 
@@ -1269,6 +1333,9 @@ void cl_wrap_release(cl_wrap* wrap) {
     if (I->d_cams) (void)hipFree(I->d_cams);
     if (I->d_motion) (void)hipFree(I->d_motion);
     if (I->acc.sum) (void)hipFree(I->acc.sum);
+    I->gb.free_channels();
+    if (I->gb.pick) (void)hipFree(I->gb.pick);
+    if (I->gb.done) (void)hipEventDestroy(I->gb.done);
     I->adapt.free_all();
     if (I->tables_fence) (void)hipEventDestroy(I->tables_fence);
     for (uint32_t* q : {I->d_grid_start, I->d_grid_items, I->d_grid_box}) if (q) (void)hipFree(q);
@@ -1499,6 +1566,90 @@ void clw_ext_set_accumulate(cl_wrap* wrap, int max_frames, int jitter) {
 }
 uint32_t clw_ext_get_accumulated(cl_wrap* wrap) { Impl* I = impl_of(wrap); return I->acc_max > 0 ? I->acc.K : 0u; }
 void clw_ext_reset_accumulation(cl_wrap* wrap) { impl_of(wrap)->acc.epoch++; }
+
+uint32_t clw_ext_render_gbuffer(cl_wrap* wrap, uint32_t channels) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    channels &= CLW_GB_ALL;
+    if (!channels) return 0;
+    whitted_params P{};
+    int flags = 0;
+    size_t dyn_lds = 0;
+    if (!gbuffer_params(wrap, I, P, flags, dyn_lds)) return 0;
+    Impl::GBuffer& B = I->gb;
+    if (B.n != P.n_items) {      /* another range: a pass under way may still write the old buffers */
+        if (B.n) { finish(I); if (B.done) (void)hipEventSynchronize(B.done); }
+        B.free_channels();
+        B.n = P.n_items;
+    }
+    void* chan[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int c = 0; c < 5; c++) {
+        if (!(channels & (1u << c))) continue;
+        if (!B.chan[c]) HIP_OK(hipMalloc(&B.chan[c], (size_t)B.n * GB_WORDS[c] * 4), "Couldn't allocate device memory");
+        chan[c] = B.chan[c];
+    }
+    launch_gbuffer(I, P, flags, dyn_lds, chan, true);
+    if (!B.done) HIP_OK(hipEventCreateWithFlags(&B.done, hipEventDisableTiming), "Couldn't create a timing event");
+    HIP_OK(hipEventRecord(B.done, I->stream), "Couldn't run the kernel");
+    B.written = channels;
+    return B.n;
+}
+
+uint32_t clw_ext_read_gbuffer(cl_wrap* wrap, uint32_t channel, void* out, uint32_t capacity_bytes) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    const Impl::GBuffer& B = I->gb;
+    const int c = gbuffer_channel(channel);
+    if (c < 0 || !(B.written & channel) || !B.chan[c]) return 0;
+    const uint64_t bytes = (uint64_t)B.n * GB_WORDS[c] * 4;
+    if (bytes > 0xFFFFFFFFull) return 0;
+    if (out && capacity_bytes >= bytes) {
+        hipError_t e = hipEventSynchronize(B.done);
+        if (e != hipSuccess) { printf("%d\n", (int)e); die("The device kernel failed"); }
+        HIP_OK(hipMemcpy(out, B.chan[c], (size_t)bytes, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
+    }
+    return (uint32_t)bytes;
+}
+
+void* clw_ext_gbuffer_device_ptr(cl_wrap* wrap, uint32_t channel) {
+    const Impl::GBuffer& B = impl_of(wrap)->gb;
+    const int c = gbuffer_channel(channel);
+    return (c < 0 || !(B.written & channel)) ? nullptr : B.chan[c];
+}
+
+int clw_ext_pick(cl_wrap* wrap, uint32_t x, uint32_t y, clw_pick* out) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    if (!out) return 0;
+    whitted_params P{};
+    int flags = 0;
+    size_t dyn_lds = 0;
+    if (!gbuffer_params(wrap, I, P, flags, dyn_lds)) return 0;
+    if (x >= P.width || y >= P.height) return 0;
+    /* is the pixel one of the wrapper's work-items? */
+    if (P.band_stride > 1u) {
+        const uint32_t band = y / 8u;
+        if (band % P.band_stride != P.band_phase) return 0;
+        const uint64_t item = (uint64_t)((band / P.band_stride) * 8u + y % 8u) * P.width + x;
+        if (item >= P.n_items) return 0;
+    } else {
+        const uint64_t id = (uint64_t)y * P.width + x;
+        if (id < P.id_offset || id - P.id_offset >= P.n_items) return 0;
+    }
+    /* the same kernel on the one-pixel range [id, id + 1): a linear range, whose work-item takes (id % W, id / W) = (x, y) */
+    P.id_offset = (uint64_t)y * P.width + x; P.n_items = 1;
+    P.band_stride = 1; P.band_phase = 0; P.tiled = 0; P.rows = 0; P.row_offset = y;
+    Impl::GBuffer& B = I->gb;
+    if (!B.pick) HIP_OK(hipMalloc((void**)&B.pick, sizeof(clw_pick)), "Couldn't allocate device memory");
+    static_assert(sizeof(clw_pick) == 44, "clw_pick is 11 words");
+    void* chan[5] = {B.pick + 1, B.pick + 0, B.pick + 5, B.pick + 2, B.pick + 8};      /* depth, id, normal, point, albedo as clw_pick lays them out */
+    launch_gbuffer(I, P, flags, dyn_lds, chan, false);
+    clw_pick h;
+    if (hipMemcpyAsync(&h, B.pick, sizeof h, hipMemcpyDeviceToHost, I->stream) != hipSuccess) die("Failed to transfer device memory to host");
+    finish(I);
+    *out = h;
+    return 1;
+}
 
 void clw_ext_set_pipeline(cl_wrap* wrap, int on) { impl_of(wrap)->pipeline = on ? 1 : 0; }
 void clw_ext_set_timing_every(cl_wrap* wrap, uint32_t n) { Impl* I = impl_of(wrap); I->timing_every = n ? n : 1; I->timing_tick = 0; I->timing_on = n != 0; }

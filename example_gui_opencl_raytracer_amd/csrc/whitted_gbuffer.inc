@@ -1,0 +1,224 @@
+/* whitted_gbuffer.inc -- the primary-hit pass: what the FIRST segment of every pixel of a launch range meets, written out as planar
+ * geometric buffers (hip_wrap_ext.h: clw_ext_render_gbuffer, clw_ext_pick).  Included by whitted_launch.inc behind whitted_trace.inc, so it
+ * exists in the fast and the strict unit and is built from the trace kernel's own pieces: the primary ray of wt_primary_dir(_xy) through the
+ * work-item mapping of wt_trace_body, the ray invariants of wt_rayq, the split sphere test (wt_sphere_pre / _disc / _root), wt_plane, the
+ * wave-uniform geometry fetch wt_geom over the scene staged by wt_stage_scene, the grid walks wt_grid_nearest / wt_grid_occluded.
+ * The search is the one of whitted_hit.inc -- findLightIntersection first, a visible light ending it (primitives.cl:262-318), then the nearest of
+ * spheres, then planes, ties keeping the earlier primitive (primitives.cl:322-394) -- in the same operations in the same order, so it takes the
+ * decisions the trace kernel of the build takes; what it adds is WHICH primitive or light won.  Nothing else runs: no shading, no shadow rays, no
+ * skybox fetch, no random numbers, no tile costs.
+ * WHICH primitive wins is decided by that search, in the build's own arithmetic: the pass names the object the trace launch of the same build
+ * shades.  WHERE it is hit -- depth, point, normal, a light's colour -- is then evaluated once more for the winner alone in the reference's
+ * arithmetic (wt_gb_ref_*: IEEE divide and square root, no fused operation), the same in both builds: D/4 = b b - c cancels near a silhouette
+ * and from afar, where the fast build's fused products move t by 1e-4 and more and a light's (1 / d) * d by an ulp, and a consumer of the buffers
+ * (a focus distance, a denoiser's normals) should not see which build made them.  In the strict build these are the search's own values.
+ * The pass sees the launch camera at pixel centres and the scene as it stands: no sample cameras, no sphere motion, no jitter, no seed. */
+
+/* id word of a pixel: kind << 30 | index (hip_wrap_ext.h: CLW_GB_ID) */
+#define WT_GB_KIND_PLANE (1u << 30)
+#define WT_GB_KIND_LIGHT (2u << 30)
+#define WT_GB_ID_NONE 0xFFFFFFFFu
+
+/* the channels a launch writes: planar, indexed by work-item like `out`; a NULL pointer = the channel was not asked for (wave-uniform) */
+struct wt_gbuffer_out {
+    float* depth;        /* 1 per work-item */
+    unsigned* id;        /* 1 */
+    float* normal;       /* 3 */
+    float* point;        /* 3 */
+    float* albedo;       /* 3 */
+};
+
+/* ---- the reference's arithmetic for ONE primitive (primitives.cl:170-215 as wt_sphere_* / wt_plane evaluate them in the strict build: b/2 and
+ *      D/4, see whitted_trace.inc), spelled out so that the fast unit computes the same bits: both units are compiled without contraction and
+ *      with correctly rounded divide and square root ---- */
+__device__ __forceinline__ float wt_gb_ref_dot(f3 a, f3 b) {
+#pragma clang fp contract(off)
+    return a.x * b.x + a.y * b.y + a.z * b.z;
+}
+__device__ __forceinline__ f3 wt_gb_ref_madd(f3 a, float s, f3 b) {      /* a * s + b */
+#pragma clang fp contract(off)
+    return mk3(a.x * s + b.x, a.y * s + b.y, a.z * s + b.z);
+}
+__device__ __forceinline__ f3 wt_gb_ref_normalize(f3 v) {
+#pragma clang fp contract(off)
+    const float len = sqrtf(wt_gb_ref_dot(v, v));
+    return mk3(v.x / len, v.y / len, v.z / len);
+}
+__device__ __forceinline__ bool wt_gb_ref_sphere(f3 o, f3 d, float4 s, float& t) {
+#pragma clang fp contract(off)
+    const float a = wt_gb_ref_dot(d, d);
+    const f3 v = o - mk3(s.x, s.y, s.z);
+    const float c = wt_gb_ref_dot(v, v) - fabsf(s.w);
+    const float b = wt_gb_ref_dot(v, d);
+    const float D = b * b + (-(a * c));
+    const float sD = sqrtf(D);
+    const float t0 = (-b - sD) / a;
+    t = (t0 < 0) ? (-b + sD) / a : t0;
+    return !(D < 0) && !(t <= 0);
+}
+__device__ __forceinline__ bool wt_gb_ref_plane(f3 o, f3 d, float4 n, float4 p0, float& t) {
+#pragma clang fp contract(off)
+    const float num = wt_gb_ref_dot(mk3(p0.x, p0.y, p0.z) - o, mk3(n.x, n.y, n.z));
+    const float b = wt_gb_ref_dot(d, mk3(n.x, n.y, n.z));
+    t = num / b;
+    return !(b == 0) && !(t <= 0);
+}
+
+__device__ __forceinline__ void wt_gb_store3(float* __restrict__ p, unsigned item, f3 v) {
+    if (p) { float* q = p + 3 * (size_t)item; q[0] = v.x; q[1] = v.y; q[2] = v.z; }
+}
+
+template <bool GEOM_LDS, bool GRID>
+__global__ void __launch_bounds__(WT_BLOCK) wt_gbuffer(const whitted_params P, const wt_gbuffer_out G) {
+    extern __shared__ float4 s_geom[];
+    if (GEOM_LDS) wt_stage_scene(P, s_geom, threadIdx.x, WT_BLOCK);
+    const float4* sg = s_geom;
+    const unsigned tid = threadIdx.x, lane = tid & 63u, wg = blockIdx.x;
+    constexpr bool UNIT_CT = !WT_STRICT && GEOM_LDS && !GRID;       /* as the fused trace launch: see whitted_hit.inc */
+
+    /* ---- work-item -> pixel: wt_trace_body's mapping in its default dispatch order (no tile order, no split tiles) ---- */
+    bool valid;
+    unsigned item, x = 0, y = 0;
+    if (P.tiled) {
+        const unsigned tpr = (P.width + 7u) >> 3;
+        const unsigned k = wg & 7u, j = wg >> 3;
+        const unsigned trow = (j / tpr) * 8u + k, tcol = j % tpr;
+        x = tcol * 8u + (lane & 7u);
+        y = trow * 8u + (lane >> 3);
+        valid = (x < P.width) && (y < P.rows);
+        item = y * P.width + x;
+    } else {
+        item = wg * WT_BLOCK + tid;
+        valid = item < P.n_items;
+        if (P.band_stride > 1u) { y = item / P.width; x = item % P.width; }
+    }
+    unsigned long long gid = P.id_offset + item;
+    unsigned gy = y;
+    if (P.band_stride > 1u) {
+        gy = ((y >> 3) * P.band_stride + P.band_phase) * 8u + (y & 7u);
+        gid = (unsigned long long)gy * P.width + x;
+    } else if (P.tiled) {
+        gy = P.row_offset + y;
+    }
+    if (!valid) return;      /* (behind the staging barrier; every ballot below is an early-out over per-lane predicates) */
+
+    f3 d;
+    if (P.tiled || P.band_stride > 1u) d = wt_primary_dir_xy(P.corner, P.right, P.up, P.w_factor, P.h_factor, x, gy);
+    else d = wt_primary_dir(P.corner, P.right, P.up, P.w_factor, P.h_factor, (unsigned)gid, P.width);
+    const f3 o = mk3(P.origin[0], P.origin[1], P.origin[2]);
+    const rayq r = UNIT_CT ? wt_rayq<true>(o, d) : wt_rayq<false>(o, d, P.unit_dirs != 0u);
+    const unsigned g_pln = P.ns, g_lgt = P.ns + 2 * P.np;
+
+    /* ---- findLightIntersection (primitives.cl:262-318): the nearest light sphere in index order, then is anything in front of it ---- */
+    bool lit = false;
+    float tl = INFINITY;
+    unsigned li = 0u;
+    for (unsigned i = 0; i < P.nl; i++) {
+        const float4 l0 = wt_geom<GEOM_LDS>(P, sg, g_lgt + 2 * i);
+        const sph_pre pre = wt_sphere_pre(r.o, l0);
+        float bq, Dq;
+        const bool ok = wt_sphere_disc(pre, r.d, r.a4, bq, Dq);
+        if (__builtin_amdgcn_ballot_w64(ok)) {              /* rare: a light sphere is on somebody's line */
+            float t;
+            const bool hit = wt_sphere_root(bq, Dq, r.a2, t) && ok;
+            if (hit && !(t >= tl)) { tl = t; li = i; lit = true; }
+        }
+    }
+    if (__builtin_amdgcn_ballot_w64(lit)) {
+        if (lit) {
+            if (GRID) {
+                if (wt_grid_occluded(P, r, tl)) lit = false;
+            }
+            for (unsigned i = 0; !GRID && i < P.ns; i++) {
+                const float4 s = wt_geom<GEOM_LDS>(P, sg, i);
+                float t;
+                const bool hit = wt_sphere(r, s, t);
+                if (hit && t <= tl && !(__float_as_uint(s.w) >> 31)) lit = false;
+            }
+            for (unsigned i = 0; i < P.np; i++) {
+                const float4 n = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * i);
+                const float4 p0 = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * i + 1);
+                float t;
+                const bool hit = wt_plane(r, n, p0, t);
+                if (hit && t <= tl) lit = false;
+            }
+        }
+    }
+
+    float depth = INFINITY;
+    unsigned id = WT_GB_ID_NONE;
+    f3 nrm = mk3(0, 0, 0), ip = mk3(0, 0, 0), alb = mk3(0, 0, 0);
+    if (lit) {
+        /* the light that was seen, in the reference's arithmetic (a test that does not confirm the hit keeps the search's t) */
+        const float4 l0 = wt_geom<GEOM_LDS>(P, sg, g_lgt + 2 * li);
+        const float4 l1 = wt_geom<GEOM_LDS>(P, sg, g_lgt + 2 * li + 1);
+        float tr;
+        if (wt_gb_ref_sphere(o, d, l0, tr)) tl = tr;
+        const f3 hp = wt_gb_ref_madd(d, tl, o);
+        const float dist = sqrtf(wt_gb_ref_dot(o - hp, o - hp));
+        depth = tl; id = WT_GB_KIND_LIGHT | li;
+        alb = mk3(l1.x, l1.y, l1.z) * (1 / dist * dist);      /* "(1/d*d)" = (1/d)*d, not inverse-square: kept (primitives.cl:287) */
+    } else {
+        /* ---- findSolidIntersection (primitives.cl:322-394): nearest wins, the strict `_t >= t` keeps the earlier primitive on ties ---- */
+        float tbest = INFINITY;
+        int best = -1;
+        if (GRID) {
+            best = wt_grid_nearest(P, r, tbest);
+        } else {
+            for (unsigned i = 0; i < P.ns; i++) {
+                const float4 s = wt_geom<GEOM_LDS>(P, sg, i);
+                const sph_pre pre = wt_sphere_pre(r.o, s);
+                float bq, Dq;
+                const bool ok = wt_sphere_disc(pre, r.d, r.a4, bq, Dq);
+                if (__builtin_amdgcn_ballot_w64(ok) == 0) continue;       /* nobody's line meets this one */
+                float t;
+                const bool hit = wt_sphere_root(bq, Dq, r.a2, t) && ok;
+                if (hit && !(t >= tbest)) { tbest = t; best = (int)i; }
+            }
+        }
+        for (unsigned i = 0; i < P.np; i++) {
+            const float4 n = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * i);
+            const float4 p0 = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * i + 1);
+            float t;
+            const bool hit = wt_plane(r, n, p0, t);
+            if (hit && !(t >= tbest)) { tbest = t; best = (int)(P.ns + i); }
+        }
+        if (best >= 0) {
+            /* the winner, in the reference's arithmetic (a test that does not confirm the hit keeps the search's t) */
+            const unsigned prim = (unsigned)best;
+            bool textured = false;
+            unsigned texpx = 0u;
+            float tr;
+            if (prim < P.ns) {
+                const float4 s = wt_geom<GEOM_LDS>(P, sg, prim);
+                if (wt_gb_ref_sphere(o, d, s, tr)) tbest = tr;
+                ip = wt_gb_ref_madd(d, tbest, o);
+                nrm = wt_gb_ref_normalize(ip - mk3(s.x, s.y, s.z));
+                id = prim;
+            } else {
+                const unsigned pi = prim - P.ns;
+                const float4 n = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * pi);
+                const float4 p0 = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * pi + 1);
+                if (wt_gb_ref_plane(o, d, n, p0, tr)) tbest = tr;
+                ip = wt_gb_ref_madd(d, tbest, o);
+                nrm = mk3(n.x, n.y, n.z);                    /* never flipped toward the ray */
+                id = WT_GB_KIND_PLANE | pi;
+                if (n.w != 0.0f && G.albedo) {               /* texture_id >= 0: the texel of the pre-offset point (primitives.cl:377) */
+                    texpx = wt_plane_texel_fetch(P, pi, ip);
+                    textured = true;
+                }
+            }
+            if (G.albedo) {
+                const float4 a_ = wt_mat_f4(P, prim, 0u, P.ns);
+                alb = textured ? wt_texel_rgb(texpx) : mk3(a_.x, a_.y, a_.z);
+            }
+            depth = tbest;
+            ip = wt_gb_ref_madd(nrm, WT_EPSILON, ip);        /* the point shading uses */
+        }
+    }
+    if (G.depth) G.depth[item] = depth;
+    if (G.id) G.id[item] = id;
+    wt_gb_store3(G.normal, item, nrm);
+    wt_gb_store3(G.point, item, ip);
+    wt_gb_store3(G.albedo, item, alb);
+}

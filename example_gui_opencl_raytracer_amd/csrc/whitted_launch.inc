@@ -1,7 +1,8 @@
-/* whitted_launch.inc -- instantiates the kernels of whitted_trace.inc in namespace WT_NS
- * and exports the two C launchers the shim calls. */
+/* whitted_launch.inc -- instantiates the kernels of whitted_trace.inc (and the primary-hit pass of whitted_gbuffer.inc, built from its
+ * pieces) in namespace WT_NS and exports the C launchers the shim calls. */
 namespace WT_NS {
 #include "whitted_trace.inc"
+#include "whitted_gbuffer.inc"
 }
 
 template <int FLAGS>
@@ -106,5 +107,22 @@ extern "C" hipError_t WT_LAUNCH_UNIT_SCENE(const whitted_params* P, int flags, i
     if (flags & 16) hipLaunchKernelGGL((WT_NS::wt_unit_scene<false, true>), grid, block, 0, s, *P, op, in, out, n, stride_in, stride_out);
     else if (flags & 4) hipLaunchKernelGGL((WT_NS::wt_unit_scene<true, false>), grid, block, dyn_lds, s, *P, op, in, out, n, stride_in, stride_out);
     else hipLaunchKernelGGL((WT_NS::wt_unit_scene<false, false>), grid, block, 0, s, *P, op, in, out, n, stride_in, stride_out);
+    return hipGetLastError();
+}
+
+/* the primary-hit pass (whitted_gbuffer.inc): geometry as bind_scene chose it -- flags & 16 the uniform grid, & 4 the scene staged in LDS, else
+ * read from global memory; the five channel pointers in CLW_GB_* bit order, NULL = not written */
+#if WT_STRICT
+#define WT_LAUNCH_GBUFFER wt_strict_launch_gbuffer
+#else
+#define WT_LAUNCH_GBUFFER wt_fast_launch_gbuffer
+#endif
+extern "C" hipError_t WT_LAUNCH_GBUFFER(const whitted_params* P, int flags, unsigned grid, size_t dyn_lds, float* depth, unsigned* id,
+                                        float* normal, float* point, float* albedo, hipStream_t s) {
+    const WT_NS::wt_gbuffer_out G = {depth, id, normal, point, albedo};
+    const dim3 g(grid), block(WT_BLOCK);
+    if (flags & 16) hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, true>), g, block, 0, s, *P, G);
+    else if (flags & 4) hipLaunchKernelGGL((WT_NS::wt_gbuffer<true, false>), g, block, dyn_lds, s, *P, G);
+    else hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, false>), g, block, 0, s, *P, G);
     return hipGetLastError();
 }

@@ -31,6 +31,10 @@ changes, every ``render()`` traces the view once more with its own random number
 running mean of the frames so far, until N frames are in; then it returns that mean without tracing (clw_ext_set_accumulate).  ``accumulated``
 tells how many frames the mean holds, ``reset_accumulation()`` starts again.  ``seed_offset=s`` shifts the random seed of every pixel
 (clw_ext_set_seed_offset).  ``render_rgb()`` returns the mean (clamped to [0, 1]) while the mode is on.
+
+``gbuffer()`` / ``pick(x, y)``: the primary-hit pass (clw_ext_render_gbuffer, clw_ext_pick) -- depth, object id, normal, hit point and albedo of
+what the launch camera sees first at every pixel of this renderer's rows, or at one pixel of the frame.  No sampling mode above changes them,
+and they leave an accumulating view counting.
 """
 from __future__ import annotations
 
@@ -118,6 +122,7 @@ class Renderer:
         else:
             w.load_global_data(1, 10, None, 4 * self.pixels, api.CL_MEM_WRITE_ONLY)
         self._rgb_dev = None
+        self._camera_set = False
 
     # ---- camera: the six values of rgen_perspective, re-settable at any time (rayinteractive.c:98-103)
     def set_camera(self, cam) -> None:
@@ -129,6 +134,7 @@ class Renderer:
         w.load_single_data(0, 3, f3(cam.right))
         w.load_single_data(0, 4, np.float32(cam.w_factor))
         w.load_single_data(0, 5, np.float32(cam.h_factor))
+        self._camera_set = True
 
     def set_sample_cameras(self, cams) -> None:
         """float32 [n*n, 12]: sample k = sy * n + sx of every pixel looks through camera k (None = the launch camera); replaces a lens."""
@@ -178,6 +184,27 @@ class Renderer:
 
     def reset_accumulation(self) -> None:
         self.w.reset_accumulation()
+
+    # ---- the primary-hit pass
+    def gbuffer(self, channels: int = api.GB_ALL) -> dict:
+        """{"depth": [n], "id": [n], "normal": [n, 3], "point": [n, 3], "albedo": [n, 3]} of the requested channels (api.GB_*) for the n work-items
+        of this renderer, through the camera set last.  The raygen launch latches it (in fused mode it does nothing else)."""
+        if self._camera_set:
+            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        if self.w.render_gbuffer(channels) != self.pixels:
+            raise RuntimeError("the primary-hit pass did not cover this renderer's range (is a camera set, is `channels` a mask of api.GB_*?)")
+        return {name: self.w.read_gbuffer(bit) for name, (bit, _, _) in api.GB_CHANNELS.items() if channels & bit}
+
+    def pick(self, x: int, y: int) -> dict | None:
+        """What lies under pixel (x, y) of the frame: {"id", "kind", "index", "depth", "point", "normal", "albedo"} -- the entries of that pixel in
+        ``gbuffer()``, bit for bit -- or None when the pixel is not one of this renderer's rows (or no camera has been set)."""
+        if self._camera_set:
+            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        p = self.w.pick(x, y)
+        if p is None:
+            return None
+        return dict(id=int(p.id), kind=int(p.id) >> 30, index=int(p.id) & 0x3FFFFFFF, depth=np.float32(p.depth), point=np.array(p.point[:], np.float32),
+                    normal=np.array(p.normal[:], np.float32), albedo=np.array(p.albedo[:], np.float32))
 
     def read_rays(self) -> np.ndarray:
         """The 64-B rray records of buffers[0][8] (materialised on demand in fused mode)."""

@@ -231,6 +231,54 @@ uint32_t clw_ext_get_accumulated(cl_wrap* wrap);
 /* The next trace launch starts the sum again at frame 0. */
 void     clw_ext_reset_accumulation(cl_wrap* wrap);
 
+/* The primary-hit pass: the geometric buffers of the view, and which object lies under a pixel.  One launch of its own kernel (wt_gbuffer,
+ * csrc/whitted_gbuffer.inc, in both arithmetic builds) generates the primary ray of every work-item exactly as the 1-sample trace launch does --
+ * the camera and range latched by the last raygen launch, clipped by the raytracer's `pixels` argument (its argument 7), id offset and row bands
+ * included -- and runs the first segment's two searches with the trace kernel's own arithmetic: findLightIntersection first, a visible light
+ * ending the search (reference primitives.cl:262-318), then the nearest of the spheres, then of the planes, ties keeping the earlier primitive
+ * (primitives.cl:322-394); the scene is read as the trace launch reads it (staged in LDS, from global memory, or through the uniform grid).
+ * WHICH object wins is decided in the arithmetic of the build in use, so the pass names the object that build's trace launch shades; the winner's
+ * depth, point and normal and a light's colour are then evaluated for that one primitive in the reference's arithmetic (IEEE divide and square
+ * root, no fused operation) in BOTH builds: the fast build's buffers are the strict build's bit for bit wherever the two agree on the winner.
+ * Nothing is shaded: no shadow rays, no skybox fetch, no random numbers.  The pass always sees the LAUNCH camera at pixel centres and the scene
+ * as it stands: supersampling factor, lens, sample cameras, moving spheres, adaptive mode, accumulation (its jitter included) and the seed offset
+ * have no effect on it, and it does not restart an accumulating view.
+ * The channels are planar device buffers owned by the wrapper, indexed by work-item like the framebuffer, one per bit of `channels`:
+ *   bit              type     a sphere / plane is hit                                        a light is seen                    miss
+ *   CLW_GB_DEPTH     f32      the winning t along the unit primary direction                 the light's t                      +inf
+ *   CLW_GB_ID        u32      kind << 30 | index: kind 0 = sphere, 1 = plane; the index is   2 << 30 | index of the light       CLW_ID_NONE
+ *                             the one of the caller's array
+ *   CLW_GB_NORMAL    f32[3]   the normal findSolidIntersection returns (a plane's is never   0                                  0
+ *                             flipped toward the ray)
+ *   CLW_GB_POINT     f32[3]   the hit point shading uses: moved by EPSILON along the normal  0                                  0
+ *   CLW_GB_ALBEDO    f32[3]   the winner's material colour; a textured plane's texel         the colour findLightIntersection   0
+ *                                                                                            returns
+ * clw_ext_render_gbuffer launches the pass, without waiting for it, on the wrapper's stream and returns the number of work-items; 0 -- and no
+ * launch, no error -- when no raygen launch has latched a camera yet, the raytracer's scene arguments are not all set, or `channels` holds no
+ * known bit.  Buffers are allocated when a channel is first asked for and again when the range changes; cl_wrap_release frees them. */
+#define CLW_GB_DEPTH  1u
+#define CLW_GB_ID     2u
+#define CLW_GB_NORMAL 4u
+#define CLW_GB_POINT  8u
+#define CLW_GB_ALBEDO 16u
+#define CLW_GB_ALL    31u
+#define CLW_ID_NONE   0xFFFFFFFFu
+uint32_t clw_ext_render_gbuffer(cl_wrap* wrap, uint32_t channels);
+/* One channel (a single CLW_GB_* bit) of the last pass -> its size in bytes, 4 or 12 per work-item; waits for the pass and copies it if `out` is
+ * not NULL and `capacity_bytes` suffices.  0 for a channel the last pass did not write. */
+uint32_t clw_ext_read_gbuffer(cl_wrap* wrap, uint32_t channel, void* out, uint32_t capacity_bytes);
+/* The device buffer of one channel of the last pass, for consumers on the device (in the order of the wrapper's stream); NULL for a channel
+ * the last pass did not write.  The next pass over another range frees it. */
+void*    clw_ext_gbuffer_device_ptr(cl_wrap* wrap, uint32_t channel);
+/* What lies under pixel (x, y) of the FRAME: one launch of the same kernel on that one-pixel range -- the pass's arithmetic, so the values are
+ * the entry of that pixel in the buffers bit for bit -- and a 44-byte read-back; the call waits for it.  Returns 1, or 0 with `out` untouched
+ * when no camera is latched (see above) or the pixel is not one of the wrapper's work-items (outside the frame, outside its id range or its row
+ * bands).  The buffers of the last pass stay as they are. */
+typedef struct clw_pick { uint32_t id; float depth, point[3], normal[3], albedo[3]; } clw_pick;   /* 44 bytes */
+int      clw_ext_pick(cl_wrap* wrap, uint32_t x, uint32_t y, clw_pick* out);
+/* The pass's launches are logged under this id in clw_ext_timing_get (a pick is not logged). */
+#define CLW_TIMING_GBUFFER 0x47425546u
+
 /* Work counters of the trace kernel.  enable=1 selects the counting build of the kernel
  * for subsequent launches (slower); read returns and clears
  *   out[0] path segments  out[1] shadow rays  out[2] light probes  out[3] skybox fetches

@@ -1,0 +1,126 @@
+"""Shared by test_gbuffer_host.py and test_gpu_gbuffer.py: what the primary-hit pass (include/hip_wrap_ext.h, clw_ext_render_gbuffer) must
+write, built from the oracle's own functions alone, and the cases both files run.
+
+For every pixel id of wo_raygen:
+  * wo_find_light hits: the id is the light that wins wo_intersect_sphere over the lights in index order under the strict tie rule
+    `not (t >= best)`, depth its t, albedo the colour wo_find_light returns, normal and point 0;
+  * otherwise the winner is the nearest over wo_intersect_sphere on the spheres, then wo_intersect_plane on the planes, under the same rule;
+    wo_find_solid gives the point (offset by EPSILON along the normal), the normal and the colour (a textured plane's texel);
+  * no winner: depth +inf, id ID_NONE, the rest 0.
+The expected buffers of a case are computed once per session (`expected_case`) and never written to."""
+import ctypes as C
+
+import numpy as np
+
+from conftest import CAM
+
+F32 = np.float32
+ID_NONE = 0xFFFFFFFF
+KIND_SPHERE, KIND_PLANE, KIND_LIGHT = 0, 1, 2
+W, H = 70, 37            # cases A, B, C: neither a multiple of 8 -- partial tiles at both edges
+WD, HD = 40, 24          # cases D, E
+CAM_HIGH = dict(origin=(0.0, 6.0, -2.0), look=(0.1, -0.3, 1.0), fov=90.0, focal=1.0)
+
+
+def _scene(name):
+    from example_gui_opencl_raytracer_amd import scene
+    if name == "demo":
+        return scene.render_map_scene()
+    if name == "grid324":
+        return scene.sphere_grid_scene(18, 18)      # above the 256-sphere staging limit: the uniform grid (or, with set_grid(0), the global scan)
+    if name == "glass16":
+        return scene.dielectric_field_scene(4)
+    raise KeyError(name)
+
+
+def _light_cam(k):
+    o = _scene("demo").lights[k]["origin"]
+    return dict(origin=(float(o[0]) - 0.1, float(o[1]) - 0.05, float(o[2]) - 0.5), look=(0.0, 0.0, 1.0), fov=90.0, focal=1.0)
+
+
+# name -> (scene, width, height, camera, {pixel kind: fewest pixels of it the case must hold})
+CASES = {
+    "A": ("demo", W, H, CAM, {KIND_SPHERE: 100, KIND_PLANE: 2000, KIND_LIGHT: 1}),
+    "B": ("demo", W, H, dict(origin=(0.8, 2.5, -8.0), look=(-0.6, 0.5, 0.6), fov=90.0, focal=1.0), {"miss": 50, KIND_PLANE: 2000}),
+    "C0": ("demo", W, H, _light_cam(0), {KIND_LIGHT: 100}),
+    "C1": ("demo", W, H, _light_cam(1), {KIND_LIGHT: 100}),
+    "C2": ("demo", W, H, _light_cam(2), {KIND_LIGHT: 100}),
+    "D0": ("grid324", WD, HD, CAM, {"distinct": 90}),
+    "D1": ("grid324", WD, HD, CAM_HIGH, {"distinct": 160}),
+    "E": ("glass16", WD, HD, CAM_HIGH, {KIND_SPHERE: 1, KIND_PLANE: 1}),
+}
+_scenes, _expected = {}, {}
+
+
+def case_scene(name):
+    key = CASES[name][0]
+    if key not in _scenes:
+        _scenes[key] = _scene(key)
+    return _scenes[key]
+
+
+def make_id(kind, index):
+    return (int(kind) << 30) | int(index)
+
+
+def expected_gbuffer(oracle, scene, tex, sky, cam):
+    """cam: an oracle Camera -> dict of depth [n] f32, id [n] u32, normal / point / albedo [n, 3] f32, and `solid` [n] bool: wo_find_solid's own
+    hit flag on the pixels where no light is seen (False where one is)."""
+    from oracle.oracle_py import _Inputs
+    L = oracle.lib
+    inp = _Inputs(scene, tex, sky)
+    sc = C.byref(inp.c)
+    rays = oracle.raygen(cam)
+    n = len(rays)
+    out = dict(depth=np.full(n, np.inf, F32), id=np.full(n, ID_NONE, np.uint32), normal=np.zeros((n, 3), F32), point=np.zeros((n, 3), F32),
+               albedo=np.zeros((n, 3), F32), solid=np.zeros(n, bool))
+    f3 = C.c_float * 3
+    spheres = [(f3(*s["origin"]), C.c_float(s["radius"])) for s in scene.spheres]
+    planes = [(f3(*p["normal"]), f3(*p["point_in_plane"])) for p in scene.planes]
+    lights = [(f3(*l["origin"]), C.c_float(l["radius"])) for l in scene.lights]
+    t = C.c_float()
+    tp = C.byref(t)
+    col, pt, nr = f3(), f3(), f3()
+    mat = (C.c_float * 16)()
+    inf = float("inf")
+    for i in range(n):
+        o, d = f3(*rays[i, 0:3]), f3(*rays[i, 4:7])
+        if L.wo_find_light(o, d, sc, col):
+            best, win = inf, -1
+            for k, (c, r) in enumerate(lights):
+                if L.wo_intersect_sphere(o, d, c, r, tp) and not (t.value >= best):
+                    best, win = t.value, k
+            assert win >= 0
+            out["depth"][i], out["id"][i], out["albedo"][i] = best, make_id(KIND_LIGHT, win), col[:]
+            continue
+        best, win = inf, -1
+        for k, (c, r) in enumerate(spheres):
+            if L.wo_intersect_sphere(o, d, c, r, tp) and not (t.value >= best):
+                best, win = t.value, make_id(KIND_SPHERE, k)
+        for k, (nn, p0) in enumerate(planes):
+            if L.wo_intersect_plane(o, d, nn, p0, tp) and not (t.value >= best):
+                best, win = t.value, make_id(KIND_PLANE, k)
+        out["solid"][i] = bool(L.wo_find_solid(o, d, sc, pt, nr, mat))
+        if win >= 0 and out["solid"][i]:
+            out["depth"][i], out["id"][i] = best, win
+            out["point"][i], out["normal"][i], out["albedo"][i] = pt[:], nr[:], mat[0:3]
+        elif win >= 0:
+            out["id"][i] = win          # (an inconsistency the host test reports: the search found a winner, wo_find_solid none)
+    for v in out.values():
+        v.setflags(write=False)
+    return out
+
+
+def expected_case(oracle, name, tex, sky):
+    if name not in _expected:
+        key, w, h, cam, _ = CASES[name]
+        _expected[name] = expected_gbuffer(oracle, case_scene(name), tex, sky, oracle.camera(cam["origin"], cam["look"], cam["fov"], cam["focal"], w, h))
+    return _expected[name]
+
+
+def kind_of(ids):
+    return np.asarray(ids, np.uint32) >> np.uint32(30)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, F32).view(np.uint32)
