@@ -1,7 +1,7 @@
 """Build the native pieces in-tree (no JIT cache: the .so travels with the repo snapshot).
 
   libopencl_wrap_hip.so  = hip_wrap.cpp (C-ABI shim) + whitted_fast.hip + whitted_strict.hip
-                           (gfx950 kernels) + scene_prep.c + png_codec.c
+                           (gfx950 kernels) + launch_plan.c (the launch planner) + scene_prep.c + host_camera.c + png_codec.c
 Usage: python -m example_gui_opencl_raytracer_amd.build [--force]
 """
 from __future__ import annotations
@@ -31,8 +31,10 @@ UNITS = [
     ("whitted_fast.hip", "hip", ["-O3", f"--offload-arch={ARCH}", "-fno-slp-vectorize", "-ffp-contract=off"], DEVICE_DEPS),
     ("whitted_strict.hip", "hip", ["-O3", f"--offload-arch={ARCH}", "-fno-slp-vectorize", "-ffp-contract=off"], DEVICE_DEPS),
     ("hip_wrap.cpp", "hip", ["-O2", "-std=c++17", "-Wall"],
-     ["whitted_params.h", "scene_prep.h", "png_codec.h", "../../include/opencl_wrap.h", "../../include/hip_wrap_ext.h"]),
+     ["whitted_params.h", "launch_plan.h", "scene_prep.h", "png_codec.h", "../../include/opencl_wrap.h", "../../include/hip_wrap_ext.h"]),
     ("scene_prep.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra"], ["scene_prep.h"]),
+    ("launch_plan.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra"],
+     ["launch_plan.h", "whitted_params.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
     ("host_camera.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra", "-D_DEFAULT_SOURCE"],
      ["../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
     ("png_codec.c", "c", ["-O2", "-std=c99", "-D_DEFAULT_SOURCE", "-pthread", "-Wall", "-Wextra"], ["png_codec.h"]),

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/hip_wrap_ext.h"
+#include "launch_plan.h"
 #include "png_codec.h"
 #include "scene_prep.h"
 #include "whitted_params.h"
@@ -44,31 +45,7 @@ extern "C" hipError_t wt_fast_launch_sched(const unsigned*, unsigned*, unsigned,
 
 namespace {
 
-enum { F_COUNT = 1, F_DEEP = 2, F_GEOM_LDS = 4, F_RAYS = 8, F_GRID = 16, F_OCC = 32, F_D8 = 64, F_D16 = 128, F_SHAPE = 256, F_SS = 1 << 17, F_MOVE = 1 << 18, F_LIST = 1 << 19, F_ACC = 1 << 20 }; /* = WT_F_* of whitted_trace.inc */
-/* shallow fast launches of small LDS-geometry scenes run a kernel with the scene's counts compiled in (wt_shape of whitted_trace.inc): the
- * counts whitted_launch.inc instantiates -- 1..SHAPE_MAX_SPHERES spheres, 0..SHAPE_MAX_PLANES planes, SHAPE_LIGHTS lights */
-constexpr uint32_t SHAPE_MAX_SPHERES = 4, SHAPE_MAX_PLANES = 2, SHAPE_LIGHTS = 3;
-/* deep launches of at least OCC_TILES_PER_DEPTH x depth wavefronts take the high-occupancy flavour: the serial tail of
- * the deepest refraction trees grows with the depth, the throughput part with the tile count (tools/occ_sweep.py on
- * render.map: wins 12-14 % at 2560x1440 depth 6 and 3840x2160 depth 6-8, loses 2-5 % at 1920x1080 and at depth 15) */
-constexpr unsigned OCC_TILES_PER_DEPTH = 9000;
-/* tree-parallel tail (whitted_tpt.inc): a deep launch enters it with at most TPT_MAX_LANES live lanes holding at least TPT_MIN_PATHS
- * pending paths; the pool holds TPT_SLOTS_PER_XCC slots per XCD (more than an XCD's CUs hold wavefronts) of at most TPT_SLICE_WORDS_MAX
- * words, TPT_POOL_MB in all (below TPT_MIN_CAP nodes per slot -- hundreds of lights -- the launch runs without the tail) */
-constexpr unsigned TPT_MAX_LANES = 40, TPT_MIN_PATHS = 4, TPT_POOL_MB = 8192, TPT_MIN_CAP = 160, TPT_SLOTS_PER_XCC = 1024;
-constexpr uint64_t TPT_SLICE_WORDS_MAX = 1u << 18;
-/* heavy tiles of such a launch are served by up to 16 wavefronts each (wt_sched_build): up to SPLIT_EXTRA_PER_SHARE more dispatch entries
- * per XCD share; a tile is split while its parts stay above SPLIT_MIN_QUOTA cost units (a part enters the tail at once and pays its
- * fixed costs: 800x600 depth 15 0.267 ms at 3 000, 0.208 at 750-1 500); the quota is the share's total cost over SPLIT_SLOTS wavefronts (384 / 512 / 640: 1920x1080 depth 15 0.370 / 0.332 / 0.322 ms, glass field 2048^2 depth 8 3.19 / 2.95 / 3.33) */
-constexpr unsigned SPLIT_EXTRA_PER_SHARE = 1024, SPLIT_MIN_QUOTA = 1500, SPLIT_SLOTS = 512;
 constexpr size_t COUNTER_WORDS = CLW_NUM_COUNTERS + 16 * (size_t)CLW_STAMP_SHARDS;
-constexpr unsigned BLOCK = 256;       /* the reference's launch rounding unit: CL_KERNEL_WORK_GROUP_SIZE on AMD (opencl_wrap.c:359-374) */
-constexpr unsigned TRACE_BLOCK = 64;  /* = WT_BLOCK: one wavefront per workgroup */
-constexpr size_t GEOM_LDS_MAX_F4 = 1024; /* <= 16 KiB of prepared geometry is staged in LDS */
-constexpr uint32_t VIS_MAX_SPHERES = 16; /* = WT_VIS_MAX_SPHERES of whitted_trace.inc */
-constexpr int SHALLOW_LEVELS = 3;   /* DFS levels the shallow builds provide (LDS + scratch): depth <= SHALLOW_LEVELS + 1 */
-constexpr uint32_t GRID_MIN_SPHERES = 256;   /* scenes beyond the reference's one-byte counts get the uniform grid (at 64 spheres it only
-                                                wins when the cells happen to align with the spheres: 9.2-15 ms vs 10.9 ms linear) */
 constexpr size_t GRID_MAX_PAIRS = (size_t)1 << 25;   /* 20 B per cell-list entry */
 
 [[noreturn]] void die(const char* fmt, ...) {
@@ -83,8 +60,8 @@ constexpr size_t GRID_MAX_PAIRS = (size_t)1 << 25;   /* 20 B per cell-list entry
 }
 
 /* the same floats bit for bit (+0 and -0 differ, a NaN equals itself): "the device table is unchanged" is decided on what it holds */
-bool same_bits(const std::vector<float>& a, const std::vector<float>& b) {
-    return a.size() == b.size() && (a.empty() || !memcmp(a.data(), b.data(), a.size() * sizeof(float)));
+bool same_bits(const std::vector<float>& a, const float* b, size_t n) {
+    return a.size() == n && (n == 0 || !memcmp(a.data(), b, n * sizeof(float)));
 }
 
 #define HIP_OK(call, what)                                                        \
@@ -95,14 +72,7 @@ bool same_bits(const std::vector<float>& a, const std::vector<float>& b) {
 
 enum KernelKind { K_RAYGEN = 0, K_RAYTRACER = 1 };
 
-struct RaygenArgs { /* snapshot of the eight by-value raygen arguments + the launch range */
-    float corner[3], origin[3], up[3], right[3];
-    float w_factor, h_factor;
-    uint32_t width, height;
-    uint64_t id_offset;
-    uint32_t n_items;
-    uint32_t band_stride, band_phase;
-};
+typedef wt_raygen RaygenArgs;   /* snapshot of the eight by-value raygen arguments + the launch range (launch_plan.h) */
 /* field by field (the struct has tail padding, which a memcmp would also compare); floats by bit pattern */
 bool same_raygen(const RaygenArgs& a, const RaygenArgs& b) {
     return !memcmp(a.corner, b.corner, 12) && !memcmp(a.origin, b.origin, 12) && !memcmp(a.up, b.up, 12) &&
@@ -248,16 +218,17 @@ struct Impl {
     struct Sched {
         unsigned* cost[2] = {nullptr, nullptr}; unsigned* order[2] = {nullptr, nullptr};
         hipEvent_t built[2] = {nullptr, nullptr};    /* order[i] complete (recorded on the sched stream) */
-        bool have[2] = {false, false};                /* order[i] holds / will hold a schedule */
-        int wr = 0;                                   /* cost buffer the next trace writes */
+        wt_order_state o{};                           /* which order holds a schedule, which cost buffer the next trace writes, what the newest order was
+                                                         built for and how long ago: plain words, stepped by wt_order_* (launch_plan.c) */
         hipEvent_t traced = nullptr;
         uint32_t w = 0, rows = 0, cap = 0;           /* frame the buffers were sized for (the virtual frame of a supersampled launch); dispatch entries per XCD share */
         int ss = 1;                                   /* supersampling factor its orders were built for: it caps how far a tile is split */
         int last_rd = -1;                             /* order[] the last tiled launch read; -1 = it ran in the default order (clw_ext_read_tile_order) */
-        wt_cam_table sig_cams{}; bool sig_has_cams = false;   /* the sample cameras belong to the signature below */
-        std::vector<float> sig_motion;                        /* ... and so do the moving spheres' device table (empty = none) */
-        RaygenArgs sig{}; int sig_depth = 0; uint64_t sig_scene = 0; bool sig_valid = false; int sig_age = 0, newest = 0; uint64_t frame = 0, newest_frame = 0;   /* what the newest order was built for, frames since */
-        void reset() { have[0] = have[1] = false; sig_valid = false; newest = 0; last_rd = -1; }
+        /* the signature the newest order was built for: camera, depth, scene, and the sample cameras and moving spheres' device tables (empty = none) */
+        RaygenArgs sig{}; int sig_depth = 0; uint64_t sig_scene = 0;
+        wt_cam_table sig_cams{}; bool sig_has_cams = false;
+        std::vector<float> sig_motion;
+        void reset() { o.have[0] = o.have[1] = 0; o.sig_valid = 0; o.newest = 0; last_rd = -1; }
         void free_all() {
             for (int i = 0; i < 2; i++) {
                 if (cost[i]) (void)hipFree(cost[i]);
@@ -279,14 +250,14 @@ struct Impl {
     hipEvent_t chunk_done[MAX_CHUNKS] = {nullptr, nullptr, nullptr, nullptr};
     /* timing log */
     std::vector<TimingEntry> timing;
-    unsigned occ_tiles_per_depth = OCC_TILES_PER_DEPTH;   /* CLWRAP_OCC_TILES_PER_DEPTH: tuning knob */
+    unsigned occ_tiles_per_depth = WT_OCC_TILES_PER_DEPTH;   /* CLWRAP_OCC_TILES_PER_DEPTH: tuning knob */
     /* the tree-parallel tail of deep launches (whitted_tpt.inc): one slice of node storage per workgroup of the launch */
     uint32_t* d_tpt_pool = nullptr; uint32_t* d_tpt_flags = nullptr; size_t tpt_pool_bytes = 0;
     uint32_t* d_tpt_jump = nullptr;              /* 7 x 32 words: M^(2^i), M = one hit's worth of xorshift steps (xorshift_jump_matrices) */
-    unsigned tpt_max = TPT_MAX_LANES, tpt_min = TPT_MIN_PATHS, tpt_pool_mb = TPT_POOL_MB;   /* CLWRAP_TPT_MAX / _MIN / _POOL_MB, clw_ext_set_tpt */
+    unsigned tpt_max = WT_TPT_MAX_LANES, tpt_min = WT_TPT_MIN_PATHS, tpt_pool_mb = WT_TPT_POOL_MB;   /* CLWRAP_TPT_MAX / _MIN / _POOL_MB, clw_ext_set_tpt */
     int tpt_clock = 0;                                    /* CLWRAP_TPT_CLOCK=1: DIAGNOSTIC phase clock of the tail (counter words 10-25) */
-    unsigned split_slots = SPLIT_SLOTS;                   /* CLWRAP_SPLIT_SLOTS: the quota is a share's total cost over this many wavefronts */
-    unsigned split_min_quota = SPLIT_MIN_QUOTA;           /* CLWRAP_SPLIT_MIN_QUOTA; 0 = heavy tiles are not split */
+    unsigned split_slots = WT_SPLIT_SLOTS;                   /* CLWRAP_SPLIT_SLOTS: the quota is a share's total cost over this many wavefronts */
+    unsigned split_min_quota = WT_SPLIT_MIN_QUOTA;           /* CLWRAP_SPLIT_MIN_QUOTA; 0 = heavy tiles are not split */
     bool timing_on = false;                       /* switched on by the first clw_ext_timing_reset / set_timing_every */
     uint32_t timing_every = 1, timing_tick = 0;   /* events around every n-th launch only */
     std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
@@ -397,7 +368,7 @@ RaygenArgs snapshot_raygen(Impl* I, const Kernel& k, size_t array_size) {
     g.id_offset = I->id_offset;
     g.band_stride = I->band_stride; g.band_phase = I->band_phase;
     /* the reference launches ceil(array_size/local)*local items guarded by id < w*h (raygen.cl:11) */
-    uint64_t rounded = ((uint64_t)array_size + BLOCK - 1) / BLOCK * BLOCK;
+    uint64_t rounded = ((uint64_t)array_size + WT_LAUNCH_ROUND - 1) / WT_LAUNCH_ROUND * WT_LAUNCH_ROUND;
     uint64_t total = (uint64_t)g.width * g.height;
     uint64_t room = total > g.id_offset ? total - g.id_offset : 0;
     if (g.band_stride > 1) {   /* this launch owns every band_stride-th 8-row band of the frame */
@@ -511,7 +482,7 @@ void prepare_scene(Impl* I, Buffer* s, uint32_t ns, Buffer* p, uint32_t np, Buff
     for (uint32_t** q : {&I->d_grid_start, &I->d_grid_items, &I->d_grid_box}) { if (*q) { (void)hipFree(*q); *q = nullptr; } }
     if (I->d_grid_geom) { (void)hipFree(I->d_grid_geom); I->d_grid_geom = nullptr; }
     I->grid_ok = false;
-    if (ns > (uint32_t)env_int("CLWRAP_GRID_MIN", (int)GRID_MIN_SPHERES)) {   /* CLWRAP_GRID_MIN: tuning knob */
+    if (ns > (uint32_t)env_int("CLWRAP_GRID_MIN", (int)WT_GRID_MIN_SPHERES)) {   /* CLWRAP_GRID_MIN: tuning knob */
         const char* dens = getenv("CLWRAP_GRID_DENSITY");   /* tuning knob: average spheres per cell */
         /* the two soft-shadow samples of a light share one walk (wt_grid_shadow_pair) when spheres are listed a light radius beyond their
          * boxes -- worth it while that is a fraction of a cell (CLWRAP_GRID_PAIR=0: every shadow ray walks on its own) */
@@ -552,10 +523,41 @@ Buffer* buffer_arg(cl_wrap* w, cl_uint kernel_id, cl_uint arg) {
     return (Buffer*)w->buffers[kernel_id][arg];
 }
 
-/* The scene side of a raytracer launch (args 1-6, 8, 9 of kernel `kid`): checks the bindings, prepares the geometry
- * (once per scene) and fills the scene fields of P; chooses between the uniform grid, LDS-staged geometry and
- * geometry read from global memory (flags F_GRID / F_GEOM_LDS, dynamic LDS bytes). */
-void bind_scene(cl_wrap* w, Impl* I, cl_uint kid, whitted_params& P, int& flags, size_t& dyn_lds) {
+/* arg 0 of the raytracer: the ray buffer, passed by value as the 8 bytes of a handle (raypng.c:61) or bound as a buffer; null = neither */
+Buffer* find_rays(const cl_wrap* w, Impl* I, cl_uint kid) {
+    if (is_registered(w, kid, 0)) return (Buffer*)w->buffers[kid][0];
+    const ArgValue& v = I->kernels[kid].values[0];
+    if (!v.set || v.size != sizeof(cl_mem)) return nullptr;
+    void* h; memcpy(&h, v.bytes, sizeof h);
+    return lookup_handle(I, h);
+}
+Buffer* rays_of(const cl_wrap* w, Impl* I, cl_uint kid) {
+    Buffer* rays = find_rays(w, I, kid);
+    if (!rays) die("Couldn't run the kernel");
+    return rays;
+}
+/* arg 7 of the raytracer: the guard `total_size` (raytracing.cl:24) */
+bool find_total(const Kernel& k, uint32_t& total) {
+    if (!k.values[7].set || k.values[7].size != 4) return false;
+    memcpy(&total, k.values[7].bytes, 4);
+    return true;
+}
+uint32_t total_of(const Kernel& k) {
+    uint32_t total;
+    if (!find_total(k, total)) die("Couldn't run the kernel");
+    return total;
+}
+
+/* the device tables, an adaptive launch's buffers and the accumulation sum are written and read in stream order: after a change of stream
+ * (clw_ext_set_stream) the first launch that touches one waits for the old stream's fence */
+void wait_tables_fence(Impl* I) {
+    if (!I->tables_fence_pending) return;
+    HIP_OK(hipStreamWaitEvent(I->stream, I->tables_fence, 0), "Couldn't run the kernel");
+    I->tables_fence_pending = false;
+}
+
+/* The scene side of a raytracer launch (args 1-6, 8, 9 of kernel `kid`): checks the bindings and prepares the geometry (once per scene) */
+void prepare_bound_scene(cl_wrap* w, Impl* I, cl_uint kid) {
     Kernel& k = I->kernels[kid];
     Buffer* bs = buffer_arg(w, kid, 1);
     Buffer* bp = buffer_arg(w, kid, 2);
@@ -566,390 +568,285 @@ void bind_scene(cl_wrap* w, Impl* I, cl_uint kid, whitted_params& P, int& flags,
     if (!tex->image || !sky->image) die("Couldn't run the kernel");
     prepare_scene(I, bs, ns, bp, np, bl, nl);
     ensure_allocated(I, bs); ensure_allocated(I, bp);
-    P.geom = I->d_geom; P.ptex = I->d_ptex; P.geom_f4 = (uint32_t)I->geom_f4;
-    P.lpt = (I->have_lpt && !(I->variant & 128)) ? 1u : 0u;
-    /* visibility classes of the lights (wt_light_vis; compiled into the strict build's LDS-geometry kernels): small scenes whose planes are
-     * covered by the side table; variant 256 = off, variant 1024 = verification (counting build: classify AND trace, disagreements in
-     * counter word 28) */
-    P.vis = (I->strict && ns <= VIS_MAX_SPHERES && (np == 0 || P.lpt) && !(I->variant & 256)) ? ((I->variant & 1024) ? 2u : 1u) : 0u;
+}
+/* ... and its device pointers, with the words that describe what they point to (flags: the geometry class, wt_plan_geometry) */
+void bind_scene_pointers(const cl_wrap* w, Impl* I, cl_uint kid, whitted_params& P, int flags) {
+    const Buffer *bs = (Buffer*)w->buffers[kid][1], *bp = (Buffer*)w->buffers[kid][2], *tex = (Buffer*)w->buffers[kid][8], *sky = (Buffer*)w->buffers[kid][9];
+    P.geom = I->d_geom; P.ptex = I->d_ptex;
     P.spheres_raw = (const uint8_t*)bs->dptr; P.planes_raw = (const uint8_t*)bp->dptr;
-    P.ns = ns; P.np = np; P.nl = nl;
-    P.through = I->through;
     P.tex = (const uint32_t*)tex->dptr; P.tex_w = (int)tex->w; P.tex_h = (int)tex->h; P.tex_layers = (int)tex->layers;
     P.sky = (const uint32_t*)sky->dptr; P.sky_w = (int)sky->w; P.sky_h = (int)sky->h;
-    if (I->grid_ok && I->use_grid && !(I->variant & 8)) {
-        flags |= F_GRID;
+    if (flags & WT_F_GRID) {
         P.grid_pair = I->grid_pair ? 1u : 0u;
         P.grid_start = I->d_grid_start; P.grid_items = I->d_grid_items; P.grid_box = I->d_grid_box; P.grid_geom = I->d_grid_geom;
         for (int a = 0; a < 3; a++) {
             P.grid_min[a] = I->grid.gmin[a]; P.grid_inv[a] = I->grid.inv[a]; P.grid_cell[a] = I->grid.cell[a]; P.grid_res[a] = I->grid.res[a];
         }
-    } else if (I->geom_f4 <= GEOM_LDS_MAX_F4 && ns <= GRID_MIN_SPHERES && !(I->variant & 1)) {   /* (<= 256 spheres: the LDS kernels take a = d.d = 1, see unit_dirs) */
-        /* the prepared geometry is staged in LDS */
-        flags |= F_GEOM_LDS;
-        dyn_lds = I->geom_f4 * 16;
     }
+}
+/* both, for the launches that are not planned (the primary-hit pass, clw_ext_unit_scene): fills the scene fields of P and chooses between the
+ * uniform grid, LDS-staged geometry and geometry read from global memory (flags WT_F_GRID / WT_F_GEOM_LDS, dynamic LDS bytes) */
+void bind_scene(cl_wrap* w, Impl* I, cl_uint kid, whitted_params& P, int& flags, size_t& dyn_lds) {
+    prepare_bound_scene(w, I, kid);
+    const wt_geom_class gc = wt_plan_geometry(I->strict, I->variant, I->prep_ns, I->prep_np, (uint32_t)I->geom_f4, I->have_lpt, I->grid_ok && I->use_grid);
+    flags |= gc.flags;
+    if (gc.flags & WT_F_GEOM_LDS) dyn_lds = gc.dyn_lds;
+    P.ns = I->prep_ns; P.np = I->prep_np; P.nl = I->prep_nl; P.geom_f4 = (uint32_t)I->geom_f4;
+    P.lpt = gc.lpt; P.vis = gc.vis;
+    P.through = I->through;
+    bind_scene_pointers(w, I, kid, P, gc.flags);
 }
 
 /* one strip of a frame: rows [row0, row0 + rows) of the launch range, scheduling state in scheds[slot] */
 struct Strip { uint32_t row0, rows; int slot; };
 
-/* what a trace launch is: the whole thing, or one of the two passes of an adaptive launch (run_raytracer) -- its 1-sample base pass, which is
- * the factor-1 launch in everything (scheduling state included), or its refine pass, the supersampled launch served from the classifier's list */
-enum TracePass { PASS_PLAIN = 0, PASS_BASE = 1, PASS_REFINE = 2 };
+/* what a trace launch is: the whole thing, or one of the two passes of an adaptive launch (run_raytracer; launch_plan.h) */
+enum TracePass { PASS_PLAIN = WT_PASS_PLAIN, PASS_BASE = WT_PASS_BASE, PASS_REFINE = WT_PASS_REFINE };
 
-/* -> whether a kernel was launched (an empty range launches none) */
-bool trace_launch(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Strip* strip, TracePass pass) {
-    Kernel& k = I->kernels[kid];
-    const char* who = pass == PASS_PLAIN ? "Supersampling" : "Adaptive supersampling";
-    /* arg 0: the ray buffer, passed by value as the 8 bytes of a handle (raypng.c:61) or bound as a buffer */
-    Buffer* rays = nullptr;
-    if (is_registered(w, kid, 0)) rays = (Buffer*)w->buffers[kid][0];
-    else {
-        const ArgValue& v = need_value(k, 0, sizeof(cl_mem), sizeof(cl_mem));
-        void* h; memcpy(&h, v.bytes, sizeof h);
-        rays = lookup_handle(I, h);
-        if (!rays) die("Couldn't run the kernel");
-    }
-    uint32_t total; memcpy(&total, need_value(k, 7, 4, 4).bytes, 4);
-    Buffer* out = buffer_arg(w, kid, 10);
+/* what the planner is told about a launch: the knobs, the prepared scene, the ray buffer, the range */
+void plan_input(const Impl* I, const Buffer* rays, size_t array_size, uint32_t total, size_t out_size, const Strip* strip, TracePass pass, wt_plan_in& in) {
+    in.depth = I->depth; in.strict = I->strict; in.fuse = I->fuse; in.counting = I->counting; in.stamps = I->stamps; in.tpt_clock = I->tpt_clock;
+    in.variant = I->variant; in.supersample = I->supersample; in.adaptive = I->adaptive; in.seed_offset = I->seed_offset;
+    in.acc_frame = I->acc.frame; in.acc_jitter = I->acc_jitter;
+    in.aperture = I->aperture; in.focus = I->focus; in.through = I->through;
+    in.tpt_max = I->tpt_max; in.tpt_pool_mb = I->tpt_pool_mb; in.tpt_min = I->tpt_min; in.split_min_quota = I->split_min_quota;
+    in.occ_tiles_per_depth = I->occ_tiles_per_depth; in.sched = I->sched;
+    in.diag = (I->variant & WT_V_TIMELINE) ? (env_int("CLWRAP_TIMELINE_EDGES", 0) ? 255u + (uint32_t)env_int("CLWRAP_TIMELINE_EDGES", 0) : 1u + (uint32_t)env_int("CLWRAP_TIMELINE_SHIFT", 0)) : 0u;
+    in.id_offset = I->id_offset; in.band_stride = I->band_stride;
+    in.scene_ok = 1;      /* (prepare_bound_scene refused anything else, with the planner's text, where the planner would) */
+    in.ns = I->prep_ns; in.np = I->prep_np; in.nl = I->prep_nl; in.geom_f4 = (uint32_t)I->geom_f4;
+    in.have_lpt = I->have_lpt; in.grid_usable = I->grid_ok && I->use_grid;
+    in.args_ok = 1;
+    in.rays_generated = rays->gen_valid; in.rays_exposed = rays->exposed; in.gen = rays->gen; in.rays_size = rays->size;
+    in.array_size = array_size; in.out_size = out_size; in.total = total;
+    in.has_strip = strip != nullptr; in.strip_row0 = strip ? strip->row0 : 0u; in.strip_rows = strip ? strip->rows : 0u;
+    in.pass = pass;
+    in.cams = I->cams.data(); in.n_cams = (uint32_t)I->cams.size();
+    in.times = I->motion_times.data(); in.n_times = (uint32_t)I->motion_times.size(); in.explicit_times = I->motion_explicit_times;
+    in.disp = I->motion_disp.data(); in.n_disp = (uint32_t)I->motion_disp.size();
+}
 
-    uint64_t rounded = ((uint64_t)array_size + BLOCK - 1) / BLOCK * BLOCK;
-    uint64_t n64 = rounded < total ? rounded : total;      /* guard `id >= total_size` (raytracing.cl:24) */
-    ensure_allocated(I, out);
-    if (n64 > out->size / 4) n64 = out->size / 4;          /* never write past the framebuffer */
-    if (n64 == 0) return false;
-    if (n64 > 0xFFFFFFFFull) die("Couldn't run the kernel");
+/* ---- the effects of a planned launch, in stream order; each touches one piece of Impl state -------------------------------------------- */
+/* the tables of the launch, for clw_ext_get_sample_cameras / _times */
+void keep_samples(Impl* I, const wt_plan_out& plan) {
+    I->cams_used.clear(); I->times_used.clear();
+    if (plan.n_cams) I->cams_used.assign(plan.cams_used, plan.cams_used + plan.n_cams);
+    if (plan.n_times) I->times_used.assign(plan.times_used, plan.times_used + plan.n_times);
+}
 
-    whitted_params P{};
-    int flags = 0;
-    size_t dyn_lds = 0;
-    bind_scene(w, I, kid, P, flags, dyn_lds);
-    P.n_items = (uint32_t)n64;
-    P.depth = I->depth;
-    P.untrimmed = (I->variant & 16384) ? 1u : 0u;
-    P.out = (uint32_t*)out->dptr;
+/* scene, framebuffer and -- for a launch that reads its rays -- the ray buffer, generated now if it is still virtual */
+void bind_buffers(cl_wrap* w, Impl* I, cl_uint kid, Buffer* rays, const Buffer* out, wt_plan_out& plan) {
+    whitted_params& P = plan.P;
+    bind_scene_pointers(w, I, kid, P, plan.flags);
+    P.out = (uint32_t*)out->dptr + plan.out_offset;
     P.out_rgb = I->debug_rgb;
-    P.seed_offset = I->seed_offset;
-    P.diag = (I->variant & 512) ? (env_int("CLWRAP_TIMELINE_EDGES", 0) ? 255u + (uint32_t)env_int("CLWRAP_TIMELINE_EDGES", 0) : 1u + (uint32_t)env_int("CLWRAP_TIMELINE_SHIFT", 0)) : 0u;
-
-    const int ss = pass == PASS_BASE ? 1 : I->supersample;
-    if (I->aperture > 0.0f && ss == 1) die("A lens needs samples: aperture %g with supersampling factor 1 (clw_ext_set_supersample / CLWRAP_SUPERSAMPLE)", (double)I->aperture);
-    if (!I->cams.empty() && (ss == 1 || I->cams.size() != (size_t)(ss * ss)))
-        die("Sample cameras: the table holds %u cameras, but supersampling factor %d %s", (unsigned)I->cams.size(), ss,
-            ss == 1 ? "takes none (set a factor of 2, 4 or 8)" : (ss == 2 ? "needs 4" : (ss == 4 ? "needs 16" : "needs 64")));
-    bool have_cams = false;
-    wt_cam_table cam_table;
-    I->cams_used.clear();
-    const bool moving = !I->motion_disp.empty();
-    std::vector<float> motion_table;             /* the device layout: 64 per-lane times, a float4 per sphere, padded to whole wt_cam_tables */
-    I->times_used.clear();
-    if (moving) {
-        if (ss == 1) die("Moving spheres need samples: a displacement table with supersampling factor 1 (clw_ext_set_supersample / CLWRAP_SUPERSAMPLE)");
-        if (I->motion_explicit_times && I->motion_times.size() != (size_t)(ss * ss))
-            die("Moving spheres: %u sample times, but supersampling factor %d needs %d", (unsigned)I->motion_times.size(), ss, ss * ss);
-        if (I->motion_disp.size() != 3 * (size_t)P.ns)
-            die("Moving spheres: the displacement table is for %u spheres, the scene has %u", (unsigned)(I->motion_disp.size() / 3), (unsigned)P.ns);
-        if ((flags & F_GRID) || P.ns > GRID_MIN_SPHERES)
-            die("Moving spheres: scenes of more than %u spheres (the uniform grid is built for one set of centres) are not supported", (unsigned)GRID_MIN_SPHERES);
-        /* the 16 KiB staging rule counts the table: a scene it pushes over the limit reads both from global memory */
-        if (flags & F_GEOM_LDS) {
-            if (I->geom_f4 + P.ns <= GEOM_LDS_MAX_F4) dyn_lds += (size_t)P.ns * 16;
-            else { flags &= ~F_GEOM_LDS; dyn_lds = 0; }
-        }
-    }
-    const bool fused = I->fuse && rays->gen_valid && !rays->exposed;   /* (a buffer whose pointer was handed out is read, not regenerated) */
-    RaygenArgs g{};
-    if (fused) {
-        g = rays->gen;
-        if (strip) {   /* the caller checked: whole rows, no bands */
-            g.id_offset += (uint64_t)strip->row0 * g.width;
-            g.n_items = strip->rows * g.width;
-            P.n_items = g.n_items;
-            P.out = (uint32_t*)out->dptr + (size_t)strip->row0 * g.width;
-        }
-        memcpy(P.corner, g.corner, 12); memcpy(P.origin, g.origin, 12);
-        memcpy(P.up, g.up, 12); memcpy(P.right, g.right, 12);
-        P.w_factor = g.w_factor; P.h_factor = g.h_factor; P.width = g.width; P.height = g.height;
-        P.id_offset = g.id_offset;
-        P.band_stride = g.band_stride; P.band_phase = g.band_phase;
-        if (P.n_items > g.n_items) P.n_items = g.n_items; /* rays past the generated range are undefined in the reference */
-        if (P.n_items == 0) return false;
-        if (I->acc.frame >= 0) {
-            /* frame f of an accumulated view (run_raytracer): its own seeds, its own sub-pixel offset, folded into the running sum by the kernel's
-             * epilogue.  Only the trace's camera words move: `g` -- the ray buffer's meaning, the scheduling signature -- stays the latched camera,
-             * so the tile order built for the still view keeps serving it (the offset moves a tile's content by less than a pixel). */
-            Impl::Accum& A = I->acc;
-            const uint32_t f = (uint32_t)A.frame;
-            P.seed_offset = I->seed_offset + clw_host_frame_seed(f);
-            if (I->acc_jitter) {
-                clw_camera base, jit;
-                memcpy(base.im_corner, g.corner, 12); memcpy(base.origin, g.origin, 12); memcpy(base.up, g.up, 12); memcpy(base.right, g.right, 12);
-                base.w_factor = g.w_factor; base.h_factor = g.h_factor; base.width = g.width; base.height = g.height;
-                if (!clw_host_jitter_camera(&base, f, (uint32_t)ss, &jit)) die("Couldn't run the kernel");
-                memcpy(P.corner, jit.im_corner, 12);
-            }
-            if (A.pixels != (size_t)P.n_items || !A.sum) {
-                if (f != 0) die("Couldn't run the kernel");      /* (the range is part of the key: a new range starts at frame 0) */
-                if (A.sum) { finish(I); (void)hipFree(A.sum); A.sum = nullptr; }
-                HIP_OK(hipMalloc((void**)&A.sum, (size_t)P.n_items * 12), "Couldn't allocate device memory");
-                A.pixels = P.n_items;
-            }
-            if (I->tables_fence_pending) { HIP_OK(hipStreamWaitEvent(I->stream, I->tables_fence, 0), "Couldn't run the kernel"); I->tables_fence_pending = false; }
-            I->tables_in_flight = true;
-            P.acc_sum = A.sum;      /* indexed like `out` (whole-range launches only: the pipelined read-back declines in the mode) */
-            P.acc_scale = 1.0f / (float)(f + 1u);
-        }
-        P.tiled = (g.id_offset % g.width == 0 || g.band_stride > 1) && (P.n_items % g.width == 0) && !(I->variant & 2);
-        if (ss > 1) {
-            /* the launch traces the virtual frame of ss x as many columns and rows that the same camera gives (for a power of two bit for bit
-             * what rgen_perspective returns for it) and stores one resolved pixel per ss x ss samples; ids -- the RNG seeds -- are the virtual
-             * frame's.  Everything the caller sized stays in output pixels: the range above, `out`, the ray buffer, the strips. */
-            if (g.band_stride > 1) die("%s does not support interleaved row bands", who);
-            if (I->variant & 2) die("%s does not support linear work-item ids (variant 2)", who);
-            if (!P.tiled) die("%s needs a launch range of whole rows", who);
-            if ((uint64_t)g.width * g.height * (uint64_t)(ss * ss) >= (1ull << 32)) die("%s: the %d x %d samples of this frame exceed 32-bit ids", who, ss, ss);
-            const uint32_t out_rows = P.n_items / g.width, row0 = (uint32_t)(g.id_offset / g.width);
-            g.w_factor /= (float)ss; g.h_factor /= (float)ss;
-            g.width *= (uint32_t)ss; g.height *= (uint32_t)ss;
-            g.id_offset = (uint64_t)row0 * (uint32_t)ss * g.width;
-            g.n_items = out_rows * (uint32_t)ss * g.width;
-            P.w_factor = g.w_factor; P.h_factor = g.h_factor; P.width = g.width; P.height = g.height;
-            P.id_offset = g.id_offset; P.n_items = g.n_items;
-            P.ss_lg = ss == 2 ? 1u : (ss == 4 ? 2u : 3u);
-            if (I->aperture > 0.0f) {   /* the lens table of the camera the raygen launch latched (the W x H one) */
-                clw_camera base;
-                memcpy(base.im_corner, rays->gen.corner, 12); memcpy(base.origin, rays->gen.origin, 12);
-                memcpy(base.up, rays->gen.up, 12); memcpy(base.right, rays->gen.right, 12);
-                base.w_factor = rays->gen.w_factor; base.h_factor = rays->gen.h_factor; base.width = rays->gen.width; base.height = rays->gen.height;
-                I->cams_used.resize((size_t)(ss * ss));
-                if (!clw_host_lens_cameras(&base, I->aperture, I->focus, (uint32_t)ss, I->cams_used.data())) die("A lens cannot be derived from this camera (its image plane passes through its origin)");
-            } else I->cams_used = I->cams;
-            if (!I->cams_used.empty()) {
-                have_cams = true;
-                for (unsigned lane = 0; lane < 64; lane++)   /* a tile's lane (lane & 7, lane >> 3) traces sub-sample (sx, sy) = both mod n */
-                    memcpy(cam_table.v + 12 * lane, &I->cams_used[(size_t)((lane >> 3) & (unsigned)(ss - 1)) * ss + ((lane & 7u) & (unsigned)(ss - 1))], 48);
-                if (!I->d_cams) HIP_OK(hipMalloc((void**)&I->d_cams, sizeof(wt_cam_table)), "Couldn't allocate device memory");
-                if (I->tables_fence_pending) { HIP_OK(hipStreamWaitEvent(I->stream, I->tables_fence, 0), "Couldn't run the kernel"); I->tables_fence_pending = false; }
-                if (!I->cams_dev_valid || memcmp(&cam_table, &I->cams_dev, sizeof cam_table)) {
-                    if (wt_fast_launch_cams(&cam_table, I->d_cams, I->stream) != hipSuccess) die("Couldn't run the kernel");
-                    I->cams_dev = cam_table; I->cams_dev_valid = true;
-                }
-                I->tables_in_flight = true;
-                P.ss_cams = I->d_cams;
-            }
-            if (moving) {
-                if (!I->motion_explicit_times) { I->times_used.resize((size_t)(ss * ss)); clw_host_sample_times((uint32_t)ss, I->times_used.data()); }
-                else I->times_used = I->motion_times;
-                const size_t pieces = (64 + 4 * (size_t)P.ns + WT_CAM_TABLE_FLOATS - 1) / WT_CAM_TABLE_FLOATS;      /* <= 2: ns <= 256 */
-                motion_table.assign(pieces * WT_CAM_TABLE_FLOATS, 0.0f);
-                for (unsigned lane = 0; lane < 64; lane++)   /* as the camera table: lane (lane & 7, lane >> 3) traces sub-sample (sx, sy) = both mod n */
-                    motion_table[lane] = I->times_used[(size_t)((lane >> 3) & (unsigned)(ss - 1)) * ss + ((lane & 7u) & (unsigned)(ss - 1))];
-                for (uint32_t i = 0; i < P.ns; i++) memcpy(&motion_table[64 + 4 * (size_t)i], &I->motion_disp[3 * (size_t)i], 12);
-                if (!I->d_motion) HIP_OK(hipMalloc((void**)&I->d_motion, 2 * sizeof(wt_cam_table)), "Couldn't allocate device memory");
-                if (I->tables_fence_pending) { HIP_OK(hipStreamWaitEvent(I->stream, I->tables_fence, 0), "Couldn't run the kernel"); I->tables_fence_pending = false; }
-                if (!same_bits(I->motion_dev, motion_table)) {
-                    for (size_t c = 0; c < pieces; c++) {
-                        wt_cam_table piece;
-                        memcpy(piece.v, &motion_table[c * WT_CAM_TABLE_FLOATS], sizeof piece);
-                        if (wt_fast_launch_cams(&piece, I->d_motion + c * WT_CAM_TABLE_FLOATS, I->stream) != hipSuccess) die("Couldn't run the kernel");
-                    }
-                    I->motion_dev = motion_table;
-                }
-                I->tables_in_flight = true;
-                P.ss_times = I->d_motion; P.ss_disp = I->d_motion + 64;
-            }
-        }
-        P.rows = P.n_items / g.width;
-        P.row_offset = (uint32_t)(g.id_offset / g.width);
-        P.unit_dirs = P.ns <= GRID_MIN_SPHERES ? 1u : 0u;      /* primary rays are generated (and normalised) in the kernel */
-    } else {
-        if (ss > 1) die("%s needs the fused raygen + trace launch (CLWRAP_FUSE=1, rays generated by this library and not rewritten)", who);
+    if (!plan.fused) {
         materialise_rays(I, rays);
         ensure_allocated(I, rays);
-        if ((uint64_t)P.n_items * 64 > rays->size) die("Couldn't run the kernel");
         P.rays = (const float*)rays->dptr;
-        P.id_offset = I->id_offset;
-        P.width = 1; P.height = 1;
-        P.unit_dirs = (rays->gen_valid && !rays->exposed && P.ns <= GRID_MIN_SPHERES) ? 1u : 0u;
-        if (rays->gen_valid) {   /* ids (RNG seeds) follow the launch that generated the rays */
-            P.id_offset = rays->gen.id_offset; P.width = rays->gen.width; P.height = rays->gen.height;
-            P.band_stride = rays->gen.band_stride; P.band_phase = rays->gen.band_phase;
-        } else if (I->band_stride > 1) die("Row bands need a raygen launch");
-        flags |= F_RAYS;
     }
-    if (I->depth > SHALLOW_LEVELS + 1) flags |= F_DEEP;
-    if (!(flags & F_GEOM_LDS)) P.vis = 0;
-    if (I->counting || I->stamps || I->tpt_clock) {
-        if (I->counting) flags |= F_COUNT;
-        P.tpt_clock = I->tpt_clock ? 1u : 0u;
-        if (!I->d_counters) {
-            HIP_OK(hipMalloc((void**)&I->d_counters, COUNTER_WORDS * sizeof(unsigned long long)), "Couldn't allocate device memory");
-            HIP_OK(hipMemsetAsync(I->d_counters, 0, COUNTER_WORDS * sizeof(unsigned long long), I->stream), "Couldn't allocate device memory");
+}
+
+/* The per-lane sample cameras and the moving spheres' table: the device copy is rewritten, only when it changed, by a small kernel on the
+ * launch stream that carries the table (in pieces of one wt_cam_table) as its argument */
+void bind_tables(Impl* I, wt_plan_out& plan) {
+    if (plan.n_cams) {
+        if (!I->d_cams) HIP_OK(hipMalloc((void**)&I->d_cams, sizeof(wt_cam_table)), "Couldn't allocate device memory");
+        wait_tables_fence(I);
+        if (!I->cams_dev_valid || memcmp(&plan.cam_table, &I->cams_dev, sizeof plan.cam_table)) {
+            if (wt_fast_launch_cams(&plan.cam_table, I->d_cams, I->stream) != hipSuccess) die("Couldn't run the kernel");
+            I->cams_dev = plan.cam_table; I->cams_dev_valid = true;
         }
-        P.counters = I->d_counters;
-    }
-    unsigned grid;
-    Impl::Sched& S = I->scheds[strip ? strip->slot : 0];
-    bool sched_rebuild = false;
-    unsigned trows = 0, tpr = 0, per_share = 0, per_share_cap = 0, base_grid = 0;
-    /* deep launches with the tree-parallel tail: a tile's cost is its total work, and heavy tiles are split over several wavefronts */
-    if (P.tiled) {
-        trows = (P.rows + 7) / 8; tpr = (P.width + 7) / 8;
-        per_share = ((trows + 7) / 8) * tpr;
-        per_share_cap = per_share;
-        grid = base_grid = 8 * per_share;
-    } else {
-        grid = base_grid = (P.n_items + TRACE_BLOCK - 1) / TRACE_BLOCK;
-    }
-    /* big deep launches are throughput-bound: the high-occupancy flavour (96 VGPRs, five waves per SIMD) -- which does not carry the tail:
-     * under that register cap the tail's passes spill, and its code cost the per-lane loop 6 % (4096^2 depth 8: 7.4 -> 7.9 ms) */
-    if ((flags & F_DEEP) && !I->strict && (uint64_t)base_grid >= (uint64_t)I->occ_tiles_per_depth * (unsigned)I->depth && !(I->variant & 64)) flags |= F_OCC;
-    /* the tree-parallel tail (whitted_tpt.inc): (27 or 29 + weights per light x lights) words per node; the parked lane state and LDS stack levels
-     * and the replay's saved sums besides; TPT_SLOTS_PER_XCC slots per XCD, taken and handed back by the waves themselves */
-    const uint64_t tpt_per_node = (I->strict ? 29u : 27u) + (I->strict ? 4u : 1u) * (uint64_t)P.nl;
-    const uint64_t tpt_fixed = (25u + 36u) * 64u + (uint64_t)I->depth * 3u * 64u;
-    const uint64_t tpt_nslots = 8u * (uint64_t)TPT_SLOTS_PER_XCC;
-    const uint64_t tpt_slice = std::min<uint64_t>(TPT_SLICE_WORDS_MAX, ((uint64_t)I->tpt_pool_mb << 18) / tpt_nslots) & ~(uint64_t)63;
-    const uint64_t tpt_cap = std::min<uint64_t>(tpt_slice > tpt_fixed ? ((tpt_slice - tpt_fixed) / tpt_per_node) & ~(uint64_t)63 : 0, 64960u);   /* whole blocks of 64 nodes; node ids are 16 bits */
-    /* (not for moving spheres: a tail node is traced by whichever lane takes it, which would need the owning pixel's time; with it goes the split of heavy tiles) */
-    const bool tail_wanted = (flags & F_DEEP) && !(flags & F_OCC) && !(I->variant & 16) && I->tpt_max != 0u && tpt_cap >= TPT_MIN_CAP && !moving;
-    bool split = false;
-    const unsigned split_max_lg = ss == 1 ? 4u : (ss == 2 ? 2u : (ss == 4 ? 1u : 0u));
-    if (pass == PASS_REFINE) {
-        /* the refine pass: its order is the classifier's list, eight per-XCD lists of up to per_share entries whose lengths only the device knows --
-         * the grid covers full lists, and the list-driven flavour sends the waves beyond a list's end home.  No costs, no split of heavy tiles;
-         * the tail, the high-occupancy flavour and the grid are chosen above and below as the plain supersampled launch chooses them. */
-        if (trows > 0xFFFu || tpr > 0xFFFu) die("Adaptive supersampling: %u x %u blocks are more than a tile list can address (4095 each way)", tpr, trows);
-        const uint32_t ow = P.width >> P.ss_lg, orows = P.rows >> P.ss_lg;
-        Impl::Adaptive& A = I->adapt;
-        if (A.w != ow || A.rows != orows || A.ss != ss || !A.mask) {
-            A.free_all();
-            HIP_OK(hipMalloc((void**)&A.mask, (size_t)trows * tpr), "Couldn't allocate device memory");
-            HIP_OK(hipMalloc((void**)&A.order, (size_t)grid * 4), "Couldn't allocate device memory");
-            HIP_OK(hipMalloc((void**)&A.count, 8 * WT_LIST_COUNT_STRIDE * 4), "Couldn't allocate device memory");
-            A.w = ow; A.rows = orows; A.ss = ss;
-        }
-        if (I->tables_fence_pending) { HIP_OK(hipStreamWaitEvent(I->stream, I->tables_fence, 0), "Couldn't run the kernel"); I->tables_fence_pending = false; }
-        HIP_OK(hipMemsetAsync(A.count, 0, 8 * WT_LIST_COUNT_STRIDE * 4, I->stream), "Couldn't run the kernel");
-        if (wt_fast_launch_classify(P.out, ow, orows, 3u - P.ss_lg, (unsigned)I->adaptive, A.mask, A.order, A.count, per_share, I->stream) != hipSuccess)
-            die("Couldn't run the kernel");
         I->tables_in_flight = true;
-        A.blocks = trows * tpr;
-        P.tile_order = A.order; P.list_count = A.count;
-    } else if (P.tiled) {
-        if (!strip) S.last_rd = -1;
-        if (I->sched && !(I->variant & 4) && trows <= 0xFFFu && tpr <= 0xFFFu) {   /* the order packs (tile column | row << 12 | parts) */
-            /* a part of a split tile owns 8 >> lg whole tile rows; a supersampled launch needs ss of them in one wavefront (ss = 8: no split) */
-            split = tail_wanted && !(flags & F_GRID) && I->split_min_quota != 0u && !(I->variant & 4096) && split_max_lg != 0u;
-            if (split) { per_share_cap = per_share + SPLIT_EXTRA_PER_SHARE; grid = 8 * per_share_cap; }
-            P.cost_sum = (tail_wanted && !(flags & F_GRID)) ? 1u : 0u;
-            if (S.w != P.width || S.rows != P.rows || S.cap != per_share_cap || S.ss != ss || !S.cost[0]) {
-                S.free_all();
-                for (int i = 0; i < 2; i++) {
-                    HIP_OK(hipMalloc((void**)&S.cost[i], (size_t)trows * tpr * 4), "Couldn't allocate device memory");
-                    HIP_OK(hipMalloc((void**)&S.order[i], (size_t)grid * 4), "Couldn't allocate device memory");
-                    HIP_OK(hipEventCreateWithFlags(&S.built[i], hipEventDisableTiming), "Couldn't create a timing event");
-                }
-                HIP_OK(hipEventCreateWithFlags(&S.traced, hipEventDisableTiming), "Couldn't create a timing event");
-                S.w = P.width; S.rows = P.rows; S.cap = per_share_cap; S.ss = ss; S.wr = 0;
+        plan.P.ss_cams = I->d_cams;
+    }
+    if (plan.motion_floats) {
+        if (!I->d_motion) HIP_OK(hipMalloc((void**)&I->d_motion, 2 * sizeof(wt_cam_table)), "Couldn't allocate device memory");
+        wait_tables_fence(I);
+        if (!same_bits(I->motion_dev, plan.motion_table, plan.motion_floats)) {
+            for (size_t c = 0; c < plan.motion_floats / WT_CAM_TABLE_FLOATS; c++) {
+                wt_cam_table piece;
+                memcpy(piece.v, &plan.motion_table[c * WT_CAM_TABLE_FLOATS], sizeof piece);
+                if (wt_fast_launch_cams(&piece, I->d_motion + c * WT_CAM_TABLE_FLOATS, I->stream) != hipSuccess) die("Couldn't run the kernel");
             }
-            const int wr = S.wr;
-            P.tile_cost = S.cost[wr];
-            /* the order built two frames ago is complete by now; the one built behind the previous frame may still be
-             * running (waiting for it costs that frame ~15 us, once) */
-            int rd = S.have[S.newest] ? S.newest : -1;
-            if (rd >= 0 && S.frame - S.newest_frame <= 1 && S.have[rd ^ 1]) rd ^= 1;   /* a still camera ends up on the newest */
-            S.frame++;
-            /* build(k-2) read cost[wr] and wrote order[wr]: it must have finished before this trace touches either */
-            if (S.have[wr]) HIP_OK(hipStreamWaitEvent(I->stream, S.built[wr], 0), "Couldn't run the kernel");
-            if (rd >= 0 && rd != wr) HIP_OK(hipStreamWaitEvent(I->stream, S.built[rd], 0), "Couldn't run the kernel");
-            P.tile_order = rd >= 0 ? S.order[rd] : nullptr;
-            if (!strip) S.last_rd = rd;
-            /* the costs can only change when the camera, the depth or the scene did */
-            sched_rebuild = !S.sig_valid || !same_raygen(g, S.sig) || S.sig_depth != I->depth || S.sig_scene != I->scene_generation ||
-                            S.sig_has_cams != have_cams || (have_cams && memcmp(&S.sig_cams, &cam_table, sizeof cam_table)) || !same_bits(S.sig_motion, motion_table);
-            /* (costs that add up: the buffer starts at zero; the build that read it two frames ago has been waited for above) */
-            if (P.cost_sum) HIP_OK(hipMemsetAsync(S.cost[wr], 0, (size_t)trows * tpr * 4, I->stream), "Couldn't run the kernel");
-            if (sched_rebuild) { S.sig_motion = motion_table; S.sig_has_cams = have_cams; if (have_cams) S.sig_cams = cam_table; S.sig = g; S.sig_depth = I->depth; S.sig_scene = I->scene_generation; S.sig_valid = true; S.sig_age = 0; }
-            /* Grid builds measure a tile by its wave's lifetime, which depends on the company it ran in: the order built
-             * from the first (unsorted, often cold) frame is refined once from the first sorted one. */
-            else if ((flags & F_GRID) && S.sig_age < 2) sched_rebuild = true;
-            if (S.sig_age < 255) S.sig_age++;
+            I->motion_dev.assign(plan.motion_table, plan.motion_table + plan.motion_floats);
+        }
+        I->tables_in_flight = true;
+        plan.P.ss_times = I->d_motion; plan.P.ss_disp = I->d_motion + 64;
+    }
+}
+
+/* the running sum of an accumulated view: 3 floats per output pixel of the launch range (whole-range launches only: the pipelined read-back
+ * declines in the mode) */
+void bind_accumulation(Impl* I, wt_plan_out& plan) {
+    Impl::Accum& A = I->acc;
+    if (!plan.fused || A.frame < 0) return;
+    if (A.pixels != (size_t)plan.out_pixels || !A.sum) {
+        if (A.frame != 0) die("Couldn't run the kernel");      /* (the range is part of the key: a new range starts at frame 0) */
+        if (A.sum) { finish(I); (void)hipFree(A.sum); A.sum = nullptr; }
+        HIP_OK(hipMalloc((void**)&A.sum, (size_t)plan.out_pixels * 12), "Couldn't allocate device memory");
+        A.pixels = plan.out_pixels;
+    }
+    wait_tables_fence(I);
+    I->tables_in_flight = true;
+    plan.P.acc_sum = A.sum;
+}
+
+void bind_counters(Impl* I, wt_plan_out& plan) {
+    if (!plan.need_counters) return;
+    if (!I->d_counters) {
+        HIP_OK(hipMalloc((void**)&I->d_counters, COUNTER_WORDS * sizeof(unsigned long long)), "Couldn't allocate device memory");
+        HIP_OK(hipMemsetAsync(I->d_counters, 0, COUNTER_WORDS * sizeof(unsigned long long), I->stream), "Couldn't allocate device memory");
+    }
+    plan.P.counters = I->d_counters;
+}
+
+/* the refine pass of an adaptive launch: the classifier reads the base pass's pixels and writes the mask, the eight tile lists and their lengths;
+ * the buffers follow the launch range and the factor */
+void classify_blocks(Impl* I, wt_plan_out& plan) {
+    whitted_params& P = plan.P;
+    const uint32_t ow = P.width >> P.ss_lg, orows = P.rows >> P.ss_lg;
+    Impl::Adaptive& A = I->adapt;
+    if (A.w != ow || A.rows != orows || A.ss != plan.ss || !A.mask) {
+        A.free_all();
+        HIP_OK(hipMalloc((void**)&A.mask, (size_t)plan.trows * plan.tpr), "Couldn't allocate device memory");
+        HIP_OK(hipMalloc((void**)&A.order, (size_t)plan.grid * 4), "Couldn't allocate device memory");
+        HIP_OK(hipMalloc((void**)&A.count, 8 * WT_LIST_COUNT_STRIDE * 4), "Couldn't allocate device memory");
+        A.w = ow; A.rows = orows; A.ss = plan.ss;
+    }
+    wait_tables_fence(I);
+    HIP_OK(hipMemsetAsync(A.count, 0, 8 * WT_LIST_COUNT_STRIDE * 4, I->stream), "Couldn't run the kernel");
+    if (wt_fast_launch_classify(P.out, ow, orows, 3u - P.ss_lg, (unsigned)I->adaptive, A.mask, A.order, A.count, plan.per_share, I->stream) != hipSuccess)
+        die("Couldn't run the kernel");
+    I->tables_in_flight = true;
+    A.blocks = plan.trows * plan.tpr;
+    P.tile_order = A.order; P.list_count = A.count;
+}
+
+/* the cost-sorted tile order of a tiled launch: the cost buffer it writes, the order it reads (wt_order_choose), the builds it waits for
+ * -> whether this frame's costs are sorted behind the launch (sort_tile_costs) */
+bool bind_tile_order(Impl* I, Impl::Sched& S, wt_plan_out& plan, const Strip* strip) {
+    whitted_params& P = plan.P;
+    if (!strip) S.last_rd = -1;
+    if (!plan.use_order) return false;
+    const size_t ntiles = (size_t)plan.trows * plan.tpr;
+    if (S.w != P.width || S.rows != P.rows || S.cap != plan.per_share_cap || S.ss != plan.ss || !S.cost[0]) {
+        S.free_all();
+        for (int i = 0; i < 2; i++) {
+            HIP_OK(hipMalloc((void**)&S.cost[i], ntiles * 4), "Couldn't allocate device memory");
+            HIP_OK(hipMalloc((void**)&S.order[i], (size_t)plan.grid * 4), "Couldn't allocate device memory");
+            HIP_OK(hipEventCreateWithFlags(&S.built[i], hipEventDisableTiming), "Couldn't create a timing event");
+        }
+        HIP_OK(hipEventCreateWithFlags(&S.traced, hipEventDisableTiming), "Couldn't create a timing event");
+        S.w = P.width; S.rows = P.rows; S.cap = plan.per_share_cap; S.ss = plan.ss; S.o.wr = 0;
+    }
+    const int wr = S.o.wr;
+    P.tile_cost = S.cost[wr];
+    const wt_order_choice c = wt_order_choose(&S.o);
+    if (c.wait_wr) HIP_OK(hipStreamWaitEvent(I->stream, S.built[wr], 0), "Couldn't run the kernel");
+    if (c.wait_rd) HIP_OK(hipStreamWaitEvent(I->stream, S.built[c.rd], 0), "Couldn't run the kernel");
+    P.tile_order = c.rd >= 0 ? S.order[c.rd] : nullptr;
+    if (!strip) S.last_rd = c.rd;
+    /* the costs can only change when the camera, the depth or the scene did */
+    const bool have_cams = plan.n_cams != 0;
+    const bool changed = !S.o.sig_valid || !same_raygen(plan.sig, S.sig) || S.sig_depth != I->depth || S.sig_scene != I->scene_generation || S.sig_has_cams != have_cams ||
+                         (have_cams && memcmp(&S.sig_cams, &plan.cam_table, sizeof plan.cam_table)) || !same_bits(S.sig_motion, plan.motion_table, plan.motion_floats);
+    /* (costs that add up: the buffer starts at zero; the build that read it two frames ago has been waited for above) */
+    if (P.cost_sum) HIP_OK(hipMemsetAsync(S.cost[wr], 0, ntiles * 4, I->stream), "Couldn't run the kernel");
+    if (changed) {
+        S.sig_motion.assign(plan.motion_table, plan.motion_table + plan.motion_floats);
+        S.sig_has_cams = have_cams; if (have_cams) S.sig_cams = plan.cam_table;
+        S.sig = plan.sig; S.sig_depth = I->depth; S.sig_scene = I->scene_generation;
+    }
+    return wt_order_rebuild(&S.o, changed, plan.flags & WT_F_GRID) != 0;
+}
+
+/* the tree-parallel tail's pool: one allocation for every launch of its size; without room the launch runs without the tail */
+void bind_tail_pool(Impl* I, wt_plan_out& plan) {
+    if (!plan.tail_wanted) return;
+    whitted_params& P = plan.P;
+    const size_t need = (size_t)plan.tpt_slice * 4u * plan.tpt_nslots;
+    if (I->tpt_pool_bytes != need) {
+        finish(I);
+        if (I->d_tpt_pool) (void)hipFree(I->d_tpt_pool);
+        if (I->d_tpt_flags) (void)hipFree(I->d_tpt_flags);
+        I->d_tpt_pool = nullptr; I->d_tpt_flags = nullptr; I->tpt_pool_bytes = 0;
+        if (hipMalloc((void**)&I->d_tpt_pool, need) == hipSuccess && hipMalloc((void**)&I->d_tpt_flags, plan.tpt_nslots * 4u) == hipSuccess) {
+            /* on the LAUNCH stream: it does not synchronise with the null stream (hipStreamNonBlocking), and a hipMemset of device memory may
+             * return before it has run -- cleared there, the flags could still be garbage when the first waves take their slots, or be
+             * zeroed under a wave that holds one, and two tiles would share a slot (seen as an occasional wrong first frame of a deep
+             * launch whose tiles all enter the tail at once, clw_ext_set_tpt(64)) */
+            HIP_OK(hipMemsetAsync(I->d_tpt_flags, 0, plan.tpt_nslots * 4u, I->stream), "Couldn't allocate device memory");
+            I->tpt_pool_bytes = need;
+        } else {                                /* no room: the launch runs without the tail */
+            (void)hipGetLastError();
+            if (I->d_tpt_pool) (void)hipFree(I->d_tpt_pool);
+            I->d_tpt_pool = nullptr;
         }
     }
-    /* deep launches: the scratch part of the DFS stack is sized for the launch's depth (7 / 15 / 31 parents) */
-    if ((flags & F_DEEP) && !(flags & F_COUNT) && !(I->variant & 2048)) flags |= I->depth <= 8 ? F_D8 : (I->depth <= 16 ? F_D16 : 0);
-    /* a small scene of the shallow fast build: its counts compiled in (the shaped kernel assumes the side table whenever there are planes);
-     * variant 8192 = the generic kernel */
-    if (!I->strict && flags == F_GEOM_LDS && P.ns >= 1u && P.ns <= SHAPE_MAX_SPHERES && P.np <= SHAPE_MAX_PLANES && P.nl == SHAPE_LIGHTS &&
-        (P.np == 0u || P.lpt) && !(I->variant & 8192))
-        flags |= F_SHAPE | (int)(P.ns << 9 | P.np << 12 | P.nl << 14);
-    if (P.ss_lg) flags |= F_SS;      /* every fused flavour has a supersampled twin, whose epilogue resolves the samples */
-    if (P.ss_lg && P.ss_disp) flags |= F_MOVE;      /* ... and the twin (not the grid builds') a flavour whose sphere reads take the lane's scene time */
-    if (pass == PASS_REFINE) flags |= F_LIST;       /* ... and one that asks the device how long its tile list is */
-    /* the strict build's shallow counting and grid kernels read the seed offset and accumulate only as their WT_F_ACC twin (wt_acc_flagged) */
-    if (I->strict && !(flags & F_DEEP) && (flags & (F_COUNT | F_GRID)) && (P.seed_offset != 0u || P.acc_sum)) flags |= F_ACC;
-    I->last_trace_flags = flags;
-    if (tail_wanted) {
-        const uint64_t nslots = tpt_nslots, slice = tpt_slice, cap = tpt_cap;
-        if (cap >= TPT_MIN_CAP) {
-            const size_t need = (size_t)slice * 4u * nslots;
-            if (I->tpt_pool_bytes != need) {
-                finish(I);
-                if (I->d_tpt_pool) (void)hipFree(I->d_tpt_pool);
-                if (I->d_tpt_flags) (void)hipFree(I->d_tpt_flags);
-                I->d_tpt_pool = nullptr; I->d_tpt_flags = nullptr; I->tpt_pool_bytes = 0;
-                if (hipMalloc((void**)&I->d_tpt_pool, need) == hipSuccess && hipMalloc((void**)&I->d_tpt_flags, nslots * 4u) == hipSuccess) {
-                    /* on the LAUNCH stream: it does not synchronise with the null stream (hipStreamNonBlocking), and a hipMemset of device memory may
-                     * return before it has run -- cleared there, the flags could still be garbage when the first waves take their slots, or be
-                     * zeroed under a wave that holds one, and two tiles would share a slot (seen as an occasional wrong first frame of a deep
-                     * launch whose tiles all enter the tail at once, clw_ext_set_tpt(64)) */
-                    HIP_OK(hipMemsetAsync(I->d_tpt_flags, 0, nslots * 4u, I->stream), "Couldn't allocate device memory");
-                    I->tpt_pool_bytes = need;
-                } else {                                /* no room: the launch runs without the tail */
-                    (void)hipGetLastError();
-                    if (I->d_tpt_pool) (void)hipFree(I->d_tpt_pool);
-                    I->d_tpt_pool = nullptr;
-                }
-            }
-            if (I->tpt_pool_bytes) {
-                P.tpt_pool = I->d_tpt_pool; P.tpt_flags = I->d_tpt_flags; P.tpt_slice_words = (uint32_t)slice; P.tpt_cap = (uint32_t)cap;
-                P.tpt_slots = TPT_SLOTS_PER_XCC; P.tpt_jump = I->d_tpt_jump;
-                P.tpt_max = std::min(I->tpt_max, 64u); P.tpt_min = I->tpt_min;
-            }
-        }
+    if (I->tpt_pool_bytes) { P.tpt_pool = I->d_tpt_pool; P.tpt_flags = I->d_tpt_flags; P.tpt_jump = I->d_tpt_jump; }
+    else P.tpt_slice_words = P.tpt_cap = P.tpt_slots = P.tpt_max = P.tpt_min = 0u;
+}
+
+/* behind the launch: when asked, sort this frame's costs on the side stream; then the cost buffers swap */
+void sort_tile_costs(Impl* I, Impl::Sched& S, const wt_plan_out& plan, bool rebuild) {
+    const int wr = S.o.wr;
+    if (rebuild) {
+        if (!I->sched_stream) HIP_OK(hipStreamCreateWithFlags(&I->sched_stream, hipStreamNonBlocking), "Couldn't create a command queue for the given device");
+        HIP_OK(hipEventRecord(S.traced, I->stream), "Couldn't run the kernel");
+        HIP_OK(hipStreamWaitEvent(I->sched_stream, S.traced, 0), "Couldn't run the kernel");
+        if (wt_fast_launch_sched(S.cost[wr], S.order[wr], plan.tpr, plan.trows, plan.per_share, (plan.flags & WT_F_GRID) ? 1u : 0u, plan.per_share_cap,
+                                 plan.split ? I->split_slots : 0u, I->split_min_quota, plan.split_max_lg, I->sched_stream) != hipSuccess)
+            die("Couldn't run the kernel");
+        HIP_OK(hipEventRecord(S.built[wr], I->sched_stream), "Couldn't run the kernel");
     }
+    wt_order_launched(&S.o, rebuild);
+}
+
+/* One trace launch: the plan (launch_plan.c decides everything that needs no device), then its effects in stream order.
+ * -> whether a kernel was launched (an empty range launches none) */
+bool trace_launch(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Strip* strip, TracePass pass) {
+    Buffer* rays = rays_of(w, I, kid);
+    const uint32_t total = total_of(I->kernels[kid]);
+    Buffer* out = buffer_arg(w, kid, 10);
+    ensure_allocated(I, out);
+    if (wt_plan_range(array_size, total, out->size) == 0) return false;      /* before the scene is looked at */
+    prepare_bound_scene(w, I, kid);
+
+    wt_plan_in in;
+    wt_plan_out plan;      /* (not cleared: the planner writes the head, and the tables only for a launch that uses them) */
+    plan_input(I, rays, array_size, total, out->size, strip, pass, in);
+    wt_plan(&in, &plan);
+    if (plan.status == WT_PLAN_REFUSED) die("%s", plan.message);
+    if (plan.samples_decided) keep_samples(I, plan);
+    if (plan.status == WT_PLAN_NONE) return false;
+
+    Impl::Sched& S = I->scheds[strip ? strip->slot : 0];
+    bind_buffers(w, I, kid, rays, out, plan);
+    bind_tables(I, plan);
+    bind_accumulation(I, plan);
+    bind_counters(I, plan);
+    bool sort = false;
+    if (pass == PASS_REFINE) classify_blocks(I, plan);
+    else if (plan.P.tiled) sort = bind_tile_order(I, S, plan, strip);
+    I->last_trace_flags = plan.flags;
+    bind_tail_pool(I, plan);
     LaunchTimer t(I, kid, pass == PASS_PLAIN);      /* (an adaptive launch is timed as one: run_raytracer) */
-    hipError_t e = I->strict ? wt_strict_launch_trace(&P, flags, grid, dyn_lds, I->stream)
-                             : wt_fast_launch_trace(&P, flags, grid, dyn_lds, I->stream);
+    hipError_t e = (I->strict ? wt_strict_launch_trace : wt_fast_launch_trace)(&plan.P, plan.flags, plan.grid, plan.dyn_lds, I->stream);
     if (e != hipSuccess) die("Couldn't run the kernel");
     t.done();
-    if (P.tile_cost) {
-        const int wr = S.wr;
-        if (sched_rebuild) {   /* sort this frame's costs behind it, on the side stream */
-            if (!I->sched_stream) HIP_OK(hipStreamCreateWithFlags(&I->sched_stream, hipStreamNonBlocking), "Couldn't create a command queue for the given device");
-            HIP_OK(hipEventRecord(S.traced, I->stream), "Couldn't run the kernel");
-            HIP_OK(hipStreamWaitEvent(I->sched_stream, S.traced, 0), "Couldn't run the kernel");
-            if (wt_fast_launch_sched(S.cost[wr], S.order[wr], tpr, trows, per_share, (flags & F_GRID) ? 1u : 0u, per_share_cap,
-                                     split ? I->split_slots : 0u, I->split_min_quota, split_max_lg, I->sched_stream) != hipSuccess)
-                die("Couldn't run the kernel");
-            HIP_OK(hipEventRecord(S.built[wr], I->sched_stream), "Couldn't run the kernel");
-            S.have[wr] = true; S.newest = wr; S.newest_frame = S.frame - 1;
-        }
-        S.wr = wr ^ 1;
-    }
+    if (plan.P.tile_cost) sort_tile_costs(I, S, plan, sort);
     return true;
 }
 
-Buffer* rays_of(cl_wrap* w, Impl* I, cl_uint kid) {
-    Kernel& k = I->kernels[kid];
-    if (is_registered(w, kid, 0)) return (Buffer*)w->buffers[kid][0];
-    const ArgValue& v = need_value(k, 0, sizeof(cl_mem), sizeof(cl_mem));
-    void* h; memcpy(&h, v.bytes, sizeof h);
-    Buffer* rays = lookup_handle(I, h);
-    if (!rays) die("Couldn't run the kernel");
-    return rays;
+/* what the sampling modes do not combine with (wt_plan_mode_check); `rays` only matters to an accumulated launch */
+void check_modes(const Impl* I, const Buffer* rays, bool accumulating) {
+    wt_plan_in in{};
+    char message[200];
+    in.fuse = I->fuse; in.supersample = I->supersample; in.adaptive = I->adaptive; in.aperture = I->aperture;
+    in.n_cams = (uint32_t)I->cams.size(); in.n_disp = (uint32_t)I->motion_disp.size();
+    if (rays) { in.rays_generated = rays->gen_valid; in.rays_exposed = rays->exposed; }
+    if (wt_plan_mode_check(&in, accumulating, message)) die("%s", message);
 }
 
 /* A trace launch with progressive accumulation on (hip_wrap_ext.h: clw_ext_set_accumulate): refuses what the mode does not combine with, restarts
@@ -957,19 +854,11 @@ Buffer* rays_of(cl_wrap* w, Impl* I, cl_uint kid) {
 void run_accumulated(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Strip* strip) {
     Kernel& k = I->kernels[kid];
     Buffer* rays = rays_of(w, I, kid);
-    /* the shim must own the camera: it moves it by a sub-pixel per frame, and the seeds are the frame's */
-    if (!(I->fuse && rays->gen_valid && !rays->exposed))
-        die("Frame accumulation needs the fused raygen + trace launch (CLWRAP_FUSE=1, rays generated by this library and not rewritten)");
-    /* per-frame decorrelated lens and time samples are not built: a frame of these would repeat its lens points and times for ever */
-    if (!I->cams.empty()) die("Frame accumulation does not combine with a table of sample cameras (clw_ext_set_sample_cameras)");
-    if (I->aperture > 0.0f) die("Frame accumulation does not combine with a lens (clw_ext_set_lens)");
-    if (!I->motion_disp.empty()) die("Frame accumulation does not combine with moving spheres (clw_ext_set_sphere_motion)");
-    if (I->adaptive >= 0) die("Frame accumulation does not combine with adaptive supersampling (clw_ext_set_adaptive)");
+    check_modes(I, rays, true);
     Impl::Accum& A = I->acc;
     Impl::AccKey key;
     key.gen = rays->gen;
-    uint32_t total; memcpy(&total, need_value(k, 7, 4, 4).bytes, 4);
-    key.total = total; key.n_out = (uint64_t)array_size;
+    key.total = total_of(k); key.n_out = (uint64_t)array_size;
     key.depth = I->depth; key.strict = I->strict; key.fuse = I->fuse; key.ss = I->supersample; key.max_frames = I->acc_max; key.jitter = I->acc_jitter;
     key.through = I->through; key.seed = I->seed_offset;
     const cl_uint args[6] = {1, 2, 3, 8, 9, 10};
@@ -992,12 +881,8 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
     if (I->acc_max > 0) { run_accumulated(w, I, kid, array_size, strip); return; }
     I->acc.key_valid = false;      /* a launch outside the mode: the next accumulated one starts at frame 0 */
     if (I->adaptive < 0) { trace_launch(w, I, kid, array_size, strip, PASS_PLAIN); return; }
-    /* Adaptive supersampling (hip_wrap_ext.h: clw_ext_set_adaptive).  Per-sample cameras and moving spheres change every pixel of the frame, so
-     * the contrast of a 1-sample frame says nothing about where their samples matter: refused. */
-    if (I->supersample == 1) die("Adaptive supersampling needs samples: threshold %d with supersampling factor 1 (clw_ext_set_supersample / CLWRAP_SUPERSAMPLE)", I->adaptive);
-    if (I->aperture > 0.0f) die("Adaptive supersampling does not combine with a lens (clw_ext_set_lens): every pixel of such a frame needs its samples");
-    if (!I->cams.empty()) die("Adaptive supersampling does not combine with a table of sample cameras (clw_ext_set_sample_cameras): every pixel of such a frame needs its samples");
-    if (!I->motion_disp.empty()) die("Adaptive supersampling does not combine with moving spheres (clw_ext_set_sphere_motion): every pixel of such a frame needs its samples");
+    /* Adaptive supersampling (hip_wrap_ext.h: clw_ext_set_adaptive): a 1-sample base pass, the classifier and a supersampled pass over the blocks it listed */
+    check_modes(I, nullptr, false);
     LaunchTimer t(I, kid);
     trace_launch(w, I, kid, array_size, strip, PASS_BASE);
     trace_launch(w, I, kid, array_size, strip, PASS_REFINE);
@@ -1010,17 +895,14 @@ void run_raytracer(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const St
  * Returns false when the call is not of that shape; the caller then takes the plain path. */
 bool pipelined_output(cl_wrap* w, Impl* I, size_t array_size, size_t output_size, cl_uint kid, cl_uint out_kernel,
                       cl_int out_arg, void* host_output) {
-    if (!I->pipeline || I->async || !host_output || !I->fuse || I->counting || I->debug_rgb || (I->variant & 2)) return false;
+    if (!I->pipeline || I->async || !host_output || !I->fuse || I->counting || I->debug_rgb || (I->variant & WT_V_LINEAR_IDS)) return false;
     if (I->acc_max > 0) return false;        /* an accumulated view is one launch per frame, or none at all once it has converged */
     if (I->adaptive >= 0) return false;      /* a strip's edge rows would be classified without their neighbours in the next strip: another frame */
     if (out_kernel != kid || out_arg != 10 || !is_registered(w, kid, 10)) return false;
-    Kernel& k = I->kernels[kid];
-    Buffer* rays = nullptr;
-    if (is_registered(w, kid, 0)) rays = (Buffer*)w->buffers[kid][0];
-    else if (k.values[0].set && k.values[0].size == sizeof(cl_mem)) { void* h; memcpy(&h, k.values[0].bytes, sizeof h); rays = lookup_handle(I, h); }
-    if (!rays || !rays->gen_valid || rays->exposed || !k.values[7].set || k.values[7].size != 4) return false;
+    Buffer* rays = find_rays(w, I, kid);
+    uint32_t total;
+    if (!rays || !rays->gen_valid || rays->exposed || !find_total(I->kernels[kid], total)) return false;
     const RaygenArgs& g = rays->gen;
-    uint32_t total; memcpy(&total, k.values[7].bytes, 4);
     Buffer* out = (Buffer*)w->buffers[kid][10];
     const uint64_t n = g.n_items;
     if (g.band_stride > 1 || g.id_offset % g.width != 0 || n % g.width != 0) return false;
@@ -1029,7 +911,7 @@ bool pipelined_output(cl_wrap* w, Impl* I, size_t array_size, size_t output_size
     /* worth it only when the copy is long and the launch is throughput-bound: measured 1.06 -> 0.745 ms at 3840x2160
      * depth 4, +3 % at 1920x1080 (four 2 MB copies are no faster than one of 8 MB), and a LOSS for deep launches,
      * where every strip would pay its own serial tail of refraction trees (0.76 -> 1.30 ms at 1280x1024 depth 15) */
-    if (n * 4 < (16u << 20) || rows < 4 * 64 || I->depth > SHALLOW_LEVELS + 1) return false;
+    if (n * 4 < (16u << 20) || rows < 4 * 64 || I->depth > WT_SHALLOW_LEVELS + 1) return false;
     ensure_allocated(I, out);
 
     const int nch = Impl::MAX_CHUNKS;
@@ -1081,34 +963,23 @@ bool gbuffer_params(cl_wrap* w, Impl* I, whitted_params& P, int& flags, size_t& 
     while (kid < I->kernels.size() && I->kernels[kid].kind != K_RAYTRACER) kid++;
     if (kid >= I->kernels.size()) return false;
     const Kernel& k = I->kernels[kid];
-    Buffer* rays = nullptr;
-    if (is_registered(w, kid, 0)) rays = (Buffer*)w->buffers[kid][0];
-    else if (k.values[0].set && k.values[0].size == sizeof(cl_mem)) { void* h; memcpy(&h, k.values[0].bytes, sizeof h); rays = lookup_handle(I, h); }
+    Buffer* rays = find_rays(w, I, kid);
     if (!rays || !rays->gen_valid) return false;
     for (cl_uint a : {1u, 2u, 3u, 8u, 9u}) if (!is_registered(w, kid, a)) return false;
     for (cl_uint a : {4u, 5u, 6u}) if (!k.values[a].set) return false;
-    if (!k.values[7].set || k.values[7].size != 4) return false;
-    uint32_t total; memcpy(&total, k.values[7].bytes, 4);
+    uint32_t total;
+    if (!find_total(k, total)) return false;
     const RaygenArgs& g = rays->gen;
     const uint32_t n = g.n_items < total ? g.n_items : total;
     if (n == 0) return false;
     bind_scene(w, I, kid, P, flags, dyn_lds);
-    memcpy(P.corner, g.corner, 12); memcpy(P.origin, g.origin, 12); memcpy(P.up, g.up, 12); memcpy(P.right, g.right, 12);
-    P.w_factor = g.w_factor; P.h_factor = g.h_factor; P.width = g.width; P.height = g.height;
-    P.id_offset = g.id_offset; P.n_items = n;
-    P.band_stride = g.band_stride; P.band_phase = g.band_phase;
-    P.tiled = ((g.id_offset % g.width == 0 || g.band_stride > 1) && n % g.width == 0) ? 1u : 0u;
-    P.rows = n / g.width;
-    P.row_offset = (uint32_t)(g.id_offset / g.width);
-    P.unit_dirs = P.ns <= GRID_MIN_SPHERES ? 1u : 0u;      /* as the fused trace launch: the rays are this library's own */
+    wt_plan_fused_range(&g, n, &P);      /* as the fused trace launch: the rays are this library's own */
     P.vis = 0;
     return true;
 }
 
 void launch_gbuffer(Impl* I, const whitted_params& P, int flags, size_t dyn_lds, void* const chan[5], bool timed) {
-    unsigned grid;
-    if (P.tiled) grid = 8u * (((P.rows + 7u) / 8u + 7u) / 8u) * ((P.width + 7u) / 8u);      /* as trace_launch: tile rows dealt to the 8 XCDs */
-    else grid = (P.n_items + TRACE_BLOCK - 1) / TRACE_BLOCK;
+    const unsigned grid = wt_plan_grid(&P);      /* as trace_launch: tile rows dealt to the 8 XCDs */
     LaunchTimer t(I, CLW_TIMING_GBUFFER, timed);
     hipError_t e = (I->strict ? wt_strict_launch_gbuffer : wt_fast_launch_gbuffer)(&P, flags, grid, dyn_lds, (float*)chan[0], (unsigned*)chan[1], (float*)chan[2],
                                                                                    (float*)chan[3], (float*)chan[4], I->stream);
@@ -1197,13 +1068,13 @@ void cl_wrap_init(cl_wrap* wrap, cl_device_type type, ...) {
     if (!(I->focus > 0.0f) || !std::isfinite(I->focus)) die("CLWRAP_FOCUS (lens focus distance) must be a finite number > 0");
     I->stamps = env_int("CLWRAP_STAMPS", 0) ? 1 : 0;
     if (const char* th = getenv("CLWRAP_THROUGH")) { if (*th) I->through = (float)atof(th); }
-    I->occ_tiles_per_depth = (unsigned)env_int("CLWRAP_OCC_TILES_PER_DEPTH", (int)OCC_TILES_PER_DEPTH);
-    I->tpt_max = (unsigned)env_int("CLWRAP_TPT_MAX", (int)TPT_MAX_LANES);
-    I->tpt_min = (unsigned)env_int("CLWRAP_TPT_MIN", (int)TPT_MIN_PATHS);
-    I->tpt_pool_mb = (unsigned)env_int("CLWRAP_TPT_POOL_MB", (int)TPT_POOL_MB);
-    I->split_min_quota = (unsigned)env_int("CLWRAP_SPLIT_MIN_QUOTA", (int)SPLIT_MIN_QUOTA);
+    I->occ_tiles_per_depth = (unsigned)env_int("CLWRAP_OCC_TILES_PER_DEPTH", (int)WT_OCC_TILES_PER_DEPTH);
+    I->tpt_max = (unsigned)env_int("CLWRAP_TPT_MAX", (int)WT_TPT_MAX_LANES);
+    I->tpt_min = (unsigned)env_int("CLWRAP_TPT_MIN", (int)WT_TPT_MIN_PATHS);
+    I->tpt_pool_mb = (unsigned)env_int("CLWRAP_TPT_POOL_MB", (int)WT_TPT_POOL_MB);
+    I->split_min_quota = (unsigned)env_int("CLWRAP_SPLIT_MIN_QUOTA", (int)WT_SPLIT_MIN_QUOTA);
     I->tpt_clock = env_int("CLWRAP_TPT_CLOCK", 0) ? 1 : 0;
-    I->split_slots = (unsigned)std::max(1, env_int("CLWRAP_SPLIT_SLOTS", (int)SPLIT_SLOTS));
+    I->split_slots = (unsigned)std::max(1, env_int("CLWRAP_SPLIT_SLOTS", (int)WT_SPLIT_SLOTS));
 
     wrap->impl = I;
     wrap->kernels_num = (cl_uint)I->kernels.size();
@@ -1429,7 +1300,7 @@ uint32_t clw_ext_read_tile_costs(cl_wrap* wrap, uint32_t* out, uint32_t capacity
     const Impl::Sched& S = I->scheds[0];
     if (!S.cost[0]) return 0;
     uint32_t n = ((S.rows + 7) / 8) * ((S.w + 7) / 8);
-    if (out && capacity >= n) HIP_OK(hipMemcpy(out, S.cost[S.wr ^ 1], (size_t)n * 4, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
+    if (out && capacity >= n) HIP_OK(hipMemcpy(out, S.cost[S.o.wr ^ 1], (size_t)n * 4, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
     return n;
 }
 uint32_t clw_ext_read_tile_order(cl_wrap* wrap, uint32_t* out, uint32_t capacity, uint32_t* per_share_cap) {
@@ -1480,7 +1351,7 @@ void clw_ext_get_split(const cl_wrap* wrap, uint32_t* slots, uint32_t* min_quota
     const Impl* I = impl_of(wrap);
     if (slots) *slots = I->split_slots;
     if (min_quota) *min_quota = I->split_min_quota;
-    if (extra_per_share) *extra_per_share = SPLIT_EXTRA_PER_SHARE;
+    if (extra_per_share) *extra_per_share = WT_SPLIT_EXTRA_PER_SHARE;
 }
 void clw_ext_set_shadow_through(cl_wrap* wrap, float factor) { impl_of(wrap)->through = factor; }
 void clw_ext_set_grid(cl_wrap* wrap, int on) { impl_of(wrap)->use_grid = on ? 1 : 0; }

@@ -11,28 +11,27 @@ static hipError_t wt_launch_one(const whitted_params* P, unsigned grid, size_t d
     return hipGetLastError();
 }
 
-extern "C" hipError_t WT_LAUNCH_TRACE(const whitted_params* P, int flags, unsigned grid, size_t dyn_lds,
-                                      hipStream_t s) {
-    using WT_NS::WT_F_SS; using WT_NS::WT_F_MOVE; using WT_NS::WT_F_LIST; using WT_NS::WT_F_ACC;
+/* the compiled trace kernel of a flag word, or null: the shaped flavours by their exact word, the others by the bits that select a kernel */
+typedef hipError_t (*wt_trace_launcher)(const whitted_params*, unsigned, size_t, hipStream_t);
+static wt_trace_launcher wt_find_trace(int flags) {
 #if !WT_STRICT
-    using WT_NS::WT_F_GEOM_LDS; using WT_NS::WT_F_SHAPE;
     if (flags & WT_F_SHAPE) {
-        /* the shaped flavour (wt_shape): exactly these counts are compiled -- 1..4 spheres, 0..2 planes, 3 lights; the shim asks for no other */
+        /* the shaped flavour (wt_shape): exactly these counts are compiled -- 1..4 spheres, 0..2 planes, 3 lights; the planner asks for no other */
         switch (flags) {
-#define WT_SHAPE_CASE(ns, np) case WT_SHAPE_FLAGS(ns, np, 3): return wt_launch_one<WT_SHAPE_FLAGS(ns, np, 3)>(P, grid, dyn_lds, s); \
-                              case WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS: return wt_launch_one<WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS>(P, grid, dyn_lds, s); \
-                              case WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS | WT_F_LIST: return wt_launch_one<WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS | WT_F_LIST>(P, grid, dyn_lds, s); \
-                              case WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS | WT_F_MOVE: return wt_launch_one<WT_SHAPE_FLAGS(ns, np, 3) | WT_F_SS | WT_F_MOVE>(P, grid, dyn_lds, s);
+#define WT_SHAPE_CASE(ns, np) case WT_SHAPE_FLAGS(ns, np, WT_SHAPE_LIGHTS): return wt_launch_one<WT_SHAPE_FLAGS(ns, np, WT_SHAPE_LIGHTS)>; \
+                              case WT_SHAPE_FLAGS(ns, np, WT_SHAPE_LIGHTS) | WT_F_SS: return wt_launch_one<WT_SHAPE_FLAGS(ns, np, WT_SHAPE_LIGHTS) | WT_F_SS>; \
+                              case WT_SHAPE_FLAGS(ns, np, WT_SHAPE_LIGHTS) | WT_F_SS | WT_F_LIST: return wt_launch_one<WT_SHAPE_FLAGS(ns, np, WT_SHAPE_LIGHTS) | WT_F_SS | WT_F_LIST>; \
+                              case WT_SHAPE_FLAGS(ns, np, WT_SHAPE_LIGHTS) | WT_F_SS | WT_F_MOVE: return wt_launch_one<WT_SHAPE_FLAGS(ns, np, WT_SHAPE_LIGHTS) | WT_F_SS | WT_F_MOVE>;
 #define WT_SHAPE_CASES(ns) WT_SHAPE_CASE(ns, 0) WT_SHAPE_CASE(ns, 1) WT_SHAPE_CASE(ns, 2)
             WT_SHAPE_CASES(1) WT_SHAPE_CASES(2) WT_SHAPE_CASES(3) WT_SHAPE_CASES(4)
 #undef WT_SHAPE_CASES
 #undef WT_SHAPE_CASE
         }
-        return hipErrorInvalidValue;
+        return nullptr;
     }
 #endif
     switch (flags & (255 | WT_F_SS | WT_F_MOVE | WT_F_LIST | WT_F_ACC)) {
-#define WT_CASE(F) case F: return wt_launch_one<F>(P, grid, dyn_lds, s);
+#define WT_CASE(F) case F: return wt_launch_one<F>;
 /* F, its supersampled twin (fused launches only: no twin for the ray-buffer flavours, bit 3) and the twin's list-driven flavour (adaptive launches) */
 #define WT_CASE2(F) WT_CASE(F) WT_CASE((F) | WT_F_SS) WT_CASE((F) | WT_F_SS | WT_F_LIST)
 /* ... and the twin's moving-spheres flavour (not the grid builds) */
@@ -60,8 +59,22 @@ extern "C" hipError_t WT_LAUNCH_TRACE(const whitted_params* P, int flags, unsign
 #undef WT_CASE2
 #undef WT_CASE
     }
-    return hipErrorInvalidValue;
+    return nullptr;
 }
+
+extern "C" hipError_t WT_LAUNCH_TRACE(const whitted_params* P, int flags, unsigned grid, size_t dyn_lds,
+                                      hipStream_t s) {
+    const wt_trace_launcher run = wt_find_trace(flags);
+    return run ? run(P, grid, dyn_lds, s) : hipErrorInvalidValue;
+}
+
+/* whether this build compiled a trace kernel for the flag word (csrc/launch_plan.h: the planner's tests hold every word it returns to it) */
+#if WT_STRICT
+#define WT_HAS_TRACE wt_strict_has_trace
+#else
+#define WT_HAS_TRACE wt_fast_has_trace
+#endif
+extern "C" int WT_HAS_TRACE(int flags) { return wt_find_trace(flags) != nullptr; }
 
 extern "C" hipError_t WT_LAUNCH_RAYGEN(const raygen_params* P, hipStream_t s) {
     unsigned grid = (P->n_items + WT_RG_BLOCK - 1) / WT_RG_BLOCK;
@@ -104,13 +117,13 @@ extern "C" hipError_t WT_LAUNCH_UNIT(int op, const float* in, float* out, unsign
 extern "C" hipError_t WT_LAUNCH_UNIT_SCENE(const whitted_params* P, int flags, int op, const float* in, float* out, unsigned n,
                                            unsigned stride_in, unsigned stride_out, size_t dyn_lds, hipStream_t s) {
     const dim3 grid((n + 63) / 64), block(64);
-    if (flags & 16) hipLaunchKernelGGL((WT_NS::wt_unit_scene<false, true>), grid, block, 0, s, *P, op, in, out, n, stride_in, stride_out);
-    else if (flags & 4) hipLaunchKernelGGL((WT_NS::wt_unit_scene<true, false>), grid, block, dyn_lds, s, *P, op, in, out, n, stride_in, stride_out);
+    if (flags & WT_F_GRID) hipLaunchKernelGGL((WT_NS::wt_unit_scene<false, true>), grid, block, 0, s, *P, op, in, out, n, stride_in, stride_out);
+    else if (flags & WT_F_GEOM_LDS) hipLaunchKernelGGL((WT_NS::wt_unit_scene<true, false>), grid, block, dyn_lds, s, *P, op, in, out, n, stride_in, stride_out);
     else hipLaunchKernelGGL((WT_NS::wt_unit_scene<false, false>), grid, block, 0, s, *P, op, in, out, n, stride_in, stride_out);
     return hipGetLastError();
 }
 
-/* the primary-hit pass (whitted_gbuffer.inc): geometry as bind_scene chose it -- flags & 16 the uniform grid, & 4 the scene staged in LDS, else
+/* the primary-hit pass (whitted_gbuffer.inc): geometry as bind_scene chose it -- WT_F_GRID the uniform grid, WT_F_GEOM_LDS the scene staged in LDS, else
  * read from global memory; the five channel pointers in CLW_GB_* bit order, NULL = not written */
 #if WT_STRICT
 #define WT_LAUNCH_GBUFFER wt_strict_launch_gbuffer
@@ -121,8 +134,8 @@ extern "C" hipError_t WT_LAUNCH_GBUFFER(const whitted_params* P, int flags, unsi
                                         float* normal, float* point, float* albedo, hipStream_t s) {
     const WT_NS::wt_gbuffer_out G = {depth, id, normal, point, albedo};
     const dim3 g(grid), block(WT_BLOCK);
-    if (flags & 16) hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, true>), g, block, 0, s, *P, G);
-    else if (flags & 4) hipLaunchKernelGGL((WT_NS::wt_gbuffer<true, false>), g, block, dyn_lds, s, *P, G);
+    if (flags & WT_F_GRID) hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, true>), g, block, 0, s, *P, G);
+    else if (flags & WT_F_GEOM_LDS) hipLaunchKernelGGL((WT_NS::wt_gbuffer<true, false>), g, block, dyn_lds, s, *P, G);
     else hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, false>), g, block, 0, s, *P, G);
     return hipGetLastError();
 }

@@ -25,6 +25,32 @@
 #define CLW_NUM_COUNTERS 32
 #define CLW_STAMP_SHARDS 1024 /* diagnostic stamp build: 16-word shards behind the counter block, summed into words 16.. on read */ /* words of the device counter block (hip_wrap_ext.h: clw_ext_read_counters_ex); 16.. = phase stamps of the diagnostic build */
 
+/* ---- the launch vocabulary: which compiled trace kernel a launch runs (the FLAGS of wt_trace<FLAGS>; clw_ext_last_trace_flags) -------- */
+#define WT_BLOCK 64                  /* one wavefront = one 8x8 tile = one workgroup: a finished tile frees its
+                                        LDS and wave slot at once instead of waiting for three neighbours      */
+#ifndef WT_VIS_MAX_SPHERES
+#define WT_VIS_MAX_SPHERES 16        /* the light visibility classes (wt_light_vis) cost one pass over the spheres per light chunk: small scenes only */
+#endif
+enum { WT_F_COUNT = 1, WT_F_DEEP = 2, WT_F_GEOM_LDS = 4, WT_F_RAYS = 8, WT_F_GRID = 16,
+       WT_F_OCC = 32 /* deep builds only: the high-occupancy flavour (see WT_LDS_LEVELS of whitted_trace.inc) */,
+       WT_F_D8 = 64, WT_F_D16 = 128 /* deep builds only: the launch's depth is <= 8 / <= 16, so the DFS stack holds at most 7 / 15 parents and the
+                                       part of it kept in scratch is sized for that instead of for CLW_MAX_DEPTH */,
+       WT_F_SHAPE = 256 /* shallow fast LDS-geometry build only: the scene's counts are compiled in (wt_shape) */,
+       WT_F_SS = 1 << 17 /* n x n supersampling, fused tiled launches only (bits 9-16: the counts of WT_SHAPE_FLAGS) */,
+       WT_F_MOVE = 1 << 18 /* on top of WT_F_SS, not the grid builds: moving spheres (wt_sphere_at) -- a flavour of its own, so that the plain
+                              supersampled kernels are the code they were */,
+       WT_F_LIST = 1 << 19 /* on top of WT_F_SS, not with WT_F_MOVE: the refine pass of an adaptive launch -- a wave first asks the device-side length of
+                              its list (list_count below) whether it has a tile at all; again a flavour of its own */,
+       WT_F_ACC = 1 << 20 /* the seed offset and progressive accumulation (seed_offset, acc_sum below) are one more scalar word and a wave-uniform
+                              run-time branch of the epilogue in every flavour but the few whose register allocation they disturbed (wt_acc_flagged:
+                              the strict build's shallow counting and grid kernels, which sit on their 128-VGPR cap): those read neither unless
+                              they are this twin, so that they are the code they were; the planner asks for the twin when the launch has a seed
+                              offset or accumulates */ };
+/* the shaped flavour (wt_shape of whitted_trace.inc) carries the scene's counts in bits 9-11, 12-13 and 14-16; exactly these counts are
+ * compiled (whitted_launch.inc) and asked for (launch_plan.c): 1..WT_SHAPE_MAX_SPHERES spheres, 0..WT_SHAPE_MAX_PLANES planes, WT_SHAPE_LIGHTS lights */
+#define WT_SHAPE_FLAGS(ns, np, nl) (WT_F_GEOM_LDS | WT_F_SHAPE | ((ns) << 9) | ((np) << 12) | ((nl) << 14))
+enum { WT_SHAPE_MAX_SPHERES = 4, WT_SHAPE_MAX_PLANES = 2, WT_SHAPE_LIGHTS = 3 };
+
 typedef struct {
     /* camera: the eight by-value raygen arguments (reference raygen.cl:5-8) */
     float corner[3], origin[3], up[3], right[3];

@@ -93,8 +93,6 @@
 #define WT_CULL_MIN_SPHERES 16u         /* deep builds: from this many spheres on a wave's shadow batch first asks which spheres its rays can meet (wt_sphere_candidates) */
 #endif
 #define WT_TPT_MAX_BATCHES 1022      /* batches of <= 64 nodes the tree-parallel tail can hold (whitted_tpt.inc) */
-#define WT_BLOCK 64                  /* one wavefront = one 8x8 tile = one workgroup: a finished tile frees its
-                                        LDS and wave slot at once instead of waiting for three neighbours      */
 
 /* ---- in-kernel stamps (DIAGNOSTIC build only: -DWT_STAMPS=1, library tag _stamp, tools/stamp_phases.py) ------------
  * s_memtime at the phase boundaries of the per-lane loop, differences summed per phase in scalar registers and added
@@ -675,21 +673,7 @@ __device__ __forceinline__ float4 wt_sphere_at(const whitted_params& P, const fl
 }
 
 
-enum { WT_F_COUNT = 1, WT_F_DEEP = 2, WT_F_GEOM_LDS = 4, WT_F_RAYS = 8, WT_F_GRID = 16,
-       WT_F_OCC = 32 /* deep builds only: the high-occupancy flavour (see WT_LDS_LEVELS above) */,
-       WT_F_D8 = 64, WT_F_D16 = 128 /* deep builds only: the launch's depth is <= 8 / <= 16, so the DFS stack holds at most 7 / 15 parents and the
-                                       part of it kept in scratch is sized for that instead of for CLW_MAX_DEPTH */,
-       WT_F_SHAPE = 256 /* shallow fast LDS-geometry build only: the scene's counts are compiled in (wt_shape) */,
-       WT_F_SS = 1 << 17 /* n x n supersampling, fused tiled launches only (bits 9-16: the counts of WT_SHAPE_FLAGS) */,
-       WT_F_MOVE = 1 << 18 /* on top of WT_F_SS, not the grid builds: moving spheres (wt_sphere_at) -- a flavour of its own, so that the plain
-                              supersampled kernels are the code they were */,
-       WT_F_LIST = 1 << 19 /* on top of WT_F_SS, not with WT_F_MOVE: the refine pass of an adaptive launch -- a wave first asks the device-side length of
-                              its list (whitted_params.h: list_count) whether it has a tile at all; again a flavour of its own */,
-       WT_F_ACC = 1 << 20 /* the seed offset and progressive accumulation (whitted_params.h: seed_offset, acc_sum) are one more scalar word and a wave-uniform
-                              run-time branch of the epilogue in every flavour but the few whose register allocation they disturbed (wt_acc_flagged:
-                              the strict build's shallow counting and grid kernels, which sit on their 128-VGPR cap): those read neither unless
-                              they are this twin, so that they are the code they were; the shim asks for the twin when the launch has a seed
-                              offset or accumulates */ };
+/* (the WT_F_* flags of FLAGS and WT_SHAPE_FLAGS: whitted_params.h) */
 /* the flavours that take the seed offset and the accumulation branch only as their WT_F_ACC twin (tools/kernel_stats.py against the parent:
  * profiles/r10_ab_experiments.txt) */
 constexpr bool wt_acc_flagged(int flags) { return WT_STRICT != 0 && (flags & WT_F_DEEP) == 0 && (flags & (WT_F_COUNT | WT_F_GRID)) != 0; }
@@ -699,8 +683,7 @@ constexpr bool wt_acc_flagged(int flags) { return WT_STRICT != 0 && (flags & WT_
  * The shaped flavour carries ns, np and nl in FLAGS bits 9-11, 12-13 and 14-16: every sphere, plane and light loop of the hot path
  * unrolls, the geometry offsets and the early-out ballots' positions become constants, and the side-table branch folds (the shim
  * launches it only when the light / plane side table is on or there are no planes).  Same operations in the same order: the frame is
- * the generic kernel's, bit for bit.  (WT_SHAPE_FLAGS: hip_wrap.cpp picks the kernel from the prepared scene.) */
-#define WT_SHAPE_FLAGS(ns, np, nl) (WT_F_GEOM_LDS | WT_F_SHAPE | ((ns) << 9) | ((np) << 12) | ((nl) << 14))
+ * the generic kernel's, bit for bit.  (WT_SHAPE_FLAGS of whitted_params.h: launch_plan.c picks the kernel from the prepared scene.) */
 template <int FLAGS>
 struct wt_shape {
     static constexpr bool on = (FLAGS & WT_F_SHAPE) != 0;
@@ -1062,9 +1045,6 @@ __device__ __forceinline__ void wt_grid_shadow_pair(const whitted_params& P, f3 
  * that meets a NaN or an infinity is false, which makes the sphere PARTIAL: when in doubt the rays are traced.
  * tests/test_gpu_parity.py runs the counting build with P.vis == 2, which classifies AND traces and counts the lights whose
  * traced factors differ from the class's (must be zero). */
-#ifndef WT_VIS_MAX_SPHERES
-#define WT_VIS_MAX_SPHERES 16        /* the classes cost one pass over the spheres per light chunk: small scenes only */
-#endif
 template <bool GEOM_LDS, int LCH>
 __device__ __forceinline__ void wt_light_vis(const whitted_params& P, const float4* sg, unsigned g_pln, unsigned g_lgt, unsigned lb,
                                              f3 ip, const bool (&want)[LCH], unsigned chunk, bool (&known)[LCH], float (&opu)[LCH],

@@ -374,7 +374,7 @@ void clw_ext_unit_scene(cl_wrap* wrap, cl_uint kernel_id, int op, const float* i
  * 512 DIAGNOSTIC builds only (-DWT_TIMELINE=1, tools/timeline.py): the tile-cost buffer receives when each tile's wave ran inside the launch
  * (CLWRAP_TIMELINE_SHIFT = tick of 10 ns << shift; CLWRAP_TIMELINE_EDGES = 1 / 2: its prologue and epilogue instead); no effect otherwise. */
 void clw_ext_set_variant(cl_wrap* wrap, int variant);
-/* The kernel flavour of the latest trace launch: its WT_F_* flags (csrc/whitted_trace.inc; bit 256 = the scene's counts compiled in,
+/* The kernel flavour of the latest trace launch: its WT_F_* flags (csrc/whitted_params.h; bit 256 = the scene's counts compiled in,
  * ns | np << 3 | nl << 5 in bits 9..16), -1 before the first launch.  For tests and A/B runs. */
 int clw_ext_last_trace_flags(cl_wrap* wrap);
 

@@ -1,20 +1,15 @@
 """Shared by test_shape_scenes_host.py, test_gpu_shape_specialised.py and test_gpu_shape_modes.py: the count pairs the shaped trace kernel is
-compiled for, the flag word of each (WT_SHAPE_FLAGS of csrc/whitted_trace.inc, read back with clw_ext_last_trace_flags), and the frame
+compiled for, the flag word of each (WT_SHAPE_FLAGS of csrc/whitted_params.h, read back with clw_ext_last_trace_flags), and the frame
 sizes, depths, factor and threshold at which the twelve scenes of fuzz_scenes.SHAPED_SEEDS are rendered."""
 from conftest import CAM
 from fuzz_scenes import SHAPED_SEEDS, shaped_scene
 
-F_DEEP, F_GEOM_LDS, F_SHAPE, F_SS, F_MOVE, F_LIST = 2, 4, 256, 1 << 17, 1 << 18, 1 << 19      # WT_F_*
+from flags_common import F_DEEP, F_GEOM_LDS, F_SHAPE, F_SS, F_MOVE, F_LIST, shape_flags      # noqa: F401
 V_GENERIC = 8192                        # clw_ext_set_variant: small scenes of the fast build keep the generic kernel
 SHAPES = [(ns, npl) for ns in (1, 2, 3, 4) for npl in (0, 1, 2)]          # x 3 lights: the switch of WT_LAUNCH_TRACE (csrc/whitted_launch.inc)
 FRAME, RAGGED = (72, 48), (61, 43)      # 9 x 6 whole tiles; the smallest size with a partial tile in both directions next to more than one whole one
 DEPTHS = (1, 4)                         # the shaped kernel drops the dead last bounce by depth
 ADAPTIVE = (2, 16)                      # factor and contrast threshold of the adaptive cases (the threshold of test_gpu_adaptive.py)
-
-
-def shape_flags(ns, npl, nl=3):
-    """WT_SHAPE_FLAGS(ns, npl, nl): the shaped flavour stages its geometry in LDS and carries its counts in bits 9.."""
-    return F_GEOM_LDS | F_SHAPE | ns << 9 | npl << 12 | nl << 14
 
 
 def shape_of(flags):

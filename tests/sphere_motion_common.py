@@ -9,7 +9,7 @@ import numpy as np
 from conftest import CAM
 from sample_cameras_common import composed, rows_of, virtual_camera
 
-F_SS = 1 << 17      # WT_F_SS of csrc/whitted_trace.inc (clw_ext_last_trace_flags)
+from flags_common import F_SS      # noqa: F401  (clw_ext_last_trace_flags)
 LENS = (0.2, 8.0)
 CAM2 = dict(origin=(1.6, 3.1, -6.5), look=(0.05, -0.15, 1.0), fov=90.0, focal=1.0)      # the other end of a camera shutter
 

@@ -112,7 +112,7 @@ def test_the_strict_twins_that_carry_the_seed_and_the_sum(R, api, demo_scene, te
     """The strict build's shallow counting and grid kernels read the seed offset and accumulate only as their WT_F_ACC twin (1 << 20): same
     frames as the kernels that carry both unflagged, and no twin while the offset is 0 and the mode off."""
     from example_gui_opencl_raytracer_amd import scene
-    F_COUNT, F_GRID, F_ACC = 1, 16, 1 << 20
+    from flags_common import F_COUNT, F_GRID, F_ACC
     W, H, depth, s = 96, 64, 4, 0x9E3779B1
     cam = base_camera(api, W, H)
     flags = {}

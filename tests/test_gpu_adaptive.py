@@ -13,10 +13,10 @@ import pytest
 
 from adaptive_common import adaptive, check_composite, composite, frames, pixel_mask, resolve, same_floats
 from conftest import CAM, ROOT
+from flags_common import F_DEEP, F_GRID, F_OCC, F_SHAPE, F_SS, F_LIST
 
 pytestmark = pytest.mark.gpu
 
-F_DEEP, F_GRID, F_OCC, F_SHAPE, F_SS, F_LIST = 2, 16, 32, 256, 1 << 17, 1 << 19      # WT_F_* of csrc/whitted_trace.inc (clw_ext_last_trace_flags)
 SHAPES = [(320, 240, 2), (200, 152, 4), (96, 64, 8), (101, 75, 2)]
 COUNTED = ("segments", "shadow_rays", "light_probes", "sky_fetches", "texel_fetches", "pushes")
 

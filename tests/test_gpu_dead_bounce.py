@@ -7,10 +7,10 @@ import numpy as np
 import pytest
 
 from conftest import CAM
+from flags_common import F_COUNT, F_DEEP, F_GEOM_LDS, F_GRID, F_SHAPE
 
 pytestmark = pytest.mark.gpu
 
-F_COUNT, F_DEEP, F_GEOM_LDS, F_GRID, F_SHAPE = 1, 2, 4, 16, 256
 V_GENERIC, V_UNTRIMMED = 8192, 16384
 GLASS_CAM = dict(origin=(3.5, 3.0, -6.0), look=(0.0, -2.5, 9.5), fov=90.0, focal=1.0)
 GRID_CAM = dict(origin=(0.0, 12.0, -10.0), look=(0.0, -0.45, 1.0), fov=90.0, focal=1.0)

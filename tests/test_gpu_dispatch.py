@@ -7,6 +7,7 @@ import pytest
 import sched_common as sc
 from adaptive_common import resolve, same_floats
 from conftest import CAM
+from flags_common import F_COUNT, F_DEEP, F_OCC, F_D8, F_D16
 from parity_common import check_exact
 
 pytestmark = pytest.mark.gpu
@@ -16,7 +17,6 @@ pytestmark = pytest.mark.gpu
 CLOSE_CAM = dict(origin=(0.8, 0.9, -0.6), look=(0.0, -0.05, 1.0), fov=90.0, focal=1.0)
 GLASS_CAM = dict(origin=(3.5, 3.0, -6.0), look=(0.0, -2.5, 9.5), fov=90.0, focal=1.0)
 TAIL_KEYS = ("segments", "shadow_rays", "light_probes", "sky_fetches", "texel_fetches", "pushes", "shadow_rays_traced")
-F_COUNT, F_DEEP, F_OCC, F_D8, F_D16 = 1, 2, 32, 64, 128      # WT_F_* of csrc/whitted_trace.inc (clw_ext_last_trace_flags)
 
 
 @pytest.fixture(scope="module")

@@ -11,11 +11,11 @@ import numpy as np
 import pytest
 
 from conftest import CAM, ROOT
+from flags_common import F_DEEP, F_GRID, F_OCC, F_SHAPE, F_SS
 from sample_cameras_common import CAM2, composed, gpu_composed, make_table, pick, resolve, rows_of, same_floats, sampled, virtual_camera
 
 pytestmark = pytest.mark.gpu
 
-F_DEEP, F_GRID, F_OCC, F_SHAPE, F_SS = 2, 16, 32, 256, 1 << 17      # WT_F_* of csrc/whitted_trace.inc (clw_ext_last_trace_flags)
 LENS = (0.2, 8.0)
 COUNTED = ("segments", "shadow_rays", "light_probes", "sky_fetches", "texel_fetches", "pushes")
 

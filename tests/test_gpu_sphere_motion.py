@@ -11,12 +11,12 @@ import numpy as np
 import pytest
 
 from conftest import CAM, ROOT
+from flags_common import F_DEEP, F_GEOM_LDS, F_GRID, F_OCC, F_SHAPE
 from sample_cameras_common import composed, pick, virtual_camera
 from sphere_motion_common import DISP, F_SS, LENS, camera_table, check_self_consistent, field_disp, gpu_virtual, moved_scene, moving, same_floats
 
 pytestmark = pytest.mark.gpu
 
-F_DEEP, F_GRID, F_OCC, F_SHAPE = 2, 16, 32, 256      # WT_F_* of csrc/whitted_trace.inc (clw_ext_last_trace_flags)
 COUNTED = ("segments", "shadow_rays", "light_probes", "sky_fetches", "texel_fetches", "pushes")
 
 
@@ -83,7 +83,6 @@ def scene_just_over_the_staging_limit():
 def test_a_table_that_does_not_fit_the_staged_16_kib_is_read_from_global_memory(R, api, tex, sky, strict):
     """The 16 KiB staging rule counts the table: the moving launch of this scene runs the kernels that read geometry and displacements from
     global memory, its static launch (and every 1-sample frame it is composed of) the ones that stage the scene in LDS."""
-    F_GEOM_LDS = 4
     sc, disp = scene_just_over_the_staging_limit()
     W, H, n, depth = 96, 64, 2, 4
     flags, _ = check_self_consistent(R, api, sc, tex, sky, W, H, n, depth, strict, disp=disp)

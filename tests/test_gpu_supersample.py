@@ -11,10 +11,10 @@ import numpy as np
 import pytest
 
 from conftest import CAM, ROOT
+from flags_common import F_DEEP, F_GRID, F_OCC, F_SHAPE, F_SS
 
 pytestmark = pytest.mark.gpu
 
-F_DEEP, F_GRID, F_OCC, F_SHAPE, F_SS = 2, 16, 32, 256, 1 << 17      # WT_F_* of csrc/whitted_trace.inc (clw_ext_last_trace_flags)
 
 
 def resolve(rgb, W, H, n):                      # rgb: float32 [n*H * n*W, 3], virtual-frame order
