@@ -35,6 +35,8 @@ tells how many frames the mean holds, ``reset_accumulation()`` starts again.  ``
 ``gbuffer()`` / ``pick(x, y)``: the primary-hit pass (clw_ext_render_gbuffer, clw_ext_pick) -- depth, object id, normal, hit point and albedo of
 what the launch camera sees first at every pixel of this renderer's rows, or at one pixel of the frame.  No sampling mode above changes them,
 and they leave an accumulating view counting.
+
+A renderer is a context manager: ``with Renderer(...) as r:`` releases it on the way out; releasing twice is harmless.
 """
 from __future__ import annotations
 
@@ -214,3 +216,9 @@ class Renderer:
 
     def release(self):
         self.w.release()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()

@@ -7,6 +7,7 @@ Constituent frame f is the plain frame with seed offset `frame_seed(f)` through 
 import numpy as np
 
 from conftest import CAM
+from render_common import rendering, take
 
 F32 = np.float32
 GOLDEN_RATIO_ODD = 0x9E3779B1
@@ -82,15 +83,8 @@ def base_camera(api, W, H, cam=CAM):
 
 def plain(R, sc, tex, sky, W, H, depth, strict, cam, n=1, seed=0, setup=None, **kw):
     """one frame of a fresh renderer with the mode off -> (packed, float)"""
-    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, seed_offset=seed, **kw)
-    try:
-        if setup:
-            setup(r.w)
-        r.set_camera(cam)
-        p, f = r.render_rgb()
-        return p.copy(), f.copy()
-    finally:
-        r.release()
+    with rendering(R, sc, tex, sky, W, H, setup=setup, cam=cam, depth=depth, strict=strict, supersample=n, seed_offset=seed, **kw) as r:
+        return take(r)[0]
 
 
 _own = {}
@@ -112,17 +106,9 @@ def own_frames(R, api, sc, tex, sky, W, H, n, depth, strict, jitter, count, cam=
 
 def accumulated(R, api, sc, tex, sky, W, H, n, depth, strict, jitter, count, max_frames=64, cam=CAM, setup=None, flags=None, **kw):
     """`count` frames in a row of one accumulating renderer -> [(packed, float, K) ...]; the flags of the last trace launch are appended to `flags`"""
-    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, accumulate=max_frames, jitter=jitter, **kw)
-    try:
-        if setup:
-            setup(r.w)
-        r.set_camera(base_camera(api, W, H, cam))
-        out = []
-        for _ in range(count):
-            p, f = r.render_rgb()
-            out.append((p.copy(), f.copy(), r.accumulated))
+    with rendering(R, sc, tex, sky, W, H, setup=setup, cam=base_camera(api, W, H, cam), depth=depth, strict=strict, supersample=n,
+                   accumulate=max_frames, jitter=jitter, **kw) as r:
+        out = take(r, count, extra=lambda r: r.accumulated)
         if flags is not None:
             flags.append(r.w.last_trace_flags())
         return out
-    finally:
-        r.release()

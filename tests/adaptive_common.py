@@ -8,6 +8,7 @@ supersampled frame in the refined blocks and B elsewhere (`composite`)."""
 import numpy as np
 
 from conftest import CAM
+from render_common import rendering, same_floats, take
 
 
 def contrast_np(xrgb, W, rows):
@@ -46,56 +47,11 @@ def composite(mask, W, rows, n, base, fine):
     return np.where(m if base.ndim == 1 else m[:, None], fine, base)
 
 
-# ---- copies of the helpers of test_gpu_supersample.py (a test module is not importable from another) ---------------------------------
-def resolve(rgb, W, H, n):                      # rgb: float32 [n*H * n*W, 3], virtual-frame order
-    s = np.clip(rgb.reshape(H * n, W * n, 3), np.float32(0), np.float32(1))
-    k = n
-    while k > 1: s = s[:, 0::2] + s[:, 1::2]; k //= 2
-    k = n
-    while k > 1: s = s[0::2] + s[1::2]; k //= 2
-    s = s * np.float32(1.0 / (n * n))
-    c = (s * np.float32(255.0)).astype(np.uint32)
-    return ((c[..., 0] << 16) | (c[..., 1] << 8) | c[..., 2]).reshape(-1), s.reshape(-1, 3)
-
-
-def frames(R, sc, tex, sky, W, H, depth, strict, n=1, count=1, setup=None, rgb=True, cam=CAM, **kw):
-    """`count` frames in a row from one renderer -> ([(packed, float) ...], flags of the last trace launch); **kw goes to the Renderer"""
-    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, **kw)
-    try:
-        if setup:
-            setup(r.w)
-        r.look(**cam)
-        out = []
-        for _ in range(count):
-            if rgb:
-                p, f = r.render_rgb()
-                out.append((p.copy(), f.copy()))
-            else:
-                out.append((r.render().copy(), None))
-        return out, r.w.last_trace_flags()
-    finally:
-        r.release()
-
-
-def same_floats(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 # ---- the adaptive launch and its check (api = the api module; `cam`: the view, conftest.CAM unless given)
 def adaptive(R, sc, tex, sky, W, H, depth, strict, n, T, count=1, setup=None, cam=CAM, **kw):
     """`count` adaptive frames in a row from one renderer -> ([(packed, float, mask) ...], flags of the last trace launch)"""
-    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, adaptive=T, **kw)
-    try:
-        if setup:
-            setup(r.w)
-        r.look(**cam)
-        out = []
-        for _ in range(count):
-            p, f = r.render_rgb()
-            out.append((p.copy(), f.copy(), r.w.read_refine_mask()))
-        return out, r.w.last_trace_flags()
-    finally:
-        r.release()
+    with rendering(R, sc, tex, sky, W, H, setup=setup, cam=cam, depth=depth, strict=strict, supersample=n, adaptive=T, **kw) as r:
+        return take(r, count, extra=lambda r: r.w.read_refine_mask()), r.w.last_trace_flags()
 
 
 def check_composite(api, ref, got, W, rows, n, T, what):

@@ -120,7 +120,3 @@ def expected_case(oracle, name, tex, sky):
 
 def kind_of(ids):
     return np.asarray(ids, np.uint32) >> np.uint32(30)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)

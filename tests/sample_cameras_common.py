@@ -1,23 +1,19 @@
 """Shared by test_sample_cameras_host.py and test_gpu_sample_cameras.py: the numpy reference of the definition of per-sample cameras.
 
 With factor n and a table cams[0 .. n*n), the sample at virtual pixel (vx, vy) is pixel (vx, vy) of a 1-sample render of the n*W x n*H
-frame through cams[(vy mod n) * n + (vx mod n)] with w_factor / n, h_factor / n; clamp, add and scale as plain supersampling (`resolve`)."""
+frame through cams[(vy mod n) * n + (vx mod n)] with w_factor / n, h_factor / n; clamp, add and scale as plain supersampling (render_common.resolve)."""
 import numpy as np
 
 from conftest import CAM
+from render_common import rendering, resolve, take
 
 CAM2 = dict(origin=(1.6, 3.1, -6.5), look=(0.05, -0.15, 1.0), fov=90.0, focal=1.0)      # a clearly different camera (the shutter's other end)
 
 
-def resolve(rgb, W, H, n):                      # rgb: float32 [n*H * n*W, 3], virtual-frame order (as in test_gpu_supersample.py)
-    s = np.clip(rgb.reshape(H * n, W * n, 3), np.float32(0), np.float32(1))
-    k = n
-    while k > 1: s = s[:, 0::2] + s[:, 1::2]; k //= 2
-    k = n
-    while k > 1: s = s[0::2] + s[1::2]; k //= 2
-    s = s * np.float32(1.0 / (n * n))
-    c = (s * np.float32(255.0)).astype(np.uint32)
-    return ((c[..., 0] << 16) | (c[..., 1] << 8) | c[..., 2]).reshape(-1), s.reshape(-1, 3)
+def slot(k, n):
+    """sample k = sy * n + sx -> lens cell / shutter slot: k with its 2 log2 n bits reversed"""
+    bits = 2 * (n.bit_length() - 1)
+    return int(format(k, f"0{bits}b")[::-1], 2)
 
 
 def pick(render_virtual, W, H, n):
@@ -57,10 +53,6 @@ def virtual_camera(cls, row, base, n):
 
 
 # ---- the GPU side of the definition (R = renderer.Renderer, api = the api module)
-def same_floats(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 def make_table(api, W, H, n, kind, cam=CAM, cam2=CAM2):
     """kind: (aperture, focus) = the lens table, "shutter" = an open shutter from cam to cam2 -> (base camera, float32 [n*n, 12])"""
     base = api.perspective(**cam, width=W, height=H)
@@ -71,37 +63,21 @@ def make_table(api, W, H, n, kind, cam=CAM, cam2=CAM2):
 
 def gpu_composed(R, api, sc, tex, sky, base, table, W, H, n, depth, strict, setup=None):
     """`composed` over the GPU's own 1-sample virtual frames (one renderer, camera re-set per table entry) -> (packed, float), flags"""
-    r = R(sc, tex, sky, n * W, n * H, depth=depth, strict=strict)
-    try:
-        if setup:
-            setup(r.w)
-
+    with rendering(R, sc, tex, sky, n * W, n * H, setup=setup, cam=None, depth=depth, strict=strict) as r:
         def render_virtual(k):
             r.set_camera(virtual_camera(api.clw_camera, table[k], base, n))
             return r.render_rgb()[1]
-        want = composed(render_virtual, table, W, H, n)
-        return want, r.w.last_trace_flags()
-    finally:
-        r.release()
+        return composed(render_virtual, table, W, H, n), r.w.last_trace_flags()
 
 
 def sampled(R, sc, tex, sky, W, H, n, depth, strict, kind, table=None, count=1, setup=None, cam=CAM, rgb=True, **kw):
     """`count` frames of one supersampled renderer with a lens (kind = (aperture, focus)), an explicit table (kind "shutter" / "table") or
     neither (kind None) -> [(packed, float)], flags, the table the last launch used"""
-    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, lens=kind if isinstance(kind, tuple) else None, **kw)
-    try:
+    def knobs_then_table(w):
         if setup:
-            setup(r.w)
+            setup(w)
         if kind in ("shutter", "table"):
-            r.set_sample_cameras(table)
-        r.look(**cam)
-        out = []
-        for _ in range(count):
-            if rgb:
-                p, f = r.render_rgb()
-                out.append((p.copy(), f.copy()))
-            else:
-                out.append((r.render().copy(), None))
-        return out, r.w.last_trace_flags(), r.w.get_sample_cameras()
-    finally:
-        r.release()
+            w.set_sample_cameras(table)
+    with rendering(R, sc, tex, sky, W, H, setup=knobs_then_table, cam=cam, depth=depth, strict=strict, supersample=n,
+                   lens=kind if isinstance(kind, tuple) else None, **kw) as r:
+        return take(r, count, rgb), r.w.last_trace_flags(), r.w.get_sample_cameras()

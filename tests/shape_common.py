@@ -3,6 +3,7 @@ compiled for, the flag word of each (WT_SHAPE_FLAGS of csrc/whitted_params.h, re
 sizes, depths, factor and threshold at which the twelve scenes of fuzz_scenes.SHAPED_SEEDS are rendered."""
 from conftest import CAM
 from fuzz_scenes import SHAPED_SEEDS, shaped_scene
+from render_common import rendering, take
 
 from flags_common import F_DEEP, F_GEOM_LDS, F_SHAPE, F_SS, F_MOVE, F_LIST, shape_flags      # noqa: F401
 V_GENERIC = 8192                        # clw_ext_set_variant: small scenes of the fast build keep the generic kernel
@@ -23,14 +24,8 @@ def scene_of(ns, npl):
 
 def frame(R, sc, tex, sky, w, h, depth, variant, cam=CAM, strict=False):
     """-> (packed frame, float radiance, flags of the trace launch)"""
-    r = R(sc, tex, sky, w, h, depth=depth, strict=strict)
-    try:
-        r.w.set_variant(variant)
-        r.look(**cam)
-        out, rgb = r.render_rgb()
-        return out, rgb, r.w.last_trace_flags()
-    finally:
-        r.release()
+    with rendering(R, sc, tex, sky, w, h, setup=lambda wrap: wrap.set_variant(variant), cam=cam, depth=depth, strict=strict) as r:
+        return (*take(r)[0], r.w.last_trace_flags())
 
 
 def empty_list_scenes(demo_scene):

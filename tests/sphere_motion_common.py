@@ -3,10 +3,11 @@ moving spheres.
 
 With factor n, a displacement table disp[spheres, 3] and sample times t[0 .. n*n), the sample at virtual pixel (vx, vy) is pixel (vx, vy) of
 the 1-sample render of the n*W x n*H frame of the scene S(t[(vy mod n) * n + (vx mod n)]), whose sphere i has centre fma(t, disp[i], c[i])
-(api.spheres_at = clw_host_spheres_at); clamp, add and scale as plain supersampling (sample_cameras_common.resolve)."""
+(api.spheres_at = clw_host_spheres_at); clamp, add and scale as plain supersampling (render_common.resolve)."""
 import numpy as np
 
 from conftest import CAM
+from render_common import assert_same_frames, rendering, take
 from sample_cameras_common import composed, rows_of, virtual_camera
 
 from flags_common import F_SS      # noqa: F401  (clw_ext_last_trace_flags)
@@ -47,10 +48,6 @@ def fma32(t, d, c):
 
 
 # ---- the GPU side of the definition (R = renderer.Renderer, api = the api module; `cam`, `cam2`: the launch camera and the shutter's other end)
-def same_floats(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 def camera_table(api, W, H, n, kind, cam=CAM, cam2=CAM2):
     """kind None: n*n copies of the launch camera; (aperture, focus): the lens table; "shutter": cam -> cam2 -> (base camera, float32 [n*n, 12])"""
     base = api.perspective(**cam, width=W, height=H)
@@ -63,15 +60,10 @@ def camera_table(api, W, H, n, kind, cam=CAM, cam2=CAM2):
 
 def gpu_virtual(R, api, sc, tex, sky, disp, t, base, row, n, depth, strict, what="rgb", setup=None):
     """the GPU's own 1-sample render of the n*W x n*H frame of S(t) through the camera `row` of a table"""
-    r = R(moved_scene(api, sc, disp, float(t)), tex, sky, n * base.width, n * base.height, depth=depth, strict=strict)
-    try:
-        if setup:
-            setup(r.w)
-        r.set_camera(virtual_camera(api.clw_camera, row, base, n))
-        out = r.render_rgb()[1] if what == "rgb" else r.render().copy()
-        return out, r.w.last_trace_flags()
-    finally:
-        r.release()
+    with rendering(R, moved_scene(api, sc, disp, float(t)), tex, sky, n * base.width, n * base.height, setup=setup,
+                   cam=virtual_camera(api.clw_camera, row, base, n), depth=depth, strict=strict) as r:
+        (p, f), = take(r, rgb=what == "rgb")
+        return (p if f is None else f), r.w.last_trace_flags()
 
 
 def gpu_composed(R, api, sc, tex, sky, disp, times, W, H, n, depth, strict, cams=None, setup=None, cam=CAM, cam2=CAM2):
@@ -89,25 +81,17 @@ def moving(R, sc, tex, sky, W, H, n, depth, strict, disp, times=None, cams=None,
     """`count` frames of one supersampled renderer with a displacement table (None = none), optional explicit times and a lens
     (cams = (aperture, focus)) or a table of cameras (cams = float32 [n*n, 12]) -> [(packed, float)], flags, the times the last launch used"""
     lens = cams if isinstance(cams, tuple) else None
-    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n, lens=lens, motion=disp if times is None else None, **kw)
-    try:
+
+    def knobs_then_tables(w):
         if setup:
-            setup(r.w)
+            setup(w)
         if times is not None:
-            r.set_sphere_motion(disp, times)
+            w.set_sphere_motion(disp, times)
         if cams is not None and lens is None:
-            r.set_sample_cameras(cams)
-        r.look(**cam)
-        out = []
-        for _ in range(count):
-            if rgb:
-                p, f = r.render_rgb()
-                out.append((p.copy(), f.copy()))
-            else:
-                out.append((r.render().copy(), None))
-        return out, r.w.last_trace_flags(), r.w.get_sample_times()
-    finally:
-        r.release()
+            w.set_sample_cameras(cams)
+    with rendering(R, sc, tex, sky, W, H, setup=knobs_then_tables, cam=cam, depth=depth, strict=strict, supersample=n, lens=lens,
+                   motion=disp if times is None else None, **kw) as r:
+        return take(r, count, rgb), r.w.last_trace_flags(), r.w.get_sample_times()
 
 
 def check_self_consistent(R, api, sc, tex, sky, W, H, n, depth, strict, disp=DISP, times=None, cams=None, count=1, setup=None, cam=CAM, cam2=CAM2):
@@ -117,13 +101,9 @@ def check_self_consistent(R, api, sc, tex, sky, W, H, n, depth, strict, disp=DIS
     got, flags, used = moving(R, sc, tex, sky, W, H, n, depth, strict, disp, times=times, cams=cams if table is None else table, count=count, setup=setup, cam=cam)
     assert flags & F_SS
     assert used.tobytes() == used_times.tobytes()
-    for k, (p, f) in enumerate(got):
+    for p, f in got:
         assert p.shape == (W * H,) and f.shape == (W * H, 3)
-        bad = int((p != want_p).sum())
-        print(f"{W}x{H} n={n} depth {depth} strict={int(strict)} cams={cams} frame {k}: {bad} packed pixels differ, "
-              f"{int((f.view(np.uint32) != want_f.view(np.uint32)).any(1).sum())} float pixels differ")
-        assert np.array_equal(p, want_p), (W, H, n, depth, strict, k, bad)
-        assert same_floats(f, want_f), (W, H, n, depth, strict, k)
+    assert_same_frames(got, want_p, want_f, f"{W}x{H} n={n} depth {depth} strict={int(strict)} cams={cams}")
     # and the moving frame is not the static supersampled one
     static = moving(R, sc, tex, sky, W, H, n, depth, strict, None, cams=cams if table is None else table, rgb=False, setup=setup, cam=cam)[0][0][0]
     print(f"  {100 * float((static != want_p).mean()):.1f} % of the pixels differ from the static supersampled frame")

@@ -7,15 +7,10 @@ import pytest
 
 from accumulate_common import F32, camera_bytes, camera_rows, fold, frame_seed, halton, jittered, pack
 from conftest import CAM
+from render_common import api, header_text  # noqa: F401  (api: the fixture)
 
 NEW_SYMBOLS = ["clw_ext_set_seed_offset", "clw_ext_get_seed_offset", "clw_ext_set_accumulate", "clw_ext_get_accumulated",
                "clw_ext_reset_accumulation", "clw_host_frame_seed", "clw_host_jitter_camera"]
-
-
-@pytest.fixture(scope="module")
-def api():
-    from example_gui_opencl_raytracer_amd import api
-    return api
 
 
 @pytest.fixture(scope="module")
@@ -92,7 +87,7 @@ def test_fold_of_one_frame_is_the_plain_pack():
 
 def test_new_symbols_are_exported_and_listed(api):
     L = api.load_library()
-    header = open(__import__("os").path.join(__import__("conftest").ROOT, "include", "hip_wrap_ext.h")).read()
+    header = header_text()
     for name in NEW_SYMBOLS:
         assert name in api.SYMBOLS, name
         assert hasattr(L, name), name

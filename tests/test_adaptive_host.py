@@ -1,15 +1,13 @@
 """Adaptive supersampling without a GPU: the C ABI and the host helper that IS the definition of the refine mask (clw_host_refine_mask),
 held to the numpy restatement of adaptive_common.py."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 from adaptive_common import composite, contrast_np, pixel_mask, refine_mask_np
-from conftest import ROOT
 from example_gui_opencl_raytracer_amd import api
+from render_common import declared_symbols
 
 NEW = ["clw_ext_set_adaptive", "clw_ext_get_adaptive", "clw_ext_read_refine_mask", "clw_host_refine_mask"]
 SHAPES = [(101, 75, 2), (200, 152, 4), (96, 64, 8), (1, 1, 2), (1, 1, 8), (37, 1, 4), (1, 9, 2)]      # (W, rows, n)
@@ -31,8 +29,7 @@ def random_frame(W, rows, seed):
 
 # ------------------------------------------------------------------ 1. the ABI
 def test_header_library_and_mirror_agree_on_the_new_symbols():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hip_wrap_ext.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b((?:clw_ext|clw_host)_\w+)\s*\(", text))
+    declared = declared_symbols()
     L = api.load_library()
     for name in NEW:
         assert name in declared and name in api.SYMBOLS and hasattr(L, name), name

@@ -1,25 +1,20 @@
 """The primary-hit pass without a GPU: its C ABI against the header and the ctypes mirror, and the expected buffers the GPU tests compare
 with (tests/gbuffer_common.py) against the oracle they are built from."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
 import gbuffer_common as gc
-from conftest import ROOT
+from render_common import header_text
 
 NEW_SYMBOLS = ["clw_ext_render_gbuffer", "clw_ext_read_gbuffer", "clw_ext_gbuffer_device_ptr", "clw_ext_pick"]
 
 
-def header_text():
-    return open(os.path.join(ROOT, "include", "hip_wrap_ext.h")).read()
-
-
 def test_header_library_and_mirror_agree_on_the_new_symbols():
     from example_gui_opencl_raytracer_amd import api
-    code = re.sub(r"/\*.*?\*/", "", header_text(), flags=re.S)
+    code = header_text(comments=False)
     L = api.load_library()
     for name in NEW_SYMBOLS:
         assert re.search(rf"\b{name}\s*\(", code), f"hip_wrap_ext.h does not declare {name}"

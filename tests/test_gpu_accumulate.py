@@ -13,27 +13,14 @@ import pytest
 
 from accumulate_common import accumulated, base_camera, fold, jittered, own_frames, plain
 from conftest import CAM, ROOT
-from sample_cameras_common import resolve, rows_of, virtual_camera
+from render_common import R, api, released, rendering, resolve, run_child, take  # noqa: F401  (R, api: the fixtures)
+from sample_cameras_common import rows_of, virtual_camera
 
 pytestmark = pytest.mark.gpu
 
 SEEDS = [1, 0x9E3779B1, 2 ** 32 - 5]          # the last makes in-frame pixel 5 the stuck generator
 # (W, H, n, depth): partial tiles both ways; the supersampled resolves; the deep build (cost-sorted order, split tiles, the tail) on three lights and glass
 SHAPES = [(101, 75, 1, 4), (96, 64, 2, 4), (64, 48, 4, 4), (96, 64, 1, 15)]
-
-
-@pytest.fixture(scope="module")
-def R():
-    import torch  # noqa: F401
-    from example_gui_opencl_raytracer_amd.renderer import Renderer
-    return Renderer
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (before the shim is loaded: both then share the ROCm runtime torch ships)
-    from example_gui_opencl_raytracer_amd import api
-    return api
 
 
 def oracle_frame(oracle, cam, sc, tex, sky, depth, seed):
@@ -67,12 +54,11 @@ def test_seed_offset_is_the_oracles_shifted_ids(R, api, oracle, demo_scene, tex,
 
 
 def test_seed_offset_get_returns_what_set(api):
-    w = api.ClWrap()
-    assert w.get_seed_offset() == 0 and w.get_accumulated() == 0
-    for s in (1, 0x9E3779B1, 2 ** 32 - 1, 0):
-        w.set_seed_offset(s)
-        assert w.get_seed_offset() == s
-    w.release()
+    with released(api.ClWrap()) as w:
+        assert w.get_seed_offset() == 0 and w.get_accumulated() == 0
+        for s in (1, 0x9E3779B1, 2 ** 32 - 1, 0):
+            w.set_seed_offset(s)
+            assert w.get_seed_offset() == s
 
 
 # ------------------------------------------------------------------ 2. the offset reaches every path, both builds
@@ -94,16 +80,12 @@ def test_seed_offset_reaches_every_path(R, api, demo_scene, tex, sky, strict):
         assert np.array_equal(np.concatenate(strips), want), depth
     loop, _ = plain(R, demo_scene, tex, sky, W, H, 15, strict, cam, seed=s, setup=lambda w: w.set_variant(16))
     assert np.array_equal(loop, want)
-    r = R(demo_scene, tex, sky, W, H, depth=15, strict=strict, seed_offset=s)
-    try:
-        r.w.set_tpt(64, 1, -1)                               # everything through the tail (as tests/test_gpu_parity.py forces it)
-        r.set_camera(cam)
+    through_the_tail = lambda w: w.set_tpt(64, 1, -1)         # everything through the tail (as tests/test_gpu_parity.py forces it)
+    with rendering(R, demo_scene, tex, sky, W, H, setup=through_the_tail, cam=cam, depth=15, strict=strict, seed_offset=s) as r:
         tail = r.render().copy()
         r.w.enable_counters(1)                               # the counting flavour of the same launch tells whether the tail ran
         counted = r.render().copy()
         c = r.w.read_counters()
-    finally:
-        r.release()
     assert c["tpt_tiles"] > 0 and c["tpt_nodes"] > 0, "the tail did not run"
     assert np.array_equal(tail, want) and np.array_equal(counted, want)
 
@@ -118,16 +100,10 @@ def test_the_strict_twins_that_carry_the_seed_and_the_sum(R, api, demo_scene, te
     flags = {}
 
     def one(sc, name, acc=0, seed=0, setup=None):
-        r = R(sc, tex, sky, W, H, depth=depth, strict=True, seed_offset=seed, accumulate=acc)
-        try:
-            if setup:
-                setup(r.w)
-            r.set_camera(cam)
-            frames = [r.render().copy() for _ in range(max(acc, 1))]
+        with rendering(R, sc, tex, sky, W, H, setup=setup, cam=cam, depth=depth, strict=True, seed_offset=seed, accumulate=acc) as r:
+            frames = take(r, max(acc, 1), rgb=False)
             flags[name] = r.w.last_trace_flags()
-            return frames[-1]
-        finally:
-            r.release()
+            return frames[-1][0]
 
     on = lambda w: w.enable_counters(1)
     assert np.array_equal(one(demo_scene, "count_seed", seed=s, setup=on), one(demo_scene, "seed", seed=s))
@@ -212,10 +188,8 @@ def test_restart_and_hold(R, api, demo_scene, tex, sky):
     plain1, _ = plain(R, demo_scene, tex, sky, W, H, depth, False, cam)
     plain2, _ = plain(R, demo_scene, tex, sky, W, H, depth, False, cam2)
     plain1_d3, _ = plain(R, demo_scene, tex, sky, W, H, 3, False, cam)
-    r = R(demo_scene, tex, sky, W, H, depth=depth, accumulate=64)
-    try:
-        r.set_camera(cam)
-        frames = [r.render().copy() for _ in range(3)]
+    with rendering(R, demo_scene, tex, sky, W, H, cam=cam, depth=depth, accumulate=64) as r:
+        frames = [p for p, _ in take(r, 3, rgb=False)]
         assert r.accumulated == 3 and np.array_equal(frames[0], plain1) and not np.array_equal(frames[2], plain1)
         r.look(**other)                                      # another camera: its plain frame, one frame in the sum
         assert np.array_equal(r.render(), plain2) and r.accumulated == 1
@@ -242,52 +216,34 @@ def test_restart_and_hold(R, api, demo_scene, tex, sky):
         r.w.set_seed_offset(7)
         r.render()
         assert r.accumulated == 1
-    finally:
-        r.release()
-    r = R(demo_scene, tex, sky, W, H, depth=depth, accumulate=3)
-    try:
-        r.set_camera(cam)
+    with rendering(R, demo_scene, tex, sky, W, H, cam=cam, depth=depth, accumulate=3) as r:
         r.w.timing_reset()
-        got = [r.render().copy() for _ in range(3)]
+        got = [p for p, _ in take(r, 3, rgb=False)]
         assert r.accumulated == 3 and r.w.timing_get(1)[0] == 3
         assert np.array_equal(got[2], frames[2])
         flags = r.w.last_trace_flags()
         for _ in range(2):                                   # converged: no launch, the same frame
             assert np.array_equal(r.render(), got[2]) and r.accumulated == 3
         assert r.w.timing_get(1)[0] == 3 and r.w.last_trace_flags() == flags
-    finally:
-        r.release()
 
 
 # ------------------------------------------------------------------ 7. it converges
 def test_it_converges(R, api, demo_scene, tex, sky):
     W, H, depth = 160, 120, 4
-    r = R(demo_scene, tex, sky, W, H, depth=depth, accumulate=64, jitter=False)
-    try:
-        r.set_camera(base_camera(api, W, H))
+    with rendering(R, demo_scene, tex, sky, W, H, cam=base_camera(api, W, H), depth=depth, accumulate=64, jitter=False) as r:
         at = {}
         for k in range(1, 65):
             p = r.render()
             if k in (1, 16, 64):
                 at[k] = np.stack([(p >> 16) & 255, (p >> 8) & 255, p & 255], 1).astype(np.int64)
         assert r.accumulated == 64
-    finally:
-        r.release()
     d1, d16 = int(np.abs(at[1] - at[64]).sum()), int(np.abs(at[16] - at[64]).sum())
     print(f"summed channel distance to the 64-frame result: 1 frame {d1}, 16 frames {d16}")
     assert d16 < d1 and (at[16] != at[1]).any()
 
 
 # ------------------------------------------------------------------ 8. refusals: message + exit(1); the environment
-def _run(snippet, env=None):
-    code = ("import sys; sys.path.insert(0, %r)\n"
-            "import numpy as np\n"
-            "import torch\n"
-            "from example_gui_opencl_raytracer_amd import api, scene, textures\n"
-            "from example_gui_opencl_raytracer_amd.renderer import Renderer\n"
-            "CAM = %r\n"
-            "sc, tex, sky = scene.render_map_scene(), textures.texture_layers(), textures.skybox_cross(64)\n" % (ROOT, CAM)) + snippet
-    return subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
+_run = run_child
 
 
 REFUSED = {
@@ -362,13 +318,10 @@ def test_unchanged_interactive_driver_accumulates(R, api, demo_scene, tex, tmp_p
 
     W, H, depth = 800, 600, 15
     still = run("", 6, "still.png", "4")                     # six frames of a still view: four accumulate, two hold
-    r = R(demo_scene, tex, sky, W, H, depth=depth, accumulate=4)
-    try:
+    with R(demo_scene, tex, sky, W, H, depth=depth, accumulate=4) as r:
         r.look((0.8, 2.5, -8.0), (0.0, 0.0, 1.0))           # the camera of rayinteractive.c:111-115
         for _ in range(4):
             want = r.render().copy()
-    finally:
-        r.release()
     assert np.array_equal(still, want)
     # a key on the last frame: the sum starts again, the dump is the PLAIN frame of the moved camera -- the one the driver shows with the mode off
     moved = run(".....W", 6, "moved.png", "4")

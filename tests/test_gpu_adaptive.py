@@ -11,28 +11,15 @@ import sys
 import numpy as np
 import pytest
 
-from adaptive_common import adaptive, check_composite, composite, frames, pixel_mask, resolve, same_floats
+from adaptive_common import adaptive, check_composite, composite, pixel_mask
 from conftest import CAM, ROOT
 from flags_common import F_DEEP, F_GRID, F_OCC, F_SHAPE, F_SS, F_LIST
+from render_common import R, api, frames, queued_on, released, rendering, resolve, run_child, same_floats, take  # noqa: F401  (R, api: the fixtures)
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(320, 240, 2), (200, 152, 4), (96, 64, 8), (101, 75, 2)]
 COUNTED = ("segments", "shadow_rays", "light_probes", "sky_fetches", "texel_fetches", "pushes")
-
-
-@pytest.fixture(scope="module")
-def R():
-    import torch  # noqa: F401
-    from example_gui_opencl_raytracer_amd.renderer import Renderer
-    return Renderer
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (before the shim is loaded: both then share the ROCm runtime torch ships)
-    from example_gui_opencl_raytracer_amd import api
-    return api
 
 
 _refs = {}
@@ -52,13 +39,12 @@ def refs(R, name, sc, tex, sky, W, H, n, depth, strict, **kw):
 
 # ------------------------------------------------------------------ the setter
 def test_get_returns_what_set_and_the_environment_set(api):
-    w = api.ClWrap()
-    assert w.get_adaptive() == -1
-    for T in (0, 16, 256, -1, 64):
-        w.set_adaptive(T)
-        assert w.get_adaptive() == T
-    assert w.read_refine_mask().size == 0
-    w.release()
+    with released(api.ClWrap()) as w:
+        assert w.get_adaptive() == -1
+        for T in (0, 16, 256, -1, 64):
+            w.set_adaptive(T)
+            assert w.get_adaptive() == T
+        assert w.read_refine_mask().size == 0
     code = ("import sys; sys.path.insert(0, %r)\n"
             "from example_gui_opencl_raytracer_amd import api\n"
             "w = api.ClWrap(); print('adaptive', w.get_adaptive()); w.release()\n" % ROOT)
@@ -171,27 +157,22 @@ def test_changing_threshold_and_factor_between_frames(R, demo_scene, tex, sky, s
     seq = [(2, 16), (2, 16), (2, 256), (2, 0), (2, -1), (8, 16), (8, -1), (4, 16), (4, 0), (4, -1), (2, 16)]      # (n, T)
     want = {}
     for n, T in set(seq):
-        r = R(demo_scene, tex, sky, W, H, depth=depth, strict=strict, supersample=n, adaptive=None if T < 0 else T)
-        r.look(**CAM)
-        p, f = r.render_rgb()
-        want[n, T] = (p.copy(), f.copy(), r.w.last_trace_flags(), r.w.read_tile_costs(), r.w.read_refine_mask())
-        r.release()
-    r = R(demo_scene, tex, sky, W, H, depth=depth, strict=strict)
-    r.look(**CAM)
-    for n, T in seq:
-        r.w.set_supersample(n)
-        r.w.set_adaptive(T)
-        p, f = r.render_rgb()
-        frame, rgb, flags, costs, mask = want[n, T]
-        assert np.array_equal(p, frame) and same_floats(f, rgb), (n, T)
-        assert r.w.last_trace_flags() == flags and bool(flags & F_LIST) == (T >= 0), (n, T)
-        assert np.array_equal(r.w.read_refine_mask(), mask) and (mask.size != 0) == (T >= 0), (n, T)
-        got_costs = r.w.read_tile_costs()
-        if T < 0:                     # the plain supersampled launch, on scheduling state of its own: the virtual frame's tiles
-            assert np.array_equal(got_costs, costs), (n, T)
-        else:                         # the base pass's: an ordinary 1-sample launch of W x H
-            assert got_costs.size == costs.size == (-(-W // 8)) * (-(-H // 8)), (n, T)
-    r.release()
+        with rendering(R, demo_scene, tex, sky, W, H, depth=depth, strict=strict, supersample=n, adaptive=None if T < 0 else T) as r:
+            want[n, T] = (*take(r)[0], r.w.last_trace_flags(), r.w.read_tile_costs(), r.w.read_refine_mask())
+    with rendering(R, demo_scene, tex, sky, W, H, depth=depth, strict=strict) as r:
+        for n, T in seq:
+            r.w.set_supersample(n)
+            r.w.set_adaptive(T)
+            p, f = r.render_rgb()
+            frame, rgb, flags, costs, mask = want[n, T]
+            assert np.array_equal(p, frame) and same_floats(f, rgb), (n, T)
+            assert r.w.last_trace_flags() == flags and bool(flags & F_LIST) == (T >= 0), (n, T)
+            assert np.array_equal(r.w.read_refine_mask(), mask) and (mask.size != 0) == (T >= 0), (n, T)
+            got_costs = r.w.read_tile_costs()
+            if T < 0:                     # the plain supersampled launch, on scheduling state of its own: the virtual frame's tiles
+                assert np.array_equal(got_costs, costs), (n, T)
+            else:                         # the base pass's: an ordinary 1-sample launch of W x H
+                assert got_costs.size == costs.size == (-(-W // 8)) * (-(-H // 8)), (n, T)
     (plain,), pflags = frames(R, demo_scene, tex, sky, W, H, depth, strict, n=2)
     assert np.array_equal(want[2, -1][0], plain[0]) and same_floats(want[2, -1][1], plain[1]) and want[2, -1][2] == pflags
     assert np.array_equal(want[2, 0][0], plain[0]) and same_floats(want[2, 0][1], plain[1])
@@ -225,14 +206,11 @@ def test_counters_add_up_over_both_passes(R, api, demo_scene, tex, sky, W, H, n)
     depth, b = 4, 8 // n
 
     def counted(k, T):
-        r = R(demo_scene, tex, sky, W, H, depth=depth, strict=True, supersample=k, adaptive=T)
-        r.look(**CAM)
-        r.w.enable_counters(1)
-        p = r.render().copy()
-        c = r.w.read_counters()
-        mask = r.w.read_refine_mask()
-        r.release()
-        return p, {x: c[x] for x in COUNTED}, mask
+        with rendering(R, demo_scene, tex, sky, W, H, depth=depth, strict=True, supersample=k, adaptive=T) as r:
+            r.w.enable_counters(1)
+            p = r.render().copy()
+            c = r.w.read_counters()
+            return p, {x: c[x] for x in COUNTED}, r.w.read_refine_mask()
 
     base_p, base_c, _ = counted(1, None)
     _, fine_c, _ = counted(n, None)
@@ -260,41 +238,29 @@ def test_async_frames_on_a_side_stream(R, api, demo_scene, tex, sky):
     fb = torch.zeros(W * H, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     side = torch.cuda.Stream()
-    r = R(demo_scene, tex, sky, W, H, depth=depth, supersample=n, framebuffer_ptr=fb.data_ptr())
-    r.w.set_stream(side.cuda_stream)
-    r.w.set_async(True)
-    r.look(**CAM)
-    r.w.timing_reset()
-    outs = []
-    for T in Ts:
-        r.w.set_adaptive(T)
+    with rendering(R, demo_scene, tex, sky, W, H, setup=queued_on(side), depth=depth, supersample=n, framebuffer_ptr=fb.data_ptr()) as r:
+        r.w.timing_reset()
+        outs = []
+        for T in Ts:
+            r.w.set_adaptive(T)
+            r.render(readback=False)
+            with torch.cuda.stream(side):
+                outs.append(fb.clone())
+        r.w.sync()
+        launches, ms = r.w.timing_get(1)
+        assert launches == len(Ts) and 0.0 < ms < 1000.0       # base + classify + refine are timed as one launch
+        for T, o in zip(Ts, outs):
+            assert np.array_equal(o.cpu().numpy().view(np.uint32), want[T]), T
+        assert np.array_equal(r.w.read_refine_mask(), api.refine_mask(bp, W, H, n, Ts[-1]).reshape(-1))
+        r.w.set_stream(0)                                       # the lists are fenced when the stream changes
+        r.w.set_adaptive(16)
         r.render(readback=False)
-        with torch.cuda.stream(side):
-            outs.append(fb.clone())
-    r.w.sync()
-    launches, ms = r.w.timing_get(1)
-    assert launches == len(Ts) and 0.0 < ms < 1000.0       # base + classify + refine are timed as one launch
-    for T, o in zip(Ts, outs):
-        assert np.array_equal(o.cpu().numpy().view(np.uint32), want[T]), T
-    assert np.array_equal(r.w.read_refine_mask(), api.refine_mask(bp, W, H, n, Ts[-1]).reshape(-1))
-    r.w.set_stream(0)                                       # the lists are fenced when the stream changes
-    r.w.set_adaptive(16)
-    r.render(readback=False)
-    r.w.sync()
-    assert np.array_equal(fb.cpu().numpy().view(np.uint32), want[16])
-    r.release()
+        r.w.sync()
+        assert np.array_equal(fb.cpu().numpy().view(np.uint32), want[16])
 
 
 # ------------------------------------------------------------------ 10. refusals: message + exit(1)
-def _run(snippet, env=None):
-    code = ("import sys; sys.path.insert(0, %r)\n"
-            "import numpy as np\n"
-            "import torch\n"
-            "from example_gui_opencl_raytracer_amd import api, scene, textures\n"
-            "from example_gui_opencl_raytracer_amd.renderer import Renderer\n"
-            "CAM = %r\n"
-            "sc, tex, sky = scene.render_map_scene(), textures.texture_layers(), textures.skybox_cross(64)\n" % (ROOT, CAM)) + snippet
-    return subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
+_run = run_child
 
 
 REFUSED = {
@@ -331,19 +297,15 @@ def test_mode_off_set_explicitly_is_the_default(R, demo_scene, tex, sky, n):
     for strict in (False, True):
         res = []
         for explicit in (False, True):
-            r = Renderer(demo_scene, tex, sky, W, H, depth=depth, strict=strict, supersample=n)
-            if explicit:
-                r.w.set_adaptive(-1)
-            r.look(**CAM)
-            frame = r.render().copy()
-            frame2 = r.render().copy()
-            flags = r.w.last_trace_flags()
-            costs = r.w.read_tile_costs()
-            assert r.w.read_refine_mask().size == 0 and r.w.get_adaptive() == -1
-            r.w.enable_counters(1)
-            r.render()
-            c = r.w.read_counters()
-            r.release()
+            with rendering(Renderer, demo_scene, tex, sky, W, H, setup=(lambda w: w.set_adaptive(-1)) if explicit else None, depth=depth, strict=strict,
+                           supersample=n) as r:
+                (frame, _), (frame2, _) = take(r, 2, rgb=False)
+                flags = r.w.last_trace_flags()
+                costs = r.w.read_tile_costs()
+                assert r.w.read_refine_mask().size == 0 and r.w.get_adaptive() == -1
+                r.w.enable_counters(1)
+                r.render()
+                c = r.w.read_counters()
             res.append((frame, frame2, costs, [c[k] for k in COUNTED], flags))
         assert not res[0][4] & F_LIST and bool(res[0][4] & F_SS) == (n > 1) and res[0][4] == res[1][4]
         assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1])

@@ -8,15 +8,9 @@ import numpy as np
 import pytest
 
 from conftest import CAM, ROOT, channel_diff
+from render_common import R, queued_on, released, rendering, take  # noqa: F401  (R: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def R():
-    import torch  # noqa: F401
-    from example_gui_opencl_raytracer_amd.renderer import Renderer
-    return Renderer
 
 
 def test_two_kernel_path_equals_fused_path(R, demo_scene, tex, sky):
@@ -24,10 +18,8 @@ def test_two_kernel_path_equals_fused_path(R, demo_scene, tex, sky):
     for strict in (True, False):
         outs = []
         for fuse in (True, False):
-            r = R(demo_scene, tex, sky, 200, 150, depth=15, strict=strict, fuse=fuse)
-            r.look(**CAM)
-            outs.append(r.render())
-            r.release()
+            with rendering(R, demo_scene, tex, sky, 200, 150, depth=15, strict=strict, fuse=fuse) as r:
+                outs.append(r.render())
         assert np.array_equal(outs[0], outs[1])
 
 
@@ -36,26 +28,23 @@ def test_ray_buffer_readback_is_the_raygen_kernel_output(R, oracle, demo_scene, 
     want = golden_frames["raygen_160x120"].view(np.uint32)
     for strict in (True, False):
         for fuse in (True, False):
-            r = R(demo_scene, tex, sky, 160, 120, depth=4, strict=strict, fuse=fuse)
-            r.look(**CAM)
-            r.render()
-            rays = r.read_rays()
-            r.release()
+            with rendering(R, demo_scene, tex, sky, 160, 120, depth=4, strict=strict, fuse=fuse) as r:
+                r.render()
+                rays = r.read_rays()
             assert np.array_equal(rays.view(np.uint32), want)
 
 
 def test_camera_args_can_be_reset_between_frames(R, oracle, demo_scene, tex, sky):
     """rayinteractive.c:98-103 re-sends raygen args 0-5 on every key event."""
     w, h = 160, 120
-    r = R(demo_scene, tex, sky, w, h, depth=4, strict=True)
     cams = [CAM, dict(origin=(0.9, 2.5, -7.9), look=(0.15, -0.05, 1.0), fov=90.0, focal=1.0),
             dict(origin=(1.2, 2.6, -7.5), look=(-0.1, -0.1, 1.0), fov=90.0, focal=1.0)]
-    for cam in cams + cams[:1]:
-        r.look(**cam)
-        got = r.render()
-        want, _, _ = oracle.render(oracle.camera(cam["origin"], cam["look"], 90.0, 1.0, w, h), demo_scene, tex, sky, 4)
-        assert (channel_diff(got, want) == 0).mean() >= 0.999
-    r.release()
+    with R(demo_scene, tex, sky, w, h, depth=4, strict=True) as r:
+        for cam in cams + cams[:1]:
+            r.look(**cam)
+            got = r.render()
+            want, _, _ = oracle.render(oracle.camera(cam["origin"], cam["look"], 90.0, 1.0, w, h), demo_scene, tex, sky, 4)
+            assert (channel_diff(got, want) == 0).mean() >= 0.999
 
 
 def test_png_ingest_equals_raw_ingest(R, demo_scene, tex, sky, tmp_path):
@@ -67,12 +56,9 @@ def test_png_ingest_equals_raw_ingest(R, demo_scene, tex, sky, tmp_path):
         paths.append(p)
     skyp = str(tmp_path / "sky.png")
     api.write_png_rgba(skyp, sky[0])
-    a = R(demo_scene, tex, sky, 160, 120, depth=4, strict=True)
-    a.look(**CAM)
-    b = R(demo_scene, None, None, 160, 120, depth=4, strict=True, texture_paths=paths, skybox_path=skyp)
-    b.look(**CAM)
-    assert np.array_equal(a.render(), b.render())
-    a.release(); b.release()
+    with rendering(R, demo_scene, tex, sky, 160, 120, depth=4, strict=True) as a, \
+         rendering(R, demo_scene, None, None, 160, 120, depth=4, strict=True, texture_paths=paths, skybox_path=skyp) as b:
+        assert np.array_equal(a.render(), b.render())
 
 
 @pytest.mark.parametrize("world", [2, 3, 8])
@@ -81,33 +67,25 @@ def test_row_strips_are_bit_identical_to_the_full_frame(R, demo_scene, tex, sky,
     from example_gui_opencl_raytracer_amd.renderer import strip_rows
     w, h, depth = 320, 200, 4
     for strict in (True, False):
-        full = R(demo_scene, tex, sky, w, h, depth=depth, strict=strict)
-        full.look(**CAM)
-        want = full.render()
-        full.release()
+        with rendering(R, demo_scene, tex, sky, w, h, depth=depth, strict=strict) as full:
+            want = full.render()
         for rank in range(world):
             r0, rows = strip_rows(h, world, rank)
-            s = R(demo_scene, tex, sky, w, h, depth=depth, strict=strict, first_row=r0, rows=rows)
-            s.look(**CAM)
-            assert np.array_equal(s.render(), want[r0 * w:(r0 + rows) * w])
-            s.release()
+            with rendering(R, demo_scene, tex, sky, w, h, depth=depth, strict=strict, first_row=r0, rows=rows) as s:
+                assert np.array_equal(s.render(), want[r0 * w:(r0 + rows) * w])
 
 
 @pytest.mark.parametrize("world", [2, 8])
 def test_interleaved_bands_are_bit_identical_to_the_full_frame(R, demo_scene, tex, sky, world):
     """bench.py's sharding: rank r renders every world-th 8-row band with global ids."""
     w, h, depth = 200, 16 * world, 4
-    full = R(demo_scene, tex, sky, w, h, depth=depth, strict=False)
-    full.look(**CAM)
-    want = full.render().reshape(h // 8, 8 * w)
-    full.release()
+    with rendering(R, demo_scene, tex, sky, w, h, depth=depth, strict=False) as full:
+        want = full.render().reshape(h // 8, 8 * w)
     for rank in range(world):
         for fuse in (True, False):
-            s = R(demo_scene, tex, sky, w, h, depth=depth, strict=False, bands=(world, rank), fuse=fuse)
-            s.look(**CAM)
-            got = s.render().reshape(-1, 8 * w)
-            assert np.array_equal(got, want[rank::world])
-            s.release()
+            with rendering(R, demo_scene, tex, sky, w, h, depth=depth, strict=False, bands=(world, rank), fuse=fuse) as s:
+                got = s.render().reshape(-1, 8 * w)
+                assert np.array_equal(got, want[rank::world])
 
 
 def test_bands_with_the_grid_the_deep_build_and_the_sorted_dispatch(R, tex, sky):
@@ -122,18 +100,14 @@ def test_bands_with_the_grid_the_deep_build_and_the_sorted_dispatch(R, tex, sky)
     cam = dict(origin=(0.0, 5.0, -5.0), look=(0.0, -0.5, 1.0), fov=90.0, focal=1.0)
     w, h, world = 200, 96, 3
     for strict in (True, False):
-        full = R(sc, tex, sky, w, h, depth=6, strict=strict)
-        full.look(**cam)
-        want = full.render()
-        assert np.array_equal(full.render(), want)            # second frame: sorted order
-        full.release()
+        with rendering(R, sc, tex, sky, w, h, cam=cam, depth=6, strict=strict) as full:
+            want = full.render()
+            assert np.array_equal(full.render(), want)            # second frame: sorted order
         want = want.reshape(h // 8, 8 * w)
         for rank in range(world):
-            s = R(sc, tex, sky, w, h, depth=6, strict=strict, bands=(world, rank))
-            s.look(**cam)
-            for _ in range(2):
-                assert np.array_equal(s.render().reshape(-1, 8 * w), want[rank::world])
-            s.release()
+            with rendering(R, sc, tex, sky, w, h, cam=cam, depth=6, strict=strict, bands=(world, rank)) as s:
+                for _ in range(2):
+                    assert np.array_equal(s.render().reshape(-1, 8 * w), want[rank::world])
 
 
 def test_external_framebuffer_and_stream(R, demo_scene, tex, sky):
@@ -143,16 +117,11 @@ def test_external_framebuffer_and_stream(R, demo_scene, tex, sky):
     fb = torch.zeros(w * h, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     side = torch.cuda.Stream()
-    r = R(demo_scene, tex, sky, w, h, depth=4, strict=True, framebuffer_ptr=fb.data_ptr())
-    r.w.set_stream(side.cuda_stream)
-    r.w.set_async(True)
-    r.look(**CAM)
-    r.render(readback=False)
-    side.synchronize()
-    own = R(demo_scene, tex, sky, w, h, depth=4, strict=True)
-    own.look(**CAM)
-    assert np.array_equal(fb.cpu().numpy().view(np.uint32), own.render())
-    r.release(); own.release()
+    with rendering(R, demo_scene, tex, sky, w, h, setup=queued_on(side), depth=4, strict=True, framebuffer_ptr=fb.data_ptr()) as r:
+        r.render(readback=False)
+        side.synchronize()
+        with rendering(R, demo_scene, tex, sky, w, h, depth=4, strict=True) as own:
+            assert np.array_equal(fb.cpu().numpy().view(np.uint32), own.render())
 
 
 def test_partial_launch_and_reinit(R, oracle, demo_scene, tex, sky):
@@ -163,45 +132,37 @@ def test_partial_launch_and_reinit(R, oracle, demo_scene, tex, sky):
     from example_gui_opencl_raytracer_amd import api
     w, h = 160, 120
     want, _, _ = oracle.render(oracle.camera(CAM["origin"], CAM["look"], 90.0, 1.0, w, h), demo_scene, tex, sky, 4)
-    r = R(demo_scene, tex, sky, w, h, depth=4, strict=True)
-    r.look(**CAM)
     n = 5000                                             # rounds up to 5120 work-items
-    full = r.render()                                    # the whole frame through the normal path
-    assert (channel_diff(full, want) == 0).mean() >= 0.999
-    r.release()
+    with rendering(R, demo_scene, tex, sky, w, h, depth=4, strict=True) as r:
+        full = r.render()                                # the whole frame through the normal path
+        assert (channel_diff(full, want) == 0).mean() >= 0.999
     # a fresh wrap with another camera fills its framebuffer; a PARTIAL launch with the test camera then
     # re-traces ids [0, 5120) only: those equal the full frame, the rest keeps the other camera's pixels
-    r = R(demo_scene, tex, sky, w, h, depth=4, strict=True)
-    r.look(origin=(1.5, 2.0, -6.0), look=(-0.1, -0.1, 1.0), fov=90.0, focal=1.0)
-    other = r.render()
-    r.look(**CAM)
-    part = np.empty(w * h, np.uint32)
-    r.w.output(n, 0, 0, 0, 0, None)
-    r.w.output(n, part.nbytes, 1, 1, 10, part)
-    assert np.array_equal(part[:5120], full[:5120]) and np.array_equal(part[5120:], other[5120:])
-    assert not np.array_equal(other[:5120], full[:5120])
-    r.release()
+    with rendering(R, demo_scene, tex, sky, w, h, cam=dict(origin=(1.5, 2.0, -6.0), look=(-0.1, -0.1, 1.0), fov=90.0, focal=1.0), depth=4, strict=True) as r:
+        other = r.render()
+        r.look(**CAM)
+        part = np.empty(w * h, np.uint32)
+        r.w.output(n, 0, 0, 0, 0, None)
+        r.w.output(n, part.nbytes, 1, 1, 10, part)
+        assert np.array_equal(part[:5120], full[:5120]) and np.array_equal(part[5120:], other[5120:])
+        assert not np.array_equal(other[:5120], full[:5120])
     assert r.w.w.impl is None or r.w.w.impl == 0
-    again = R(demo_scene, tex, sky, w, h, depth=4, strict=True)          # re-init after release
-    again.look(**CAM)
-    assert np.array_equal(again.render(), full)
-    again.release()
+    with rendering(R, demo_scene, tex, sky, w, h, depth=4, strict=True) as again:          # re-init after release
+        assert np.array_equal(again.render(), full)
 
 
 def test_timing_log(R, demo_scene, tex, sky):
-    r = R(demo_scene, tex, sky, 320, 240, depth=4)
-    r.look(**CAM)
-    r.render(readback=False)
-    r.w.timing_reset()
-    r.w.set_async(True)
-    for _ in range(5):
+    with rendering(R, demo_scene, tex, sky, 320, 240, depth=4) as r:
         r.render(readback=False)
-    r.w.sync()
-    n, ms = r.w.timing_get(1)
-    assert n == 5 and 0.0 < ms < 1000.0
-    n0, _ = r.w.timing_get(0)
-    assert n0 == 0                                    # fused: the raygen launch does no device work
-    r.release()
+        r.w.timing_reset()
+        r.w.set_async(True)
+        for _ in range(5):
+            r.render(readback=False)
+        r.w.sync()
+        n, ms = r.w.timing_get(1)
+        assert n == 5 and 0.0 < ms < 1000.0
+        n0, _ = r.w.timing_get(0)
+        assert n0 == 0                                    # fused: the raygen launch does no device work
 
 
 def test_pipelined_readback_returns_the_same_frame(R, demo_scene, tex, sky):
@@ -211,15 +172,11 @@ def test_pipelined_readback_returns_the_same_frame(R, demo_scene, tex, sky):
     w, h = 2560, 1664
     frames = {}
     for on in (1, 0):
-        r = R(demo_scene, tex, sky, w, h, depth=4)
-        r.w.set_pipeline(on)
-        r.look(**CAM)
-        a = r.render().copy()
-        b = r.render().copy()
-        r.look(origin=(1.5, 2.0, -7.0), look=(0.1, -0.1, 1.0), fov=80.0, focal=1.0)
-        c = r.render().copy()
-        frames[on] = (a, b, c)
-        r.release()
+        with rendering(R, demo_scene, tex, sky, w, h, setup=lambda wrap: wrap.set_pipeline(on), depth=4) as r:
+            (a, _), (b, _) = take(r, 2, rgb=False)
+            r.look(origin=(1.5, 2.0, -7.0), look=(0.1, -0.1, 1.0), fov=80.0, focal=1.0)
+            c = r.render().copy()
+            frames[on] = (a, b, c)
     for x, y in zip(frames[1], frames[0]):
         assert np.array_equal(x, y)
     assert np.array_equal(frames[1][0], frames[1][1]) and not np.array_equal(frames[1][0], frames[1][2])
@@ -227,12 +184,9 @@ def test_pipelined_readback_returns_the_same_frame(R, demo_scene, tex, sky):
     for (ww, hh) in ((2304, 1900), (640, 480)):
         outs = []
         for on in (1, 0):
-            r = R(demo_scene, tex, sky, ww, hh, depth=3)
-            r.w.set_pipeline(on)
-            r.look(**CAM)
-            r.render()
-            outs.append(r.render().copy())
-            r.release()
+            with rendering(R, demo_scene, tex, sky, ww, hh, setup=lambda wrap: wrap.set_pipeline(on), depth=3) as r:
+                r.render()
+                outs.append(r.render().copy())
         assert np.array_equal(outs[0], outs[1])
 
 
@@ -454,38 +408,37 @@ def test_scene_arrays_are_snapshotted_until_invalidated(R, oracle, demo_scene, t
     from example_gui_opencl_raytracer_amd.scene import RAY, Scene
     w, h, depth = 96, 64, 4
     sph = torch.from_numpy(np.frombuffer(demo_scene.spheres.tobytes(), np.uint8).copy()).cuda()
-    cw = api.ClWrap()
-    cw.set_depth(depth); cw.set_strict(True)
-    cam = api.perspective(CAM["origin"], CAM["look"], 90.0, 1.0, w, h)
-    f3 = lambda v: np.array([v[0], v[1], v[2], 0.0], np.float32)
-    for a, v in enumerate((f3(cam.im_corner), f3(cam.origin), f3(cam.up), f3(cam.right), np.float32(cam.w_factor), np.float32(cam.h_factor),
-                           np.uint32(w), np.uint32(h))):
-        cw.load_single_data(0, a, v)
-    cw.load_global_data(0, 8, None, RAY.itemsize * w * h)
-    cw.load_single_data(1, 0, cw.buffer_handle(0, 8))
-    cw.bind_device_buffer(1, 1, sph.data_ptr(), sph.numel())            # caller-owned sphere array
-    cw.load_global_data(1, 2, demo_scene.planes)
-    cw.load_global_data(1, 3, demo_scene.lights)
-    for a, n in ((4, len(demo_scene.spheres)), (5, len(demo_scene.planes)), (6, len(demo_scene.lights))):
-        cw.load_single_data(1, a, np.uint8(n))
-    cw.load_single_data(1, 7, np.uint32(w * h))
-    cw.load_images_raw(1, 8, tex); cw.load_images_raw(1, 9, sky)
-    cw.load_global_data(1, 10, None, 4 * w * h)
+    with released(api.ClWrap()) as cw:
+        cw.set_depth(depth); cw.set_strict(True)
+        cam = api.perspective(CAM["origin"], CAM["look"], 90.0, 1.0, w, h)
+        f3 = lambda v: np.array([v[0], v[1], v[2], 0.0], np.float32)
+        for a, v in enumerate((f3(cam.im_corner), f3(cam.origin), f3(cam.up), f3(cam.right), np.float32(cam.w_factor), np.float32(cam.h_factor),
+                               np.uint32(w), np.uint32(h))):
+            cw.load_single_data(0, a, v)
+        cw.load_global_data(0, 8, None, RAY.itemsize * w * h)
+        cw.load_single_data(1, 0, cw.buffer_handle(0, 8))
+        cw.bind_device_buffer(1, 1, sph.data_ptr(), sph.numel())            # caller-owned sphere array
+        cw.load_global_data(1, 2, demo_scene.planes)
+        cw.load_global_data(1, 3, demo_scene.lights)
+        for a, n in ((4, len(demo_scene.spheres)), (5, len(demo_scene.planes)), (6, len(demo_scene.lights))):
+            cw.load_single_data(1, a, np.uint8(n))
+        cw.load_single_data(1, 7, np.uint32(w * h))
+        cw.load_images_raw(1, 8, tex); cw.load_images_raw(1, 9, sky)
+        cw.load_global_data(1, 10, None, 4 * w * h)
 
-    def frame():
-        out = np.empty(w * h, np.uint32)
-        cw.output(w * h, 0, 0, 0, 0, None)
-        cw.output(w * h, out.nbytes, 1, 1, 10, out)
-        return out
-    first = frame()
-    moved = demo_scene.spheres.copy()
-    moved["origin"][0] = (1.5, 0.5, -2.0)                       # sphere 0 moves into view
-    sph.copy_(torch.from_numpy(np.frombuffer(moved.tobytes(), np.uint8).copy()))
-    torch.cuda.synchronize()
-    assert np.array_equal(frame(), first)                       # still the snapshot
-    cw.invalidate_scene()
-    second = frame()
-    cw.release()
+        def frame():
+            out = np.empty(w * h, np.uint32)
+            cw.output(w * h, 0, 0, 0, 0, None)
+            cw.output(w * h, out.nbytes, 1, 1, 10, out)
+            return out
+        first = frame()
+        moved = demo_scene.spheres.copy()
+        moved["origin"][0] = (1.5, 0.5, -2.0)                       # sphere 0 moves into view
+        sph.copy_(torch.from_numpy(np.frombuffer(moved.tobytes(), np.uint8).copy()))
+        torch.cuda.synchronize()
+        assert np.array_equal(frame(), first)                       # still the snapshot
+        cw.invalidate_scene()
+        second = frame()
     ocam = oracle.camera(CAM["origin"], CAM["look"], 90.0, 1.0, w, h)
     want, _, _ = oracle.render(ocam, Scene(moved, demo_scene.planes, demo_scene.lights), tex, sky, depth)
     assert np.array_equal(second, want) and not np.array_equal(second, first)
@@ -496,12 +449,10 @@ def test_traced_ray_counter(R, oracle, demo_scene, tex, sky):
     the kernel elides those of surfaces whose specular and diffuse coefficients are both zero (glass)."""
     from example_gui_opencl_raytracer_amd.renderer import Renderer
     w, h, depth = 160, 120, 4
-    r = Renderer(demo_scene, tex, sky, w, h, depth=depth, strict=True)
-    r.look(**CAM)
-    r.w.enable_counters(1)
-    r.render(readback=False)
-    c = r.w.read_counters()
-    r.release()
+    with rendering(Renderer, demo_scene, tex, sky, w, h, depth=depth, strict=True) as r:
+        r.w.enable_counters(1)
+        r.render(readback=False)
+        c = r.w.read_counters()
     cam = oracle.camera(CAM["origin"], CAM["look"], 90.0, 1.0, w, h)
     _, _, cnt = oracle.render(cam, demo_scene, tex, sky, depth)
     assert c["shadow_rays"] == cnt.shadow_rays and c["segments"] == cnt.segments

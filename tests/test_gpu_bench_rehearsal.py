@@ -5,22 +5,16 @@ on rank 0 and, for config C5, the single PNG -- is the code the 8-GPU run uses. 
 single-GPU render."""
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from conftest import CAM, ROOT
+from conftest import ROOT
+from render_common import free_port as _free_port, rendering
 
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _run_bench(extra, png):
@@ -35,11 +29,8 @@ def _single_gpu_frame(demo_scene, tex, w, h):
     import torch  # noqa: F401
     from example_gui_opencl_raytracer_amd import textures
     from example_gui_opencl_raytracer_amd.renderer import Renderer
-    r = Renderer(demo_scene, tex, textures.skybox_cross(4096), w, h, depth=4)
-    r.look(**CAM)
-    want = r.render()
-    r.release()
-    return want
+    with rendering(Renderer, demo_scene, tex, textures.skybox_cross(4096), w, h, depth=4) as r:
+        return r.render()
 
 
 def _png_frame(path):

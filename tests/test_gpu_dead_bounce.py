@@ -8,6 +8,8 @@ import pytest
 
 from conftest import CAM
 from flags_common import F_COUNT, F_DEEP, F_GEOM_LDS, F_GRID, F_SHAPE
+from render_common import R, rendering  # noqa: F401  (R: the fixture)
+from shape_common import frame
 
 pytestmark = pytest.mark.gpu
 
@@ -18,25 +20,6 @@ GRID_CAM = dict(origin=(0.0, 12.0, -10.0), look=(0.0, -0.45, 1.0), fov=90.0, foc
 # float -> int conversion / image read in the reference, so there is no defined frame to hold either variant to.  Every other seed runs.
 FUZZ_SKIPPED = (11,)
 FUZZ_SEEDS = [s for s in range(40) if s not in FUZZ_SKIPPED]
-
-
-@pytest.fixture(scope="module")
-def R():
-    import torch  # noqa: F401  (the shim then shares torch's ROCm runtime)
-    from example_gui_opencl_raytracer_amd.renderer import Renderer
-    return Renderer
-
-
-def frame(R, sc, tex, sky, w, h, depth, variant, cam=CAM, strict=False):
-    """-> (packed frame, float radiance, flags of the trace launch)"""
-    r = R(sc, tex, sky, w, h, depth=depth, strict=strict)
-    try:
-        r.w.set_variant(variant)
-        r.look(**cam)
-        out, rgb = r.render_rgb()
-        return out, rgb, r.w.last_trace_flags()
-    finally:
-        r.release()
 
 
 def check_pair(R, sc, tex, sky, w, h, depth, cam=CAM, strict=False, base=0):
@@ -108,16 +91,11 @@ def test_grid_scene(R, tex, sky, strict):
 def _costs(R, sc, tex, sky, w, h, depth, variant, cam, frames=3):
     """The per-tile cost buffer after `frames` frames (the later ones dispatched in the order the earlier ones' costs gave), read back as
     tools/tile_costs.py reads it."""
-    r = R(sc, tex, sky, w, h, depth=depth)
-    try:
-        r.w.set_variant(variant)
-        r.look(**cam)
+    with rendering(R, sc, tex, sky, w, h, setup=lambda wrap: wrap.set_variant(variant), cam=cam, depth=depth) as r:
         for _ in range(frames):
             r.render(readback=False)
         r.w.sync()
         return r.w.read_tile_costs().copy(), r.w.last_trace_flags()
-    finally:
-        r.release()
 
 
 @pytest.mark.parametrize("base", [0, V_GENERIC])
@@ -150,17 +128,12 @@ LOOP_KEYS = WORK_KEYS + ("lane_iters", "wave_iters_x64", "lights_classified", "v
 
 
 def _counted(R, sc, tex, sky, w, h, depth, variant, cam, strict):
-    r = R(sc, tex, sky, w, h, depth=depth, strict=strict)
-    try:
-        r.w.set_variant(variant)
-        r.look(**cam)
+    with rendering(R, sc, tex, sky, w, h, setup=lambda wrap: wrap.set_variant(variant), cam=cam, depth=depth, strict=strict) as r:
         r.w.enable_counters(1)
         img = r.render()
         c = r.w.read_counters()
         assert r.w.last_trace_flags() & F_COUNT
         return img, c
-    finally:
-        r.release()
 
 
 @pytest.mark.parametrize("strict", [False, True])

@@ -5,10 +5,10 @@ import numpy as np
 import pytest
 
 import sched_common as sc
-from adaptive_common import resolve, same_floats
 from conftest import CAM
 from flags_common import F_COUNT, F_DEEP, F_OCC, F_D8, F_D16
 from parity_common import check_exact
+from render_common import R, released, rendering, resolve, same_floats, take  # noqa: F401  (R: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -20,19 +20,11 @@ TAIL_KEYS = ("segments", "shadow_rays", "light_probes", "sky_fetches", "texel_fe
 
 
 @pytest.fixture(scope="module")
-def R():
-    import torch  # noqa: F401  (the shim then shares torch's ROCm runtime)
-    from example_gui_opencl_raytracer_amd.renderer import Renderer
-    return Renderer
-
-
-@pytest.fixture(scope="module")
 def wrap(R):
     """A wrapper to run the builder on: clw_ext_unit_sched needs no scene."""
     from example_gui_opencl_raytracer_amd import api
-    w = api.ClWrap("src/cl/raygen.cl", "raygen", "src/cl/raytracing.cl", "raytracer")
-    yield w
-    w.release()
+    with released(api.ClWrap("src/cl/raygen.cl", "raygen", "src/cl/raytracing.cl", "raytracer")) as w:
+        yield w
 
 
 # ------------------------------------------------------------ C. wt_sched_build on synthetic cost tables
@@ -199,12 +191,10 @@ def test_forced_split_on_render_map(R, oracle, demo_scene, tex, sky, w, h, stric
     the edge tiles own no pixel), the order the launch read
     is the one the contract gives for the costs it was built from, and frame, radiance and ray counters are the per-lane loop's."""
     cam = CLOSE_CAM if w < 100 else CAM
-    r = R(demo_scene, tex, sky, w, h, depth=15, strict=strict)
-    r.look(**cam)
-    ref = per_lane(r)
-    for tpt in ((-1, -1), (64, 1)):
-        check_split_frame(f"render.map {w}x{h} strict={strict} tail at {tpt[0]}", forced_split(r, 4, tpt), ref, 4)
-    r.release()
+    with rendering(R, demo_scene, tex, sky, w, h, cam=cam, depth=15, strict=strict) as r:
+        ref = per_lane(r)
+        for tpt in ((-1, -1), (64, 1)):
+            check_split_frame(f"render.map {w}x{h} strict={strict} tail at {tpt[0]}", forced_split(r, 4, tpt), ref, 4)
     if strict:
         want, _, _ = oracle.render(oracle.camera(cam["origin"], cam["look"], 90.0, 1.0, w, h), demo_scene, tex, sky, 15)
         check_exact(ref[0], want, f"forced split / per-lane loop vs oracle: render.map {w}x{h}")
@@ -216,17 +206,15 @@ def test_forced_split_with_a_pool_the_tail_gives_up_on(R, oracle, tex, sky, stri
     per-lane loop finishes it."""
     from example_gui_opencl_raytracer_amd import scene
     field = scene.dielectric_field_scene(4)
-    r = R(field, tex, sky, 160, 120, depth=15, strict=strict)
-    r.look(**GLASS_CAM)
-    ref = per_lane(r)
-    per_node = (29 + 4 * 3) if strict else (27 + 3)
-    words = (25 + 36) * 64 + 15 * 192 + per_node * 192 + 63
-    r.w.set_tpt(-1, -1, max(1, (words * 8192 * 4) >> 20))
-    for tpt in ((24, -1), (64, 1)):
-        got = forced_split(r, 4, tpt)
-        assert got[2]["tpt_gave_up"] > 0, got[2]
-        check_split_frame(f"glass field, small pool, strict={strict}, tail at {tpt[0]}", got, ref, 4)
-    r.release()
+    with rendering(R, field, tex, sky, 160, 120, cam=GLASS_CAM, depth=15, strict=strict) as r:
+        ref = per_lane(r)
+        per_node = (29 + 4 * 3) if strict else (27 + 3)
+        words = (25 + 36) * 64 + 15 * 192 + per_node * 192 + 63
+        r.w.set_tpt(-1, -1, max(1, (words * 8192 * 4) >> 20))
+        for tpt in ((24, -1), (64, 1)):
+            got = forced_split(r, 4, tpt)
+            assert got[2]["tpt_gave_up"] > 0, got[2]
+            check_split_frame(f"glass field, small pool, strict={strict}, tail at {tpt[0]}", got, ref, 4)
     if strict:
         want, _, _ = oracle.render(oracle.camera(GLASS_CAM["origin"], GLASS_CAM["look"], 90.0, 1.0, 160, 120), field, tex, sky, 15)
         check_exact(ref[0], want, "forced split with a small pool / per-lane loop vs oracle: glass field 160x120")
@@ -237,19 +225,15 @@ def test_forced_split_with_a_pool_the_tail_gives_up_on(R, oracle, tex, sky, stri
 def test_forced_split_of_supersampled_launches(R, oracle, demo_scene, tex, sky, n, W, H, max_lg, strict):
     """A part of a split tile must hold whole n x n sample groups: at most 4 parts with n = 2, 2 with n = 4.  The frame is the resolve of the
     1-sample per-lane frame of the n*W x n*H view."""
-    v = R(demo_scene, tex, sky, n * W, n * H, depth=15, strict=strict)
-    v.look(**CAM)
-    v.w.set_variant(16)
-    virt_p, virt = v.render_rgb()
-    v.release()
+    with rendering(R, demo_scene, tex, sky, n * W, n * H, depth=15, strict=strict) as v:
+        v.w.set_variant(16)
+        (virt_p, virt), = take(v)
     if strict:      # the virtual frame is the oracle's, so the supersampled frame is the resolve of the oracle's samples
         want, _, _ = oracle.render(oracle.camera(CAM["origin"], CAM["look"], 90.0, 1.0, n * W, n * H), demo_scene, tex, sky, 15)
         check_exact(virt_p, want, f"virtual frame {n * W}x{n * H} of the supersampled forced split vs oracle")
     want_p, want_f = resolve(virt, W, H, n)
-    r = R(demo_scene, tex, sky, W, H, depth=15, strict=strict, supersample=n)
-    r.look(**CAM)
-    img, rgb, c, order, cap, shares = forced_split(r, max_lg, (64, 1))
-    r.release()
+    with rendering(R, demo_scene, tex, sky, W, H, depth=15, strict=strict, supersample=n) as r:
+        img, rgb, c, order, cap, shares = forced_split(r, max_lg, (64, 1))
     errs = sc.check_order(order, shares, cap)
     assert errs == [], errs[:4]
     assert sc.order_lgs(order, cap).max() == max_lg
@@ -265,16 +249,14 @@ def test_launches_that_must_not_split(R, demo_scene, tex, sky, case, strict):
     the order is the unsplit one of the costs it was built from."""
     from sphere_motion_common import DISP
     n, W, H, kw = (8, 20, 15, {}) if case == "n = 8" else (2, 80, 60, dict(motion=DISP))
-    r = R(demo_scene, tex, sky, W, H, depth=15, strict=strict, supersample=n, **kw)
-    r.look(**CAM)
-    r.w.set_split(4096, 1)
-    r.render(readback=False)
-    tpr, trows = (n * W + 7) // 8, (n * H + 7) // 8
-    cost = r.w.read_tile_costs().reshape(trows, tpr)
-    r.render(readback=False)
-    r.render(readback=False)
-    order, cap = r.w.read_tile_order()
-    r.release()
+    with rendering(R, demo_scene, tex, sky, W, H, depth=15, strict=strict, supersample=n, **kw) as r:
+        r.w.set_split(4096, 1)
+        r.render(readback=False)
+        tpr, trows = (n * W + 7) // 8, (n * H + 7) // 8
+        cost = r.w.read_tile_costs().reshape(trows, tpr)
+        r.render(readback=False)
+        r.render(readback=False)
+        order, cap = r.w.read_tile_order()
     assert cap == sc.per_share_of(tpr, trows) and order.size == 8 * cap
     assert cost.max() > 16, "costs a quota of 1 would split"
     assert sc.check_order(order, sc.model(cost, 0, cap, 0, 1, 0), cap) == []
@@ -299,12 +281,9 @@ def test_stack_flavours_at_their_edges(R, oracle, glass8, tex, sky, depth, stric
     assert cnt.max_stack == depth, (depth, int(cnt.max_stack))
     outs = []
     for variant in (0, 2048, 64, 64 | 2048):
-        r = R(glass8, tex, sky, w, h, depth=depth, strict=strict)
-        r.w.set_variant(variant)
-        r.look(**GLASS_CAM)
-        outs.append(r.render_rgb())
-        flags = r.w.last_trace_flags()
-        r.release()
+        with rendering(R, glass8, tex, sky, w, h, setup=lambda wrap: wrap.set_variant(variant), cam=GLASS_CAM, depth=depth, strict=strict) as r:
+            outs += take(r)
+            flags = r.w.last_trace_flags()
         want_flavour = 0 if variant & 2048 else (F_D8 if depth <= 8 else (F_D16 if depth <= 16 else 0))
         assert flags & F_DEEP and not flags & (F_COUNT | F_OCC) and flags & (F_D8 | F_D16) == want_flavour, (depth, variant, flags)
     for p, f in outs[1:]:
@@ -324,16 +303,14 @@ def test_the_top_of_the_full_stack(R, oracle, tex, sky, strict):
     import time
     import fuzz_scenes as F
     sc_, cam = F.deep_scene(F.DEEP_TOP_SEED)
-    r = R(sc_, tex, sky, F.DEEP_W, F.DEEP_H, depth=32, strict=strict)
-    r.look(**cam)
-    t0 = time.time()
-    ref = mode_frame(r, "per-lane loop", one_launch=True)
-    t1 = time.time()
-    got = mode_frame(r, "tail at 64, forced split", one_launch=True)
-    print(f"deep scene {F.DEEP_TOP_SEED} depth 32 strict={strict}: per-lane launch {t1 - t0:.2f} s, two launches through the split tail {time.time() - t1:.2f} s; "
-          f"tail tiles {got[2]['tpt_tiles']}, gave up {got[2]['tpt_gave_up']}, split entries {int((got[3] > 0).sum())}")
-    flags = r.w.last_trace_flags()
-    r.release()
+    with rendering(R, sc_, tex, sky, F.DEEP_W, F.DEEP_H, cam=cam, depth=32, strict=strict) as r:
+        t0 = time.time()
+        ref = mode_frame(r, "per-lane loop", one_launch=True)
+        t1 = time.time()
+        got = mode_frame(r, "tail at 64, forced split", one_launch=True)
+        print(f"deep scene {F.DEEP_TOP_SEED} depth 32 strict={strict}: per-lane launch {t1 - t0:.2f} s, two launches through the split tail {time.time() - t1:.2f} s; "
+              f"tail tiles {got[2]['tpt_tiles']}, gave up {got[2]['tpt_gave_up']}, split entries {int((got[3] > 0).sum())}")
+        flags = r.w.last_trace_flags()
     assert flags & F_DEEP and not flags & (F_D8 | F_D16)
     assert ref[2]["tpt_tiles"] == 0 and got[2]["tpt_tiles"] > 0 and (got[3] > 0).any()
     assert np.array_equal(got[0], ref[0]) and same_floats(got[1], ref[1])
@@ -399,30 +376,27 @@ def test_tail_modes_on_deep_scenes(R, oracle, tex, sky, seed, strict):
     five modes per depth, all bit-equal in the packed frame, the float radiance and the ray counters; the strict frames are the oracle's."""
     import fuzz_scenes as F
     sc_, cam = F.deep_scene(seed)
-    r = R(sc_, tex, sky, F.DEEP_W, F.DEEP_H, depth=5, strict=strict)
-    r.look(**cam)
-    for depth in F.DEEP_SEEDS[seed]:
-        r.w.set_depth(depth)
-        what = f"deep scene {seed} ({len(sc_.lights)} lights) depth {depth} strict={strict}"
-        frame = check_modes(r, what)
-        if strict:
-            want, _, _ = oracle.render(oracle.camera(cam["origin"], cam["look"], cam["fov"], cam["focal"], F.DEEP_W, F.DEEP_H), sc_, tex, sky, depth)
-            check_exact(frame, want, what)
-    r.release()
+    with rendering(R, sc_, tex, sky, F.DEEP_W, F.DEEP_H, cam=cam, depth=5, strict=strict) as r:
+        for depth in F.DEEP_SEEDS[seed]:
+            r.w.set_depth(depth)
+            what = f"deep scene {seed} ({len(sc_.lights)} lights) depth {depth} strict={strict}"
+            frame = check_modes(r, what)
+            if strict:
+                want, _, _ = oracle.render(oracle.camera(cam["origin"], cam["look"], cam["fov"], cam["focal"], F.DEEP_W, F.DEEP_H), sc_, tex, sky, depth)
+                check_exact(frame, want, what)
 
 
 def test_fast_tail_on_the_uniform_grid(R, tex, sky):
     """The fast build's tail with segments that walk the uniform grid: 576 spheres at depth 8, everything through the tail."""
     from example_gui_opencl_raytracer_amd import scene
-    r = R(scene.sphere_grid_scene(24, 24), tex, sky, 160, 96, depth=8, strict=False)
-    r.look(origin=(0.0, 6.0, -8.0), look=(0.0, -0.45, 1.0), fov=90.0, focal=1.0)
-    ref = mode_frame(r, "per-lane loop")
-    for mode in ("tail", "tail at 64"):
-        img, rgb, c, _ = mode_frame(r, mode)
-        assert c["tpt_tiles"] > 0 and np.array_equal(img, ref[0]) and same_floats(rgb, ref[1]), mode
-        assert all(c[k] == ref[2][k] for k in TAIL_KEYS), (mode, {k: (c[k], ref[2][k]) for k in TAIL_KEYS})
-    assert r.w.last_trace_flags() & 16, "the launch did not walk the grid"
-    r.release()
+    cam = dict(origin=(0.0, 6.0, -8.0), look=(0.0, -0.45, 1.0), fov=90.0, focal=1.0)
+    with rendering(R, scene.sphere_grid_scene(24, 24), tex, sky, 160, 96, cam=cam, depth=8, strict=False) as r:
+        ref = mode_frame(r, "per-lane loop")
+        for mode in ("tail", "tail at 64"):
+            img, rgb, c, _ = mode_frame(r, mode)
+            assert c["tpt_tiles"] > 0 and np.array_equal(img, ref[0]) and same_floats(rgb, ref[1]), mode
+            assert all(c[k] == ref[2][k] for k in TAIL_KEYS), (mode, {k: (c[k], ref[2][k]) for k in TAIL_KEYS})
+        assert r.w.last_trace_flags() & 16, "the launch did not walk the grid"
 
 
 @pytest.mark.parametrize("strict", [True, False], ids=["strict", "fast"])
@@ -435,15 +409,13 @@ def test_tail_with_255_lights(R, oracle, demo_scene, tex, sky, strict):
     lights["origin"][:, :3] += rng.uniform(-1.5, 1.5, (255, 3)).astype(np.float32)
     lights["intensity"] *= np.float32(1 / 40)
     many = scene.Scene(demo_scene.spheres, demo_scene.planes, lights)
-    r = R(many, tex, sky, 24, 16, depth=5, strict=strict)
-    r.look(**CLOSE_CAM)
-    if not strict:
-        # a slot of the default pool holds 192 strict nodes of 29 + 4 * 255 words, but 896 fast ones of 27 + 255: the fast build gets the pool
-        # that gives its slots 192 nodes as well (the sizes of the give-up test of test_gpu_parity.py)
-        words = (25 + 36) * 64 + 5 * 192 + (27 + 255) * 192 + 63
-        r.w.set_tpt(-1, -1, (words * 8192 * 4) >> 20)
-    frame = check_modes(r, f"255 lights strict={strict}", gave_up=True)
-    r.release()
+    with rendering(R, many, tex, sky, 24, 16, cam=CLOSE_CAM, depth=5, strict=strict) as r:
+        if not strict:
+            # a slot of the default pool holds 192 strict nodes of 29 + 4 * 255 words, but 896 fast ones of 27 + 255: the fast build gets the pool
+            # that gives its slots 192 nodes as well (the sizes of the give-up test of test_gpu_parity.py)
+            words = (25 + 36) * 64 + 5 * 192 + (27 + 255) * 192 + 63
+            r.w.set_tpt(-1, -1, (words * 8192 * 4) >> 20)
+        frame = check_modes(r, f"255 lights strict={strict}", gave_up=True)
     if strict:
         want, _, cnt = oracle.render(oracle.camera(CLOSE_CAM["origin"], CLOSE_CAM["look"], 90.0, 1.0, 24, 16), many, tex, sky, 5)
         assert cnt.int_cast_oor == 0 and cnt.oob_reads == 0

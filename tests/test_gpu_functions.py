@@ -5,6 +5,8 @@ strict build: bit-exact.  fast build: booleans equal away from thresholds, conti
 import numpy as np
 import pytest
 
+from render_common import bits, released
+
 pytestmark = pytest.mark.gpu
 
 OP = dict(sphere=0, plane=1, reflect=2, refract=3, schlick=4, cube=5, xorshift=6, emod=7, sincos=8, pow=9, normalize=10)
@@ -20,14 +22,9 @@ def inputs():
 def dev(request):
     import torch  # noqa: F401
     from example_gui_opencl_raytracer_amd import api
-    w = api.ClWrap()
-    w.set_strict(request.param)
-    yield w, request.param
-    w.release()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+    with released(api.ClWrap()) as w:
+        w.set_strict(request.param)
+        yield w, request.param
 
 
 def close(got, want, strict, rel=1e-4):
@@ -154,9 +151,8 @@ def scene_dev(request, demo_scene, tex, sky):
     """A wrapper with render.map bound through the reference's call protocol; the unit ops run on that scene."""
     import torch  # noqa: F401
     from example_gui_opencl_raytracer_amd.renderer import Renderer
-    r = Renderer(demo_scene, tex, sky, 64, 64, depth=4, strict=request.param)
-    yield r.w, request.param
-    r.release()
+    with Renderer(demo_scene, tex, sky, 64, 64, depth=4, strict=request.param) as r:
+        yield r.w, request.param
 
 
 def test_find_light_intersection(scene_dev, inputs, golden_vectors):

@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 import gbuffer_common as gc
-from gbuffer_common import bits
+from render_common import bits, released, rendering
 
 pytestmark = pytest.mark.gpu
 
@@ -34,21 +34,18 @@ _got = {}
 
 
 def render_case(name, strict, tex, sky, grid=True, **kw):
+    """`with render_case(...) as r:` -- a renderer of the case's scene that looks through the case's camera"""
     from example_gui_opencl_raytracer_amd.renderer import Renderer
     key, w, h, cam, _ = gc.CASES[name]
-    r = Renderer(gc.case_scene(name), tex, sky, w, h, depth=4, strict=strict, **kw)
-    if not grid:
-        r.w.set_grid(0)
-    r.look(**cam)
-    return r
+    return rendering(Renderer, gc.case_scene(name), tex, sky, w, h, setup=None if grid else (lambda wrap: wrap.set_grid(0)), cam=cam, depth=4,
+                     strict=strict, **kw)
 
 
 def gbuffer_of(name, strict, tex, sky):
     """The full-frame buffers of a case in one build, rendered once per module."""
     if (name, strict) not in _got:
-        r = render_case(name, strict, tex, sky)
-        _got[name, strict] = r.gbuffer()
-        r.release()
+        with render_case(name, strict, tex, sky) as r:
+            _got[name, strict] = r.gbuffer()
     return _got[name, strict]
 
 
@@ -113,18 +110,16 @@ def test_fast_build_point_and_normal(oracle, tex, sky, name):
     if case == name:
         g = gbuffer_of(case, False, tex, sky)
     else:
-        r = render_case(case, False, tex, sky, grid=False)
-        g = r.gbuffer()
-        r.release()
+        with render_case(case, False, tex, sky, grid=False) as r:
+            g = r.gbuffer()
     check_fast_geometry(g, gc.expected_case(oracle, case, tex, sky), name)
 
 
 @pytest.mark.parametrize("name", ["D0", "D1"])
 def test_linear_scan_of_a_big_scene_equals_the_oracle(oracle, tex, sky, strict, name):
     """324 spheres with the uniform grid switched off: the scene read from global memory, every sphere tested."""
-    r = render_case(name, strict, tex, sky, grid=False)
-    g = r.gbuffer()
-    r.release()
+    with render_case(name, strict, tex, sky, grid=False) as r:
+        g = r.gbuffer()
     check_against_oracle(g, gc.expected_case(oracle, name, tex, sky), strict, name + " (no grid)")
     if strict:
         assert_same_bits(g, gbuffer_of(name, strict, tex, sky))
@@ -133,22 +128,21 @@ def test_linear_scan_of_a_big_scene_equals_the_oracle(oracle, tex, sky, strict, 
 def test_channel_mask(tex, sky, strict):
     from example_gui_opencl_raytracer_amd import api
     full = gbuffer_of("A", strict, tex, sky)
-    r = render_case("A", strict, tex, sky)
-    g = r.gbuffer(api.GB_DEPTH | api.GB_ID)
-    assert set(g) == {"depth", "id"}
-    assert_same_bits(g, {k: full[k] for k in g})
-    assert r.w.read_gbuffer(api.GB_NORMAL).size == 0
-    assert r.w.L.clw_ext_read_gbuffer(C.byref(r.w.w), api.GB_NORMAL, None, 0) == 0
-    assert not r.w.gbuffer_device_ptr(api.GB_NORMAL)
-    assert r.w.gbuffer_device_ptr(api.GB_DEPTH) and r.w.gbuffer_device_ptr(api.GB_ID)
-    assert r.w.L.clw_ext_read_gbuffer(C.byref(r.w.w), api.GB_DEPTH, None, 0) == 4 * r.pixels
-    assert r.w.read_gbuffer(api.GB_ID).shape == (r.pixels,)
-    assert r.w.L.clw_ext_read_gbuffer(C.byref(r.w.w), api.GB_DEPTH | api.GB_ID, None, 0) == 0      # one bit at a time
-    assert r.w.render_gbuffer(0) == 0 and r.w.render_gbuffer(1 << 7) == 0          # no known bit: no pass, the last one stands
-    assert r.w.read_gbuffer(api.GB_DEPTH).shape == (r.pixels,)
-    # a later pass with more channels allocates the missing ones
-    assert_same_bits(r.gbuffer(), full)
-    r.release()
+    with render_case("A", strict, tex, sky) as r:
+        g = r.gbuffer(api.GB_DEPTH | api.GB_ID)
+        assert set(g) == {"depth", "id"}
+        assert_same_bits(g, {k: full[k] for k in g})
+        assert r.w.read_gbuffer(api.GB_NORMAL).size == 0
+        assert r.w.L.clw_ext_read_gbuffer(C.byref(r.w.w), api.GB_NORMAL, None, 0) == 0
+        assert not r.w.gbuffer_device_ptr(api.GB_NORMAL)
+        assert r.w.gbuffer_device_ptr(api.GB_DEPTH) and r.w.gbuffer_device_ptr(api.GB_ID)
+        assert r.w.L.clw_ext_read_gbuffer(C.byref(r.w.w), api.GB_DEPTH, None, 0) == 4 * r.pixels
+        assert r.w.read_gbuffer(api.GB_ID).shape == (r.pixels,)
+        assert r.w.L.clw_ext_read_gbuffer(C.byref(r.w.w), api.GB_DEPTH | api.GB_ID, None, 0) == 0      # one bit at a time
+        assert r.w.render_gbuffer(0) == 0 and r.w.render_gbuffer(1 << 7) == 0          # no known bit: no pass, the last one stands
+        assert r.w.read_gbuffer(api.GB_DEPTH).shape == (r.pixels,)
+        # a later pass with more channels allocates the missing ones
+        assert_same_bits(r.gbuffer(), full)
 
 
 def test_strips_compose(tex, sky, strict):
@@ -160,9 +154,8 @@ def test_strips_compose(tex, sky, strict):
         r0, n = strip_rows(gc.H, 3, rank)
         assert r0 == rows and n > 0
         rows += n
-        r = render_case("A", strict, tex, sky, first_row=r0, rows=n)
-        parts.append(r.gbuffer())
-        r.release()
+        with render_case("A", strict, tex, sky, first_row=r0, rows=n) as r:
+            parts.append(r.gbuffer())
     assert rows == gc.H and strip_rows(gc.H, 3, 2)[1] % 8 != 0
     assert_same_bits({k: np.concatenate([p[k] for p in parts]) for k in CHANNELS}, full)
 
@@ -173,11 +166,8 @@ def test_row_bands_compose(tex, sky, strict):
     w, h = gc.W, 32
     cam = gc.CASES["A"][3]
     def one(**kw):
-        r = Renderer(gc.case_scene("A"), tex, sky, w, h, depth=4, strict=strict, **kw)
-        r.look(**cam)
-        g = r.gbuffer()
-        r.release()
-        return g
+        with rendering(Renderer, gc.case_scene("A"), tex, sky, w, h, cam=cam, depth=4, strict=strict, **kw) as r:
+            return r.gbuffer()
     full = one()
     built = {k: np.zeros_like(full[k]) for k in CHANNELS}
     for phase in range(2):
@@ -207,27 +197,25 @@ def test_pick_is_the_buffers_entry(oracle, tex, sky, strict):
     sphere_px = int(np.flatnonzero(~miss & (kind == gc.KIND_SPHERE))[0])
     light_px = int(np.flatnonzero(~miss & (kind == gc.KIND_LIGHT))[0])
     pixels = [(0, 0), (W - 1, 0), (0, H - 1), (W - 1, H - 1), (66, 10), (20, 34), (sphere_px % W, sphere_px // W), (light_px % W, light_px // W)]
-    r = render_case("A", strict, tex, sky)
-    for x, y in pixels:
-        pick_equals(r.pick(x, y), full, y * W + x)
-    if strict:
-        assert r.pick(sphere_px % W, sphere_px // W)["kind"] == gc.KIND_SPHERE and r.pick(light_px % W, light_px // W)["kind"] == gc.KIND_LIGHT
-    assert r.pick(W, 0) is None and r.pick(0, H) is None                  # outside the frame
-    # a pick leaves the last pass's buffers alone
-    g = r.gbuffer()
-    r.pick(3, 3)
-    assert_same_bits({k: r.w.read_gbuffer(bit) for k, (bit, _, _) in api.GB_CHANNELS.items()}, g)
-    r.release()
+    with render_case("A", strict, tex, sky) as r:
+        for x, y in pixels:
+            pick_equals(r.pick(x, y), full, y * W + x)
+        if strict:
+            assert r.pick(sphere_px % W, sphere_px // W)["kind"] == gc.KIND_SPHERE and r.pick(light_px % W, light_px // W)["kind"] == gc.KIND_LIGHT
+        assert r.pick(W, 0) is None and r.pick(0, H) is None                  # outside the frame
+        # a pick leaves the last pass's buffers alone
+        g = r.gbuffer()
+        r.pick(3, 3)
+        assert_same_bits({k: r.w.read_gbuffer(bit) for k, (bit, _, _) in api.GB_CHANNELS.items()}, g)
     # a sky pixel of case B
     eb = gc.expected_case(oracle, "B", tex, sky)
     sky_px = int(np.flatnonzero(eb["id"] == gc.ID_NONE)[0])
     fb = gbuffer_of("B", strict, tex, sky)
-    r = render_case("B", strict, tex, sky)
-    p = r.pick(sky_px % W, sky_px // W)
-    pick_equals(p, fb, sky_px)
-    if strict:
-        assert p["id"] == gc.ID_NONE and np.isposinf(p["depth"]) and not p["point"].any() and not p["albedo"].any()
-    r.release()
+    with render_case("B", strict, tex, sky) as r:
+        p = r.pick(sky_px % W, sky_px // W)
+        pick_equals(p, fb, sky_px)
+        if strict:
+            assert p["id"] == gc.ID_NONE and np.isposinf(p["depth"]) and not p["point"].any() and not p["albedo"].any()
 
 
 def test_pick_in_a_strip_and_in_a_band(tex, sky, strict):
@@ -235,77 +223,69 @@ def test_pick_in_a_strip_and_in_a_band(tex, sky, strict):
     W, H = gc.W, gc.H
     full = gbuffer_of("A", strict, tex, sky)
     r0, n = strip_rows(H, 3, 1)                                           # rows 16..31
-    r = render_case("A", strict, tex, sky, first_row=r0, rows=n)
-    assert r.pick(5, r0 - 1) is None and r.pick(5, r0 + n) is None and r.pick(5, 0) is None
-    pick_equals(r.pick(5, r0), full, r0 * W + 5)
-    pick_equals(r.pick(W - 1, r0 + n - 1), full, (r0 + n - 1) * W + W - 1)
-    r.release()
+    with render_case("A", strict, tex, sky, first_row=r0, rows=n) as r:
+        assert r.pick(5, r0 - 1) is None and r.pick(5, r0 + n) is None and r.pick(5, 0) is None
+        pick_equals(r.pick(5, r0), full, r0 * W + 5)
+        pick_equals(r.pick(W - 1, r0 + n - 1), full, (r0 + n - 1) * W + W - 1)
     cam = gc.CASES["A"][3]
-    a = Renderer(gc.case_scene("A"), tex, sky, W, 32, depth=4, strict=strict)
-    b = Renderer(gc.case_scene("A"), tex, sky, W, 32, depth=4, strict=strict, bands=(2, 1))
-    a.look(**cam); b.look(**cam)
-    ga = a.gbuffer()
-    assert b.pick(7, 3) is None and b.pick(7, 16) is None                 # bands 0 and 2 belong to phase 0
-    for y in (8, 15, 24, 31):
-        pick_equals(b.pick(7, y), ga, y * W + 7)
-    a.release(); b.release()
+    with Renderer(gc.case_scene("A"), tex, sky, W, 32, depth=4, strict=strict) as a, \
+         Renderer(gc.case_scene("A"), tex, sky, W, 32, depth=4, strict=strict, bands=(2, 1)) as b:
+        a.look(**cam); b.look(**cam)
+        ga = a.gbuffer()
+        assert b.pick(7, 3) is None and b.pick(7, 16) is None                 # bands 0 and 2 belong to phase 0
+        for y in (8, 15, 24, 31):
+            pick_equals(b.pick(7, y), ga, y * W + 7)
 
 
 def test_nothing_latched_returns_zero_and_the_process_lives_on(tex, sky, strict):
     from example_gui_opencl_raytracer_amd import api
     from example_gui_opencl_raytracer_amd.renderer import Renderer
-    w = api.ClWrap()
-    w.set_strict(strict)
-    assert w.pick(0, 0) is None and w.render_gbuffer(api.GB_ALL) == 0
-    assert w.read_gbuffer(api.GB_DEPTH).size == 0 and not w.gbuffer_device_ptr(api.GB_DEPTH)
-    w.release()
-    r = Renderer(gc.case_scene("A"), tex, sky, gc.W, gc.H, depth=4, strict=strict)      # a scene, but no raygen launch yet
-    assert r.pick(1, 1) is None and r.w.render_gbuffer(api.GB_ALL) == 0
-    with pytest.raises(RuntimeError):
-        r.gbuffer()
-    r.look(**gc.CASES["A"][3])
-    assert_same_bits(r.gbuffer(), gbuffer_of("A", strict, tex, sky))
-    r.release()
+    with released(api.ClWrap()) as w:
+        w.set_strict(strict)
+        assert w.pick(0, 0) is None and w.render_gbuffer(api.GB_ALL) == 0
+        assert w.read_gbuffer(api.GB_DEPTH).size == 0 and not w.gbuffer_device_ptr(api.GB_DEPTH)
+    with Renderer(gc.case_scene("A"), tex, sky, gc.W, gc.H, depth=4, strict=strict) as r:      # a scene, but no raygen launch yet
+        assert r.pick(1, 1) is None and r.w.render_gbuffer(api.GB_ALL) == 0
+        with pytest.raises(RuntimeError):
+            r.gbuffer()
+        r.look(**gc.CASES["A"][3])
+        assert_same_bits(r.gbuffer(), gbuffer_of("A", strict, tex, sky))
 
 
 def test_sampling_modes_do_not_change_the_buffers(tex, sky, strict):
     full = gbuffer_of("A", strict, tex, sky)
     disp = np.array([[0.5, 0.0, 0.0], [0.0, 0.3, 0.0], [0.0, 0.0, -0.4], [0.2, 0.2, 0.2]], np.float32)
     for kw in (dict(supersample=4, lens=(0.1, 8.0)), dict(supersample=2, motion=disp)):
-        r = render_case("A", strict, tex, sky, **kw)
-        assert_same_bits(r.gbuffer(), full)
-        r.render()                                                        # ... and with the mode's tables on the device
-        assert_same_bits(r.gbuffer(), full)
-        pick_equals(r.pick(40, 20), full, 20 * gc.W + 40)
-        r.release()
+        with render_case("A", strict, tex, sky, **kw) as r:
+            assert_same_bits(r.gbuffer(), full)
+            r.render()                                                        # ... and with the mode's tables on the device
+            assert_same_bits(r.gbuffer(), full)
+            pick_equals(r.pick(40, 20), full, 20 * gc.W + 40)
 
 
 def test_an_accumulating_view_keeps_counting(tex, sky, strict):
     full = gbuffer_of("A", strict, tex, sky)
-    plain = render_case("A", strict, tex, sky, accumulate=8)
-    for _ in range(7):
-        plain.render()
-    want = plain.render_rgb()
-    assert plain.accumulated == 8
-    plain.release()
-    r = render_case("A", strict, tex, sky, accumulate=8)
-    for f in range(7):
-        r.render()
-        assert r.accumulated == f + 1
-        assert_same_bits(r.gbuffer(), full)
-        pick_equals(r.pick(33, 12), full, 12 * gc.W + 33)
-        assert r.accumulated == f + 1
-    got = r.render_rgb()
-    assert r.accumulated == 8
-    assert np.array_equal(got[0], want[0]) and np.array_equal(bits(got[1]), bits(want[1]))
-    r.release()
+    with render_case("A", strict, tex, sky, accumulate=8) as plain:
+        for _ in range(7):
+            plain.render()
+        want = plain.render_rgb()
+        assert plain.accumulated == 8
+    with render_case("A", strict, tex, sky, accumulate=8) as r:
+        for f in range(7):
+            r.render()
+            assert r.accumulated == f + 1
+            assert_same_bits(r.gbuffer(), full)
+            pick_equals(r.pick(33, 12), full, 12 * gc.W + 33)
+            assert r.accumulated == f + 1
+        got = r.render_rgb()
+        assert r.accumulated == 8
+        assert np.array_equal(got[0], want[0]) and np.array_equal(bits(got[1]), bits(want[1]))
 
 
 def test_the_frame_is_unchanged(tex, sky, strict):
-    r = render_case("A", strict, tex, sky)
-    before = r.render()
-    r.gbuffer()
-    r.pick(10, 10)
-    after = r.render()
-    assert np.array_equal(before, after)
-    r.release()
+    with render_case("A", strict, tex, sky) as r:
+        before = r.render()
+        r.gbuffer()
+        r.pick(10, 10)
+        after = r.render()
+        assert np.array_equal(before, after)

@@ -15,23 +15,16 @@ import pytest
 
 from conftest import CAM, channel_diff, frame_mask
 from parity_common import check_exact, report
+from render_common import R, rendering, take  # noqa: F401  (R: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def R():
-    import torch  # noqa: F401  (the shim then shares torch's ROCm runtime)
-    from example_gui_opencl_raytracer_amd.renderer import Renderer
-    return Renderer
-
-
-def gpu_frame(R, sc, tex, sky, w, h, depth, strict, cam=CAM, rgb=False, **kw):
-    r = R(sc, tex, sky, w, h, depth=depth, strict=strict, **kw)
-    r.look(**cam)
-    out = r.render_rgb() if rgb else r.render()
-    r.release()
-    return out
+def gpu_frame(R, sc, tex, sky, w, h, depth, strict, cam=CAM, rgb=False, setup=None, **kw):
+    """-> (packed, float) with rgb, else the packed frame; `setup(r.w)`: knobs set on the wrapper before the camera"""
+    with rendering(R, sc, tex, sky, w, h, setup=setup, cam=cam, depth=depth, strict=strict, **kw) as r:
+        (p, f), = take(r, rgb=rgb)
+        return (p, f) if rgb else p
 
 
 def device_libm_rows(w, log):
@@ -306,11 +299,7 @@ def test_uniform_grid_equals_linear_scan(R, oracle, tex, sky, cam, kind):
     outs = {}
     for strict in (True, False):
         for grid in (1, 0):
-            r = Renderer(sc, tex, sky, w, h, depth=depth, strict=strict)
-            r.w.set_grid(grid)
-            r.look(**cam)
-            outs[(strict, grid)] = r.render()
-            r.release()
+            outs[(strict, grid)] = gpu_frame(Renderer, sc, tex, sky, w, h, depth, strict, cam, setup=lambda wrap: wrap.set_grid(grid))
         assert np.array_equal(outs[(strict, 1)], outs[(strict, 0)])
     want, _, _ = oracle.render(oracle.camera(cam["origin"], cam["look"], cam["fov"], 1.0, w, h), sc, tex, sky, depth)
     check_exact(outs[(True, 1)], want, f"grid {kind}")
@@ -341,11 +330,7 @@ def test_light_spheres_seen_through_the_grid(R, oracle, tex, sky, kind):
         outs = {}
         for strict in (True, False):
             for grid in (1, 0):
-                r = Renderer(sc, tex, sky, w, h, depth=depth, strict=strict)
-                r.w.set_grid(grid)
-                r.look(**cam)
-                outs[(strict, grid)] = r.render()
-                r.release()
+                outs[(strict, grid)] = gpu_frame(Renderer, sc, tex, sky, w, h, depth, strict, cam, setup=lambda wrap: wrap.set_grid(grid))
             assert np.array_equal(outs[(strict, 1)], outs[(strict, 0)]), (kind, cam, strict)
         check_exact(outs[(True, 1)], want, f"lights through the grid, {kind}")
 
@@ -381,11 +366,7 @@ def test_random_sphere_cloud_through_the_grid(R, oracle, tex, sky, seed):
         outs = {}
         for strict in (True, False):
             for grid in (1, 0):
-                r = Renderer(sc, tex, sky, w, h, depth=depth, strict=strict)
-                r.w.set_grid(grid)
-                r.look(**cam)
-                outs[(strict, grid)] = r.render()
-                r.release()
+                outs[(strict, grid)] = gpu_frame(Renderer, sc, tex, sky, w, h, depth, strict, cam, setup=lambda wrap: wrap.set_grid(grid))
             assert np.array_equal(outs[(strict, 1)], outs[(strict, 0)]), (seed, cam, strict)
         check_exact(outs[(True, 1)], want, f"sphere cloud {seed}")
 
@@ -410,11 +391,7 @@ def test_nan_rays_on_the_grid_path_end_like_the_linear_scan(R, oracle, tex, sky)
     assert np.isnan(rgb).any()
     outs = {}
     for grid in (1, 0):
-        r = Renderer(sc, tex, sky, w, h, depth=depth, strict=True)
-        r.w.set_grid(grid)
-        r.look(**cam)
-        outs[grid] = r.render()
-        r.release()
+        outs[grid] = gpu_frame(Renderer, sc, tex, sky, w, h, depth, True, cam, setup=lambda wrap: wrap.set_grid(grid))
     assert np.array_equal(outs[1], outs[0])
     check_exact(outs[1], want, "NaN rays on the grid path")
 
@@ -423,11 +400,7 @@ def test_lds_and_global_geometry_paths_agree_exactly(R, demo_scene, tex, sky):
     from example_gui_opencl_raytracer_amd.renderer import Renderer
     outs = []
     for variant in (0, 1, 2, 3):               # bit 0: geometry from global memory, bit 1: linear id mapping
-        r = Renderer(demo_scene, tex, sky, 160, 120, depth=15, strict=True)
-        r.w.set_variant(variant)
-        r.look(**CAM)
-        outs.append(r.render())
-        r.release()
+        outs.append(gpu_frame(Renderer, demo_scene, tex, sky, 160, 120, 15, True, setup=lambda wrap: wrap.set_variant(variant)))
     for o in outs[1:]:
         assert np.array_equal(o, outs[0])
 
@@ -452,11 +425,7 @@ def test_plane_test_skipping_is_pure_work_skipping(R, demo_scene, tex, sky, stri
     for sc, cam, depth in cases:
         outs = []
         for variant in (0, 128):
-            r = Renderer(sc, tex, sky, 200, 120, depth=depth, strict=strict)
-            r.w.set_variant(variant)
-            r.look(**cam)
-            outs.append(r.render())
-            r.release()
+            outs.append(gpu_frame(Renderer, sc, tex, sky, 200, 120, depth, strict, cam, setup=lambda wrap: wrap.set_variant(variant)))
         assert np.array_equal(outs[0], outs[1])
 
 
@@ -483,6 +452,12 @@ def _vis_cases(demo_scene):
     return cases
 
 
+def verifying(wrap):
+    """the counting build in verification mode: classify AND trace"""
+    wrap.set_variant(1024)
+    wrap.enable_counters(1)
+
+
 def test_light_visibility_classes_are_pure_work_skipping(R, demo_scene, tex, sky):
     """wt_light_vis (strict build, small scenes) decides the shadow samples of a light without tracing them when every ray of the
     light's cone has the same outcome.  (1) Same bits with the classes off (variant 256).  (2) The counting build in verification
@@ -493,19 +468,11 @@ def test_light_visibility_classes_are_pure_work_skipping(R, demo_scene, tex, sky
     for sc, cam, depth in _vis_cases(demo_scene):
         outs = []
         for variant in (0, 256):
-            r = Renderer(sc, tex, sky, 240, 160, depth=depth, strict=strict)
-            r.w.set_variant(variant)
-            r.look(**cam)
-            outs.append(r.render())
-            r.release()
+            outs.append(gpu_frame(Renderer, sc, tex, sky, 240, 160, depth, strict, cam, setup=lambda wrap: wrap.set_variant(variant)))
         assert np.array_equal(outs[0], outs[1])
-        r = Renderer(sc, tex, sky, 240, 160, depth=depth, strict=strict)
-        r.w.set_variant(1024)
-        r.w.enable_counters(1)
-        r.look(**cam)
-        chk = r.render()
-        c = r.w.read_counters()
-        r.release()
+        with rendering(Renderer, sc, tex, sky, 240, 160, setup=verifying, cam=cam, depth=depth, strict=strict) as r:
+            chk = r.render()
+            c = r.w.read_counters()
         assert np.array_equal(chk, outs[0])
         assert c["vis_mismatches"] == 0, c
         classified += c["lights_classified"]
@@ -520,13 +487,9 @@ def test_light_visibility_classes_verified_at_full_c2_size(R, demo_scene, tex):
     sky4k = textures.skybox_cross(4096)
     for (w, h, depth) in ((1920, 1080, 4), (800, 600, 15)):
         for strict in (True,):
-            r = Renderer(demo_scene, tex, sky4k, w, h, depth=depth, strict=strict)
-            r.w.set_variant(1024)
-            r.w.enable_counters(1)
-            r.look(**CAM)
-            r.render(readback=False)
-            c = r.w.read_counters()
-            r.release()
+            with rendering(Renderer, demo_scene, tex, sky4k, w, h, setup=verifying, depth=depth, strict=strict) as r:
+                r.render(readback=False)
+                c = r.w.read_counters()
             report(dict(test="visibility classes", frame=f"{w}x{h} d{depth}", strict=strict, shadow_rays=c["shadow_rays"],
                         lights_classified=c["lights_classified"], mismatches=c["vis_mismatches"]))
             assert c["vis_mismatches"] == 0 and 2 * c["lights_classified"] > 0.5 * c["shadow_rays"], c
@@ -539,18 +502,16 @@ def test_cost_sorted_dispatch_is_pure_scheduling(R, demo_scene, tex, sky):
     w, h = 328, 203                                   # ragged: 41 tile columns, 26 tile rows (25.4)
     cams = [CAM, dict(origin=(1.5, 2.0, -6.0), look=(-0.1, -0.1, 1.0), fov=90.0, focal=1.0)]
     ref = []
-    off = Renderer(demo_scene, tex, sky, w, h, depth=15, strict=True)
-    off.w.set_tile_sched(0)
-    for cam in cams:
-        off.look(**cam)
-        ref.append(off.render())
-    off.release()
-    on = Renderer(demo_scene, tex, sky, w, h, depth=15, strict=True)
-    for cam, want in zip(cams + cams, ref + ref):
-        on.look(**cam)
-        for _ in range(3):
-            assert np.array_equal(on.render(), want)
-    on.release()
+    with Renderer(demo_scene, tex, sky, w, h, depth=15, strict=True) as off:
+        off.w.set_tile_sched(0)
+        for cam in cams:
+            off.look(**cam)
+            ref.append(off.render())
+    with Renderer(demo_scene, tex, sky, w, h, depth=15, strict=True) as on:
+        for cam, want in zip(cams + cams, ref + ref):
+            on.look(**cam)
+            for _ in range(3):
+                assert np.array_equal(on.render(), want)
 
 
 # ------------------------------------------------------------ edge cases
@@ -663,18 +624,16 @@ def test_full_size_c2_against_the_oracle_and_ray_count(R, oracle, demo_scene, te
     want, _, cnt = oracle.render(oracle.camera(CAM["origin"], CAM["look"], 90.0, 1.0, w, h), demo_scene, tex, sky4k, depth)
     assert 13.8 < cnt.rays / (w * h) < 13.95                      # 13.88 rays/px
     for strict in (True, False):
-        r = Renderer(demo_scene, tex, sky4k, w, h, depth=depth, strict=strict)
-        r.look(**CAM)
-        got = r.render()
-        if strict:
-            pin_strict_residual(r.w, got, want, oracle, oracle.camera(CAM["origin"], CAM["look"], 90.0, 1.0, w, h), demo_scene, tex, sky4k, depth, "C2 strict")
-        else:
-            ex = check(got, want, 0.999, 0.9995)
-            report(dict(test="C2 fast", exact=ex, within_1lsb=float((channel_diff(got, want) <= 1).mean())))
-        r.w.enable_counters(1)
-        r.render(readback=False)
-        c = r.w.read_counters()
-        r.release()
+        with rendering(Renderer, demo_scene, tex, sky4k, w, h, depth=depth, strict=strict) as r:
+            got = r.render()
+            if strict:
+                pin_strict_residual(r.w, got, want, oracle, oracle.camera(CAM["origin"], CAM["look"], 90.0, 1.0, w, h), demo_scene, tex, sky4k, depth, "C2 strict")
+            else:
+                ex = check(got, want, 0.999, 0.9995)
+                report(dict(test="C2 fast", exact=ex, within_1lsb=float((channel_diff(got, want) <= 1).mean())))
+            r.w.enable_counters(1)
+            r.render(readback=False)
+            c = r.w.read_counters()
         rays = c["segments"] + c["shadow_rays"]
         assert abs(rays - cnt.rays) <= (0 if strict else 2e-4 * cnt.rays)
         # shadow rays really traced: the ones of zero-coefficient (glass) surfaces are drawn from the RNG but elided, and so are
@@ -703,11 +662,7 @@ def test_large_frame_is_deterministic_and_tile_order_free(R, tex, sky):
     outs = []
     # (2048: the scratch part of the DFS stack sized for CLW_MAX_DEPTH instead of for this depth)
     for variant in (0, 0, 2, 64, 2048):
-        r = Renderer(sc, tex, sky, 4096, 4096, depth=8, strict=False)
-        r.w.set_variant(variant)
-        r.look(**cam)
-        outs.append(r.render())
-        r.release()
+        outs.append(gpu_frame(Renderer, sc, tex, sky, 4096, 4096, 8, False, cam, setup=lambda wrap: wrap.set_variant(variant)))
     assert all(np.array_equal(outs[0], o) for o in outs[1:])
     assert len(np.unique(outs[0])) > 1000
 
@@ -725,11 +680,7 @@ def test_deep_refraction_trees_on_the_glass_field(R, oracle, tex, sky, strict):
     for depth, w, h in ((15, 192, 160), (20, 96, 80)):
         outs = []
         for variant in (0, 64, 2048, 64 | 2048):
-            r = Renderer(sc, tex, sky, w, h, depth=depth, strict=strict)
-            r.w.set_variant(variant)
-            r.look(**cam)
-            outs.append(r.render())
-            r.release()
+            outs.append(gpu_frame(Renderer, sc, tex, sky, w, h, depth, strict, cam, setup=lambda wrap: wrap.set_variant(variant)))
         assert all(np.array_equal(outs[0], o) for o in outs[1:])
         if strict:
             want, _, cnt = oracle.render(oracle.camera(cam["origin"], cam["look"], 90.0, 1.0, w, h), sc, tex, sky, depth)
@@ -768,21 +719,19 @@ def test_tree_parallel_tail_equals_the_per_lane_loop(R, oracle, demo_scene, tex,
     sc, w, h, depth, cam = {"render.map d15": (demo_scene, 320, 240, 15, CAM), "render.map d8": (demo_scene, 200, 152, 8, CAM),
                             "glass field d8": (scene.dielectric_field_scene(8), 256, 256, 8, glass_cam),
                             "glass field d15": (scene.dielectric_field_scene(4), 160, 160, 15, glass_cam)}[case]
-    r = R(sc, tex, sky, w, h, depth=depth, strict=strict)
-    r.look(**cam)
-    ref, cref = _tail_frame(r, 0)
-    assert cref["tpt_tiles"] == 0
-    for max_lanes in (8, 24, 64):
-        img, c = _tail_frame(r, max_lanes)
-        assert c["tpt_tiles"] > 0 and c["tpt_nodes"] > 0, "the tail did not run"
-        assert np.array_equal(img, ref), f"{case}: tail entered at <= {max_lanes} lanes: {int((img != ref).sum())} pixels differ from the per-lane loop"
-        assert all(c[k] == cref[k] for k in TAIL_KEYS), (max_lanes, {k: (c[k], cref[k]) for k in TAIL_KEYS})
-    r.w.set_variant(4096)                                   # heavy tiles not split
-    r.w.set_tpt(24, -1, -1)
-    for _ in range(2):
-        r.render(readback=False)
-    assert np.array_equal(r.render(), ref)
-    r.release()
+    with rendering(R, sc, tex, sky, w, h, cam=cam, depth=depth, strict=strict) as r:
+        ref, cref = _tail_frame(r, 0)
+        assert cref["tpt_tiles"] == 0
+        for max_lanes in (8, 24, 64):
+            img, c = _tail_frame(r, max_lanes)
+            assert c["tpt_tiles"] > 0 and c["tpt_nodes"] > 0, "the tail did not run"
+            assert np.array_equal(img, ref), f"{case}: tail entered at <= {max_lanes} lanes: {int((img != ref).sum())} pixels differ from the per-lane loop"
+            assert all(c[k] == cref[k] for k in TAIL_KEYS), (max_lanes, {k: (c[k], cref[k]) for k in TAIL_KEYS})
+        r.w.set_variant(4096)                                   # heavy tiles not split
+        r.w.set_tpt(24, -1, -1)
+        for _ in range(2):
+            r.render(readback=False)
+        assert np.array_equal(r.render(), ref)
     if strict:
         want, _, _ = oracle.render(oracle.camera(cam["origin"], cam["look"], cam.get("fov", 90.0), cam.get("focal", 1.0), w, h), sc, tex, sky, depth)
         check_exact(ref, want, f"tail / per-lane loop vs oracle: {case}")
@@ -795,18 +744,16 @@ def test_tree_parallel_tail_gives_up_cleanly_when_its_slot_is_full(R, tex, sky, 
     from example_gui_opencl_raytracer_amd import scene
     sc = scene.dielectric_field_scene(4)
     cam = dict(origin=(3.5, 3.0, -6.0), look=(0.0, -2.5, 9.5), fov=90.0, focal=1.0)
-    r = R(sc, tex, sky, 160, 160, depth=15, strict=strict)
-    r.look(**cam)
-    ref, cref = _tail_frame(r, 0)
-    per_node = (29 + 4 * 3) if strict else (27 + 3)
-    words = (25 + 36) * 64 + 15 * 192 + per_node * 192 + 63
-    r.w.set_tpt(-1, -1, max(1, (words * 8192 * 4) >> 20))
-    for max_lanes in (24, 64):
-        img, c = _tail_frame(r, max_lanes)
-        assert c["tpt_gave_up"] > 0 and c["tpt_tiles"] > 0, c
-        assert np.array_equal(img, ref)
-        assert all(c[k] == cref[k] for k in TAIL_KEYS)
-    r.release()
+    with rendering(R, sc, tex, sky, 160, 160, cam=cam, depth=15, strict=strict) as r:
+        ref, cref = _tail_frame(r, 0)
+        per_node = (29 + 4 * 3) if strict else (27 + 3)
+        words = (25 + 36) * 64 + 15 * 192 + per_node * 192 + 63
+        r.w.set_tpt(-1, -1, max(1, (words * 8192 * 4) >> 20))
+        for max_lanes in (24, 64):
+            img, c = _tail_frame(r, max_lanes)
+            assert c["tpt_gave_up"] > 0 and c["tpt_tiles"] > 0, c
+            assert np.array_equal(img, ref)
+            assert all(c[k] == cref[k] for k in TAIL_KEYS)
 
 
 def test_tree_parallel_tail_with_many_lights_and_on_the_grid(R, oracle, tex, sky):
@@ -822,13 +769,11 @@ def test_tree_parallel_tail_with_many_lights_and_on_the_grid(R, oracle, tex, sky
     many = scene.Scene(base.spheres, base.planes, lights)
     for sc_, cam_, w, h in ((many, CAM, 160, 120), (sc, cam, 160, 96)):
         want, _, _ = oracle.render(oracle.camera(cam_["origin"], cam_["look"], cam_.get("fov", 90.0), cam_.get("focal", 1.0), w, h), sc_, tex, sky, 8)
-        r = R(sc_, tex, sky, w, h, depth=8, strict=True)
-        r.look(**cam_)
-        for max_lanes in (16, 64):
-            img, c = _tail_frame(r, max_lanes)
-            assert c["tpt_tiles"] > 0
-            check_exact(img, want, f"tail, {len(sc_.lights)} lights, {len(sc_.spheres)} spheres, entered at <= {max_lanes}")
-        r.release()
+        with rendering(R, sc_, tex, sky, w, h, cam=cam_, depth=8, strict=True) as r:
+            for max_lanes in (16, 64):
+                img, c = _tail_frame(r, max_lanes)
+                assert c["tpt_tiles"] > 0
+                check_exact(img, want, f"tail, {len(sc_.lights)} lights, {len(sc_.spheres)} spheres, entered at <= {max_lanes}")
 
 
 # ------------------------------------------------------------ the other BASELINE.json configurations at FULL size
@@ -842,17 +787,13 @@ def test_full_size_c3_glass_field_against_the_oracle(R, oracle, tex):
     w = h = 4096
     want, _, cnt = oracle.render(oracle.camera(cam["origin"], cam["look"], 90.0, 1.0, w, h), sc, tex, sky4k, 8)
     assert 29.0 < cnt.rays / (w * h) < 30.0
-    r = Renderer(sc, tex, sky4k, w, h, depth=8, strict=True)
-    r.look(**cam)
-    pin_strict_residual(r.w, r.render(), want, oracle, oracle.camera(cam["origin"], cam["look"], 90.0, 1.0, w, h), sc, tex, sky4k, 8, "C3 strict")
-    r.w.enable_counters(1); r.render(readback=False); c = r.w.read_counters(); r.release()
+    with rendering(Renderer, sc, tex, sky4k, w, h, cam=cam, depth=8, strict=True) as r:
+        pin_strict_residual(r.w, r.render(), want, oracle, oracle.camera(cam["origin"], cam["look"], 90.0, 1.0, w, h), sc, tex, sky4k, 8, "C3 strict")
+        r.w.enable_counters(1); r.render(readback=False); c = r.w.read_counters()
     assert c["segments"] + c["shadow_rays"] == cnt.rays
     assert c["shadow_rays_traced"] < 0.5 * c["shadow_rays"]       # a field of glass: most counted shadow rays are elided
-    r = Renderer(sc, tex, sky4k, w, h, depth=8, strict=False)
-    r.look(**cam)
-    got = r.render()
+    got = gpu_frame(Renderer, sc, tex, sky4k, w, h, 8, False, cam)
     report(dict(test="C3 fast", exact=check(got, want, 0.99, 0.995), within_1lsb=float((channel_diff(got, want) <= 1).mean())))
-    r.release()
 
 
 def test_full_size_c4_ten_thousand_spheres_against_the_oracle(R, oracle, tex):
@@ -865,16 +806,13 @@ def test_full_size_c4_ten_thousand_spheres_against_the_oracle(R, oracle, tex):
     cam = dict(origin=(0.0, 12.0, -10.0), look=(0.0, -0.45, 1.0), fov=90.0, focal=1.0)
     w, h = 1920, 1080
     want, _, cnt = oracle.render(oracle.camera(cam["origin"], cam["look"], 90.0, 1.0, w, h), sc, tex, sky4k, 4)
-    r = Renderer(sc, tex, sky4k, w, h, depth=4, strict=True)
-    r.look(**cam)
-    pin_strict_residual(r.w, r.render(), want, oracle, oracle.camera(cam["origin"], cam["look"], 90.0, 1.0, w, h), sc, tex, sky4k, 4, "C4 strict")
-    r.w.enable_counters(1); r.render(readback=False); c = r.w.read_counters(); r.release()
+    with rendering(Renderer, sc, tex, sky4k, w, h, cam=cam, depth=4, strict=True) as r:
+        pin_strict_residual(r.w, r.render(), want, oracle, oracle.camera(cam["origin"], cam["look"], 90.0, 1.0, w, h), sc, tex, sky4k, 4, "C4 strict")
+        r.w.enable_counters(1); r.render(readback=False); c = r.w.read_counters()
     assert c["segments"] + c["shadow_rays"] == cnt.rays
     # opaque plastic everywhere: only the rays to a light BEHIND the surface (diffuse and specular terms exactly zero) are elided
     assert 0.9 * c["shadow_rays"] < c["shadow_rays_traced"] < c["shadow_rays"]
-    r = Renderer(sc, tex, sky4k, w, h, depth=4, strict=False)      # the benchmarked build at the full size
-    r.look(**cam)
-    got = r.render()
+    got = gpu_frame(Renderer, sc, tex, sky4k, w, h, 4, False, cam)      # the benchmarked build at the full size
     # This scene's own noise floor is low: shadow and reflection rays start up to 100 units from the spheres they pass, so
     # b*b and 4ac of intersect_sphere (primitives.cl:181) agree to 5-7 digits and the sign of their difference is rounding
     # noise over much of a sphere's cross-section.  The bar is what the scene itself predicts: the oracle built WITH FMA
@@ -889,7 +827,6 @@ def test_full_size_c4_ten_thousand_spheres_against_the_oracle(R, oracle, tex):
     ex = check(got, want, floor_exact - 0.005, floor_le1 - 0.005)
     report(dict(test="C4 fast", exact=ex, within_1lsb=float((channel_diff(got, want) <= 1).mean()),
                 oracle_fma_exact=floor_exact, oracle_fma_within_1lsb=floor_le1))
-    r.release()
 
 
 def test_full_size_c5_strips_equal_the_single_gpu_frame(R, oracle, demo_scene, tex):
@@ -899,19 +836,13 @@ def test_full_size_c5_strips_equal_the_single_gpu_frame(R, oracle, demo_scene, t
     from example_gui_opencl_raytracer_amd.renderer import Renderer, strip_rows
     sky4k = textures.skybox_cross(4096)
     w = h = 8192
-    full = Renderer(demo_scene, tex, sky4k, w, h, depth=4, strict=True)
-    full.look(**CAM)
-    want = full.render()
-    full.release()
+    want = gpu_frame(Renderer, demo_scene, tex, sky4k, w, h, 4, True)
     import zlib
     cam = oracle.camera(CAM["origin"], CAM["look"], 90.0, 1.0, w, h)
     for rank in range(8):
         r0, rows = strip_rows(h, 8, rank)
         assert rows == 1024
-        s = Renderer(demo_scene, tex, sky4k, w, h, depth=4, strict=True, first_row=r0, rows=rows)
-        s.look(**CAM)
-        got = s.render()
-        s.release()
+        got = gpu_frame(Renderer, demo_scene, tex, sky4k, w, h, 4, True, first_row=r0, rows=rows)
         assert zlib.crc32(got.tobytes()) == zlib.crc32(want[r0 * w:(r0 + rows) * w].tobytes())
         if rank in (3, 5):
             ref, _, _ = oracle.render(cam, demo_scene, tex, sky4k, 4, id_begin=r0 * w, id_end=(r0 + 64) * w)

@@ -5,32 +5,19 @@ is pixel (vx, vy) of a 1-sample render of the n*W x n*H frame through cams[(vy m
 the samples are clamped, added and scaled as in plain supersampling (`resolve`)."""
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from conftest import CAM, ROOT
 from flags_common import F_DEEP, F_GRID, F_OCC, F_SHAPE, F_SS
-from sample_cameras_common import CAM2, composed, gpu_composed, make_table, pick, resolve, rows_of, same_floats, sampled, virtual_camera
+from render_common import R, api, assert_same_frames, queued_on, rendering, run_child, same_floats, take  # noqa: F401  (R, api: the fixtures)
+from sample_cameras_common import CAM2, composed, gpu_composed, make_table, pick, rows_of, sampled, virtual_camera
 
 pytestmark = pytest.mark.gpu
 
 LENS = (0.2, 8.0)
 COUNTED = ("segments", "shadow_rays", "light_probes", "sky_fetches", "texel_fetches", "pushes")
-
-
-@pytest.fixture(scope="module")
-def R():
-    import torch  # noqa: F401
-    from example_gui_opencl_raytracer_amd.renderer import Renderer
-    return Renderer
-
-
-@pytest.fixture(scope="module")
-def api():
-    from example_gui_opencl_raytracer_amd import api
-    return api
 
 
 def check_self_consistent(R, api, sc, tex, sky, W, H, n, depth, strict, kind=LENS, count=1, setup=None):
@@ -39,13 +26,9 @@ def check_self_consistent(R, api, sc, tex, sky, W, H, n, depth, strict, kind=LEN
     got, flags, used = sampled(R, sc, tex, sky, W, H, n, depth, strict, kind, table=table, count=count, setup=setup)
     assert flags & F_SS and not vflags & F_SS
     assert used.tobytes() == table.tobytes()
-    for k, (p, f) in enumerate(got):
+    for p, f in got:
         assert p.shape == (W * H,) and f.shape == (W * H, 3)
-        bad = int((p != want_p).sum())
-        print(f"{W}x{H} n={n} depth {depth} strict={int(strict)} {kind} frame {k}: {bad} packed pixels differ, "
-              f"{int((f.view(np.uint32) != want_f.view(np.uint32)).any(1).sum())} float pixels differ")
-        assert np.array_equal(p, want_p), (W, H, n, depth, strict, k, bad)
-        assert same_floats(f, want_f), (W, H, n, depth, strict, k)
+    assert_same_frames(got, want_p, want_f, f"{W}x{H} n={n} depth {depth} strict={int(strict)} {kind}")
     return flags, want_p
 
 
@@ -118,13 +101,11 @@ def test_strict_lens_frame_is_composed_of_the_oracles_virtual_frames(R, api, ora
         return f
     want_p, want_f = composed(oracle_virtual, table, W, H, n)
 
-    r = R(demo_scene, tex, sky, n * W, n * H, depth=depth, strict=True)
-
-    def differs(k):
-        r.set_camera(virtual_camera(api.clw_camera, table[k], base, n))
-        return r.render() != oracle_frames[k]
-    selected = pick(differs, W, H, n)
-    r.release()
+    with R(demo_scene, tex, sky, n * W, n * H, depth=depth, strict=True) as r:
+        def differs(k):
+            r.set_camera(virtual_camera(api.clw_camera, table[k], base, n))
+            return r.render() != oracle_frames[k]
+        selected = pick(differs, W, H, n)
     left_out = selected.reshape(H, n, W, n).any((1, 3)).reshape(-1)
     print(f"{W}x{H} n={n} depth {depth}: {int(selected.sum())} selected virtual pixels differ from the oracle, {int(left_out.sum())} output pixels left out")
     assert left_out.sum() <= 4
@@ -137,19 +118,16 @@ def test_strict_lens_frame_is_composed_of_the_oracles_virtual_frames(R, api, ora
 
 # ------------------------------------------------------------------ 7. degenerate tables
 def counted_frames(R, sc, tex, sky, W, H, n, depth, strict, prepare, cam=CAM):
-    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n)
-    try:
+    with R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n) as r:
         camera = r.look(**cam)
         prepare(r, camera)
-        p, f = r.render_rgb()
+        (p, f), = take(r)
         p2 = r.render().copy()
         flags, costs = r.w.last_trace_flags(), r.w.read_tile_costs()
         r.w.enable_counters(1)
         r.render()
         c = r.w.read_counters()
-        return p.copy(), f.copy(), p2, flags, costs, [c[k] for k in COUNTED]
-    finally:
-        r.release()
+        return p, f, p2, flags, costs, [c[k] for k in COUNTED]
 
 
 @pytest.mark.parametrize("strict", [True, False], ids=["strict", "fast"])
@@ -174,17 +152,16 @@ def test_degenerate_tables_give_the_plain_supersampled_frame(R, api, demo_scene,
 def test_the_launch_uses_the_host_helpers_table_under_a_moving_camera(R, api, demo_scene, tex, sky):
     W, H, n, depth = 320, 240, 2, 4
     for strict in (True, False):
-        r = R(demo_scene, tex, sky, W, H, depth=depth, strict=strict, supersample=n, lens=(0.1, 8.0))
-        assert r.w.get_sample_cameras().shape == (0, 12)          # no launch yet
-        frames = []
-        for k in range(5):
-            cam = dict(CAM, origin=(0.8 + 0.3 * k, 2.5, -8.0 + 0.2 * k))
-            camera = r.look(**cam)
-            frames.append(r.render().copy())
-            assert r.w.get_sample_cameras().tobytes() == api.lens_cameras(camera, 0.1, 8.0, n).tobytes(), k
-            fresh = sampled(R, demo_scene, tex, sky, W, H, n, depth, strict, (0.1, 8.0), cam=cam, rgb=False)[0][0][0]
-            assert np.array_equal(frames[-1], fresh), (strict, k)
-        r.release()
+        with R(demo_scene, tex, sky, W, H, depth=depth, strict=strict, supersample=n, lens=(0.1, 8.0)) as r:
+            assert r.w.get_sample_cameras().shape == (0, 12)          # no launch yet
+            frames = []
+            for k in range(5):
+                cam = dict(CAM, origin=(0.8 + 0.3 * k, 2.5, -8.0 + 0.2 * k))
+                camera = r.look(**cam)
+                frames.append(r.render().copy())
+                assert r.w.get_sample_cameras().tobytes() == api.lens_cameras(camera, 0.1, 8.0, n).tobytes(), k
+                fresh = sampled(R, demo_scene, tex, sky, W, H, n, depth, strict, (0.1, 8.0), cam=cam, rgb=False)[0][0][0]
+                assert np.array_equal(frames[-1], fresh), (strict, k)
         assert not np.array_equal(frames[0], frames[1])
 
 
@@ -227,19 +204,17 @@ def test_changing_aperture_focus_table_and_factor_between_frames(R, api, demo_sc
         for n, kind in set(steps):
             table = make_table(api, W, H, n, kind)[1] if kind == "shutter" else None
             want[(n, kind)] = sampled(R, demo_scene, tex, sky, W, H, n, depth, strict, kind, table=table, rgb=False)[0][0][0]
-        r = R(demo_scene, tex, sky, W, H, depth=depth, strict=strict)
-        r.look(**CAM)
-        for n, kind in steps:
-            r.w.set_supersample(n)
-            if kind == "shutter":
-                r.set_sample_cameras(make_table(api, W, H, n, kind)[1])
-            elif kind is None:
-                r.w.set_lens(0.0, 1.0)
-                r.set_sample_cameras(None)
-            else:
-                r.w.set_lens(*kind)
-            assert np.array_equal(r.render(), want[(n, kind)]), (strict, n, kind)
-        r.release()
+        with rendering(R, demo_scene, tex, sky, W, H, depth=depth, strict=strict) as r:
+            for n, kind in steps:
+                r.w.set_supersample(n)
+                if kind == "shutter":
+                    r.set_sample_cameras(make_table(api, W, H, n, kind)[1])
+                elif kind is None:
+                    r.w.set_lens(0.0, 1.0)
+                    r.set_sample_cameras(None)
+                else:
+                    r.w.set_lens(*kind)
+                assert np.array_equal(r.render(), want[(n, kind)]), (strict, n, kind)
         assert len({v.tobytes() for v in want.values()}) == len(want)
 
 
@@ -254,20 +229,16 @@ def test_tables_that_change_under_queued_launches(R, demo_scene, tex, sky):
     fb = torch.zeros(W * H, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     side = torch.cuda.Stream()
-    r = R(demo_scene, tex, sky, W, H, depth=depth, supersample=n, framebuffer_ptr=fb.data_ptr())
-    r.w.set_stream(side.cuda_stream)
-    r.w.set_async(True)
-    r.look(**CAM)
-    outs = []
-    for lens in lenses:
-        r.w.set_lens(*lens)
-        r.render(readback=False)
-        with torch.cuda.stream(side):
-            outs.append(fb.clone())
-    side.synchronize()
-    for k, lens in enumerate(lenses):
-        assert np.array_equal(outs[k].cpu().numpy().view(np.uint32), want[lens]), (k, lens)
-    r.release()
+    with rendering(R, demo_scene, tex, sky, W, H, setup=queued_on(side), depth=depth, supersample=n, framebuffer_ptr=fb.data_ptr()) as r:
+        outs = []
+        for lens in lenses:
+            r.w.set_lens(*lens)
+            r.render(readback=False)
+            with torch.cuda.stream(side):
+                outs.append(fb.clone())
+        side.synchronize()
+        for k, lens in enumerate(lenses):
+            assert np.array_equal(outs[k].cpu().numpy().view(np.uint32), want[lens]), (k, lens)
 
 
 def test_changing_the_stream_between_lens_frames(R, demo_scene, tex, sky):
@@ -276,13 +247,11 @@ def test_changing_the_stream_between_lens_frames(R, demo_scene, tex, sky):
     W, H, n, depth = 320, 240, 2, 4
     want = {a: sampled(R, demo_scene, tex, sky, W, H, n, depth, True, (a, 8.0), rgb=False)[0][0][0] for a in (0.05, 0.2)}
     side = torch.cuda.Stream()
-    r = R(demo_scene, tex, sky, W, H, depth=depth, strict=True, supersample=n, lens=(0.05, 8.0))
-    r.look(**CAM)
-    for stream, aperture in ((0, 0.05), (side.cuda_stream, 0.05), (side.cuda_stream, 0.2), (0, 0.2), (0, 0.05), (side.cuda_stream, 0.2), (0, 0.2)):
-        r.w.set_stream(stream)
-        r.w.set_lens(aperture, 8.0)
-        assert np.array_equal(r.render(), want[aperture]), (stream != 0, aperture)
-    r.release()
+    with rendering(R, demo_scene, tex, sky, W, H, depth=depth, strict=True, supersample=n, lens=(0.05, 8.0)) as r:
+        for stream, aperture in ((0, 0.05), (side.cuda_stream, 0.05), (side.cuda_stream, 0.2), (0, 0.2), (0, 0.05), (side.cuda_stream, 0.2), (0, 0.2)):
+            r.w.set_stream(stream)
+            r.w.set_lens(aperture, 8.0)
+            assert np.array_equal(r.render(), want[aperture]), (stream != 0, aperture)
 
 
 # ------------------------------------------------------------------ 11. the reference's own driver, unchanged
@@ -309,26 +278,16 @@ def test_unchanged_raypng_driver_gets_the_lens_from_the_environment(R, api, tmp_
         assert img.shape == (600, 800, 4)
         return (img[..., 0].astype(np.uint32) << 16 | img[..., 1].astype(np.uint32) << 8 | img[..., 2]).reshape(-1)
     got = driver(CLWRAP_APERTURE="0.1", CLWRAP_FOCUS="8")
-    r = R(Scene.load(os.path.join(FIX, "render.map")), None, None, 800, 600, depth=15, strict=True, supersample=2, lens=(0.1, 8),
-          texture_paths=[os.path.join(FIX, nm + ".png") for nm in names], skybox_path=os.path.join(FIX, "stormydays.png"))
-    r.look(**CAM)
-    want = r.render().copy()
-    r.release()
+    with rendering(R, Scene.load(os.path.join(FIX, "render.map")), None, None, 800, 600, depth=15, strict=True, supersample=2, lens=(0.1, 8),
+                   texture_paths=[os.path.join(FIX, nm + ".png") for nm in names], skybox_path=os.path.join(FIX, "stormydays.png")) as r:
+        want = r.render().copy()
     assert np.array_equal(got, want), int((got != want).sum())
     assert not np.array_equal(driver(), got)          # and it is not the frame without the lens
 
 
 # ------------------------------------------------------------------ 12. refusals: message + exit(1)
 def _run(snippet, env=None):
-    code = ("import sys; sys.path.insert(0, %r)\n"
-            "import numpy as np\n"
-            "import torch\n"
-            "from example_gui_opencl_raytracer_amd import api, scene, textures\n"
-            "from example_gui_opencl_raytracer_amd.renderer import Renderer\n"
-            "CAM = %r\n"
-            "sc, tex, sky = scene.render_map_scene(), textures.texture_layers(), textures.skybox_cross(64)\n"
-            "table = lambda n: api.lens_cameras(api.perspective(**CAM, width=64, height=48), 0.1, 8.0, n)\n" % (ROOT, CAM)) + snippet
-    return subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
+    return run_child("table = lambda n: api.lens_cameras(api.perspective(**CAM, width=64, height=48), 0.1, 8.0, n)\n" + snippet, env)
 
 
 REFUSED = {

@@ -15,9 +15,6 @@ The seed offset and the accumulation are run-time branches of the plain and the 
 Every shaped frame is compared bit for bit, packed and float, with the generic kernel's (variant 8192) and held to the mode's definition in
 the *_common.py module of its suite; the plain flavour also to the CPU oracle.  The second half runs the modes on the generic kernels, in
 both builds, for the counts just outside the compiled set and for empty primitive lists."""
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
@@ -25,9 +22,10 @@ import accumulate_common as acc
 import adaptive_common as ada
 import sample_cameras_common as cams
 import sphere_motion_common as motion
-from conftest import CAM, ROOT, channel_diff
+from conftest import CAM, channel_diff
 from fuzz_scenes import random_scene, sphere_displacement
 from parity_common import check_exact, report
+from render_common import R, api, frames, resolve, run_child, same_floats  # noqa: F401  (R, api: the fixtures)
 from shape_common import (ADAPTIVE, DEPTHS, F_GEOM_LDS, F_LIST, F_MOVE, F_SHAPE, F_SS, FRAME, RAGGED, SHAPES, V_GENERIC, empty_list_scenes, frame,
                           scene_of, shape_flags)
 
@@ -35,7 +33,6 @@ pytestmark = pytest.mark.gpu
 
 SEED = 0x9E3779B1
 shapes = pytest.mark.parametrize("ns,npl", SHAPES, ids=[f"{s}s{p}p" for s, p in SHAPES])
-same_floats = ada.same_floats
 
 
 def generic(w):
@@ -46,20 +43,6 @@ def other_end(cam):
     """the camera at the other end of a shutter that opens on `cam`"""
     o, l = cam["origin"], cam["look"]
     return dict(cam, origin=(o[0] + 0.4, o[1] + 0.3, o[2] + 0.5), look=(l[0] - 0.1, l[1] - 0.05, l[2]))
-
-
-@pytest.fixture(scope="module")
-def R():
-    import torch  # noqa: F401  (the shim then shares torch's ROCm runtime)
-    from example_gui_opencl_raytracer_amd.renderer import Renderer
-    return Renderer
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401
-    from example_gui_opencl_raytracer_amd import api
-    return api
 
 
 LAUNCHED = set()      # the flag words of the shaped launches the sweep asserted
@@ -111,10 +94,10 @@ def test_plain(R, oracle, tex, sky, ns, npl, W, H):
 def test_supersampled(R, tex, sky, ns, npl, W, H, n):
     sc, cam, _ = scene_of(ns, npl)
     for depth in DEPTHS:
-        (virt,), vflags = ada.frames(R, sc, tex, sky, n * W, n * H, depth, False, cam=cam)
-        want = ada.resolve(virt[1], W, H, n)
-        (got,), flags = ada.frames(R, sc, tex, sky, W, H, depth, False, n=n, cam=cam)
-        (gen,), gflags = ada.frames(R, sc, tex, sky, W, H, depth, False, n=n, cam=cam, setup=generic)
+        (virt,), vflags = frames(R, sc, tex, sky, n * W, n * H, depth, False, cam=cam)
+        want = resolve(virt[1], W, H, n)
+        (got,), flags = frames(R, sc, tex, sky, W, H, depth, False, n=n, cam=cam)
+        (gen,), gflags = frames(R, sc, tex, sky, W, H, depth, False, n=n, cam=cam, setup=generic)
         assert vflags == shape_flags(ns, npl)
         check_flags(ns, npl, F_SS, flags, gflags)
         print(f"{ns} spheres {npl} planes {W}x{H} n={n} depth {depth}: {int((got[0] != want[0]).sum())} packed pixels differ from the resolve")
@@ -145,8 +128,8 @@ def test_adaptive(R, api, tex, sky, ns, npl):
     W, H = FRAME
     n, T = ADAPTIVE
     for depth in DEPTHS:
-        ((bp, bf),), bflags = ada.frames(R, sc, tex, sky, W, H, depth, False, cam=cam)
-        ((fp, ff),), fflags = ada.frames(R, sc, tex, sky, W, H, depth, False, n=n, cam=cam)
+        ((bp, bf),), bflags = frames(R, sc, tex, sky, W, H, depth, False, cam=cam)
+        ((fp, ff),), fflags = frames(R, sc, tex, sky, W, H, depth, False, n=n, cam=cam)
         got, flags = ada.adaptive(R, sc, tex, sky, W, H, depth, False, n, T, cam=cam)
         gen, gflags = ada.adaptive(R, sc, tex, sky, W, H, depth, False, n, T, cam=cam, setup=generic)
         assert bflags == shape_flags(ns, npl) and fflags == shape_flags(ns, npl) | F_SS
@@ -166,9 +149,9 @@ def test_adaptive(R, api, tex, sky, ns, npl):
 def test_seed_offset_and_accumulation(R, api, tex, sky, ns, npl, depth):
     sc, cam, _ = scene_of(ns, npl)
     W, H = FRAME
-    (seeded,), flags = ada.frames(R, sc, tex, sky, W, H, depth, False, cam=cam, seed_offset=SEED)
-    (gen,), gflags = ada.frames(R, sc, tex, sky, W, H, depth, False, cam=cam, seed_offset=SEED, setup=generic)
-    (unseeded,), _ = ada.frames(R, sc, tex, sky, W, H, depth, False, cam=cam)
+    (seeded,), flags = frames(R, sc, tex, sky, W, H, depth, False, cam=cam, seed_offset=SEED)
+    (gen,), gflags = frames(R, sc, tex, sky, W, H, depth, False, cam=cam, seed_offset=SEED, setup=generic)
+    (unseeded,), _ = frames(R, sc, tex, sky, W, H, depth, False, cam=cam)
     check_flags(ns, npl, 0, flags, gflags)
     assert same_frames(seeded, gen) and not np.array_equal(seeded[0], unseeded[0])
     K = 3
@@ -196,7 +179,7 @@ def test_shutter_cameras(R, api, tex, sky, ns, npl, depth):
     want, vflags = cams.gpu_composed(R, api, sc, tex, sky, base, table, W, H, n, depth, False)
     (got,), flags, used = cams.sampled(R, sc, tex, sky, W, H, n, depth, False, "shutter", table=table, cam=cam)
     (gen,), gflags, _ = cams.sampled(R, sc, tex, sky, W, H, n, depth, False, "shutter", table=table, cam=cam, setup=generic)
-    (still,), _ = ada.frames(R, sc, tex, sky, W, H, depth, False, n=n, cam=cam, rgb=False)
+    (still,), _ = frames(R, sc, tex, sky, W, H, depth, False, n=n, cam=cam, rgb=False)
     assert vflags == shape_flags(ns, npl) and used.tobytes() == table.tobytes()
     check_flags(ns, npl, F_SS, flags, gflags)
     assert same_frames(got, gen) and same_frames(got, want)
@@ -226,11 +209,11 @@ def test_modes_on_the_generic_kernels(R, api, demo_scene, tex, sky, which, stric
     W, H = FRAME
     n, T = ADAPTIVE
     # supersampled == resolve of the 1-sample virtual frame
-    (virt,), vflags = ada.frames(R, sc, tex, sky, n * W, n * H, depth, strict, cam=cam, setup=generic)
-    ((bp, bf),), bflags = ada.frames(R, sc, tex, sky, W, H, depth, strict, cam=cam, setup=generic)
-    ((fp, ff),), fflags = ada.frames(R, sc, tex, sky, W, H, depth, strict, n=n, cam=cam, setup=generic)
+    (virt,), vflags = frames(R, sc, tex, sky, n * W, n * H, depth, strict, cam=cam, setup=generic)
+    ((bp, bf),), bflags = frames(R, sc, tex, sky, W, H, depth, strict, cam=cam, setup=generic)
+    ((fp, ff),), fflags = frames(R, sc, tex, sky, W, H, depth, strict, n=n, cam=cam, setup=generic)
     assert not (vflags | bflags) & (F_SHAPE | F_SS) and fflags & F_SS and not fflags & (F_SHAPE | F_MOVE | F_LIST)
-    assert same_frames((fp, ff), ada.resolve(virt[1], W, H, n))
+    assert same_frames((fp, ff), resolve(virt[1], W, H, n))
     # adaptive == composite
     got, flags = ada.adaptive(R, sc, tex, sky, W, H, depth, strict, n, T, cam=cam, setup=generic)
     assert flags & F_LIST and flags & F_SS and not flags & (F_SHAPE | F_MOVE)
@@ -298,14 +281,8 @@ def test_an_empty_table_on_a_scene_without_spheres_is_no_motion(R, demo_scene, t
 
 
 def test_a_table_for_a_scene_without_spheres_is_refused():
-    code = ("import sys; sys.path.insert(0, %r)\n"
-            "import numpy as np\n"
-            "import torch\n"
-            "from example_gui_opencl_raytracer_amd import scene, textures\n"
-            "from example_gui_opencl_raytracer_amd.renderer import Renderer\n"
-            "sc = scene.render_map_scene(); sc = scene.Scene(sc.spheres[:0], sc.planes, sc.lights)\n"
-            "r = Renderer(sc, textures.texture_layers(), textures.skybox_cross(64), 64, 48, depth=2, supersample=2, motion=np.full((1, 3), 0.25, np.float32))\n"
-            "r.look(**%r); r.render()\nprint('unreachable')\n" % (ROOT, CAM))
-    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    p = run_child("sc = scene.Scene(sc.spheres[:0], sc.planes, sc.lights)\n"
+                  "r = Renderer(sc, tex, sky, 64, 48, depth=2, supersample=2, motion=np.full((1, 3), 0.25, np.float32))\n"
+                  "r.look(**CAM); r.render()\nprint('unreachable')\n")
     assert p.returncode == 1 and "ERROR:\t" in p.stdout and "unreachable" not in p.stdout, p.stdout + p.stderr
     assert "the displacement table is for 1 spheres, the scene has 0" in p.stdout.split("ERROR:\t", 1)[1], p.stdout

@@ -7,15 +7,10 @@ import numpy as np
 import pytest
 
 from conftest import CAM
+from render_common import R  # noqa: F401  (the fixture)
 from shape_common import F_DEEP, F_GEOM_LDS, F_SHAPE, V_GENERIC, frame, shape_of
 
 pytestmark = pytest.mark.gpu
-
-@pytest.fixture(scope="module")
-def R():
-    import torch  # noqa: F401  (the shim then shares torch's ROCm runtime)
-    from example_gui_opencl_raytracer_amd.renderer import Renderer
-    return Renderer
 
 
 def check_pair(R, sc, tex, sky, w, h, depth, cam=CAM, shaped=True):

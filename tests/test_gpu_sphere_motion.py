@@ -3,34 +3,18 @@
 The definition every test uses (sphere_motion_common.py): with factor n, a displacement table and sample times t[0 .. n*n), the sample at
 virtual pixel (vx, vy) is pixel (vx, vy) of the 1-sample render of the n*W x n*H frame of the scene S(t[(vy mod n) * n + (vx mod n)])
 (api.spheres_at) -- through the launch camera, or through camera k of a table of sample cameras; the samples are clamped, added and
-scaled as in plain supersampling (sample_cameras_common.resolve)."""
-import subprocess
-import sys
-
+scaled as in plain supersampling (render_common.resolve)."""
 import numpy as np
 import pytest
 
-from conftest import CAM, ROOT
 from flags_common import F_DEEP, F_GEOM_LDS, F_GRID, F_OCC, F_SHAPE
+from render_common import R, api, queued_on, rendering, run_child, same_floats, take  # noqa: F401  (R, api: the fixtures)
 from sample_cameras_common import composed, pick, virtual_camera
-from sphere_motion_common import DISP, F_SS, LENS, camera_table, check_self_consistent, field_disp, gpu_virtual, moved_scene, moving, same_floats
+from sphere_motion_common import DISP, F_SS, LENS, camera_table, check_self_consistent, field_disp, gpu_virtual, moved_scene, moving
 
 pytestmark = pytest.mark.gpu
 
 COUNTED = ("segments", "shadow_rays", "light_probes", "sky_fetches", "texel_fetches", "pushes")
-
-
-@pytest.fixture(scope="module")
-def R():
-    import torch  # noqa: F401
-    from example_gui_opencl_raytracer_amd.renderer import Renderer
-    return Renderer
-
-
-@pytest.fixture(scope="module")
-def api():
-    from example_gui_opencl_raytracer_amd import api
-    return api
 
 
 # ------------------------------------------------------------------ 1. self-consistency, exact, both builds
@@ -145,19 +129,15 @@ def test_explicit_times_are_honoured(R, api, demo_scene, tex, sky, strict):
 
 # ------------------------------------------------------------------ 4. degenerate tables
 def counted_frames(R, sc, tex, sky, W, H, n, depth, strict, prepare):
-    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n)
-    try:
-        r.look(**CAM)
+    with rendering(R, sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n) as r:
         prepare(r)
-        p, f = r.render_rgb()
+        (p, f), = take(r)
         p2 = r.render().copy()
         flags, costs, used = r.w.last_trace_flags(), r.w.read_tile_costs(), r.w.get_sample_times()
         r.w.enable_counters(1)
         r.render()
         c = r.w.read_counters()
-        return p.copy(), f.copy(), p2, flags, costs, [c[k] for k in COUNTED], used
-    finally:
-        r.release()
+        return p, f, p2, flags, costs, [c[k] for k in COUNTED], used
 
 
 @pytest.mark.parametrize("strict", [True, False], ids=["strict", "fast"])
@@ -199,15 +179,13 @@ def test_changing_displacement_times_factor_and_lens_between_frames(R, api, demo
         for n, d, t, lens in set(steps):
             want[(n, d, t, lens)] = moving(R, demo_scene, tex, sky, W, H, n, depth, strict, disp_of[d], times=rev(n) if t else None, cams=lens, rgb=False)[0][0][0]
         assert len({v.tobytes() for v in want.values()}) == len(want)
-        r = R(demo_scene, tex, sky, W, H, depth=depth, strict=strict)
-        r.look(**CAM)
-        for n, d, t, lens in steps:
-            r.w.set_supersample(n)
-            r.set_sphere_motion(disp_of[d], rev(n) if t else None)
-            r.w.set_lens(*(lens or (0.0, 1.0)))
-            assert np.array_equal(r.render(), want[(n, d, t, lens)]), (strict, n, d, t, lens)
-            assert r.w.get_sample_times().tobytes() == (b"" if d is None else (rev(n) if t else api.sample_times(n)).tobytes())
-        r.release()
+        with rendering(R, demo_scene, tex, sky, W, H, depth=depth, strict=strict) as r:
+            for n, d, t, lens in steps:
+                r.w.set_supersample(n)
+                r.set_sphere_motion(disp_of[d], rev(n) if t else None)
+                r.w.set_lens(*(lens or (0.0, 1.0)))
+                assert np.array_equal(r.render(), want[(n, d, t, lens)]), (strict, n, d, t, lens)
+                assert r.w.get_sample_times().tobytes() == (b"" if d is None else (rev(n) if t else api.sample_times(n)).tobytes())
 
 
 def test_tables_that_change_under_queued_launches(R, demo_scene, tex, sky):
@@ -222,20 +200,16 @@ def test_tables_that_change_under_queued_launches(R, demo_scene, tex, sky):
     fb = torch.zeros(W * H, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     side = torch.cuda.Stream()
-    r = R(demo_scene, tex, sky, W, H, depth=depth, supersample=n, framebuffer_ptr=fb.data_ptr())
-    r.w.set_stream(side.cuda_stream)
-    r.w.set_async(True)
-    r.look(**CAM)
-    outs = []
-    for s in scales:
-        r.set_sphere_motion(disp[s])
-        r.render(readback=False)
-        with torch.cuda.stream(side):
-            outs.append(fb.clone())
-    side.synchronize()
-    for k, s in enumerate(scales):
-        assert np.array_equal(outs[k].cpu().numpy().view(np.uint32), want[s]), (k, s)
-    r.release()
+    with rendering(R, demo_scene, tex, sky, W, H, setup=queued_on(side), depth=depth, supersample=n, framebuffer_ptr=fb.data_ptr()) as r:
+        outs = []
+        for s in scales:
+            r.set_sphere_motion(disp[s])
+            r.render(readback=False)
+            with torch.cuda.stream(side):
+                outs.append(fb.clone())
+        side.synchronize()
+        for k, s in enumerate(scales):
+            assert np.array_equal(outs[k].cpu().numpy().view(np.uint32), want[s]), (k, s)
 
 
 def test_changing_the_stream_between_moving_frames(R, demo_scene, tex, sky):
@@ -245,13 +219,11 @@ def test_changing_the_stream_between_moving_frames(R, demo_scene, tex, sky):
     disp = {s: (DISP * np.float32(s)).astype(np.float32) for s in (0.5, 1.0)}
     want = {s: moving(R, demo_scene, tex, sky, W, H, n, depth, True, disp[s], rgb=False)[0][0][0] for s in disp}
     side = torch.cuda.Stream()
-    r = R(demo_scene, tex, sky, W, H, depth=depth, strict=True, supersample=n)
-    r.look(**CAM)
-    for stream, s in ((0, 0.5), (side.cuda_stream, 0.5), (side.cuda_stream, 1.0), (0, 1.0), (0, 0.5), (side.cuda_stream, 1.0), (0, 1.0)):
-        r.w.set_stream(stream)
-        r.set_sphere_motion(disp[s])
-        assert np.array_equal(r.render(), want[s]), (stream != 0, s)
-    r.release()
+    with rendering(R, demo_scene, tex, sky, W, H, depth=depth, strict=True, supersample=n) as r:
+        for stream, s in ((0, 0.5), (side.cuda_stream, 0.5), (side.cuda_stream, 1.0), (0, 1.0), (0, 0.5), (side.cuda_stream, 1.0), (0, 1.0)):
+            r.w.set_stream(stream)
+            r.set_sphere_motion(disp[s])
+            assert np.array_equal(r.render(), want[s]), (stream != 0, s)
 
 
 @pytest.mark.parametrize("n", [2, 4])
@@ -273,15 +245,7 @@ def test_row_strips_compose(R, demo_scene, tex, sky, n):
 
 # ------------------------------------------------------------------ 6. refusals: message + exit(1)
 def _run(snippet, env=None):
-    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
-            "import numpy as np\n"
-            "import torch\n"
-            "from example_gui_opencl_raytracer_amd import api, scene, textures\n"
-            "from example_gui_opencl_raytracer_amd.renderer import Renderer\n"
-            "from sphere_motion_common import DISP\n"
-            "CAM = %r\n"
-            "sc, tex, sky = scene.render_map_scene(), textures.texture_layers(), textures.skybox_cross(64)\n" % (ROOT, ROOT + "/tests", CAM)) + snippet
-    return subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
+    return run_child("from sphere_motion_common import DISP\n" + snippet, env)
 
 
 BAD = "d = DISP.copy(); d[2, 1] = float(%r); "

@@ -2,7 +2,7 @@
 
 The definition every test uses: sub-sample (sx, sy) of output pixel (x, y) is pixel (n x + sx, n y + sy) of the n*W x n*H frame the same
 camera gives, traced exactly as a 1-sample launch of that frame traces it; the samples are clamped to [0, 1], added in float32 -- adjacent
-pairs along x (log2 n rounds), then adjacent pairs along y -- scaled by 1 / n^2 and packed like any pixel: `resolve` below."""
+pairs along x (log2 n rounds), then adjacent pairs along y -- scaled by 1 / n^2 and packed like any pixel: render_common.resolve."""
 import os
 import subprocess
 import sys
@@ -12,50 +12,9 @@ import pytest
 
 from conftest import CAM, ROOT
 from flags_common import F_DEEP, F_GRID, F_OCC, F_SHAPE, F_SS
+from render_common import R, assert_same_frames, frames, released, rendering, resolve, run_child, same_floats, take  # noqa: F401  (R: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-
-def resolve(rgb, W, H, n):                      # rgb: float32 [n*H * n*W, 3], virtual-frame order
-    s = np.clip(rgb.reshape(H * n, W * n, 3), np.float32(0), np.float32(1))
-    k = n
-    while k > 1: s = s[:, 0::2] + s[:, 1::2]; k //= 2
-    k = n
-    while k > 1: s = s[0::2] + s[1::2]; k //= 2
-    s = s * np.float32(1.0 / (n * n))
-    c = (s * np.float32(255.0)).astype(np.uint32)
-    return ((c[..., 0] << 16) | (c[..., 1] << 8) | c[..., 2]).reshape(-1), s.reshape(-1, 3)
-
-
-@pytest.fixture(scope="module")
-def R():
-    import torch  # noqa: F401
-    from example_gui_opencl_raytracer_amd.renderer import Renderer
-    return Renderer
-
-
-def frames(R, sc, tex, sky, W, H, depth, strict, n=1, count=1, setup=None, rgb=True):
-    """`count` frames in a row from one renderer -> ([(packed, float) ...], flags of the last trace launch)"""
-    r = R(sc, tex, sky, W, H, depth=depth, strict=strict, supersample=n)
-    try:
-        if setup:
-            setup(r.w)
-        r.look(**CAM)
-        out = []
-        for _ in range(count):
-            if rgb:
-                p, f = r.render_rgb()
-                out.append((p.copy(), f.copy()))
-            else:
-                out.append((r.render().copy(), None))
-        return out, r.w.last_trace_flags()
-    finally:
-        r.release()
-
-
-def same_floats(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def check_self_consistent(R, sc, tex, sky, W, H, n, depth, strict, count=1, setup=None):
@@ -64,25 +23,20 @@ def check_self_consistent(R, sc, tex, sky, W, H, n, depth, strict, count=1, setu
     want_p, want_f = resolve(virt[1], W, H, n)
     got, flags = frames(R, sc, tex, sky, W, H, depth, strict, n=n, count=count, setup=setup)
     assert flags & F_SS and not vflags & F_SS
-    for k, (p, f) in enumerate(got):
+    for p, f in got:
         assert p.shape == (W * H,) and f.shape == (W * H, 3)
-        bad = int((p != want_p).sum())
-        print(f"{W}x{H} n={n} depth {depth} strict={int(strict)} frame {k}: {bad} packed pixels differ, "
-              f"{int((f.view(np.uint32) != want_f.view(np.uint32)).any(1).sum())} float pixels differ")
-        assert np.array_equal(p, want_p), (W, H, n, depth, strict, k, bad)
-        assert same_floats(f, want_f), (W, H, n, depth, strict, k)
+    assert_same_frames(got, want_p, want_f, f"{W}x{H} n={n} depth {depth} strict={int(strict)}")
     return flags
 
 
 # ------------------------------------------------------------------ the setter
 def test_get_returns_what_set_and_the_environment_set():
     from example_gui_opencl_raytracer_amd import api
-    w = api.ClWrap()
-    assert w.get_supersample() == 1
-    for n in (2, 4, 8, 1):
-        w.set_supersample(n)
-        assert w.get_supersample() == n
-    w.release()
+    with released(api.ClWrap()) as w:
+        assert w.get_supersample() == 1
+        for n in (2, 4, 8, 1):
+            w.set_supersample(n)
+            assert w.get_supersample() == n
     code = ("import sys; sys.path.insert(0, %r)\n"
             "from example_gui_opencl_raytracer_amd import api\n"
             "w = api.ClWrap(); print('supersample', w.get_supersample()); w.release()\n" % ROOT)
@@ -180,13 +134,11 @@ def test_counters_and_tile_costs_describe_the_virtual_frame(R, demo_scene, tex, 
     for depth in (4, 15):
         res = []
         for (w, h, k) in ((W, H, n), (n * W, n * H, 1)):
-            r = R(demo_scene, tex, sky, w, h, depth=depth, strict=True, supersample=k)
-            r.look(**CAM)
-            r.w.enable_counters(1)
-            r.render()
-            c = r.w.read_counters()
-            costs = r.w.read_tile_costs()
-            r.release()
+            with rendering(R, demo_scene, tex, sky, w, h, depth=depth, strict=True, supersample=k) as r:
+                r.w.enable_counters(1)
+                r.render()
+                c = r.w.read_counters()
+                costs = r.w.read_tile_costs()
             res.append(({x: c[x] for x in ("segments", "shadow_rays", "sky_fetches", "texel_fetches", "pushes")}, costs))
         assert res[0][0] == res[1][0] and res[0][0]["segments"] >= n * n * W * H
         assert len(res[0][1]) == ((n * W + 7) // 8) * ((n * H + 7) // 8) and np.array_equal(res[0][1], res[1][1])
@@ -197,12 +149,10 @@ def test_changing_the_factor_between_frames(R, demo_scene, tex, sky):
     from example_gui_opencl_raytracer_amd.renderer import Renderer
     W, H, depth = 160, 120, 15
     want = {n: frames(R, demo_scene, tex, sky, W, H, depth, True, n=n, rgb=False)[0][0][0] for n in (1, 2, 4, 8)}
-    r = Renderer(demo_scene, tex, sky, W, H, depth=depth, strict=True)
-    r.look(**CAM)
-    for n in (2, 2, 2, 8, 8, 1, 1, 4, 4, 4, 2):
-        r.w.set_supersample(n)
-        assert np.array_equal(r.render(), want[n]), n
-    r.release()
+    with rendering(Renderer, demo_scene, tex, sky, W, H, depth=depth, strict=True) as r:
+        for n in (2, 2, 2, 8, 8, 1, 1, 4, 4, 4, 2):
+            r.w.set_supersample(n)
+            assert np.array_equal(r.render(), want[n]), n
     assert not np.array_equal(want[1], want[2])
 
 
@@ -216,11 +166,9 @@ def test_row_strips_compose(R, demo_scene, tex, sky, n):
         parts = []
         for rank in range(3):
             r0, rows = strip_rows(H, 3, rank)
-            r = R(demo_scene, tex, sky, W, H, depth=depth, strict=strict, first_row=r0, rows=rows, supersample=n)
-            r.look(**CAM)
-            parts.append(r.render().copy())
-            assert parts[-1].shape == (rows * W,)
-            r.release()
+            with rendering(R, demo_scene, tex, sky, W, H, depth=depth, strict=strict, first_row=r0, rows=rows, supersample=n) as r:
+                parts.append(r.render().copy())
+                assert parts[-1].shape == (rows * W,)
         assert np.array_equal(np.concatenate(parts), full)
 
 
@@ -228,13 +176,9 @@ def test_pipelined_readback_returns_the_same_frame(R, demo_scene, tex, sky):
     W, H, n, depth = 2048, 2048, 2, 2
     outs = []
     for on in (1, 0):
-        r = R(demo_scene, tex, sky, W, H, depth=depth, supersample=n)
-        r.w.set_pipeline(on)
-        r.look(**CAM)
-        a = r.render().copy()
-        b = r.render().copy()
-        outs.append((a, b))
-        r.release()
+        with rendering(R, demo_scene, tex, sky, W, H, setup=lambda w: w.set_pipeline(on), depth=depth, supersample=n) as r:
+            (a, _), (b, _) = take(r, 2, rgb=False)
+            outs.append((a, b))
     assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1]) and np.array_equal(outs[0][0], outs[0][1])
 
 
@@ -242,11 +186,9 @@ def test_ray_buffer_keeps_its_one_ray_per_pixel_meaning(R, demo_scene, tex, sky)
     W, H = 96, 64
     rays = []
     for n in (1, 2):
-        r = R(demo_scene, tex, sky, W, H, depth=2, supersample=n)
-        r.look(**CAM)
-        r.render()
-        rays.append(r.read_rays().copy())
-        r.release()
+        with rendering(R, demo_scene, tex, sky, W, H, depth=2, supersample=n) as r:
+            r.render()
+            rays.append(r.read_rays().copy())
     assert rays[0].shape == (W * H, 16) and np.array_equal(rays[0], rays[1])
 
 
@@ -273,11 +215,9 @@ def test_unchanged_raypng_driver_is_supersampled_by_the_environment(R, tmp_path)
     img = api.read_png(str(tmp_path / "out" / "scene.png"))
     assert img.shape == (600, 800, 4)
     got = (img[..., 0].astype(np.uint32) << 16 | img[..., 1].astype(np.uint32) << 8 | img[..., 2]).reshape(-1)
-    r = R(Scene.load(os.path.join(FIX, "render.map")), None, None, 800, 600, depth=15, strict=True, supersample=2,
-          texture_paths=[os.path.join(FIX, nm + ".png") for nm in names], skybox_path=os.path.join(FIX, "stormydays.png"))
-    r.look(**CAM)
-    want = r.render().copy()
-    r.release()
+    with rendering(R, Scene.load(os.path.join(FIX, "render.map")), None, None, 800, 600, depth=15, strict=True, supersample=2,
+                   texture_paths=[os.path.join(FIX, nm + ".png") for nm in names], skybox_path=os.path.join(FIX, "stormydays.png")) as r:
+        want = r.render().copy()
     assert np.array_equal(got, want), int((got != want).sum())
     # and it is not the 1-sample frame
     env1 = dict(os.environ, CLWRAP_STRICT="1")
@@ -288,15 +228,7 @@ def test_unchanged_raypng_driver_is_supersampled_by_the_environment(R, tmp_path)
 
 
 # ------------------------------------------------------------------ 6. refusals: message + exit(1)
-def _run(snippet, env=None):
-    code = ("import sys; sys.path.insert(0, %r)\n"
-            "import numpy as np\n"
-            "import torch\n"
-            "from example_gui_opencl_raytracer_amd import api, scene, textures\n"
-            "from example_gui_opencl_raytracer_amd.renderer import Renderer\n"
-            "CAM = %r\n"
-            "sc, tex, sky = scene.render_map_scene(), textures.texture_layers(), textures.skybox_cross(64)\n" % (ROOT, CAM)) + snippet
-    return subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
+_run = run_child
 
 
 REFUSED = {
@@ -335,18 +267,13 @@ def test_factor_one_set_explicitly_is_the_default(R, demo_scene, tex, sky, W, H,
     for strict in (False, True):
         res = []
         for explicit in (False, True):
-            r = Renderer(demo_scene, tex, sky, W, H, depth=depth, strict=strict)
-            if explicit:
-                r.w.set_supersample(1)
-            r.look(**CAM)
-            frame = r.render().copy()
-            frame2 = r.render().copy()
-            flags = r.w.last_trace_flags()
-            costs = r.w.read_tile_costs()
-            r.w.enable_counters(1)
-            r.render()
-            c = r.w.read_counters()
-            r.release()
+            with rendering(Renderer, demo_scene, tex, sky, W, H, setup=(lambda w: w.set_supersample(1)) if explicit else None, depth=depth, strict=strict) as r:
+                (frame, _), (frame2, _) = take(r, 2, rgb=False)
+                flags = r.w.last_trace_flags()
+                costs = r.w.read_tile_costs()
+                r.w.enable_counters(1)
+                r.render()
+                c = r.w.read_counters()
             res.append((frame, frame2, costs, [c[k] for k in ("segments", "shadow_rays", "light_probes", "sky_fetches", "texel_fetches", "pushes")], flags))
         assert not res[0][4] & F_SS and res[0][4] == res[1][4]
         assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1])

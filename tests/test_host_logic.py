@@ -2,14 +2,14 @@
 prepared geometry, and that the C-ABI library loads and exports every declared symbol."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, CAM, ROOT
+from conftest import GOLDEN, CAM
 from example_gui_opencl_raytracer_amd import api, scene as S, textures as T
 from example_gui_opencl_raytracer_amd.renderer import strip_rows
+from render_common import declared_symbols
 
 
 # ------------------------------------------------------------------ scene archive (render.map)
@@ -249,11 +249,7 @@ def test_prepared_geometry_stream(demo_scene):
 # ------------------------------------------------------------------ the C-ABI library
 def test_library_exports_every_declared_symbol():
     L = api.load_library()
-    declared = set()
-    for hdr in ("opencl_wrap.h", "hip_wrap_ext.h"):
-        text = open(os.path.join(ROOT, "include", hdr)).read()
-        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        declared |= set(re.findall(r"\b((?:cl_wrap|clw_ext|clw_host)_\w+)\s*\(", text))
+    declared = declared_symbols("opencl_wrap.h", "hip_wrap_ext.h", prefixes=("cl_wrap", "clw_ext", "clw_host"))
     assert len(declared) >= 29 and declared == set(api.SYMBOLS)
     for name in sorted(declared):
         assert hasattr(L, name), f"libopencl_wrap_hip.so does not export {name}"
@@ -263,6 +259,15 @@ def test_library_exports_every_declared_symbol():
 def test_struct_mirror_matches_header():
     assert C.sizeof(api.cl_wrap) == 8 + 4 + 4 * 16 + 4 * 16 * 32 + 4 + 8 * 16 * 32   # impl, num, nums, ids, (pad), handles
     assert api.cl_wrap.buffers.offset % 8 == 0
+
+
+def test_renderer_is_a_context_manager():
+    """`with Renderer(...) as r:` -- the protocol only (entering and leaving need a device: every GPU test does both)"""
+    import inspect
+    from example_gui_opencl_raytracer_amd.renderer import Renderer
+    assert hasattr(Renderer, "__enter__") and hasattr(Renderer, "__exit__") and callable(Renderer.release)
+    assert list(inspect.signature(Renderer.__enter__).parameters) == ["self"]
+    inspect.signature(Renderer.__exit__).bind(None, None, None, None)                  # (self, exc_type, exc, traceback)
 
 
 # ------------------------------------------------------------------ bench.py --dump-outputs

@@ -2,7 +2,6 @@
 (the oracle stands in for the GPU renderer -- tests may use it), the strips are gathered by the
 same `distributed.gather_strips` bench.py uses, and rank 0 compares with a single-rank frame."""
 import os
-import socket
 import sys
 
 import numpy as np
@@ -11,14 +10,9 @@ import torch
 import torch.multiprocessing as mp
 
 from conftest import CAM, ROOT
+from render_common import free_port as _free_port
 
 W, H, DEPTH = 96, 60, 4      # 60 rows: strips of unequal height (8-row tiles: 32/28 and 24/24/12)
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _worker(rank, world, port, out_path):

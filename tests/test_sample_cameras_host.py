@@ -1,15 +1,15 @@
 """Per-sample cameras without a GPU: the C ABI, the two host helpers that build tables (thin lens, open shutter), and -- with the
 oracle alone -- that the definition the GPU tests hold the kernels to is not a trivial one."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-from conftest import CAM, ROOT
+from conftest import CAM
 from example_gui_opencl_raytracer_amd import api
-from sample_cameras_common import composed, resolve, rows_of, virtual_camera
+from render_common import declared_symbols, header_text, resolve
+from sample_cameras_common import composed, rows_of, slot, virtual_camera
 
 NEW = ["clw_ext_set_sample_cameras", "clw_ext_get_sample_cameras", "clw_ext_set_lens", "clw_host_lens_cameras", "clw_host_shutter_cameras"]
 SIZES = [(320, 240), (1920, 1080), (101, 75)]
@@ -24,23 +24,17 @@ def f64(v):
     return np.asarray(list(v), np.float32).astype(np.float64)
 
 
-def slot(k, n):
-    """sample k = sy * n + sx -> lens cell / shutter slot: k with its 2 log2 n bits reversed"""
-    bits = 2 * (n.bit_length() - 1)
-    return int(format(k, f"0{bits}b")[::-1], 2)
-
-
 # ------------------------------------------------------------------ 1. the ABI
 def test_header_library_and_mirror_agree_on_the_new_symbols():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hip_wrap_ext.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b((?:clw_ext|clw_host)_\w+)\s*\(", text))
+    declared = declared_symbols()
     L = api.load_library()
     for name in NEW:
         assert name in declared and name in api.SYMBOLS and hasattr(L, name), name
     assert C.sizeof(api.clw_sample_camera) == 48
-    assert re.search(r"typedef struct clw_sample_camera \{ float im_corner\[3\], origin\[3\], up\[3\], right\[3\]; \} clw_sample_camera;", text)
+    assert re.search(r"typedef struct clw_sample_camera \{ float im_corner\[3\], origin\[3\], up\[3\], right\[3\]; \} clw_sample_camera;",
+                     header_text(comments=False))
     for env in ("CLWRAP_APERTURE", "CLWRAP_FOCUS"):
-        assert env in open(os.path.join(ROOT, "include", "hip_wrap_ext.h")).read()
+        assert env in header_text()
 
 
 def test_renderer_takes_a_lens_and_a_table():

@@ -7,14 +7,9 @@ import pytest
 
 from adaptive_common import refine_mask_np
 from fuzz_scenes import SHAPED_SEEDS, random_scene, shaped_scene
+from render_common import api  # noqa: F401  (the fixture)
 from shape_common import ADAPTIVE, DEPTHS, FRAME, RAGGED, SHAPES, scene_of
 from sphere_motion_common import moved_scene
-
-
-@pytest.fixture(scope="module")
-def api():
-    from example_gui_opencl_raytracer_amd import api
-    return api
 
 
 SEED = 0x9E3779B1      # the seed offset of the GPU tests: it must show (soft shadows draw random points on the lights)

@@ -1,30 +1,22 @@
 """Moving spheres without a GPU: the C ABI, the two host helpers that ARE the definition (sample times, the moved scene) and -- with the
 oracle alone -- that the definition the GPU tests hold the kernels to is not a trivial one."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import CAM, ROOT
+from conftest import CAM
 from example_gui_opencl_raytracer_amd import api, scene
-from sample_cameras_common import composed, resolve
+from render_common import declared_symbols, resolve
+from sample_cameras_common import composed, slot
 from sphere_motion_common import DISP, field_disp, fma32, moved_scene
 
 NEW = ["clw_ext_set_sphere_motion", "clw_ext_get_sample_times", "clw_host_sample_times", "clw_host_spheres_at"]
 
 
-def slot(k, n):
-    """sample k = sy * n + sx -> shutter slot: k with its 2 log2 n bits reversed"""
-    bits = 2 * (n.bit_length() - 1)
-    return int(format(k, f"0{bits}b")[::-1], 2)
-
-
 # ------------------------------------------------------------------ 1. the ABI
 def test_header_library_and_mirror_agree_on_the_new_symbols():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hip_wrap_ext.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b((?:clw_ext|clw_host)_\w+)\s*\(", text))
+    declared = declared_symbols()
     L = api.load_library()
     for name in NEW:
         assert name in declared and name in api.SYMBOLS and hasattr(L, name), name

@@ -2,26 +2,15 @@
 (the n*W x n*H frame of the same camera is the W x H one with w_factor / n, h_factor / n), and the resolve order as a numpy spec.
 
 (Reading the factor back through clw_ext_get_supersample needs an initialised cl_wrap, i.e. a device: tests/test_gpu_supersample.py.)"""
-import os
 import re
 
 import numpy as np
 import pytest
 
-from conftest import CAM, ROOT
+from conftest import CAM
+from render_common import header_text, resolve
 
 from example_gui_opencl_raytracer_amd import api
-
-
-def resolve(rgb, W, H, n):                      # rgb: float32 [n*H * n*W, 3], virtual-frame order
-    s = np.clip(rgb.reshape(H * n, W * n, 3), np.float32(0), np.float32(1))
-    k = n
-    while k > 1: s = s[:, 0::2] + s[:, 1::2]; k //= 2
-    k = n
-    while k > 1: s = s[0::2] + s[1::2]; k //= 2
-    s = s * np.float32(1.0 / (n * n))
-    c = (s * np.float32(255.0)).astype(np.uint32)
-    return ((c[..., 0] << 16) | (c[..., 1] << 8) | c[..., 2]).reshape(-1), s.reshape(-1, 3)
 
 
 def resolve_y_first(rgb, W, H, n):
@@ -40,7 +29,7 @@ def pack1(rgb):
 
 
 def test_header_library_and_symbol_list_agree_on_the_supersample_symbols():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hip_wrap_ext.h")).read(), flags=re.S)
+    text = header_text(comments=False)
     assert re.search(r"\bvoid\s+clw_ext_set_supersample\s*\(\s*cl_wrap\s*\*\s*\w+\s*,\s*int\s+\w+\s*\)\s*;", text)
     assert re.search(r"\bint\s+clw_ext_get_supersample\s*\(\s*const\s+cl_wrap\s*\*\s*\w+\s*\)\s*;", text)
     L = api.load_library()
