@@ -46,6 +46,7 @@ SYMBOLS = [
     "clw_host_frame_seed", "clw_host_jitter_camera",
     "clw_ext_set_split", "clw_ext_get_split", "clw_ext_get_tpt", "clw_ext_read_tile_order", "clw_ext_unit_sched",
     "clw_ext_render_gbuffer", "clw_ext_read_gbuffer", "clw_ext_gbuffer_device_ptr", "clw_ext_pick",
+    "clw_ext_get_grid", "clw_ext_set_grid_pair",
 ]
 
 # the channels of the primary-hit pass (hip_wrap_ext.h: CLW_GB_*), the id of a miss and the pass's id in the timing log
@@ -106,6 +107,12 @@ class clw_sample_camera(C.Structure):
 class clw_pick(C.Structure):
     """What clw_ext_pick returns (44 bytes): the entries of one pixel in the channels of the primary-hit pass."""
     _fields_ = [("id", C.c_uint32), ("depth", C.c_float), ("point", C.c_float * 3), ("normal", C.c_float * 3), ("albedo", C.c_float * 3)]
+
+
+class clw_grid_info(C.Structure):
+    """What clw_ext_get_grid returns: the uniform grid of the scene as last prepared."""
+    _fields_ = [("built", C.c_int32), ("pair", C.c_int32), ("res", C.c_int32 * 3), ("ncells", C.c_uint32), ("pairs", C.c_uint64),
+                ("cell", C.c_float * 3), ("gmin", C.c_float * 3), ("reg_pad", C.c_float)]
 
 
 _lib = None
@@ -201,6 +208,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         L.clw_ext_gbuffer_device_ptr.restype = vp
         L.clw_ext_pick.argtypes = [W, u32, u32, C.POINTER(clw_pick)]
         L.clw_ext_pick.restype = C.c_int
+    if hasattr(L, "clw_ext_get_grid") or not os.environ.get("CLWRAP_LIB"):                # (an older A/B build may lack them)
+        L.clw_ext_get_grid.argtypes = [W, C.POINTER(clw_grid_info)]
+        L.clw_ext_get_grid.restype = C.c_int
+        L.clw_ext_set_grid_pair.argtypes = [W, C.c_int]
     L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
     L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
     L.clw_ext_read_tile_costs.restype = u32
@@ -451,6 +462,20 @@ class ClWrap:
     def set_split(self, slots=-1, min_quota=-1): self.L.clw_ext_set_split(C.byref(self.w), int(slots), int(min_quota))
     def set_shadow_through(self, f): self.L.clw_ext_set_shadow_through(C.byref(self.w), float(f))
     def set_grid(self, on): self.L.clw_ext_set_grid(C.byref(self.w), int(on))
+
+    def get_grid(self):
+        """The grid of the scene as last prepared (see clw_ext_get_grid): dict(built, pair, res, ncells, pairs, cell, gmin, reg_pad), or
+        None while no scene is prepared.  built 0 = the scene runs the linear scan (the other entries are then 0)."""
+        g = clw_grid_info()
+        if not self.L.clw_ext_get_grid(C.byref(self.w), C.byref(g)):
+            return None
+        return dict(built=int(g.built), pair=int(g.pair), res=tuple(int(x) for x in g.res), ncells=int(g.ncells), pairs=int(g.pairs),
+                    cell=tuple(float(x) for x in g.cell), gmin=tuple(float(x) for x in g.gmin), reg_pad=float(g.reg_pad))
+
+    def set_grid_pair(self, on=-1):
+        """Shadow walk of grid scenes: -1 default (paired unless CLWRAP_GRID_PAIR=0), 0 single, 1 paired where the shim's rule allows it.
+        Same image either way; the next launch prepares the scene again."""
+        self.L.clw_ext_set_grid_pair(C.byref(self.w), int(on))
     def set_tile_sched(self, on): self.L.clw_ext_set_tile_sched(C.byref(self.w), int(on))
     def set_variant(self, v): self.L.clw_ext_set_variant(C.byref(self.w), int(v))
     def last_trace_flags(self): return int(self.L.clw_ext_last_trace_flags(C.byref(self.w)))

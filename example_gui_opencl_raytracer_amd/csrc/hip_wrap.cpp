@@ -207,6 +207,8 @@ struct Impl {
     uint32_t *d_grid_start = nullptr, *d_grid_items = nullptr, *d_grid_box = nullptr;
     float* d_grid_geom = nullptr;
     wprep_grid grid{}; bool grid_ok = false, grid_pair = false; int use_grid = 1;
+    size_t grid_pairs = 0;                       /* cell-list entries of the grid built (clw_ext_get_grid) */
+    int grid_pair_req = -1;                      /* clw_ext_set_grid_pair: -1 = env CLWRAP_GRID_PAIR (default on), 0 / 1 */
     unsigned long long* d_counters = nullptr;
     /* cost-sorted tile dispatch: costs written by frame n order the tiles of frame n+1 */
     int sched = 1;
@@ -491,7 +493,8 @@ void prepare_scene(Impl* I, Buffer* s, uint32_t ns, Buffer* p, uint32_t np, Buff
         const float density = dens ? (float)atof(dens) : 1.6f;
         size_t pairs = 0;
         I->grid_pair = false;
-        if (env_int("CLWRAP_GRID_PAIR", 1) && nl > 0 && maxr > 0.0f && std::isfinite(maxr)) {
+        const bool want_pair = I->grid_pair_req < 0 ? env_int("CLWRAP_GRID_PAIR", 1) != 0 : I->grid_pair_req != 0;
+        if (want_pair && nl > 0 && maxr > 0.0f && std::isfinite(maxr)) {
             pairs = wprep_grid_plan(hs, ns, density, maxr, &I->grid);
             I->grid_pair = maxr <= 0.3f * std::min(I->grid.cell[0], std::min(I->grid.cell[1], I->grid.cell[2])) && pairs <= GRID_MAX_PAIRS;
         }
@@ -511,6 +514,7 @@ void prepare_scene(Impl* I, Buffer* s, uint32_t ns, Buffer* p, uint32_t np, Buff
             HIP_OK(hipMalloc((void**)&I->d_grid_geom, cg.size() * 4), "Couldn't allocate device memory");
             HIP_OK(hipMemcpy(I->d_grid_geom, cg.data(), cg.size() * 4, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
             I->grid_ok = true;
+            I->grid_pairs = pairs;
         }
     }
     I->geom_f4 = f4;
@@ -1355,6 +1359,23 @@ void clw_ext_get_split(const cl_wrap* wrap, uint32_t* slots, uint32_t* min_quota
 }
 void clw_ext_set_shadow_through(cl_wrap* wrap, float factor) { impl_of(wrap)->through = factor; }
 void clw_ext_set_grid(cl_wrap* wrap, int on) { impl_of(wrap)->use_grid = on ? 1 : 0; }
+int clw_ext_get_grid(const cl_wrap* wrap, clw_grid_info* out) {
+    const Impl* I = impl_of(wrap);
+    if (!I->d_geom || !out) return 0;
+    memset(out, 0, sizeof *out);
+    if (!I->grid_ok) return 1;
+    out->built = 1; out->pair = I->grid_pair ? 1 : 0;
+    out->ncells = I->grid.ncells; out->pairs = (uint64_t)I->grid_pairs; out->reg_pad = I->grid.reg_pad;
+    for (int a = 0; a < 3; a++) { out->res[a] = I->grid.res[a]; out->cell[a] = I->grid.cell[a]; out->gmin[a] = I->grid.gmin[a]; }
+    return 1;
+}
+void clw_ext_set_grid_pair(cl_wrap* wrap, int on) {
+    if (on < -1 || on > 1) die("The grid's shadow walk must be -1 (default), 0 (single) or 1 (paired)");
+    Impl* I = impl_of(wrap);
+    I->grid_pair_req = on;
+    I->prep_s = I->prep_p = I->prep_l = nullptr;      /* the next launch prepares the scene again, as clw_ext_invalidate_scene makes it */
+    I->acc.epoch++;
+}
 void clw_ext_set_tile_sched(cl_wrap* wrap, int on) { Impl* I = impl_of(wrap); I->sched = on ? 1 : 0; for (auto& sc : I->scheds) sc.reset(); }
 void clw_ext_set_variant(cl_wrap* wrap, int variant) { impl_of(wrap)->variant = variant; }
 int clw_ext_last_trace_flags(cl_wrap* wrap) { return impl_of(wrap)->last_trace_flags; }

@@ -117,17 +117,29 @@ void wprep_build_lpt(const uint8_t* planes, uint32_t np, const uint8_t* lights, 
 }
 
 /* ---- uniform grid ---------------------------------------------------------------------------------- */
+/* floor(x) as a cell index of an axis with `res` cells, clamped BEFORE the conversion: a float outside int's range (or a NaN) never
+ * reaches the cast, which C leaves undefined for it */
+static int cell_index(float x, int res) {
+    float f = floorf(x);
+    return !(f >= 0.0f) ? 0 : (f >= (float)res ? res - 1 : (int)f);
+}
+
 static void sphere_cells(const uint8_t* s, const wprep_grid* g, int lo[3], int hi[3]) {
-    float r = ldf(s, 16);
+    float r = fabsf(ldf(s, 16));                /* the sphere test only reads r * r: a negative radius is the sphere of its magnitude */
     for (int a = 0; a < 3; a++) {
         float c = ldf(s, 4 * (size_t)a);
         /* conservative: the box is widened by a margin far larger than the traversal's rounding error */
         float pad = 1e-3f * g->cell[a] + 1e-5f * (fabsf(c) + r) + g->reg_pad;
-        int l = (int)floorf((c - r - pad - g->gmin[a]) * g->inv[a]);
-        int h = (int)floorf((c + r + pad - g->gmin[a]) * g->inv[a]);
-        lo[a] = l < 0 ? 0 : (l >= g->res[a] ? g->res[a] - 1 : l);
-        hi[a] = h < 0 ? 0 : (h >= g->res[a] ? g->res[a] - 1 : h);
+        lo[a] = cell_index((c - r - pad - g->gmin[a]) * g->inv[a], g->res[a]);
+        hi[a] = cell_index((c + r + pad - g->gmin[a]) * g->inv[a], g->res[a]);
     }
+}
+
+/* no grid for this scene: a one-cell placeholder in `g` and a pair count no limit admits (the caller then keeps the linear scan) */
+static size_t grid_refused(wprep_grid* g) {
+    for (int a = 0; a < 3; a++) { g->gmin[a] = 0.0f; g->cell[a] = 1.0f; g->inv[a] = 1.0f; g->res[a] = 1; }
+    g->ncells = 1;
+    return SIZE_MAX;
 }
 
 size_t wprep_grid_plan(const uint8_t* spheres, uint32_t ns, float density, float reg_pad, wprep_grid* g) {
@@ -135,9 +147,11 @@ size_t wprep_grid_plan(const uint8_t* spheres, uint32_t ns, float density, float
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (uint32_t i = 0; i < ns; i++) {
         const uint8_t* s = spheres + 96 * (size_t)i;
-        float r = ldf(s, 16);
+        float r = fabsf(ldf(s, 16));
+        if (!isfinite(r)) return grid_refused(g);
         for (int a = 0; a < 3; a++) {
             float c = ldf(s, 4 * (size_t)a);
+            if (!isfinite(c)) return grid_refused(g);       /* a sphere that is not finite has no box: such a scene takes the linear scan */
             if (c - r < mn[a]) mn[a] = c - r;
             if (c + r > mx[a]) mx[a] = c + r;
         }
@@ -152,13 +166,14 @@ size_t wprep_grid_plan(const uint8_t* spheres, uint32_t ns, float density, float
          * 1.0 above a layer 0.6 thick; 9.5 -> 5 cells per shadow ray at C4) */
         float pad = 1e-2f * ext[a] + 2e-5f * fmaxf(fabsf(mn[a]), fabsf(mx[a])) + 1e-3f + 1.01f * g->reg_pad;
         mn[a] -= pad; mx[a] += pad; ext[a] = mx[a] - mn[a];
+        if (!isfinite(mn[a]) || !isfinite(ext[a])) return grid_refused(g);   /* finite spheres whose bounds overflow a float (or no sphere) */
         vol *= ext[a];
     }
     /* cubic cells about one mean sphere diameter wide (finer cells make every sphere span several of them, coarser
      * ones put several spheres in a cell), kept between 1/8 and 4 spheres per cell on average; `density` scales
      * the side (tuning knob; the shim passes 1.6); 1..1024 cells per axis (10-bit cell boxes), <= 2^22 cells */
     double diam = 0.0;
-    for (uint32_t i = 0; i < ns; i++) diam += 2.0 * ldf(spheres + 96 * (size_t)i, 16);
+    for (uint32_t i = 0; i < ns; i++) diam += 2.0 * fabsf(ldf(spheres + 96 * (size_t)i, 16));
     diam /= (double)(ns ? ns : 1);
     float side_lo = cbrtf(vol * 0.125f / (float)(ns ? ns : 1)), side_hi = cbrtf(vol * 4.0f / (float)(ns ? ns : 1));
     float side = (float)diam * density;
@@ -166,9 +181,8 @@ size_t wprep_grid_plan(const uint8_t* spheres, uint32_t ns, float density, float
     if (side > side_hi) side = side_hi;
     uint64_t total = 1;
     for (int a = 0; a < 3; a++) {
-        int n = (int)(ext[a] / side + 0.5f);
-        if (n < 1) n = 1;
-        if (n > 1024) n = 1024;
+        float q = ext[a] / side + 0.5f;         /* clamped as a float: a thin scene a long way across asks for more cells than an int holds */
+        int n = !(q >= 1.0f) ? 1 : (q >= 1024.0f ? 1024 : (int)q);
         g->res[a] = n;
         total *= (uint64_t)n;
     }

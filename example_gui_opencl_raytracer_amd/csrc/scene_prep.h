@@ -27,7 +27,10 @@ typedef struct {
 } wprep_grid;
 /* reg_pad > 0 (the largest light radius): the two soft-shadow samples of a light can then share ONE walk along the ray to the light's
  * centre -- a sphere either sample meets lies within reg_pad of that ray, so a cell the walk visits lists it (whitted_trace.inc
- * wt_grid_shadow_pair) */
+ * wt_grid_shadow_pair).
+ * A scene with a centre or radius that is not finite, or whose padded bounds overflow a float, gets no grid: wprep_grid_plan returns
+ * SIZE_MAX (above any limit a caller sets; `g` is a one-cell placeholder) and wprep_grid_fill must not be called.  A negative radius is
+ * the sphere of its magnitude, as in the sphere test (r * r). */
 size_t wprep_grid_plan(const uint8_t* spheres, uint32_t ns, float density, float reg_pad, wprep_grid* g);
 void wprep_grid_fill(const uint8_t* spheres, uint32_t ns, const wprep_grid* g, uint32_t* start, uint32_t* items,
                      uint32_t* box);

@@ -303,6 +303,25 @@ void clw_ext_set_shadow_through(cl_wrap* wrap, float factor);
  * spheres registered in the cells they cross instead of all of them.  Same arithmetic per test, same nearest
  * hit and same shadow factor as the reference's linear scan; 0 forces the linear scan. */
 void clw_ext_set_grid(cl_wrap* wrap, int on);
+/* The grid of the scene as last prepared (the first trace, G-buffer or unit-scene launch after the scene changed prepares it).  `built` 0: the
+ * scene has no grid -- at most 256 spheres, a sphere that is not finite, or more cell-list entries than the shim allows -- and runs the linear
+ * scan; every other field is then 0.  `pair` 1: the two soft-shadow samples of a light share one walk along the ray to its centre
+ * (wt_grid_shadow_pair) and every sphere is listed `reg_pad` beyond its box; 0: every shadow ray walks on its own (wt_grid_shadow), which is
+ * also what the tree-parallel tail always does.  The shim pairs when the largest light radius is at most 0.3 of the smallest cell side and
+ * the padded lists fit.  res / cell / gmin: cells per axis, their sides, the low corner of the bounds; ncells = res[0] * res[1] * res[2];
+ * pairs = (cell, sphere) entries = start[ncells].  Returns 1, or 0 (and writes nothing) while no scene is prepared.  For tests. */
+typedef struct {
+    int32_t built, pair;
+    int32_t res[3];
+    uint32_t ncells;
+    uint64_t pairs;
+    float cell[3], gmin[3], reg_pad;
+} clw_grid_info;
+int clw_ext_get_grid(const cl_wrap* wrap, clw_grid_info* out);
+/* Which shadow walk a grid scene takes: -1 the default (pairing unless env CLWRAP_GRID_PAIR=0), 0 never pair, 1 pair wherever the rule above
+ * allows it, whatever the environment says (clw_ext_get_grid reports what came of it).  Same image either way.  Takes effect at the next scene
+ * preparation and forces one, as a changed scene does.  Errors (print + exit(1)): a value outside [-1, 1]. */
+void clw_ext_set_grid_pair(cl_wrap* wrap, int on);
 
 /* Cost-sorted tile dispatch (default on): every 8x8 tile reports its cost, and the next frame serves each
  * XCD's tiles heaviest-first, so the expensive refraction tiles no longer end up in the tail of the launch.

@@ -182,3 +182,126 @@ def deep_scene(seed: int):
     cam = dict(origin=(float(np.float32(rng.uniform(-0.5, 0.5))), float(np.float32(rng.uniform(0.4, 1.4) * pitch)), float(np.float32(-rng.uniform(1.2, 2.2) * pitch))),
                look=(float(np.float32(rng.uniform(-0.1, 0.1))), float(np.float32(rng.uniform(-0.35, -0.05))), 1.0), fov=90.0, focal=1.0)
     return S.Scene(sph, pln, lgt), cam
+
+
+# ---- grid layouts: scenes of more than 256 spheres whose uniform grid (csrc/scene_prep.c) and both of its shadow walks decide something
+GRID_LAYOUTS = ("cloud", "giants", "coincident", "touching", "tower", "offset")
+GRID_3D = ("cloud", "giants", "tower", "offset")          # layouts whose grid has more than one cell on every axis
+GRID_OFFSET = (4000.0, 4000.0, 4000.0)
+GLASS_FIELDS = ("ambient", "diffuse", "specular", "shininess", "transperent", "dielectric", "n", "reflectivity")
+
+
+def _plastic_spheres(n):
+    return S.sphere_grid_scene(n, 1).spheres.copy()          # n plastic spheres with hashed colours: the geometry is overwritten
+
+
+def _glass(sp, sel):
+    g = S.glass()
+    for name in GLASS_FIELDS:
+        sp["material"][name][sel] = g[name]
+
+
+def _cam(origin, look, fov):
+    return dict(origin=tuple(float(np.float32(x)) for x in origin), look=tuple(float(x) for x in look), fov=float(fov), focal=1.0)
+
+
+def grid_layout(name: str, lights: str = "small"):
+    """-> (scene, [camera outside the sphere set, camera inside it]).  Every layout keeps the demo floor plane and three lights.
+    lights "small": radii <= 0.1, a fraction of a cell (the grid pairs the two samples of a light in one walk); "large": light 0 has radius
+    1.5 and sits INSIDE the sphere set (more than 0.3 of a cell: every shadow ray walks on its own).  Every sphere lies within 40 units of
+    every camera and light, the cameras see the floor beyond 300 units in at most one pixel row, and radii are >= 0.05: inside the domain where the float sphere test still decides.
+      cloud       600 spheres scattered in a box, radii 0.12 .. 1.2, a third glass (test_gpu_parity's cloud, seed 1)
+      giants      400 spheres of r 0.05 .. 0.15 in a box and three of r 6, 8 and 10 (opaque, glass, glass) around its middle: listed in
+                  (nearly) every cell, a glass one crossed over a dozen consecutive cells; the inside camera sits in both glass giants
+      coincident  300 spheres on ONE centre, radii 0.5 .. 0.9 in steps of 1 / 64 (equal-t ties), even indices opaque (r <= 0.7) and odd ones
+                  glass, and 10 elsewhere: long cell lists, every glass shell counted once; the inside camera sits between the shells
+      touching    r 0.5 at pitch 1, 14 x 2 x 14: tangent spheres; the inside camera sits in a void of the lattice
+      tower       a column 3 x 66 x 3 of r 0.3 at pitch 1 (the tallest that keeps its ends within 40 units of a camera and light at
+                  mid-height): res[1] far above res[0] and res[2]; the inside camera looks up the column
+      offset      cloud moved by GRID_OFFSET -- cameras, lights and the floor with it
+    The floor matters: a shadow ray starts at its hit point, and a floor point thousands of units from the spheres is as far outside that
+    domain as a camera there (the linear scan then "hits" spheres whose padded boxes the ray misses, by rounding alone).  So the floor
+    moves with `offset`, and the tower's outside camera looks down at the column instead of at the horizon behind it."""
+    assert name in GRID_LAYOUTS and lights in ("small", "large")
+    base = S.render_map_scene()
+    planes, li = base.planes[:1].copy(), base.lights.copy()
+    li["radius"] = (0.1, 0.08, 0.1)
+    shift = np.zeros(3, np.float32)
+    if name in ("cloud", "offset"):
+        rng = np.random.default_rng(1)
+        sp = S.sphere_grid_scene(25, 24).spheres.copy()
+        n = len(sp)
+        sp["origin"][:, 0] = rng.uniform(-9.0, 9.0, n).astype(np.float32)
+        sp["origin"][:, 1] = rng.uniform(0.2, 7.0, n).astype(np.float32)
+        sp["origin"][:, 2] = rng.uniform(2.0, 20.0, n).astype(np.float32)
+        sp["radius"] = (0.12 * 10.0 ** rng.uniform(0.0, 1.0, n)).astype(np.float32)
+        _glass(sp, rng.random(n) < 0.33)
+        li["origin"] = [(0.0, 3.5, 11.0), (-4.0, 1.5, 6.0), (3.0, 9.0, 4.0)]
+        big = (-3.0, 4.0, 14.0)
+        cams = [_cam((0.0, 4.0, -6.0), (0.0, -0.1, 1.0), 80.0), _cam((1.0, 3.0, 10.0), (-0.3, 0.1, 1.0), 100.0)]
+        if name == "offset":
+            shift = np.asarray(GRID_OFFSET, np.float32)
+    elif name == "giants":
+        rng = np.random.default_rng(0x61A27)
+        n = 400
+        sp = _plastic_spheres(n + 3)
+        sp["origin"][:n] = rng.uniform([-8.0, 0.3, 2.0], [8.0, 12.0, 18.0], (n, 3)).astype(np.float32)
+        sp["radius"][:n] = rng.uniform(0.05, 0.15, n).astype(np.float32)
+        sel = np.zeros(n + 3, bool)
+        sel[:n] = rng.random(n) < 0.33
+        sp["origin"][n:] = [(0.0, 6.0, 10.0), (1.5, 6.0, 9.0), (-1.0, 7.0, 11.0)]
+        sp["radius"][n:] = (6.0, 8.0, 10.0)
+        sel[n + 1:] = True
+        _glass(sp, sel)
+        li["origin"] = [(0.5, 6.5, 2.5), (-6.0, 9.0, 5.0), (7.5, 3.0, 16.0)]      # in both glass giants; in the r 10 one; in none
+        big = (-3.0, 5.0, 4.0)
+        cams = [_cam((0.0, 6.0, -16.0), (0.0, 0.0, 1.0), 80.0), _cam((0.0, 6.0, 3.0), (0.6, -0.1, 1.0), 100.0)]
+    elif name == "coincident":
+        rng = np.random.default_rng(0xC01C)
+        n = 300
+        sp = _plastic_spheres(n + 10)
+        sp["origin"][:n] = (0.0, 2.0, 8.0)
+        r = np.where(np.arange(n) % 2 == 0, rng.uniform(0.5, 0.7, n), rng.uniform(0.5, 0.9, n))
+        sp["radius"][:n] = (np.round(r * 64.0) / 64.0).astype(np.float32)
+        sp["origin"][n:] = rng.uniform([-6.0, 0.5, 3.0], [6.0, 5.0, 14.0], (10, 3)).astype(np.float32)
+        sp["radius"][n:] = rng.uniform(0.3, 0.6, 10).astype(np.float32)
+        sel = np.zeros(n + 10, bool)
+        sel[1:n:2] = True
+        _glass(sp, sel)
+        li["origin"] = [(-2.5, 4.5, 6.0), (2.0, 1.0, 5.0), (0.5, 5.0, 11.0)]
+        big = (-2.0, 2.5, 9.5)
+        cams = [_cam((0.0, 2.5, 4.5), (0.0, -0.1, 1.0), 70.0), _cam((0.8, 2.0, 8.0), (-1.0, 0.05, 0.3), 100.0)]
+    elif name == "touching":
+        rng = np.random.default_rng(0x70C4)
+        n = 14 * 2 * 14
+        sp = _plastic_spheres(n)
+        k = np.arange(n)
+        sp["origin"][:, 0] = (k % 14).astype(np.float32) - np.float32(6.5)
+        sp["origin"][:, 1] = ((k // 14) % 2).astype(np.float32) + np.float32(0.5)
+        sp["origin"][:, 2] = (k // 28).astype(np.float32) + np.float32(2.0)
+        sp["radius"] = 0.5
+        _glass(sp, rng.random(n) < 0.33)
+        li["origin"] = [(0.0, 4.0, 8.0), (-3.0, 3.0, 5.0), (2.0, 1.0, 6.5)]         # the last one in a void of the lattice
+        big = (3.0, 1.0, 10.5)
+        cams = [_cam((0.0, 5.0, -4.0), (0.0, -0.4, 1.0), 80.0), _cam((0.0, 1.0, 8.5), (1.0, 0.1, 0.3), 100.0)]
+    else:
+        rng = np.random.default_rng(0x703E)
+        n = 3 * 66 * 3
+        sp = _plastic_spheres(n)
+        k = np.arange(n)
+        sp["origin"][:, 0] = (k % 3).astype(np.float32) - np.float32(1.0)
+        sp["origin"][:, 1] = (k // 9).astype(np.float32) + np.float32(0.5)
+        sp["origin"][:, 2] = ((k // 3) % 3).astype(np.float32) + np.float32(5.0)
+        sp["radius"] = 0.3
+        _glass(sp, rng.random(n) < 0.33)
+        li["origin"] = [(-0.5, 30.0, 6.5), (3.0, 36.0, 3.0), (0.5, 34.0, 5.5)]
+        big = (0.5, 38.0, 6.5)
+        cams = [_cam((-9.0, 38.0, 6.0), (1.0, -1.0, 0.0), 60.0), _cam((-0.5, 33.0, 5.5), (0.2, 1.0, 0.3), 100.0)]
+    if lights == "large":
+        li["origin"][0] = big
+        li["radius"][0] = 1.5
+    sp["origin"] += shift
+    li["origin"] += shift
+    planes["point_in_plane"] += shift
+    cams = [dict(c, origin=tuple(float(x) for x in (np.asarray(c["origin"], np.float32) + shift))) for c in cams]
+    return S.Scene(sp, planes, li), cams

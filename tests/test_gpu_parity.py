@@ -310,7 +310,8 @@ def test_light_spheres_seen_through_the_grid(R, oracle, tex, sky, kind):
     """findLightIntersection's visibility check (is an opaque sphere met before the light sphere? primitives.cl:296-318)
     walks the grid in the big-scene build.  Big light spheres above, at the edge of and INSIDE a field of 576 spheres, seen
     from above and grazing along the rows (where field spheres hide them, transparent ones must not): grid == linear scan
-    in both builds, strict == oracle, and the lights really are in view."""
+    in both builds, strict == oracle, and the lights really are in view.  Lights this large are never paired: every shadow
+    ray of these frames takes the single walk (wt_grid_shadow), which the grid's read-out confirms at the end."""
     from example_gui_opencl_raytracer_amd import scene
     from example_gui_opencl_raytracer_amd.renderer import Renderer
     sc = scene.sphere_grid_scene(24, 24)
@@ -333,6 +334,11 @@ def test_light_spheres_seen_through_the_grid(R, oracle, tex, sky, kind):
                 outs[(strict, grid)] = gpu_frame(Renderer, sc, tex, sky, w, h, depth, strict, cam, setup=lambda wrap: wrap.set_grid(grid))
             assert np.array_equal(outs[(strict, 1)], outs[(strict, 0)]), (kind, cam, strict)
         check_exact(outs[(True, 1)], want, f"lights through the grid, {kind}")
+    # lights this large (1.5 against cells about 0.96 wide) are beyond what the grid pairs: every shadow ray above walked on its own
+    with rendering(Renderer, sc, tex, sky, w, h, cam=GRID_CAMS[0], depth=depth, strict=True) as r:
+        take(r, rgb=False)
+        g = r.w.get_grid()
+        assert g["built"] == 1 and g["pair"] == 0 and g["res"][1] == 1 and r.w.last_trace_flags() & 16, g
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
