@@ -47,6 +47,7 @@ SYMBOLS = [
     "clw_ext_set_split", "clw_ext_get_split", "clw_ext_get_tpt", "clw_ext_read_tile_order", "clw_ext_unit_sched",
     "clw_ext_render_gbuffer", "clw_ext_read_gbuffer", "clw_ext_gbuffer_device_ptr", "clw_ext_pick",
     "clw_ext_get_grid", "clw_ext_set_grid_pair",
+    "clw_host_overlay", "clw_ext_render_overlay", "clw_ext_read_overlay", "clw_ext_overlay_device_ptr", "clw_ext_unit_overlay",
 ]
 
 # the channels of the primary-hit pass (hip_wrap_ext.h: CLW_GB_*), the id of a miss and the pass's id in the timing log
@@ -56,6 +57,10 @@ ID_SPHERE, ID_PLANE, ID_LIGHT = 0, 1, 2
 TIMING_GBUFFER = 0x47425546
 GB_CHANNELS = {"depth": (GB_DEPTH, np.float32, 1), "id": (GB_ID, np.uint32, 1), "normal": (GB_NORMAL, np.float32, 3),
                "point": (GB_POINT, np.float32, 3), "albedo": (GB_ALBEDO, np.float32, 3)}     # name -> (bit, dtype, entries per work-item)
+
+# the selection overlay (hip_wrap_ext.h: CLW_OV_*): what a style draws, and the pass's id in the timing log
+OV_OUTLINE, OV_FILL, OV_EDGES, OV_ALL = 1, 2, 4, 7
+TIMING_OVERLAY = 0x4F564C59
 
 
 def id_kind(ids):
@@ -107,6 +112,12 @@ class clw_sample_camera(C.Structure):
 class clw_pick(C.Structure):
     """What clw_ext_pick returns (44 bytes): the entries of one pixel in the channels of the primary-hit pass."""
     _fields_ = [("id", C.c_uint32), ("depth", C.c_float), ("point", C.c_float * 3), ("normal", C.c_float * 3), ("albedo", C.c_float * 3)]
+
+
+class clw_overlay(C.Structure):
+    """The style of a selection overlay (24 bytes): what to draw (OV_* bits), the outline's width and the three colours, 0x00RRGGBB."""
+    _fields_ = [("flags", C.c_uint32), ("radius", C.c_uint32), ("outline_rgb", C.c_uint32), ("fill_rgb", C.c_uint32), ("fill_alpha", C.c_uint32),
+                ("edge_rgb", C.c_uint32)]
 
 
 class clw_grid_info(C.Structure):
@@ -212,6 +223,18 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         L.clw_ext_get_grid.argtypes = [W, C.POINTER(clw_grid_info)]
         L.clw_ext_get_grid.restype = C.c_int
         L.clw_ext_set_grid_pair.argtypes = [W, C.c_int]
+    if hasattr(L, "clw_ext_render_overlay") or not os.environ.get("CLWRAP_LIB"):          # (an older A/B build may lack them)
+        OV = C.POINTER(clw_overlay)
+        L.clw_host_overlay.argtypes = [vp, vp, u32, u32, OV, vp, u32, vp]
+        L.clw_host_overlay.restype = C.c_int
+        L.clw_ext_render_overlay.argtypes = [W, OV, vp, u32]
+        L.clw_ext_render_overlay.restype = u32
+        L.clw_ext_read_overlay.argtypes = [W, vp, u32]
+        L.clw_ext_read_overlay.restype = u32
+        L.clw_ext_overlay_device_ptr.argtypes = [W]
+        L.clw_ext_overlay_device_ptr.restype = vp
+        L.clw_ext_unit_overlay.argtypes = [W, vp, vp, u32, u32, OV, vp, u32, vp]
+        L.clw_ext_unit_overlay.restype = u32
     L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
     L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
     L.clw_ext_read_tile_costs.restype = u32
@@ -308,6 +331,30 @@ def refine_mask(xrgb, width: int, rows: int, n: int, threshold: int) -> np.ndarr
     out = np.zeros((-(-rows // b), -(-width // b)), np.uint8)
     if not load_library().clw_host_refine_mask(_ptr(xrgb), width, rows, n, int(threshold), _ptr(out)):
         raise ValueError("clw_host_refine_mask rejects these arguments (threshold in [0, 256])")
+    return out
+
+
+def overlay_style(flags: int, radius: int = 2, outline: int = 0xFFFF00, fill: int = 0, alpha: int = 0, edges: int = 0) -> clw_overlay:
+    """A clw_overlay from its six words (nothing is checked here: the library refuses what hip_wrap_ext.h says it refuses)."""
+    return clw_overlay(int(flags), int(radius), int(outline), int(fill), int(alpha), int(edges))
+
+
+def _selection(sel) -> np.ndarray:
+    return np.ascontiguousarray(np.atleast_1d(np.asarray(sel, np.uint32) if sel is not None else np.zeros(0, np.uint32)).reshape(-1))
+
+
+def overlay(frame, ids, width: int, rows: int, style: clw_overlay, sel) -> np.ndarray:
+    """clw_host_overlay: the selection overlay of a packed width x rows frame and its id channel, on the host -- THE definition the device pass is
+    held to -> uint32 [width * rows].  `sel`: the selected ids (at most 64 words, or None)."""
+    frame = np.ascontiguousarray(frame, np.uint32).reshape(-1)
+    ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+    width, rows = int(width), int(rows)
+    if width <= 0 or rows <= 0 or frame.size != width * rows or ids.size != width * rows:
+        raise ValueError("clw_host_overlay rejects these arguments (a frame and ids of width * rows words each)")
+    sel = _selection(sel)
+    out = np.empty(width * rows, np.uint32)
+    if not load_library().clw_host_overlay(_ptr(frame), _ptr(ids), width, rows, C.byref(style), _ptr(sel) if sel.size else None, sel.size, _ptr(out)):
+        raise ValueError("clw_host_overlay rejects this style or selection (flags in 1..7, radius in 1..4, alpha in 0..256, at most 64 ids)")
     return out
 
 
@@ -530,6 +577,34 @@ class ClWrap:
         """clw_ext_pick: the clw_pick of frame pixel (x, y), or None (no camera latched, or the pixel is not one of this wrapper's)."""
         p = clw_pick()
         return p if self.L.clw_ext_pick(C.byref(self.w), int(x), int(y), C.byref(p)) else None
+
+    def render_overlay(self, style: clw_overlay, sel) -> int:
+        """clw_ext_render_overlay: compose the selection overlay of the wrapper's range on the device -> work-items (0 = refused, nothing launched)."""
+        sel = _selection(sel)
+        return int(self.L.clw_ext_render_overlay(C.byref(self.w), C.byref(style), _ptr(sel) if sel.size else None, sel.size))
+
+    def read_overlay(self) -> np.ndarray:
+        """The overlay frame of the last render_overlay -> uint32 [n]; empty before the first."""
+        nbytes = int(self.L.clw_ext_read_overlay(C.byref(self.w), None, 0))
+        out = np.empty(nbytes // 4, np.uint32)
+        if nbytes:
+            assert self.L.clw_ext_read_overlay(C.byref(self.w), _ptr(out), nbytes) == nbytes
+        return out
+
+    def overlay_device_ptr(self):
+        """Device address of the overlay frame of the last render_overlay (None before the first)."""
+        return self.L.clw_ext_overlay_device_ptr(C.byref(self.w))
+
+    def unit_overlay(self, frame, ids, width: int, rows: int, style: clw_overlay, sel):
+        """clw_ext_unit_overlay: the device pass on a synthetic frame and id channel -> uint32 [width * rows], or None when it is refused."""
+        frame = np.ascontiguousarray(frame, np.uint32).reshape(-1)
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        assert frame.size == int(width) * int(rows) == ids.size
+        sel = _selection(sel)
+        out = np.empty(frame.size, np.uint32)
+        n = self.L.clw_ext_unit_overlay(C.byref(self.w), _ptr(frame), _ptr(ids), int(width), int(rows), C.byref(style),
+                                        _ptr(sel) if sel.size else None, sel.size, _ptr(out))
+        return out if n == frame.size and n else None
 
     def set_adaptive(self, threshold): self.L.clw_ext_set_adaptive(C.byref(self.w), int(threshold))
     def get_adaptive(self): return int(self.L.clw_ext_get_adaptive(C.byref(self.w)))

@@ -25,6 +25,7 @@
 
 #include "../../include/hip_wrap_ext.h"
 #include "launch_plan.h"
+#include "overlay_host.h"
 #include "png_codec.h"
 #include "scene_prep.h"
 #include "whitted_params.h"
@@ -39,6 +40,8 @@ extern "C" hipError_t wt_fast_launch_unit_scene(const whitted_params*, int, int,
 extern "C" hipError_t wt_strict_launch_unit_scene(const whitted_params*, int, int, const float*, float*, unsigned, unsigned, unsigned, size_t, hipStream_t);
 extern "C" hipError_t wt_fast_launch_gbuffer(const whitted_params*, int, unsigned, size_t, float*, unsigned*, float*, float*, float*, hipStream_t);
 extern "C" hipError_t wt_strict_launch_gbuffer(const whitted_params*, int, unsigned, size_t, float*, unsigned*, float*, float*, float*, hipStream_t);
+extern "C" hipError_t wt_fast_launch_overlay(const unsigned*, const unsigned*, unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, unsigned, hipStream_t);
+extern "C" hipError_t wt_strict_launch_overlay(const unsigned*, const unsigned*, unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, unsigned, hipStream_t);
 extern "C" hipError_t wt_fast_launch_cams(const wt_cam_table*, float*, hipStream_t);
 extern "C" hipError_t wt_fast_launch_classify(const unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned char*, unsigned*, unsigned*, unsigned, hipStream_t);
 extern "C" hipError_t wt_fast_launch_sched(const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
@@ -197,6 +200,15 @@ struct Impl {
         hipEvent_t done = nullptr;
         void free_channels() { for (void*& q : chan) { if (q) (void)hipFree(q); q = nullptr; } n = 0; written = 0; }
     } gb;
+    /* the selection overlay (clw_ext_render_overlay; whitted_overlay.inc): its own id buffer -- the primary-hit pass writes it, `gb` is not touched --
+     * and the composed frame, both sized for the pass's range; `done` as above */
+    struct Overlay {
+        uint32_t* ids = nullptr; uint32_t* frame = nullptr;
+        uint32_t n = 0;                 /* work-items the buffers are sized for */
+        bool written = false;           /* a pass has composed `frame` */
+        hipEvent_t done = nullptr;
+        void free_buffers() { if (ids) (void)hipFree(ids); if (frame) (void)hipFree(frame); ids = frame = nullptr; n = 0; written = false; }
+    } ov;
     /* prepared scene cache */
     const Buffer *prep_s = nullptr, *prep_p = nullptr, *prep_l = nullptr;
     uint32_t prep_ns = 0, prep_np = 0, prep_nl = 0;
@@ -997,6 +1009,18 @@ int gbuffer_channel(uint32_t channel) {
     return -1;
 }
 
+/* ---- the selection overlay ------------------------------------------------------------------------------------------------------- */
+/* wt_overlay over a width x rows range on the launch stream; the caller has checked style and selection (wt_overlay_check).  The kernel is
+ * integer work compiled into both units; the build in use launches its own copy. */
+void launch_overlay(Impl* I, const uint32_t* frame, const uint32_t* ids, uint32_t* out, uint32_t width, uint32_t rows, const clw_overlay& st,
+                    const uint32_t* sel, uint32_t count, bool timed) {
+    const unsigned style[5] = {st.radius, st.outline_rgb, st.fill_rgb, st.fill_alpha, st.edge_rgb};
+    LaunchTimer t(I, CLW_TIMING_OVERLAY, timed);
+    hipError_t e = (I->strict ? wt_strict_launch_overlay : wt_fast_launch_overlay)(frame, ids, out, width, rows, st.flags, style, sel, count, I->stream);
+    if (e != hipSuccess) die("Couldn't run the kernel");
+    t.done();
+}
+
 } /* namespace */
 
 /* ======================================================================================== */
@@ -1211,6 +1235,8 @@ void cl_wrap_release(cl_wrap* wrap) {
     I->gb.free_channels();
     if (I->gb.pick) (void)hipFree(I->gb.pick);
     if (I->gb.done) (void)hipEventDestroy(I->gb.done);
+    I->ov.free_buffers();
+    if (I->ov.done) (void)hipEventDestroy(I->ov.done);
     I->adapt.free_all();
     if (I->tables_fence) (void)hipEventDestroy(I->tables_fence);
     for (uint32_t* q : {I->d_grid_start, I->d_grid_items, I->d_grid_box}) if (q) (void)hipFree(q);
@@ -1541,6 +1567,82 @@ int clw_ext_pick(cl_wrap* wrap, uint32_t x, uint32_t y, clw_pick* out) {
     finish(I);
     *out = h;
     return 1;
+}
+
+uint32_t clw_ext_render_overlay(cl_wrap* wrap, const clw_overlay* style, const uint32_t* sel, uint32_t count) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    if (!wt_overlay_check(style, sel, count)) return 0;
+    if (I->band_stride > 1u) return 0;
+    cl_uint kid = 0;
+    while (kid < I->kernels.size() && I->kernels[kid].kind != K_RAYTRACER) kid++;
+    if (kid >= I->kernels.size() || !is_registered(wrap, kid, 10)) return 0;
+    whitted_params P{};
+    int flags = 0;
+    size_t dyn_lds = 0;
+    if (!gbuffer_params(wrap, I, P, flags, dyn_lds)) return 0;
+    /* whole rows of one contiguous range: work-item i is pixel (i % width, i / width) of the range's own image */
+    if (P.band_stride > 1u || !P.tiled || P.rows == 0u) return 0;
+    Buffer* fb = (Buffer*)wrap->buffers[kid][10];
+    if (fb->size < (size_t)P.n_items * 4) return 0;
+    ensure_allocated(I, fb);
+    Impl::Overlay& O = I->ov;
+    if (O.n != P.n_items) {      /* another range: a pass under way may still use the old buffers */
+        if (O.n) { finish(I); if (O.done) (void)hipEventSynchronize(O.done); }
+        O.free_buffers();
+        HIP_OK(hipMalloc((void**)&O.ids, (size_t)P.n_items * 4), "Couldn't allocate device memory");
+        HIP_OK(hipMalloc((void**)&O.frame, (size_t)P.n_items * 4), "Couldn't allocate device memory");
+        O.n = P.n_items;
+    }
+    void* chan[5] = {nullptr, O.ids, nullptr, nullptr, nullptr};
+    launch_gbuffer(I, P, flags, dyn_lds, chan, true);
+    launch_overlay(I, (const uint32_t*)fb->dptr, O.ids, O.frame, P.width, P.rows, *style, sel, count, true);
+    if (!O.done) HIP_OK(hipEventCreateWithFlags(&O.done, hipEventDisableTiming), "Couldn't create a timing event");
+    HIP_OK(hipEventRecord(O.done, I->stream), "Couldn't run the kernel");
+    O.written = true;
+    return O.n;
+}
+
+uint32_t clw_ext_read_overlay(cl_wrap* wrap, void* out, uint32_t capacity_bytes) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    const Impl::Overlay& O = I->ov;
+    if (!O.written) return 0;
+    const uint64_t bytes = (uint64_t)O.n * 4;
+    if (bytes > 0xFFFFFFFFull) return 0;
+    if (out && capacity_bytes >= bytes) {
+        hipError_t e = hipEventSynchronize(O.done);
+        if (e != hipSuccess) { printf("%d\n", (int)e); die("The device kernel failed"); }
+        HIP_OK(hipMemcpy(out, O.frame, (size_t)bytes, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
+    }
+    return (uint32_t)bytes;
+}
+
+void* clw_ext_overlay_device_ptr(cl_wrap* wrap) {
+    const Impl::Overlay& O = impl_of(wrap)->ov;
+    return O.written ? O.frame : nullptr;
+}
+
+uint32_t clw_ext_unit_overlay(cl_wrap* wrap, const uint32_t* frame, const uint32_t* ids, uint32_t width, uint32_t rows, const clw_overlay* style,
+                              const uint32_t* sel, uint32_t count, uint32_t* out) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    if (!wt_overlay_check(style, sel, count) || width == 0u || rows == 0u || !frame || !ids || !out) return 0;
+    const uint64_t n = (uint64_t)width * rows;
+    if (n > 0x3FFFFFFFull) return 0;      /* (4 n bytes per buffer in 32 bits) */
+    const size_t bytes = (size_t)n * 4;
+    uint32_t *dframe = nullptr, *dids = nullptr, *dout = nullptr;
+    HIP_OK(hipMalloc((void**)&dframe, bytes), "Couldn't allocate device memory");
+    HIP_OK(hipMalloc((void**)&dids, bytes), "Couldn't allocate device memory");
+    HIP_OK(hipMalloc((void**)&dout, bytes), "Couldn't allocate device memory");
+    HIP_OK(hipMemcpy(dframe, frame, bytes, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+    HIP_OK(hipMemcpy(dids, ids, bytes, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+    HIP_OK(hipDeviceSynchronize(), "The device kernel failed");
+    launch_overlay(I, dframe, dids, dout, width, rows, *style, sel, count, false);
+    finish(I);
+    HIP_OK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
+    (void)hipFree(dframe); (void)hipFree(dids); (void)hipFree(dout);
+    return (uint32_t)n;
 }
 
 void clw_ext_set_pipeline(cl_wrap* wrap, int on) { impl_of(wrap)->pipeline = on ? 1 : 0; }

@@ -1,8 +1,9 @@
 /* whitted_launch.inc -- instantiates the kernels of whitted_trace.inc (and the primary-hit pass of whitted_gbuffer.inc, built from its
- * pieces) in namespace WT_NS and exports the C launchers the shim calls. */
+ * pieces, and the selection overlay of whitted_overlay.inc) in namespace WT_NS and exports the C launchers the shim calls. */
 namespace WT_NS {
 #include "whitted_trace.inc"
 #include "whitted_gbuffer.inc"
+#include "whitted_overlay.inc"
 }
 
 template <int FLAGS>
@@ -137,5 +138,33 @@ extern "C" hipError_t WT_LAUNCH_GBUFFER(const whitted_params* P, int flags, unsi
     if (flags & WT_F_GRID) hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, true>), g, block, 0, s, *P, G);
     else if (flags & WT_F_GEOM_LDS) hipLaunchKernelGGL((WT_NS::wt_gbuffer<true, false>), g, block, dyn_lds, s, *P, G);
     else hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, false>), g, block, 0, s, *P, G);
+    return hipGetLastError();
+}
+
+/* the selection overlay (whitted_overlay.inc) over a width x rows range: one workgroup per tile of 32 x 8 pixels, the kernel compiled for the
+ * flag word (CLW_OV_* bits, 1..7); `style` = radius, outline_rgb, fill_rgb, fill_alpha, edge_rgb; the caller has checked style and selection
+ * (csrc/overlay_host.h: wt_overlay_check) */
+#if WT_STRICT
+#define WT_LAUNCH_OVERLAY wt_strict_launch_overlay
+#else
+#define WT_LAUNCH_OVERLAY wt_fast_launch_overlay
+#endif
+extern "C" hipError_t WT_LAUNCH_OVERLAY(const unsigned* frame, const unsigned* ids, unsigned* out, unsigned width, unsigned rows, unsigned flags,
+                                        const unsigned style[5], const unsigned* sel, unsigned count, hipStream_t s) {
+    const unsigned long long tpr = (width + (WT_OV_TILE_W - 1ull)) / WT_OV_TILE_W, trows = (rows + (WT_OV_TILE_H - 1ull)) / WT_OV_TILE_H;
+    if (width == 0u || rows == 0u || width > 0x7FFFFFFFu || tpr * trows > 0x7FFFFFFFull || count > 64u || flags < 1u || flags > 7u ||
+        ((flags & WT_OV_OUTLINE) && (style[0] < 1u || style[0] > 4u)))
+        return hipErrorInvalidValue;
+    WT_NS::wt_overlay_args A = {};
+    A.frame = frame; A.ids = ids; A.out = out; A.width = width; A.rows = rows; A.tiles_per_row = (unsigned)tpr;
+    A.radius = style[0]; A.outline_rgb = style[1] & 0x00FFFFFFu; A.fill_rgb = style[2] & 0x00FFFFFFu; A.fill_alpha = style[3];
+    A.edge_rgb = style[4] & 0x00FFFFFFu; A.count = count;
+    for (unsigned k = 0; k < count; k++) A.sel[k] = sel[k];
+    const dim3 g((unsigned)(tpr * trows)), block(WT_OV_TILE_W * WT_OV_TILE_H);
+    switch (flags) {
+#define WT_OV_CASE(F) case F: hipLaunchKernelGGL(WT_NS::wt_overlay<F>, g, block, 0, s, A); break;
+        WT_OV_CASE(1) WT_OV_CASE(2) WT_OV_CASE(3) WT_OV_CASE(4) WT_OV_CASE(5) WT_OV_CASE(6) WT_OV_CASE(7)
+#undef WT_OV_CASE
+    }
     return hipGetLastError();
 }

@@ -36,6 +36,11 @@ tells how many frames the mean holds, ``reset_accumulation()`` starts again.  ``
 what the launch camera sees first at every pixel of this renderer's rows, or at one pixel of the frame.  No sampling mode above changes them,
 and they leave an accumulating view counting.
 
+``highlight(ids, ...)``: the selection overlay (clw_ext_render_overlay) -- the frame of the last ``render()`` with the objects whose ids are listed
+(``pick(x, y)["id"]``, up to 64) outlined, tinted, or both, and optionally a line along every object boundary, composed on the device from the
+frame and an id pass where they lie.  It never writes the traced frame, leaves ``gbuffer()``'s buffers and an accumulating view alone, and is
+not available with row bands.  A strip is composed on its own rows: within ``radius`` rows of its edges it can differ from the full frame's.
+
 A renderer is a context manager: ``with Renderer(...) as r:`` releases it on the way out; releasing twice is harmless.
 """
 from __future__ import annotations
@@ -207,6 +212,21 @@ class Renderer:
             return None
         return dict(id=int(p.id), kind=int(p.id) >> 30, index=int(p.id) & 0x3FFFFFFF, depth=np.float32(p.depth), point=np.array(p.point[:], np.float32),
                     normal=np.array(p.normal[:], np.float32), albedo=np.array(p.albedo[:], np.float32))
+
+    # ---- the selection overlay
+    def highlight(self, ids, *, outline: int | None = 0xFFFF00, radius: int = 2, fill: int | None = None, alpha: int = 96,
+                  edges: int | None = None) -> np.ndarray:
+        """The frame of the last ``render()`` with the objects in `ids` (an id or up to 64 of them, e.g. ``pick(x, y)["id"]``) shown as selected
+        -> uint32 [pixels].  outline: colour of a band of `radius` (1..4) pixels around them, None = none; fill: colour blended over them with
+        weight alpha / 256, None = none; edges: colour of a line along every boundary between two objects, None = none.  Colours are 0x00RRGGBB."""
+        flags = (api.OV_OUTLINE if outline is not None else 0) | (api.OV_FILL if fill is not None else 0) | (api.OV_EDGES if edges is not None else 0)
+        style = api.overlay_style(flags, radius, outline or 0, fill or 0, alpha, edges or 0)
+        if self._camera_set:
+            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        if self.w.render_overlay(style, ids) != self.pixels:
+            raise RuntimeError("the selection overlay was refused (a camera set and a frame rendered? at most 64 ids, radius in 1..4, alpha in "
+                               "0..256, something to draw, no row bands?)")
+        return self.w.read_overlay()
 
     def read_rays(self) -> np.ndarray:
         """The 64-B rray records of buffers[0][8] (materialised on demand in fused mode)."""

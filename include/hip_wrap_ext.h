@@ -279,6 +279,61 @@ int      clw_ext_pick(cl_wrap* wrap, uint32_t x, uint32_t y, clw_pick* out);
 /* The pass's launches are logged under this id in clw_ext_timing_get (a pick is not logged). */
 #define CLW_TIMING_GBUFFER 0x47425546u
 
+/* The selection overlay: shows which objects are selected -- an outline around them, a tint over them, a line along every object boundary --
+ * composed on the device from the traced frame and the ids of the primary-hit pass, both read where they lie.  Integer arithmetic only, the
+ * same in both builds; clw_host_overlay is THE definition, and the device pass (wt_overlay, csrc/whitted_overlay.inc) equals it bit for bit.
+ * For pixel p = (x, y) of a width x rows image: sel(p) is true iff ids[p] equals one of the `count` words of `sel` (any 32-bit value may be
+ * listed; CLW_ID_NONE selects the sky); pixels outside the image are absent, neither selected nor different.  In this order:
+ *   1. c = frame[p] & 0x00FFFFFF;
+ *   2. with CLW_OV_EDGES: if (x + 1 < width && ids[p] != ids[p + 1]) || (y + 1 < rows && ids[p] != ids[p + width]), c = edge_rgb & 0xFFFFFF;
+ *   3. with CLW_OV_FILL and sel(p): every 8-bit channel becomes (c_ch * (256 - a) + t_ch * a + 128) >> 8, a = fill_alpha, t = fill_rgb
+ *      (a = 0 leaves c as it is, a = 256 gives t exactly);
+ *   4. with CLW_OV_OUTLINE and !sel(p): if some present q with |qx - x| <= radius && |qy - y| <= radius has sel(q), c = outline_rgb & 0xFFFFFF
+ *      -- an OUTER band: a selected object is never covered by its own outline;
+ *   5. out[p] = c (the top byte is 0).
+ * Refused (0 returned, nothing written): unknown flag bits, flags == 0, OUTLINE with a radius outside 1..4, FILL with alpha > 256, count > 64,
+ * count > 0 with sel == NULL, a width or rows of zero (and a NULL frame, ids, style or out).  count == 0 is legal: only EDGES can then draw. */
+#define CLW_OV_OUTLINE 1u
+#define CLW_OV_FILL    2u
+#define CLW_OV_EDGES   4u
+#define CLW_OV_ALL     7u
+typedef struct clw_overlay {      /* 24 bytes */
+    uint32_t flags;               /* CLW_OV_OUTLINE | CLW_OV_FILL | CLW_OV_EDGES */
+    uint32_t radius;              /* outline width in pixels, 1..4 (read only with OUTLINE) */
+    uint32_t outline_rgb;         /* 0x00RRGGBB */
+    uint32_t fill_rgb;            /* 0x00RRGGBB */
+    uint32_t fill_alpha;          /* 0..256 (read only with FILL) */
+    uint32_t edge_rgb;            /* 0x00RRGGBB */
+} clw_overlay;
+int clw_host_overlay(const uint32_t* frame, const uint32_t* ids, uint32_t width, uint32_t rows,
+                     const clw_overlay* style, const uint32_t* sel, uint32_t count, uint32_t* out);   /* 1 = done, 0 = refused */
+/* clw_ext_render_overlay composes the overlay of the wrapper's range on its stream, without waiting: an id-only primary-hit pass over the range
+ * the next trace launch would cover (as clw_ext_render_gbuffer, into an id buffer the overlay owns), then wt_overlay over those ids and the
+ * raytracer's framebuffer argument (its argument 10) as the last launch left it, in stream order with that launch, into a packed u32 frame the
+ * wrapper owns.  Returns the number of work-items.  The traced framebuffer is never written; the buffers of clw_ext_render_gbuffer (channels,
+ * what an earlier clw_ext_read_gbuffer returned), an accumulating view, its float sum and the tile order are left alone.
+ * Returns 0 -- no launch, and the process goes on -- when the style or the selection is refused as above, no camera is latched, no scene is
+ * bound, no framebuffer is registered (or it is smaller than the range), the wrapper has row bands, or the range is not a whole number of rows.
+ * A strip (an id offset of whole rows) is composed on its OWN rows: rows of other strips are absent, so a strip's overlay can differ from the
+ * full frame's within `radius` rows of its edges (and EDGES in its last row).
+ * Buffers are allocated at first use and again when the range changes; cl_wrap_release frees them.  The id pass is logged under
+ * CLW_TIMING_GBUFFER, wt_overlay under CLW_TIMING_OVERLAY in clw_ext_timing_get.
+ * Not built: a latched mode in which cl_wrap_output hands the unchanged drivers the overlay frame instead of the traced one -- it would touch
+ * the blocking and the pipelined read-back paths. */
+uint32_t clw_ext_render_overlay(cl_wrap* wrap, const clw_overlay* style, const uint32_t* sel, uint32_t count);
+/* The overlay frame of the last clw_ext_render_overlay -> its size in bytes, 4 per work-item (0 = there is none); waits for the pass and
+ * copies it if `out` is not NULL and `capacity_bytes` suffices. */
+uint32_t clw_ext_read_overlay(cl_wrap* wrap, void* out, uint32_t capacity_bytes);
+/* Its device buffer, for consumers on the device (in the order of the wrapper's stream); NULL before the first pass.  A pass over another
+ * range frees it. */
+void*    clw_ext_overlay_device_ptr(cl_wrap* wrap);
+/* Test seam: uploads a caller's synthetic frame and ids (width x rows words each), runs the kernel instantiation and launch shape that
+ * clw_ext_render_overlay would run for this style, and reads the result back into `out`.  Returns width * rows, or 0 -- nothing launched,
+ * `out` untouched -- when refused as clw_host_overlay refuses (or width * rows does not fit 32 bits).  Waits. */
+uint32_t clw_ext_unit_overlay(cl_wrap* wrap, const uint32_t* frame, const uint32_t* ids, uint32_t width, uint32_t rows,
+                              const clw_overlay* style, const uint32_t* sel, uint32_t count, uint32_t* out);
+#define CLW_TIMING_OVERLAY 0x4F564C59u
+
 /* Work counters of the trace kernel.  enable=1 selects the counting build of the kernel
  * for subsequent launches (slower); read returns and clears
  *   out[0] path segments  out[1] shadow rays  out[2] light probes  out[3] skybox fetches
