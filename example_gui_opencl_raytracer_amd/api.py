@@ -48,6 +48,7 @@ SYMBOLS = [
     "clw_ext_render_gbuffer", "clw_ext_read_gbuffer", "clw_ext_gbuffer_device_ptr", "clw_ext_pick",
     "clw_ext_get_grid", "clw_ext_set_grid_pair",
     "clw_host_overlay", "clw_ext_render_overlay", "clw_ext_read_overlay", "clw_ext_overlay_device_ptr", "clw_ext_unit_overlay",
+    "clw_host_object_stats", "clw_host_merge_object_stats", "clw_ext_object_stats", "clw_ext_unit_object_stats",
 ]
 
 # the channels of the primary-hit pass (hip_wrap_ext.h: CLW_GB_*), the id of a miss and the pass's id in the timing log
@@ -61,6 +62,11 @@ GB_CHANNELS = {"depth": (GB_DEPTH, np.float32, 1), "id": (GB_ID, np.uint32, 1), 
 # the selection overlay (hip_wrap_ext.h: CLW_OV_*): what a style draws, and the pass's id in the timing log
 OV_OUTLINE, OV_FILL, OV_EDGES, OV_ALL = 1, 2, 4, 7
 TIMING_OVERLAY = 0x4F564C59
+
+# the visible-object table (hip_wrap_ext.h: clw_object_stat): a record as a numpy dtype, and the pass's id in the timing log
+OBJECT_STAT = np.dtype([("id", np.uint32), ("pixels", np.uint32), ("x0", np.uint32), ("y0", np.uint32), ("x1", np.uint32), ("y1", np.uint32),
+                        ("depth_min", np.float32), ("depth_max", np.float32), ("sum_x", np.uint64), ("sum_y", np.uint64)])
+TIMING_OBJECTS = 0x4F424A53
 
 
 def id_kind(ids):
@@ -118,6 +124,22 @@ class clw_overlay(C.Structure):
     """The style of a selection overlay (24 bytes): what to draw (OV_* bits), the outline's width and the three colours, 0x00RRGGBB."""
     _fields_ = [("flags", C.c_uint32), ("radius", C.c_uint32), ("outline_rgb", C.c_uint32), ("fill_rgb", C.c_uint32), ("fill_alpha", C.c_uint32),
                 ("edge_rgb", C.c_uint32)]
+
+
+class clw_rect(C.Structure):
+    """A rectangle in frame pixels (16 bytes)."""
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class clw_object_stat(C.Structure):
+    """One record of the visible-object table (48 bytes): an element of an OBJECT_STAT array."""
+    _fields_ = [("id", C.c_uint32), ("pixels", C.c_uint32), ("x0", C.c_uint32), ("y0", C.c_uint32), ("x1", C.c_uint32), ("y1", C.c_uint32),
+                ("depth_min", C.c_float), ("depth_max", C.c_float), ("sum_x", C.c_uint64), ("sum_y", C.c_uint64)]
+
+
+class clw_object_summary(C.Structure):
+    """What comes with a visible-object table (16 bytes): records, pixels inside the rectangle, pixels whose id is not known."""
+    _fields_ = [("objects", C.c_uint32), ("pixels", C.c_uint32), ("foreign", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class clw_grid_info(C.Structure):
@@ -235,6 +257,16 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         L.clw_ext_overlay_device_ptr.restype = vp
         L.clw_ext_unit_overlay.argtypes = [W, vp, vp, u32, u32, OV, vp, u32, vp]
         L.clw_ext_unit_overlay.restype = u32
+    if hasattr(L, "clw_ext_object_stats") or not os.environ.get("CLWRAP_LIB"):            # (an older A/B build may lack them)
+        RC, SM = C.POINTER(clw_rect), C.POINTER(clw_object_summary)
+        L.clw_host_object_stats.argtypes = [vp, vp, u32, u32, u32, RC, vp, vp, u32, SM]
+        L.clw_host_object_stats.restype = C.c_int
+        L.clw_host_merge_object_stats.argtypes = [vp, u32, vp, u32, vp, u32]
+        L.clw_host_merge_object_stats.restype = u32
+        L.clw_ext_object_stats.argtypes = [W, RC, vp, u32, SM]
+        L.clw_ext_object_stats.restype = C.c_int
+        L.clw_ext_unit_object_stats.argtypes = [W, vp, vp, u32, u32, u32, RC, vp, vp, u32, SM]
+        L.clw_ext_unit_object_stats.restype = C.c_int
     L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
     L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
     L.clw_ext_read_tile_costs.restype = u32
@@ -356,6 +388,63 @@ def overlay(frame, ids, width: int, rows: int, style: clw_overlay, sel) -> np.nd
     if not load_library().clw_host_overlay(_ptr(frame), _ptr(ids), width, rows, C.byref(style), _ptr(sel) if sel.size else None, sel.size, _ptr(out)):
         raise ValueError("clw_host_overlay rejects this style or selection (flags in 1..7, radius in 1..4, alpha in 0..256, at most 64 ids)")
     return out
+
+
+def _rect(rect):
+    """None (the whole frame), a clw_rect or (x, y, width, height) -> what ctypes passes for a `const clw_rect*`"""
+    if rect is None:
+        return None
+    if not isinstance(rect, clw_rect):
+        rect = clw_rect(*(int(v) for v in rect))
+    return C.byref(rect)
+
+
+def _summary(s: clw_object_summary) -> dict:
+    return dict(objects=int(s.objects), pixels=int(s.pixels), foreign=int(s.foreign))
+
+
+def _object_table(call, first_capacity: int = 16384):
+    """`call(out pointer, capacity, summary pointer)` -> (records, summary dict), or None when it is refused: once with room for
+    `first_capacity` records (generous: a second device pass costs more than 768 KB of host memory), and once more with room for all of them
+    when there are more"""
+    s = clw_object_summary()
+    out = np.zeros(first_capacity, OBJECT_STAT)
+    if not call(_ptr(out), out.size, C.byref(s)):
+        return None
+    if s.objects > out.size:
+        out = np.zeros(s.objects, OBJECT_STAT)
+        if not call(_ptr(out), out.size, C.byref(s)):
+            return None
+    return out[:min(s.objects, out.size)].copy(), _summary(s)
+
+
+def object_stats(ids, depth, width: int, rows: int, counts, first_row: int = 0, rect=None):
+    """clw_host_object_stats: the visible-object table of a width x rows range of an id channel (and its depth channel, or None) whose first row
+    is row `first_row` of the frame, on the host -- THE definition the device pass is held to -> (OBJECT_STAT [objects], {"objects", "pixels",
+    "foreign"}).  counts = (spheres, planes, lights); rect = (x, y, width, height) in frame pixels, None = the whole frame."""
+    ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+    width, rows = int(width), int(rows)
+    if width <= 0 or rows <= 0 or ids.size != width * rows:
+        raise ValueError("clw_host_object_stats rejects these arguments (an id channel of width * rows words)")
+    if depth is not None:
+        depth = np.ascontiguousarray(depth, np.float32).reshape(-1)
+        if depth.size != ids.size:
+            raise ValueError("clw_host_object_stats rejects these arguments (a depth channel of width * rows words)")
+    counts = np.ascontiguousarray(counts, np.uint32).reshape(3)
+    L = load_library()
+    got = _object_table(lambda out, cap, s: L.clw_host_object_stats(_ptr(ids), _ptr(depth), width, rows, int(first_row), _rect(rect), _ptr(counts),
+                                                                    out, cap, s))
+    if got is None:
+        raise ValueError("clw_host_object_stats rejects these arguments (an empty rectangle, more than 2^24 - 1 primitives, 2^30 pixels or more)")
+    return got
+
+
+def merge_object_stats(a, b) -> np.ndarray:
+    """clw_host_merge_object_stats: two tables sorted by id -> the table of both (the tables of two strips of a frame -> the frame's)."""
+    a, b = np.ascontiguousarray(a, OBJECT_STAT).reshape(-1), np.ascontiguousarray(b, OBJECT_STAT).reshape(-1)
+    out = np.zeros(a.size + b.size or 1, OBJECT_STAT)
+    n = load_library().clw_host_merge_object_stats(_ptr(a), a.size, _ptr(b), b.size, _ptr(out), out.size)
+    return out[:n].copy()
 
 
 def frame_seed(f: int) -> int:
@@ -605,6 +694,24 @@ class ClWrap:
         n = self.L.clw_ext_unit_overlay(C.byref(self.w), _ptr(frame), _ptr(ids), int(width), int(rows), C.byref(style),
                                         _ptr(sel) if sel.size else None, sel.size, _ptr(out))
         return out if n == frame.size and n else None
+
+    def object_stats(self, rect=None):
+        """clw_ext_object_stats: the visible-object table of the wrapper's range, reduced on the device -> (OBJECT_STAT [objects], {"objects",
+        "pixels", "foreign"}), or None when it is refused (nothing launched).  rect = (x, y, width, height) in frame pixels, None = the whole frame."""
+        return _object_table(lambda out, cap, s: self.L.clw_ext_object_stats(C.byref(self.w), _rect(rect), out, cap, s))
+
+    def unit_object_stats(self, ids, depth, width: int, rows: int, counts, first_row: int = 0, rect=None):
+        """clw_ext_unit_object_stats: the device pass on a synthetic id channel (and depth channel, or None) -> (records, summary), or None when
+        it is refused."""
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        assert ids.size == int(width) * int(rows)
+        if depth is not None:
+            depth = np.ascontiguousarray(depth, np.float32).reshape(-1)
+            assert depth.size == ids.size
+        counts = np.ascontiguousarray(counts, np.uint32).reshape(3)
+        return _object_table(lambda out, cap, s: self.L.clw_ext_unit_object_stats(C.byref(self.w), _ptr(ids), _ptr(depth), int(width), int(rows), int(first_row),
+                                                                                  _rect(rect), _ptr(counts), out, cap, s),
+                             first_capacity=max(1024, min(ids.size, int(counts.astype(np.uint64).sum()) + 1)))
 
     def set_adaptive(self, threshold): self.L.clw_ext_set_adaptive(C.byref(self.w), int(threshold))
     def get_adaptive(self): return int(self.L.clw_ext_get_adaptive(C.byref(self.w)))

@@ -25,6 +25,7 @@
 
 #include "../../include/hip_wrap_ext.h"
 #include "launch_plan.h"
+#include "objects_host.h"
 #include "overlay_host.h"
 #include "png_codec.h"
 #include "scene_prep.h"
@@ -42,6 +43,8 @@ extern "C" hipError_t wt_fast_launch_gbuffer(const whitted_params*, int, unsigne
 extern "C" hipError_t wt_strict_launch_gbuffer(const whitted_params*, int, unsigned, size_t, float*, unsigned*, float*, float*, float*, hipStream_t);
 extern "C" hipError_t wt_fast_launch_overlay(const unsigned*, const unsigned*, unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, unsigned, hipStream_t);
 extern "C" hipError_t wt_strict_launch_overlay(const unsigned*, const unsigned*, unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, unsigned, hipStream_t);
+extern "C" hipError_t wt_fast_launch_objects(const unsigned*, const unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, void*, void*, hipStream_t);
+extern "C" hipError_t wt_strict_launch_objects(const unsigned*, const unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, void*, void*, hipStream_t);
 extern "C" hipError_t wt_fast_launch_cams(const wt_cam_table*, float*, hipStream_t);
 extern "C" hipError_t wt_fast_launch_classify(const unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned char*, unsigned*, unsigned*, unsigned, hipStream_t);
 extern "C" hipError_t wt_fast_launch_sched(const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
@@ -209,6 +212,38 @@ struct Impl {
         hipEvent_t done = nullptr;
         void free_buffers() { if (ids) (void)hipFree(ids); if (frame) (void)hipFree(frame); ids = frame = nullptr; n = 0; written = false; }
     } ov;
+    /* the visible-object table (clw_ext_object_stats; whitted_objects.inc): its own id and depth buffers -- the primary-hit pass writes them, `gb`
+     * and `ov` are not touched -- sized for the pass's range, and the slot table (16 bytes of counters + 48 per slot) and the result (the 16-byte
+     * summary + room for a 48-byte record per slot), sized for the scene's counts.  Every call waits for its own work, so nothing is ever in flight
+     * on these buffers between calls. */
+    struct Objects {
+        uint32_t* ids = nullptr; float* depth = nullptr;
+        uint32_t n = 0;                 /* work-items ids and depth are sized for */
+        void* table = nullptr; void* result = nullptr;
+        uint32_t slots = 0;             /* slots table and result are sized for */
+        void size_range(uint32_t items) {
+            if (n == items) return;
+            if (ids) (void)hipFree(ids);
+            if (depth) (void)hipFree(depth);
+            ids = nullptr; depth = nullptr; n = 0;
+            HIP_OK(hipMalloc((void**)&ids, (size_t)items * 4), "Couldn't allocate device memory");
+            HIP_OK(hipMalloc((void**)&depth, (size_t)items * 4), "Couldn't allocate device memory");
+            n = items;
+        }
+        void size_table(uint32_t count) {
+            if (slots == count) return;
+            if (table) (void)hipFree(table);
+            if (result) (void)hipFree(result);
+            table = result = nullptr; slots = 0;
+            HIP_OK(hipMalloc(&table, 16 + (size_t)count * sizeof(clw_object_stat)), "Couldn't allocate device memory");
+            HIP_OK(hipMalloc(&result, sizeof(clw_object_summary) + (size_t)count * sizeof(clw_object_stat)), "Couldn't allocate device memory");
+            slots = count;
+        }
+        void free_buffers() {
+            for (void* q : {(void*)ids, (void*)depth, table, result}) if (q) (void)hipFree(q);
+            ids = nullptr; depth = nullptr; table = result = nullptr; n = 0; slots = 0;
+        }
+    } obj;
     /* prepared scene cache */
     const Buffer *prep_s = nullptr, *prep_p = nullptr, *prep_l = nullptr;
     uint32_t prep_ns = 0, prep_np = 0, prep_nl = 0;
@@ -1021,6 +1056,37 @@ void launch_overlay(Impl* I, const uint32_t* frame, const uint32_t* ids, uint32_
     t.done();
 }
 
+/* ---- the visible-object table ---------------------------------------------------------------------------------------------------- */
+/* The clear of the slot table, wt_objects_reduce and wt_objects_compact over device channels of a width x rows range on the launch stream, then
+ * the read-back of the summary and of min(objects, capacity) records; waits.  The caller has checked the arguments (wt_objects_check).  The
+ * kernels are integer work compiled into both units; the build in use launches its own copy. */
+void run_objects(Impl* I, const uint32_t* ids, const float* depth, uint32_t width, uint32_t rows, uint32_t first_row, const clw_rect* rect,
+                 const uint32_t counts[3], clw_object_stat* out, uint32_t capacity, clw_object_summary* summary, bool timed) {
+    static_assert(sizeof(clw_object_stat) == 48 && sizeof(clw_object_summary) == 16 && sizeof(clw_rect) == 16, "the table's ABI");
+    uint32_t clip[4];
+    (void)wt_objects_clip(width, rows, first_row, rect, clip);      /* a rectangle that misses the range: clip = 0 -> nothing reduced, an empty table */
+    Impl::Objects& O = I->obj;
+    O.size_table(counts[0] + counts[1] + counts[2] + 1u);
+    {
+        LaunchTimer t(I, CLW_TIMING_OBJECTS, timed);
+        hipError_t e = (I->strict ? wt_strict_launch_objects : wt_fast_launch_objects)(ids, (const unsigned*)depth, width, rows, first_row, clip, counts,
+                                                                                       O.table, O.result, I->stream);
+        if (e != hipSuccess) die("Couldn't run the kernel");
+        t.done();
+    }
+    clw_object_summary h;
+    if (hipMemcpyAsync(&h, O.result, sizeof h, hipMemcpyDeviceToHost, I->stream) != hipSuccess) die("Failed to transfer device memory to host");
+    finish(I);
+    const uint32_t n = !out ? 0u : h.objects < capacity ? h.objects : capacity;
+    if (n) {
+        if (n > O.slots) die("The device kernel failed");      /* (more records than slots cannot be) */
+        if (hipMemcpyAsync(out, (const uint8_t*)O.result + sizeof h, (size_t)n * sizeof(clw_object_stat), hipMemcpyDeviceToHost, I->stream) != hipSuccess)
+            die("Failed to transfer device memory to host");
+        finish(I);
+    }
+    *summary = h;
+}
+
 } /* namespace */
 
 /* ======================================================================================== */
@@ -1237,6 +1303,7 @@ void cl_wrap_release(cl_wrap* wrap) {
     if (I->gb.done) (void)hipEventDestroy(I->gb.done);
     I->ov.free_buffers();
     if (I->ov.done) (void)hipEventDestroy(I->ov.done);
+    I->obj.free_buffers();
     I->adapt.free_all();
     if (I->tables_fence) (void)hipEventDestroy(I->tables_fence);
     for (uint32_t* q : {I->d_grid_start, I->d_grid_items, I->d_grid_box}) if (q) (void)hipFree(q);
@@ -1643,6 +1710,47 @@ uint32_t clw_ext_unit_overlay(cl_wrap* wrap, const uint32_t* frame, const uint32
     HIP_OK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
     (void)hipFree(dframe); (void)hipFree(dids); (void)hipFree(dout);
     return (uint32_t)n;
+}
+
+int clw_ext_object_stats(cl_wrap* wrap, const clw_rect* rect, clw_object_stat* out, uint32_t capacity, clw_object_summary* summary) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    if (!summary || I->band_stride > 1u) return 0;
+    whitted_params P{};
+    int flags = 0;
+    size_t dyn_lds = 0;
+    if (!gbuffer_params(wrap, I, P, flags, dyn_lds)) return 0;
+    /* whole rows of one contiguous range: work-item i is pixel (i % width, row_offset + i / width) of the frame */
+    if (P.band_stride > 1u || !P.tiled || P.rows == 0u) return 0;
+    const uint32_t counts[3] = {P.ns, P.np, P.nl};
+    Impl::Objects& O = I->obj;
+    if (!wt_objects_check(&O, P.width, P.rows, P.row_offset, rect, counts, summary)) return 0;      /* (the ids are the pass's own: any non-NULL pointer) */
+    O.size_range(P.n_items);
+    void* chan[5] = {O.depth, O.ids, nullptr, nullptr, nullptr};
+    launch_gbuffer(I, P, flags, dyn_lds, chan, true);
+    run_objects(I, O.ids, O.depth, P.width, P.rows, P.row_offset, rect, counts, out, capacity, summary, true);
+    return 1;
+}
+
+int clw_ext_unit_object_stats(cl_wrap* wrap, const uint32_t* ids, const float* depth, uint32_t width, uint32_t rows, uint32_t first_row,
+                              const clw_rect* rect, const uint32_t counts[3], clw_object_stat* out, uint32_t capacity, clw_object_summary* summary) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    if (!wt_objects_check(ids, width, rows, first_row, rect, counts, summary)) return 0;
+    const size_t bytes = (size_t)width * rows * 4;      /* (width * rows fits 30 bits) */
+    uint32_t* dids = nullptr;
+    float* ddepth = nullptr;
+    HIP_OK(hipMalloc((void**)&dids, bytes), "Couldn't allocate device memory");
+    HIP_OK(hipMemcpy(dids, ids, bytes, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+    if (depth) {
+        HIP_OK(hipMalloc((void**)&ddepth, bytes), "Couldn't allocate device memory");
+        HIP_OK(hipMemcpy(ddepth, depth, bytes, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+    }
+    HIP_OK(hipDeviceSynchronize(), "The device kernel failed");
+    run_objects(I, dids, ddepth, width, rows, first_row, rect, counts, out, capacity, summary, false);
+    (void)hipFree(dids);
+    if (ddepth) (void)hipFree(ddepth);
+    return 1;
 }
 
 void clw_ext_set_pipeline(cl_wrap* wrap, int on) { impl_of(wrap)->pipeline = on ? 1 : 0; }

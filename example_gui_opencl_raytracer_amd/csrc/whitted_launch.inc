@@ -1,9 +1,11 @@
 /* whitted_launch.inc -- instantiates the kernels of whitted_trace.inc (and the primary-hit pass of whitted_gbuffer.inc, built from its
- * pieces, and the selection overlay of whitted_overlay.inc) in namespace WT_NS and exports the C launchers the shim calls. */
+ * pieces, the selection overlay of whitted_overlay.inc and the visible-object table of whitted_objects.inc) in namespace WT_NS and exports
+ * the C launchers the shim calls. */
 namespace WT_NS {
 #include "whitted_trace.inc"
 #include "whitted_gbuffer.inc"
 #include "whitted_overlay.inc"
+#include "whitted_objects.inc"
 }
 
 template <int FLAGS>
@@ -166,5 +168,46 @@ extern "C" hipError_t WT_LAUNCH_OVERLAY(const unsigned* frame, const unsigned* i
         WT_OV_CASE(1) WT_OV_CASE(2) WT_OV_CASE(3) WT_OV_CASE(4) WT_OV_CASE(5) WT_OV_CASE(6) WT_OV_CASE(7)
 #undef WT_OV_CASE
     }
+    return hipGetLastError();
+}
+
+/* the visible-object table (whitted_objects.inc) of a width x rows range whose first row is row `first_row` of the frame: clears `table` (16
+ * bytes of counters, then a 48-byte slot per possible id: counts[0] + counts[1] + counts[2] + 1 of them), reduces the pixels of the clipped
+ * rectangle `clip` = {first column, first row of the range, columns, rows} (columns 0 = it misses the range: nothing to reduce) into it, in
+ * tiles of 32 x 8 pixels dealt to at most WT_OBJ_MAX_GROUPS workgroups, and compacts the occupied slots into `result` (the 16-byte summary, then the records, room for one
+ * per slot).  `depth` = the depth channel's bit patterns, or null.  The caller has checked the arguments (csrc/objects_host.h:
+ * wt_objects_check, wt_objects_clip) */
+#if WT_STRICT
+#define WT_LAUNCH_OBJECTS wt_strict_launch_objects
+#else
+#define WT_LAUNCH_OBJECTS wt_fast_launch_objects
+#endif
+extern "C" hipError_t WT_LAUNCH_OBJECTS(const unsigned* ids, const unsigned* depth, unsigned width, unsigned rows, unsigned first_row,
+                                        const unsigned clip[4], const unsigned counts[3], void* table, void* result, hipStream_t s) {
+    const unsigned long long nslots = (unsigned long long)counts[0] + counts[1] + counts[2] + 1ull;
+    const unsigned long long tpr = (clip[2] + (WT_OBJ_TILE_W - 1ull)) / WT_OBJ_TILE_W, trows = (clip[3] + (WT_OBJ_TILE_H - 1ull)) / WT_OBJ_TILE_H;
+    if (width == 0u || rows == 0u || (unsigned long long)width * rows >= (1ull << 30) || nslots > (1ull << 24) || !ids || !table || !result ||
+        (unsigned long long)clip[0] + clip[2] > width || (unsigned long long)clip[1] + clip[3] > rows || (unsigned long long)first_row + rows > (1ull << 32))
+        return hipErrorInvalidValue;
+    WT_NS::wt_obj_head* head = (WT_NS::wt_obj_head*)table;
+    WT_NS::wt_obj_slot* slots = (WT_NS::wt_obj_slot*)(head + 1);
+    hipError_t e = hipMemsetAsync(table, 0, sizeof(WT_NS::wt_obj_head) + (size_t)nslots * sizeof(WT_NS::wt_obj_slot), s);
+    if (e != hipSuccess) return e;
+    if (clip[2] != 0u && clip[3] != 0u) {
+        WT_NS::wt_objects_args A = {};
+        A.ids = ids; A.depth = depth; A.head = head; A.slots = slots; A.width = width; A.first_row = first_row;
+        A.cx = clip[0]; A.cy = clip[1]; A.cw = clip[2]; A.ch = clip[3]; A.tiles_per_row = (unsigned)tpr;
+        A.c0 = counts[0]; A.c1 = counts[1]; A.c2 = counts[2];
+        /* at most WT_OBJ_MAX_GROUPS workgroups, each a run of consecutive tiles (tiles <= pixels < 2^30) */
+        const unsigned tiles = (unsigned)(tpr * trows), wanted = tiles < WT_OBJ_MAX_GROUPS ? tiles : WT_OBJ_MAX_GROUPS;
+        A.tiles = tiles; A.tiles_per_group = (tiles + wanted - 1u) / wanted;
+        const unsigned groups = (tiles + A.tiles_per_group - 1u) / A.tiles_per_group;
+        hipLaunchKernelGGL(WT_NS::wt_objects_reduce, dim3(groups), dim3(WT_OBJ_TILE_W * WT_OBJ_TILE_H), 0, s, A);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    unsigned* summary = (unsigned*)result;
+    hipLaunchKernelGGL(WT_NS::wt_objects_compact, dim3(1), dim3(WT_OBJ_CHUNK), 0, s, head, slots, (unsigned)nslots, counts[0], counts[1], counts[2],
+                       depth ? 1u : 0u, summary, (WT_NS::wt_obj_record*)(summary + 4));
     return hipGetLastError();
 }

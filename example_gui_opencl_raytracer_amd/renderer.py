@@ -228,6 +228,29 @@ class Renderer:
                                "0..256, something to draw, no row bands?)")
         return self.w.read_overlay()
 
+    # ---- the visible-object table
+    def objects(self, rect=None) -> np.ndarray:
+        """Which objects show inside `rect` = (x, y, width, height) in frame pixels (None = the whole frame) on this renderer's rows, through the
+        camera set last -> api.OBJECT_STAT [objects], sorted by id: id, pixels, the inclusive bounding box x0, y0, x1, y1 in frame coordinates,
+        depth_min, depth_max, and sum_x, sum_y (centroid = sum / pixels).  Reduced on the device: only the records travel."""
+        if self._camera_set:
+            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        got = self.w.object_stats(rect)
+        if got is None:
+            raise RuntimeError("the visible-object table was refused (a camera set? a rectangle of at least one pixel? no row bands?)")
+        return got[0]
+
+    def select_rect(self, x0: int, y0: int, x1: int, y1: int, *, min_pixels: int = 1, kinds=(api.ID_SPHERE, api.ID_PLANE)) -> np.ndarray:
+        """Rubber-band selection: the ids of the objects of `kinds` that show at least `min_pixels` pixels inside the inclusive rectangle
+        (x0, y0) .. (x1, y1) of the frame (the corners in either order) -> uint32 [<= 64], largest first, ties by id: what ``highlight`` takes."""
+        xa, xb, ya, yb = min(int(x0), int(x1)), max(int(x0), int(x1)), min(int(y0), int(y1)), max(int(y0), int(y1))
+        if xa < 0 or ya < 0:
+            raise RuntimeError("the visible-object table was refused (a rectangle with a negative corner)")
+        t = self.objects((xa, ya, xb - xa + 1, yb - ya + 1))
+        t = t[np.isin(api.id_kind(t["id"]), np.asarray(kinds, np.uint32).reshape(-1)) & (t["id"] != api.ID_NONE) & (t["pixels"] >= min_pixels)]
+        order = np.lexsort((t["id"], -t["pixels"].astype(np.int64)))
+        return np.ascontiguousarray(t["id"][order][:64], np.uint32)
+
     def read_rays(self) -> np.ndarray:
         """The 64-B rray records of buffers[0][8] (materialised on demand in fused mode)."""
         rays = np.empty((self.pixels, 16), np.float32)

@@ -334,6 +334,63 @@ uint32_t clw_ext_unit_overlay(cl_wrap* wrap, const uint32_t* frame, const uint32
                               const clw_overlay* style, const uint32_t* sel, uint32_t count, uint32_t* out);
 #define CLW_TIMING_OVERLAY 0x4F564C59u
 
+/* The visible-object table: which objects show inside a rectangle of the view, each with its pixel count, screen bounding box, depth range and
+ * the sums its centroid comes from -- what rubber-band selection, placing a label or a gizmo, zooming or focusing on an object and a
+ * visibility list need -- reduced on the device from the id and depth channels of the primary-hit pass, read where they lie: a few 48-byte
+ * records travel to the host, not the channels.  Integer work only (comparisons, counts, minima, maxima, integer sums), the same in both
+ * builds; clw_host_object_stats is THE definition, and the device pass (wt_objects_reduce, wt_objects_compact: csrc/whitted_objects.inc)
+ * equals it bit for bit.
+ * Take a range of whole rows -- width x rows pixels, its first row being row `first_row` of the frame --, its id channel (CLW_GB_ID words),
+ * optionally its depth channel, and a rectangle in FRAME pixels (NULL = the whole frame), clipped in 64-bit arithmetic to the columns of the
+ * frame and the rows of the range.  counts[3] = (spheres, planes, lights); an id is KNOWN if its kind is 0..2 and its index below that kind's
+ * count, or if it is CLW_ID_NONE.  The table has one record per distinct known id among the pixels of the range inside the rectangle, sorted
+ * by id ascending as uint32: spheres, then planes, then lights, CLW_ID_NONE last.  A pixel whose id is not known enters no record and is
+ * counted in summary.foreign (the primary-hit pass writes no such id).  summary.pixels = the pixels of the range inside the rectangle, foreign
+ * ones included; summary.objects = the number of records, whatever `capacity` is: the first min(objects, capacity) are written (out == NULL
+ * counts as capacity 0).  Depth extremes are defined on BIT PATTERNS read as uint32, so a NaN needs no rule; for the pass's own depths (t > 0,
+ * +inf for the sky) that is the order of the values.
+ * Refused (0 returned, nothing written): a NULL ids, counts or summary, a width or rows of zero, a rectangle of zero width or height,
+ * counts[0] + counts[1] + counts[2] + 1 > 1 << 24, width * rows not fitting 30 bits (and first_row + rows > 2^32: y would not fit).  A
+ * rectangle that misses the range is NOT refused: objects = pixels = 0. */
+typedef struct clw_rect { uint32_t x, y, width, height; } clw_rect;                 /* 16 bytes, frame pixels */
+typedef struct clw_object_stat {                                                     /* 48 bytes */
+    uint32_t id;                 /* as CLW_GB_ID */
+    uint32_t pixels;             /* pixels of the rectangle that show it */
+    uint32_t x0, y0, x1, y1;     /* inclusive bounding box of those pixels, FRAME coordinates */
+    float    depth_min, depth_max;   /* the two depths whose bit patterns, read as uint32, are smallest / largest; 0, 0 without a depth channel */
+    uint64_t sum_x, sum_y;       /* sums of the frame coordinates of those pixels: centroid = sum / pixels */
+} clw_object_stat;
+typedef struct clw_object_summary { uint32_t objects, pixels, foreign, reserved; } clw_object_summary;   /* 16 bytes */
+int clw_host_object_stats(const uint32_t* ids, const float* depth /* or NULL */, uint32_t width, uint32_t rows, uint32_t first_row,
+                          const clw_rect* rect, const uint32_t counts[3], clw_object_stat* out, uint32_t capacity,
+                          clw_object_summary* summary);                                                   /* 1 = done, 0 = refused */
+/* Two tables sorted by id -> the table of both, sorted: an object in both has its pixels and sums added, its boxes united, its depth extremes
+ * combined by bit pattern.  Returns the merged count and writes the first min(count, capacity) records (`out` may be neither input).  The
+ * tables of two strips of a frame, merged, are the frame's table exactly: boxes and sums are in frame coordinates. */
+uint32_t clw_host_merge_object_stats(const clw_object_stat* a, uint32_t na, const clw_object_stat* b, uint32_t nb, clw_object_stat* out,
+                                     uint32_t capacity);
+/* clw_ext_object_stats builds the table of the wrapper's range on its stream and WAITS for it (as clw_ext_pick): an id + depth primary-hit
+ * pass over the range the next trace launch would cover (as clw_ext_render_gbuffer, into two buffers the table owns), a clear of the slot
+ * table, wt_objects_reduce and wt_objects_compact -- first_row and counts being the launch's own -- then a read-back of the 16-byte summary
+ * and of min(objects, capacity) records.  Returns 1.  The slot table is direct-indexed, one 48-byte slot per possible id, so a scene of n
+ * primitives costs 96 (n + 1) bytes of device memory from the first call on.
+ * Returns 0 -- no launch, `out` and `summary` untouched, and the process goes on -- when the arguments are refused as above, no camera is
+ * latched, no scene is bound, the wrapper has row bands, or the range is not a whole number of rows.
+ * The traced framebuffer, the buffers of clw_ext_render_gbuffer and of the overlay, an accumulating view, its count and the tile order are
+ * left alone.  A strip (an id offset of whole rows) gives the table of its OWN rows in frame coordinates: merge the strips' tables.
+ * Buffers are allocated at first use and again when the range or the counts change; cl_wrap_release frees them.  The id pass is logged under
+ * CLW_TIMING_GBUFFER; the clear and the two kernels, as one entry, under CLW_TIMING_OBJECTS in clw_ext_timing_get.
+ * Not built: a latched mode in which every trace launch is followed by its table, and with it a per-frame automatic table a driver could
+ * poll -- each call is one explicit pass; nor a device-resident result for consumers on the device. */
+int clw_ext_object_stats(cl_wrap* wrap, const clw_rect* rect, clw_object_stat* out, uint32_t capacity, clw_object_summary* summary);
+/* Test seam: uploads a caller's synthetic id field (and depth field, or NULL), runs the clear, the two kernels and the read-back that
+ * clw_ext_object_stats would run for them, with the caller's first_row and counts.  Returns 1, or 0 -- nothing launched, `out` and `summary`
+ * untouched -- when refused as clw_host_object_stats refuses.  Waits. */
+int clw_ext_unit_object_stats(cl_wrap* wrap, const uint32_t* ids, const float* depth, uint32_t width, uint32_t rows, uint32_t first_row,
+                              const clw_rect* rect, const uint32_t counts[3], clw_object_stat* out, uint32_t capacity,
+                              clw_object_summary* summary);
+#define CLW_TIMING_OBJECTS 0x4F424A53u
+
 /* Work counters of the trace kernel.  enable=1 selects the counting build of the kernel
  * for subsequent launches (slower); read returns and clears
  *   out[0] path segments  out[1] shadow rays  out[2] light probes  out[3] skybox fetches
