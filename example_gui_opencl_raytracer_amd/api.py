@@ -49,6 +49,8 @@ SYMBOLS = [
     "clw_ext_get_grid", "clw_ext_set_grid_pair",
     "clw_host_overlay", "clw_ext_render_overlay", "clw_ext_read_overlay", "clw_ext_overlay_device_ptr", "clw_ext_unit_overlay",
     "clw_host_object_stats", "clw_host_merge_object_stats", "clw_ext_object_stats", "clw_ext_unit_object_stats",
+    "clw_host_projection_rays", "clw_host_projection_tables", "clw_host_ortho_camera",
+    "clw_ext_set_projection", "clw_ext_get_projection", "clw_ext_unit_projection",
 ]
 
 # the channels of the primary-hit pass (hip_wrap_ext.h: CLW_GB_*), the id of a miss and the pass's id in the timing log
@@ -67,6 +69,10 @@ TIMING_OVERLAY = 0x4F564C59
 OBJECT_STAT = np.dtype([("id", np.uint32), ("pixels", np.uint32), ("x0", np.uint32), ("y0", np.uint32), ("x1", np.uint32), ("y1", np.uint32),
                         ("depth_min", np.float32), ("depth_max", np.float32), ("sum_x", np.uint64), ("sum_y", np.uint64)])
 TIMING_OBJECTS = 0x4F424A53
+
+# the camera models (hip_wrap_ext.h: CLW_PROJ_*)
+PROJ_PERSPECTIVE, PROJ_ORTHO, PROJ_EQUIRECT = 0, 1, 2
+PROJ_MODELS = {"perspective": PROJ_PERSPECTIVE, "ortho": PROJ_ORTHO, "equirect": PROJ_EQUIRECT}
 
 
 def id_kind(ids):
@@ -140,6 +146,13 @@ class clw_object_stat(C.Structure):
 class clw_object_summary(C.Structure):
     """What comes with a visible-object table (16 bytes): records, pixels inside the rectangle, pixels whose id is not known."""
     _fields_ = [("objects", C.c_uint32), ("pixels", C.c_uint32), ("foreign", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class clw_projection(C.Structure):
+    """A camera model beside the pinhole (32 bytes): PROJ_ORTHO or PROJ_EQUIRECT, the view axis (all zero = the camera's own centre direction),
+    the world width an orthographic frame spans (0 = the camera's image plane as it stands), the degrees a panorama covers (0 = 360 / 180)."""
+    _fields_ = [("model", C.c_uint32), ("axis", C.c_float * 3), ("ortho_width", C.c_float), ("h_span", C.c_float), ("v_span", C.c_float),
+                ("reserved", C.c_uint32)]
 
 
 class clw_grid_info(C.Structure):
@@ -267,6 +280,18 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         L.clw_ext_object_stats.restype = C.c_int
         L.clw_ext_unit_object_stats.argtypes = [W, vp, vp, u32, u32, u32, RC, vp, vp, u32, SM]
         L.clw_ext_unit_object_stats.restype = C.c_int
+    if hasattr(L, "clw_ext_set_projection") or not os.environ.get("CLWRAP_LIB"):          # (an older A/B build may lack them)
+        CM, PR = C.POINTER(clw_camera), C.POINTER(clw_projection)
+        L.clw_host_projection_rays.argtypes = [CM, PR, C.c_uint64, C.c_uint64, vp]
+        L.clw_host_projection_rays.restype = C.c_int
+        L.clw_host_projection_tables.argtypes = [CM, PR, vp, vp]
+        L.clw_host_projection_tables.restype = C.c_int
+        L.clw_host_ortho_camera.argtypes = [C.c_float * 3, C.c_float * 3, C.c_float, u32, u32, CM, PR]
+        L.clw_host_ortho_camera.restype = C.c_int
+        L.clw_ext_set_projection.argtypes = [W, PR]
+        L.clw_ext_get_projection.argtypes = [W, PR]
+        L.clw_ext_unit_projection.argtypes = [W, CM, PR, C.c_uint64, C.c_uint64, vp]
+        L.clw_ext_unit_projection.restype = C.c_int
     L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
     L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
     L.clw_ext_read_tile_costs.restype = u32
@@ -445,6 +470,48 @@ def merge_object_stats(a, b) -> np.ndarray:
     out = np.zeros(a.size + b.size or 1, OBJECT_STAT)
     n = load_library().clw_host_merge_object_stats(_ptr(a), a.size, _ptr(b), b.size, _ptr(out), out.size)
     return out[:n].copy()
+
+
+def projection(model, axis=None, ortho_width: float = 0.0, span=(360.0, 180.0)) -> clw_projection:
+    """A clw_projection from a model (PROJ_* or 'perspective' / 'ortho' / 'equirect'), the view axis (None = the camera's own centre
+    direction), the world width of an orthographic frame (0 = the camera's image plane as it stands) and the (horizontal, vertical) degrees of
+    a panorama.  Nothing is checked here: the library refuses what hip_wrap_ext.h says it refuses."""
+    p = clw_projection()
+    p.model = PROJ_MODELS[model] if isinstance(model, str) else int(model)
+    if axis is not None:
+        p.axis[:] = [float(v) for v in axis]
+    p.ortho_width, p.h_span, p.v_span = float(ortho_width), float(span[0]), float(span[1])
+    return p
+
+
+def projection_rays(cam: clw_camera, proj: clw_projection, id_begin: int = 0, id_end: int | None = None) -> np.ndarray:
+    """clw_host_projection_rays: THE definition of the rays of a camera model -> float32 [id_end - id_begin, 16], the 64-byte records
+    {origin, 0, direction, 0, 0 ...} of the global ids [id_begin, id_end) of the camera's frame (id_end None = its last)."""
+    id_end = cam.width * cam.height if id_end is None else int(id_end)
+    rays = np.zeros((max(id_end - int(id_begin), 0), 16), np.float32)
+    if not load_library().clw_host_projection_rays(C.byref(cam), C.byref(proj), int(id_begin), id_end, _ptr(rays)):
+        raise ValueError("clw_host_projection_rays rejects these arguments (model 0..2, a finite axis, ortho_width >= 0, spans in [0, 360] / "
+                         "[0, 180], reserved 0, ids inside the frame)")
+    return rays
+
+
+def projection_tables(cam: clw_camera, proj: clw_projection):
+    """clw_host_projection_tables: the two tables of a panorama -> (float32 [W, 4] {sin(theta) r + cos(theta) a, 0}, float32 [H, 4]
+    {cos(phi), sin(phi) u}); ray (x, y) = normalize(col[x].xyz * row[y].x + row[y].yzw) in float32."""
+    col, row = np.zeros((cam.width, 4), np.float32), np.zeros((cam.height, 4), np.float32)
+    if not load_library().clw_host_projection_tables(C.byref(cam), C.byref(proj), _ptr(col), _ptr(row)):
+        raise ValueError("clw_host_projection_tables rejects these arguments (an equirectangular projection the library accepts)")
+    return col, row
+
+
+def ortho_camera(origin, look, view_width: float, width: int, height: int):
+    """clw_host_ortho_camera: an orthographic view from `origin` along `look` whose frame spans `view_width` world units -> (clw_camera,
+    clw_projection): the image plane passes through the origin, pixels are square."""
+    cam, proj = clw_camera(), clw_projection()
+    if not load_library().clw_host_ortho_camera((C.c_float * 3)(*origin), (C.c_float * 3)(*look), float(view_width), int(width), int(height),
+                                                C.byref(cam), C.byref(proj)):
+        raise ValueError("clw_host_ortho_camera rejects these arguments (a finite look that is not vertical, view_width > 0, a frame)")
+    return cam, proj
 
 
 def frame_seed(f: int) -> int:
@@ -712,6 +779,22 @@ class ClWrap:
         return _object_table(lambda out, cap, s: self.L.clw_ext_unit_object_stats(C.byref(self.w), _ptr(ids), _ptr(depth), int(width), int(rows), int(first_row),
                                                                                   _rect(rect), _ptr(counts), out, cap, s),
                              first_capacity=max(1024, min(ids.size, int(counts.astype(np.uint64).sum()) + 1)))
+
+    def set_projection(self, proj: clw_projection | None):
+        """clw_ext_set_projection: the camera model of the following launches and inspection passes; None = the pinhole."""
+        self.L.clw_ext_set_projection(C.byref(self.w), None if proj is None else C.byref(proj))
+
+    def get_projection(self) -> clw_projection:
+        p = clw_projection()
+        self.L.clw_ext_get_projection(C.byref(self.w), C.byref(p))
+        return p
+
+    def unit_projection(self, cam: clw_camera, proj: clw_projection, id_begin: int = 0, id_end: int | None = None):
+        """clw_ext_unit_projection: wt_raygen_proj on a synthetic camera -> float32 [id_end - id_begin, 16], or None when it is refused."""
+        id_end = cam.width * cam.height if id_end is None else int(id_end)
+        rays = np.zeros((max(id_end - int(id_begin), 0), 16), np.float32)
+        ok = self.L.clw_ext_unit_projection(C.byref(self.w), C.byref(cam), C.byref(proj), int(id_begin), id_end, _ptr(rays))
+        return rays if ok else None
 
     def set_adaptive(self, threshold): self.L.clw_ext_set_adaptive(C.byref(self.w), int(threshold))
     def get_adaptive(self): return int(self.L.clw_ext_get_adaptive(C.byref(self.w)))

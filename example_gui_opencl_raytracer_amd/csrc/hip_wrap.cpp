@@ -28,6 +28,7 @@
 #include "objects_host.h"
 #include "overlay_host.h"
 #include "png_codec.h"
+#include "projection_host.h"
 #include "scene_prep.h"
 #include "whitted_params.h"
 
@@ -39,8 +40,10 @@ extern "C" hipError_t wt_fast_launch_unit(int, const float*, float*, unsigned, u
 extern "C" hipError_t wt_strict_launch_unit(int, const float*, float*, unsigned, unsigned, unsigned, unsigned, hipStream_t);
 extern "C" hipError_t wt_fast_launch_unit_scene(const whitted_params*, int, int, const float*, float*, unsigned, unsigned, unsigned, size_t, hipStream_t);
 extern "C" hipError_t wt_strict_launch_unit_scene(const whitted_params*, int, int, const float*, float*, unsigned, unsigned, unsigned, size_t, hipStream_t);
-extern "C" hipError_t wt_fast_launch_gbuffer(const whitted_params*, int, unsigned, size_t, float*, unsigned*, float*, float*, float*, hipStream_t);
-extern "C" hipError_t wt_strict_launch_gbuffer(const whitted_params*, int, unsigned, size_t, float*, unsigned*, float*, float*, float*, hipStream_t);
+extern "C" hipError_t wt_fast_launch_gbuffer(const whitted_params*, int, unsigned, size_t, float*, unsigned*, float*, float*, float*, const wt_projection*, hipStream_t);
+extern "C" hipError_t wt_strict_launch_gbuffer(const whitted_params*, int, unsigned, size_t, float*, unsigned*, float*, float*, float*, const wt_projection*, hipStream_t);
+extern "C" hipError_t wt_fast_launch_raygen_proj(const raygen_params*, const wt_projection*, hipStream_t);
+extern "C" hipError_t wt_strict_launch_raygen_proj(const raygen_params*, const wt_projection*, hipStream_t);
 extern "C" hipError_t wt_fast_launch_overlay(const unsigned*, const unsigned*, unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, unsigned, hipStream_t);
 extern "C" hipError_t wt_strict_launch_overlay(const unsigned*, const unsigned*, unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, unsigned, hipStream_t);
 extern "C" hipError_t wt_fast_launch_objects(const unsigned*, const unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, void*, void*, hipStream_t);
@@ -100,6 +103,7 @@ struct Buffer {
                                       rewritten them in place, so they are no longer known to be this library's own unit vectors */
     bool gen_materialised = false;
     RaygenArgs gen{};
+    clw_projection gen_proj{};     /* the camera model the materialised rays were generated with (all zero = the pinhole) */
 };
 
 struct ArgValue {
@@ -192,6 +196,16 @@ struct Impl {
         uint64_t epoch = 0;                           /* bumped by whatever changes the image behind the key's back (uploads, invalidate, reset) */
         bool key_valid = false; AccKey key;
     } acc;
+    /* the camera model beside the pinhole (clw_ext_set_projection / CLWRAP_PROJECTION; whitted_projection.inc): model 0 = none.  The two tables
+     * of a panorama (width and height float4) are the wrapper's: `tab_col` / `tab_row` are what the device copies hold, and they are written
+     * again -- behind a wait for the launches that read them -- only when a launch resolves to other values. */
+    clw_projection proj{};
+    struct ProjTables {
+        float* d_col = nullptr; float* d_row = nullptr;
+        uint32_t cap_w = 0, cap_h = 0;               /* float4s the device buffers hold */
+        std::vector<float> tab_col, tab_row;         /* the tables on the device (4 floats per column / row) */
+        void free_all() { if (d_col) (void)hipFree(d_col); if (d_row) (void)hipFree(d_row); d_col = d_row = nullptr; cap_w = cap_h = 0; tab_col.clear(); tab_row.clear(); }
+    } ptab;
     /* the primary-hit pass (clw_ext_render_gbuffer / clw_ext_pick; whitted_gbuffer.inc): planar channel buffers indexed like the framebuffer, one per
      * CLW_GB_* bit, allocated when a pass first asks for them and sized for the pass's range; `done` is recorded behind every pass on the stream it
      * ran on, so a read-back waits for the pass whatever the launch stream is by then */
@@ -447,11 +461,70 @@ void run_raygen_kernel(Impl* I, const RaygenArgs& g, Buffer* rays, cl_uint kerne
     t.done();
 }
 
-void materialise_rays(Impl* I, Buffer* b) {
-    if (b->gen_valid && !b->gen_materialised) {
-        run_raygen_kernel(I, b->gen, b, 0);
-        b->gen_materialised = true;
+void finish(Impl* I);
+
+clw_camera camera_of(const RaygenArgs& g) {
+    clw_camera c{};
+    memcpy(c.im_corner, g.corner, 12); memcpy(c.origin, g.origin, 12); memcpy(c.up, g.up, 12); memcpy(c.right, g.right, 12);
+    c.w_factor = g.w_factor; c.h_factor = g.h_factor; c.width = g.width; c.height = g.height;
+    return c;
+}
+
+/* The wrapper's projection resolved for a latched camera: the scalar terms and, for the panorama, the device tables -- uploaded only when they
+ * differ from what the device holds, behind a wait for the launches that may still read the old ones.  false = the definition refuses this
+ * camera / projection pair (projection_host.c). */
+bool resolve_projection(Impl* I, const RaygenArgs& g, wt_projection& T) {
+    const clw_camera cam = camera_of(g);
+    if (!wt_projection_terms(&cam, &I->proj, &T)) return false;
+    if (T.model != CLW_PROJ_EQUIRECT) return true;
+    Impl::ProjTables& B = I->ptab;
+    std::vector<float> col(4 * (size_t)g.width), row(4 * (size_t)g.height);
+    if (!clw_host_projection_tables(&cam, &I->proj, col.data(), row.data())) return false;
+    if (!same_bits(B.tab_col, col.data(), col.size()) || !same_bits(B.tab_row, row.data(), row.size())) {
+        finish(I);
+        if (B.cap_w < g.width || B.cap_h < g.height) {
+            B.free_all();
+            HIP_OK(hipMalloc((void**)&B.d_col, col.size() * sizeof(float)), "Couldn't allocate device memory");
+            HIP_OK(hipMalloc((void**)&B.d_row, row.size() * sizeof(float)), "Couldn't allocate device memory");
+            B.cap_w = g.width; B.cap_h = g.height;
+        }
+        HIP_OK(hipMemcpy(B.d_col, col.data(), col.size() * sizeof(float), hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+        HIP_OK(hipMemcpy(B.d_row, row.data(), row.size() * sizeof(float), hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+        B.tab_col.swap(col); B.tab_row.swap(row);
     }
+    T.col = B.d_col; T.row = B.d_row;
+    return true;
+}
+
+/* wt_raygen_proj over the range a raygen launch latched: the records of the wrapper's projection, logged under the raygen kernel's id */
+void run_raygen_proj_kernel(Impl* I, const RaygenArgs& g, Buffer* rays, cl_uint kernel_id) {
+    ensure_allocated(I, rays);
+    size_t cap = rays->size / 64;
+    uint32_t n = g.n_items < cap ? g.n_items : (uint32_t)cap; /* never write past the buffer */
+    if (n == 0) return;
+    wt_projection T;
+    if (!resolve_projection(I, g, T)) die("The projection (clw_ext_set_projection / CLWRAP_PROJECTION) cannot be resolved for this camera: a zero axis over a camera whose image plane is centred on its origin, or a panorama whose axis is parallel to the camera's right or up");
+    raygen_params P{};
+    P.width = g.width; P.height = g.height;
+    P.id_offset = g.id_offset; P.n_items = n; P.rays = (float*)rays->dptr;
+    P.band_stride = g.band_stride; P.band_phase = g.band_phase;
+    LaunchTimer t(I, kernel_id);
+    hipError_t e = (I->strict ? wt_strict_launch_raygen_proj : wt_fast_launch_raygen_proj)(&P, &T, I->stream);
+    if (e != hipSuccess) die("Couldn't run the kernel");
+    t.done();
+}
+
+bool same_projection(const clw_projection& a, const clw_projection& b) { return !memcmp(&a, &b, sizeof a); }
+
+/* the records of a generated ray buffer, if they are not there yet -- or were generated under another camera model (a buffer whose pointer was
+ * handed out is the caller's: traced as written) */
+void materialise_rays(Impl* I, Buffer* b) {
+    if (!b->gen_valid) return;
+    if (b->gen_materialised && (b->exposed || same_projection(b->gen_proj, I->proj))) return;
+    if (I->proj.model != CLW_PROJ_PERSPECTIVE) run_raygen_proj_kernel(I, b->gen, b, 0);
+    else run_raygen_kernel(I, b->gen, b, 0);
+    b->gen_materialised = true;
+    b->gen_proj = I->proj;
 }
 
 uint32_t read_count(const Kernel& k, cl_uint arg) {
@@ -668,7 +741,7 @@ void plan_input(const Impl* I, const Buffer* rays, size_t array_size, uint32_t t
     in.ns = I->prep_ns; in.np = I->prep_np; in.nl = I->prep_nl; in.geom_f4 = (uint32_t)I->geom_f4;
     in.have_lpt = I->have_lpt; in.grid_usable = I->grid_ok && I->use_grid;
     in.args_ok = 1;
-    in.rays_generated = rays->gen_valid; in.rays_exposed = rays->exposed; in.gen = rays->gen; in.rays_size = rays->size;
+    in.rays_generated = rays->gen_valid ? 1 + (int32_t)I->proj.model : 0; in.rays_exposed = rays->exposed; in.gen = rays->gen; in.rays_size = rays->size;
     in.array_size = array_size; in.out_size = out_size; in.total = total;
     in.has_strip = strip != nullptr; in.strip_row0 = strip ? strip->row0 : 0u; in.strip_rows = strip ? strip->rows : 0u;
     in.pass = pass;
@@ -896,7 +969,8 @@ void check_modes(const Impl* I, const Buffer* rays, bool accumulating) {
     char message[200];
     in.fuse = I->fuse; in.supersample = I->supersample; in.adaptive = I->adaptive; in.aperture = I->aperture;
     in.n_cams = (uint32_t)I->cams.size(); in.n_disp = (uint32_t)I->motion_disp.size();
-    if (rays) { in.rays_generated = rays->gen_valid; in.rays_exposed = rays->exposed; }
+    in.rays_generated = 1 + (int32_t)I->proj.model;      /* (an adaptive call does not look at the buffer: the plan of its passes does) */
+    if (rays) { in.rays_generated = rays->gen_valid ? 1 + (int32_t)I->proj.model : 0; in.rays_exposed = rays->exposed; }
     if (wt_plan_mode_check(&in, accumulating, message)) die("%s", message);
 }
 
@@ -948,6 +1022,7 @@ bool pipelined_output(cl_wrap* w, Impl* I, size_t array_size, size_t output_size
                       cl_int out_arg, void* host_output) {
     if (!I->pipeline || I->async || !host_output || !I->fuse || I->counting || I->debug_rgb || (I->variant & WT_V_LINEAR_IDS)) return false;
     if (I->acc_max > 0) return false;        /* an accumulated view is one launch per frame, or none at all once it has converged */
+    if (I->proj.model != CLW_PROJ_PERSPECTIVE) return false;      /* a projected frame is traced from its ray buffer: one launch */
     if (I->adaptive >= 0) return false;      /* a strip's edge rows would be classified without their neighbours in the next strip: another frame */
     if (out_kernel != kid || out_arg != 10 || !is_registered(w, kid, 10)) return false;
     Buffer* rays = find_rays(w, I, kid);
@@ -993,13 +1068,19 @@ void run_raygen(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size) {
     Kernel& k = I->kernels[kid];
     Buffer* rays = buffer_arg(w, kid, 8);
     RaygenArgs g = snapshot_raygen(I, k, array_size);
+    /* under a camera model the records live in the buffer: a still view -- the same latched values, range and projection, the buffer not handed
+     * out -- keeps the ones it has */
+    const bool keep = I->proj.model != CLW_PROJ_PERSPECTIVE && rays->gen_valid && rays->gen_materialised && !rays->exposed && same_raygen(g, rays->gen) &&
+                      same_projection(rays->gen_proj, I->proj);
     rays->gen = g;
     rays->gen_valid = true;
-    rays->gen_materialised = false;
+    rays->gen_materialised = keep;
     rays->exposed = false;
-    if (!I->fuse) {
-        run_raygen_kernel(I, g, rays, kid);
+    if (!I->fuse && !keep) {
+        if (I->proj.model != CLW_PROJ_PERSPECTIVE) run_raygen_proj_kernel(I, g, rays, kid);
+        else run_raygen_kernel(I, g, rays, kid);
         rays->gen_materialised = true;
+        rays->gen_proj = I->proj;
     }
 }
 
@@ -1009,7 +1090,8 @@ constexpr uint32_t GB_WORDS[5] = {1, 1, 3, 3, 3};      /* 4-byte words per work-
 /* The pass's launch parameters over the range the next trace launch would cover: the camera and range the raygen launch latched, clipped by
  * the raytracer's `pixels` argument, bands included; the scene as bind_scene binds it.  false (nothing filled in) when there is no raytracer
  * kernel, no latched camera or no bound scene yet -- the callers return 0 then, they do not terminate the process. */
-bool gbuffer_params(cl_wrap* w, Impl* I, whitted_params& P, int& flags, size_t& dyn_lds) {
+bool gbuffer_params(cl_wrap* w, Impl* I, whitted_params& P, int& flags, size_t& dyn_lds, wt_projection& T) {
+    memset(&T, 0, sizeof T);      /* model 0: the pinhole */
     cl_uint kid = 0;
     while (kid < I->kernels.size() && I->kernels[kid].kind != K_RAYTRACER) kid++;
     if (kid >= I->kernels.size()) return false;
@@ -1023,17 +1105,19 @@ bool gbuffer_params(cl_wrap* w, Impl* I, whitted_params& P, int& flags, size_t& 
     const RaygenArgs& g = rays->gen;
     const uint32_t n = g.n_items < total ? g.n_items : total;
     if (n == 0) return false;
+    if (I->proj.model != CLW_PROJ_PERSPECTIVE && !resolve_projection(I, g, T)) return false;      /* (before anything is bound or launched) */
     bind_scene(w, I, kid, P, flags, dyn_lds);
     wt_plan_fused_range(&g, n, &P);      /* as the fused trace launch: the rays are this library's own */
+    if (T.model != CLW_PROJ_PERSPECTIVE) P.unit_dirs = 0u;      /* as the trace launch of a projected view: no direction is taken for unit */
     P.vis = 0;
     return true;
 }
 
-void launch_gbuffer(Impl* I, const whitted_params& P, int flags, size_t dyn_lds, void* const chan[5], bool timed) {
+void launch_gbuffer(Impl* I, const whitted_params& P, int flags, size_t dyn_lds, void* const chan[5], const wt_projection& T, bool timed) {
     const unsigned grid = wt_plan_grid(&P);      /* as trace_launch: tile rows dealt to the 8 XCDs */
     LaunchTimer t(I, CLW_TIMING_GBUFFER, timed);
     hipError_t e = (I->strict ? wt_strict_launch_gbuffer : wt_fast_launch_gbuffer)(&P, flags, grid, dyn_lds, (float*)chan[0], (unsigned*)chan[1], (float*)chan[2],
-                                                                                   (float*)chan[3], (float*)chan[4], I->stream);
+                                                                                   (float*)chan[3], (float*)chan[4], &T, I->stream);
     if (e != hipSuccess) die("Couldn't run the kernel");
     t.done();
 }
@@ -1160,6 +1244,31 @@ void cl_wrap_init(cl_wrap* wrap, cl_device_type type, ...) {
     I->focus = env_float("CLWRAP_FOCUS", 1.0f);
     if (!(I->aperture >= 0.0f) || !std::isfinite(I->aperture)) die("CLWRAP_APERTURE (lens aperture) must be a finite number >= 0");
     if (!(I->focus > 0.0f) || !std::isfinite(I->focus)) die("CLWRAP_FOCUS (lens focus distance) must be a finite number > 0");
+    if (const char* pm = getenv("CLWRAP_PROJECTION")) {
+        if (*pm) {
+            if (!strcmp(pm, "ortho")) I->proj.model = CLW_PROJ_ORTHO;
+            else if (!strcmp(pm, "equirect")) I->proj.model = CLW_PROJ_EQUIRECT;
+            else if (strcmp(pm, "perspective")) die("CLWRAP_PROJECTION (camera model) must be ortho or equirect (or perspective, the default)");
+        }
+    }
+    if (const char* ow = getenv("CLWRAP_ORTHO_WIDTH")) {
+        if (*ow) {
+            char* end = nullptr;
+            const float v = strtof(ow, &end);
+            if (end == ow || *end || !std::isfinite(v) || v < 0.0f) die("CLWRAP_ORTHO_WIDTH (world units an orthographic frame's width spans) must be a finite number >= 0");
+            I->proj.ortho_width = v;
+        }
+    }
+    if (const char* ps = getenv("CLWRAP_PANO_SPAN")) {
+        if (*ps) {
+            char *end = nullptr, *end2 = nullptr;
+            const float h = strtof(ps, &end);
+            const float v = (end != ps && *end == ',') ? strtof(end + 1, &end2) : 0.0f;
+            if (end == ps || *end != ',' || end2 == end + 1 || !end2 || *end2 || !std::isfinite(h) || !std::isfinite(v) || h < 0.0f || h > 360.0f || v < 0.0f || v > 180.0f)
+                die("CLWRAP_PANO_SPAN (degrees a panorama covers) must be <h>,<v> with h in [0, 360] and v in [0, 180] (0 = 360 / 180)");
+            I->proj.h_span = h; I->proj.v_span = v;
+        }
+    }
     I->stamps = env_int("CLWRAP_STAMPS", 0) ? 1 : 0;
     if (const char* th = getenv("CLWRAP_THROUGH")) { if (*th) I->through = (float)atof(th); }
     I->occ_tiles_per_depth = (unsigned)env_int("CLWRAP_OCC_TILES_PER_DEPTH", (int)WT_OCC_TILES_PER_DEPTH);
@@ -1304,6 +1413,7 @@ void cl_wrap_release(cl_wrap* wrap) {
     I->ov.free_buffers();
     if (I->ov.done) (void)hipEventDestroy(I->ov.done);
     I->obj.free_buffers();
+    I->ptab.free_all();
     I->adapt.free_all();
     if (I->tables_fence) (void)hipEventDestroy(I->tables_fence);
     for (uint32_t* q : {I->d_grid_start, I->d_grid_items, I->d_grid_box}) if (q) (void)hipFree(q);
@@ -1552,6 +1662,54 @@ void clw_ext_set_accumulate(cl_wrap* wrap, int max_frames, int jitter) {
 uint32_t clw_ext_get_accumulated(cl_wrap* wrap) { Impl* I = impl_of(wrap); return I->acc_max > 0 ? I->acc.K : 0u; }
 void clw_ext_reset_accumulation(cl_wrap* wrap) { impl_of(wrap)->acc.epoch++; }
 
+void clw_ext_set_projection(cl_wrap* wrap, const clw_projection* proj) {
+    Impl* I = impl_of(wrap);
+    clw_projection p{};
+    if (proj && proj->model != CLW_PROJ_PERSPECTIVE) {
+        p = *proj;
+        if (p.model > CLW_PROJ_EQUIRECT) die("The projection model must be CLW_PROJ_PERSPECTIVE, CLW_PROJ_ORTHO or CLW_PROJ_EQUIRECT");
+        if (p.reserved != 0u) die("The projection's reserved word must be 0");
+        if (!std::isfinite(p.axis[0]) || !std::isfinite(p.axis[1]) || !std::isfinite(p.axis[2])) die("The projection's axis must be finite");
+        if (!std::isfinite(p.ortho_width) || p.ortho_width < 0.0f) die("The projection's ortho_width must be a finite number >= 0");
+        if (!std::isfinite(p.h_span) || p.h_span < 0.0f || p.h_span > 360.0f || !std::isfinite(p.v_span) || p.v_span < 0.0f || p.v_span > 180.0f)
+            die("The projection's spans must be in [0, 360] and [0, 180] degrees (0 = 360 / 180)");
+    }
+    I->proj = p;      /* (the pinhole is stored as all zero, whatever else the caller's struct held) */
+}
+void clw_ext_get_projection(const cl_wrap* wrap, clw_projection* out) { if (out) *out = impl_of(wrap)->proj; }
+
+int clw_ext_unit_projection(cl_wrap* wrap, const clw_camera* cam, const clw_projection* proj, uint64_t id_begin, uint64_t id_end, float* out_rays) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    wt_projection T;
+    if (!out_rays || !wt_projection_terms(cam, proj, &T) || T.model == CLW_PROJ_PERSPECTIVE) return 0;
+    const uint64_t total = (uint64_t)cam->width * cam->height;
+    if (id_begin >= id_end || id_end > total || id_end - id_begin > 0x03FFFFFFull) return 0;      /* (64 n bytes in 32 bits) */
+    const uint32_t n = (uint32_t)(id_end - id_begin);
+    float *drays = nullptr, *dcol = nullptr, *drow = nullptr;
+    if (T.model == CLW_PROJ_EQUIRECT) {
+        std::vector<float> col(4 * (size_t)cam->width), row(4 * (size_t)cam->height);
+        if (!clw_host_projection_tables(cam, proj, col.data(), row.data())) return 0;
+        HIP_OK(hipMalloc((void**)&dcol, col.size() * sizeof(float)), "Couldn't allocate device memory");
+        HIP_OK(hipMalloc((void**)&drow, row.size() * sizeof(float)), "Couldn't allocate device memory");
+        HIP_OK(hipMemcpy(dcol, col.data(), col.size() * sizeof(float), hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+        HIP_OK(hipMemcpy(drow, row.data(), row.size() * sizeof(float), hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+        T.col = dcol; T.row = drow;
+    }
+    HIP_OK(hipMalloc((void**)&drays, (size_t)n * 64), "Couldn't allocate device memory");
+    HIP_OK(hipDeviceSynchronize(), "The device kernel failed");
+    raygen_params P{};
+    P.width = cam->width; P.height = cam->height; P.id_offset = id_begin; P.n_items = n; P.rays = drays; P.band_stride = 1; P.band_phase = 0;
+    hipError_t e = (I->strict ? wt_strict_launch_raygen_proj : wt_fast_launch_raygen_proj)(&P, &T, I->stream);
+    if (e != hipSuccess) die("Couldn't run the kernel");
+    finish(I);
+    HIP_OK(hipMemcpy(out_rays, drays, (size_t)n * 64, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
+    (void)hipFree(drays);
+    if (dcol) (void)hipFree(dcol);
+    if (drow) (void)hipFree(drow);
+    return 1;
+}
+
 uint32_t clw_ext_render_gbuffer(cl_wrap* wrap, uint32_t channels) {
     Impl* I = impl_of(wrap);
     use_device(I);
@@ -1560,7 +1718,8 @@ uint32_t clw_ext_render_gbuffer(cl_wrap* wrap, uint32_t channels) {
     whitted_params P{};
     int flags = 0;
     size_t dyn_lds = 0;
-    if (!gbuffer_params(wrap, I, P, flags, dyn_lds)) return 0;
+    wt_projection T;
+    if (!gbuffer_params(wrap, I, P, flags, dyn_lds, T)) return 0;
     Impl::GBuffer& B = I->gb;
     if (B.n != P.n_items) {      /* another range: a pass under way may still write the old buffers */
         if (B.n) { finish(I); if (B.done) (void)hipEventSynchronize(B.done); }
@@ -1573,7 +1732,7 @@ uint32_t clw_ext_render_gbuffer(cl_wrap* wrap, uint32_t channels) {
         if (!B.chan[c]) HIP_OK(hipMalloc(&B.chan[c], (size_t)B.n * GB_WORDS[c] * 4), "Couldn't allocate device memory");
         chan[c] = B.chan[c];
     }
-    launch_gbuffer(I, P, flags, dyn_lds, chan, true);
+    launch_gbuffer(I, P, flags, dyn_lds, chan, T, true);
     if (!B.done) HIP_OK(hipEventCreateWithFlags(&B.done, hipEventDisableTiming), "Couldn't create a timing event");
     HIP_OK(hipEventRecord(B.done, I->stream), "Couldn't run the kernel");
     B.written = channels;
@@ -1609,7 +1768,8 @@ int clw_ext_pick(cl_wrap* wrap, uint32_t x, uint32_t y, clw_pick* out) {
     whitted_params P{};
     int flags = 0;
     size_t dyn_lds = 0;
-    if (!gbuffer_params(wrap, I, P, flags, dyn_lds)) return 0;
+    wt_projection T;
+    if (!gbuffer_params(wrap, I, P, flags, dyn_lds, T)) return 0;
     if (x >= P.width || y >= P.height) return 0;
     /* is the pixel one of the wrapper's work-items? */
     if (P.band_stride > 1u) {
@@ -1628,7 +1788,7 @@ int clw_ext_pick(cl_wrap* wrap, uint32_t x, uint32_t y, clw_pick* out) {
     if (!B.pick) HIP_OK(hipMalloc((void**)&B.pick, sizeof(clw_pick)), "Couldn't allocate device memory");
     static_assert(sizeof(clw_pick) == 44, "clw_pick is 11 words");
     void* chan[5] = {B.pick + 1, B.pick + 0, B.pick + 5, B.pick + 2, B.pick + 8};      /* depth, id, normal, point, albedo as clw_pick lays them out */
-    launch_gbuffer(I, P, flags, dyn_lds, chan, false);
+    launch_gbuffer(I, P, flags, dyn_lds, chan, T, false);
     clw_pick h;
     if (hipMemcpyAsync(&h, B.pick, sizeof h, hipMemcpyDeviceToHost, I->stream) != hipSuccess) die("Failed to transfer device memory to host");
     finish(I);
@@ -1647,7 +1807,8 @@ uint32_t clw_ext_render_overlay(cl_wrap* wrap, const clw_overlay* style, const u
     whitted_params P{};
     int flags = 0;
     size_t dyn_lds = 0;
-    if (!gbuffer_params(wrap, I, P, flags, dyn_lds)) return 0;
+    wt_projection T;
+    if (!gbuffer_params(wrap, I, P, flags, dyn_lds, T)) return 0;
     /* whole rows of one contiguous range: work-item i is pixel (i % width, i / width) of the range's own image */
     if (P.band_stride > 1u || !P.tiled || P.rows == 0u) return 0;
     Buffer* fb = (Buffer*)wrap->buffers[kid][10];
@@ -1662,7 +1823,7 @@ uint32_t clw_ext_render_overlay(cl_wrap* wrap, const clw_overlay* style, const u
         O.n = P.n_items;
     }
     void* chan[5] = {nullptr, O.ids, nullptr, nullptr, nullptr};
-    launch_gbuffer(I, P, flags, dyn_lds, chan, true);
+    launch_gbuffer(I, P, flags, dyn_lds, chan, T, true);
     launch_overlay(I, (const uint32_t*)fb->dptr, O.ids, O.frame, P.width, P.rows, *style, sel, count, true);
     if (!O.done) HIP_OK(hipEventCreateWithFlags(&O.done, hipEventDisableTiming), "Couldn't create a timing event");
     HIP_OK(hipEventRecord(O.done, I->stream), "Couldn't run the kernel");
@@ -1719,7 +1880,8 @@ int clw_ext_object_stats(cl_wrap* wrap, const clw_rect* rect, clw_object_stat* o
     whitted_params P{};
     int flags = 0;
     size_t dyn_lds = 0;
-    if (!gbuffer_params(wrap, I, P, flags, dyn_lds)) return 0;
+    wt_projection T;
+    if (!gbuffer_params(wrap, I, P, flags, dyn_lds, T)) return 0;
     /* whole rows of one contiguous range: work-item i is pixel (i % width, row_offset + i / width) of the frame */
     if (P.band_stride > 1u || !P.tiled || P.rows == 0u) return 0;
     const uint32_t counts[3] = {P.ns, P.np, P.nl};
@@ -1727,7 +1889,7 @@ int clw_ext_object_stats(cl_wrap* wrap, const clw_rect* rect, clw_object_stat* o
     if (!wt_objects_check(&O, P.width, P.rows, P.row_offset, rect, counts, summary)) return 0;      /* (the ids are the pass's own: any non-NULL pointer) */
     O.size_range(P.n_items);
     void* chan[5] = {O.depth, O.ids, nullptr, nullptr, nullptr};
-    launch_gbuffer(I, P, flags, dyn_lds, chan, true);
+    launch_gbuffer(I, P, flags, dyn_lds, chan, T, true);
     run_objects(I, O.ids, O.depth, P.width, P.rows, P.row_offset, rect, counts, out, capacity, summary, true);
     return 1;
 }

@@ -80,6 +80,9 @@ typedef struct {
     int32_t have_lpt, grid_usable;
     /* the ray buffer of argument 0 */
     int32_t args_ok;                /* the ray handle resolves, `total` and the framebuffer are bound */
+    /* rays_generated: 0 = the caller's rays; else the rays of a raygen launch of this library, 1 + the CLW_PROJ_* camera model they are generated
+     * under -- 1 = the pinhole, 2 = the orthographic view, 3 = the panorama (wt_plan_projection).  A projected launch is never fused: its records
+     * are generated into the ray buffer (wt_raygen_proj) and traced as a ray buffer is. */
     int32_t rays_generated, rays_exposed;
     wt_raygen gen;
     uint64_t rays_size;
@@ -136,6 +139,8 @@ int wt_plan(const wt_plan_in* in, wt_plan_out* out);
 /* What the modes do not combine with, before any launch of a trace call: `accumulating` = frame accumulation is on, else in->adaptive says
  * whether the call is adaptive.  -> 0, or WT_PLAN_REFUSED and the text in message[200]. */
 int wt_plan_mode_check(const wt_plan_in* in, int accumulating, char* message);
+/* the camera model of the launch's generated rays (CLW_PROJ_*; 0 = the pinhole, and what a caller's rays have) */
+int wt_plan_projection(const wt_plan_in* in);
 /* work-items of a launch: the size argument rounded as the reference rounds it, guarded by `total` and the framebuffer */
 uint64_t wt_plan_range(uint64_t array_size, uint32_t total, uint64_t out_size);
 /* a tile's lane (lane & 7, lane >> 3) traces sub-sample (sx, sy) = both mod n -> sy * n + sx */

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "whitted_params.h"
+#include "projection_host.h"
 #define WT_STRICT 0
 #define WT_NS wt_fast
 #define WT_LAUNCH_TRACE wt_fast_launch_trace

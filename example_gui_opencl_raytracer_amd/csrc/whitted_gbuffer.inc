@@ -12,7 +12,11 @@
  * arithmetic (wt_gb_ref_*: IEEE divide and square root, no fused operation), the same in both builds: D/4 = b b - c cancels near a silhouette
  * and from afar, where the fast build's fused products move t by 1e-4 and more and a light's (1 / d) * d by an ulp, and a consumer of the buffers
  * (a focus distance, a denoiser's normals) should not see which build made them.  In the strict build these are the search's own values.
- * The pass sees the launch camera at pixel centres and the scene as it stands: no sample cameras, no sphere motion, no jitter, no seed. */
+ * The pass sees the launch camera at pixel centres and the scene as it stands: no sample cameras, no sphere motion, no jitter, no seed.
+ * Under a camera model beside the pinhole (the kernel's third argument, wt_projection: hip_wrap_ext.h, clw_ext_set_projection) the primary ray is
+ * wt_proj_ray's and no direction is taken for unit, as the trace launch of such a view takes none.  That is the PROJ instantiation: a run-time
+ * branch on the model was measured first and cost the pinhole's pass 5-8 % on the demo scene (0.0245 against 0.0230 ms at 1920x1080: a = d.d = 1
+ * stopped being a compile-time constant of the sphere tests), so the pinhole keeps an instantiation that executes what it executed. */
 
 /* id word of a pixel: kind << 30 | index (hip_wrap_ext.h: CLW_GB_ID) */
 #define WT_GB_KIND_PLANE (1u << 30)
@@ -68,13 +72,16 @@ __device__ __forceinline__ void wt_gb_store3(float* __restrict__ p, unsigned ite
     if (p) { float* q = p + 3 * (size_t)item; q[0] = v.x; q[1] = v.y; q[2] = v.z; }
 }
 
-template <bool GEOM_LDS, bool GRID>
-__global__ void __launch_bounds__(WT_BLOCK) wt_gbuffer(const whitted_params P, const wt_gbuffer_out G) {
+/* the ray of a pixel under a camera model beside the pinhole (whitted_projection.inc) */
+__device__ __forceinline__ void wt_proj_ray(const wt_projection& T, unsigned x, unsigned y, f3& o, f3& d);
+
+template <bool GEOM_LDS, bool GRID, bool PROJ>
+__global__ void __launch_bounds__(WT_BLOCK) wt_gbuffer(const whitted_params P, const wt_gbuffer_out G, const wt_projection T) {
     extern __shared__ float4 s_geom[];
     if (GEOM_LDS) wt_stage_scene(P, s_geom, threadIdx.x, WT_BLOCK);
     const float4* sg = s_geom;
     const unsigned tid = threadIdx.x, lane = tid & 63u, wg = blockIdx.x;
-    constexpr bool UNIT_CT = !WT_STRICT && GEOM_LDS && !GRID;       /* as the fused trace launch: see whitted_hit.inc */
+    constexpr bool UNIT_CT = !WT_STRICT && GEOM_LDS && !GRID && !PROJ;       /* as the fused trace launch: see whitted_hit.inc (a projected view takes no direction for unit, as its trace launch takes none) */
 
     /* ---- work-item -> pixel: wt_trace_body's mapping in its default dispatch order (no tile order, no split tiles) ---- */
     bool valid;
@@ -103,9 +110,12 @@ __global__ void __launch_bounds__(WT_BLOCK) wt_gbuffer(const whitted_params P, c
     if (!valid) return;      /* (behind the staging barrier; every ballot below is an early-out over per-lane predicates) */
 
     f3 d;
-    if (P.tiled || P.band_stride > 1u) d = wt_primary_dir_xy(P.corner, P.right, P.up, P.w_factor, P.h_factor, x, gy);
+    f3 o = mk3(P.origin[0], P.origin[1], P.origin[2]);
+    if (PROJ) {      /* the orthographic view or the panorama (the shim clears unit_dirs); the pinhole's instantiation never reads T */
+        if (P.tiled || P.band_stride > 1u) wt_proj_ray(T, x, gy, o, d);
+        else wt_proj_ray(T, (unsigned)gid % P.width, (unsigned)gid / P.width, o, d);
+    } else if (P.tiled || P.band_stride > 1u) d = wt_primary_dir_xy(P.corner, P.right, P.up, P.w_factor, P.h_factor, x, gy);
     else d = wt_primary_dir(P.corner, P.right, P.up, P.w_factor, P.h_factor, (unsigned)gid, P.width);
-    const f3 o = mk3(P.origin[0], P.origin[1], P.origin[2]);
     const rayq r = UNIT_CT ? wt_rayq<true>(o, d) : wt_rayq<false>(o, d, P.unit_dirs != 0u);
     const unsigned g_pln = P.ns, g_lgt = P.ns + 2 * P.np;
 

@@ -1,9 +1,11 @@
 /* whitted_launch.inc -- instantiates the kernels of whitted_trace.inc (and the primary-hit pass of whitted_gbuffer.inc, built from its
- * pieces, the selection overlay of whitted_overlay.inc and the visible-object table of whitted_objects.inc) in namespace WT_NS and exports
+ * pieces, the camera models of whitted_projection.inc, the selection overlay of whitted_overlay.inc and the visible-object table of
+ * whitted_objects.inc) in namespace WT_NS and exports
  * the C launchers the shim calls. */
 namespace WT_NS {
 #include "whitted_trace.inc"
 #include "whitted_gbuffer.inc"
+#include "whitted_projection.inc"
 #include "whitted_overlay.inc"
 #include "whitted_objects.inc"
 }
@@ -127,19 +129,39 @@ extern "C" hipError_t WT_LAUNCH_UNIT_SCENE(const whitted_params* P, int flags, i
 }
 
 /* the primary-hit pass (whitted_gbuffer.inc): geometry as bind_scene chose it -- WT_F_GRID the uniform grid, WT_F_GEOM_LDS the scene staged in LDS, else
- * read from global memory; the five channel pointers in CLW_GB_* bit order, NULL = not written */
+ * read from global memory; the five channel pointers in CLW_GB_* bit order, NULL = not written; `T` = the camera model (model 0: the pinhole) */
 #if WT_STRICT
 #define WT_LAUNCH_GBUFFER wt_strict_launch_gbuffer
 #else
 #define WT_LAUNCH_GBUFFER wt_fast_launch_gbuffer
 #endif
 extern "C" hipError_t WT_LAUNCH_GBUFFER(const whitted_params* P, int flags, unsigned grid, size_t dyn_lds, float* depth, unsigned* id,
-                                        float* normal, float* point, float* albedo, hipStream_t s) {
+                                        float* normal, float* point, float* albedo, const wt_projection* T, hipStream_t s) {
     const WT_NS::wt_gbuffer_out G = {depth, id, normal, point, albedo};
     const dim3 g(grid), block(WT_BLOCK);
-    if (flags & WT_F_GRID) hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, true>), g, block, 0, s, *P, G);
-    else if (flags & WT_F_GEOM_LDS) hipLaunchKernelGGL((WT_NS::wt_gbuffer<true, false>), g, block, dyn_lds, s, *P, G);
-    else hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, false>), g, block, 0, s, *P, G);
+    if (T->model != CLW_PROJ_PERSPECTIVE) {      /* the instantiation that calls wt_proj_ray */
+        if (flags & WT_F_GRID) hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, true, true>), g, block, 0, s, *P, G, *T);
+        else if (flags & WT_F_GEOM_LDS) hipLaunchKernelGGL((WT_NS::wt_gbuffer<true, false, true>), g, block, dyn_lds, s, *P, G, *T);
+        else hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, false, true>), g, block, 0, s, *P, G, *T);
+    } else if (flags & WT_F_GRID) hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, true, false>), g, block, 0, s, *P, G, *T);
+    else if (flags & WT_F_GEOM_LDS) hipLaunchKernelGGL((WT_NS::wt_gbuffer<true, false, false>), g, block, dyn_lds, s, *P, G, *T);
+    else hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, false, false>), g, block, 0, s, *P, G, *T);
+    return hipGetLastError();
+}
+
+/* the raygen of the camera models beside the pinhole (whitted_projection.inc): wt_raygen's launch shape; `T` carries the model's terms and, for
+ * the panorama, the device addresses of its two tables (width and height float4) */
+#if WT_STRICT
+#define WT_LAUNCH_RAYGEN_PROJ wt_strict_launch_raygen_proj
+#else
+#define WT_LAUNCH_RAYGEN_PROJ wt_fast_launch_raygen_proj
+#endif
+extern "C" hipError_t WT_LAUNCH_RAYGEN_PROJ(const raygen_params* P, const wt_projection* T, hipStream_t s) {
+    if (P->n_items == 0u || P->width == 0u || (T->model != CLW_PROJ_ORTHO && T->model != CLW_PROJ_EQUIRECT) ||
+        (T->model == CLW_PROJ_EQUIRECT && (!T->col || !T->row || T->width != P->width || T->height != P->height)))
+        return hipErrorInvalidValue;
+    unsigned grid = (P->n_items + WT_RG_BLOCK - 1) / WT_RG_BLOCK;
+    hipLaunchKernelGGL(WT_NS::wt_raygen_proj, dim3(grid), dim3(WT_RG_BLOCK), 0, s, *P, *T);
     return hipGetLastError();
 }
 

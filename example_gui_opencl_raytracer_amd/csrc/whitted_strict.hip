@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "whitted_params.h"
+#include "projection_host.h"
 #define WT_STRICT 1
 #define WT_NS wt_strict
 #define WT_LAUNCH_TRACE wt_strict_launch_trace

@@ -41,6 +41,13 @@ and they leave an accumulating view counting.
 frame and an id pass where they lie.  It never writes the traced frame, leaves ``gbuffer()``'s buffers and an accumulating view alone, and is
 not available with row bands.  A strip is composed on its own rows: within ``radius`` rows of its edges it can differ from the full frame's.
 
+``projection=...`` / ``set_projection(model, ...)`` / ``look_ortho`` / ``look_panorama``: the camera models beside the pinhole
+(clw_ext_set_projection) -- ``'ortho'``: parallel rays from the image plane, the top / front / side view of an editor; ``'equirect'``: a
+latitude-longitude panorama of up to 360 x 180 degrees around the camera origin.  ``render()``, ``read_rays()``, ``gbuffer()``, ``pick``,
+``highlight``, ``objects`` and ``select_rect`` all honour the model; row strips and bands work unchanged (everything is indexed by global id).
+A projected frame is traced from a generated ray buffer, so it does not combine with ``supersample`` > 1, ``lens``, sample cameras,
+``motion``, ``adaptive`` or ``accumulate``: the trace launch refuses them.
+
 A renderer is a context manager: ``with Renderer(...) as r:`` releases it on the way out; releasing twice is harmless.
 """
 from __future__ import annotations
@@ -70,7 +77,7 @@ class Renderer:
                  rows: int | None = None, bands: tuple[int, int] | None = None, framebuffer_ptr: int | None = None, wide_counts: bool | None = None,
                  texture_paths=None, skybox_path=None, supersample: int = 1,
                  lens: tuple[float, float] | None = None, motion=None, adaptive: int | None = None,
-                 accumulate: int = 0, jitter: bool = True, seed_offset: int = 0):
+                 accumulate: int = 0, jitter: bool = True, seed_offset: int = 0, projection=None):
         self.width, self.height = width, height
         self.first_row = first_row
         self.rows = height - first_row if rows is None else rows
@@ -99,6 +106,8 @@ class Renderer:
             w.set_accumulate(self.accumulate, jitter)
         if bands is not None:
             w.set_row_bands(*bands)
+        if projection is not None:      # a model name, an api.PROJ_* value or an api.clw_projection: the camera model beside the pinhole
+            self.set_projection(projection)
 
         u32 = lambda v: np.uint32(v)
         w.load_single_data(0, 6, u32(width))
@@ -155,6 +164,30 @@ class Renderer:
     def look(self, origin, look, fov=90.0, focal=1.0):
         cam = api.perspective(origin, look, fov, focal, self.width, self.height)
         self.set_camera(cam)
+        return cam
+
+    # ---- the camera models beside the pinhole
+    def set_projection(self, model, *, axis=None, ortho_width: float = 0.0, span=(360, 180)) -> None:
+        """model: None / 'perspective' (the pinhole), 'ortho', 'equirect', an api.PROJ_* value, or a ready api.clw_projection.  axis: the view
+        direction (None = from the camera origin to the centre of its image plane); ortho_width: the world units an orthographic frame's width
+        spans (0 = the camera's image plane as it stands); span: the (horizontal, vertical) degrees a panorama covers."""
+        if model is None or isinstance(model, api.clw_projection):
+            self.w.set_projection(model)
+        else:
+            self.w.set_projection(api.projection(model, axis, ortho_width, span))
+
+    def look_ortho(self, origin, look, view_width: float):
+        """An orthographic view from `origin` along `look` whose frame spans `view_width` world units -> the camera set."""
+        cam, proj = api.ortho_camera(origin, look, view_width, self.width, self.height)
+        self.set_camera(cam)
+        self.w.set_projection(proj)
+        return cam
+
+    def look_panorama(self, origin, look=(0, 0, 1), span=(360, 180)):
+        """A latitude-longitude panorama around `origin` whose centre column looks along `look` -> the camera set."""
+        cam = api.perspective(origin, look, 90.0, 1.0, self.width, self.height)
+        self.set_camera(cam)
+        self.w.set_projection(api.projection(api.PROJ_EQUIRECT, look, 0.0, span))
         return cam
 
     # ---- one frame: raygen launch + trace launch (+ blocking read-back)

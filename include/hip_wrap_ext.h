@@ -14,6 +14,7 @@
  *   CLWRAP_DEPTH=<1..32>   CLWRAP_STRICT=<0|1>   CLWRAP_FUSE=<0|1>   CLWRAP_DEVICE=<ordinal>   CLWRAP_PIPELINE=<0|1>   CLWRAP_THROUGH=<float>
  *   CLWRAP_SUPERSAMPLE=<1|2|4|8>   CLWRAP_APERTURE=<float >= 0>   CLWRAP_FOCUS=<float > 0>   (thin lens: clw_ext_set_lens)
  *   CLWRAP_ADAPTIVE=<0..256>   CLWRAP_SEED_OFFSET=<uint32>   CLWRAP_ACCUMULATE=<0..65536>   CLWRAP_ACC_JITTER=<0|1>   (clw_ext_set_accumulate)
+ *   CLWRAP_PROJECTION=<ortho|equirect>   CLWRAP_ORTHO_WIDTH=<float >= 0>   CLWRAP_PANO_SPAN=<h>,<v>   (camera model: clw_ext_set_projection)
  * Tuning / experiment knobs (defaults are the measured optima): CLWRAP_GRID_MIN, CLWRAP_GRID_DENSITY (uniform grid),
  *   CLWRAP_OCC_TILES_PER_DEPTH (deep launches of >= this x depth tiles take the high-occupancy kernel flavour),
  *   CLWRAP_TIMING_EVERY, CLWRAP_VARIANT (bit mask of clw_ext_set_variant).
@@ -390,6 +391,75 @@ int clw_ext_unit_object_stats(cl_wrap* wrap, const uint32_t* ids, const float* d
                               const clw_rect* rect, const uint32_t counts[3], clw_object_stat* out, uint32_t capacity,
                               clw_object_summary* summary);
 #define CLW_TIMING_OBJECTS 0x4F424A53u
+
+/* Camera models beside the pinhole: the orthographic view (parallel rays: the top / front / side views of an editor; size does not depend on
+ * distance) and the equirectangular panorama (a latitude-longitude frame of up to 360 x 180 degrees: the environment map OUT of a tracer that
+ * takes one in).  clw_host_projection_rays is THE definition: it writes the 64-byte records {origin, 0, dir, 0, 0,0,0,0, 0,0,0,0} of the global
+ * ids [id_begin, id_end) of the camera's width x height frame, x = id % width, y = id / width, and returns 1 -- or 0, writing nothing, for what it
+ * refuses.  Every ray is a few float32 operations, one rounding each, no fused operation, IEEE square root and divide, on terms the host resolves
+ * once per (camera, frame, projection); the device (csrc/whitted_projection.inc) performs the same operations on the same terms and equals it bit for bit.
+ *   axis a: `axis`, or -- all zero -- the centre of the camera's image plane relative to its origin, im_corner + right (w_factor W / 2) - up
+ *     (h_factor H / 2) [double, rounded to float]; normalised once: a / sqrtf(a.a) [float32].
+ *   CLW_PROJ_PERSPECTIVE: the pinhole of raygen.cl:13-21 -- direction normalize(v), v = im_corner + right w_factor x - up h_factor y [float32, in
+ *     that order], origin the camera's.
+ *   CLW_PROJ_ORTHO: every ray has direction a; the origin of pixel (x, y) is the camera origin + v, v as above: the image plane is the near plane.
+ *     ortho_width > 0 first rescales the plane about its centre so that the frame's width, |right| w_factor W, spans that many world units:
+ *     w_factor and h_factor times s = ortho_width / (|right| |w_factor| W), im_corner moved accordingly [double, each stored to float].
+ *   CLW_PROJ_EQUIRECT: pixel centres are sampled -- longitude theta(x) = ((x + 1/2) / W - 1/2) h_span, latitude phi(y) = (1/2 - (y + 1/2) / H)
+ *     v_span, evaluated as (2x + 1 - W) / 2W and (H - 1 - 2y) / 2H so that mirrored columns and rows get exactly opposite angles -- and the
+ *     direction is cos(phi) (sin(theta) r + cos(theta) a) + sin(phi) u, r and u the camera's right and up made orthonormal to a (Gram-Schmidt:
+ *     r first, then u against both).  All of this in double, in clw_host_projection_tables, which fills a column table of W float4
+ *     {sin(theta) r + cos(theta) a, 0} and a row table of H float4 {cos(phi), sin(phi) u}; the ray is normalize(col[x].xyz * row[y].x +
+ *     row[y].yzw) [float32, multiply then add], its origin the camera's.  Returns 1, or 0 for what is refused and for the other two models.
+ * Refused: a NULL pointer, an empty frame, ids outside it, an unknown model, reserved != 0, an ortho_width that is not finite or negative, a span
+ * that is not finite, negative or above 360 / 180 (every field is checked whatever the model), an axis or a camera value that is not finite, a
+ * zero axis when the camera's own centre direction is zero too (shorter than 1e-6 of the image plane's half diagonal: what float32 rounding leaves
+ * of a plane centred on the origin is no direction; or a normalised to something not finite), ORTHO with ortho_width > 0 over a camera
+ * of zero `right` or w_factor, EQUIRECT with a `right` parallel to the axis or an `up` in the plane of both. */
+enum { CLW_PROJ_PERSPECTIVE = 0, CLW_PROJ_ORTHO = 1, CLW_PROJ_EQUIRECT = 2 };
+typedef struct clw_projection {      /* 32 bytes */
+    uint32_t model;
+    float axis[3];        /* view direction; all zero = the direction from the camera origin to the centre of its image plane */
+    float ortho_width;    /* ORTHO: world units the frame's width spans; 0 = the camera's own image plane as it stands */
+    float h_span, v_span; /* EQUIRECT: degrees covered, (0, 360] and (0, 180]; 0 = 360 / 180 */
+    uint32_t reserved;    /* 0 */
+} clw_projection;
+/* (the camera structure is declared further down with its helper; a declaration of the tag is enough here) */
+struct clw_camera;
+int clw_host_projection_rays(const struct clw_camera* cam, const clw_projection* proj, uint64_t id_begin, uint64_t id_end, float* rays16);
+int clw_host_projection_tables(const struct clw_camera* cam, const clw_projection* proj, float* col4 /* 4 W floats */, float* row4 /* 4 H floats */);
+/* The convenience most callers want: an orthographic view from `origin` along `look` (need not be normalised) whose frame's width spans
+ * `view_width` world units.  The camera has `right` and `up` as clw_host_perspective builds them, the image plane THROUGH the origin, square
+ * pixels and w_factor = h_factor = view_width / width; the projection has axis = look / |look| and ortho_width = view_width (`right` is not unit
+ * when `look` leaves the horizontal: the rescaling above makes the span hold whatever its length).  Returns 0 for a NULL pointer, an empty frame,
+ * a look that is zero, not finite or vertical, a view_width that is not finite or not positive, else 1. */
+int clw_host_ortho_camera(const float origin[3], const float look[3], float view_width, uint32_t width, uint32_t height, struct clw_camera* cam,
+                          clw_projection* proj);
+/* The model of the wrapper's launches and inspection passes; NULL or model CLW_PROJ_PERSPECTIVE = the pinhole, the default (then nothing here
+ * applies and every launch is what it was).  Env CLWRAP_PROJECTION=ortho|equirect, CLWRAP_ORTHO_WIDTH=<float >= 0>, CLWRAP_PANO_SPAN=<h>,<v>:
+ * with them the unchanged raypng / rayinteractive drivers render a plan view or a panorama.  With a model set:
+ *   - the raygen launch latches its eight arguments as ever; the trace launch -- or a read of the ray buffer -- materialises the records of the
+ *     model with wt_raygen_proj (logged under the raygen kernel's id in clw_ext_timing_get), and the trace runs the ray-buffer flavour (WT_F_RAYS in
+ *     clw_ext_last_trace_flags) it would run for a caller's ray buffer, with the ids, width, height and bands of the generating launch.  It is NEVER
+ *     fused, and it takes no direction for unit: the frame is bit for bit the frame of the same records uploaded by a caller;
+ *   - the records stay valid while the latched values, the range and the projection do not change: a still view generates them once.  The two
+ *     tables of a panorama belong to the wrapper and are rebuilt only when the camera's right or up, the frame size, the axis or a span changes;
+ *   - rays a caller wrote (the buffer's pointer handed out, clw_ext_device_ptr) are traced as written, as without a model;
+ *   - the primary-hit pass and everything built on it -- clw_ext_render_gbuffer, clw_ext_pick, clw_ext_render_overlay, clw_ext_object_stats -- see
+ *     the model's rays where they see the pinhole's (depth is the distance along the unit direction from the ray's origin: for ORTHO, from the
+ *     image plane); they return 0 when the projection cannot be resolved for the latched camera;
+ *   - the pipelined read-back of cl_wrap_output declines.
+ * Errors (print + exit(1)): at the call or at cl_wrap_init, a field the definition refuses whatever the camera; at the trace launch, a projection
+ * that cannot be resolved for the latched camera, and the modes that need the fused launch: supersampling, a lens or a table of sample cameras,
+ * moving spheres, adaptive supersampling, frame accumulation.
+ * Not built: a fused projected trace flavour (the cost of the ray buffer's round trip is measured in DESIGN.md), and with it the modes above. */
+void clw_ext_set_projection(cl_wrap* wrap, const clw_projection* proj);
+void clw_ext_get_projection(const cl_wrap* wrap, clw_projection* out);
+/* Test seam: runs wt_raygen_proj for the ids [id_begin, id_end) of a synthetic camera's frame into a scratch buffer and reads the records back
+ * into `out_rays` (16 floats each).  Needs no scene.  Returns 1, or 0 -- nothing launched, `out_rays` untouched -- when refused as
+ * clw_host_projection_rays refuses, and for CLW_PROJ_PERSPECTIVE (whose kernel is wt_raygen).  Waits; not logged in the timing log. */
+int clw_ext_unit_projection(cl_wrap* wrap, const struct clw_camera* cam, const clw_projection* proj, uint64_t id_begin, uint64_t id_end,
+                            float* out_rays);
 
 /* Work counters of the trace kernel.  enable=1 selects the counting build of the kernel
  * for subsequent launches (slower); read returns and clears
