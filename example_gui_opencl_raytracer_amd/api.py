@@ -51,6 +51,8 @@ SYMBOLS = [
     "clw_host_object_stats", "clw_host_merge_object_stats", "clw_ext_object_stats", "clw_ext_unit_object_stats",
     "clw_host_projection_rays", "clw_host_projection_tables", "clw_host_ortho_camera",
     "clw_ext_set_projection", "clw_ext_get_projection", "clw_ext_unit_projection",
+    "clw_host_ao_dirs", "clw_host_ao_open", "clw_host_ao_resolve", "clw_ext_render_ao", "clw_ext_read_ao", "clw_ext_ao_device_ptr",
+    "clw_ext_unit_ao_open", "clw_ext_unit_ao_resolve",
 ]
 
 # the channels of the primary-hit pass (hip_wrap_ext.h: CLW_GB_*), the id of a miss and the pass's id in the timing log
@@ -73,6 +75,12 @@ TIMING_OBJECTS = 0x4F424A53
 # the camera models (hip_wrap_ext.h: CLW_PROJ_*)
 PROJ_PERSPECTIVE, PROJ_ORTHO, PROJ_EQUIRECT = 0, 1, 2
 PROJ_MODELS = {"perspective": PROJ_PERSPECTIVE, "ortho": PROJ_ORTHO, "equirect": PROJ_EQUIRECT}
+
+# ambient occlusion (hip_wrap_ext.h: CLW_AO_*): the flags of a clw_ao, what clw_ext_read_ao reads, and the two kernels' ids in the timing log
+AO_FILTER, AO_COMPOSE = 1, 2
+AO_FRAME, AO_COUNTS = 0, 1
+TIMING_AO = 0x414F5452
+TIMING_AO_RESOLVE = 0x414F5253
 
 
 def id_kind(ids):
@@ -130,6 +138,11 @@ class clw_overlay(C.Structure):
     """The style of a selection overlay (24 bytes): what to draw (OV_* bits), the outline's width and the three colours, 0x00RRGGBB."""
     _fields_ = [("flags", C.c_uint32), ("radius", C.c_uint32), ("outline_rgb", C.c_uint32), ("fill_rgb", C.c_uint32), ("fill_alpha", C.c_uint32),
                 ("edge_rgb", C.c_uint32)]
+
+
+class clw_ao(C.Structure):
+    """The parameters of an ambient occlusion pass (16 bytes): AO_* flags, rays per pixel (1..32), the rays' length, strength 0..256."""
+    _fields_ = [("flags", C.c_uint32), ("rays", C.c_uint32), ("radius", C.c_float), ("strength", C.c_uint32)]
 
 
 class clw_rect(C.Structure):
@@ -292,6 +305,24 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         L.clw_ext_get_projection.argtypes = [W, PR]
         L.clw_ext_unit_projection.argtypes = [W, CM, PR, C.c_uint64, C.c_uint64, vp]
         L.clw_ext_unit_projection.restype = C.c_int
+    if hasattr(L, "clw_ext_render_ao") or not os.environ.get("CLWRAP_LIB"):               # (an older A/B build may lack them)
+        AO = C.POINTER(clw_ao)
+        L.clw_host_ao_dirs.argtypes = [u32, vp]
+        L.clw_host_ao_dirs.restype = C.c_int
+        L.clw_host_ao_open.argtypes = [vp, vp, vp, u32, u32, u32, vp, u32, vp, u32, AO, vp, vp]
+        L.clw_host_ao_open.restype = C.c_int
+        L.clw_host_ao_resolve.argtypes = [vp, vp, vp, u32, u32, AO, vp]
+        L.clw_host_ao_resolve.restype = C.c_int
+        L.clw_ext_render_ao.argtypes = [W, AO]
+        L.clw_ext_render_ao.restype = u32
+        L.clw_ext_read_ao.argtypes = [W, u32, vp, u32]
+        L.clw_ext_read_ao.restype = u32
+        L.clw_ext_ao_device_ptr.argtypes = [W, u32]
+        L.clw_ext_ao_device_ptr.restype = vp
+        L.clw_ext_unit_ao_open.argtypes = [W, vp, vp, vp, u32, u32, u32, AO, vp]
+        L.clw_ext_unit_ao_open.restype = u32
+        L.clw_ext_unit_ao_resolve.argtypes = [W, vp, vp, vp, u32, u32, AO, vp]
+        L.clw_ext_unit_ao_resolve.restype = u32
     L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
     L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
     L.clw_ext_read_tile_costs.restype = u32
@@ -412,6 +443,56 @@ def overlay(frame, ids, width: int, rows: int, style: clw_overlay, sel) -> np.nd
     out = np.empty(width * rows, np.uint32)
     if not load_library().clw_host_overlay(_ptr(frame), _ptr(ids), width, rows, C.byref(style), _ptr(sel) if sel.size else None, sel.size, _ptr(out)):
         raise ValueError("clw_host_overlay rejects this style or selection (flags in 1..7, radius in 1..4, alpha in 0..256, at most 64 ids)")
+    return out
+
+
+def ao_params(rays: int = 8, radius: float = 1.0, strength: int = 256, filter: bool = True, compose: bool = False) -> clw_ao:
+    """A clw_ao from its values (nothing is checked here: the library refuses what hip_wrap_ext.h says it refuses)."""
+    return clw_ao((AO_FILTER if filter else 0) | (AO_COMPOSE if compose else 0), int(rays), float(radius), int(strength))
+
+
+def ao_dirs(rays: int) -> np.ndarray:
+    """clw_host_ao_dirs: the direction table of K rays per pixel -> float32 [16, K, 4] (pattern, ray, {x, y, z, 0})."""
+    out = np.empty((16, max(int(rays), 0), 4), np.float32)
+    if not 0 <= int(rays) < 2 ** 32 or not load_library().clw_host_ao_dirs(int(rays), _ptr(out)):
+        raise ValueError("clw_host_ao_dirs rejects this number of rays (1..32)")
+    return out
+
+
+def ao_open(point, normal, ids, width: int, rows: int, first_row: int, spheres, planes, ao: clw_ao, dirs=None) -> np.ndarray:
+    """clw_host_ao_open: the open rays of every pixel of a range of whole rows, on the host -- THE definition the device pass is held to ->
+    uint8 [width * rows].  point, normal: float32 [n, 3]; ids: uint32 [n]; spheres, planes: the scene's record arrays (or None)."""
+    width, rows = int(width), int(rows)
+    point = np.ascontiguousarray(point, np.float32).reshape(-1)
+    normal = np.ascontiguousarray(normal, np.float32).reshape(-1)
+    ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+    if width <= 0 or rows <= 0 or ids.size != width * rows or point.size != 3 * ids.size or normal.size != 3 * ids.size:
+        raise ValueError("clw_host_ao_open rejects these arguments (point and normal of 3, ids of 1 entry per pixel of width * rows)")
+    if dirs is None:
+        dirs = ao_dirs(ao.rays)
+    dirs = np.ascontiguousarray(dirs, np.float32)
+    ns, np_ = (0 if spheres is None else len(spheres)), (0 if planes is None else len(planes))
+    out = np.empty(ids.size, np.uint8)
+    if dirs.size != 64 * ao.rays or not load_library().clw_host_ao_open(_ptr(point), _ptr(normal), _ptr(ids), width, rows, int(first_row),
+                                                                        _ptr(spheres) if ns else None, ns, _ptr(planes) if np_ else None, np_,
+                                                                        C.byref(ao), _ptr(dirs), _ptr(out)):
+        raise ValueError("clw_host_ao_open rejects these parameters (rays in 1..32, radius > 0, strength in 0..256, known flags)")
+    return out
+
+
+def ao_resolve(open_u8, ids, frame, width: int, rows: int, ao: clw_ao) -> np.ndarray:
+    """clw_host_ao_resolve: open-ray counts -> packed pixels, on the host -- THE definition the device pass is held to -> uint32 [width * rows].
+    `frame` (read with AO_COMPOSE only) may be None without it."""
+    width, rows = int(width), int(rows)
+    open_u8 = np.ascontiguousarray(open_u8, np.uint8).reshape(-1)
+    ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+    if frame is not None:
+        frame = np.ascontiguousarray(frame, np.uint32).reshape(-1)
+    if width <= 0 or rows <= 0 or open_u8.size != width * rows or ids.size != width * rows or (frame is not None and frame.size != width * rows):
+        raise ValueError("clw_host_ao_resolve rejects these arguments (counts, ids and frame of width * rows entries each)")
+    out = np.empty(width * rows, np.uint32)
+    if not load_library().clw_host_ao_resolve(_ptr(open_u8), _ptr(ids), _ptr(frame), width, rows, C.byref(ao), _ptr(out)):
+        raise ValueError("clw_host_ao_resolve rejects these parameters (rays in 1..32, radius > 0, strength in 0..256, known flags, a frame with AO_COMPOSE)")
     return out
 
 
@@ -779,6 +860,44 @@ class ClWrap:
         return _object_table(lambda out, cap, s: self.L.clw_ext_unit_object_stats(C.byref(self.w), _ptr(ids), _ptr(depth), int(width), int(rows), int(first_row),
                                                                                   _rect(rect), _ptr(counts), out, cap, s),
                              first_capacity=max(1024, min(ids.size, int(counts.astype(np.uint64).sum()) + 1)))
+
+    def render_ao(self, ao: clw_ao) -> int:
+        """clw_ext_render_ao: trace and resolve the ambient occlusion of the wrapper's range on the device -> work-items (0 = refused, nothing launched)."""
+        return int(self.L.clw_ext_render_ao(C.byref(self.w), C.byref(ao)))
+
+    def read_ao(self, what: int = AO_FRAME) -> np.ndarray:
+        """What the last render_ao left: AO_FRAME -> uint32 [n], AO_COUNTS -> uint8 [n]; empty before the first."""
+        dtype = np.uint8 if what == AO_COUNTS else np.uint32
+        nbytes = int(self.L.clw_ext_read_ao(C.byref(self.w), int(what), None, 0))
+        out = np.empty(nbytes // np.dtype(dtype).itemsize, dtype)
+        if nbytes:
+            assert self.L.clw_ext_read_ao(C.byref(self.w), int(what), _ptr(out), nbytes) == nbytes
+        return out
+
+    def ao_device_ptr(self, what: int = AO_FRAME):
+        """Device address of the frame or the counts of the last render_ao (None before the first)."""
+        return self.L.clw_ext_ao_device_ptr(C.byref(self.w), int(what))
+
+    def unit_ao_open(self, point, normal, ids, width: int, rows: int, first_row: int, ao: clw_ao):
+        """clw_ext_unit_ao_open: wt_ao_trace on synthetic channels against the bound scene -> uint8 [width * rows], or None when it is refused."""
+        point = np.ascontiguousarray(point, np.float32).reshape(-1)
+        normal = np.ascontiguousarray(normal, np.float32).reshape(-1)
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        assert ids.size == int(width) * int(rows) and point.size == normal.size == 3 * ids.size
+        out = np.empty(ids.size, np.uint8)
+        n = self.L.clw_ext_unit_ao_open(C.byref(self.w), _ptr(point), _ptr(normal), _ptr(ids), int(width), int(rows), int(first_row), C.byref(ao), _ptr(out))
+        return out if n == ids.size and n else None
+
+    def unit_ao_resolve(self, open_u8, ids, frame, width: int, rows: int, ao: clw_ao):
+        """clw_ext_unit_ao_resolve: wt_ao_resolve on synthetic counts, ids and frame (or None) -> uint32 [width * rows], or None when it is refused."""
+        open_u8 = np.ascontiguousarray(open_u8, np.uint8).reshape(-1)
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        if frame is not None:
+            frame = np.ascontiguousarray(frame, np.uint32).reshape(-1)
+        assert open_u8.size == int(width) * int(rows) == ids.size
+        out = np.empty(ids.size, np.uint32)
+        n = self.L.clw_ext_unit_ao_resolve(C.byref(self.w), _ptr(open_u8), _ptr(ids), _ptr(frame), int(width), int(rows), C.byref(ao), _ptr(out))
+        return out if n == ids.size and n else None
 
     def set_projection(self, proj: clw_projection | None):
         """clw_ext_set_projection: the camera model of the following launches and inspection passes; None = the pinhole."""

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/hip_wrap_ext.h"
+#include "ao_host.h"
 #include "launch_plan.h"
 #include "objects_host.h"
 #include "overlay_host.h"
@@ -48,6 +49,10 @@ extern "C" hipError_t wt_fast_launch_overlay(const unsigned*, const unsigned*, u
 extern "C" hipError_t wt_strict_launch_overlay(const unsigned*, const unsigned*, unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, unsigned, hipStream_t);
 extern "C" hipError_t wt_fast_launch_objects(const unsigned*, const unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, void*, void*, hipStream_t);
 extern "C" hipError_t wt_strict_launch_objects(const unsigned*, const unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, void*, void*, hipStream_t);
+extern "C" hipError_t wt_fast_launch_ao_trace(const whitted_params*, int, const float*, const float*, const unsigned*, const float*, unsigned char*, unsigned, unsigned, unsigned, unsigned, float, hipStream_t);
+extern "C" hipError_t wt_strict_launch_ao_trace(const whitted_params*, int, const float*, const float*, const unsigned*, const float*, unsigned char*, unsigned, unsigned, unsigned, unsigned, float, hipStream_t);
+extern "C" hipError_t wt_fast_launch_ao_resolve(const unsigned char*, const unsigned*, const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
+extern "C" hipError_t wt_strict_launch_ao_resolve(const unsigned char*, const unsigned*, const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
 extern "C" hipError_t wt_fast_launch_cams(const wt_cam_table*, float*, hipStream_t);
 extern "C" hipError_t wt_fast_launch_classify(const unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned char*, unsigned*, unsigned*, unsigned, hipStream_t);
 extern "C" hipError_t wt_fast_launch_sched(const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
@@ -258,6 +263,20 @@ struct Impl {
             ids = nullptr; depth = nullptr; table = result = nullptr; n = 0; slots = 0;
         }
     } obj;
+    /* ambient occlusion (clw_ext_render_ao; whitted_ao.inc): its own point, normal and id buffers -- the primary-hit pass writes them, `gb`, `ov`
+     * and `obj` are not touched --, the open-ray counts and the resolved frame, all sized for the pass's range; `done` as above.  The direction
+     * table (16 x K float4, room for K = 32) is written only when K changes, behind a wait for the passes that read the old one. */
+    struct AO {
+        float* point = nullptr; float* normal = nullptr; uint32_t* ids = nullptr; uint8_t* open = nullptr; uint32_t* frame = nullptr;
+        uint32_t n = 0;                 /* work-items the buffers are sized for */
+        bool written = false;           /* a pass has filled `open` and `frame` */
+        float* dirs = nullptr; uint32_t dirs_K = 0;      /* the table on the device and the K it was built for (0 = none yet) */
+        hipEvent_t done = nullptr;
+        void free_buffers() {
+            for (void* q : {(void*)point, (void*)normal, (void*)ids, (void*)open, (void*)frame}) if (q) (void)hipFree(q);
+            point = normal = nullptr; ids = nullptr; open = nullptr; frame = nullptr; n = 0; written = false;
+        }
+    } ao;
     /* prepared scene cache */
     const Buffer *prep_s = nullptr, *prep_p = nullptr, *prep_l = nullptr;
     uint32_t prep_ns = 0, prep_np = 0, prep_nl = 0;
@@ -1140,6 +1159,44 @@ void launch_overlay(Impl* I, const uint32_t* frame, const uint32_t* ids, uint32_
     t.done();
 }
 
+/* ---- ambient occlusion ------------------------------------------------------------------------------------------------------------ */
+/* the direction table of K rays on the device: built by the definition (clw_host_ao_dirs) and uploaded only when K changes -- then behind a wait
+ * for whatever the launch stream still runs, which may read the old one */
+const float* ao_dirs(Impl* I, uint32_t K) {
+    Impl::AO& O = I->ao;
+    if (O.dirs && O.dirs_K == K) return O.dirs;
+    std::vector<float> tab(4 * (size_t)WT_AO_PATTERNS * K);
+    if (!clw_host_ao_dirs(K, tab.data())) die("Couldn't run the kernel");
+    if (!O.dirs) HIP_OK(hipMalloc((void**)&O.dirs, 4 * sizeof(float) * WT_AO_PATTERNS * WT_AO_MAX_RAYS), "Couldn't allocate device memory");
+    finish(I);
+    if (O.done) (void)hipEventSynchronize(O.done);
+    HIP_OK(hipMemcpy(O.dirs, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+    O.dirs_K = K;
+    return O.dirs;
+}
+
+/* wt_ao_trace over device channels of a width x rows range on the launch stream, the scene as `P` and `flags` bind it (bind_scene); the caller
+ * has checked `ao` and the range (wt_ao_check, wt_ao_range_ok) */
+void launch_ao_trace(Impl* I, const whitted_params& P, int flags, const float* point, const float* normal, const uint32_t* ids, uint32_t width,
+                     uint32_t rows, uint32_t first_row, const clw_ao& ao, uint8_t* open, bool timed) {
+    const float* dirs = ao_dirs(I, ao.rays);
+    LaunchTimer t(I, CLW_TIMING_AO, timed);
+    hipError_t e = (I->strict ? wt_strict_launch_ao_trace : wt_fast_launch_ao_trace)(&P, flags, point, normal, ids, dirs, open, width, rows, first_row,
+                                                                                     ao.rays, ao.radius, I->stream);
+    if (e != hipSuccess) die("Couldn't run the kernel");
+    t.done();
+}
+
+/* wt_ao_resolve likewise.  Integer work compiled into both units; the build in use launches its own copy. */
+void launch_ao_resolve(Impl* I, const uint8_t* open, const uint32_t* ids, const uint32_t* frame, uint32_t* out, uint32_t width, uint32_t rows,
+                       const clw_ao& ao, bool timed) {
+    LaunchTimer t(I, CLW_TIMING_AO_RESOLVE, timed);
+    hipError_t e = (I->strict ? wt_strict_launch_ao_resolve : wt_fast_launch_ao_resolve)(open, ids, frame, out, width, rows, ao.flags, ao.rays, ao.strength,
+                                                                                         I->stream);
+    if (e != hipSuccess) die("Couldn't run the kernel");
+    t.done();
+}
+
 /* ---- the visible-object table ---------------------------------------------------------------------------------------------------- */
 /* The clear of the slot table, wt_objects_reduce and wt_objects_compact over device channels of a width x rows range on the launch stream, then
  * the read-back of the summary and of min(objects, capacity) records; waits.  The caller has checked the arguments (wt_objects_check).  The
@@ -1413,6 +1470,9 @@ void cl_wrap_release(cl_wrap* wrap) {
     I->ov.free_buffers();
     if (I->ov.done) (void)hipEventDestroy(I->ov.done);
     I->obj.free_buffers();
+    I->ao.free_buffers();
+    if (I->ao.dirs) (void)hipFree(I->ao.dirs);
+    if (I->ao.done) (void)hipEventDestroy(I->ao.done);
     I->ptab.free_all();
     I->adapt.free_all();
     if (I->tables_fence) (void)hipEventDestroy(I->tables_fence);
@@ -1913,6 +1973,132 @@ int clw_ext_unit_object_stats(cl_wrap* wrap, const uint32_t* ids, const float* d
     (void)hipFree(dids);
     if (ddepth) (void)hipFree(ddepth);
     return 1;
+}
+
+uint32_t clw_ext_render_ao(cl_wrap* wrap, const clw_ao* ao) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    static_assert(sizeof(clw_ao) == 16, "the pass's ABI");
+    if (!wt_ao_check(ao)) return 0;
+    if (I->band_stride > 1u) return 0;
+    cl_uint kid = 0;
+    while (kid < I->kernels.size() && I->kernels[kid].kind != K_RAYTRACER) kid++;
+    if (kid >= I->kernels.size()) return 0;
+    const bool compose = (ao->flags & CLW_AO_COMPOSE) != 0u;
+    if (compose && !is_registered(wrap, kid, 10)) return 0;
+    whitted_params P{};
+    int flags = 0;
+    size_t dyn_lds = 0;
+    wt_projection T;
+    if (!gbuffer_params(wrap, I, P, flags, dyn_lds, T)) return 0;
+    /* whole rows of one contiguous range: work-item i is pixel (i % width, row_offset + i / width) of the frame */
+    if (P.band_stride > 1u || !P.tiled || P.rows == 0u || !wt_ao_range_ok(P.width, P.rows)) return 0;
+    Buffer* fb = nullptr;
+    if (compose) {
+        fb = (Buffer*)wrap->buffers[kid][10];
+        if (fb->size < (size_t)P.n_items * 4) return 0;
+        ensure_allocated(I, fb);
+    }
+    Impl::AO& O = I->ao;
+    if (O.n != P.n_items) {      /* another range: a pass under way may still use the old buffers */
+        if (O.n) { finish(I); if (O.done) (void)hipEventSynchronize(O.done); }
+        O.free_buffers();
+        HIP_OK(hipMalloc((void**)&O.point, (size_t)P.n_items * 12), "Couldn't allocate device memory");
+        HIP_OK(hipMalloc((void**)&O.normal, (size_t)P.n_items * 12), "Couldn't allocate device memory");
+        HIP_OK(hipMalloc((void**)&O.ids, (size_t)P.n_items * 4), "Couldn't allocate device memory");
+        HIP_OK(hipMalloc((void**)&O.open, (size_t)P.n_items), "Couldn't allocate device memory");
+        HIP_OK(hipMalloc((void**)&O.frame, (size_t)P.n_items * 4), "Couldn't allocate device memory");
+        O.n = P.n_items;
+    }
+    void* chan[5] = {nullptr, O.ids, O.normal, O.point, nullptr};
+    launch_gbuffer(I, P, flags, dyn_lds, chan, T, true);
+    launch_ao_trace(I, P, flags, O.point, O.normal, O.ids, P.width, P.rows, P.row_offset, *ao, O.open, true);
+    launch_ao_resolve(I, O.open, O.ids, compose ? (const uint32_t*)fb->dptr : nullptr, O.frame, P.width, P.rows, *ao, true);
+    if (!O.done) HIP_OK(hipEventCreateWithFlags(&O.done, hipEventDisableTiming), "Couldn't create a timing event");
+    HIP_OK(hipEventRecord(O.done, I->stream), "Couldn't run the kernel");
+    O.written = true;
+    return O.n;
+}
+
+uint32_t clw_ext_read_ao(cl_wrap* wrap, uint32_t what, void* out, uint32_t capacity_bytes) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    const Impl::AO& O = I->ao;
+    if (!O.written || what > 1u) return 0;
+    const uint64_t bytes = (uint64_t)O.n * (what == 0u ? 4u : 1u);      /* (n < 2^30) */
+    if (out && capacity_bytes >= bytes) {
+        hipError_t e = hipEventSynchronize(O.done);
+        if (e != hipSuccess) { printf("%d\n", (int)e); die("The device kernel failed"); }
+        HIP_OK(hipMemcpy(out, what == 0u ? (const void*)O.frame : (const void*)O.open, (size_t)bytes, hipMemcpyDeviceToHost),
+               "Failed to transfer device memory to host");
+    }
+    return (uint32_t)bytes;
+}
+
+void* clw_ext_ao_device_ptr(cl_wrap* wrap, uint32_t what) {
+    const Impl::AO& O = impl_of(wrap)->ao;
+    if (!O.written || what > 1u) return nullptr;
+    return what == 0u ? (void*)O.frame : (void*)O.open;
+}
+
+uint32_t clw_ext_unit_ao_open(cl_wrap* wrap, const float* point, const float* normal, const uint32_t* ids, uint32_t width, uint32_t rows,
+                              uint32_t first_row, const clw_ao* ao, uint8_t* open_u8) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    if (!wt_ao_check(ao) || !wt_ao_range_ok(width, rows) || !point || !normal || !ids || !open_u8) return 0;
+    /* the wrapper's bound scene, as gbuffer_params asks for it */
+    cl_uint kid = 0;
+    while (kid < I->kernels.size() && I->kernels[kid].kind != K_RAYTRACER) kid++;
+    if (kid >= I->kernels.size()) return 0;
+    for (cl_uint a : {1u, 2u, 3u, 8u, 9u}) if (!is_registered(wrap, kid, a)) return 0;
+    for (cl_uint a : {4u, 5u, 6u}) if (!I->kernels[kid].values[a].set) return 0;
+    whitted_params P{};
+    int flags = 0;
+    size_t dyn_lds = 0;
+    bind_scene(wrap, I, kid, P, flags, dyn_lds);
+    const size_t n = (size_t)width * rows;
+    float *dpoint = nullptr, *dnormal = nullptr;
+    uint32_t* dids = nullptr;
+    uint8_t* dopen = nullptr;
+    HIP_OK(hipMalloc((void**)&dpoint, n * 12), "Couldn't allocate device memory");
+    HIP_OK(hipMalloc((void**)&dnormal, n * 12), "Couldn't allocate device memory");
+    HIP_OK(hipMalloc((void**)&dids, n * 4), "Couldn't allocate device memory");
+    HIP_OK(hipMalloc((void**)&dopen, n), "Couldn't allocate device memory");
+    HIP_OK(hipMemcpy(dpoint, point, n * 12, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+    HIP_OK(hipMemcpy(dnormal, normal, n * 12, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+    HIP_OK(hipMemcpy(dids, ids, n * 4, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+    HIP_OK(hipDeviceSynchronize(), "The device kernel failed");
+    launch_ao_trace(I, P, flags, dpoint, dnormal, dids, width, rows, first_row, *ao, dopen, false);
+    finish(I);
+    HIP_OK(hipMemcpy(open_u8, dopen, n, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
+    (void)hipFree(dpoint); (void)hipFree(dnormal); (void)hipFree(dids); (void)hipFree(dopen);
+    return (uint32_t)n;
+}
+
+uint32_t clw_ext_unit_ao_resolve(cl_wrap* wrap, const uint8_t* open_u8, const uint32_t* ids, const uint32_t* frame, uint32_t width, uint32_t rows,
+                                 const clw_ao* ao, uint32_t* out) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    if (!wt_ao_check(ao) || !wt_ao_range_ok(width, rows) || !open_u8 || !ids || !out || ((ao->flags & CLW_AO_COMPOSE) && !frame)) return 0;
+    const size_t n = (size_t)width * rows;
+    uint8_t* dopen = nullptr;
+    uint32_t *dids = nullptr, *dframe = nullptr, *dout = nullptr;
+    HIP_OK(hipMalloc((void**)&dopen, n), "Couldn't allocate device memory");
+    HIP_OK(hipMalloc((void**)&dids, n * 4), "Couldn't allocate device memory");
+    HIP_OK(hipMalloc((void**)&dout, n * 4), "Couldn't allocate device memory");
+    HIP_OK(hipMemcpy(dopen, open_u8, n, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+    HIP_OK(hipMemcpy(dids, ids, n * 4, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+    if (ao->flags & CLW_AO_COMPOSE) {
+        HIP_OK(hipMalloc((void**)&dframe, n * 4), "Couldn't allocate device memory");
+        HIP_OK(hipMemcpy(dframe, frame, n * 4, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
+    }
+    HIP_OK(hipDeviceSynchronize(), "The device kernel failed");
+    launch_ao_resolve(I, dopen, dids, dframe, dout, width, rows, *ao, false);
+    finish(I);
+    HIP_OK(hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
+    (void)hipFree(dopen); (void)hipFree(dids); (void)hipFree(dout);
+    if (dframe) (void)hipFree(dframe);
+    return (uint32_t)n;
 }
 
 void clw_ext_set_pipeline(cl_wrap* wrap, int on) { impl_of(wrap)->pipeline = on ? 1 : 0; }

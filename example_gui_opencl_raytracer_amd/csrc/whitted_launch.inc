@@ -1,11 +1,12 @@
 /* whitted_launch.inc -- instantiates the kernels of whitted_trace.inc (and the primary-hit pass of whitted_gbuffer.inc, built from its
- * pieces, the camera models of whitted_projection.inc, the selection overlay of whitted_overlay.inc and the visible-object table of
- * whitted_objects.inc) in namespace WT_NS and exports
+ * pieces, the camera models of whitted_projection.inc, the ambient occlusion pass of whitted_ao.inc, the selection overlay of
+ * whitted_overlay.inc and the visible-object table of whitted_objects.inc) in namespace WT_NS and exports
  * the C launchers the shim calls. */
 namespace WT_NS {
 #include "whitted_trace.inc"
 #include "whitted_gbuffer.inc"
 #include "whitted_projection.inc"
+#include "whitted_ao.inc"
 #include "whitted_overlay.inc"
 #include "whitted_objects.inc"
 }
@@ -231,5 +232,52 @@ extern "C" hipError_t WT_LAUNCH_OBJECTS(const unsigned* ids, const unsigned* dep
     unsigned* summary = (unsigned*)result;
     hipLaunchKernelGGL(WT_NS::wt_objects_compact, dim3(1), dim3(WT_OBJ_CHUNK), 0, s, head, slots, (unsigned)nslots, counts[0], counts[1], counts[2],
                        depth ? 1u : 0u, summary, (WT_NS::wt_obj_record*)(summary + 4));
+    return hipGetLastError();
+}
+
+/* ambient occlusion (whitted_ao.inc).  wt_ao_trace over the planar point / normal / id channels of a width x rows range whose first row is row
+ * `first_row` of the frame: one workgroup of one wave per 8 x 8 tile, geometry as bind_scene chose it (flags as WT_LAUNCH_GBUFFER), `dirs` = the
+ * 16 x K float4 of clw_host_ao_dirs on the device, staged in LDS behind the geometry; `open` receives a byte per pixel.  The caller has checked
+ * K, radius and the range (csrc/ao_host.h: wt_ao_check, wt_ao_range_ok) */
+#if WT_STRICT
+#define WT_LAUNCH_AO_TRACE wt_strict_launch_ao_trace
+#define WT_LAUNCH_AO_RESOLVE wt_strict_launch_ao_resolve
+#else
+#define WT_LAUNCH_AO_TRACE wt_fast_launch_ao_trace
+#define WT_LAUNCH_AO_RESOLVE wt_fast_launch_ao_resolve
+#endif
+extern "C" hipError_t WT_LAUNCH_AO_TRACE(const whitted_params* P, int flags, const float* point, const float* normal, const unsigned* ids,
+                                         const float* dirs, unsigned char* open, unsigned width, unsigned rows, unsigned first_row, unsigned K,
+                                         float radius, hipStream_t s) {
+    const unsigned long long tpr = (width + 7ull) / 8ull, trows = (rows + 7ull) / 8ull;
+    if (width == 0u || rows == 0u || (unsigned long long)width * rows >= (1ull << 30) || K < 1u || K > 32u || !(radius > 0.0f) || !point || !normal ||
+        !ids || !dirs || !open)
+        return hipErrorInvalidValue;
+    const bool lds = !(flags & WT_F_GRID) && (flags & WT_F_GEOM_LDS);
+    const size_t dyn_lds = ((lds ? (size_t)P->geom_f4 : 0u) + 16u * (size_t)K) * sizeof(float4);
+    if (dyn_lds > 48u * 1024u) return hipErrorInvalidValue;
+    WT_NS::wt_ao_args A = {};
+    A.point = point; A.normal = normal; A.ids = ids; A.dirs = (const float4*)dirs; A.open = open;
+    A.width = width; A.rows = rows; A.first_row = first_row; A.tiles_per_row = (unsigned)tpr; A.K = K; A.radius = radius;
+    const dim3 g((unsigned)(tpr * trows)), block(WT_BLOCK);
+    if (flags & WT_F_GRID) hipLaunchKernelGGL((WT_NS::wt_ao_trace<false, true>), g, block, dyn_lds, s, *P, A);
+    else if (lds) hipLaunchKernelGGL((WT_NS::wt_ao_trace<true, false>), g, block, dyn_lds, s, *P, A);
+    else hipLaunchKernelGGL((WT_NS::wt_ao_trace<false, false>), g, block, dyn_lds, s, *P, A);
+    return hipGetLastError();
+}
+
+/* wt_ao_resolve over a width x rows range: one workgroup per tile of 32 x 8 pixels; ao_flags = CLW_AO_* bits (`frame` is read with COMPOSE only) */
+extern "C" hipError_t WT_LAUNCH_AO_RESOLVE(const unsigned char* open, const unsigned* ids, const unsigned* frame, unsigned* out, unsigned width,
+                                           unsigned rows, unsigned ao_flags, unsigned K, unsigned strength, hipStream_t s) {
+    const unsigned long long tpr = (width + (WT_AO_TILE_W - 1ull)) / WT_AO_TILE_W, trows = (rows + (WT_AO_TILE_H - 1ull)) / WT_AO_TILE_H;
+    if (width == 0u || rows == 0u || (unsigned long long)width * rows >= (1ull << 30) || K < 1u || K > 32u || strength > 256u || (ao_flags & ~3u) ||
+        !open || !ids || !out || ((ao_flags & WT_AO_COMPOSE) && !frame))
+        return hipErrorInvalidValue;
+    WT_NS::wt_ao_resolve_args A = {};
+    A.open = open; A.ids = ids; A.frame = frame; A.out = out; A.width = width; A.rows = rows; A.tiles_per_row = (unsigned)tpr;
+    A.K = K; A.strength = strength; A.compose = (ao_flags & WT_AO_COMPOSE) ? 1u : 0u;
+    const dim3 g((unsigned)(tpr * trows)), block(WT_AO_TILE_W * WT_AO_TILE_H);
+    if (ao_flags & WT_AO_FILTER) hipLaunchKernelGGL(WT_NS::wt_ao_resolve<true>, g, block, 0, s, A);
+    else hipLaunchKernelGGL(WT_NS::wt_ao_resolve<false>, g, block, 0, s, A);
     return hipGetLastError();
 }

@@ -41,6 +41,12 @@ and they leave an accumulating view counting.
 frame and an id pass where they lie.  It never writes the traced frame, leaves ``gbuffer()``'s buffers and an accumulating view alone, and is
 not available with row bands.  A strip is composed on its own rows: within ``radius`` rows of its edges it can differ from the full frame's.
 
+``ambient_occlusion(rays, radius, ...)`` / ``ao_counts()``: ray-traced ambient occlusion (clw_ext_render_ao) -- the "clay" view: every visible
+point shaded by how much of the hemisphere above it is open within ``radius``, from ``rays`` short any-hit rays per pixel traced on the device
+over a primary-hit pass; or, with ``compose=True``, the frame of the last ``render()`` multiplied by it.  It never writes the traced frame, leaves
+``gbuffer()``'s buffers, the overlay, the object table and an accumulating view alone, honours the camera model, and is not available with row
+bands.  Strips' counts concatenate to the frame's; the filter runs on a strip's own rows.
+
 ``projection=...`` / ``set_projection(model, ...)`` / ``look_ortho`` / ``look_panorama``: the camera models beside the pinhole
 (clw_ext_set_projection) -- ``'ortho'``: parallel rays from the image plane, the top / front / side view of an editor; ``'equirect'``: a
 latitude-longitude panorama of up to 360 x 180 degrees around the camera origin.  ``render()``, ``read_rays()``, ``gbuffer()``, ``pick``,
@@ -260,6 +266,27 @@ class Renderer:
             raise RuntimeError("the selection overlay was refused (a camera set and a frame rendered? at most 64 ids, radius in 1..4, alpha in "
                                "0..256, something to draw, no row bands?)")
         return self.w.read_overlay()
+
+    # ---- ambient occlusion
+    def ambient_occlusion(self, rays: int = 8, radius: float = 1.0, strength: int = 256, filter: bool = True, compose: bool = False) -> np.ndarray:
+        """The view shaded by geometry alone -> uint32 [rows, width], grey 0x00VVVVVV: `rays` (1..32) short any-hit rays of length `radius` (world
+        units; inf = unlimited) over the hemisphere of every visible point's normal, traced on the device from a primary-hit pass; `strength`
+        (0..256) scales how much of the occlusion shows; `filter` averages the 4 x 4 interleaved ray patterns away among pixels of the same
+        object; `compose` multiplies the frame of the last ``render()`` by the result instead."""
+        ao = api.ao_params(rays, radius, strength, filter, compose)
+        if self._camera_set:
+            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        if self.w.render_ao(ao) != self.pixels:
+            raise RuntimeError("the ambient occlusion pass was refused (a camera set? rays in 1..32, radius > 0, strength in 0..256, no row bands, "
+                               "with compose a frame rendered?)")
+        return self.w.read_ao(api.AO_FRAME).reshape(self.rows, self.width)
+
+    def ao_counts(self) -> np.ndarray:
+        """The open rays (0..rays) of every pixel in the last ``ambient_occlusion()`` -> uint8 [rows, width]."""
+        counts = self.w.read_ao(api.AO_COUNTS)
+        if counts.size != self.pixels:
+            raise RuntimeError("no ambient occlusion pass has run on this renderer's range yet")
+        return counts.reshape(self.rows, self.width)
 
     # ---- the visible-object table
     def objects(self, rect=None) -> np.ndarray:

@@ -461,6 +461,88 @@ void clw_ext_get_projection(const cl_wrap* wrap, clw_projection* out);
 int clw_ext_unit_projection(cl_wrap* wrap, const struct clw_camera* cam, const clw_projection* proj, uint64_t id_begin, uint64_t id_end,
                             float* out_rays);
 
+/* Ray-traced ambient occlusion: the view shaded by geometry alone (the "clay" view of an editor) -- how much of the hemisphere above every
+ * visible point is open within `radius` -- traced on the device from the point, normal and id channels of the primary-hit pass: K short any-hit
+ * rays per pixel against the spheres and planes of the scene.  All of its arithmetic is defined here, on the host: clw_host_ao_dirs,
+ * clw_host_ao_open and clw_host_ao_resolve are THE definition, and the device pass (wt_ao_trace, wt_ao_resolve: csrc/whitted_ao.inc) equals
+ * them bit for bit in both builds.  float32 operations are rounded once each, never fused; square root and divide are IEEE.
+ * (a) clw_host_ao_dirs: the direction table, indexed [j][i], pattern j = 0..15, ray i = 0..K-1; the only trigonometry and the only double
+ *     arithmetic of the feature.  In double: u1 = (i + (j + 0.5) / 16) / K; u2 = frac(i * 0.6180339887498949 + rev4(j) / 16), rev4 = the 4-bit
+ *     reversal of j; l = (sqrt(u1) cos(2 pi u2), sqrt(u1) sin(2 pi u2), sqrt(1 - u1)), each component rounded once to float, w = 0.
+ *     Cosine-weighted (the open fraction IS the estimate), stratified in elevation per pixel, rotated and jittered across the 16 patterns of a
+ *     4 x 4 block of pixels; l.z >= sqrt(0.03125 / K) > 0.
+ * (b) clw_host_ao_open: point and normal (3 floats per pixel) and ids (CLW_GB_ID words), planar, of a range of `rows` whole rows whose first
+ *     row is row `first_row` of the frame; spheres / planes = the 96-byte records of the scene arrays, read through the prepared words
+ *     {centre, +-r * r} and {n}, {p0} the device reads.  For pixel (x, y) of the range, p = y * width + x:
+ *       - ids[p] is neither a sphere (kind 0, index < ns) nor a plane (kind 1, index < np) -- the sky, a light, any other word: open[p] = K;
+ *       - else o = point[p] (the EPSILON-offset point) and n = normal[p] as stored (a plane's normal is not flipped toward the viewer, as in
+ *         the reference's shading), and the branchless orthonormal basis, every operation left to right:
+ *           sg = copysignf(1, n.z); a = -1 / (sg + n.z); b = n.x * n.y * a;
+ *           t = (1 + sg * n.x * n.x * a, sg * b, -sg * n.x); u = (b, sg + n.y * n.y * a, -n.y);
+ *       - pattern j = (x & 3) | ((first_row + y) & 3) << 2; ray i has direction d = t * l.x + u * l.y + n * l.z, l = dirs[j][i], per component
+ *         three products, then two sums left to right; it is NOT normalised;
+ *       - ray i is occluded iff some sphere 0..ns-1 (whatever its material) or some plane 0..np-1 gives hit && t <= radius, with
+ *           sphere {c, q}: A = d.d; v = o - c; C = v.v - |q|; B = v.d; D = B * B + (-(A * C)); s = sqrtf(D); t0 = (-B - s) / A;
+ *                          t = t0 < 0 ? (-B + s) / A : t0; hit = !(D < 0) && !(t <= 0);
+ *           plane {n, p0}: num = (p0 - o).n; B = d.n; t = num / B; hit = !(B == 0) && !(t <= 0);
+ *         (a dot product is x x' + y y' + z z' left to right) -- the primary-hit pass's own evaluation of its winner.  Lights never occlude;
+ *       - open[p] = the number of rays that are not occluded.  The comparisons as written decide a zero or NaN normal: a NaN direction is
+ *         never occluded.
+ * (c) clw_host_ao_resolve, integers only.  W(p) = {p}, or with CLW_AO_FILTER the present pixels q with x - 2 <= qx <= x + 1, y - 2 <= qy <=
+ *     y + 1 and ids[q] == ids[p] (any 4 x 4 window holds every pattern once); S = the sum of open over W(p), m = |W(p)|;
+ *     v = (255 S + (m K >> 1)) / (m K); v' = 255 - (((255 - v) strength + 128) >> 8); out[p] = v' * 0x010101, or with CLW_AO_COMPOSE every
+ *     8-bit channel c of frame[p] & 0xFFFFFF becomes (c v' + 127) / 255.  The top byte is 0.
+ * Refused (0 returned, nothing written), by every function where it applies: a NULL pointer (ns or np > 0 with its array NULL; COMPOSE with a
+ * NULL frame), unknown flag bits, rays outside 1..32, a radius that is NaN or <= 0 (+inf = unlimited is legal), strength > 256, a width or rows
+ * of zero, width * rows not fitting 30 bits. */
+#define CLW_AO_FILTER  1u   /* average the 4x4 interleave pattern away, among pixels of the same id */
+#define CLW_AO_COMPOSE 2u   /* multiply the traced frame by the result instead of showing it as grey */
+typedef struct clw_ao {     /* 16 bytes */
+    uint32_t flags;         /* CLW_AO_FILTER | CLW_AO_COMPOSE; 0 is legal */
+    uint32_t rays;          /* K, 1..32 rays per pixel */
+    float    radius;        /* > 0; +inf = unlimited; NaN, 0 and negative are refused */
+    uint32_t strength;      /* 0..256: how much of the occlusion shows */
+} clw_ao;
+int clw_host_ao_dirs(uint32_t K, float* dirs4 /* 16 * K float4 */);                                         /* 1 = done, 0 = refused */
+int clw_host_ao_open(const float* point, const float* normal, const uint32_t* ids, uint32_t width, uint32_t rows, uint32_t first_row,
+                     const void* spheres, uint32_t ns, const void* planes, uint32_t np, const clw_ao* ao, const float* dirs4,
+                     uint8_t* open_u8);
+int clw_host_ao_resolve(const uint8_t* open_u8, const uint32_t* ids, const uint32_t* frame /* or NULL without COMPOSE */, uint32_t width,
+                        uint32_t rows, const clw_ao* ao, uint32_t* out_u32);
+/* clw_ext_render_ao composes the pass of the wrapper's range on its stream, without waiting: (1) a point + normal + id primary-hit pass over
+ * the range the next trace launch would cover (as clw_ext_render_gbuffer -- every camera model -- into buffers the pass owns); (2) wt_ao_trace
+ * into a u8 count buffer, the scene read as the primary-hit pass reads it (staged in LDS, from global memory, or through the uniform grid);
+ * (3) wt_ao_resolve over the counts, the ids and, with COMPOSE, the raytracer's framebuffer argument (its argument 10) as the last launch left
+ * it, into a packed u32 frame the wrapper owns.  Returns the number of work-items.
+ * Returns 0 -- no launch, and the process goes on -- for what the definition refuses, when no camera is latched or no scene is bound, the
+ * wrapper has row bands, the range is not a whole number of rows, or, with COMPOSE, no framebuffer is registered or it is smaller than the range.
+ * A strip (an id offset of whole rows) is traced with FRAME row numbers, so the strips' counts concatenate to the frame's exactly; it is resolved
+ * on its OWN rows (rows of other strips are absent from a window), as the overlay is.
+ * The traced framebuffer, the buffers of clw_ext_render_gbuffer, the overlay, the object table, an accumulating view, its count and the tile
+ * order are left alone.  The direction table is rebuilt only when K changes; the other buffers are allocated at first use and again when the
+ * range changes; cl_wrap_release frees them.  The primary-hit pass is logged under CLW_TIMING_GBUFFER, wt_ao_trace under CLW_TIMING_AO,
+ * wt_ao_resolve under CLW_TIMING_AO_RESOLVE in clw_ext_timing_get.
+ * Not built: a latched mode in which cl_wrap_output hands the unchanged drivers the AO frame; facing the hemisphere toward the viewer (a plane
+ * seen from behind is shaded by what lies on its normal's side); accumulation of AO over frames. */
+uint32_t clw_ext_render_ao(cl_wrap* wrap, const clw_ao* ao);
+/* What the last clw_ext_render_ao left: what = 0 the frame (u32 per work-item), 1 the open-ray counts (u8 per work-item) -> its size in bytes
+ * (0 = there is none, or `what` is neither); waits for the pass and copies it if `out` is not NULL and `capacity_bytes` suffices. */
+uint32_t clw_ext_read_ao(cl_wrap* wrap, uint32_t what, void* out, uint32_t capacity_bytes);
+/* Its device buffer, for consumers on the device (in the order of the wrapper's stream); NULL before the first pass.  A pass over another
+ * range frees it. */
+void*    clw_ext_ao_device_ptr(cl_wrap* wrap, uint32_t what);
+/* Test seam: uploads synthetic channels and runs the wt_ao_trace instantiation and launch shape clw_ext_render_ao would run for the wrapper's
+ * bound scene, grid setting and variant; reads the counts back into `open_u8`.  Returns width * rows, or 0 -- nothing launched, `open_u8`
+ * untouched -- when refused as clw_host_ao_open refuses or no scene is bound.  Waits; not logged. */
+uint32_t clw_ext_unit_ao_open(cl_wrap* wrap, const float* point, const float* normal, const uint32_t* ids, uint32_t width, uint32_t rows,
+                              uint32_t first_row, const clw_ao* ao, uint8_t* open_u8);
+/* Test seam: wt_ao_resolve over synthetic counts, ids and (with COMPOSE) frame -> `out`.  Needs no scene.  Returns width * rows, or 0 when
+ * refused as clw_host_ao_resolve refuses.  Waits; not logged. */
+uint32_t clw_ext_unit_ao_resolve(cl_wrap* wrap, const uint8_t* open_u8, const uint32_t* ids, const uint32_t* frame, uint32_t width,
+                                 uint32_t rows, const clw_ao* ao, uint32_t* out);
+#define CLW_TIMING_AO         0x414F5452u
+#define CLW_TIMING_AO_RESOLVE 0x414F5253u
+
 /* Work counters of the trace kernel.  enable=1 selects the counting build of the kernel
  * for subsequent launches (slower); read returns and clears
  *   out[0] path segments  out[1] shadow rays  out[2] light probes  out[3] skybox fetches
