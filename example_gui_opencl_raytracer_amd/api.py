@@ -53,6 +53,7 @@ SYMBOLS = [
     "clw_ext_set_projection", "clw_ext_get_projection", "clw_ext_unit_projection",
     "clw_host_ao_dirs", "clw_host_ao_open", "clw_host_ao_resolve", "clw_ext_render_ao", "clw_ext_read_ao", "clw_ext_ao_device_ptr",
     "clw_ext_unit_ao_open", "clw_ext_unit_ao_resolve",
+    "clw_host_cast_rays", "clw_host_occluded_rays", "clw_ext_cast_rays", "clw_ext_occluded_rays", "clw_ext_cast_rays_device",
 ]
 
 # the channels of the primary-hit pass (hip_wrap_ext.h: CLW_GB_*), the id of a miss and the pass's id in the timing log
@@ -81,6 +82,14 @@ AO_FILTER, AO_COMPOSE = 1, 2
 AO_FRAME, AO_COUNTS = 0, 1
 TIMING_AO = 0x414F5452
 TIMING_AO_RESOLVE = 0x414F5253
+
+# ray queries (hip_wrap_ext.h: clw_ray, clw_hit, CLW_CAST_*): a ray and a hit as numpy dtypes (32 bytes each), the kinds a query tests, and
+# the kernel's id in the timing log
+RAY_QUERY = np.dtype([("origin", np.float32, 3), ("tmax", np.float32), ("dir", np.float32, 3), ("ignore", np.uint32)])
+HIT = np.dtype([("t", np.float32), ("id", np.uint32), ("normal", np.float32, 3), ("point", np.float32, 3)])
+CAST_SPHERES, CAST_PLANES, CAST_LIGHTS, CAST_KINDS, CAST_OPAQUE = 1, 2, 4, 7, 8
+CAST_KIND_NAMES = {"sphere": CAST_SPHERES, "plane": CAST_PLANES, "light": CAST_LIGHTS}
+TIMING_CAST = 0x43415354
 
 
 def id_kind(ids):
@@ -143,6 +152,17 @@ class clw_overlay(C.Structure):
 class clw_ao(C.Structure):
     """The parameters of an ambient occlusion pass (16 bytes): AO_* flags, rays per pixel (1..32), the rays' length, strength 0..256."""
     _fields_ = [("flags", C.c_uint32), ("rays", C.c_uint32), ("radius", C.c_float), ("strength", C.c_uint32)]
+
+
+class clw_ray(C.Structure):
+    """A query ray (32 bytes): origin, the largest t it reaches (inf = unlimited), direction (not normalised: t is in units of its length),
+    the id word of the one primitive it does not test (ID_NONE = none)."""
+    _fields_ = [("origin", C.c_float * 3), ("tmax", C.c_float), ("dir", C.c_float * 3), ("ignore", C.c_uint32)]
+
+
+class clw_hit(C.Structure):
+    """What a nearest-hit query answers per ray (32 bytes): t (inf = a miss), the id word (ID_NONE = a miss), the normal and the point."""
+    _fields_ = [("t", C.c_float), ("id", C.c_uint32), ("normal", C.c_float * 3), ("point", C.c_float * 3)]
 
 
 class clw_rect(C.Structure):
@@ -323,6 +343,17 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         L.clw_ext_unit_ao_open.restype = u32
         L.clw_ext_unit_ao_resolve.argtypes = [W, vp, vp, vp, u32, u32, AO, vp]
         L.clw_ext_unit_ao_resolve.restype = u32
+    if hasattr(L, "clw_ext_cast_rays") or not os.environ.get("CLWRAP_LIB"):               # (an older A/B build may lack them)
+        L.clw_host_cast_rays.argtypes = [vp, u32, u32, vp, u32, vp, u32, vp, u32, vp]
+        L.clw_host_cast_rays.restype = C.c_int
+        L.clw_host_occluded_rays.argtypes = [vp, u32, u32, vp, u32, vp, u32, vp, u32, vp]
+        L.clw_host_occluded_rays.restype = C.c_int
+        L.clw_ext_cast_rays.argtypes = [W, vp, u32, u32, vp]
+        L.clw_ext_cast_rays.restype = u32
+        L.clw_ext_occluded_rays.argtypes = [W, vp, u32, u32, vp]
+        L.clw_ext_occluded_rays.restype = u32
+        L.clw_ext_cast_rays_device.argtypes = [W, vp, u32, u32, vp, vp]
+        L.clw_ext_cast_rays_device.restype = u32
     L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
     L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
     L.clw_ext_read_tile_costs.restype = u32
@@ -493,6 +524,53 @@ def ao_resolve(open_u8, ids, frame, width: int, rows: int, ao: clw_ao) -> np.nda
     out = np.empty(width * rows, np.uint32)
     if not load_library().clw_host_ao_resolve(_ptr(open_u8), _ptr(ids), _ptr(frame), width, rows, C.byref(ao), _ptr(out)):
         raise ValueError("clw_host_ao_resolve rejects these parameters (rays in 1..32, radius > 0, strength in 0..256, known flags, a frame with AO_COMPOSE)")
+    return out
+
+
+def cast_flags(kinds=("sphere", "plane"), opaque_only: bool = False) -> int:
+    """The flag word of a ray query from the names of the kinds it tests ('sphere', 'plane', 'light'; or a ready CAST_* mask)."""
+    if isinstance(kinds, (int, np.integer)):
+        flags = int(kinds)
+    else:
+        flags = 0
+        for k in kinds:
+            flags |= CAST_KIND_NAMES[k]
+    return flags | (CAST_OPAQUE if opaque_only else 0)
+
+
+def make_rays(origins, dirs, tmax=np.inf, ignore=None) -> np.ndarray:
+    """RAY_QUERY [n] from origins and dirs of [n, 3]; tmax and ignore (id words; None = ID_NONE) are scalar or per ray."""
+    origins = np.asarray(origins, np.float32).reshape(-1, 3)
+    rays = np.empty(origins.shape[0], RAY_QUERY)
+    rays["origin"] = origins
+    rays["dir"] = np.asarray(dirs, np.float32).reshape(-1, 3)
+    rays["tmax"] = np.asarray(tmax, np.float32)
+    rays["ignore"] = ID_NONE if ignore is None else np.asarray(ignore, np.uint32)
+    return rays
+
+
+def _cast_args(rays, spheres, planes, lights):
+    rays = np.ascontiguousarray(rays, RAY_QUERY).reshape(-1)
+    arrs = [None if a is None else np.ascontiguousarray(a) for a in (spheres, planes, lights)]
+    counts = [0 if a is None else int(a.shape[0]) for a in arrs]
+    return rays, arrs, counts
+
+
+def cast_rays_host(rays, flags: int, spheres, planes, lights=None) -> np.ndarray:
+    """clw_host_cast_rays: the nearest hit of every ray, on the host -- THE definition the device pass is held to -> HIT [n]."""
+    rays, (s, p, l), (ns, np_, nl) = _cast_args(rays, spheres, planes, lights)
+    out = np.empty(rays.size, HIT)
+    if not 0 <= int(flags) < 2 ** 32 or not load_library().clw_host_cast_rays(_ptr(rays), rays.size, int(flags), _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, _ptr(out)):
+        raise ValueError("clw_host_cast_rays rejects these arguments (at least one ray, fewer than 2^30, a kind bit and only CAST_* bits in flags)")
+    return out
+
+
+def occluded_rays_host(rays, flags: int, spheres, planes, lights=None) -> np.ndarray:
+    """clw_host_occluded_rays: whether every ray meets anything within its tmax, on the host -- THE definition -> uint8 [n] of 0 / 1."""
+    rays, (s, p, l), (ns, np_, nl) = _cast_args(rays, spheres, planes, lights)
+    out = np.empty(rays.size, np.uint8)
+    if not 0 <= int(flags) < 2 ** 32 or not load_library().clw_host_occluded_rays(_ptr(rays), rays.size, int(flags), _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, _ptr(out)):
+        raise ValueError("clw_host_occluded_rays rejects these arguments (at least one ray, fewer than 2^30, a kind bit and only CAST_* bits in flags)")
     return out
 
 
@@ -877,6 +955,33 @@ class ClWrap:
     def ao_device_ptr(self, what: int = AO_FRAME):
         """Device address of the frame or the counts of the last render_ao (None before the first)."""
         return self.L.clw_ext_ao_device_ptr(C.byref(self.w), int(what))
+
+    def cast_rays(self, rays, flags: int = CAST_SPHERES | CAST_PLANES):
+        """clw_ext_cast_rays: the nearest hit of every ray (RAY_QUERY [n]) against the bound scene, on the device -> HIT [n], or None when it is
+        refused (no scene bound, no ray, unknown flag bits, no kind)."""
+        rays = np.ascontiguousarray(rays, RAY_QUERY).reshape(-1)
+        out = np.empty(rays.size, HIT)
+        if rays.size >= 2 ** 32 or not 0 <= int(flags) < 2 ** 32:
+            return None
+        n = self.L.clw_ext_cast_rays(C.byref(self.w), _ptr(rays), rays.size, int(flags), _ptr(out))
+        return out if n == rays.size and n else None
+
+    def occluded_rays(self, rays, flags: int = CAST_SPHERES | CAST_PLANES):
+        """clw_ext_occluded_rays: whether every ray meets anything within its tmax, on the device -> uint8 [n] of 0 / 1, or None when it is refused."""
+        rays = np.ascontiguousarray(rays, RAY_QUERY).reshape(-1)
+        out = np.empty(rays.size, np.uint8)
+        if rays.size >= 2 ** 32 or not 0 <= int(flags) < 2 ** 32:
+            return None
+        n = self.L.clw_ext_occluded_rays(C.byref(self.w), _ptr(rays), rays.size, int(flags), _ptr(out))
+        return out if n == rays.size and n else None
+
+    def cast_rays_device(self, rays_ptr: int, n: int, flags: int = CAST_SPHERES | CAST_PLANES, hits_ptr: int | None = None, blocked_ptr: int | None = None) -> int:
+        """clw_ext_cast_rays_device: the query over the caller's device memory (integer addresses: n RAY_QUERY records; n HIT records or n bytes --
+        exactly one of the two), on the wrapper's stream, without waiting -> n, or 0 when it is refused."""
+        if not 0 <= int(n) < 2 ** 32 or not 0 <= int(flags) < 2 ** 32:
+            return 0
+        return int(self.L.clw_ext_cast_rays_device(C.byref(self.w), C.c_void_p(rays_ptr or None), int(n), int(flags), C.c_void_p(hits_ptr or None),
+                                                   C.c_void_p(blocked_ptr or None)))
 
     def unit_ao_open(self, point, normal, ids, width: int, rows: int, first_row: int, ao: clw_ao):
         """clw_ext_unit_ao_open: wt_ao_trace on synthetic channels against the bound scene -> uint8 [width * rows], or None when it is refused."""

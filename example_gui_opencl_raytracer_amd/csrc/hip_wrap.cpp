@@ -25,6 +25,7 @@
 
 #include "../../include/hip_wrap_ext.h"
 #include "ao_host.h"
+#include "cast_host.h"
 #include "launch_plan.h"
 #include "objects_host.h"
 #include "overlay_host.h"
@@ -53,6 +54,8 @@ extern "C" hipError_t wt_fast_launch_ao_trace(const whitted_params*, int, const 
 extern "C" hipError_t wt_strict_launch_ao_trace(const whitted_params*, int, const float*, const float*, const unsigned*, const float*, unsigned char*, unsigned, unsigned, unsigned, unsigned, float, hipStream_t);
 extern "C" hipError_t wt_fast_launch_ao_resolve(const unsigned char*, const unsigned*, const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
 extern "C" hipError_t wt_strict_launch_ao_resolve(const unsigned char*, const unsigned*, const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
+extern "C" hipError_t wt_fast_launch_cast(const whitted_params*, int, unsigned, unsigned, size_t, const void*, unsigned, unsigned, void*, unsigned char*, hipStream_t);
+extern "C" hipError_t wt_strict_launch_cast(const whitted_params*, int, unsigned, unsigned, size_t, const void*, unsigned, unsigned, void*, unsigned char*, hipStream_t);
 extern "C" hipError_t wt_fast_launch_cams(const wt_cam_table*, float*, hipStream_t);
 extern "C" hipError_t wt_fast_launch_classify(const unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned char*, unsigned*, unsigned*, unsigned, hipStream_t);
 extern "C" hipError_t wt_fast_launch_sched(const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
@@ -277,6 +280,17 @@ struct Impl {
             point = normal = nullptr; ids = nullptr; open = nullptr; frame = nullptr; n = 0; written = false;
         }
     } ao;
+    /* ray queries (clw_ext_cast_rays / clw_ext_occluded_rays; whitted_cast.inc): the buffers of the host-array entry points -- the rays as uploaded,
+     * the hits, the blocked bytes -- sized for the largest n so far.  Those calls wait for their own work, so nothing is in flight on them between
+     * calls; clw_ext_cast_rays_device works on the caller's memory and owns nothing. */
+    struct Cast {
+        void* rays = nullptr; void* hits = nullptr; uint8_t* blocked = nullptr;
+        uint32_t cap = 0;               /* rays the buffers hold */
+        void free_buffers() {
+            for (void* q : {rays, hits, (void*)blocked}) if (q) (void)hipFree(q);
+            rays = hits = nullptr; blocked = nullptr; cap = 0;
+        }
+    } cast;
     /* prepared scene cache */
     const Buffer *prep_s = nullptr, *prep_p = nullptr, *prep_l = nullptr;
     uint32_t prep_ns = 0, prep_np = 0, prep_nl = 0;
@@ -1147,6 +1161,68 @@ int gbuffer_channel(uint32_t channel) {
     return -1;
 }
 
+/* ---- ray queries ------------------------------------------------------------------------------------------------------------------ */
+/* The scene side of a query of n rays: the raytracer's arguments 1-6, prepared as a primary-hit pass prepares them (once per scene), and the plan
+ * (wt_plan_cast).  Needs no ray buffer, no camera, no images and no framebuffer.  false (nothing prepared or filled in) when there is no
+ * raytracer kernel or no bound scene -- the callers return 0 then, they do not terminate the process. */
+bool cast_params(cl_wrap* w, Impl* I, uint32_t n, whitted_params& P, wt_cast_class& cc) {
+    cl_uint kid = 0;
+    while (kid < I->kernels.size() && I->kernels[kid].kind != K_RAYTRACER) kid++;
+    if (kid >= I->kernels.size()) return false;
+    const Kernel& k = I->kernels[kid];
+    for (cl_uint a : {1u, 2u, 3u}) if (!is_registered(w, kid, a)) return false;
+    for (cl_uint a : {4u, 5u, 6u}) if (!k.values[a].set) return false;
+    Buffer* bs = (Buffer*)w->buffers[kid][1];
+    Buffer* bp = (Buffer*)w->buffers[kid][2];
+    Buffer* bl = (Buffer*)w->buffers[kid][3];
+    prepare_scene(I, bs, read_count(k, 4), bp, read_count(k, 5), bl, read_count(k, 6));
+    cc = wt_plan_cast(I->variant, I->prep_ns, (uint32_t)I->geom_f4, I->grid_ok && I->use_grid, n, (uint32_t)std::max(0, env_int("CLWRAP_CAST_BATCHES", 0)));   /* CLWRAP_CAST_BATCHES: tuning knob */
+    if (cc.groups == 0u) return false;
+    P.ns = I->prep_ns; P.np = I->prep_np; P.nl = I->prep_nl; P.geom_f4 = (uint32_t)I->geom_f4;
+    P.geom = I->d_geom; P.ptex = I->d_ptex;
+    if (cc.flags & WT_F_GRID) {
+        P.grid_pair = I->grid_pair ? 1u : 0u;
+        P.grid_start = I->d_grid_start; P.grid_items = I->d_grid_items; P.grid_box = I->d_grid_box; P.grid_geom = I->d_grid_geom;
+        for (int a = 0; a < 3; a++) {
+            P.grid_min[a] = I->grid.gmin[a]; P.grid_inv[a] = I->grid.inv[a]; P.grid_cell[a] = I->grid.cell[a]; P.grid_res[a] = I->grid.res[a];
+        }
+    }
+    return true;
+}
+
+/* wt_cast over device memory on the launch stream; exactly one of hits / blocked */
+void launch_cast(Impl* I, const whitted_params& P, const wt_cast_class& cc, const void* rays, uint32_t n, uint32_t flags, void* hits, uint8_t* blocked) {
+    LaunchTimer t(I, CLW_TIMING_CAST, true);
+    hipError_t e = (I->strict ? wt_strict_launch_cast : wt_fast_launch_cast)(&P, cc.flags, cc.groups, cc.batches, cc.dyn_lds, rays, n, flags, hits, blocked, I->stream);
+    if (e != hipSuccess) die("Couldn't run the kernel");
+    t.done();
+}
+
+/* the two host-array entry points: upload, launch, read back, all in the order of the launch stream, then wait */
+uint32_t cast_host_arrays(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uint32_t flags, clw_hit* hits, uint8_t* blocked) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    static_assert(sizeof(clw_ray) == 32 && sizeof(clw_hit) == 32, "the queries' ABI");
+    if (!wt_cast_check(n, flags) || !rays || (!hits && !blocked)) return 0;
+    whitted_params P{};
+    wt_cast_class cc;
+    if (!cast_params(wrap, I, n, P, cc)) return 0;
+    Impl::Cast& C = I->cast;
+    if (C.cap < n) {
+        C.free_buffers();
+        HIP_OK(hipMalloc(&C.rays, (size_t)n * sizeof(clw_ray)), "Couldn't allocate device memory");
+        HIP_OK(hipMalloc(&C.hits, (size_t)n * sizeof(clw_hit)), "Couldn't allocate device memory");
+        HIP_OK(hipMalloc((void**)&C.blocked, (size_t)n), "Couldn't allocate device memory");
+        C.cap = n;
+    }
+    HIP_OK(hipMemcpyAsync(C.rays, rays, (size_t)n * sizeof(clw_ray), hipMemcpyHostToDevice, I->stream), "Couldn't transfer the data from host to the device");
+    launch_cast(I, P, cc, C.rays, n, flags, hits ? C.hits : nullptr, hits ? nullptr : C.blocked);
+    if (hits) HIP_OK(hipMemcpyAsync(hits, C.hits, (size_t)n * sizeof(clw_hit), hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    else HIP_OK(hipMemcpyAsync(blocked, C.blocked, (size_t)n, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    finish(I);
+    return n;
+}
+
 /* ---- the selection overlay ------------------------------------------------------------------------------------------------------- */
 /* wt_overlay over a width x rows range on the launch stream; the caller has checked style and selection (wt_overlay_check).  The kernel is
  * integer work compiled into both units; the build in use launches its own copy. */
@@ -1473,6 +1549,7 @@ void cl_wrap_release(cl_wrap* wrap) {
     I->ao.free_buffers();
     if (I->ao.dirs) (void)hipFree(I->ao.dirs);
     if (I->ao.done) (void)hipEventDestroy(I->ao.done);
+    I->cast.free_buffers();
     I->ptab.free_all();
     I->adapt.free_all();
     if (I->tables_fence) (void)hipEventDestroy(I->tables_fence);
@@ -2099,6 +2176,27 @@ uint32_t clw_ext_unit_ao_resolve(cl_wrap* wrap, const uint8_t* open_u8, const ui
     (void)hipFree(dopen); (void)hipFree(dids); (void)hipFree(dout);
     if (dframe) (void)hipFree(dframe);
     return (uint32_t)n;
+}
+
+uint32_t clw_ext_cast_rays(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uint32_t flags, clw_hit* hits) {
+    if (!hits) return 0;
+    return cast_host_arrays(wrap, rays, n, flags, hits, nullptr);
+}
+
+uint32_t clw_ext_occluded_rays(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uint32_t flags, uint8_t* blocked) {
+    if (!blocked) return 0;
+    return cast_host_arrays(wrap, rays, n, flags, nullptr, blocked);
+}
+
+uint32_t clw_ext_cast_rays_device(cl_wrap* wrap, const void* d_rays, uint32_t n, uint32_t flags, void* d_hits, void* d_blocked) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    if (!wt_cast_check(n, flags) || !d_rays || (d_hits != nullptr) == (d_blocked != nullptr)) return 0;
+    whitted_params P{};
+    wt_cast_class cc;
+    if (!cast_params(wrap, I, n, P, cc)) return 0;
+    launch_cast(I, P, cc, d_rays, n, flags, d_hits, (uint8_t*)d_blocked);
+    return n;
 }
 
 void clw_ext_set_pipeline(cl_wrap* wrap, int on) { impl_of(wrap)->pipeline = on ? 1 : 0; }

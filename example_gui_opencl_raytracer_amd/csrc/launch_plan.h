@@ -153,6 +153,18 @@ void wt_plan_fused_range(const wt_raygen* g, uint32_t n_items, whitted_params* P
  * with it the side table and the visibility classes of the lights */
 typedef struct { int32_t flags; uint32_t dyn_lds, lpt, vis; } wt_geom_class;
 wt_geom_class wt_plan_geometry(int strict, int variant, uint32_t ns, uint32_t np, uint32_t geom_f4, int have_lpt, int grid_usable);
+/* how a ray query (whitted_cast.inc: wt_cast) of `n` rays reads the scene and how it is launched.  The geometry class is the primary-hit
+ * pass's, by the same rules: the uniform grid when it is built and on (not WT_V_NO_GRID), else the scene staged in LDS when it fits
+ * WT_GEOM_LDS_MAX_F4 float4 (and not WT_V_GEOM_GLOBAL), else global memory.  A workgroup is one wave that serves `batches` consecutive batches
+ * of 64 rays: WT_CAST_BATCHES_LDS where the scene is staged (the staging is paid once per workgroup), 1 elsewhere; `batches_req` > 0 overrides
+ * it (the tuning knob CLWRAP_CAST_BATCHES; capped at WT_CAST_BATCHES_MAX).  groups = 0: n is not a count the queries accept.
+ * WT_CAST_BATCHES_LDS = 1 is the measured optimum (tools/cast_times.py --batches, 2 M rays: 1 / 2 / 4 / 8 / 16 batches cost 0.0235 / 0.0238 /
+ * 0.0244 / 0.0271 / 0.0335 ms on the demo scene and 0.256 / 0.268 / 0.297 / 0.368 / 0.534 ms on 256 spheres): at most 4.2 KiB are ever staged
+ * (more than 256 spheres are not), four loads per lane against hundreds of tests, while every further batch takes a wave's worth of parallelism
+ * away from the machine. */
+enum { WT_CAST_BATCHES_LDS = 1, WT_CAST_BATCHES_MAX = 64 };
+typedef struct { int32_t flags; uint32_t dyn_lds, groups, batches; } wt_cast_class;
+wt_cast_class wt_plan_cast(int variant, uint32_t ns, uint32_t geom_f4, int grid_usable, uint32_t n, uint32_t batches_req);
 
 /* Which tile order a tiled launch reads and which builds it must wait for (hip_wrap.cpp: Impl::Sched).  Trace k writes its tile costs into
  * cost[wr]; when the signature changed, order[wr] is built from them on a side stream behind it, while trace k + 1 already runs with the

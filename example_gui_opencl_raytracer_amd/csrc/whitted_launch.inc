@@ -1,5 +1,5 @@
 /* whitted_launch.inc -- instantiates the kernels of whitted_trace.inc (and the primary-hit pass of whitted_gbuffer.inc, built from its
- * pieces, the camera models of whitted_projection.inc, the ambient occlusion pass of whitted_ao.inc, the selection overlay of
+ * pieces, the camera models of whitted_projection.inc, the ambient occlusion pass of whitted_ao.inc, the ray queries of whitted_cast.inc, the selection overlay of
  * whitted_overlay.inc and the visible-object table of whitted_objects.inc) in namespace WT_NS and exports
  * the C launchers the shim calls. */
 namespace WT_NS {
@@ -7,6 +7,7 @@ namespace WT_NS {
 #include "whitted_gbuffer.inc"
 #include "whitted_projection.inc"
 #include "whitted_ao.inc"
+#include "whitted_cast.inc"
 #include "whitted_overlay.inc"
 #include "whitted_objects.inc"
 }
@@ -279,5 +280,36 @@ extern "C" hipError_t WT_LAUNCH_AO_RESOLVE(const unsigned char* open, const unsi
     const dim3 g((unsigned)(tpr * trows)), block(WT_AO_TILE_W * WT_AO_TILE_H);
     if (ao_flags & WT_AO_FILTER) hipLaunchKernelGGL(WT_NS::wt_ao_resolve<true>, g, block, 0, s, A);
     else hipLaunchKernelGGL(WT_NS::wt_ao_resolve<false>, g, block, 0, s, A);
+    return hipGetLastError();
+}
+
+/* ray queries (whitted_cast.inc): wt_cast over `n` rays (2 float4 each) on the device, geometry as the caller's plan chose it (launch_plan.c:
+ * wt_plan_cast -- flags as WT_LAUNCH_GBUFFER, `groups` workgroups of one wave serving `batches` batches of 64 rays each).  Exactly one of
+ * `hits` (nearest: 2 float4 per ray) and `blocked` (any: a byte per ray) is given.  The caller has checked n and cast_flags (csrc/cast_host.h:
+ * wt_cast_check) */
+#if WT_STRICT
+#define WT_LAUNCH_CAST wt_strict_launch_cast
+#else
+#define WT_LAUNCH_CAST wt_fast_launch_cast
+#endif
+extern "C" hipError_t WT_LAUNCH_CAST(const whitted_params* P, int flags, unsigned groups, unsigned batches, size_t dyn_lds, const void* rays,
+                                     unsigned n, unsigned cast_flags, void* hits, unsigned char* blocked, hipStream_t s) {
+    if (n == 0u || n >= (1u << 30) || !(cast_flags & 7u) || (cast_flags & ~15u) || !rays || (hits != nullptr) == (blocked != nullptr) || batches == 0u ||
+        groups == 0u || (unsigned long long)groups * batches * 64ull < n || (unsigned long long)groups * batches * 64ull >= (1ull << 31) ||
+        dyn_lds > 48u * 1024u)
+        return hipErrorInvalidValue;
+    const bool grid = (flags & WT_F_GRID) != 0, lds = !grid && (flags & WT_F_GEOM_LDS);
+    WT_NS::wt_cast_args A = {};
+    A.rays = (const float4*)rays; A.hits = (float4*)hits; A.blocked = blocked; A.n = n; A.flags = cast_flags; A.batches = batches;
+    const dim3 g(groups), block(WT_BLOCK);
+    if (hits) {
+        if (grid) hipLaunchKernelGGL((WT_NS::wt_cast<false, true, false>), g, block, 0, s, *P, A);
+        else if (lds) hipLaunchKernelGGL((WT_NS::wt_cast<true, false, false>), g, block, dyn_lds, s, *P, A);
+        else hipLaunchKernelGGL((WT_NS::wt_cast<false, false, false>), g, block, 0, s, *P, A);
+    } else {
+        if (grid) hipLaunchKernelGGL((WT_NS::wt_cast<false, true, true>), g, block, 0, s, *P, A);
+        else if (lds) hipLaunchKernelGGL((WT_NS::wt_cast<true, false, true>), g, block, dyn_lds, s, *P, A);
+        else hipLaunchKernelGGL((WT_NS::wt_cast<false, false, true>), g, block, 0, s, *P, A);
+    }
     return hipGetLastError();
 }

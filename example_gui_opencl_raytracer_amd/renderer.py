@@ -47,6 +47,11 @@ over a primary-hit pass; or, with ``compose=True``, the frame of the last ``rend
 ``gbuffer()``'s buffers, the overlay, the object table and an accumulating view alone, honours the camera model, and is not available with row
 bands.  Strips' counts concatenate to the frame's; the filter runs on a strip's own rows.
 
+``cast_rays(origins, dirs, ...)`` / ``cast_rays_device(...)`` / ``line_of_sight(a, b)``: ray queries (clw_ext_cast_rays) -- where the CALLER's
+rays meet the scene, from anywhere, no camera involved: the nearest hit (t, id, normal, point) of every ray, or with ``any_hit`` whether it meets
+anything within ``tmax``.  Directions are not normalised: t is in units of their length, so ``line_of_sight(a, b)`` casts ``b - a`` with
+``tmax = 1``.  Nothing else the renderer holds is touched.
+
 ``projection=...`` / ``set_projection(model, ...)`` / ``look_ortho`` / ``look_panorama``: the camera models beside the pinhole
 (clw_ext_set_projection) -- ``'ortho'``: parallel rays from the image plane, the top / front / side view of an editor; ``'equirect'``: a
 latitude-longitude panorama of up to 360 x 180 degrees around the camera origin.  ``render()``, ``read_rays()``, ``gbuffer()``, ``pick``,
@@ -287,6 +292,37 @@ class Renderer:
         if counts.size != self.pixels:
             raise RuntimeError("no ambient occlusion pass has run on this renderer's range yet")
         return counts.reshape(self.rows, self.width)
+
+    # ---- ray queries
+    def cast_rays(self, origins, dirs, tmax=np.inf, ignore=None, kinds=("sphere", "plane"), opaque_only: bool = False, any_hit: bool = False) -> np.ndarray:
+        """Where the rays origins[k] + t * dirs[k] (arrays of [n, 3]; dirs as given, not normalised: t is in units of their length) meet the scene
+        -> api.HIT [n]: t (inf = a miss), id (api.ID_NONE = a miss), normal, point of the nearest primitive with 0 < t <= tmax; with `any_hit` a
+        bool [n] instead: does the ray meet anything that near.  tmax and ignore (the id word of the one primitive a ray does not test, e.g. the
+        object it starts on; None = none) are scalar or per ray; kinds: which of 'sphere', 'plane', 'light' take part; opaque_only: transparent
+        spheres let the ray pass.  Needs no camera."""
+        rays = api.make_rays(origins, dirs, tmax, ignore)
+        flags = api.cast_flags(kinds, opaque_only)
+        got = self.w.occluded_rays(rays, flags) if any_hit else self.w.cast_rays(rays, flags)
+        if got is None:
+            raise RuntimeError("the ray query was refused (at least one ray, at least one kind?)")
+        return got.astype(bool) if any_hit else got
+
+    def cast_rays_device(self, rays_ptr: int, n: int, hits_ptr: int | None = None, blocked_ptr: int | None = None, kinds=("sphere", "plane"),
+                         opaque_only: bool = False) -> int:
+        """The query over the caller's device memory, by integer device address as ``framebuffer_ptr``: n api.RAY_QUERY records in, n api.HIT
+        records (`hits_ptr`: nearest) or n bytes (`blocked_ptr`: any) out -- exactly one of the two.  Launched on the wrapper's stream
+        (``w.set_stream``) without waiting -> n."""
+        got = self.w.cast_rays_device(rays_ptr, n, api.cast_flags(kinds, opaque_only), hits_ptr, blocked_ptr)
+        if got != n:
+            raise RuntimeError("the ray query was refused (at least one ray, at least one kind, exactly one of hits_ptr and blocked_ptr?)")
+        return got
+
+    def line_of_sight(self, a, b, opaque_only: bool = True) -> np.ndarray:
+        """Can a[k] see b[k]? -> bool [n]: no sphere or plane (with `opaque_only`, no opaque one) is met by the ray from a to b with direction
+        b - a at 0 < t <= 1 -- t is in units of |b - a|, so tmax = 1 ends the ray exactly at b."""
+        a = np.asarray(a, np.float32).reshape(-1, 3)
+        b = np.asarray(b, np.float32).reshape(-1, 3)
+        return ~self.cast_rays(a, b - a, tmax=1.0, opaque_only=opaque_only, any_hit=True)
 
     # ---- the visible-object table
     def objects(self, rect=None) -> np.ndarray:

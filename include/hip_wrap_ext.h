@@ -543,6 +543,65 @@ uint32_t clw_ext_unit_ao_resolve(cl_wrap* wrap, const uint8_t* open_u8, const ui
 #define CLW_TIMING_AO         0x414F5452u
 #define CLW_TIMING_AO_RESOLVE 0x414F5253u
 
+/* Ray queries: where a CALLER's rays meet the scene -- from anywhere, toward anything, no camera involved: drop an object onto what lies below
+ * it, snap to the surface under a point, measure a distance, ask whether a light sees a sphere, scan a fan of sensor rays, send a second bounce
+ * from the points a first query returned.  A nearest-hit query answers a clw_hit per ray, an any-hit query one byte.  All of the arithmetic is
+ * defined here, on the host: clw_host_cast_rays and clw_host_occluded_rays are THE definition, and the device pass (wt_cast:
+ * csrc/whitted_cast.inc) equals them bit for bit in both builds.  float32 operations are rounded once each, never fused; square root and divide
+ * are IEEE.  spheres / planes / lights = the 96- / 96- / 48-byte records of the scene arrays, read through the prepared words the device reads:
+ * {centre, +-r * r} per sphere (sign bit set = material.transperent != 0), {n}, {p0} per plane, {centre, r * r} per light.
+ * Per ray {o = origin, tmax, d = dir, ignore}:
+ *   - d is used as given, NOT normalised; t is in units of |d|: the ray from a to b with d = b - a and tmax = 1 ends exactly at b.
+ *   - The primitives that take part: the kinds enabled in `flags`, in the order spheres 0..ns-1, planes 0..np-1, lights 0..nl-1 (a light is the
+ *     plain sphere of its radius).  A primitive whose id word -- kind << 30 | index as CLW_GB_ID: kind 0 sphere, 1 plane, 2 light -- equals
+ *     `ignore` is skipped (the object a ray starts on); CLW_ID_NONE skips nothing.  With CLW_CAST_OPAQUE a sphere whose prepared r * r word has
+ *     its sign bit set is skipped: the ray passes transparent spheres.
+ *   - The tests, a dot product being x x' + y y' + z z' left to right:
+ *       sphere or light {c, q}: A = d.d; v = o - c; C = v.v - |q|; B = v.d; D = B * B + (-(A * C)); s = sqrtf(D); t0 = (-B - s) / A;
+ *                               t = t0 < 0 ? (-B + s) / A : t0; hit = !(D < 0) && !(t <= 0);
+ *       plane {n, p0}:          num = (p0 - o).n; B = d.n; t = num / B; hit = !(B == 0) && !(t <= 0);
+ *     -- the primary-hit pass's own evaluation of its winner.  A ray that starts inside a sphere meets its far side.
+ *   - A primitive is a CANDIDATE iff hit && t <= tmax.  So a NaN t, a NaN ray or a NaN tmax meets nothing -- this is NOT the trace kernel's
+ *     rule, under which a poisoned ray "hits" the last primitive --, a zero direction meets nothing, and tmax = +inf means unlimited.
+ *   - Nearest: a candidate replaces the best iff t < tbest; equal t keeps the earlier primitive in the order above.
+ *       miss: {t = +inf, id = CLW_ID_NONE, normal = 0, point = 0};
+ *       hit:  t, id, point = d * t + o per component (the product, then the sum; WITHOUT the EPSILON offset of the primary-hit pass's point
+ *             channel), normal = (point - c) / sqrtf((point - c).(point - c)) per component for a sphere or a light, the stored normal for a
+ *             plane (never flipped toward the ray).
+ *   - Any: blocked[k] = 1 iff ray k has a candidate, else 0.
+ * Refused (0 returned, nothing written): a NULL pointer (a count > 0 with its array NULL), n == 0 or n >= 1 << 30, a flag bit beside the five
+ * below, no kind bit set. */
+typedef struct clw_ray { float origin[3]; float tmax; float dir[3]; uint32_t ignore; } clw_ray;   /* 32 bytes */
+typedef struct clw_hit { float t; uint32_t id; float normal[3]; float point[3]; } clw_hit;        /* 32 bytes */
+#define CLW_CAST_SPHERES 1u
+#define CLW_CAST_PLANES  2u
+#define CLW_CAST_LIGHTS  4u     /* light spheres as plain geometry, kind 2 ids */
+#define CLW_CAST_KINDS   7u
+#define CLW_CAST_OPAQUE  8u     /* transparent spheres (material.transperent != 0) let the ray pass */
+int clw_host_cast_rays(const clw_ray* rays, uint32_t n, uint32_t flags, const void* spheres, uint32_t ns, const void* planes, uint32_t np,
+                       const void* lights, uint32_t nl, clw_hit* hits);          /* 1 = done, 0 = refused */
+int clw_host_occluded_rays(const clw_ray* rays, uint32_t n, uint32_t flags, const void* spheres, uint32_t ns, const void* planes, uint32_t np,
+                           const void* lights, uint32_t nl, uint8_t* blocked);   /* blocked[k] = 0 / 1 */
+/* The queries on the device, against the wrapper's bound scene (the raytracer's arguments 1-6: the three arrays and their counts); no camera,
+ * no ray buffer, no framebuffer and no textures are needed.  The scene is prepared if no launch has prepared it yet, exactly as a primary-hit
+ * pass does, and read as that pass reads it: staged in LDS, from global memory, or through the uniform grid (which only skips tests: the answer
+ * is the definition's in every flavour).  A call after clw_ext_invalidate_scene sees the rewritten scene.
+ * clw_ext_cast_rays / clw_ext_occluded_rays take HOST arrays: they upload the rays into a buffer the feature owns, launch on the wrapper's
+ * stream, wait, read the answers back and return n.  The buffers are allocated at first use, grown when n grows and freed by cl_wrap_release.
+ * clw_ext_cast_rays_device takes the caller's DEVICE memory (n clw_ray; n clw_hit or n bytes): exactly one of d_hits / d_blocked is non-NULL and
+ * selects nearest or any.  It launches on the wrapper's stream -- the caller's after clw_ext_set_stream --, does not wait, and returns n; the
+ * caller orders its own reads and writes on that stream.
+ * All three return 0 -- nothing launched, the outputs untouched, and the process goes on -- for what the definition refuses (for the device
+ * entry point also both or neither output given) and when no scene is bound.
+ * The framebuffer, the buffers of clw_ext_render_gbuffer, the overlay, the object table and the AO pass, an accumulating view and its count, the
+ * tile order and clw_ext_last_trace_flags are left alone.  Launches are logged under CLW_TIMING_CAST in clw_ext_timing_get.
+ * Not built: sorting incoherent rays by grid cell before the launch; per-ray flags; the texel or the material of the hit; a latched "bounce"
+ * helper that turns hits into the next rays on the device. */
+uint32_t clw_ext_cast_rays(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uint32_t flags, clw_hit* hits);          /* host arrays; waits */
+uint32_t clw_ext_occluded_rays(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uint32_t flags, uint8_t* blocked);  /* host arrays; waits */
+uint32_t clw_ext_cast_rays_device(cl_wrap* wrap, const void* d_rays, uint32_t n, uint32_t flags, void* d_hits, void* d_blocked);
+#define CLW_TIMING_CAST 0x43415354u
+
 /* Work counters of the trace kernel.  enable=1 selects the counting build of the kernel
  * for subsequent launches (slower); read returns and clears
  *   out[0] path segments  out[1] shadow rays  out[2] light probes  out[3] skybox fetches
