@@ -875,13 +875,18 @@ class ClWrap:
         """Launch the primary-hit pass over the range the next trace launch would cover -> work-items (0 = no camera latched / no known channel)."""
         return int(self.L.clw_ext_render_gbuffer(C.byref(self.w), int(channels)))
 
+    def _read_pass(self, read, dtype) -> np.ndarray:
+        """What a range pass left on the device: `read(out, capacity_bytes)` is asked for the byte count, then again with an array that holds it."""
+        nbytes = int(read(None, 0))
+        out = np.zeros(nbytes // np.dtype(dtype).itemsize, dtype)
+        if nbytes:
+            assert read(_ptr(out), nbytes) == nbytes
+        return out
+
     def read_gbuffer(self, channel) -> np.ndarray:
         """One channel (a GB_* bit) of the last pass -> float32 [n] / uint32 [n] / float32 [n, 3]; empty for a channel it did not write."""
         _, dtype, per = next(v for v in GB_CHANNELS.values() if v[0] == channel)
-        nbytes = int(self.L.clw_ext_read_gbuffer(C.byref(self.w), int(channel), None, 0))
-        out = np.zeros(nbytes // 4, dtype)
-        if nbytes:
-            assert self.L.clw_ext_read_gbuffer(C.byref(self.w), int(channel), _ptr(out), nbytes) == nbytes
+        out = self._read_pass(lambda p, cap: self.L.clw_ext_read_gbuffer(C.byref(self.w), int(channel), p, cap), dtype)
         return out.reshape(-1, 3) if per == 3 else out
 
     def gbuffer_device_ptr(self, channel):
@@ -900,11 +905,7 @@ class ClWrap:
 
     def read_overlay(self) -> np.ndarray:
         """The overlay frame of the last render_overlay -> uint32 [n]; empty before the first."""
-        nbytes = int(self.L.clw_ext_read_overlay(C.byref(self.w), None, 0))
-        out = np.empty(nbytes // 4, np.uint32)
-        if nbytes:
-            assert self.L.clw_ext_read_overlay(C.byref(self.w), _ptr(out), nbytes) == nbytes
-        return out
+        return self._read_pass(lambda p, cap: self.L.clw_ext_read_overlay(C.byref(self.w), p, cap), np.uint32)
 
     def overlay_device_ptr(self):
         """Device address of the overlay frame of the last render_overlay (None before the first)."""
@@ -945,12 +946,7 @@ class ClWrap:
 
     def read_ao(self, what: int = AO_FRAME) -> np.ndarray:
         """What the last render_ao left: AO_FRAME -> uint32 [n], AO_COUNTS -> uint8 [n]; empty before the first."""
-        dtype = np.uint8 if what == AO_COUNTS else np.uint32
-        nbytes = int(self.L.clw_ext_read_ao(C.byref(self.w), int(what), None, 0))
-        out = np.empty(nbytes // np.dtype(dtype).itemsize, dtype)
-        if nbytes:
-            assert self.L.clw_ext_read_ao(C.byref(self.w), int(what), _ptr(out), nbytes) == nbytes
-        return out
+        return self._read_pass(lambda p, cap: self.L.clw_ext_read_ao(C.byref(self.w), int(what), p, cap), np.uint8 if what == AO_COUNTS else np.uint32)
 
     def ao_device_ptr(self, what: int = AO_FRAME):
         """Device address of the frame or the counts of the last render_ao (None before the first)."""

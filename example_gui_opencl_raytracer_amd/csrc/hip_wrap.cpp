@@ -11,60 +11,11 @@
  * There is NO CPU fallback: without a HIP device cl_wrap_init fails exactly as the
  * reference fails without an OpenCL GPU (opencl_wrap.c:31-34).
  */
-#include <hip/hip_runtime.h>
+#include "hip_wrap_impl.h"
 
-#include <algorithm>
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cmath>
-#include <cstring>
-#include <string>
-#include <vector>
+using namespace clw;
 
-#include "../../include/hip_wrap_ext.h"
-#include "ao_host.h"
-#include "cast_host.h"
-#include "launch_plan.h"
-#include "objects_host.h"
-#include "overlay_host.h"
-#include "png_codec.h"
-#include "projection_host.h"
-#include "scene_prep.h"
-#include "whitted_params.h"
-
-extern "C" hipError_t wt_fast_launch_trace(const whitted_params*, int, unsigned, size_t, hipStream_t);
-extern "C" hipError_t wt_fast_launch_raygen(const raygen_params*, hipStream_t);
-extern "C" hipError_t wt_strict_launch_trace(const whitted_params*, int, unsigned, size_t, hipStream_t);
-extern "C" hipError_t wt_strict_launch_raygen(const raygen_params*, hipStream_t);
-extern "C" hipError_t wt_fast_launch_unit(int, const float*, float*, unsigned, unsigned, unsigned, unsigned, hipStream_t);
-extern "C" hipError_t wt_strict_launch_unit(int, const float*, float*, unsigned, unsigned, unsigned, unsigned, hipStream_t);
-extern "C" hipError_t wt_fast_launch_unit_scene(const whitted_params*, int, int, const float*, float*, unsigned, unsigned, unsigned, size_t, hipStream_t);
-extern "C" hipError_t wt_strict_launch_unit_scene(const whitted_params*, int, int, const float*, float*, unsigned, unsigned, unsigned, size_t, hipStream_t);
-extern "C" hipError_t wt_fast_launch_gbuffer(const whitted_params*, int, unsigned, size_t, float*, unsigned*, float*, float*, float*, const wt_projection*, hipStream_t);
-extern "C" hipError_t wt_strict_launch_gbuffer(const whitted_params*, int, unsigned, size_t, float*, unsigned*, float*, float*, float*, const wt_projection*, hipStream_t);
-extern "C" hipError_t wt_fast_launch_raygen_proj(const raygen_params*, const wt_projection*, hipStream_t);
-extern "C" hipError_t wt_strict_launch_raygen_proj(const raygen_params*, const wt_projection*, hipStream_t);
-extern "C" hipError_t wt_fast_launch_overlay(const unsigned*, const unsigned*, unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, unsigned, hipStream_t);
-extern "C" hipError_t wt_strict_launch_overlay(const unsigned*, const unsigned*, unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, unsigned, hipStream_t);
-extern "C" hipError_t wt_fast_launch_objects(const unsigned*, const unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, void*, void*, hipStream_t);
-extern "C" hipError_t wt_strict_launch_objects(const unsigned*, const unsigned*, unsigned, unsigned, unsigned, const unsigned*, const unsigned*, void*, void*, hipStream_t);
-extern "C" hipError_t wt_fast_launch_ao_trace(const whitted_params*, int, const float*, const float*, const unsigned*, const float*, unsigned char*, unsigned, unsigned, unsigned, unsigned, float, hipStream_t);
-extern "C" hipError_t wt_strict_launch_ao_trace(const whitted_params*, int, const float*, const float*, const unsigned*, const float*, unsigned char*, unsigned, unsigned, unsigned, unsigned, float, hipStream_t);
-extern "C" hipError_t wt_fast_launch_ao_resolve(const unsigned char*, const unsigned*, const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
-extern "C" hipError_t wt_strict_launch_ao_resolve(const unsigned char*, const unsigned*, const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
-extern "C" hipError_t wt_fast_launch_cast(const whitted_params*, int, unsigned, unsigned, size_t, const void*, unsigned, unsigned, void*, unsigned char*, hipStream_t);
-extern "C" hipError_t wt_strict_launch_cast(const whitted_params*, int, unsigned, unsigned, size_t, const void*, unsigned, unsigned, void*, unsigned char*, hipStream_t);
-extern "C" hipError_t wt_fast_launch_cams(const wt_cam_table*, float*, hipStream_t);
-extern "C" hipError_t wt_fast_launch_classify(const unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned char*, unsigned*, unsigned*, unsigned, hipStream_t);
-extern "C" hipError_t wt_fast_launch_sched(const unsigned*, unsigned*, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t);
-
-namespace {
-
-constexpr size_t COUNTER_WORDS = CLW_NUM_COUNTERS + 16 * (size_t)CLW_STAMP_SHARDS;
-constexpr size_t GRID_MAX_PAIRS = (size_t)1 << 25;   /* 20 B per cell-list entry */
-
+namespace clw {
 [[noreturn]] void die(const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -75,21 +26,18 @@ constexpr size_t GRID_MAX_PAIRS = (size_t)1 << 25;   /* 20 B per cell-list entry
     fflush(stdout);
     exit(1);
 }
+} /* namespace clw */
+
+namespace {
+
+constexpr size_t COUNTER_WORDS = CLW_NUM_COUNTERS + 16 * (size_t)CLW_STAMP_SHARDS;
+constexpr size_t GRID_MAX_PAIRS = (size_t)1 << 25;   /* 20 B per cell-list entry */
 
 /* the same floats bit for bit (+0 and -0 differ, a NaN equals itself): "the device table is unchanged" is decided on what it holds */
 bool same_bits(const std::vector<float>& a, const float* b, size_t n) {
     return a.size() == n && (n == 0 || !memcmp(a.data(), b, n * sizeof(float)));
 }
 
-#define HIP_OK(call, what)                                                        \
-    do {                                                                          \
-        hipError_t e_ = (call);                                                   \
-        if (e_ != hipSuccess) die("%s (%s)", what, hipGetErrorString(e_));        \
-    } while (0)
-
-enum KernelKind { K_RAYGEN = 0, K_RAYTRACER = 1 };
-
-typedef wt_raygen RaygenArgs;   /* snapshot of the eight by-value raygen arguments + the launch range (launch_plan.h) */
 /* field by field (the struct has tail padding, which a memcmp would also compare); floats by bit pattern */
 bool same_raygen(const RaygenArgs& a, const RaygenArgs& b) {
     return !memcmp(a.corner, b.corner, 12) && !memcmp(a.origin, b.origin, 12) && !memcmp(a.up, b.up, 12) &&
@@ -98,288 +46,11 @@ bool same_raygen(const RaygenArgs& a, const RaygenArgs& b) {
            a.band_stride == b.band_stride && a.band_phase == b.band_phase;
 }
 
-struct Buffer {
-    void* dptr = nullptr;
-    size_t size = 0;
-    bool owned = true;       /* freed by release */
-    bool lazy = false;       /* created with data == NULL: allocated on first real use */
-    bool image = false;
-    uint32_t w = 0, h = 0, layers = 0;
-    std::vector<uint8_t> shadow;   /* host copy of uploaded data (scene arrays are re-read by scene prep) */
-    bool gen_valid = false;        /* holds rays "generated" by a fused raygen launch */
-    bool exposed = false;          /* its device pointer was handed out (clw_ext_device_ptr) since the rays were generated: a caller may have
-                                      rewritten them in place, so they are no longer known to be this library's own unit vectors */
-    bool gen_materialised = false;
-    RaygenArgs gen{};
-    clw_projection gen_proj{};     /* the camera model the materialised rays were generated with (all zero = the pinhole) */
-};
-
-struct ArgValue {
-    bool set = false;
-    size_t size = 0;
-    uint8_t bytes[32] = {0};
-};
-
-struct Kernel {
-    KernelKind kind;
-    std::string name;
-    ArgValue values[__MAX_BUFFERS];
-};
-
-struct TimingEntry { hipEvent_t start, stop; cl_uint kernel; };
-
-struct Impl {
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    std::vector<Kernel> kernels;
-    std::vector<Buffer*> live;      /* every buffer handed out as a cl_mem handle */
-    /* knobs */
-    int depth = 15;
-    int strict = 0;
-    int fuse = 1;
-    int async = 0;
-    int variant = 0;
-    int last_trace_flags = -1;    /* the kernel flavour (WT_F_* flags) of the latest trace launch; -1 = none yet */
-    int counting = 0;
-    float through = 0.8f;  /* primitives.cl:7 TRANSPERENT_THROUGH; CLWRAP_THROUGH / clw_ext_set_shadow_through */
-    int stamps = 0;        /* CLWRAP_STAMPS=1: hand the counter block to the (diagnostic) stamp build of the kernel */
-    uint64_t id_offset = 0;
-    uint32_t band_stride = 1, band_phase = 0;
-    int supersample = 1;   /* n x n samples per pixel, resolved in the trace kernel (clw_ext_set_supersample / CLWRAP_SUPERSAMPLE): 1, 2, 4 or 8 */
-    float* debug_rgb = nullptr;
-    /* adaptive supersampling (clw_ext_set_adaptive / CLWRAP_ADAPTIVE): a trace launch becomes a 1-sample base pass, the classifier
-     * (wt_refine_classify) and a supersampled pass over the blocks it listed, all three on the launch stream and none waited for.  The
-     * buffers follow the launch range and the factor; a change of stream fences them like the camera table (tables_fence). */
-    int adaptive = -1;            /* contrast threshold, 0..256; -1 = off */
-    struct Adaptive {
-        uint8_t* mask = nullptr; uint32_t* order = nullptr; uint32_t* count = nullptr;
-        uint32_t w = 0, rows = 0; int ss = 0;     /* output pixels of the range the buffers were sized for, and the factor */
-        uint32_t blocks = 0;                      /* blocks of the LAST trace launch when it was adaptive, else 0 (clw_ext_read_refine_mask) */
-        void free_all() {
-            for (void* q : {(void*)mask, (void*)order, (void*)count}) if (q) (void)hipFree(q);
-            mask = nullptr; order = nullptr; count = nullptr; w = rows = 0; ss = 0;
-        }
-    } adapt;
-    /* per-sample cameras of supersampled launches (clw_ext_set_sample_cameras / clw_ext_set_lens: alternatives, the later call clears the
-     * other).  The device copy is laid out per lane of a tile's wavefront (whitted_params.h: ss_cams) and is rewritten, only when it changed,
-     * by a small kernel on the launch stream that carries the table as its argument: stream order keeps it behind every queued launch that
-     * reads the previous table, and no host memory has to outlive the call.  A change of stream (clw_ext_set_stream) records tables_fence on
-     * the old stream, which the next launch with a table waits for on the new one. */
-    std::vector<clw_sample_camera> cams;         /* the explicit table, sy * n + sx order; empty = none */
-    float aperture = 0.0f, focus = 1.0f;         /* thin lens: the table is derived at every launch from the latched camera; aperture 0 = pinhole */
-    std::vector<clw_sample_camera> cams_used;    /* the table of the latest trace launch (clw_ext_get_sample_cameras) */
-    float* d_cams = nullptr;
-    wt_cam_table cams_dev{}; bool cams_dev_valid = false;   /* what d_cams holds once the stream gets there */
-    hipEvent_t tables_fence = nullptr; bool tables_fence_pending = false, tables_in_flight = false;   /* one fence for every device table written and read in stream order: sample cameras, moving spheres, an adaptive launch's mask / list / counters */
-    /* moving spheres of supersampled launches (clw_ext_set_sphere_motion).  The device copy -- 64 per-lane times, then a float4 per sphere
-     * (whitted_params.h: ss_times, ss_disp) -- is written like the camera table: only when it changed, in pieces of one wt_cam_table by the
-     * same small kernel on the launch stream, and behind the same fence when the stream changes. */
-    std::vector<float> motion_disp;              /* 3 per sphere; empty = the scene stands still (an all-zero table is stored as none) */
-    std::vector<float> motion_times;             /* explicit sample times, sy * n + sx order (only when motion_explicit_times) */
-    bool motion_explicit_times = false;          /* the caller gave times (of any count: the launch checks it); false = the shutter times of the launch's factor */
-    std::vector<float> times_used;               /* the times of the latest trace launch (clw_ext_get_sample_times) */
-    float* d_motion = nullptr;
-    std::vector<float> motion_dev;               /* what d_motion holds once the stream gets there; empty = nothing yet */
-    /* the seed offset of every trace launch (clw_ext_set_seed_offset / CLWRAP_SEED_OFFSET): a work-item's xorshift state starts at id + seed_offset */
-    uint32_t seed_offset = 0;
-    /* progressive frame accumulation (clw_ext_set_accumulate / CLWRAP_ACCUMULATE, CLWRAP_ACC_JITTER): frame f = K of a still view is traced with
-     * seed offset seed_offset + clw_host_frame_seed(f) through clw_host_jitter_camera(latched camera, f, n) and folded into `sum` by the trace
-     * kernel's epilogue (whitted_params.h: acc_sum); the key is everything that defines the image -- a launch whose key differs from the previous
-     * one's starts again at frame 0.  `sum` follows the launch range and is fenced across a change of stream like the tables (tables_fence). */
-    int acc_max = 0, acc_jitter = 1;          /* frames a still view accumulates (0 = the mode is off); per-frame sub-pixel offset on / off */
-    struct AccKey {
-        RaygenArgs gen{}; uint64_t n_out = 0; uint32_t total = 0;
-        int depth = 0, strict = 0, fuse = 0, ss = 0, max_frames = 0, jitter = 0;
-        float through = 0.0f; uint32_t seed = 0;
-        const Buffer* buf[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   /* rays, spheres, planes, lights, textures, skybox, framebuffer */
-        const void* dptr[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t size[7] = {0, 0, 0, 0, 0, 0, 0};
-        uint32_t counts[3] = {0, 0, 0}, img[5] = {0, 0, 0, 0, 0};
-        uint64_t epoch = 0;
-    };
-    struct Accum {
-        float* sum = nullptr; size_t pixels = 0;      /* 3 floats per output pixel of the launch range */
-        uint32_t K = 0;                               /* frames in the sum */
-        int frame = -1;                               /* the frame the trace launch under way folds in; -1 = not an accumulated launch */
-        uint64_t epoch = 0;                           /* bumped by whatever changes the image behind the key's back (uploads, invalidate, reset) */
-        bool key_valid = false; AccKey key;
-    } acc;
-    /* the camera model beside the pinhole (clw_ext_set_projection / CLWRAP_PROJECTION; whitted_projection.inc): model 0 = none.  The two tables
-     * of a panorama (width and height float4) are the wrapper's: `tab_col` / `tab_row` are what the device copies hold, and they are written
-     * again -- behind a wait for the launches that read them -- only when a launch resolves to other values. */
-    clw_projection proj{};
-    struct ProjTables {
-        float* d_col = nullptr; float* d_row = nullptr;
-        uint32_t cap_w = 0, cap_h = 0;               /* float4s the device buffers hold */
-        std::vector<float> tab_col, tab_row;         /* the tables on the device (4 floats per column / row) */
-        void free_all() { if (d_col) (void)hipFree(d_col); if (d_row) (void)hipFree(d_row); d_col = d_row = nullptr; cap_w = cap_h = 0; tab_col.clear(); tab_row.clear(); }
-    } ptab;
-    /* the primary-hit pass (clw_ext_render_gbuffer / clw_ext_pick; whitted_gbuffer.inc): planar channel buffers indexed like the framebuffer, one per
-     * CLW_GB_* bit, allocated when a pass first asks for them and sized for the pass's range; `done` is recorded behind every pass on the stream it
-     * ran on, so a read-back waits for the pass whatever the launch stream is by then */
-    struct GBuffer {
-        void* chan[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   /* depth, id, normal, point, albedo */
-        uint32_t n = 0;                 /* work-items the buffers are sized for */
-        uint32_t written = 0;           /* the channels of the last pass */
-        uint32_t* pick = nullptr;       /* the 11 words of one clw_pick: a pick is the pass on a one-pixel range, its channels laid out as the struct */
-        hipEvent_t done = nullptr;
-        void free_channels() { for (void*& q : chan) { if (q) (void)hipFree(q); q = nullptr; } n = 0; written = 0; }
-    } gb;
-    /* the selection overlay (clw_ext_render_overlay; whitted_overlay.inc): its own id buffer -- the primary-hit pass writes it, `gb` is not touched --
-     * and the composed frame, both sized for the pass's range; `done` as above */
-    struct Overlay {
-        uint32_t* ids = nullptr; uint32_t* frame = nullptr;
-        uint32_t n = 0;                 /* work-items the buffers are sized for */
-        bool written = false;           /* a pass has composed `frame` */
-        hipEvent_t done = nullptr;
-        void free_buffers() { if (ids) (void)hipFree(ids); if (frame) (void)hipFree(frame); ids = frame = nullptr; n = 0; written = false; }
-    } ov;
-    /* the visible-object table (clw_ext_object_stats; whitted_objects.inc): its own id and depth buffers -- the primary-hit pass writes them, `gb`
-     * and `ov` are not touched -- sized for the pass's range, and the slot table (16 bytes of counters + 48 per slot) and the result (the 16-byte
-     * summary + room for a 48-byte record per slot), sized for the scene's counts.  Every call waits for its own work, so nothing is ever in flight
-     * on these buffers between calls. */
-    struct Objects {
-        uint32_t* ids = nullptr; float* depth = nullptr;
-        uint32_t n = 0;                 /* work-items ids and depth are sized for */
-        void* table = nullptr; void* result = nullptr;
-        uint32_t slots = 0;             /* slots table and result are sized for */
-        void size_range(uint32_t items) {
-            if (n == items) return;
-            if (ids) (void)hipFree(ids);
-            if (depth) (void)hipFree(depth);
-            ids = nullptr; depth = nullptr; n = 0;
-            HIP_OK(hipMalloc((void**)&ids, (size_t)items * 4), "Couldn't allocate device memory");
-            HIP_OK(hipMalloc((void**)&depth, (size_t)items * 4), "Couldn't allocate device memory");
-            n = items;
-        }
-        void size_table(uint32_t count) {
-            if (slots == count) return;
-            if (table) (void)hipFree(table);
-            if (result) (void)hipFree(result);
-            table = result = nullptr; slots = 0;
-            HIP_OK(hipMalloc(&table, 16 + (size_t)count * sizeof(clw_object_stat)), "Couldn't allocate device memory");
-            HIP_OK(hipMalloc(&result, sizeof(clw_object_summary) + (size_t)count * sizeof(clw_object_stat)), "Couldn't allocate device memory");
-            slots = count;
-        }
-        void free_buffers() {
-            for (void* q : {(void*)ids, (void*)depth, table, result}) if (q) (void)hipFree(q);
-            ids = nullptr; depth = nullptr; table = result = nullptr; n = 0; slots = 0;
-        }
-    } obj;
-    /* ambient occlusion (clw_ext_render_ao; whitted_ao.inc): its own point, normal and id buffers -- the primary-hit pass writes them, `gb`, `ov`
-     * and `obj` are not touched --, the open-ray counts and the resolved frame, all sized for the pass's range; `done` as above.  The direction
-     * table (16 x K float4, room for K = 32) is written only when K changes, behind a wait for the passes that read the old one. */
-    struct AO {
-        float* point = nullptr; float* normal = nullptr; uint32_t* ids = nullptr; uint8_t* open = nullptr; uint32_t* frame = nullptr;
-        uint32_t n = 0;                 /* work-items the buffers are sized for */
-        bool written = false;           /* a pass has filled `open` and `frame` */
-        float* dirs = nullptr; uint32_t dirs_K = 0;      /* the table on the device and the K it was built for (0 = none yet) */
-        hipEvent_t done = nullptr;
-        void free_buffers() {
-            for (void* q : {(void*)point, (void*)normal, (void*)ids, (void*)open, (void*)frame}) if (q) (void)hipFree(q);
-            point = normal = nullptr; ids = nullptr; open = nullptr; frame = nullptr; n = 0; written = false;
-        }
-    } ao;
-    /* ray queries (clw_ext_cast_rays / clw_ext_occluded_rays; whitted_cast.inc): the buffers of the host-array entry points -- the rays as uploaded,
-     * the hits, the blocked bytes -- sized for the largest n so far.  Those calls wait for their own work, so nothing is in flight on them between
-     * calls; clw_ext_cast_rays_device works on the caller's memory and owns nothing. */
-    struct Cast {
-        void* rays = nullptr; void* hits = nullptr; uint8_t* blocked = nullptr;
-        uint32_t cap = 0;               /* rays the buffers hold */
-        void free_buffers() {
-            for (void* q : {rays, hits, (void*)blocked}) if (q) (void)hipFree(q);
-            rays = hits = nullptr; blocked = nullptr; cap = 0;
-        }
-    } cast;
-    /* prepared scene cache */
-    const Buffer *prep_s = nullptr, *prep_p = nullptr, *prep_l = nullptr;
-    uint32_t prep_ns = 0, prep_np = 0, prep_nl = 0;
-    float* d_geom = nullptr; size_t geom_f4 = 0;
-    float* d_ptex = nullptr;
-    bool have_lpt = false;    /* the light / plane side table follows the lights in d_geom */
-    uint64_t scene_generation = 0;   /* bumped every time the prepared scene is rebuilt (device pointers can be reused) */
-    uint32_t *d_grid_start = nullptr, *d_grid_items = nullptr, *d_grid_box = nullptr;
-    float* d_grid_geom = nullptr;
-    wprep_grid grid{}; bool grid_ok = false, grid_pair = false; int use_grid = 1;
-    size_t grid_pairs = 0;                       /* cell-list entries of the grid built (clw_ext_get_grid) */
-    int grid_pair_req = -1;                      /* clw_ext_set_grid_pair: -1 = env CLWRAP_GRID_PAIR (default on), 0 / 1 */
-    unsigned long long* d_counters = nullptr;
-    /* cost-sorted tile dispatch: costs written by frame n order the tiles of frame n+1 */
-    int sched = 1;
-    /* Double-buffered: trace k writes its tile costs into cost[k & 1]; when the camera / depth / scene changed, the
-     * order for those costs is built on a SIDE stream behind trace k (order[k & 1], 15 us, 8 workgroups) while trace
-     * k+1 already runs with the order built two frames earlier -- so a moving camera (the interactive loop of
-     * rayinteractive.c:183-197) never waits for the sort.  Any order built for the same tile grid is a valid
-     * permutation, so a stale one only costs balance, never pixels. */
-    struct Sched {
-        unsigned* cost[2] = {nullptr, nullptr}; unsigned* order[2] = {nullptr, nullptr};
-        hipEvent_t built[2] = {nullptr, nullptr};    /* order[i] complete (recorded on the sched stream) */
-        wt_order_state o{};                           /* which order holds a schedule, which cost buffer the next trace writes, what the newest order was
-                                                         built for and how long ago: plain words, stepped by wt_order_* (launch_plan.c) */
-        hipEvent_t traced = nullptr;
-        uint32_t w = 0, rows = 0, cap = 0;           /* frame the buffers were sized for (the virtual frame of a supersampled launch); dispatch entries per XCD share */
-        int ss = 1;                                   /* supersampling factor its orders were built for: it caps how far a tile is split */
-        int last_rd = -1;                             /* order[] the last tiled launch read; -1 = it ran in the default order (clw_ext_read_tile_order) */
-        /* the signature the newest order was built for: camera, depth, scene, and the sample cameras and moving spheres' device tables (empty = none) */
-        RaygenArgs sig{}; int sig_depth = 0; uint64_t sig_scene = 0;
-        wt_cam_table sig_cams{}; bool sig_has_cams = false;
-        std::vector<float> sig_motion;
-        void reset() { o.have[0] = o.have[1] = 0; o.sig_valid = 0; o.newest = 0; last_rd = -1; }
-        void free_all() {
-            for (int i = 0; i < 2; i++) {
-                if (cost[i]) (void)hipFree(cost[i]);
-                if (order[i]) (void)hipFree(order[i]);
-                if (built[i]) (void)hipEventDestroy(built[i]);
-                cost[i] = order[i] = nullptr; built[i] = nullptr;
-            }
-            if (traced) { (void)hipEventDestroy(traced); traced = nullptr; }
-            reset();
-        }
-    };
-    hipStream_t sched_stream = nullptr;
-    static constexpr int MAX_CHUNKS = 4;
-    Sched scheds[1 + MAX_CHUNKS];   /* [0]: whole-range launches; [1 + c]: strip c of a pipelined read-back */
-    /* pipelined read-back (cl_wrap_output of a large frame): strips rendered back to back, each copied to the host
-     * while the next one renders */
-    int pipeline = 1;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t chunk_done[MAX_CHUNKS] = {nullptr, nullptr, nullptr, nullptr};
-    /* timing log */
-    std::vector<TimingEntry> timing;
-    unsigned occ_tiles_per_depth = WT_OCC_TILES_PER_DEPTH;   /* CLWRAP_OCC_TILES_PER_DEPTH: tuning knob */
-    /* the tree-parallel tail of deep launches (whitted_tpt.inc): one slice of node storage per workgroup of the launch */
-    uint32_t* d_tpt_pool = nullptr; uint32_t* d_tpt_flags = nullptr; size_t tpt_pool_bytes = 0;
-    uint32_t* d_tpt_jump = nullptr;              /* 7 x 32 words: M^(2^i), M = one hit's worth of xorshift steps (xorshift_jump_matrices) */
-    unsigned tpt_max = WT_TPT_MAX_LANES, tpt_min = WT_TPT_MIN_PATHS, tpt_pool_mb = WT_TPT_POOL_MB;   /* CLWRAP_TPT_MAX / _MIN / _POOL_MB, clw_ext_set_tpt */
-    int tpt_clock = 0;                                    /* CLWRAP_TPT_CLOCK=1: DIAGNOSTIC phase clock of the tail (counter words 10-25) */
-    unsigned split_slots = WT_SPLIT_SLOTS;                   /* CLWRAP_SPLIT_SLOTS: the quota is a share's total cost over this many wavefronts */
-    unsigned split_min_quota = WT_SPLIT_MIN_QUOTA;           /* CLWRAP_SPLIT_MIN_QUOTA; 0 = heavy tiles are not split */
-    bool timing_on = false;                       /* switched on by the first clw_ext_timing_reset / set_timing_every */
-    uint32_t timing_every = 1, timing_tick = 0;   /* events around every n-th launch only */
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
-};
-
 bool same_acc_key(const Impl::AccKey& a, const Impl::AccKey& b) {
     return same_raygen(a.gen, b.gen) && a.n_out == b.n_out && a.total == b.total && a.depth == b.depth && a.strict == b.strict && a.fuse == b.fuse &&
            a.ss == b.ss && a.max_frames == b.max_frames && a.jitter == b.jitter && !memcmp(&a.through, &b.through, 4) && a.seed == b.seed &&
            !memcmp(a.buf, b.buf, sizeof a.buf) && !memcmp(a.dptr, b.dptr, sizeof a.dptr) && !memcmp(a.size, b.size, sizeof a.size) &&
            !memcmp(a.counts, b.counts, sizeof a.counts) && !memcmp(a.img, b.img, sizeof a.img) && a.epoch == b.epoch;
-}
-
-Impl* impl_of(const cl_wrap* w) {
-    if (!w || !w->impl) die("cl_wrap is not initialised");
-    return (Impl*)w->impl;
-}
-
-void use_device(Impl* I) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != I->device) HIP_OK(hipSetDevice(I->device), "Cannot select the HIP device");
-}
-
-bool is_registered(const cl_wrap* w, cl_uint kernel_id, cl_uint arg_id) {
-    for (cl_uint i = 0; i < w->buffers_num[kernel_id]; i++)
-        if (w->buffers_ids[kernel_id][i] == arg_id) return true;
-    return false;
 }
 
 void check_kernel_id(const cl_wrap* w, cl_uint kernel_id) {
@@ -392,19 +63,6 @@ Buffer* new_buffer(Impl* I) {
     return b;
 }
 
-Buffer* lookup_handle(Impl* I, const void* handle) {
-    for (Buffer* b : I->live)
-        if ((const void*)b == handle) return b;
-    return nullptr;
-}
-
-void ensure_allocated(Impl* I, Buffer* b) {
-    (void)I;
-    if (b->dptr || b->size == 0) return;
-    HIP_OK(hipMalloc(&b->dptr, b->size), "Couldn't allocate device memory");
-    b->lazy = false;
-}
-
 void register_buffer(cl_wrap* w, cl_uint kernel_id, cl_uint arg_id, Buffer* b) {
     w->buffers[kernel_id][arg_id] = (cl_mem)b;
     w->buffers_ids[kernel_id][w->buffers_num[kernel_id]++] = arg_id;
@@ -414,34 +72,6 @@ void precheck_buffer_arg(cl_wrap* w, cl_uint kernel_id, cl_uint arg_id) {
     check_kernel_id(w, kernel_id);
     if (arg_id < __MAX_BUFFERS && is_registered(w, kernel_id, arg_id)) die("Given kernel argument already in use");
     if (arg_id >= __MAX_BUFFERS) die("Wrong kernel ID given"); /* the reference's wording (opencl_wrap.c:144) */
-}
-
-/* ---- launch helpers -------------------------------------------------------------------- */
-std::pair<hipEvent_t, hipEvent_t> take_events(Impl* I) {
-    if (!I->free_events.empty()) {
-        auto p = I->free_events.back();
-        I->free_events.pop_back();
-        return p;
-    }
-    hipEvent_t a, b;
-    HIP_OK(hipEventCreate(&a), "Couldn't create a timing event");
-    HIP_OK(hipEventCreate(&b), "Couldn't create a timing event");
-    return {a, b};
-}
-
-struct LaunchTimer {
-    Impl* I; cl_uint kernel; bool on; std::pair<hipEvent_t, hipEvent_t> ev;
-    LaunchTimer(Impl* I_, cl_uint k, bool wanted = true) : I(I_), kernel(k), on(wanted && I_->timing_on && I_->timing.size() < 16384 && (I_->timing_tick++ % I_->timing_every) == 0) {
-        if (on) { ev = take_events(I); HIP_OK(hipEventRecord(ev.first, I->stream), "Couldn't run the kernel"); }
-    }
-    void done() {
-        if (on) { HIP_OK(hipEventRecord(ev.second, I->stream), "Couldn't run the kernel"); I->timing.push_back({ev.first, ev.second, kernel}); }
-    }
-};
-
-void finish(Impl* I) {
-    hipError_t e = hipStreamSynchronize(I->stream);
-    if (e != hipSuccess) { printf("%d\n", (int)e); die("The device kernel failed"); }
 }
 
 const ArgValue& need_value(const Kernel& k, cl_uint arg, size_t min_size, size_t max_size) {
@@ -489,12 +119,10 @@ void run_raygen_kernel(Impl* I, const RaygenArgs& g, Buffer* rays, cl_uint kerne
     P.id_offset = g.id_offset; P.n_items = n; P.rays = (float*)rays->dptr;
     P.band_stride = g.band_stride; P.band_phase = g.band_phase;
     LaunchTimer t(I, kernel_id);
-    hipError_t e = I->strict ? wt_strict_launch_raygen(&P, I->stream) : wt_fast_launch_raygen(&P, I->stream);
+    hipError_t e = WT_LAUNCH(I, raygen)(&P, I->stream);
     if (e != hipSuccess) die("Couldn't run the kernel");
     t.done();
 }
-
-void finish(Impl* I);
 
 clw_camera camera_of(const RaygenArgs& g) {
     clw_camera c{};
@@ -503,6 +131,8 @@ clw_camera camera_of(const RaygenArgs& g) {
     return c;
 }
 
+} /* namespace */
+namespace clw {
 /* The wrapper's projection resolved for a latched camera: the scalar terms and, for the panorama, the device tables -- uploaded only when they
  * differ from what the device holds, behind a wait for the launches that may still read the old ones.  false = the definition refuses this
  * camera / projection pair (projection_host.c). */
@@ -528,6 +158,8 @@ bool resolve_projection(Impl* I, const RaygenArgs& g, wt_projection& T) {
     T.col = B.d_col; T.row = B.d_row;
     return true;
 }
+} /* namespace clw */
+namespace {
 
 /* wt_raygen_proj over the range a raygen launch latched: the records of the wrapper's projection, logged under the raygen kernel's id */
 void run_raygen_proj_kernel(Impl* I, const RaygenArgs& g, Buffer* rays, cl_uint kernel_id) {
@@ -542,7 +174,7 @@ void run_raygen_proj_kernel(Impl* I, const RaygenArgs& g, Buffer* rays, cl_uint 
     P.id_offset = g.id_offset; P.n_items = n; P.rays = (float*)rays->dptr;
     P.band_stride = g.band_stride; P.band_phase = g.band_phase;
     LaunchTimer t(I, kernel_id);
-    hipError_t e = (I->strict ? wt_strict_launch_raygen_proj : wt_fast_launch_raygen_proj)(&P, &T, I->stream);
+    hipError_t e = WT_LAUNCH(I, raygen_proj)(&P, &T, I->stream);
     if (e != hipSuccess) die("Couldn't run the kernel");
     t.done();
 }
@@ -560,17 +192,6 @@ void materialise_rays(Impl* I, Buffer* b) {
     b->gen_proj = I->proj;
 }
 
-uint32_t read_count(const Kernel& k, cl_uint arg) {
-    const ArgValue& v = k.values[arg];
-    if (!v.set) die("Couldn't run the kernel");
-    switch (v.size) { /* uchar in the reference (raytracing.cl:17); 2/4 bytes = wide-count extension */
-        case 1: return v.bytes[0];
-        case 2: { uint16_t x; memcpy(&x, v.bytes, 2); return x; }
-        case 4: { uint32_t x; memcpy(&x, v.bytes, 4); return x; }
-        default: die("Couldn't run the kernel");
-    }
-}
-
 const uint8_t* host_view(Impl* I, Buffer* b, size_t need, std::vector<uint8_t>& tmp) {
     if (b->size < need) die("Couldn't run the kernel");
     if (b->shadow.size() >= need) return b->shadow.data();
@@ -580,10 +201,6 @@ const uint8_t* host_view(Impl* I, Buffer* b, size_t need, std::vector<uint8_t>& 
     return tmp.data();
 }
 
-int env_int(const char* name, int dflt) {
-    const char* s = getenv(name);
-    return (s && *s) ? atoi(s) : dflt;
-}
 /* a float from the environment; anything that is not a number reads as NaN, which every caller refuses */
 float env_float(const char* name, float dflt) {
     const char* s = getenv(name);
@@ -607,6 +224,8 @@ void xorshift_jump_matrices(uint32_t steps, uint32_t out[7][32]) {
     for (int i = 1; i < 7; i++) mul(out[i - 1], out[i - 1], out[i]);
 }
 
+} /* namespace */
+namespace clw {
 void prepare_scene(Impl* I, Buffer* s, uint32_t ns, Buffer* p, uint32_t np, Buffer* l, uint32_t nl) {
     if (I->d_geom && I->prep_s == s && I->prep_p == p && I->prep_l == l && I->prep_ns == ns &&
         I->prep_np == np && I->prep_nl == nl)
@@ -674,30 +293,18 @@ void prepare_scene(Impl* I, Buffer* s, uint32_t ns, Buffer* p, uint32_t np, Buff
     I->scene_generation++;
     I->prep_s = s; I->prep_p = p; I->prep_l = l; I->prep_ns = ns; I->prep_np = np; I->prep_nl = nl;
 }
+} /* namespace clw */
+namespace {
 
 Buffer* buffer_arg(cl_wrap* w, cl_uint kernel_id, cl_uint arg) {
     if (!is_registered(w, kernel_id, arg)) die("Couldn't run the kernel");
     return (Buffer*)w->buffers[kernel_id][arg];
 }
 
-/* arg 0 of the raytracer: the ray buffer, passed by value as the 8 bytes of a handle (raypng.c:61) or bound as a buffer; null = neither */
-Buffer* find_rays(const cl_wrap* w, Impl* I, cl_uint kid) {
-    if (is_registered(w, kid, 0)) return (Buffer*)w->buffers[kid][0];
-    const ArgValue& v = I->kernels[kid].values[0];
-    if (!v.set || v.size != sizeof(cl_mem)) return nullptr;
-    void* h; memcpy(&h, v.bytes, sizeof h);
-    return lookup_handle(I, h);
-}
 Buffer* rays_of(const cl_wrap* w, Impl* I, cl_uint kid) {
     Buffer* rays = find_rays(w, I, kid);
     if (!rays) die("Couldn't run the kernel");
     return rays;
-}
-/* arg 7 of the raytracer: the guard `total_size` (raytracing.cl:24) */
-bool find_total(const Kernel& k, uint32_t& total) {
-    if (!k.values[7].set || k.values[7].size != 4) return false;
-    memcpy(&total, k.values[7].bytes, 4);
-    return true;
 }
 uint32_t total_of(const Kernel& k) {
     uint32_t total;
@@ -729,18 +336,13 @@ void prepare_bound_scene(cl_wrap* w, Impl* I, cl_uint kid) {
 /* ... and its device pointers, with the words that describe what they point to (flags: the geometry class, wt_plan_geometry) */
 void bind_scene_pointers(const cl_wrap* w, Impl* I, cl_uint kid, whitted_params& P, int flags) {
     const Buffer *bs = (Buffer*)w->buffers[kid][1], *bp = (Buffer*)w->buffers[kid][2], *tex = (Buffer*)w->buffers[kid][8], *sky = (Buffer*)w->buffers[kid][9];
-    P.geom = I->d_geom; P.ptex = I->d_ptex;
+    bind_geometry(I, P, flags);
     P.spheres_raw = (const uint8_t*)bs->dptr; P.planes_raw = (const uint8_t*)bp->dptr;
     P.tex = (const uint32_t*)tex->dptr; P.tex_w = (int)tex->w; P.tex_h = (int)tex->h; P.tex_layers = (int)tex->layers;
     P.sky = (const uint32_t*)sky->dptr; P.sky_w = (int)sky->w; P.sky_h = (int)sky->h;
-    if (flags & WT_F_GRID) {
-        P.grid_pair = I->grid_pair ? 1u : 0u;
-        P.grid_start = I->d_grid_start; P.grid_items = I->d_grid_items; P.grid_box = I->d_grid_box; P.grid_geom = I->d_grid_geom;
-        for (int a = 0; a < 3; a++) {
-            P.grid_min[a] = I->grid.gmin[a]; P.grid_inv[a] = I->grid.inv[a]; P.grid_cell[a] = I->grid.cell[a]; P.grid_res[a] = I->grid.res[a];
-        }
-    }
 }
+} /* namespace */
+namespace clw {
 /* both, for the launches that are not planned (the primary-hit pass, clw_ext_unit_scene): fills the scene fields of P and chooses between the
  * uniform grid, LDS-staged geometry and geometry read from global memory (flags WT_F_GRID / WT_F_GEOM_LDS, dynamic LDS bytes) */
 void bind_scene(cl_wrap* w, Impl* I, cl_uint kid, whitted_params& P, int& flags, size_t& dyn_lds) {
@@ -748,11 +350,12 @@ void bind_scene(cl_wrap* w, Impl* I, cl_uint kid, whitted_params& P, int& flags,
     const wt_geom_class gc = wt_plan_geometry(I->strict, I->variant, I->prep_ns, I->prep_np, (uint32_t)I->geom_f4, I->have_lpt, I->grid_ok && I->use_grid);
     flags |= gc.flags;
     if (gc.flags & WT_F_GEOM_LDS) dyn_lds = gc.dyn_lds;
-    P.ns = I->prep_ns; P.np = I->prep_np; P.nl = I->prep_nl; P.geom_f4 = (uint32_t)I->geom_f4;
     P.lpt = gc.lpt; P.vis = gc.vis;
     P.through = I->through;
     bind_scene_pointers(w, I, kid, P, gc.flags);
 }
+} /* namespace clw */
+namespace {
 
 /* one strip of a frame: rows [row0, row0 + rows) of the launch range, scheduling state in scheds[slot] */
 struct Strip { uint32_t row0, rows; int slot; };
@@ -989,7 +592,7 @@ bool trace_launch(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size, const Str
     I->last_trace_flags = plan.flags;
     bind_tail_pool(I, plan);
     LaunchTimer t(I, kid, pass == PASS_PLAIN);      /* (an adaptive launch is timed as one: run_raytracer) */
-    hipError_t e = (I->strict ? wt_strict_launch_trace : wt_fast_launch_trace)(&plan.P, plan.flags, plan.grid, plan.dyn_lds, I->stream);
+    hipError_t e = WT_LAUNCH(I, trace)(&plan.P, plan.flags, plan.grid, plan.dyn_lds, I->stream);
     if (e != hipSuccess) die("Couldn't run the kernel");
     t.done();
     if (plan.P.tile_cost) sort_tile_costs(I, S, plan, sort);
@@ -1115,193 +718,6 @@ void run_raygen(cl_wrap* w, Impl* I, cl_uint kid, size_t array_size) {
         rays->gen_materialised = true;
         rays->gen_proj = I->proj;
     }
-}
-
-/* ---- the primary-hit pass -------------------------------------------------------------------------------------------------------- */
-constexpr uint32_t GB_WORDS[5] = {1, 1, 3, 3, 3};      /* 4-byte words per work-item of the channels depth, id, normal, point, albedo */
-
-/* The pass's launch parameters over the range the next trace launch would cover: the camera and range the raygen launch latched, clipped by
- * the raytracer's `pixels` argument, bands included; the scene as bind_scene binds it.  false (nothing filled in) when there is no raytracer
- * kernel, no latched camera or no bound scene yet -- the callers return 0 then, they do not terminate the process. */
-bool gbuffer_params(cl_wrap* w, Impl* I, whitted_params& P, int& flags, size_t& dyn_lds, wt_projection& T) {
-    memset(&T, 0, sizeof T);      /* model 0: the pinhole */
-    cl_uint kid = 0;
-    while (kid < I->kernels.size() && I->kernels[kid].kind != K_RAYTRACER) kid++;
-    if (kid >= I->kernels.size()) return false;
-    const Kernel& k = I->kernels[kid];
-    Buffer* rays = find_rays(w, I, kid);
-    if (!rays || !rays->gen_valid) return false;
-    for (cl_uint a : {1u, 2u, 3u, 8u, 9u}) if (!is_registered(w, kid, a)) return false;
-    for (cl_uint a : {4u, 5u, 6u}) if (!k.values[a].set) return false;
-    uint32_t total;
-    if (!find_total(k, total)) return false;
-    const RaygenArgs& g = rays->gen;
-    const uint32_t n = g.n_items < total ? g.n_items : total;
-    if (n == 0) return false;
-    if (I->proj.model != CLW_PROJ_PERSPECTIVE && !resolve_projection(I, g, T)) return false;      /* (before anything is bound or launched) */
-    bind_scene(w, I, kid, P, flags, dyn_lds);
-    wt_plan_fused_range(&g, n, &P);      /* as the fused trace launch: the rays are this library's own */
-    if (T.model != CLW_PROJ_PERSPECTIVE) P.unit_dirs = 0u;      /* as the trace launch of a projected view: no direction is taken for unit */
-    P.vis = 0;
-    return true;
-}
-
-void launch_gbuffer(Impl* I, const whitted_params& P, int flags, size_t dyn_lds, void* const chan[5], const wt_projection& T, bool timed) {
-    const unsigned grid = wt_plan_grid(&P);      /* as trace_launch: tile rows dealt to the 8 XCDs */
-    LaunchTimer t(I, CLW_TIMING_GBUFFER, timed);
-    hipError_t e = (I->strict ? wt_strict_launch_gbuffer : wt_fast_launch_gbuffer)(&P, flags, grid, dyn_lds, (float*)chan[0], (unsigned*)chan[1], (float*)chan[2],
-                                                                                   (float*)chan[3], (float*)chan[4], &T, I->stream);
-    if (e != hipSuccess) die("Couldn't run the kernel");
-    t.done();
-}
-
-/* index of a single CLW_GB_* bit, -1 for anything else */
-int gbuffer_channel(uint32_t channel) {
-    for (int c = 0; c < 5; c++) if (channel == (1u << c)) return c;
-    return -1;
-}
-
-/* ---- ray queries ------------------------------------------------------------------------------------------------------------------ */
-/* The scene side of a query of n rays: the raytracer's arguments 1-6, prepared as a primary-hit pass prepares them (once per scene), and the plan
- * (wt_plan_cast).  Needs no ray buffer, no camera, no images and no framebuffer.  false (nothing prepared or filled in) when there is no
- * raytracer kernel or no bound scene -- the callers return 0 then, they do not terminate the process. */
-bool cast_params(cl_wrap* w, Impl* I, uint32_t n, whitted_params& P, wt_cast_class& cc) {
-    cl_uint kid = 0;
-    while (kid < I->kernels.size() && I->kernels[kid].kind != K_RAYTRACER) kid++;
-    if (kid >= I->kernels.size()) return false;
-    const Kernel& k = I->kernels[kid];
-    for (cl_uint a : {1u, 2u, 3u}) if (!is_registered(w, kid, a)) return false;
-    for (cl_uint a : {4u, 5u, 6u}) if (!k.values[a].set) return false;
-    Buffer* bs = (Buffer*)w->buffers[kid][1];
-    Buffer* bp = (Buffer*)w->buffers[kid][2];
-    Buffer* bl = (Buffer*)w->buffers[kid][3];
-    prepare_scene(I, bs, read_count(k, 4), bp, read_count(k, 5), bl, read_count(k, 6));
-    cc = wt_plan_cast(I->variant, I->prep_ns, (uint32_t)I->geom_f4, I->grid_ok && I->use_grid, n, (uint32_t)std::max(0, env_int("CLWRAP_CAST_BATCHES", 0)));   /* CLWRAP_CAST_BATCHES: tuning knob */
-    if (cc.groups == 0u) return false;
-    P.ns = I->prep_ns; P.np = I->prep_np; P.nl = I->prep_nl; P.geom_f4 = (uint32_t)I->geom_f4;
-    P.geom = I->d_geom; P.ptex = I->d_ptex;
-    if (cc.flags & WT_F_GRID) {
-        P.grid_pair = I->grid_pair ? 1u : 0u;
-        P.grid_start = I->d_grid_start; P.grid_items = I->d_grid_items; P.grid_box = I->d_grid_box; P.grid_geom = I->d_grid_geom;
-        for (int a = 0; a < 3; a++) {
-            P.grid_min[a] = I->grid.gmin[a]; P.grid_inv[a] = I->grid.inv[a]; P.grid_cell[a] = I->grid.cell[a]; P.grid_res[a] = I->grid.res[a];
-        }
-    }
-    return true;
-}
-
-/* wt_cast over device memory on the launch stream; exactly one of hits / blocked */
-void launch_cast(Impl* I, const whitted_params& P, const wt_cast_class& cc, const void* rays, uint32_t n, uint32_t flags, void* hits, uint8_t* blocked) {
-    LaunchTimer t(I, CLW_TIMING_CAST, true);
-    hipError_t e = (I->strict ? wt_strict_launch_cast : wt_fast_launch_cast)(&P, cc.flags, cc.groups, cc.batches, cc.dyn_lds, rays, n, flags, hits, blocked, I->stream);
-    if (e != hipSuccess) die("Couldn't run the kernel");
-    t.done();
-}
-
-/* the two host-array entry points: upload, launch, read back, all in the order of the launch stream, then wait */
-uint32_t cast_host_arrays(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uint32_t flags, clw_hit* hits, uint8_t* blocked) {
-    Impl* I = impl_of(wrap);
-    use_device(I);
-    static_assert(sizeof(clw_ray) == 32 && sizeof(clw_hit) == 32, "the queries' ABI");
-    if (!wt_cast_check(n, flags) || !rays || (!hits && !blocked)) return 0;
-    whitted_params P{};
-    wt_cast_class cc;
-    if (!cast_params(wrap, I, n, P, cc)) return 0;
-    Impl::Cast& C = I->cast;
-    if (C.cap < n) {
-        C.free_buffers();
-        HIP_OK(hipMalloc(&C.rays, (size_t)n * sizeof(clw_ray)), "Couldn't allocate device memory");
-        HIP_OK(hipMalloc(&C.hits, (size_t)n * sizeof(clw_hit)), "Couldn't allocate device memory");
-        HIP_OK(hipMalloc((void**)&C.blocked, (size_t)n), "Couldn't allocate device memory");
-        C.cap = n;
-    }
-    HIP_OK(hipMemcpyAsync(C.rays, rays, (size_t)n * sizeof(clw_ray), hipMemcpyHostToDevice, I->stream), "Couldn't transfer the data from host to the device");
-    launch_cast(I, P, cc, C.rays, n, flags, hits ? C.hits : nullptr, hits ? nullptr : C.blocked);
-    if (hits) HIP_OK(hipMemcpyAsync(hits, C.hits, (size_t)n * sizeof(clw_hit), hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
-    else HIP_OK(hipMemcpyAsync(blocked, C.blocked, (size_t)n, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
-    finish(I);
-    return n;
-}
-
-/* ---- the selection overlay ------------------------------------------------------------------------------------------------------- */
-/* wt_overlay over a width x rows range on the launch stream; the caller has checked style and selection (wt_overlay_check).  The kernel is
- * integer work compiled into both units; the build in use launches its own copy. */
-void launch_overlay(Impl* I, const uint32_t* frame, const uint32_t* ids, uint32_t* out, uint32_t width, uint32_t rows, const clw_overlay& st,
-                    const uint32_t* sel, uint32_t count, bool timed) {
-    const unsigned style[5] = {st.radius, st.outline_rgb, st.fill_rgb, st.fill_alpha, st.edge_rgb};
-    LaunchTimer t(I, CLW_TIMING_OVERLAY, timed);
-    hipError_t e = (I->strict ? wt_strict_launch_overlay : wt_fast_launch_overlay)(frame, ids, out, width, rows, st.flags, style, sel, count, I->stream);
-    if (e != hipSuccess) die("Couldn't run the kernel");
-    t.done();
-}
-
-/* ---- ambient occlusion ------------------------------------------------------------------------------------------------------------ */
-/* the direction table of K rays on the device: built by the definition (clw_host_ao_dirs) and uploaded only when K changes -- then behind a wait
- * for whatever the launch stream still runs, which may read the old one */
-const float* ao_dirs(Impl* I, uint32_t K) {
-    Impl::AO& O = I->ao;
-    if (O.dirs && O.dirs_K == K) return O.dirs;
-    std::vector<float> tab(4 * (size_t)WT_AO_PATTERNS * K);
-    if (!clw_host_ao_dirs(K, tab.data())) die("Couldn't run the kernel");
-    if (!O.dirs) HIP_OK(hipMalloc((void**)&O.dirs, 4 * sizeof(float) * WT_AO_PATTERNS * WT_AO_MAX_RAYS), "Couldn't allocate device memory");
-    finish(I);
-    if (O.done) (void)hipEventSynchronize(O.done);
-    HIP_OK(hipMemcpy(O.dirs, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
-    O.dirs_K = K;
-    return O.dirs;
-}
-
-/* wt_ao_trace over device channels of a width x rows range on the launch stream, the scene as `P` and `flags` bind it (bind_scene); the caller
- * has checked `ao` and the range (wt_ao_check, wt_ao_range_ok) */
-void launch_ao_trace(Impl* I, const whitted_params& P, int flags, const float* point, const float* normal, const uint32_t* ids, uint32_t width,
-                     uint32_t rows, uint32_t first_row, const clw_ao& ao, uint8_t* open, bool timed) {
-    const float* dirs = ao_dirs(I, ao.rays);
-    LaunchTimer t(I, CLW_TIMING_AO, timed);
-    hipError_t e = (I->strict ? wt_strict_launch_ao_trace : wt_fast_launch_ao_trace)(&P, flags, point, normal, ids, dirs, open, width, rows, first_row,
-                                                                                     ao.rays, ao.radius, I->stream);
-    if (e != hipSuccess) die("Couldn't run the kernel");
-    t.done();
-}
-
-/* wt_ao_resolve likewise.  Integer work compiled into both units; the build in use launches its own copy. */
-void launch_ao_resolve(Impl* I, const uint8_t* open, const uint32_t* ids, const uint32_t* frame, uint32_t* out, uint32_t width, uint32_t rows,
-                       const clw_ao& ao, bool timed) {
-    LaunchTimer t(I, CLW_TIMING_AO_RESOLVE, timed);
-    hipError_t e = (I->strict ? wt_strict_launch_ao_resolve : wt_fast_launch_ao_resolve)(open, ids, frame, out, width, rows, ao.flags, ao.rays, ao.strength,
-                                                                                         I->stream);
-    if (e != hipSuccess) die("Couldn't run the kernel");
-    t.done();
-}
-
-/* ---- the visible-object table ---------------------------------------------------------------------------------------------------- */
-/* The clear of the slot table, wt_objects_reduce and wt_objects_compact over device channels of a width x rows range on the launch stream, then
- * the read-back of the summary and of min(objects, capacity) records; waits.  The caller has checked the arguments (wt_objects_check).  The
- * kernels are integer work compiled into both units; the build in use launches its own copy. */
-void run_objects(Impl* I, const uint32_t* ids, const float* depth, uint32_t width, uint32_t rows, uint32_t first_row, const clw_rect* rect,
-                 const uint32_t counts[3], clw_object_stat* out, uint32_t capacity, clw_object_summary* summary, bool timed) {
-    static_assert(sizeof(clw_object_stat) == 48 && sizeof(clw_object_summary) == 16 && sizeof(clw_rect) == 16, "the table's ABI");
-    uint32_t clip[4];
-    (void)wt_objects_clip(width, rows, first_row, rect, clip);      /* a rectangle that misses the range: clip = 0 -> nothing reduced, an empty table */
-    Impl::Objects& O = I->obj;
-    O.size_table(counts[0] + counts[1] + counts[2] + 1u);
-    {
-        LaunchTimer t(I, CLW_TIMING_OBJECTS, timed);
-        hipError_t e = (I->strict ? wt_strict_launch_objects : wt_fast_launch_objects)(ids, (const unsigned*)depth, width, rows, first_row, clip, counts,
-                                                                                       O.table, O.result, I->stream);
-        if (e != hipSuccess) die("Couldn't run the kernel");
-        t.done();
-    }
-    clw_object_summary h;
-    if (hipMemcpyAsync(&h, O.result, sizeof h, hipMemcpyDeviceToHost, I->stream) != hipSuccess) die("Failed to transfer device memory to host");
-    finish(I);
-    const uint32_t n = !out ? 0u : h.objects < capacity ? h.objects : capacity;
-    if (n) {
-        if (n > O.slots) die("The device kernel failed");      /* (more records than slots cannot be) */
-        if (hipMemcpyAsync(out, (const uint8_t*)O.result + sizeof h, (size_t)n * sizeof(clw_object_stat), hipMemcpyDeviceToHost, I->stream) != hipSuccess)
-            die("Failed to transfer device memory to host");
-        finish(I);
-    }
-    *summary = h;
 }
 
 } /* namespace */
@@ -1540,15 +956,10 @@ void cl_wrap_release(cl_wrap* wrap) {
     if (I->d_cams) (void)hipFree(I->d_cams);
     if (I->d_motion) (void)hipFree(I->d_motion);
     if (I->acc.sum) (void)hipFree(I->acc.sum);
-    I->gb.free_channels();
-    if (I->gb.pick) (void)hipFree(I->gb.pick);
-    if (I->gb.done) (void)hipEventDestroy(I->gb.done);
-    I->ov.free_buffers();
-    if (I->ov.done) (void)hipEventDestroy(I->ov.done);
-    I->obj.free_buffers();
-    I->ao.free_buffers();
-    if (I->ao.dirs) (void)hipFree(I->ao.dirs);
-    if (I->ao.done) (void)hipEventDestroy(I->ao.done);
+    I->gb.release();
+    I->ov.release();
+    I->obj.release();
+    I->ao.release();
     I->cast.free_buffers();
     I->ptab.free_all();
     I->adapt.free_all();
@@ -1605,8 +1016,7 @@ void clw_ext_unit(cl_wrap* wrap, int op, const float* in, uint32_t stride_in, fl
     HIP_OK(hipMemcpy(din, in, (size_t)n * stride_in * 4, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
     HIP_OK(hipMemset(dout, 0, (size_t)n * stride_out * 4), "Couldn't allocate device memory");
     HIP_OK(hipDeviceSynchronize(), "The device kernel failed");
-    hipError_t e = I->strict ? wt_strict_launch_unit(op, din, dout, n, stride_in, stride_out, aux, I->stream)
-                             : wt_fast_launch_unit(op, din, dout, n, stride_in, stride_out, aux, I->stream);
+    hipError_t e = WT_LAUNCH(I, unit)(op, din, dout, n, stride_in, stride_out, aux, I->stream);
     if (e != hipSuccess) die("Couldn't run the kernel");
     finish(I);
     HIP_OK(hipMemcpy(out, dout, (size_t)n * stride_out * 4, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
@@ -1630,8 +1040,7 @@ void clw_ext_unit_scene(cl_wrap* wrap, cl_uint kernel_id, int op, const float* i
     HIP_OK(hipMemcpy(din, in, (size_t)n * stride_in * 4, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
     HIP_OK(hipMemset(dout, 0, (size_t)n * stride_out * 4), "Couldn't allocate device memory");
     HIP_OK(hipDeviceSynchronize(), "The device kernel failed");
-    hipError_t e = I->strict ? wt_strict_launch_unit_scene(&P, flags, op, din, dout, n, stride_in, stride_out, dyn_lds, I->stream)
-                             : wt_fast_launch_unit_scene(&P, flags, op, din, dout, n, stride_in, stride_out, dyn_lds, I->stream);
+    hipError_t e = WT_LAUNCH(I, unit_scene)(&P, flags, op, din, dout, n, stride_in, stride_out, dyn_lds, I->stream);
     if (e != hipSuccess) die("Couldn't run the kernel");
     finish(I);
     HIP_OK(hipMemcpy(out, dout, (size_t)n * stride_out * 4, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
@@ -1823,380 +1232,22 @@ int clw_ext_unit_projection(cl_wrap* wrap, const clw_camera* cam, const clw_proj
     const uint64_t total = (uint64_t)cam->width * cam->height;
     if (id_begin >= id_end || id_end > total || id_end - id_begin > 0x03FFFFFFull) return 0;      /* (64 n bytes in 32 bits) */
     const uint32_t n = (uint32_t)(id_end - id_begin);
-    float *drays = nullptr, *dcol = nullptr, *drow = nullptr;
+    std::vector<float> col, row;      /* the panorama's tables; the other model has none: null host arrays, null device pointers */
     if (T.model == CLW_PROJ_EQUIRECT) {
-        std::vector<float> col(4 * (size_t)cam->width), row(4 * (size_t)cam->height);
+        col.resize(4 * (size_t)cam->width); row.resize(4 * (size_t)cam->height);
         if (!clw_host_projection_tables(cam, proj, col.data(), row.data())) return 0;
-        HIP_OK(hipMalloc((void**)&dcol, col.size() * sizeof(float)), "Couldn't allocate device memory");
-        HIP_OK(hipMalloc((void**)&drow, row.size() * sizeof(float)), "Couldn't allocate device memory");
-        HIP_OK(hipMemcpy(dcol, col.data(), col.size() * sizeof(float), hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
-        HIP_OK(hipMemcpy(drow, row.data(), row.size() * sizeof(float), hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
-        T.col = dcol; T.row = drow;
     }
-    HIP_OK(hipMalloc((void**)&drays, (size_t)n * 64), "Couldn't allocate device memory");
+    const DeviceTemp<float> dcol(col.empty() ? nullptr : col.data(), col.size() * sizeof(float)), drow(row.empty() ? nullptr : row.data(), row.size() * sizeof(float));
+    const DeviceTemp<float> drays((size_t)n * 64);
+    if (T.model == CLW_PROJ_EQUIRECT) { T.col = dcol; T.row = drow; }
     HIP_OK(hipDeviceSynchronize(), "The device kernel failed");
     raygen_params P{};
     P.width = cam->width; P.height = cam->height; P.id_offset = id_begin; P.n_items = n; P.rays = drays; P.band_stride = 1; P.band_phase = 0;
-    hipError_t e = (I->strict ? wt_strict_launch_raygen_proj : wt_fast_launch_raygen_proj)(&P, &T, I->stream);
+    hipError_t e = WT_LAUNCH(I, raygen_proj)(&P, &T, I->stream);
     if (e != hipSuccess) die("Couldn't run the kernel");
     finish(I);
-    HIP_OK(hipMemcpy(out_rays, drays, (size_t)n * 64, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
-    (void)hipFree(drays);
-    if (dcol) (void)hipFree(dcol);
-    if (drow) (void)hipFree(drow);
+    drays.read(out_rays, (size_t)n * 64);
     return 1;
-}
-
-uint32_t clw_ext_render_gbuffer(cl_wrap* wrap, uint32_t channels) {
-    Impl* I = impl_of(wrap);
-    use_device(I);
-    channels &= CLW_GB_ALL;
-    if (!channels) return 0;
-    whitted_params P{};
-    int flags = 0;
-    size_t dyn_lds = 0;
-    wt_projection T;
-    if (!gbuffer_params(wrap, I, P, flags, dyn_lds, T)) return 0;
-    Impl::GBuffer& B = I->gb;
-    if (B.n != P.n_items) {      /* another range: a pass under way may still write the old buffers */
-        if (B.n) { finish(I); if (B.done) (void)hipEventSynchronize(B.done); }
-        B.free_channels();
-        B.n = P.n_items;
-    }
-    void* chan[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int c = 0; c < 5; c++) {
-        if (!(channels & (1u << c))) continue;
-        if (!B.chan[c]) HIP_OK(hipMalloc(&B.chan[c], (size_t)B.n * GB_WORDS[c] * 4), "Couldn't allocate device memory");
-        chan[c] = B.chan[c];
-    }
-    launch_gbuffer(I, P, flags, dyn_lds, chan, T, true);
-    if (!B.done) HIP_OK(hipEventCreateWithFlags(&B.done, hipEventDisableTiming), "Couldn't create a timing event");
-    HIP_OK(hipEventRecord(B.done, I->stream), "Couldn't run the kernel");
-    B.written = channels;
-    return B.n;
-}
-
-uint32_t clw_ext_read_gbuffer(cl_wrap* wrap, uint32_t channel, void* out, uint32_t capacity_bytes) {
-    Impl* I = impl_of(wrap);
-    use_device(I);
-    const Impl::GBuffer& B = I->gb;
-    const int c = gbuffer_channel(channel);
-    if (c < 0 || !(B.written & channel) || !B.chan[c]) return 0;
-    const uint64_t bytes = (uint64_t)B.n * GB_WORDS[c] * 4;
-    if (bytes > 0xFFFFFFFFull) return 0;
-    if (out && capacity_bytes >= bytes) {
-        hipError_t e = hipEventSynchronize(B.done);
-        if (e != hipSuccess) { printf("%d\n", (int)e); die("The device kernel failed"); }
-        HIP_OK(hipMemcpy(out, B.chan[c], (size_t)bytes, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
-    }
-    return (uint32_t)bytes;
-}
-
-void* clw_ext_gbuffer_device_ptr(cl_wrap* wrap, uint32_t channel) {
-    const Impl::GBuffer& B = impl_of(wrap)->gb;
-    const int c = gbuffer_channel(channel);
-    return (c < 0 || !(B.written & channel)) ? nullptr : B.chan[c];
-}
-
-int clw_ext_pick(cl_wrap* wrap, uint32_t x, uint32_t y, clw_pick* out) {
-    Impl* I = impl_of(wrap);
-    use_device(I);
-    if (!out) return 0;
-    whitted_params P{};
-    int flags = 0;
-    size_t dyn_lds = 0;
-    wt_projection T;
-    if (!gbuffer_params(wrap, I, P, flags, dyn_lds, T)) return 0;
-    if (x >= P.width || y >= P.height) return 0;
-    /* is the pixel one of the wrapper's work-items? */
-    if (P.band_stride > 1u) {
-        const uint32_t band = y / 8u;
-        if (band % P.band_stride != P.band_phase) return 0;
-        const uint64_t item = (uint64_t)((band / P.band_stride) * 8u + y % 8u) * P.width + x;
-        if (item >= P.n_items) return 0;
-    } else {
-        const uint64_t id = (uint64_t)y * P.width + x;
-        if (id < P.id_offset || id - P.id_offset >= P.n_items) return 0;
-    }
-    /* the same kernel on the one-pixel range [id, id + 1): a linear range, whose work-item takes (id % W, id / W) = (x, y) */
-    P.id_offset = (uint64_t)y * P.width + x; P.n_items = 1;
-    P.band_stride = 1; P.band_phase = 0; P.tiled = 0; P.rows = 0; P.row_offset = y;
-    Impl::GBuffer& B = I->gb;
-    if (!B.pick) HIP_OK(hipMalloc((void**)&B.pick, sizeof(clw_pick)), "Couldn't allocate device memory");
-    static_assert(sizeof(clw_pick) == 44, "clw_pick is 11 words");
-    void* chan[5] = {B.pick + 1, B.pick + 0, B.pick + 5, B.pick + 2, B.pick + 8};      /* depth, id, normal, point, albedo as clw_pick lays them out */
-    launch_gbuffer(I, P, flags, dyn_lds, chan, T, false);
-    clw_pick h;
-    if (hipMemcpyAsync(&h, B.pick, sizeof h, hipMemcpyDeviceToHost, I->stream) != hipSuccess) die("Failed to transfer device memory to host");
-    finish(I);
-    *out = h;
-    return 1;
-}
-
-uint32_t clw_ext_render_overlay(cl_wrap* wrap, const clw_overlay* style, const uint32_t* sel, uint32_t count) {
-    Impl* I = impl_of(wrap);
-    use_device(I);
-    if (!wt_overlay_check(style, sel, count)) return 0;
-    if (I->band_stride > 1u) return 0;
-    cl_uint kid = 0;
-    while (kid < I->kernels.size() && I->kernels[kid].kind != K_RAYTRACER) kid++;
-    if (kid >= I->kernels.size() || !is_registered(wrap, kid, 10)) return 0;
-    whitted_params P{};
-    int flags = 0;
-    size_t dyn_lds = 0;
-    wt_projection T;
-    if (!gbuffer_params(wrap, I, P, flags, dyn_lds, T)) return 0;
-    /* whole rows of one contiguous range: work-item i is pixel (i % width, i / width) of the range's own image */
-    if (P.band_stride > 1u || !P.tiled || P.rows == 0u) return 0;
-    Buffer* fb = (Buffer*)wrap->buffers[kid][10];
-    if (fb->size < (size_t)P.n_items * 4) return 0;
-    ensure_allocated(I, fb);
-    Impl::Overlay& O = I->ov;
-    if (O.n != P.n_items) {      /* another range: a pass under way may still use the old buffers */
-        if (O.n) { finish(I); if (O.done) (void)hipEventSynchronize(O.done); }
-        O.free_buffers();
-        HIP_OK(hipMalloc((void**)&O.ids, (size_t)P.n_items * 4), "Couldn't allocate device memory");
-        HIP_OK(hipMalloc((void**)&O.frame, (size_t)P.n_items * 4), "Couldn't allocate device memory");
-        O.n = P.n_items;
-    }
-    void* chan[5] = {nullptr, O.ids, nullptr, nullptr, nullptr};
-    launch_gbuffer(I, P, flags, dyn_lds, chan, T, true);
-    launch_overlay(I, (const uint32_t*)fb->dptr, O.ids, O.frame, P.width, P.rows, *style, sel, count, true);
-    if (!O.done) HIP_OK(hipEventCreateWithFlags(&O.done, hipEventDisableTiming), "Couldn't create a timing event");
-    HIP_OK(hipEventRecord(O.done, I->stream), "Couldn't run the kernel");
-    O.written = true;
-    return O.n;
-}
-
-uint32_t clw_ext_read_overlay(cl_wrap* wrap, void* out, uint32_t capacity_bytes) {
-    Impl* I = impl_of(wrap);
-    use_device(I);
-    const Impl::Overlay& O = I->ov;
-    if (!O.written) return 0;
-    const uint64_t bytes = (uint64_t)O.n * 4;
-    if (bytes > 0xFFFFFFFFull) return 0;
-    if (out && capacity_bytes >= bytes) {
-        hipError_t e = hipEventSynchronize(O.done);
-        if (e != hipSuccess) { printf("%d\n", (int)e); die("The device kernel failed"); }
-        HIP_OK(hipMemcpy(out, O.frame, (size_t)bytes, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
-    }
-    return (uint32_t)bytes;
-}
-
-void* clw_ext_overlay_device_ptr(cl_wrap* wrap) {
-    const Impl::Overlay& O = impl_of(wrap)->ov;
-    return O.written ? O.frame : nullptr;
-}
-
-uint32_t clw_ext_unit_overlay(cl_wrap* wrap, const uint32_t* frame, const uint32_t* ids, uint32_t width, uint32_t rows, const clw_overlay* style,
-                              const uint32_t* sel, uint32_t count, uint32_t* out) {
-    Impl* I = impl_of(wrap);
-    use_device(I);
-    if (!wt_overlay_check(style, sel, count) || width == 0u || rows == 0u || !frame || !ids || !out) return 0;
-    const uint64_t n = (uint64_t)width * rows;
-    if (n > 0x3FFFFFFFull) return 0;      /* (4 n bytes per buffer in 32 bits) */
-    const size_t bytes = (size_t)n * 4;
-    uint32_t *dframe = nullptr, *dids = nullptr, *dout = nullptr;
-    HIP_OK(hipMalloc((void**)&dframe, bytes), "Couldn't allocate device memory");
-    HIP_OK(hipMalloc((void**)&dids, bytes), "Couldn't allocate device memory");
-    HIP_OK(hipMalloc((void**)&dout, bytes), "Couldn't allocate device memory");
-    HIP_OK(hipMemcpy(dframe, frame, bytes, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
-    HIP_OK(hipMemcpy(dids, ids, bytes, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
-    HIP_OK(hipDeviceSynchronize(), "The device kernel failed");
-    launch_overlay(I, dframe, dids, dout, width, rows, *style, sel, count, false);
-    finish(I);
-    HIP_OK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
-    (void)hipFree(dframe); (void)hipFree(dids); (void)hipFree(dout);
-    return (uint32_t)n;
-}
-
-int clw_ext_object_stats(cl_wrap* wrap, const clw_rect* rect, clw_object_stat* out, uint32_t capacity, clw_object_summary* summary) {
-    Impl* I = impl_of(wrap);
-    use_device(I);
-    if (!summary || I->band_stride > 1u) return 0;
-    whitted_params P{};
-    int flags = 0;
-    size_t dyn_lds = 0;
-    wt_projection T;
-    if (!gbuffer_params(wrap, I, P, flags, dyn_lds, T)) return 0;
-    /* whole rows of one contiguous range: work-item i is pixel (i % width, row_offset + i / width) of the frame */
-    if (P.band_stride > 1u || !P.tiled || P.rows == 0u) return 0;
-    const uint32_t counts[3] = {P.ns, P.np, P.nl};
-    Impl::Objects& O = I->obj;
-    if (!wt_objects_check(&O, P.width, P.rows, P.row_offset, rect, counts, summary)) return 0;      /* (the ids are the pass's own: any non-NULL pointer) */
-    O.size_range(P.n_items);
-    void* chan[5] = {O.depth, O.ids, nullptr, nullptr, nullptr};
-    launch_gbuffer(I, P, flags, dyn_lds, chan, T, true);
-    run_objects(I, O.ids, O.depth, P.width, P.rows, P.row_offset, rect, counts, out, capacity, summary, true);
-    return 1;
-}
-
-int clw_ext_unit_object_stats(cl_wrap* wrap, const uint32_t* ids, const float* depth, uint32_t width, uint32_t rows, uint32_t first_row,
-                              const clw_rect* rect, const uint32_t counts[3], clw_object_stat* out, uint32_t capacity, clw_object_summary* summary) {
-    Impl* I = impl_of(wrap);
-    use_device(I);
-    if (!wt_objects_check(ids, width, rows, first_row, rect, counts, summary)) return 0;
-    const size_t bytes = (size_t)width * rows * 4;      /* (width * rows fits 30 bits) */
-    uint32_t* dids = nullptr;
-    float* ddepth = nullptr;
-    HIP_OK(hipMalloc((void**)&dids, bytes), "Couldn't allocate device memory");
-    HIP_OK(hipMemcpy(dids, ids, bytes, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
-    if (depth) {
-        HIP_OK(hipMalloc((void**)&ddepth, bytes), "Couldn't allocate device memory");
-        HIP_OK(hipMemcpy(ddepth, depth, bytes, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
-    }
-    HIP_OK(hipDeviceSynchronize(), "The device kernel failed");
-    run_objects(I, dids, ddepth, width, rows, first_row, rect, counts, out, capacity, summary, false);
-    (void)hipFree(dids);
-    if (ddepth) (void)hipFree(ddepth);
-    return 1;
-}
-
-uint32_t clw_ext_render_ao(cl_wrap* wrap, const clw_ao* ao) {
-    Impl* I = impl_of(wrap);
-    use_device(I);
-    static_assert(sizeof(clw_ao) == 16, "the pass's ABI");
-    if (!wt_ao_check(ao)) return 0;
-    if (I->band_stride > 1u) return 0;
-    cl_uint kid = 0;
-    while (kid < I->kernels.size() && I->kernels[kid].kind != K_RAYTRACER) kid++;
-    if (kid >= I->kernels.size()) return 0;
-    const bool compose = (ao->flags & CLW_AO_COMPOSE) != 0u;
-    if (compose && !is_registered(wrap, kid, 10)) return 0;
-    whitted_params P{};
-    int flags = 0;
-    size_t dyn_lds = 0;
-    wt_projection T;
-    if (!gbuffer_params(wrap, I, P, flags, dyn_lds, T)) return 0;
-    /* whole rows of one contiguous range: work-item i is pixel (i % width, row_offset + i / width) of the frame */
-    if (P.band_stride > 1u || !P.tiled || P.rows == 0u || !wt_ao_range_ok(P.width, P.rows)) return 0;
-    Buffer* fb = nullptr;
-    if (compose) {
-        fb = (Buffer*)wrap->buffers[kid][10];
-        if (fb->size < (size_t)P.n_items * 4) return 0;
-        ensure_allocated(I, fb);
-    }
-    Impl::AO& O = I->ao;
-    if (O.n != P.n_items) {      /* another range: a pass under way may still use the old buffers */
-        if (O.n) { finish(I); if (O.done) (void)hipEventSynchronize(O.done); }
-        O.free_buffers();
-        HIP_OK(hipMalloc((void**)&O.point, (size_t)P.n_items * 12), "Couldn't allocate device memory");
-        HIP_OK(hipMalloc((void**)&O.normal, (size_t)P.n_items * 12), "Couldn't allocate device memory");
-        HIP_OK(hipMalloc((void**)&O.ids, (size_t)P.n_items * 4), "Couldn't allocate device memory");
-        HIP_OK(hipMalloc((void**)&O.open, (size_t)P.n_items), "Couldn't allocate device memory");
-        HIP_OK(hipMalloc((void**)&O.frame, (size_t)P.n_items * 4), "Couldn't allocate device memory");
-        O.n = P.n_items;
-    }
-    void* chan[5] = {nullptr, O.ids, O.normal, O.point, nullptr};
-    launch_gbuffer(I, P, flags, dyn_lds, chan, T, true);
-    launch_ao_trace(I, P, flags, O.point, O.normal, O.ids, P.width, P.rows, P.row_offset, *ao, O.open, true);
-    launch_ao_resolve(I, O.open, O.ids, compose ? (const uint32_t*)fb->dptr : nullptr, O.frame, P.width, P.rows, *ao, true);
-    if (!O.done) HIP_OK(hipEventCreateWithFlags(&O.done, hipEventDisableTiming), "Couldn't create a timing event");
-    HIP_OK(hipEventRecord(O.done, I->stream), "Couldn't run the kernel");
-    O.written = true;
-    return O.n;
-}
-
-uint32_t clw_ext_read_ao(cl_wrap* wrap, uint32_t what, void* out, uint32_t capacity_bytes) {
-    Impl* I = impl_of(wrap);
-    use_device(I);
-    const Impl::AO& O = I->ao;
-    if (!O.written || what > 1u) return 0;
-    const uint64_t bytes = (uint64_t)O.n * (what == 0u ? 4u : 1u);      /* (n < 2^30) */
-    if (out && capacity_bytes >= bytes) {
-        hipError_t e = hipEventSynchronize(O.done);
-        if (e != hipSuccess) { printf("%d\n", (int)e); die("The device kernel failed"); }
-        HIP_OK(hipMemcpy(out, what == 0u ? (const void*)O.frame : (const void*)O.open, (size_t)bytes, hipMemcpyDeviceToHost),
-               "Failed to transfer device memory to host");
-    }
-    return (uint32_t)bytes;
-}
-
-void* clw_ext_ao_device_ptr(cl_wrap* wrap, uint32_t what) {
-    const Impl::AO& O = impl_of(wrap)->ao;
-    if (!O.written || what > 1u) return nullptr;
-    return what == 0u ? (void*)O.frame : (void*)O.open;
-}
-
-uint32_t clw_ext_unit_ao_open(cl_wrap* wrap, const float* point, const float* normal, const uint32_t* ids, uint32_t width, uint32_t rows,
-                              uint32_t first_row, const clw_ao* ao, uint8_t* open_u8) {
-    Impl* I = impl_of(wrap);
-    use_device(I);
-    if (!wt_ao_check(ao) || !wt_ao_range_ok(width, rows) || !point || !normal || !ids || !open_u8) return 0;
-    /* the wrapper's bound scene, as gbuffer_params asks for it */
-    cl_uint kid = 0;
-    while (kid < I->kernels.size() && I->kernels[kid].kind != K_RAYTRACER) kid++;
-    if (kid >= I->kernels.size()) return 0;
-    for (cl_uint a : {1u, 2u, 3u, 8u, 9u}) if (!is_registered(wrap, kid, a)) return 0;
-    for (cl_uint a : {4u, 5u, 6u}) if (!I->kernels[kid].values[a].set) return 0;
-    whitted_params P{};
-    int flags = 0;
-    size_t dyn_lds = 0;
-    bind_scene(wrap, I, kid, P, flags, dyn_lds);
-    const size_t n = (size_t)width * rows;
-    float *dpoint = nullptr, *dnormal = nullptr;
-    uint32_t* dids = nullptr;
-    uint8_t* dopen = nullptr;
-    HIP_OK(hipMalloc((void**)&dpoint, n * 12), "Couldn't allocate device memory");
-    HIP_OK(hipMalloc((void**)&dnormal, n * 12), "Couldn't allocate device memory");
-    HIP_OK(hipMalloc((void**)&dids, n * 4), "Couldn't allocate device memory");
-    HIP_OK(hipMalloc((void**)&dopen, n), "Couldn't allocate device memory");
-    HIP_OK(hipMemcpy(dpoint, point, n * 12, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
-    HIP_OK(hipMemcpy(dnormal, normal, n * 12, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
-    HIP_OK(hipMemcpy(dids, ids, n * 4, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
-    HIP_OK(hipDeviceSynchronize(), "The device kernel failed");
-    launch_ao_trace(I, P, flags, dpoint, dnormal, dids, width, rows, first_row, *ao, dopen, false);
-    finish(I);
-    HIP_OK(hipMemcpy(open_u8, dopen, n, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
-    (void)hipFree(dpoint); (void)hipFree(dnormal); (void)hipFree(dids); (void)hipFree(dopen);
-    return (uint32_t)n;
-}
-
-uint32_t clw_ext_unit_ao_resolve(cl_wrap* wrap, const uint8_t* open_u8, const uint32_t* ids, const uint32_t* frame, uint32_t width, uint32_t rows,
-                                 const clw_ao* ao, uint32_t* out) {
-    Impl* I = impl_of(wrap);
-    use_device(I);
-    if (!wt_ao_check(ao) || !wt_ao_range_ok(width, rows) || !open_u8 || !ids || !out || ((ao->flags & CLW_AO_COMPOSE) && !frame)) return 0;
-    const size_t n = (size_t)width * rows;
-    uint8_t* dopen = nullptr;
-    uint32_t *dids = nullptr, *dframe = nullptr, *dout = nullptr;
-    HIP_OK(hipMalloc((void**)&dopen, n), "Couldn't allocate device memory");
-    HIP_OK(hipMalloc((void**)&dids, n * 4), "Couldn't allocate device memory");
-    HIP_OK(hipMalloc((void**)&dout, n * 4), "Couldn't allocate device memory");
-    HIP_OK(hipMemcpy(dopen, open_u8, n, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
-    HIP_OK(hipMemcpy(dids, ids, n * 4, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
-    if (ao->flags & CLW_AO_COMPOSE) {
-        HIP_OK(hipMalloc((void**)&dframe, n * 4), "Couldn't allocate device memory");
-        HIP_OK(hipMemcpy(dframe, frame, n * 4, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
-    }
-    HIP_OK(hipDeviceSynchronize(), "The device kernel failed");
-    launch_ao_resolve(I, dopen, dids, dframe, dout, width, rows, *ao, false);
-    finish(I);
-    HIP_OK(hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
-    (void)hipFree(dopen); (void)hipFree(dids); (void)hipFree(dout);
-    if (dframe) (void)hipFree(dframe);
-    return (uint32_t)n;
-}
-
-uint32_t clw_ext_cast_rays(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uint32_t flags, clw_hit* hits) {
-    if (!hits) return 0;
-    return cast_host_arrays(wrap, rays, n, flags, hits, nullptr);
-}
-
-uint32_t clw_ext_occluded_rays(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uint32_t flags, uint8_t* blocked) {
-    if (!blocked) return 0;
-    return cast_host_arrays(wrap, rays, n, flags, nullptr, blocked);
-}
-
-uint32_t clw_ext_cast_rays_device(cl_wrap* wrap, const void* d_rays, uint32_t n, uint32_t flags, void* d_hits, void* d_blocked) {
-    Impl* I = impl_of(wrap);
-    use_device(I);
-    if (!wt_cast_check(n, flags) || !d_rays || (d_hits != nullptr) == (d_blocked != nullptr)) return 0;
-    whitted_params P{};
-    wt_cast_class cc;
-    if (!cast_params(wrap, I, n, P, cc)) return 0;
-    launch_cast(I, P, cc, d_rays, n, flags, d_hits, (uint8_t*)d_blocked);
-    return n;
 }
 
 void clw_ext_set_pipeline(cl_wrap* wrap, int on) { impl_of(wrap)->pipeline = on ? 1 : 0; }

@@ -11,11 +11,5 @@
 #include "projection_host.h"
 #define WT_STRICT 0
 #define WT_NS wt_fast
-#define WT_LAUNCH_TRACE wt_fast_launch_trace
-#define WT_LAUNCH_RAYGEN wt_fast_launch_raygen
-#define WT_LAUNCH_SCHED wt_fast_launch_sched
-#define WT_LAUNCH_CAMS wt_fast_launch_cams
-#define WT_LAUNCH_CLASSIFY wt_fast_launch_classify
-#define WT_LAUNCH_UNIT wt_fast_launch_unit
-#define WT_LAUNCH_UNIT_SCENE wt_fast_launch_unit_scene
+#include "whitted_launch.h"
 #include "whitted_launch.inc"

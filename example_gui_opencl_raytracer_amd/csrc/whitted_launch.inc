@@ -69,27 +69,22 @@ static wt_trace_launcher wt_find_trace(int flags) {
     return nullptr;
 }
 
-extern "C" hipError_t WT_LAUNCH_TRACE(const whitted_params* P, int flags, unsigned grid, size_t dyn_lds,
+WT_LAUNCHER(trace)(const whitted_params* P, int flags, unsigned grid, size_t dyn_lds,
                                       hipStream_t s) {
     const wt_trace_launcher run = wt_find_trace(flags);
     return run ? run(P, grid, dyn_lds, s) : hipErrorInvalidValue;
 }
 
 /* whether this build compiled a trace kernel for the flag word (csrc/launch_plan.h: the planner's tests hold every word it returns to it) */
-#if WT_STRICT
-#define WT_HAS_TRACE wt_strict_has_trace
-#else
-#define WT_HAS_TRACE wt_fast_has_trace
-#endif
-extern "C" int WT_HAS_TRACE(int flags) { return wt_find_trace(flags) != nullptr; }
+extern "C" int WT_NAME(has_trace)(int flags) { return wt_find_trace(flags) != nullptr; }
 
-extern "C" hipError_t WT_LAUNCH_RAYGEN(const raygen_params* P, hipStream_t s) {
+WT_LAUNCHER(raygen)(const raygen_params* P, hipStream_t s) {
     unsigned grid = (P->n_items + WT_RG_BLOCK - 1) / WT_RG_BLOCK;
     hipLaunchKernelGGL(WT_NS::wt_raygen, dim3(grid), dim3(WT_RG_BLOCK), 0, s, *P);
     return hipGetLastError();
 }
 
-extern "C" hipError_t WT_LAUNCH_SCHED(const unsigned* cost, unsigned* order, unsigned tpr, unsigned trows,
+WT_LAUNCHER(sched)(const unsigned* cost, unsigned* order, unsigned tpr, unsigned trows,
                                       unsigned per_share, unsigned clamp_outliers, unsigned per_share_cap, unsigned split_slots,
                                       unsigned min_quota, unsigned max_lg, hipStream_t s) {
     hipLaunchKernelGGL(WT_NS::wt_sched_build, dim3(8), dim3(256), 0, s, cost, order, tpr, trows, per_share, clamp_outliers, per_share_cap,
@@ -98,7 +93,7 @@ extern "C" hipError_t WT_LAUNCH_SCHED(const unsigned* cost, unsigned* order, uns
 }
 
 #if !WT_STRICT   /* integer work: one copy, in the fast unit, serves both builds */
-extern "C" hipError_t WT_LAUNCH_CLASSIFY(const unsigned* frame, unsigned width, unsigned rows, unsigned lgb, unsigned threshold,
+WT_LAUNCHER(classify)(const unsigned* frame, unsigned width, unsigned rows, unsigned lgb, unsigned threshold,
                                          unsigned char* mask, unsigned* order, unsigned* count, unsigned cap, hipStream_t s) {
     const unsigned b = 1u << lgb, nbc = (width + b - 1u) / b, nbr = (rows + b - 1u) / b;
     const unsigned per_wave = 64u >> (2u * lgb), wpr = (nbc + per_wave - 1u) / per_wave;      /* blocks a wave owns; waves per block row */
@@ -110,18 +105,18 @@ extern "C" hipError_t WT_LAUNCH_CLASSIFY(const unsigned* frame, unsigned width, 
 }
 #endif
 
-extern "C" hipError_t WT_LAUNCH_CAMS(const wt_cam_table* T, float* dst, hipStream_t s) {
+WT_LAUNCHER(cams)(const wt_cam_table* T, float* dst, hipStream_t s) {
     hipLaunchKernelGGL(WT_NS::wt_cams_store, dim3(1), dim3(64), 0, s, *T, (float4*)dst);
     return hipGetLastError();
 }
 
-extern "C" hipError_t WT_LAUNCH_UNIT(int op, const float* in, float* out, unsigned n, unsigned stride_in,
+WT_LAUNCHER(unit)(int op, const float* in, float* out, unsigned n, unsigned stride_in,
                                      unsigned stride_out, unsigned aux, hipStream_t s) {
     hipLaunchKernelGGL(WT_NS::wt_unit, dim3((n + 63) / 64), dim3(64), 0, s, op, in, out, n, stride_in, stride_out, aux);
     return hipGetLastError();
 }
 
-extern "C" hipError_t WT_LAUNCH_UNIT_SCENE(const whitted_params* P, int flags, int op, const float* in, float* out, unsigned n,
+WT_LAUNCHER(unit_scene)(const whitted_params* P, int flags, int op, const float* in, float* out, unsigned n,
                                            unsigned stride_in, unsigned stride_out, size_t dyn_lds, hipStream_t s) {
     const dim3 grid((n + 63) / 64), block(64);
     if (flags & WT_F_GRID) hipLaunchKernelGGL((WT_NS::wt_unit_scene<false, true>), grid, block, 0, s, *P, op, in, out, n, stride_in, stride_out);
@@ -132,12 +127,7 @@ extern "C" hipError_t WT_LAUNCH_UNIT_SCENE(const whitted_params* P, int flags, i
 
 /* the primary-hit pass (whitted_gbuffer.inc): geometry as bind_scene chose it -- WT_F_GRID the uniform grid, WT_F_GEOM_LDS the scene staged in LDS, else
  * read from global memory; the five channel pointers in CLW_GB_* bit order, NULL = not written; `T` = the camera model (model 0: the pinhole) */
-#if WT_STRICT
-#define WT_LAUNCH_GBUFFER wt_strict_launch_gbuffer
-#else
-#define WT_LAUNCH_GBUFFER wt_fast_launch_gbuffer
-#endif
-extern "C" hipError_t WT_LAUNCH_GBUFFER(const whitted_params* P, int flags, unsigned grid, size_t dyn_lds, float* depth, unsigned* id,
+WT_LAUNCHER(gbuffer)(const whitted_params* P, int flags, unsigned grid, size_t dyn_lds, float* depth, unsigned* id,
                                         float* normal, float* point, float* albedo, const wt_projection* T, hipStream_t s) {
     const WT_NS::wt_gbuffer_out G = {depth, id, normal, point, albedo};
     const dim3 g(grid), block(WT_BLOCK);
@@ -153,12 +143,7 @@ extern "C" hipError_t WT_LAUNCH_GBUFFER(const whitted_params* P, int flags, unsi
 
 /* the raygen of the camera models beside the pinhole (whitted_projection.inc): wt_raygen's launch shape; `T` carries the model's terms and, for
  * the panorama, the device addresses of its two tables (width and height float4) */
-#if WT_STRICT
-#define WT_LAUNCH_RAYGEN_PROJ wt_strict_launch_raygen_proj
-#else
-#define WT_LAUNCH_RAYGEN_PROJ wt_fast_launch_raygen_proj
-#endif
-extern "C" hipError_t WT_LAUNCH_RAYGEN_PROJ(const raygen_params* P, const wt_projection* T, hipStream_t s) {
+WT_LAUNCHER(raygen_proj)(const raygen_params* P, const wt_projection* T, hipStream_t s) {
     if (P->n_items == 0u || P->width == 0u || (T->model != CLW_PROJ_ORTHO && T->model != CLW_PROJ_EQUIRECT) ||
         (T->model == CLW_PROJ_EQUIRECT && (!T->col || !T->row || T->width != P->width || T->height != P->height)))
         return hipErrorInvalidValue;
@@ -170,12 +155,7 @@ extern "C" hipError_t WT_LAUNCH_RAYGEN_PROJ(const raygen_params* P, const wt_pro
 /* the selection overlay (whitted_overlay.inc) over a width x rows range: one workgroup per tile of 32 x 8 pixels, the kernel compiled for the
  * flag word (CLW_OV_* bits, 1..7); `style` = radius, outline_rgb, fill_rgb, fill_alpha, edge_rgb; the caller has checked style and selection
  * (csrc/overlay_host.h: wt_overlay_check) */
-#if WT_STRICT
-#define WT_LAUNCH_OVERLAY wt_strict_launch_overlay
-#else
-#define WT_LAUNCH_OVERLAY wt_fast_launch_overlay
-#endif
-extern "C" hipError_t WT_LAUNCH_OVERLAY(const unsigned* frame, const unsigned* ids, unsigned* out, unsigned width, unsigned rows, unsigned flags,
+WT_LAUNCHER(overlay)(const unsigned* frame, const unsigned* ids, unsigned* out, unsigned width, unsigned rows, unsigned flags,
                                         const unsigned style[5], const unsigned* sel, unsigned count, hipStream_t s) {
     const unsigned long long tpr = (width + (WT_OV_TILE_W - 1ull)) / WT_OV_TILE_W, trows = (rows + (WT_OV_TILE_H - 1ull)) / WT_OV_TILE_H;
     if (width == 0u || rows == 0u || width > 0x7FFFFFFFu || tpr * trows > 0x7FFFFFFFull || count > 64u || flags < 1u || flags > 7u ||
@@ -201,12 +181,7 @@ extern "C" hipError_t WT_LAUNCH_OVERLAY(const unsigned* frame, const unsigned* i
  * tiles of 32 x 8 pixels dealt to at most WT_OBJ_MAX_GROUPS workgroups, and compacts the occupied slots into `result` (the 16-byte summary, then the records, room for one
  * per slot).  `depth` = the depth channel's bit patterns, or null.  The caller has checked the arguments (csrc/objects_host.h:
  * wt_objects_check, wt_objects_clip) */
-#if WT_STRICT
-#define WT_LAUNCH_OBJECTS wt_strict_launch_objects
-#else
-#define WT_LAUNCH_OBJECTS wt_fast_launch_objects
-#endif
-extern "C" hipError_t WT_LAUNCH_OBJECTS(const unsigned* ids, const unsigned* depth, unsigned width, unsigned rows, unsigned first_row,
+WT_LAUNCHER(objects)(const unsigned* ids, const unsigned* depth, unsigned width, unsigned rows, unsigned first_row,
                                         const unsigned clip[4], const unsigned counts[3], void* table, void* result, hipStream_t s) {
     const unsigned long long nslots = (unsigned long long)counts[0] + counts[1] + counts[2] + 1ull;
     const unsigned long long tpr = (clip[2] + (WT_OBJ_TILE_W - 1ull)) / WT_OBJ_TILE_W, trows = (clip[3] + (WT_OBJ_TILE_H - 1ull)) / WT_OBJ_TILE_H;
@@ -237,17 +212,10 @@ extern "C" hipError_t WT_LAUNCH_OBJECTS(const unsigned* ids, const unsigned* dep
 }
 
 /* ambient occlusion (whitted_ao.inc).  wt_ao_trace over the planar point / normal / id channels of a width x rows range whose first row is row
- * `first_row` of the frame: one workgroup of one wave per 8 x 8 tile, geometry as bind_scene chose it (flags as WT_LAUNCH_GBUFFER), `dirs` = the
+ * `first_row` of the frame: one workgroup of one wave per 8 x 8 tile, geometry as bind_scene chose it (flags as the gbuffer launcher), `dirs` = the
  * 16 x K float4 of clw_host_ao_dirs on the device, staged in LDS behind the geometry; `open` receives a byte per pixel.  The caller has checked
  * K, radius and the range (csrc/ao_host.h: wt_ao_check, wt_ao_range_ok) */
-#if WT_STRICT
-#define WT_LAUNCH_AO_TRACE wt_strict_launch_ao_trace
-#define WT_LAUNCH_AO_RESOLVE wt_strict_launch_ao_resolve
-#else
-#define WT_LAUNCH_AO_TRACE wt_fast_launch_ao_trace
-#define WT_LAUNCH_AO_RESOLVE wt_fast_launch_ao_resolve
-#endif
-extern "C" hipError_t WT_LAUNCH_AO_TRACE(const whitted_params* P, int flags, const float* point, const float* normal, const unsigned* ids,
+WT_LAUNCHER(ao_trace)(const whitted_params* P, int flags, const float* point, const float* normal, const unsigned* ids,
                                          const float* dirs, unsigned char* open, unsigned width, unsigned rows, unsigned first_row, unsigned K,
                                          float radius, hipStream_t s) {
     const unsigned long long tpr = (width + 7ull) / 8ull, trows = (rows + 7ull) / 8ull;
@@ -268,7 +236,7 @@ extern "C" hipError_t WT_LAUNCH_AO_TRACE(const whitted_params* P, int flags, con
 }
 
 /* wt_ao_resolve over a width x rows range: one workgroup per tile of 32 x 8 pixels; ao_flags = CLW_AO_* bits (`frame` is read with COMPOSE only) */
-extern "C" hipError_t WT_LAUNCH_AO_RESOLVE(const unsigned char* open, const unsigned* ids, const unsigned* frame, unsigned* out, unsigned width,
+WT_LAUNCHER(ao_resolve)(const unsigned char* open, const unsigned* ids, const unsigned* frame, unsigned* out, unsigned width,
                                            unsigned rows, unsigned ao_flags, unsigned K, unsigned strength, hipStream_t s) {
     const unsigned long long tpr = (width + (WT_AO_TILE_W - 1ull)) / WT_AO_TILE_W, trows = (rows + (WT_AO_TILE_H - 1ull)) / WT_AO_TILE_H;
     if (width == 0u || rows == 0u || (unsigned long long)width * rows >= (1ull << 30) || K < 1u || K > 32u || strength > 256u || (ao_flags & ~3u) ||
@@ -284,15 +252,10 @@ extern "C" hipError_t WT_LAUNCH_AO_RESOLVE(const unsigned char* open, const unsi
 }
 
 /* ray queries (whitted_cast.inc): wt_cast over `n` rays (2 float4 each) on the device, geometry as the caller's plan chose it (launch_plan.c:
- * wt_plan_cast -- flags as WT_LAUNCH_GBUFFER, `groups` workgroups of one wave serving `batches` batches of 64 rays each).  Exactly one of
+ * wt_plan_cast -- flags as the gbuffer launcher, `groups` workgroups of one wave serving `batches` batches of 64 rays each).  Exactly one of
  * `hits` (nearest: 2 float4 per ray) and `blocked` (any: a byte per ray) is given.  The caller has checked n and cast_flags (csrc/cast_host.h:
  * wt_cast_check) */
-#if WT_STRICT
-#define WT_LAUNCH_CAST wt_strict_launch_cast
-#else
-#define WT_LAUNCH_CAST wt_fast_launch_cast
-#endif
-extern "C" hipError_t WT_LAUNCH_CAST(const whitted_params* P, int flags, unsigned groups, unsigned batches, size_t dyn_lds, const void* rays,
+WT_LAUNCHER(cast)(const whitted_params* P, int flags, unsigned groups, unsigned batches, size_t dyn_lds, const void* rays,
                                      unsigned n, unsigned cast_flags, void* hits, unsigned char* blocked, hipStream_t s) {
     if (n == 0u || n >= (1u << 30) || !(cast_flags & 7u) || (cast_flags & ~15u) || !rays || (hits != nullptr) == (blocked != nullptr) || batches == 0u ||
         groups == 0u || (unsigned long long)groups * batches * 64ull < n || (unsigned long long)groups * batches * 64ull >= (1ull << 31) ||

@@ -10,10 +10,5 @@
 #include "projection_host.h"
 #define WT_STRICT 1
 #define WT_NS wt_strict
-#define WT_LAUNCH_TRACE wt_strict_launch_trace
-#define WT_LAUNCH_RAYGEN wt_strict_launch_raygen
-#define WT_LAUNCH_SCHED wt_strict_launch_sched
-#define WT_LAUNCH_CAMS wt_strict_launch_cams
-#define WT_LAUNCH_UNIT wt_strict_launch_unit
-#define WT_LAUNCH_UNIT_SCENE wt_strict_launch_unit_scene
+#include "whitted_launch.h"
 #include "whitted_launch.inc"
