@@ -54,6 +54,7 @@ SYMBOLS = [
     "clw_host_ao_dirs", "clw_host_ao_open", "clw_host_ao_resolve", "clw_ext_render_ao", "clw_ext_read_ao", "clw_ext_ao_device_ptr",
     "clw_ext_unit_ao_open", "clw_ext_unit_ao_resolve",
     "clw_host_cast_rays", "clw_host_occluded_rays", "clw_ext_cast_rays", "clw_ext_occluded_rays", "clw_ext_cast_rays_device",
+    "clw_host_primary_cull", "clw_ext_read_primary_cull",
 ]
 
 # the channels of the primary-hit pass (hip_wrap_ext.h: CLW_GB_*), the id of a miss and the pass's id in the timing log
@@ -354,6 +355,11 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         L.clw_ext_occluded_rays.restype = u32
         L.clw_ext_cast_rays_device.argtypes = [W, vp, u32, u32, vp, vp]
         L.clw_ext_cast_rays_device.restype = u32
+    if hasattr(L, "clw_ext_read_primary_cull") or not os.environ.get("CLWRAP_LIB"):       # (an older A/B build may lack them)
+        L.clw_host_primary_cull.argtypes = [C.POINTER(clw_camera), u32, u32, u32, u32, vp, u32, vp, u32, vp]
+        L.clw_host_primary_cull.restype = u32
+        L.clw_ext_read_primary_cull.argtypes = [W, vp, u32, C.POINTER(C.c_uint64)]
+        L.clw_ext_read_primary_cull.restype = u32
     L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
     L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
     L.clw_ext_read_tile_costs.restype = u32
@@ -572,6 +578,25 @@ def occluded_rays_host(rays, flags: int, spheres, planes, lights=None) -> np.nda
     if not 0 <= int(flags) < 2 ** 32 or not load_library().clw_host_occluded_rays(_ptr(rays), rays.size, int(flags), _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, _ptr(out)):
         raise ValueError("clw_host_occluded_rays rejects these arguments (at least one ray, fewer than 2^30, a kind bit and only CAST_* bits in flags)")
     return out
+
+
+CULL_SPHERES, CULL_LIGHTS = 1, 2      # the bits of a primary-ray cull table's bytes (hip_wrap_ext.h: clw_host_primary_cull)
+VARIANT_NO_CULL = 32768               # clw_ext_set_variant: no cull table
+
+
+def host_primary_cull(cam: clw_camera, spheres, lights, rows: int | None = None, row_offset: int = 0, band_stride: int = 1, band_phase: int = 0) -> np.ndarray:
+    """clw_host_primary_cull: THE definition of the primary-ray cull table of a launch over `rows` rows (default: the camera's height) of the
+    camera's frame -> uint8 [tile rows, tiles per row], bit 0 = the tile's rays miss the line test of every sphere, bit 1 = of every light."""
+    rows = int(cam.height) if rows is None else int(rows)
+    s = None if spheres is None else np.ascontiguousarray(spheres)
+    l = None if lights is None else np.ascontiguousarray(lights)
+    ns, nl = (0 if a is None else int(a.shape[0]) for a in (s, l))
+    trows, tpr = (rows + 7) // 8, (int(cam.width) + 7) // 8
+    out = np.empty(max(trows * tpr, 1), np.uint8)
+    n = load_library().clw_host_primary_cull(C.byref(cam), int(row_offset), rows, int(band_stride), int(band_phase), _ptr(s), ns, _ptr(l), nl, _ptr(out))
+    if n != trows * tpr or n == 0:
+        raise ValueError("clw_host_primary_cull rejects these arguments (a frame with tiles, band_phase below band_stride)")
+    return out[:n].reshape(trows, tpr)
 
 
 def _rect(rect):
@@ -841,6 +866,17 @@ class ClWrap:
     def set_tile_sched(self, on): self.L.clw_ext_set_tile_sched(C.byref(self.w), int(on))
     def set_variant(self, v): self.L.clw_ext_set_variant(C.byref(self.w), int(v))
     def last_trace_flags(self): return int(self.L.clw_ext_last_trace_flags(C.byref(self.w)))
+
+    def read_primary_cull(self):
+        """clw_ext_read_primary_cull -> (the cull table the last whole-range trace launch was given as uint8 [tiles], or None when it had
+        none; how often the builder has run)."""
+        builds = C.c_uint64()
+        n = self.L.clw_ext_read_primary_cull(C.byref(self.w), None, 0, C.byref(builds))
+        if n == 0:
+            return None, int(builds.value)
+        out = np.empty(n, np.uint8)
+        self.L.clw_ext_read_primary_cull(C.byref(self.w), _ptr(out), n, C.byref(builds))
+        return out, int(builds.value)
     def set_tpt(self, max_lanes=-1, min_paths=-1, pool_mb=-1): self.L.clw_ext_set_tpt(C.byref(self.w), int(max_lanes), int(min_paths), int(pool_mb))
     def timing_reset(self): self.L.clw_ext_timing_reset(C.byref(self.w))
     def set_timing_every(self, n): self.L.clw_ext_set_timing_every(C.byref(self.w), int(n))

@@ -25,6 +25,7 @@
 #include "objects_host.h"
 #include "overlay_host.h"
 #include "png_codec.h"
+#include "primary_cull_host.h"
 #include "projection_host.h"
 #include "scene_prep.h"
 #include "whitted_launch.h"
@@ -290,6 +291,22 @@ struct Impl {
     hipStream_t sched_stream = nullptr;
     static constexpr int MAX_CHUNKS = 4;
     Sched scheds[1 + MAX_CHUNKS];   /* [0]: whole-range launches; [1 + c]: strip c of a pipelined read-back */
+    /* The primary-ray cull table (primary_cull_host.h; launch_plan.h: wt_plan_cull), one per scheduling slot: built on the launch stream ahead of
+     * the trace that reads it, and only when its key -- the camera terms, frame width and row range, and the prepared scene -- changed and has
+     * now come twice in a row, so a still view pays for it once and a camera that moves every frame never.  It is written and read in stream
+     * order (the tables fence covers a change of stream). */
+    struct Cull {
+        unsigned char* table = nullptr; size_t bytes = 0;   /* a byte per tile, rounded up to whole words */
+        bool valid = false;                                  /* `table` holds the table of `view` and `scene` */
+        wt_cull_view view{}; uint64_t scene = 0;
+        uint32_t tiles = 0;
+        bool seen = false;                                   /* the key of the slot's last launch that could read a table: a view is built for when it comes twice in a row */
+        wt_cull_view seen_view{}; uint64_t seen_scene = 0; uint32_t seen_tiles = 0;
+        uint64_t builds = 0;                                 /* builder launches so far (clw_ext_read_primary_cull) */
+        bool last_used = false;                              /* the slot's last trace launch was given the table */
+        void free_all() { if (table) (void)hipFree(table); table = nullptr; bytes = 0; valid = false; last_used = false; tiles = 0; }
+    };
+    Cull culls[1 + MAX_CHUNKS];
     /* pipelined read-back (cl_wrap_output of a large frame): strips rendered back to back, each copied to the host
      * while the next one renders */
     int pipeline = 1;

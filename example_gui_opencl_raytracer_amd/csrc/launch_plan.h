@@ -22,7 +22,7 @@ extern "C" {
 /* the bits of clw_ext_set_variant / CLWRAP_VARIANT (documented in hip_wrap_ext.h) */
 enum { WT_V_GEOM_GLOBAL = 1, WT_V_LINEAR_IDS = 2, WT_V_NO_TILE_ORDER = 4, WT_V_NO_GRID = 8, WT_V_NO_TAIL = 16, WT_V_NO_OCC = 64,
        WT_V_NO_LPT = 128, WT_V_NO_VIS = 256, WT_V_TIMELINE = 512, WT_V_VIS_VERIFY = 1024, WT_V_FULL_STACK = 2048, WT_V_NO_SPLIT = 4096,
-       WT_V_NO_SHAPE = 8192, WT_V_UNTRIMMED = 16384 };
+       WT_V_NO_SHAPE = 8192, WT_V_UNTRIMMED = 16384, WT_V_NO_CULL = 32768 };
 
 /* limits and thresholds of the plan (the defaults of the knobs below are the measured optima) */
 enum {
@@ -182,6 +182,12 @@ wt_order_choice wt_order_choose(wt_order_state* s);
 int wt_order_rebuild(wt_order_state* s, int sig_changed, int grid_build);
 /* the launch is enqueued: note the build behind it (if any) and swap the buffers */
 void wt_order_launched(wt_order_state* s, int rebuilt);
+
+/* Whether a planned launch reads a primary-ray cull table (whitted_params.h: whitted_kargs; primary_cull_host.h): a shallow, tiled, fused
+ * 1-sample launch of the pinhole camera over a linearly scanned scene, unless variant 32768.  Everything else -- a grid scene, a launch from a
+ * ray buffer (a projection's included), sample cameras, moving spheres, any supersampled or deep launch -- gets a null table.  The table is
+ * indexed like the tile costs and keyed by the launch's camera, range and scene (hip_wrap.cpp: bind_primary_cull). */
+int wt_plan_cull(const wt_plan_in* in, const wt_plan_out* out);
 
 /* whether the fast / strict build compiled a trace kernel for a flag word (whitted_launch.inc) */
 int wt_fast_has_trace(int flags);

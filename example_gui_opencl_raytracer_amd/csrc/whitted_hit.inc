@@ -57,6 +57,8 @@
                     }
                 }
             };
+            /* (a tile whose primary rays all miss the line test of every light skips the chunks in its first iteration: the cull table, wave-uniform) */
+            if (!(CULL && (cullb & WT_CULL_LIGHTS)))
             for (unsigned base = 0; base < SH::nl(P); base += 4u) {
                 const unsigned left = SH::nl(P) - base;
                 if (left >= 4u) probe_chunk(wt_int<4>{}, base);
@@ -96,7 +98,7 @@
                 int best = -1;
                 if (GRID) {
                     best = wt_grid_nearest(P, r, tbest);
-                } else {
+                } else if (!(CULL && (cullb & WT_CULL_SPHERES))) {               /* (the cull table again: no lane's line meets any sphere) */
                     for (unsigned base = 0; base < SH::ns(P); base += 4u) {      /* four spheres at a time, see the light probe */
                         float4 s4[4]; float bq[4], Dq[4]; bool ok[4]; bool any = false;
 #pragma unroll

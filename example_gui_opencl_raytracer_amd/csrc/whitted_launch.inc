@@ -1,7 +1,8 @@
 /* whitted_launch.inc -- instantiates the kernels of whitted_trace.inc (and the primary-hit pass of whitted_gbuffer.inc, built from its
  * pieces, the camera models of whitted_projection.inc, the ambient occlusion pass of whitted_ao.inc, the ray queries of whitted_cast.inc, the selection overlay of
- * whitted_overlay.inc and the visible-object table of whitted_objects.inc) in namespace WT_NS and exports
- * the C launchers the shim calls. */
+ * whitted_overlay.inc, the visible-object table of whitted_objects.inc and the builder of the primary-ray cull table of whitted_cull.inc) in
+ * namespace WT_NS and exports the C launchers the shim calls. */
+#include "primary_cull_host.h"
 namespace WT_NS {
 #include "whitted_trace.inc"
 #include "whitted_gbuffer.inc"
@@ -10,16 +11,25 @@ namespace WT_NS {
 #include "whitted_cast.inc"
 #include "whitted_overlay.inc"
 #include "whitted_objects.inc"
+#include "whitted_cull.inc"
 }
 
 template <int FLAGS>
-static hipError_t wt_launch_one(const whitted_params* P, unsigned grid, size_t dyn_lds, hipStream_t s) {
+static hipError_t wt_launch_one(const whitted_params* P, const unsigned char* tile_cull, unsigned grid, size_t dyn_lds, hipStream_t s) {
+    /* a launch with a cull table runs the twin that reads it; every other launch runs wt_trace, which knows nothing of tables */
+    if constexpr (WT_NS::wt_cull_flavour(FLAGS)) {
+        if (tile_cull) {
+            const whitted_kargs K = {*P, tile_cull};
+            hipLaunchKernelGGL(WT_NS::wt_trace_cull<FLAGS>, dim3(grid), dim3(WT_BLOCK), dyn_lds, s, K);
+            return hipGetLastError();
+        }
+    } else if (tile_cull) return hipErrorInvalidValue;      /* (launch_plan.c: wt_plan_cull gives such a flavour no table) */
     hipLaunchKernelGGL(WT_NS::wt_trace<FLAGS>, dim3(grid), dim3(WT_BLOCK), dyn_lds, s, *P);
     return hipGetLastError();
 }
 
 /* the compiled trace kernel of a flag word, or null: the shaped flavours by their exact word, the others by the bits that select a kernel */
-typedef hipError_t (*wt_trace_launcher)(const whitted_params*, unsigned, size_t, hipStream_t);
+typedef hipError_t (*wt_trace_launcher)(const whitted_params*, const unsigned char*, unsigned, size_t, hipStream_t);
 static wt_trace_launcher wt_find_trace(int flags) {
 #if !WT_STRICT
     if (flags & WT_F_SHAPE) {
@@ -69,11 +79,28 @@ static wt_trace_launcher wt_find_trace(int flags) {
     return nullptr;
 }
 
-WT_LAUNCHER(trace)(const whitted_params* P, int flags, unsigned grid, size_t dyn_lds,
+/* `tile_cull`: the primary-ray cull table of the launch (whitted_params.h: whitted_kargs), or null = every test runs */
+WT_LAUNCHER(trace)(const whitted_params* P, const unsigned char* tile_cull, int flags, unsigned grid, size_t dyn_lds,
                                       hipStream_t s) {
     const wt_trace_launcher run = wt_find_trace(flags);
-    return run ? run(P, grid, dyn_lds, s) : hipErrorInvalidValue;
+    return run ? run(P, tile_cull, grid, dyn_lds, s) : hipErrorInvalidValue;
 }
+
+#if !WT_STRICT   /* double-precision work that is the same in both builds: one copy, in the fast unit */
+/* the primary-ray cull table (whitted_cull.inc) of the tiled launch `P` describes, into `table`: a byte per tile, trows x tpr of them */
+WT_LAUNCHER(cull)(const whitted_params* P, unsigned char* table, hipStream_t s) {
+    const unsigned long long tpr = (P->width + 7ull) / 8ull, trows = (P->rows + 7ull) / 8ull;
+    if (!P->tiled || P->width == 0u || P->rows == 0u || tpr * trows >= (1ull << 31) || !table || !P->geom) return hipErrorInvalidValue;
+    WT_NS::wt_cull_args A = {};
+    for (int a = 0; a < 3; a++) { A.V.corner[a] = P->corner[a]; A.V.origin[a] = P->origin[a]; A.V.up[a] = P->up[a]; A.V.right[a] = P->right[a]; }
+    A.V.w_factor = P->w_factor; A.V.h_factor = P->h_factor;
+    A.V.width = P->width; A.V.rows = P->rows; A.V.row_offset = P->row_offset; A.V.band_stride = P->band_stride; A.V.band_phase = P->band_phase;
+    A.spheres = P->geom; A.lights = P->geom + 4 * ((size_t)P->ns + 2 * (size_t)P->np);
+    A.ns = P->ns; A.nl = P->nl; A.tiles = (unsigned)(tpr * trows); A.tpr = (unsigned)tpr; A.table = table;
+    hipLaunchKernelGGL(WT_NS::wt_primary_cull_build, dim3((A.tiles + 255u) / 256u), dim3(256), 0, s, A);
+    return hipGetLastError();
+}
+#endif
 
 /* whether this build compiled a trace kernel for the flag word (csrc/launch_plan.h: the planner's tests hold every word it returns to it) */
 extern "C" int WT_NAME(has_trace)(int flags) { return wt_find_trace(flags) != nullptr; }

@@ -1373,7 +1373,11 @@ __device__ __forceinline__ void wt_acc_fold(float* __restrict__ s, const float s
 /* One tile (tiled launches) or one block of work-items: the whole trace of its pixels.  `wg` is the workgroup's number in
  * the launch's dispatch order (blockIdx.x). */
 typedef const __attribute__((address_space(4))) whitted_params* wt_kparams_t;
-template <int FLAGS>
+/* the flavours that have a twin reading the primary-ray cull table (wt_trace_cull): shallow, 1 sample, rays generated in the kernel, linear scan */
+constexpr bool wt_cull_flavour(int flags) { return (flags & (WT_F_DEEP | WT_F_GRID | WT_F_RAYS | WT_F_SS)) == 0; }
+/* TABLE: the body of wt_trace_cull -- `Pk` then points at a whitted_kargs (the parameters first, the table's pointer behind them); false: the
+ * body of wt_trace, `Pk` points at the whitted_params alone and nothing of the table is compiled */
+template <int FLAGS, bool TABLE>
 __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsigned wg) {
     constexpr bool COUNT = (FLAGS & WT_F_COUNT) != 0;
     constexpr bool DEEP = (FLAGS & WT_F_DEEP) != 0;
@@ -1391,6 +1395,11 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
      * instructions: +4 % inside this batch loop, +19 % as a loop of its own with the remaining rays compacted over the wave -- the
      * six-ray batch traces a ray 3.6 times cheaper than any one-ray-per-lane scheme (profiles/r03_ab_experiments.txt). */
     constexpr bool CLASSES = WT_STRICT != 0 && GEOM_LDS && !GRID;
+    /* The primary-ray cull table (whitted_params.h: whitted_kargs) is compiled into a TWIN of the shallow 1-sample kernels that generate their
+     * rays and scan the spheres linearly (wt_trace_cull), which only launches with a table run; wt_trace itself, every flavour of it, is the
+     * code it was (the deep kernels' split tiles start in the tail, not in this loop). */
+    constexpr bool CULL = TABLE && wt_cull_flavour(FLAGS);
+    static_assert(!TABLE || wt_cull_flavour(FLAGS), "no table twin of this flavour");
 
     constexpr int LDSL = wt_cfg<FLAGS>::lds_levels;
     __shared__ float s_stk[LDSL * WT_REC * WT_BLOCK];
@@ -1431,6 +1440,7 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
     unsigned x = 0, y = 0;  /* position inside this launch's row range (fused mode) */
     unsigned tile = 0xFFFFFFFFu;   /* row-major tile index (tiled mode) */
     unsigned part_lg = 0u, part = 0u; /* this wave serves part `part` of 2^part_lg of the tile */
+    unsigned cullb = 0u;    /* wave-uniform: the groups of tests the FIRST loop iteration skips (WT_CULL_*), cleared after it */
     if (P.tiled) {
         /* workgroups are dealt to XCDs round-robin (b % 8): XCD k owns the tile rows r = 8m + k, so a
          * framebuffer line is written by one L2 and per-XCD work stays balanced.  Within an XCD's share
@@ -1456,6 +1466,13 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
          * 2^lg owns 64 >> lg of its pixels, the other lanes only help in the tree-parallel tail, which such a wave enters at once */
         valid = (tile != 0xFFFFFFFFu) && (x < P.width) && (y < P.rows) && ((lane >> (6u - part_lg)) == part);
         item = y * P.width + x;
+        /* the tile's byte of the cull table: a scalar load of the word that holds it, issued here, first needed at the light probe */
+        if (CULL) {
+            typedef const __attribute__((address_space(1))) unsigned* wt_gwords_t;
+            const uint8_t* tc = ((const __attribute__((address_space(4))) whitted_kargs*)Pk)->tile_cull;
+            if (tc && tile != 0xFFFFFFFFu && trow * 8u < P.rows)      /* (the default order's grid is rounded up to 8 tile rows: those lie beyond the table) */
+                cullb = (unsigned)__builtin_amdgcn_readfirstlane((int)((((wt_gwords_t)tc)[tile >> 2] >> ((tile & 3u) * 8u)) & 3u));
+        }
     } else {
         item = wg * WT_BLOCK + tid;
         valid = item < P.n_items;
@@ -1581,6 +1598,7 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
 #include "whitted_pop.inc"
             WT_STAMP(WT_ST_POP);
         }
+        if (CULL) cullb = 0u;      /* the table speaks of primary rays: every live lane has just traced its own */
     }
     if (!TPT || __builtin_amdgcn_ballot_w64(active) == 0) break;
     {
@@ -1678,7 +1696,16 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
 template <int FLAGS>
 __global__ void __launch_bounds__(WT_BLOCK, wt_cfg<FLAGS>::min_waves) wt_trace(const whitted_params P_arg) {
     const wt_kparams_t Pk = (wt_kparams_t)__builtin_amdgcn_kernarg_segment_ptr();     /* = &P_arg */
-    wt_trace_body<FLAGS>(Pk, blockIdx.x);
+    wt_trace_body<FLAGS, false>(Pk, blockIdx.x);
+}
+/* Its twin for a launch with a primary-ray cull table (the flavours of wt_cull_flavour only): the same body with the table's hooks compiled in.
+ * The body reads the table's pointer THROUGH Pk, behind the parameters: that is whitted_kargs' layout, held here. */
+static_assert(__builtin_offsetof(whitted_kargs, P) == 0 && __builtin_offsetof(whitted_kargs, tile_cull) == sizeof(whitted_params) && sizeof(whitted_params) % 8 == 0,
+              "wt_trace_body<FLAGS, true> reads tile_cull behind the whitted_params its Pk points at");
+template <int FLAGS>
+__global__ void __launch_bounds__(WT_BLOCK, wt_cfg<FLAGS>::min_waves) wt_trace_cull(const whitted_kargs K_arg) {
+    const wt_kparams_t Pk = (wt_kparams_t)__builtin_amdgcn_kernarg_segment_ptr();     /* = &K_arg.P */
+    wt_trace_body<FLAGS, true>(Pk, blockIdx.x);
 }
 
 /* ---- the per-lane table of sample cameras (whitted_params.h: ss_cams) travels as a by-value kernel argument and is written by the launch
@@ -1973,6 +2000,7 @@ __global__ void __launch_bounds__(64) wt_unit_scene(const whitted_params P, int 
     float* res = out + (size_t)i * stride_out;
     WT_STAMP_DECL
     constexpr bool COUNT = false, FROM_RAYS = false;    /* like the fused kernel: the test rows carry unit directions */
+    constexpr bool CULL = false; constexpr unsigned cullb = 0u;      /* any ray, not a tile's primary rays: every test runs */
     unsigned cost = 0, c_iter = 0, c_witer = 0, c_probe = 0, c_seg = 0, c_sky = 0, c_tex = 0;
     const wt_motion mv = {false, 0.0f, 0u};             /* the unit-test kernel sees the scene as it stands */
     (void)lane; (void)c_iter; (void)c_witer; (void)c_probe; (void)c_seg; (void)c_sky; (void)c_tex;

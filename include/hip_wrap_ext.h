@@ -710,6 +710,7 @@ void clw_ext_unit_scene(cl_wrap* wrap, cl_uint kernel_id, int op, const float* i
  * 8192 small scenes of the shallow fast build run the generic trace kernel instead of the one with the scene's counts compiled in,
  * 16384 the trace loop runs the Fresnel / reflection block on a path's last level too, where nothing reads its results, and the tile cost is
  * reduced over the wave by the shuffle butterfly instead of DPP row operations (the kernel as it was before both were trimmed),
+ * 32768 no primary-ray cull table: the first loop iteration of every tile tests every sphere and every light (clw_host_primary_cull below),
  * 2048 deep launches always carry the full-depth (31-parent) scratch stack instead of one sized for their depth,
  * 1024 (with clw_ext_enable_counters) VERIFICATION of the visibility classes: lights are classified AND traced, counter word 9 =
  * lights classified, word 28 = lights whose traced factors differ from their class's (must read 0),
@@ -719,6 +720,37 @@ void clw_ext_set_variant(cl_wrap* wrap, int variant);
 /* The kernel flavour of the latest trace launch: its WT_F_* flags (csrc/whitted_params.h; bit 256 = the scene's counts compiled in,
  * ns | np << 3 | nl << 5 in bits 9..16), -1 before the first launch.  For tests and A/B runs. */
 int clw_ext_last_trace_flags(cl_wrap* wrap);
+
+/* The primary-ray cull table.  The first loop iteration of a tile's wavefront traces 64 rays of the pinhole camera from one origin; where no
+ * ray of the tile can pass the line test of a sphere (the discriminant D >= 0 of intersect_sphere, primitives.cl:170-195), the test is the same
+ * failure in every lane and skipping it changes no bit of the image.  The table holds one byte per 8x8 tile of a launch's rows:
+ *   bit 0  no primary ray of the tile has D >= 0 for ANY scene sphere       bit 1  the same for every light sphere
+ * and the trace kernel skips the nearest-hit sphere loop / the light probe of a tile's first iteration when the bit is set.
+ * clw_host_primary_cull is THE definition (csrc/primary_cull_host.h states the rule and justifies its margin): the tile's directions are bounded
+ * by a cone -- the axis through the tile centre, the half-angle the largest angle to its four corner pixels -- and a sphere is clear of the tile
+ * when the angle between the axis and the LINE through the origin and the sphere's centre (a sphere behind the camera fails the line test too)
+ * exceeds half-angle + asin(r / distance) by 3e-3 rad, both sines first enlarged by 1e-3.  Conservative: a set bit implies D < 0 for every
+ * pixel of the tile as the kernel computes it in float32, never the converse.  No bit of a group is set when the origin lies inside or on one
+ * of its spheres; none at all when a camera term is not finite.  An empty group has its bit set.
+ *   cam: the raygen arguments (its width is the frame's; its height is not read); the launch covers `rows` rows from global row `row_offset`, or
+ *   -- band_stride > 1 -- the interleaved 8-row bands of clw_ext_set_row_bands (local row y = global row ((y / 8) band_stride + band_phase) 8 + y % 8);
+ *   spheres / lights: the 96-byte rsphere and 48-byte rlight arrays of the raytracer's arguments 1 and 3.
+ * Writes ceil(rows / 8) * ceil(width / 8) bytes, row-major tiles, and returns that count; 0 = refused (a NULL pointer, no tiles, band_phase >=
+ * band_stride), nothing written.
+ * On the device the shim builds the same table (wt_primary_cull_build, the same arithmetic compiled for the device: bit for bit this one) on the
+ * launch stream ahead of a trace, only when the camera, the frame width, the row range or the scene changed since it was built, and then for
+ * the SECOND launch in a row of the new view: a still view builds once, behind its first frame (which tests everything), a camera that moves
+ * every frame never builds and never reads a table (the builder's launch costs a frame more than the table saves it).  Only shallow
+ * (depth <= 4), tiled, fused 1-sample launches of the pinhole camera over a scene without a uniform grid read a table; a launch from a ray
+ * buffer (a projection's included), sample cameras (lens, shutter), moving spheres, every supersampled, adaptive-refine or deep launch and
+ * variant 32768 run with none.
+ * clw_ext_read_primary_cull: the table the LAST whole-range trace launch was given -> its tile count, the bytes copied if `capacity` suffices;
+ * 0 = that launch had no table (or there was none).  `builds` (may be NULL) receives how often the builder has run for whole-range launches.
+ * Waits for the launch.  For tests and A/B runs. */
+struct clw_camera;      /* (below) */
+uint32_t clw_host_primary_cull(const struct clw_camera* cam, uint32_t row_offset, uint32_t rows, uint32_t band_stride, uint32_t band_phase, const void* spheres,
+                               uint32_t ns, const void* lights, uint32_t nl, uint8_t* out);
+uint32_t clw_ext_read_primary_cull(cl_wrap* wrap, uint8_t* out, uint32_t capacity, uint64_t* builds);
 
 /* The tree-parallel tail of deep launches (depth > 4; csrc/whitted_tpt.inc): once at most `max_lanes` lanes of a tile's wavefront are
  * alive and they hold at least `min_paths` pending paths (current segments + continuations on their stacks), the rest of the tile is

@@ -17,7 +17,7 @@ info = {}
 for f in sorted(glob.glob(os.path.join(src, "pmc_*", "**", "*counter_collection.csv"), recursive=True)):
     for r in csv.DictReader(open(f)):
         k = r["Kernel_Name"]
-        m = re.search(r"wt_trace<(\d+)>", k)
+        m = re.search(r"wt_trace(?:_cull)?<(\d+)>", k)                 # (wt_trace_cull: the twin a launch with a cull table runs)
         if not m or int(m.group(1)) & 1:                       # skip the one-off counting build (flag bit 0)
             continue
         pm.setdefault(k, collections.OrderedDict()).setdefault(r["Counter_Name"], []).append(float(r["Counter_Value"]))
