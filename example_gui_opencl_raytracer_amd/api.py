@@ -55,6 +55,8 @@ SYMBOLS = [
     "clw_ext_unit_ao_open", "clw_ext_unit_ao_resolve",
     "clw_host_cast_rays", "clw_host_occluded_rays", "clw_ext_cast_rays", "clw_ext_occluded_rays", "clw_ext_cast_rays_device",
     "clw_host_primary_cull", "clw_ext_read_primary_cull",
+    "clw_host_cast_layers", "clw_host_camera_rays", "clw_ext_cast_layers", "clw_ext_cast_layers_device", "clw_ext_camera_rays",
+    "clw_ext_camera_rays_device", "clw_ext_render_layers", "clw_ext_read_layers", "clw_ext_layers_device_ptr", "clw_ext_pick_layers",
 ]
 
 # the channels of the primary-hit pass (hip_wrap_ext.h: CLW_GB_*), the id of a miss and the pass's id in the timing log
@@ -91,6 +93,14 @@ HIT = np.dtype([("t", np.float32), ("id", np.uint32), ("normal", np.float32, 3),
 CAST_SPHERES, CAST_PLANES, CAST_LIGHTS, CAST_KINDS, CAST_OPAQUE = 1, 2, 4, 7, 8
 CAST_KIND_NAMES = {"sphere": CAST_SPHERES, "plane": CAST_PLANES, "light": CAST_LIGHTS}
 TIMING_CAST = 0x43415354
+
+# layered ray queries (hip_wrap_ext.h: clw_layer, clw_host_cast_layers): one entry of a ray's list as a numpy dtype (8 bytes), the largest K,
+# what clw_ext_read_layers reads, and the two kernels' ids in the timing log
+LAYER = np.dtype([("t", np.float32), ("id", np.uint32)])
+LAYERS_MAX = 8
+LAYERS_T, LAYERS_ID = 0, 1
+TIMING_LAYERS = 0x4C415952
+TIMING_CAMRAYS = 0x43524159
 
 
 def id_kind(ids):
@@ -164,6 +174,11 @@ class clw_ray(C.Structure):
 class clw_hit(C.Structure):
     """What a nearest-hit query answers per ray (32 bytes): t (inf = a miss), the id word (ID_NONE = a miss), the normal and the point."""
     _fields_ = [("t", C.c_float), ("id", C.c_uint32), ("normal", C.c_float * 3), ("point", C.c_float * 3)]
+
+
+class clw_layer(C.Structure):
+    """One entry of a ray's layer list (8 bytes): t (inf = empty) and the id word (ID_NONE = empty)."""
+    _fields_ = [("t", C.c_float), ("id", C.c_uint32)]
 
 
 class clw_rect(C.Structure):
@@ -360,6 +375,27 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         L.clw_host_primary_cull.restype = u32
         L.clw_ext_read_primary_cull.argtypes = [W, vp, u32, C.POINTER(C.c_uint64)]
         L.clw_ext_read_primary_cull.restype = u32
+    if hasattr(L, "clw_ext_cast_layers") or not os.environ.get("CLWRAP_LIB"):             # (an older A/B build may lack them)
+        L.clw_host_cast_layers.argtypes = [vp, u32, u32, u32, vp, u32, vp, u32, vp, u32, vp, vp]
+        L.clw_host_cast_layers.restype = C.c_int
+        L.clw_host_camera_rays.argtypes = [C.POINTER(clw_camera), C.POINTER(clw_projection), C.c_uint64, C.c_uint64, vp]
+        L.clw_host_camera_rays.restype = C.c_int
+        L.clw_ext_cast_layers.argtypes = [W, vp, u32, u32, u32, vp, vp]
+        L.clw_ext_cast_layers.restype = u32
+        L.clw_ext_cast_layers_device.argtypes = [W, vp, u32, u32, u32, vp, vp]
+        L.clw_ext_cast_layers_device.restype = u32
+        L.clw_ext_camera_rays.argtypes = [W, vp, u32]
+        L.clw_ext_camera_rays.restype = u32
+        L.clw_ext_camera_rays_device.argtypes = [W, vp, u32]
+        L.clw_ext_camera_rays_device.restype = u32
+        L.clw_ext_render_layers.argtypes = [W, u32, u32]
+        L.clw_ext_render_layers.restype = u32
+        L.clw_ext_read_layers.argtypes = [W, u32, vp, u32]
+        L.clw_ext_read_layers.restype = u32
+        L.clw_ext_layers_device_ptr.argtypes = [W, u32]
+        L.clw_ext_layers_device_ptr.restype = vp
+        L.clw_ext_pick_layers.argtypes = [W, u32, u32, u32, u32, vp]
+        L.clw_ext_pick_layers.restype = C.c_int
     L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
     L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
     L.clw_ext_read_tile_costs.restype = u32
@@ -578,6 +614,29 @@ def occluded_rays_host(rays, flags: int, spheres, planes, lights=None) -> np.nda
     if not 0 <= int(flags) < 2 ** 32 or not load_library().clw_host_occluded_rays(_ptr(rays), rays.size, int(flags), _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, _ptr(out)):
         raise ValueError("clw_host_occluded_rays rejects these arguments (at least one ray, fewer than 2^30, a kind bit and only CAST_* bits in flags)")
     return out
+
+
+def cast_layers_host(rays, flags: int, K: int, spheres, planes, lights=None) -> dict:
+    """clw_host_cast_layers: the K nearest listed candidates of every ray, on the host -- THE definition the device pass is held to ->
+    {"t": float32 [K, n], "id": uint32 [K, n]}, nearest first, empty entries {inf, ID_NONE}."""
+    rays, (s, p, l), (ns, np_, nl) = _cast_args(rays, spheres, planes, lights)
+    K = int(K)
+    t, ids = np.empty((max(K, 0), rays.size), np.float32), np.empty((max(K, 0), rays.size), np.uint32)
+    if not 0 <= int(flags) < 2 ** 32 or not 0 <= K < 2 ** 32 or not load_library().clw_host_cast_layers(
+            _ptr(rays), rays.size, int(flags), K, _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, _ptr(t), _ptr(ids)):
+        raise ValueError("clw_host_cast_layers rejects these arguments (at least one ray, fewer than 2^30, a kind bit and only CAST_* bits in flags, K in 1..8)")
+    return {"t": t, "id": ids}
+
+
+def camera_rays_host(cam: clw_camera, proj: clw_projection | None = None, id_begin: int = 0, id_end: int | None = None) -> np.ndarray:
+    """clw_host_camera_rays: the rays of the global ids [id_begin, id_end) of the camera's frame (id_end None = its last) under a camera model
+    (None = the pinhole) as query rays -> RAY_QUERY [id_end - id_begin] with tmax = inf and ignore = ID_NONE."""
+    proj = clw_projection() if proj is None else proj
+    id_end = cam.width * cam.height if id_end is None else int(id_end)
+    rays = np.zeros(max(id_end - int(id_begin), 0), RAY_QUERY)
+    if not load_library().clw_host_camera_rays(C.byref(cam), C.byref(proj), int(id_begin), id_end, _ptr(rays)):
+        raise ValueError("clw_host_camera_rays rejects these arguments (what clw_host_projection_rays rejects)")
+    return rays
 
 
 CULL_SPHERES, CULL_LIGHTS = 1, 2      # the bits of a primary-ray cull table's bytes (hip_wrap_ext.h: clw_host_primary_cull)
@@ -1014,6 +1073,57 @@ class ClWrap:
             return 0
         return int(self.L.clw_ext_cast_rays_device(C.byref(self.w), C.c_void_p(rays_ptr or None), int(n), int(flags), C.c_void_p(hits_ptr or None),
                                                    C.c_void_p(blocked_ptr or None)))
+
+    def cast_layers(self, rays, flags: int = CAST_SPHERES | CAST_PLANES, K: int = 4):
+        """clw_ext_cast_layers: the K nearest listed candidates of every ray (RAY_QUERY [n]) against the bound scene, on the device ->
+        {"t": float32 [K, n], "id": uint32 [K, n]}, or None when it is refused (no scene bound, no ray, unknown flag bits, no kind, K outside 1..8)."""
+        rays = np.ascontiguousarray(rays, RAY_QUERY).reshape(-1)
+        if rays.size >= 2 ** 32 or not 0 <= int(flags) < 2 ** 32 or not 0 <= int(K) < 2 ** 32:
+            return None
+        t, ids = np.empty((int(K), rays.size), np.float32), np.empty((int(K), rays.size), np.uint32)
+        n = self.L.clw_ext_cast_layers(C.byref(self.w), _ptr(rays), rays.size, int(flags), int(K), _ptr(t), _ptr(ids))
+        return {"t": t, "id": ids} if n == rays.size and n else None
+
+    def cast_layers_device(self, rays_ptr: int, n: int, flags: int, K: int, t_ptr: int, id_ptr: int) -> int:
+        """clw_ext_cast_layers_device: the layered query over the caller's device memory (integer addresses: n RAY_QUERY records; K * n floats;
+        K * n words, layer-major), on the wrapper's stream, without waiting -> n, or 0 when it is refused."""
+        if not 0 <= int(n) < 2 ** 32 or not 0 <= int(flags) < 2 ** 32 or not 0 <= int(K) < 2 ** 32:
+            return 0
+        return int(self.L.clw_ext_cast_layers_device(C.byref(self.w), C.c_void_p(rays_ptr or None), int(n), int(flags), int(K), C.c_void_p(t_ptr or None),
+                                                     C.c_void_p(id_ptr or None)))
+
+    def camera_rays(self, capacity: int):
+        """clw_ext_camera_rays: the query rays of the range the next trace launch would cover -> RAY_QUERY [n], or None when it is refused (no
+        camera latched, row bands, a projection that does not resolve, fewer than n records of capacity)."""
+        out = np.zeros(max(int(capacity), 1), RAY_QUERY)
+        n = self.L.clw_ext_camera_rays(C.byref(self.w), _ptr(out), int(capacity))
+        return out[:n].copy() if n else None
+
+    def camera_rays_device(self, rays_ptr: int, capacity: int) -> int:
+        """clw_ext_camera_rays_device: the same into the caller's device memory of `capacity` records, without waiting -> n, or 0."""
+        return int(self.L.clw_ext_camera_rays_device(C.byref(self.w), C.c_void_p(rays_ptr or None), int(capacity)))
+
+    def render_layers(self, flags: int = CAST_SPHERES | CAST_PLANES, K: int = 4) -> int:
+        """clw_ext_render_layers: the K layers of the launch camera's rays over the wrapper's range, on the device -> work-items (0 = refused)."""
+        if not 0 <= int(flags) < 2 ** 32 or not 0 <= int(K) < 2 ** 32:
+            return 0
+        return int(self.L.clw_ext_render_layers(C.byref(self.w), int(flags), int(K)))
+
+    def read_layers(self, what: int = LAYERS_T) -> np.ndarray:
+        """What the last render_layers left: LAYERS_T -> float32 [K * n], LAYERS_ID -> uint32 [K * n], layer-major; empty before the first."""
+        return self._read_pass(lambda p, cap: self.L.clw_ext_read_layers(C.byref(self.w), int(what), p, cap), np.uint32 if what == LAYERS_ID else np.float32)
+
+    def layers_device_ptr(self, what: int = LAYERS_T):
+        """Device address of the t or the id layers of the last render_layers (None before the first)."""
+        return self.L.clw_ext_layers_device_ptr(C.byref(self.w), int(what))
+
+    def pick_layers(self, x, y, flags: int = CAST_SPHERES | CAST_PLANES, K: int = 8):
+        """clw_ext_pick_layers: the K layers under frame pixel (x, y) -> LAYER [K], or None (no camera latched, the pixel is not one of this
+        wrapper's, refused flags or K)."""
+        if not 0 <= int(flags) < 2 ** 32 or not 1 <= int(K) <= LAYERS_MAX:
+            return None
+        out = np.zeros(int(K), LAYER)
+        return out if self.L.clw_ext_pick_layers(C.byref(self.w), int(x), int(y), int(flags), int(K), _ptr(out)) else None
 
     def unit_ao_open(self, point, normal, ids, width: int, rows: int, first_row: int, ao: clw_ao):
         """clw_ext_unit_ao_open: wt_ao_trace on synthetic channels against the bound scene -> uint8 [width * rows], or None when it is refused."""

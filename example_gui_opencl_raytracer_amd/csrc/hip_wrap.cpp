@@ -1002,6 +1002,7 @@ void cl_wrap_release(cl_wrap* wrap) {
     I->obj.release();
     I->ao.release();
     I->cast.free_buffers();
+    I->layers.release();
     I->ptab.free_all();
     I->adapt.free_all();
     if (I->tables_fence) (void)hipEventDestroy(I->tables_fence);

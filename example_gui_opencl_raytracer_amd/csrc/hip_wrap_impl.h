@@ -21,6 +21,7 @@
 #include "../../include/hip_wrap_ext.h"
 #include "ao_host.h"
 #include "cast_host.h"
+#include "layers_host.h"
 #include "launch_plan.h"
 #include "objects_host.h"
 #include "overlay_host.h"
@@ -243,6 +244,26 @@ struct Impl {
             rays = hits = nullptr; blocked = nullptr; cap = 0;
         }
     } cast;
+    /* layered ray queries (clw_ext_cast_layers / clw_ext_render_layers / clw_ext_pick_layers / clw_ext_camera_rays; whitted_layers.inc).  The
+     * range part -- the camera rays of a render_layers and its K planar layers of t and id, sized for the pass's range and its K -- is read back
+     * like every range pass (`done`).  The host-array entry points have buffers of their own, sized for the largest n and K * n so far; those
+     * calls wait for their own work.  A pick is both kernels on a one-pixel range into `pick`: the ray, then 8 t and 8 id words.  The device
+     * entry points work on the caller's memory and own nothing. */
+    struct Layers : RangePass {
+        void* rays = nullptr; float* t = nullptr; uint32_t* id = nullptr;
+        uint32_t K = 0;                 /* layers the range buffers hold per work-item */
+        void* h_rays = nullptr; float* h_t = nullptr; uint32_t* h_id = nullptr;
+        uint32_t h_rays_cap = 0;        /* rays h_rays holds (also the camera rays of clw_ext_camera_rays) */
+        size_t h_out_cap = 0;           /* words h_t and h_id hold each */
+        uint32_t* pick = nullptr;
+        void free_range() {
+            for (void* q : {rays, (void*)t, (void*)id}) if (q) (void)hipFree(q);
+            rays = nullptr; t = nullptr; id = nullptr; n = 0; K = 0; written = 0;
+        }
+        void free_host_rays() { if (h_rays) (void)hipFree(h_rays); h_rays = nullptr; h_rays_cap = 0; }
+        void free_host_out() { if (h_t) (void)hipFree(h_t); if (h_id) (void)hipFree(h_id); h_t = nullptr; h_id = nullptr; h_out_cap = 0; }
+        void release() { free_range(); free_host_rays(); free_host_out(); if (pick) (void)hipFree(pick); pick = nullptr; drop_done(); }
+    } layers;
     /* prepared scene cache */
     const Buffer *prep_s = nullptr, *prep_p = nullptr, *prep_l = nullptr;
     uint32_t prep_ns = 0, prep_np = 0, prep_nl = 0;

@@ -1,6 +1,6 @@
 /*
  * hip_wrap_passes.cpp -- the passes beside the trace launch (include/hip_wrap_ext.h): the primary-hit pass and the pick, the selection
- * overlay, the visible-object table, ambient occlusion and the ray queries.  Same conventions as hip_wrap.cpp; the shared internals are
+ * overlay, the visible-object table, ambient occlusion, the ray queries and the layered ray queries.  Same conventions as hip_wrap.cpp; the shared internals are
  * hip_wrap_impl.h's.
  */
 #include "hip_wrap_impl.h"
@@ -163,6 +163,46 @@ uint32_t cast_host_arrays(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uint32
     else HIP_OK(hipMemcpyAsync(blocked, C.blocked, (size_t)n, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
     finish(I);
     return n;
+}
+
+/* ---- layered ray queries ------------------------------------------------------------------------------------------------------------ */
+/* wt_cast_layers over device memory on the launch stream: K * n words into each of t and id.  CLWRAP_LAYERS_CAPACITY (4 or 8): tuning knob, the
+ * compiled list capacity to run where both hold K; anything else = the smallest that does */
+void launch_layers(Impl* I, const whitted_params& P, const wt_cast_class& cc, const void* rays, uint32_t n, uint32_t flags, uint32_t K, float* t,
+                   uint32_t* id, bool timed) {
+    const int want = env_int("CLWRAP_LAYERS_CAPACITY", 0);
+    const unsigned capacity = ((want == 4 || want == 8) && (uint32_t)want >= K) ? (unsigned)want : 0u;
+    LaunchTimer tm(I, CLW_TIMING_LAYERS, timed);
+    hipError_t e = WT_LAUNCH(I, cast_layers)(&P, cc.flags, cc.dyn_lds, rays, n, flags, K, capacity, t, id, I->stream);
+    if (e != hipSuccess) die("Couldn't run the kernel");
+    tm.done();
+}
+
+/* What the camera-ray kernel launches over: the linear range the next trace launch would cover -- the camera and range the raygen launch
+ * latched, clipped by the raytracer's `pixels` argument -- under the wrapper's camera model.  Needs no scene.  false (nothing launched; the
+ * panorama's tables may have been resolved) without a raytracer kernel or a latched camera, with row bands, for a projection the definition
+ * refuses, and for a range whose ids leave 32 bits. */
+struct CameraRange { whitted_params P; wt_projection T; };
+bool camera_range(cl_wrap* w, Impl* I, CameraRange& R) {
+    R = CameraRange{};
+    const int kid = raytracer_kernel(I);
+    if (kid < 0 || I->band_stride > 1u) return false;
+    Buffer* rays = find_rays(w, I, (cl_uint)kid);
+    uint32_t total;
+    if (!rays || !rays->gen_valid || !find_total(I->kernels[kid], total)) return false;
+    const RaygenArgs& g = rays->gen;
+    const uint32_t n = g.n_items < total ? g.n_items : total;
+    if (n == 0 || n >= (1u << 30) || g.width == 0u || g.band_stride > 1u || g.id_offset + n > (1ull << 32)) return false;
+    if (!resolve_projection(I, g, R.T)) return false;      /* (the pinhole too: what clw_host_camera_rays refuses) */
+    wt_plan_fused_range(&g, n, &R.P);
+    return true;
+}
+
+void launch_camera_rays(Impl* I, const CameraRange& R, void* rays, bool timed) {
+    LaunchTimer t(I, CLW_TIMING_CAMRAYS, timed);
+    hipError_t e = WT_LAUNCH(I, camera_rays)(&R.P, &R.T, rays, I->stream);
+    if (e != hipSuccess) die("Couldn't run the kernel");
+    t.done();
 }
 
 /* ---- the selection overlay ------------------------------------------------------------------------------------------------------- */
@@ -482,6 +522,138 @@ uint32_t clw_ext_cast_rays_device(cl_wrap* wrap, const void* d_rays, uint32_t n,
     if (!cast_params(wrap, I, n, P, cc)) return 0;
     launch_cast(I, P, cc, d_rays, n, flags, d_hits, (uint8_t*)d_blocked);
     return n;
+}
+
+uint32_t clw_ext_cast_layers(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uint32_t flags, uint32_t K, float* t, uint32_t* id) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    static_assert(sizeof(clw_layer) == 8, "the layered queries' ABI");
+    if (!wt_layers_check(n, flags, K) || !rays || !t || !id) return 0;
+    whitted_params P{};
+    wt_cast_class cc;
+    if (!cast_params(wrap, I, n, P, cc)) return 0;
+    Impl::Layers& B = I->layers;
+    const size_t words = (size_t)K * n;
+    if (B.h_rays_cap < n) {
+        B.free_host_rays();
+        HIP_OK(hipMalloc(&B.h_rays, (size_t)n * sizeof(clw_ray)), "Couldn't allocate device memory");
+        B.h_rays_cap = n;
+    }
+    if (B.h_out_cap < words) {
+        B.free_host_out();
+        HIP_OK(hipMalloc((void**)&B.h_t, words * 4), "Couldn't allocate device memory");
+        HIP_OK(hipMalloc((void**)&B.h_id, words * 4), "Couldn't allocate device memory");
+        B.h_out_cap = words;
+    }
+    HIP_OK(hipMemcpyAsync(B.h_rays, rays, (size_t)n * sizeof(clw_ray), hipMemcpyHostToDevice, I->stream), "Couldn't transfer the data from host to the device");
+    launch_layers(I, P, cc, B.h_rays, n, flags, K, B.h_t, B.h_id, true);
+    HIP_OK(hipMemcpyAsync(t, B.h_t, words * 4, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    HIP_OK(hipMemcpyAsync(id, B.h_id, words * 4, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    finish(I);
+    return n;
+}
+
+uint32_t clw_ext_cast_layers_device(cl_wrap* wrap, const void* d_rays, uint32_t n, uint32_t flags, uint32_t K, void* d_t, void* d_id) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    if (!wt_layers_check(n, flags, K) || !d_rays || !d_t || !d_id) return 0;
+    whitted_params P{};
+    wt_cast_class cc;
+    if (!cast_params(wrap, I, n, P, cc)) return 0;
+    launch_layers(I, P, cc, d_rays, n, flags, K, (float*)d_t, (uint32_t*)d_id, true);
+    return n;
+}
+
+uint32_t clw_ext_camera_rays_device(cl_wrap* wrap, void* d_rays, uint32_t capacity) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    CameraRange R;
+    if (!d_rays || !camera_range(wrap, I, R) || capacity < R.P.n_items) return 0;
+    launch_camera_rays(I, R, d_rays, true);
+    return R.P.n_items;
+}
+
+uint32_t clw_ext_camera_rays(cl_wrap* wrap, clw_ray* out, uint32_t capacity) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    CameraRange R;
+    if (!out || !camera_range(wrap, I, R) || capacity < R.P.n_items) return 0;
+    const uint32_t n = R.P.n_items;
+    Impl::Layers& B = I->layers;
+    if (B.h_rays_cap < n) {
+        B.free_host_rays();
+        HIP_OK(hipMalloc(&B.h_rays, (size_t)n * sizeof(clw_ray)), "Couldn't allocate device memory");
+        B.h_rays_cap = n;
+    }
+    launch_camera_rays(I, R, B.h_rays, true);
+    HIP_OK(hipMemcpyAsync(out, B.h_rays, (size_t)n * sizeof(clw_ray), hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    finish(I);
+    return n;
+}
+
+uint32_t clw_ext_render_layers(cl_wrap* wrap, uint32_t flags, uint32_t K) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    CameraRange R;
+    if (!wt_layers_check(1u, flags, K) || !camera_range(wrap, I, R)) return 0;
+    const uint32_t n = R.P.n_items;
+    whitted_params P{};
+    wt_cast_class cc;
+    if (!cast_params(wrap, I, n, P, cc)) return 0;
+    Impl::Layers& B = I->layers;
+    if (B.n != n || B.K < K) {      /* (as range_resize: a pass under way may still use the old buffers) */
+        if (B.n && B.done) { finish(I); (void)hipEventSynchronize(B.done); }
+        B.free_range();
+        HIP_OK(hipMalloc(&B.rays, (size_t)n * sizeof(clw_ray)), "Couldn't allocate device memory");
+        HIP_OK(hipMalloc((void**)&B.t, (size_t)K * n * 4), "Couldn't allocate device memory");
+        HIP_OK(hipMalloc((void**)&B.id, (size_t)K * n * 4), "Couldn't allocate device memory");
+        B.n = n; B.K = K;
+    }
+    launch_camera_rays(I, R, B.rays, true);
+    launch_layers(I, P, cc, B.rays, n, flags, K, B.t, B.id, true);
+    range_mark_done(I, B, K);      /* (written: the layers the last pass left to read) */
+    return n;
+}
+
+uint32_t clw_ext_read_layers(cl_wrap* wrap, uint32_t what, void* out, uint32_t capacity_bytes) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    const Impl::Layers& B = I->layers;
+    if (!B.written || what > 1u) return 0;
+    return range_read(B, what == 0u ? (const void*)B.t : (const void*)B.id, 4u * B.written, out, capacity_bytes);
+}
+
+void* clw_ext_layers_device_ptr(cl_wrap* wrap, uint32_t what) {
+    const Impl::Layers& B = impl_of(wrap)->layers;
+    if (!B.written || what > 1u) return nullptr;
+    return what == 0u ? (void*)B.t : (void*)B.id;
+}
+
+int clw_ext_pick_layers(cl_wrap* wrap, uint32_t x, uint32_t y, uint32_t flags, uint32_t K, clw_layer* out) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    CameraRange R;
+    if (!out || !wt_layers_check(1u, flags, K) || !camera_range(wrap, I, R)) return 0;
+    if (x >= R.P.width || y >= R.P.height) return 0;
+    const uint64_t pixel = (uint64_t)y * R.P.width + x;      /* is the pixel one of the wrapper's work-items? */
+    if (pixel < R.P.id_offset || pixel - R.P.id_offset >= R.P.n_items) return 0;
+    whitted_params P{};
+    wt_cast_class cc;
+    if (!cast_params(wrap, I, 1u, P, cc)) return 0;
+    /* the same two kernels on the one-pixel range [pixel, pixel + 1) */
+    R.P.id_offset = pixel; R.P.n_items = 1; R.P.tiled = 0; R.P.rows = 0; R.P.row_offset = y;
+    Impl::Layers& B = I->layers;
+    constexpr uint32_t RAY_WORDS = sizeof(clw_ray) / 4;
+    if (!B.pick) HIP_OK(hipMalloc((void**)&B.pick, (RAY_WORDS + 2 * WT_LAYERS_MAX) * 4), "Couldn't allocate device memory");
+    float* dt = (float*)(B.pick + RAY_WORDS);
+    uint32_t* did = B.pick + RAY_WORDS + WT_LAYERS_MAX;
+    launch_camera_rays(I, R, B.pick, false);
+    launch_layers(I, P, cc, B.pick, 1u, flags, K, dt, did, false);      /* (n = 1: layer k is word k) */
+    uint32_t h[2 * WT_LAYERS_MAX];
+    if (hipMemcpyAsync(h, dt, sizeof h, hipMemcpyDeviceToHost, I->stream) != hipSuccess) die("Failed to transfer device memory to host");
+    finish(I);
+    for (uint32_t k = 0; k < K; k++) { memcpy(&out[k].t, &h[k], 4); out[k].id = h[WT_LAYERS_MAX + k]; }
+    return 1;
 }
 
 } /* extern "C" */

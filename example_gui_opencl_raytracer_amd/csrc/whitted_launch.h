@@ -37,6 +37,9 @@ WT_BOTH(hipError_t, launch_ao_resolve, (const unsigned char* open, const unsigne
                                         unsigned rows, unsigned ao_flags, unsigned K, unsigned strength, hipStream_t s))
 WT_BOTH(hipError_t, launch_cast, (const whitted_params* P, int flags, unsigned groups, unsigned batches, size_t dyn_lds, const void* rays, unsigned n,
                                   unsigned cast_flags, void* hits, unsigned char* blocked, hipStream_t s))
+WT_BOTH(hipError_t, launch_cast_layers, (const whitted_params* P, int flags, size_t dyn_lds, const void* rays, unsigned n, unsigned cast_flags, unsigned K,
+                                         unsigned capacity, float* t, unsigned* id, hipStream_t s))
+WT_BOTH(hipError_t, launch_camera_rays, (const whitted_params* P, const wt_projection* T, void* rays, hipStream_t s))
 #undef WT_BOTH
 #undef WT_FAST_ONLY
 

@@ -1,5 +1,6 @@
 /* whitted_launch.inc -- instantiates the kernels of whitted_trace.inc (and the primary-hit pass of whitted_gbuffer.inc, built from its
- * pieces, the camera models of whitted_projection.inc, the ambient occlusion pass of whitted_ao.inc, the ray queries of whitted_cast.inc, the selection overlay of
+ * pieces, the camera models of whitted_projection.inc, the ambient occlusion pass of whitted_ao.inc, the ray queries of whitted_cast.inc, the layered
+ * ray queries of whitted_layers.inc, the selection overlay of
  * whitted_overlay.inc, the visible-object table of whitted_objects.inc and the builder of the primary-ray cull table of whitted_cull.inc) in
  * namespace WT_NS and exports the C launchers the shim calls. */
 #include "primary_cull_host.h"
@@ -9,6 +10,7 @@ namespace WT_NS {
 #include "whitted_projection.inc"
 #include "whitted_ao.inc"
 #include "whitted_cast.inc"
+#include "whitted_layers.inc"
 #include "whitted_overlay.inc"
 #include "whitted_objects.inc"
 #include "whitted_cull.inc"
@@ -301,5 +303,49 @@ WT_LAUNCHER(cast)(const whitted_params* P, int flags, unsigned groups, unsigned 
         else if (lds) hipLaunchKernelGGL((WT_NS::wt_cast<true, false, true>), g, block, dyn_lds, s, *P, A);
         else hipLaunchKernelGGL((WT_NS::wt_cast<false, false, true>), g, block, 0, s, *P, A);
     }
+    return hipGetLastError();
+}
+
+/* layered ray queries (whitted_layers.inc): wt_cast_layers over `n` rays (2 float4 each) on the device, one workgroup of one wave per 64 rays,
+ * geometry as the caller's plan chose it (launch_plan.c: wt_plan_cast -- flags as the gbuffer launcher).  `t` and `id` receive K * n words each,
+ * layer-major.  `capacity`: the compiled list capacity to run, 4 or 8 (>= K), or 0 = the smallest that holds K.  The caller has checked n,
+ * cast_flags and K (csrc/layers_host.h: wt_layers_check) */
+WT_LAUNCHER(cast_layers)(const whitted_params* P, int flags, size_t dyn_lds, const void* rays, unsigned n, unsigned cast_flags, unsigned K,
+                         unsigned capacity, float* t, unsigned* id, hipStream_t s) {
+    if (capacity == 0u) capacity = K <= 4u ? 4u : 8u;
+    if (n == 0u || n >= (1u << 30) || !(cast_flags & 7u) || (cast_flags & ~15u) || K == 0u || K > capacity || (capacity != 4u && capacity != 8u) || !rays ||
+        !t || !id || dyn_lds > 48u * 1024u)
+        return hipErrorInvalidValue;
+    const bool grid = (flags & WT_F_GRID) != 0, lds = !grid && (flags & WT_F_GEOM_LDS);
+    WT_NS::wt_layers_args A = {};
+    A.rays = (const float4*)rays; A.t = t; A.id = id; A.n = n; A.flags = cast_flags; A.K = K;
+    const dim3 g((n + 63u) / 64u), block(WT_BLOCK);
+    if (capacity == 4u) {
+        if (grid) hipLaunchKernelGGL((WT_NS::wt_cast_layers<false, true, 4>), g, block, 0, s, *P, A);
+        else if (lds) hipLaunchKernelGGL((WT_NS::wt_cast_layers<true, false, 4>), g, block, dyn_lds, s, *P, A);
+        else hipLaunchKernelGGL((WT_NS::wt_cast_layers<false, false, 4>), g, block, 0, s, *P, A);
+    } else {
+        if (grid) hipLaunchKernelGGL((WT_NS::wt_cast_layers<false, true, 8>), g, block, 0, s, *P, A);
+        else if (lds) hipLaunchKernelGGL((WT_NS::wt_cast_layers<true, false, 8>), g, block, dyn_lds, s, *P, A);
+        else hipLaunchKernelGGL((WT_NS::wt_cast_layers<false, false, 8>), g, block, 0, s, *P, A);
+    }
+    return hipGetLastError();
+}
+
+/* the launch camera's rays as query rays (whitted_layers.inc: wt_camera_rays): the `P->n_items` work-items of the linear range that starts at
+ * global id `P->id_offset` of the camera `P` carries (wt_plan_fused_range), 2 float4 each into `rays`; `T` = the camera model (model 0: the
+ * pinhole; the panorama's tables sized for the frame, as the raygen_proj launcher asks) */
+WT_LAUNCHER(camera_rays)(const whitted_params* P, const wt_projection* T, void* rays, hipStream_t s) {
+    const bool proj = T->model != CLW_PROJ_PERSPECTIVE;
+    if (P->n_items == 0u || P->n_items >= (1u << 30) || P->width == 0u || P->band_stride > 1u || P->id_offset + P->n_items > (1ull << 32) || !rays ||
+        (proj && T->model != CLW_PROJ_ORTHO && T->model != CLW_PROJ_EQUIRECT) ||
+        (T->model == CLW_PROJ_EQUIRECT && (!T->col || !T->row || T->width != P->width || T->height != P->height)))
+        return hipErrorInvalidValue;
+    WT_NS::wt_camrays_args A = {};
+    for (int a = 0; a < 3; a++) { A.corner[a] = P->corner[a]; A.right[a] = P->right[a]; A.up[a] = P->up[a]; A.origin[a] = P->origin[a]; }
+    A.w_factor = P->w_factor; A.h_factor = P->h_factor; A.width = P->width; A.n = P->n_items; A.id_offset = P->id_offset; A.rays = (float4*)rays;
+    const dim3 g((A.n + 255u) / 256u), block(256);
+    if (proj) hipLaunchKernelGGL(WT_NS::wt_camera_rays<true>, g, block, 0, s, A, *T);
+    else hipLaunchKernelGGL(WT_NS::wt_camera_rays<false>, g, block, 0, s, A, *T);
     return hipGetLastError();
 }

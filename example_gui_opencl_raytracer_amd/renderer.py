@@ -52,6 +52,11 @@ rays meet the scene, from anywhere, no camera involved: the nearest hit (t, id, 
 anything within ``tmax``.  Directions are not normalised: t is in units of their length, so ``line_of_sight(a, b)`` casts ``b - a`` with
 ``tmax = 1``.  Nothing else the renderer holds is touched.
 
+``cast_layers(origins, dirs, K, ...)`` / ``layers(K)`` / ``pick_through(x, y)`` / ``camera_rays()``: layered ray queries
+(clw_ext_cast_layers) -- the K (1..8) nearest surfaces of every ray in depth order instead of the first one, in one launch: along the
+caller's rays, along every pixel's camera ray, or under one pixel (click again to select the object behind).  ``camera_rays()`` returns the
+launch camera's rays as query rays.  Nothing else the renderer holds is touched; not available with row bands.
+
 ``projection=...`` / ``set_projection(model, ...)`` / ``look_ortho`` / ``look_panorama``: the camera models beside the pinhole
 (clw_ext_set_projection) -- ``'ortho'``: parallel rays from the image plane, the top / front / side view of an editor; ``'equirect'``: a
 latitude-longitude panorama of up to 360 x 180 degrees around the camera origin.  ``render()``, ``read_rays()``, ``gbuffer()``, ``pick``,
@@ -323,6 +328,57 @@ class Renderer:
         a = np.asarray(a, np.float32).reshape(-1, 3)
         b = np.asarray(b, np.float32).reshape(-1, 3)
         return ~self.cast_rays(a, b - a, tmax=1.0, opaque_only=opaque_only, any_hit=True)
+
+    # ---- layered ray queries
+    def cast_layers(self, origins, dirs, K: int = 4, tmax=np.inf, ignore=None, kinds=("sphere", "plane"), opaque_only: bool = False) -> dict:
+        """The K nearest surfaces of every ray (arguments as ``cast_rays``) -> {"t": float32 [K, n], "id": uint32 [K, n]}: layer k of ray i at
+        [k, i], ordered by (t, id word), every primitive at most once, entries past a ray's candidates {inf, api.ID_NONE}.  K is 1..8; there
+        is no total count: ask for K + 1 to learn whether there is more."""
+        got = self.w.cast_layers(api.make_rays(origins, dirs, tmax, ignore), api.cast_flags(kinds, opaque_only), K)
+        if got is None:
+            raise RuntimeError("the layered ray query was refused (at least one ray, at least one kind, K in 1..8?)")
+        return got
+
+    def cast_layers_device(self, rays_ptr: int, n: int, K: int, t_ptr: int, id_ptr: int, kinds=("sphere", "plane"), opaque_only: bool = False) -> int:
+        """The layered query over the caller's device memory, by integer device address: n api.RAY_QUERY records in, K * n floats and K * n id
+        words out, layer-major.  Launched on the wrapper's stream (``w.set_stream``) without waiting -> n."""
+        got = self.w.cast_layers_device(rays_ptr, n, api.cast_flags(kinds, opaque_only), K, t_ptr, id_ptr)
+        if got != n:
+            raise RuntimeError("the layered ray query was refused (at least one ray, at least one kind, K in 1..8, all three addresses?)")
+        return got
+
+    def camera_rays(self) -> np.ndarray:
+        """The rays of this renderer's pixels through the camera set last, under the camera model, as query rays -> api.RAY_QUERY [pixels]
+        (tmax = inf, ignore = api.ID_NONE): what ``cast_rays`` / ``cast_layers`` take.  Not available with row bands."""
+        if self._camera_set:
+            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        got = self.w.camera_rays(self.pixels)
+        if got is None or got.size != self.pixels:
+            raise RuntimeError("the camera rays were refused (a camera set? no row bands? a projection that resolves?)")
+        return got
+
+    def layers(self, K: int = 4, kinds=("sphere", "plane"), opaque_only: bool = False) -> dict:
+        """What lies behind every pixel, in depth order -> {"t": float32 [K, rows, width], "id": uint32 [K, rows, width]}: the K nearest surfaces
+        along the pixel's camera ray (``camera_rays()`` through ``cast_layers``, both on the device).  Layer 0 is what ``gbuffer()`` sees where
+        the kinds agree; t is in units of the ray's direction (unit for the pinhole and the panorama)."""
+        if self._camera_set:
+            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        if self.w.render_layers(api.cast_flags(kinds, opaque_only), K) != self.pixels:
+            raise RuntimeError("the layers pass was refused (a camera set? at least one kind, K in 1..8, no row bands?)")
+        shape = (int(K), self.rows, self.width)
+        return {"t": self.w.read_layers(api.LAYERS_T).reshape(shape), "id": self.w.read_layers(api.LAYERS_ID).reshape(shape)}
+
+    def pick_through(self, x: int, y: int, K: int = 8, kinds=("sphere", "plane"), opaque_only: bool = False) -> list | None:
+        """Everything under pixel (x, y) of the frame, nearest first -> a list of {"id", "kind", "index", "depth"} of at most K entries (click
+        again to select the object behind: the next entry), empty where the ray meets nothing; None when the pixel is not one of this
+        renderer's rows (or no camera has been set)."""
+        if self._camera_set:
+            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        got = self.w.pick_layers(x, y, api.cast_flags(kinds, opaque_only), K)
+        if got is None:
+            return None
+        return [dict(id=int(e["id"]), kind=int(e["id"]) >> 30, index=int(e["id"]) & 0x3FFFFFFF, depth=np.float32(e["t"])) for e in got
+                if int(e["id"]) != api.ID_NONE]
 
     # ---- the visible-object table
     def objects(self, rect=None) -> np.ndarray:

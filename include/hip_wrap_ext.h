@@ -602,6 +602,63 @@ uint32_t clw_ext_occluded_rays(cl_wrap* wrap, const clw_ray* rays, uint32_t n, u
 uint32_t clw_ext_cast_rays_device(cl_wrap* wrap, const void* d_rays, uint32_t n, uint32_t flags, void* d_hits, void* d_blocked);
 #define CLW_TIMING_CAST 0x43415354u
 
+/* Layered ray queries: not the first thing a ray meets but the K nearest, in depth order -- select the object behind the one just selected,
+ * list what lies under the cursor, count the surfaces between two points, measure how far behind a glass sphere the floor is -- in ONE launch
+ * and one scan of the scene, where peeling with `ignore` costs K of each and loses or doubles the second of two primitives at the same t.
+ * clw_host_cast_layers is THE definition; the device pass (wt_cast_layers: csrc/whitted_layers.inc) equals it bit for bit in both builds.
+ * Rays, flags (CLW_CAST_*), the kinds that take part, `ignore`, CLW_CAST_OPAQUE, the sphere and plane tests and the rule `candidate iff hit &&
+ * t <= tmax` are exactly those of clw_host_cast_rays above.  On top of them:
+ *   - A candidate is LISTED iff additionally t < +inf.  {+inf, CLW_ID_NONE} is the empty entry, so a candidate at infinity cannot be told from
+ *     none.
+ *   - The listed candidates of a ray are ordered by (t ascending, id word ascending as uint32).  The id word is kind << 30 | index, so its
+ *     order is the scan order spheres, planes, lights: equal t keeps the earlier primitive first, as the nearest query does.  A primitive
+ *     appears at most once.  A sphere is listed at the one t its test returns -- its near side, or its far side for a ray that starts
+ *     inside.
+ *   - Output is planar, layer-major: entry k of ray i is t[k * n + i], id[k * n + i], k = 0 .. K-1; entries past the number of listed
+ *     candidates hold {+inf, CLW_ID_NONE}.  A caller who needs to know whether there is more asks for K + 1.
+ *   - Refused (0 returned, nothing written): whatever clw_host_cast_rays refuses; K == 0 or K > 8; a NULL t or id.
+ * So layer 0 is {t, id} of clw_host_cast_rays for every ray whose nearest t is finite, and the layers for K are a prefix of those for K + 1.
+ * clw_host_camera_rays: the records of clw_host_projection_rays for the global ids [id_begin, id_end) of the camera's frame, repacked as query
+ * rays {origin, tmax = +inf, dir, ignore = CLW_ID_NONE} -- all three models, the pinhole included (its direction is the raygen's, normalised);
+ * it refuses what clw_host_projection_rays refuses.  The device kernel (wt_camera_rays) equals it bit for bit. */
+typedef struct clw_layer { float t; uint32_t id; } clw_layer;   /* 8 bytes */
+int clw_host_cast_layers(const clw_ray* rays, uint32_t n, uint32_t flags, uint32_t K, const void* spheres, uint32_t ns, const void* planes,
+                         uint32_t np, const void* lights, uint32_t nl, float* t /* K * n */, uint32_t* id /* K * n */);   /* 1 = done, 0 = refused */
+int clw_host_camera_rays(const struct clw_camera* cam, const clw_projection* proj, uint64_t id_begin, uint64_t id_end, clw_ray* out);
+/* On the device, against the wrapper's bound scene, with the semantics of the three clw_ext_cast_* calls: the scene is prepared if needed and
+ * read staged in LDS, from global memory or through the uniform grid (which only skips tests); the caller's stream is used after
+ * clw_ext_set_stream; 0 is returned and nothing launched for what the definition refuses and when no scene is bound; the buffers of the
+ * host-array calls are allocated at first use, grown at need and freed by cl_wrap_release.
+ * clw_ext_cast_layers takes HOST arrays (n rays; K * n floats; K * n words), waits and returns n.  clw_ext_cast_layers_device takes the caller's
+ * DEVICE memory of the same sizes, does not wait and returns n.
+ * clw_ext_camera_rays / clw_ext_camera_rays_device write the query rays of the range the next trace launch would cover -- the latched camera
+ * under the projection set, work-item i being global id id_offset + i, as clw_ext_render_gbuffer -- into a host array (waits) or the caller's
+ * device memory (no wait) of `capacity` records, and return the work-items n.  They need no scene.  0 -- nothing launched -- without a latched
+ * camera, with row bands, with a projection that cannot be resolved, and when capacity < n.
+ * clw_ext_render_layers: the camera rays, then their K layers, into buffers the feature owns (sized for the range and K) -> work-items, 0 when
+ * either half refuses.  clw_ext_read_layers copies what the last render_layers left -- what = 0: K * n floats, 1: K * n id words, layer-major
+ * -- and returns the byte count (out = NULL or too small a capacity: the count only); clw_ext_layers_device_ptr is the device address, NULL
+ * before the first pass.
+ * clw_ext_pick_layers: the same two kernels on the one-pixel range of frame pixel (x, y), one small read-back: out[k] = layer k, k < K -- the
+ * pixel's column of clw_ext_render_layers, bit for bit.  1, or 0 as clw_ext_pick (no latched camera, a pixel that is not one of the wrapper's
+ * work-items, out = NULL), for refused flags or K, and with row bands.  Neither it nor clw_ext_render_layers restarts an accumulating view.
+ * All of these leave alone the framebuffer, the buffers of clw_ext_render_gbuffer, the overlay, the object table, the AO pass and the ray
+ * queries, an accumulating view and its count, the tile order and clw_ext_last_trace_flags.  Launches are logged under CLW_TIMING_LAYERS and
+ * CLW_TIMING_CAMRAYS in clw_ext_timing_get (a pick's are not, as clw_ext_pick's).
+ * Not built: the far side of a sphere as a layer of its own (exits); K > 8; a through-selection in the marquee and an X-ray outline in the
+ * overlay (consumers of the planar id layers on the device); a total candidate count -- the grid walk meets a sphere once per cell it is listed
+ * in and only the list tells repeats apart. */
+uint32_t clw_ext_cast_layers(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uint32_t flags, uint32_t K, float* t, uint32_t* id);     /* host arrays; waits */
+uint32_t clw_ext_cast_layers_device(cl_wrap* wrap, const void* d_rays, uint32_t n, uint32_t flags, uint32_t K, void* d_t, void* d_id);   /* no wait */
+uint32_t clw_ext_camera_rays(cl_wrap* wrap, clw_ray* out, uint32_t capacity);              /* host array; waits */
+uint32_t clw_ext_camera_rays_device(cl_wrap* wrap, void* d_rays, uint32_t capacity);       /* no wait */
+uint32_t clw_ext_render_layers(cl_wrap* wrap, uint32_t flags, uint32_t K);
+uint32_t clw_ext_read_layers(cl_wrap* wrap, uint32_t what /* 0 = t, 1 = id */, void* out, uint32_t capacity_bytes);
+void*    clw_ext_layers_device_ptr(cl_wrap* wrap, uint32_t what);
+int      clw_ext_pick_layers(cl_wrap* wrap, uint32_t x, uint32_t y, uint32_t flags, uint32_t K, clw_layer* out /* K */);
+#define CLW_TIMING_LAYERS  0x4C415952u
+#define CLW_TIMING_CAMRAYS 0x43524159u
+
 /* Work counters of the trace kernel.  enable=1 selects the counting build of the kernel
  * for subsequent launches (slower); read returns and clears
  *   out[0] path segments  out[1] shadow rays  out[2] light probes  out[3] skybox fetches
