@@ -25,7 +25,7 @@ HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc
 CC = os.environ.get("CC") or "gcc"
 
 DEVICE_DEPS = ["whitted_trace.inc", "whitted_hit.inc", "whitted_shade.inc", "whitted_bounce.inc", "whitted_pop.inc", "whitted_tpt.inc", "whitted_terms.inc",
-               "whitted_gbuffer.inc", "whitted_projection.inc", "whitted_ao.inc", "whitted_cast.inc", "whitted_layers.inc", "whitted_overlay.inc", "whitted_objects.inc", "whitted_cull.inc", "primary_cull_host.h", "whitted_launch.inc", "whitted_launch.h", "whitted_params.h",
+               "whitted_gbuffer.inc", "whitted_projection.inc", "whitted_query.inc", "whitted_ao.inc", "whitted_cast.inc", "whitted_layers.inc", "whitted_overlay.inc", "whitted_objects.inc", "whitted_cull.inc", "primary_cull_host.h", "whitted_launch.inc", "whitted_launch.h", "whitted_params.h",
                "projection_host.h"]
 SHIM_FLAGS = ["-O2", "-std=c++17", "-Wall"]
 SHIM_DEPS = ["hip_wrap_impl.h", "whitted_params.h", "whitted_launch.h", "launch_plan.h", "scene_prep.h", "ao_host.h", "cast_host.h", "layers_host.h", "overlay_host.h", "objects_host.h", "projection_host.h",
@@ -44,11 +44,11 @@ UNITS = [
     ("overlay_host.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra"],
      ["overlay_host.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
     ("ao_host.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra", "-D_DEFAULT_SOURCE"],
-     ["ao_host.h", "scene_prep.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
+     ["ao_host.h", "ref_tests.h", "scene_prep.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
     ("cast_host.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra", "-D_DEFAULT_SOURCE"],
-     ["cast_host.h", "scene_prep.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
+     ["cast_host.h", "ref_tests.h", "scene_prep.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
     ("layers_host.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra", "-D_DEFAULT_SOURCE"],
-     ["layers_host.h", "cast_host.h", "scene_prep.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
+     ["layers_host.h", "cast_host.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
     ("objects_host.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra"],
      ["objects_host.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
     ("primary_cull_host.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra", "-D_DEFAULT_SOURCE"],

@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "ref_tests.h"
 #include "scene_prep.h"
 
 int wt_ao_check(const clw_ao* ao) {
@@ -44,28 +45,7 @@ int clw_host_ao_dirs(uint32_t K, float* dirs4) {
 }
 
 /* ---- (b) the open rays of every pixel ----------------------------------------------------------------------------------------------- */
-static float dot3(const float a[3], const float b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-
-/* the primary-hit pass's evaluation of its winner (whitted_gbuffer.inc: wt_gb_ref_sphere, wt_gb_ref_plane), the same operations in C */
-static int ref_sphere(const float o[3], const float d[3], const float s[4], float* t) {
-    const float a = dot3(d, d);
-    const float v[3] = {o[0] - s[0], o[1] - s[1], o[2] - s[2]};
-    const float c = dot3(v, v) - fabsf(s[3]);
-    const float b = dot3(v, d);
-    const float D = b * b + (-(a * c));
-    const float sD = sqrtf(D);
-    const float t0 = (-b - sD) / a;
-    *t = (t0 < 0) ? (-b + sD) / a : t0;
-    return !(D < 0) && !(*t <= 0);
-}
-static int ref_plane(const float o[3], const float d[3], const float n[4], const float p0[4], float* t) {
-    const float w[3] = {p0[0] - o[0], p0[1] - o[1], p0[2] - o[2]};
-    const float num = dot3(w, n);
-    const float b = dot3(d, n);
-    *t = num / b;
-    return !(b == 0) && !(*t <= 0);
-}
-
+/* the two hit tests: ref_tests.h (ref_sphere, ref_plane), the one copy */
 int clw_host_ao_open(const float* point, const float* normal, const uint32_t* ids, uint32_t width, uint32_t rows, uint32_t first_row,
                      const void* spheres, uint32_t ns, const void* planes, uint32_t np, const clw_ao* ao, const float* dirs4,
                      uint8_t* open_u8) {

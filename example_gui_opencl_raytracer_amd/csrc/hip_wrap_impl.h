@@ -76,6 +76,22 @@ struct Kernel {
 
 struct TimingEntry { hipEvent_t start, stop; cl_uint kernel; };
 
+/* A device staging buffer that only grows: freed and allocated again when a call needs more than it holds, kept otherwise.  Its owner's calls
+ * wait for their own work, so nothing is in flight on it when it is replaced. */
+struct DeviceGrow {
+    void* p = nullptr;
+    size_t cap = 0;                 /* bytes p holds */
+    void* reserve(size_t bytes) {
+        if (cap < bytes) {
+            release();
+            HIP_OK(hipMalloc(&p, bytes), "Couldn't allocate device memory");
+            cap = bytes;
+        }
+        return p;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
 struct Impl {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -234,35 +250,27 @@ struct Impl {
         void release() { free_buffers(); if (dirs) (void)hipFree(dirs); dirs = nullptr; drop_done(); }
     } ao;
     /* ray queries (clw_ext_cast_rays / clw_ext_occluded_rays; whitted_cast.inc): the buffers of the host-array entry points -- the rays as uploaded,
-     * the hits, the blocked bytes -- sized for the largest n so far.  Those calls wait for their own work, so nothing is in flight on them between
+     * the hits, the blocked bytes -- each grown to the largest n so far (DeviceGrow).  Those calls wait for their own work, so nothing is in flight on them between
      * calls; clw_ext_cast_rays_device works on the caller's memory and owns nothing. */
     struct Cast {
-        void* rays = nullptr; void* hits = nullptr; uint8_t* blocked = nullptr;
-        uint32_t cap = 0;               /* rays the buffers hold */
-        void free_buffers() {
-            for (void* q : {rays, hits, (void*)blocked}) if (q) (void)hipFree(q);
-            rays = hits = nullptr; blocked = nullptr; cap = 0;
-        }
+        DeviceGrow rays, hits, blocked;
+        void free_buffers() { rays.release(); hits.release(); blocked.release(); }
     } cast;
     /* layered ray queries (clw_ext_cast_layers / clw_ext_render_layers / clw_ext_pick_layers / clw_ext_camera_rays; whitted_layers.inc).  The
      * range part -- the camera rays of a render_layers and its K planar layers of t and id, sized for the pass's range and its K -- is read back
-     * like every range pass (`done`).  The host-array entry points have buffers of their own, sized for the largest n and K * n so far; those
+     * like every range pass (`done`).  The host-array entry points have buffers of their own, grown to the largest n and K * n so far (DeviceGrow); those
      * calls wait for their own work.  A pick is both kernels on a one-pixel range into `pick`: the ray, then 8 t and 8 id words.  The device
      * entry points work on the caller's memory and own nothing. */
     struct Layers : RangePass {
         void* rays = nullptr; float* t = nullptr; uint32_t* id = nullptr;
         uint32_t K = 0;                 /* layers the range buffers hold per work-item */
-        void* h_rays = nullptr; float* h_t = nullptr; uint32_t* h_id = nullptr;
-        uint32_t h_rays_cap = 0;        /* rays h_rays holds (also the camera rays of clw_ext_camera_rays) */
-        size_t h_out_cap = 0;           /* words h_t and h_id hold each */
+        DeviceGrow h_rays, h_t, h_id;   /* (h_rays also holds the camera rays of clw_ext_camera_rays) */
         uint32_t* pick = nullptr;
         void free_range() {
             for (void* q : {rays, (void*)t, (void*)id}) if (q) (void)hipFree(q);
             rays = nullptr; t = nullptr; id = nullptr; n = 0; K = 0; written = 0;
         }
-        void free_host_rays() { if (h_rays) (void)hipFree(h_rays); h_rays = nullptr; h_rays_cap = 0; }
-        void free_host_out() { if (h_t) (void)hipFree(h_t); if (h_id) (void)hipFree(h_id); h_t = nullptr; h_id = nullptr; h_out_cap = 0; }
-        void release() { free_range(); free_host_rays(); free_host_out(); if (pick) (void)hipFree(pick); pick = nullptr; drop_done(); }
+        void release() { free_range(); h_rays.release(); h_t.release(); h_id.release(); if (pick) (void)hipFree(pick); pick = nullptr; drop_done(); }
     } layers;
     /* prepared scene cache */
     const Buffer *prep_s = nullptr, *prep_p = nullptr, *prep_l = nullptr;

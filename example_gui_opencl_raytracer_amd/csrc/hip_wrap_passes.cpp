@@ -150,17 +150,12 @@ uint32_t cast_host_arrays(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uint32
     wt_cast_class cc;
     if (!cast_params(wrap, I, n, P, cc)) return 0;
     Impl::Cast& C = I->cast;
-    if (C.cap < n) {
-        C.free_buffers();
-        HIP_OK(hipMalloc(&C.rays, (size_t)n * sizeof(clw_ray)), "Couldn't allocate device memory");
-        HIP_OK(hipMalloc(&C.hits, (size_t)n * sizeof(clw_hit)), "Couldn't allocate device memory");
-        HIP_OK(hipMalloc((void**)&C.blocked, (size_t)n), "Couldn't allocate device memory");
-        C.cap = n;
-    }
-    HIP_OK(hipMemcpyAsync(C.rays, rays, (size_t)n * sizeof(clw_ray), hipMemcpyHostToDevice, I->stream), "Couldn't transfer the data from host to the device");
-    launch_cast(I, P, cc, C.rays, n, flags, hits ? C.hits : nullptr, hits ? nullptr : C.blocked);
-    if (hits) HIP_OK(hipMemcpyAsync(hits, C.hits, (size_t)n * sizeof(clw_hit), hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
-    else HIP_OK(hipMemcpyAsync(blocked, C.blocked, (size_t)n, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    void* d_rays = C.rays.reserve((size_t)n * sizeof(clw_ray));
+    void* d_out = hits ? C.hits.reserve((size_t)n * sizeof(clw_hit)) : C.blocked.reserve((size_t)n);
+    HIP_OK(hipMemcpyAsync(d_rays, rays, (size_t)n * sizeof(clw_ray), hipMemcpyHostToDevice, I->stream), "Couldn't transfer the data from host to the device");
+    launch_cast(I, P, cc, d_rays, n, flags, hits ? d_out : nullptr, hits ? nullptr : (uint8_t*)d_out);
+    if (hits) HIP_OK(hipMemcpyAsync(hits, d_out, (size_t)n * sizeof(clw_hit), hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    else HIP_OK(hipMemcpyAsync(blocked, d_out, (size_t)n, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
     finish(I);
     return n;
 }
@@ -534,21 +529,13 @@ uint32_t clw_ext_cast_layers(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uin
     if (!cast_params(wrap, I, n, P, cc)) return 0;
     Impl::Layers& B = I->layers;
     const size_t words = (size_t)K * n;
-    if (B.h_rays_cap < n) {
-        B.free_host_rays();
-        HIP_OK(hipMalloc(&B.h_rays, (size_t)n * sizeof(clw_ray)), "Couldn't allocate device memory");
-        B.h_rays_cap = n;
-    }
-    if (B.h_out_cap < words) {
-        B.free_host_out();
-        HIP_OK(hipMalloc((void**)&B.h_t, words * 4), "Couldn't allocate device memory");
-        HIP_OK(hipMalloc((void**)&B.h_id, words * 4), "Couldn't allocate device memory");
-        B.h_out_cap = words;
-    }
-    HIP_OK(hipMemcpyAsync(B.h_rays, rays, (size_t)n * sizeof(clw_ray), hipMemcpyHostToDevice, I->stream), "Couldn't transfer the data from host to the device");
-    launch_layers(I, P, cc, B.h_rays, n, flags, K, B.h_t, B.h_id, true);
-    HIP_OK(hipMemcpyAsync(t, B.h_t, words * 4, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
-    HIP_OK(hipMemcpyAsync(id, B.h_id, words * 4, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    void* d_rays = B.h_rays.reserve((size_t)n * sizeof(clw_ray));
+    float* d_t = (float*)B.h_t.reserve(words * 4);
+    uint32_t* d_id = (uint32_t*)B.h_id.reserve(words * 4);
+    HIP_OK(hipMemcpyAsync(d_rays, rays, (size_t)n * sizeof(clw_ray), hipMemcpyHostToDevice, I->stream), "Couldn't transfer the data from host to the device");
+    launch_layers(I, P, cc, d_rays, n, flags, K, d_t, d_id, true);
+    HIP_OK(hipMemcpyAsync(t, d_t, words * 4, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    HIP_OK(hipMemcpyAsync(id, d_id, words * 4, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
     finish(I);
     return n;
 }
@@ -579,14 +566,9 @@ uint32_t clw_ext_camera_rays(cl_wrap* wrap, clw_ray* out, uint32_t capacity) {
     CameraRange R;
     if (!out || !camera_range(wrap, I, R) || capacity < R.P.n_items) return 0;
     const uint32_t n = R.P.n_items;
-    Impl::Layers& B = I->layers;
-    if (B.h_rays_cap < n) {
-        B.free_host_rays();
-        HIP_OK(hipMalloc(&B.h_rays, (size_t)n * sizeof(clw_ray)), "Couldn't allocate device memory");
-        B.h_rays_cap = n;
-    }
-    launch_camera_rays(I, R, B.h_rays, true);
-    HIP_OK(hipMemcpyAsync(out, B.h_rays, (size_t)n * sizeof(clw_ray), hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    void* d_rays = I->layers.h_rays.reserve((size_t)n * sizeof(clw_ray));
+    launch_camera_rays(I, R, d_rays, true);
+    HIP_OK(hipMemcpyAsync(out, d_rays, (size_t)n * sizeof(clw_ray), hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
     finish(I);
     return n;
 }

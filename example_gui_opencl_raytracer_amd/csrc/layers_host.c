@@ -1,41 +1,15 @@
 /* layers_host.c -- THE definition of the layered ray queries (include/hip_wrap_ext.h: clw_host_cast_layers, clw_host_camera_rays): the device
  * passes (wt_cast_layers, wt_camera_rays: whitted_layers.inc) are held to it bit for bit.  Written for reading, not for speed: every ray on its
- * own against every primitive that takes part, the rules in the header's order.  The two tests are those of cast_host.c, restated: the same
- * operations in the same order.  Built with -ffp-contract=off: every float32 operation below is rounded once. */
+ * own against every primitive that takes part, the rules in the header's order.  The per-ray rule -- which primitives are candidates, in which order -- is
+ * cast_host.c's wt_cast_enumerate, the one copy; what is defined here is what becomes of a candidate.  Built with -ffp-contract=off: every float32 operation below is rounded once. */
 #include "layers_host.h"
 
 #include <math.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include "cast_host.h"
-#include "scene_prep.h"
 
 int wt_layers_check(uint32_t n, uint32_t flags, uint32_t K) { return wt_cast_check(n, flags) && K >= 1u && K <= (uint32_t)WT_LAYERS_MAX; }
-
-static float dot3(const float a[3], const float b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-
-/* cast_host.c's ref_sphere and ref_plane */
-static int ref_sphere(const float o[3], const float d[3], const float s[4], float* t) {
-    const float a = dot3(d, d);
-    const float v[3] = {o[0] - s[0], o[1] - s[1], o[2] - s[2]};
-    const float c = dot3(v, v) - fabsf(s[3]);
-    const float b = dot3(v, d);
-    const float D = b * b + (-(a * c));
-    const float sD = sqrtf(D);
-    const float t0 = (-b - sD) / a;
-    *t = (t0 < 0) ? (-b + sD) / a : t0;
-    return !(D < 0) && !(*t <= 0);
-}
-static int ref_plane(const float o[3], const float d[3], const float n[4], const float p0[4], float* t) {
-    const float w[3] = {p0[0] - o[0], p0[1] - o[1], p0[2] - o[2]};
-    const float num = dot3(w, n);
-    const float b = dot3(d, n);
-    *t = num / b;
-    return !(b == 0) && !(*t <= 0);
-}
-
-static int sign_bit(float f) { uint32_t u; memcpy(&u, &f, 4); return (int)(u >> 31); }
 
 /* a ray's list: the K smallest keys (t, id) met so far, ascending; entries past `count` are not read */
 typedef struct { clw_layer e[WT_LAYERS_MAX]; uint32_t count, K; } layer_list;
@@ -54,49 +28,29 @@ static void list_candidate(layer_list* L, float t, uint32_t id) {
     L->e[at].id = id;
 }
 
+/* the visitor of cast_host.c's wt_cast_enumerate: the list of the ray under way, and where a finished one goes */
+typedef struct { layer_list L; float* t_out; uint32_t* id_out; uint32_t n; } layers_out;
+
+static void layers_begin(void* ctx) { ((layers_out*)ctx)->L.count = 0u; }
+
+static void layers_take(void* ctx, float t, uint32_t id) { list_candidate(&((layers_out*)ctx)->L, t, id); }
+
+static void layers_done(void* ctx, uint32_t k, const clw_ray* ray, const wt_cast_geom* g) {
+    layers_out* s = (layers_out*)ctx;
+    (void)ray; (void)g;
+    for (uint32_t j = 0; j < s->L.K; j++) {      /* planar, layer-major */
+        s->t_out[(size_t)j * s->n + k] = j < s->L.count ? s->L.e[j].t : INFINITY;
+        s->id_out[(size_t)j * s->n + k] = j < s->L.count ? s->L.e[j].id : CLW_ID_NONE;
+    }
+}
+
 int clw_host_cast_layers(const clw_ray* rays, uint32_t n, uint32_t flags, uint32_t K, const void* spheres, uint32_t ns, const void* planes,
                          uint32_t np, const void* lights, uint32_t nl, float* t_out, uint32_t* id_out) {
-    if (!wt_layers_check(n, flags, K) || !rays || !t_out || !id_out || (ns > 0u && !spheres) || (np > 0u && !planes) || (nl > 0u && !lights)) return 0;
-    /* the words the device reads (cast_host.c) */
-    const size_t f4 = wprep_geom_f4(ns, np, nl);
-    float* geom = (float*)malloc(16 * (f4 ? f4 : 1));
-    float* ptex = (float*)malloc(32 * (size_t)(np ? np : 1));
-    if (!geom || !ptex) { free(geom); free(ptex); return 0; }
-    wprep_build((const uint8_t*)spheres, ns, (const uint8_t*)planes, np, (const uint8_t*)lights, nl, geom, ptex);
-    const float* pl = geom + 4 * (size_t)ns;
-    const float* lg = pl + 8 * (size_t)np;
-    for (uint32_t k = 0; k < n; k++) {
-        const float* o = rays[k].origin;
-        const float* d = rays[k].dir;
-        const float tmax = rays[k].tmax;
-        const uint32_t ignore = rays[k].ignore;
-        layer_list L;
-        L.count = 0u; L.K = K;
-        float t;
-        if (flags & CLW_CAST_SPHERES)
-            for (uint32_t i = 0; i < ns; i++) {
-                const float* s = geom + 4 * (size_t)i;
-                if (i == ignore || ((flags & CLW_CAST_OPAQUE) && sign_bit(s[3]))) continue;
-                if (ref_sphere(o, d, s, &t) && t <= tmax) list_candidate(&L, t, i);
-            }
-        if (flags & CLW_CAST_PLANES)
-            for (uint32_t i = 0; i < np; i++) {
-                if (((1u << 30) | i) == ignore) continue;
-                if (ref_plane(o, d, pl + 8 * (size_t)i, pl + 8 * (size_t)i + 4, &t) && t <= tmax) list_candidate(&L, t, (1u << 30) | i);
-            }
-        if (flags & CLW_CAST_LIGHTS)
-            for (uint32_t i = 0; i < nl; i++) {
-                if (((2u << 30) | i) == ignore) continue;
-                if (ref_sphere(o, d, lg + 8 * (size_t)i, &t) && t <= tmax) list_candidate(&L, t, (2u << 30) | i);
-            }
-        for (uint32_t j = 0; j < K; j++) {      /* planar, layer-major */
-            t_out[(size_t)j * n + k] = j < L.count ? L.e[j].t : INFINITY;
-            id_out[(size_t)j * n + k] = j < L.count ? L.e[j].id : CLW_ID_NONE;
-        }
-    }
-    free(geom);
-    free(ptex);
-    return 1;
+    if (!wt_layers_check(n, flags, K) || !t_out || !id_out) return 0;
+    layers_out s;
+    s.L.count = 0u; s.L.K = K; s.t_out = t_out; s.id_out = id_out; s.n = n;
+    const wt_cast_visitor v = {layers_begin, layers_take, layers_done, &s};
+    return wt_cast_enumerate(rays, n, flags, spheres, ns, planes, np, lights, nl, &v);
 }
 
 int clw_host_camera_rays(const struct clw_camera* cam, const clw_projection* proj, uint64_t id_begin, uint64_t id_end, clw_ray* out) {

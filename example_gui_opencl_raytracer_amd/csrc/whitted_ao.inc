@@ -1,6 +1,6 @@
 /* whitted_ao.inc -- ray-traced ambient occlusion over the primary-hit buffers (hip_wrap_ext.h: clw_ao, clw_ext_render_ao): wt_ao_trace counts,
  * for every pixel of a range of whole rows, how many of K short any-hit rays over the hemisphere of its normal stay open; wt_ao_resolve turns
- * the counts into pixels.  Included by whitted_launch.inc behind whitted_projection.inc, so both exist in the fast and the strict unit.
+ * the counts into pixels.  Included by whitted_launch.inc behind whitted_query.inc, so both exist in the fast and the strict unit.
  * csrc/ao_host.c is their definition: the arithmetic below is that file's, operation for operation -- wt_gb_ref_dot's sums, IEEE square root
  * and divide, no fused operation (`#pragma clang fp contract(off)` wherever a float is computed) -- so both builds give the host's bits.
  *
@@ -34,17 +34,10 @@ struct wt_ao_args {
     float radius;               /* > 0, +inf = unlimited */
 };
 
-/* the definition's sphere test, the invariants of the origin (v = o - c, cc = v.v - |r r|) and of the direction (a = d.d) already taken: the
- * operations of wt_gb_ref_sphere in its order.  D < 0 leaves before the roots: wt_gb_ref_sphere's verdict is then `no hit` whatever t is. */
+/* the definition's sphere test with the invariants already taken (whitted_query.inc: wt_query_sphere, the one copy): is it met at t <= radius? */
 __device__ __forceinline__ bool wt_ao_sphere(f3 v, float cc, f3 d, float a, float radius) {
-#pragma clang fp contract(off)
-    const float b = wt_gb_ref_dot(v, d);
-    const float D = b * b + (-(a * cc));
-    if (D < 0) return false;
-    const float sD = sqrtf(D);
-    const float t0 = (-b - sD) / a;
-    const float t = (t0 < 0) ? (-b + sD) / a : t0;
-    return !(t <= 0) && t <= radius;
+    float t;
+    return wt_query_sphere(v, cc, d, a, radius, t);
 }
 
 /* the definition's plane test, num = (p0 - o).n taken: the operations of wt_gb_ref_plane in its order */

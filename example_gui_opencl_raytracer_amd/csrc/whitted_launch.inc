@@ -1,6 +1,6 @@
 /* whitted_launch.inc -- instantiates the kernels of whitted_trace.inc (and the primary-hit pass of whitted_gbuffer.inc, built from its
- * pieces, the camera models of whitted_projection.inc, the ambient occlusion pass of whitted_ao.inc, the ray queries of whitted_cast.inc, the layered
- * ray queries of whitted_layers.inc, the selection overlay of
+ * pieces, the camera models of whitted_projection.inc, the queries' shared scan of whitted_query.inc, the ambient occlusion pass of
+ * whitted_ao.inc, the ray queries of whitted_cast.inc, the layered ray queries of whitted_layers.inc, the selection overlay of
  * whitted_overlay.inc, the visible-object table of whitted_objects.inc and the builder of the primary-ray cull table of whitted_cull.inc) in
  * namespace WT_NS and exports the C launchers the shim calls. */
 #include "primary_cull_host.h"
@@ -8,6 +8,7 @@ namespace WT_NS {
 #include "whitted_trace.inc"
 #include "whitted_gbuffer.inc"
 #include "whitted_projection.inc"
+#include "whitted_query.inc"
 #include "whitted_ao.inc"
 #include "whitted_cast.inc"
 #include "whitted_layers.inc"
@@ -145,12 +146,21 @@ WT_LAUNCHER(unit)(int op, const float* in, float* out, unsigned n, unsigned stri
     return hipGetLastError();
 }
 
+/* The geometry-flavour ladder, written once: KERNEL<GEOM_LDS, GRID TAIL> as bind_scene chose the geometry -- WT_F_GRID the uniform grid, else
+ * WT_F_GEOM_LDS the scene staged in LDS, else read from global memory.  TAIL = WT_TAIL(the kernel's further template arguments), or empty.
+ * Each flavour gets the dynamic LDS bytes its launcher names for it; what follows `s` are the kernel's arguments. */
+#define WT_TAIL(...) , __VA_ARGS__
+#define WT_LAUNCH_FLAVOUR(KERNEL, TAIL, flags, g, block, lds_grid, lds_staged, lds_global, s, ...) \
+    do { \
+        if ((flags) & WT_F_GRID) hipLaunchKernelGGL((WT_NS::KERNEL<false, true TAIL>), g, block, lds_grid, s, __VA_ARGS__); \
+        else if ((flags) & WT_F_GEOM_LDS) hipLaunchKernelGGL((WT_NS::KERNEL<true, false TAIL>), g, block, lds_staged, s, __VA_ARGS__); \
+        else hipLaunchKernelGGL((WT_NS::KERNEL<false, false TAIL>), g, block, lds_global, s, __VA_ARGS__); \
+    } while (0)
+
 WT_LAUNCHER(unit_scene)(const whitted_params* P, int flags, int op, const float* in, float* out, unsigned n,
                                            unsigned stride_in, unsigned stride_out, size_t dyn_lds, hipStream_t s) {
     const dim3 grid((n + 63) / 64), block(64);
-    if (flags & WT_F_GRID) hipLaunchKernelGGL((WT_NS::wt_unit_scene<false, true>), grid, block, 0, s, *P, op, in, out, n, stride_in, stride_out);
-    else if (flags & WT_F_GEOM_LDS) hipLaunchKernelGGL((WT_NS::wt_unit_scene<true, false>), grid, block, dyn_lds, s, *P, op, in, out, n, stride_in, stride_out);
-    else hipLaunchKernelGGL((WT_NS::wt_unit_scene<false, false>), grid, block, 0, s, *P, op, in, out, n, stride_in, stride_out);
+    WT_LAUNCH_FLAVOUR(wt_unit_scene, /* no tail */, flags, grid, block, 0, dyn_lds, 0, s, *P, op, in, out, n, stride_in, stride_out);
     return hipGetLastError();
 }
 
@@ -160,13 +170,8 @@ WT_LAUNCHER(gbuffer)(const whitted_params* P, int flags, unsigned grid, size_t d
                                         float* normal, float* point, float* albedo, const wt_projection* T, hipStream_t s) {
     const WT_NS::wt_gbuffer_out G = {depth, id, normal, point, albedo};
     const dim3 g(grid), block(WT_BLOCK);
-    if (T->model != CLW_PROJ_PERSPECTIVE) {      /* the instantiation that calls wt_proj_ray */
-        if (flags & WT_F_GRID) hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, true, true>), g, block, 0, s, *P, G, *T);
-        else if (flags & WT_F_GEOM_LDS) hipLaunchKernelGGL((WT_NS::wt_gbuffer<true, false, true>), g, block, dyn_lds, s, *P, G, *T);
-        else hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, false, true>), g, block, 0, s, *P, G, *T);
-    } else if (flags & WT_F_GRID) hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, true, false>), g, block, 0, s, *P, G, *T);
-    else if (flags & WT_F_GEOM_LDS) hipLaunchKernelGGL((WT_NS::wt_gbuffer<true, false, false>), g, block, dyn_lds, s, *P, G, *T);
-    else hipLaunchKernelGGL((WT_NS::wt_gbuffer<false, false, false>), g, block, 0, s, *P, G, *T);
+    if (T->model != CLW_PROJ_PERSPECTIVE) WT_LAUNCH_FLAVOUR(wt_gbuffer, WT_TAIL(true), flags, g, block, 0, dyn_lds, 0, s, *P, G, *T);      /* (calls wt_proj_ray) */
+    else WT_LAUNCH_FLAVOUR(wt_gbuffer, WT_TAIL(false), flags, g, block, 0, dyn_lds, 0, s, *P, G, *T);
     return hipGetLastError();
 }
 
@@ -258,9 +263,7 @@ WT_LAUNCHER(ao_trace)(const whitted_params* P, int flags, const float* point, co
     A.point = point; A.normal = normal; A.ids = ids; A.dirs = (const float4*)dirs; A.open = open;
     A.width = width; A.rows = rows; A.first_row = first_row; A.tiles_per_row = (unsigned)tpr; A.K = K; A.radius = radius;
     const dim3 g((unsigned)(tpr * trows)), block(WT_BLOCK);
-    if (flags & WT_F_GRID) hipLaunchKernelGGL((WT_NS::wt_ao_trace<false, true>), g, block, dyn_lds, s, *P, A);
-    else if (lds) hipLaunchKernelGGL((WT_NS::wt_ao_trace<true, false>), g, block, dyn_lds, s, *P, A);
-    else hipLaunchKernelGGL((WT_NS::wt_ao_trace<false, false>), g, block, dyn_lds, s, *P, A);
+    WT_LAUNCH_FLAVOUR(wt_ao_trace, /* no tail */, flags, g, block, dyn_lds, dyn_lds, dyn_lds, s, *P, A);      /* (the table in every flavour) */
     return hipGetLastError();
 }
 
@@ -290,19 +293,11 @@ WT_LAUNCHER(cast)(const whitted_params* P, int flags, unsigned groups, unsigned 
         groups == 0u || (unsigned long long)groups * batches * 64ull < n || (unsigned long long)groups * batches * 64ull >= (1ull << 31) ||
         dyn_lds > 48u * 1024u)
         return hipErrorInvalidValue;
-    const bool grid = (flags & WT_F_GRID) != 0, lds = !grid && (flags & WT_F_GEOM_LDS);
     WT_NS::wt_cast_args A = {};
     A.rays = (const float4*)rays; A.hits = (float4*)hits; A.blocked = blocked; A.n = n; A.flags = cast_flags; A.batches = batches;
     const dim3 g(groups), block(WT_BLOCK);
-    if (hits) {
-        if (grid) hipLaunchKernelGGL((WT_NS::wt_cast<false, true, false>), g, block, 0, s, *P, A);
-        else if (lds) hipLaunchKernelGGL((WT_NS::wt_cast<true, false, false>), g, block, dyn_lds, s, *P, A);
-        else hipLaunchKernelGGL((WT_NS::wt_cast<false, false, false>), g, block, 0, s, *P, A);
-    } else {
-        if (grid) hipLaunchKernelGGL((WT_NS::wt_cast<false, true, true>), g, block, 0, s, *P, A);
-        else if (lds) hipLaunchKernelGGL((WT_NS::wt_cast<true, false, true>), g, block, dyn_lds, s, *P, A);
-        else hipLaunchKernelGGL((WT_NS::wt_cast<false, false, true>), g, block, 0, s, *P, A);
-    }
+    if (hits) WT_LAUNCH_FLAVOUR(wt_cast, WT_TAIL(false), flags, g, block, 0, dyn_lds, 0, s, *P, A);
+    else WT_LAUNCH_FLAVOUR(wt_cast, WT_TAIL(true), flags, g, block, 0, dyn_lds, 0, s, *P, A);
     return hipGetLastError();
 }
 
@@ -316,19 +311,11 @@ WT_LAUNCHER(cast_layers)(const whitted_params* P, int flags, size_t dyn_lds, con
     if (n == 0u || n >= (1u << 30) || !(cast_flags & 7u) || (cast_flags & ~15u) || K == 0u || K > capacity || (capacity != 4u && capacity != 8u) || !rays ||
         !t || !id || dyn_lds > 48u * 1024u)
         return hipErrorInvalidValue;
-    const bool grid = (flags & WT_F_GRID) != 0, lds = !grid && (flags & WT_F_GEOM_LDS);
     WT_NS::wt_layers_args A = {};
     A.rays = (const float4*)rays; A.t = t; A.id = id; A.n = n; A.flags = cast_flags; A.K = K;
     const dim3 g((n + 63u) / 64u), block(WT_BLOCK);
-    if (capacity == 4u) {
-        if (grid) hipLaunchKernelGGL((WT_NS::wt_cast_layers<false, true, 4>), g, block, 0, s, *P, A);
-        else if (lds) hipLaunchKernelGGL((WT_NS::wt_cast_layers<true, false, 4>), g, block, dyn_lds, s, *P, A);
-        else hipLaunchKernelGGL((WT_NS::wt_cast_layers<false, false, 4>), g, block, 0, s, *P, A);
-    } else {
-        if (grid) hipLaunchKernelGGL((WT_NS::wt_cast_layers<false, true, 8>), g, block, 0, s, *P, A);
-        else if (lds) hipLaunchKernelGGL((WT_NS::wt_cast_layers<true, false, 8>), g, block, dyn_lds, s, *P, A);
-        else hipLaunchKernelGGL((WT_NS::wt_cast_layers<false, false, 8>), g, block, 0, s, *P, A);
-    }
+    if (capacity == 4u) WT_LAUNCH_FLAVOUR(wt_cast_layers, WT_TAIL(4), flags, g, block, 0, dyn_lds, 0, s, *P, A);
+    else WT_LAUNCH_FLAVOUR(wt_cast_layers, WT_TAIL(8), flags, g, block, 0, dyn_lds, 0, s, *P, A);
     return hipGetLastError();
 }
 

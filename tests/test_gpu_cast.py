@@ -290,3 +290,24 @@ def test_line_of_sight(R, api, tex, sky, strict):
     rays = api.make_rays(a, b - a, tmax=1.0)
     for got, flags in ((opaque, S | P | O), (everything, S | P)):
         assert np.array_equal(got, api.occluded_rays_host(rays, flags, sc.spheres, sc.planes, sc.lights) == 0)
+
+
+# ------------------------------------------------------------------ 8. more than one batch per wave
+@pytest.mark.parametrize("batches", [2, 3])
+@pytest.mark.parametrize("name", ["small", "ns257-grid"])
+def test_several_batches_per_wave_equal_the_definition(R, api, tex, sky, strict, monkeypatch, name, batches):
+    """CLWRAP_CAST_BATCHES (read on every call): a wave serves 2 or 3 batches of 64 rays per staging.  The sizes hold ragged counts, and 193 rays
+    under 3 batches leave the second workgroup one valid lane in its first batch and nothing for the others (base >= n)."""
+    assert 193 in SIZES and any(n % 64 for n in SIZES)
+    monkeypatch.setenv("CLWRAP_CAST_BATCHES", str(batches))
+    sc, (setup, geometry) = cc.scene_of(name.split("-")[0]), UNIT_SCENES[name]
+    bad = []
+    with rendering(R, sc, tex, sky, 8, 8, setup=setup, cam=None, strict=strict) as r:
+        for (n, flags, rays, hits, blocked) in expected(name):
+            d = (differing(r.w.cast_rays(rays, flags), hits), differing(r.w.occluded_rays(rays, flags), blocked))
+            if any(d):
+                bad.append((n, flags) + d)
+        grid = r.w.get_grid()
+        assert bool(grid and grid["built"]) == (geometry == "grid")
+    print(f"{name} {'strict' if strict else 'fast'} {batches} batches: {len(expected(name))} cases x nearest and any, differing bytes {bad[:8]}")
+    assert not bad

@@ -382,3 +382,24 @@ def test_the_timing_ids_count_the_launches(R, api, demo_scene, tex, sky, strict)
         # the parent's ids count what they counted
         assert r.w.timing_get(api.TIMING_GBUFFER)[0] == 1 and r.w.timing_get(api.TIMING_CAST)[0] == 1 and r.w.timing_get(1)[0] == 1
         assert r.w.timing_get(api.TIMING_AO)[0] == 0 and r.w.timing_get(api.TIMING_OVERLAY)[0] == 0
+
+
+# ------------------------------------------------------------------ 10. the larger compiled capacity at a small K
+@pytest.mark.parametrize("name", ["stack", "coincident-grid"])
+def test_capacity_8_at_small_K_equals_the_definition(R, api, tex, sky, strict, monkeypatch, name):
+    """CLWRAP_LAYERS_CAPACITY=8 (read on every call) runs the C = 8 kernel where K <= 4 would take C = 4: the worst entry, and the entry the grid
+    walk ends on, is K - 1, not C - 1."""
+    monkeypatch.setenv("CLWRAP_LAYERS_CAPACITY", "8")
+    sc, (setup, geometry) = lc.scene_of(name.split("-")[0]), SCENES[name]
+    cases = [e for e in expected(name) if e[2] in (1, 3, 4)]
+    assert {e[2] for e in cases} == {1, 3, 4}
+    bad = []
+    with rendering(R, sc, tex, sky, 8, 8, setup=setup, cam=None, strict=strict) as r:
+        for (n, flags, K, rays, want) in cases:
+            d = differing(r.w.cast_layers(rays, flags, K), want)
+            if d:
+                bad.append((n, flags, K, d))
+        grid = r.w.get_grid()
+        assert bool(grid and grid["built"]) == (geometry == "grid")
+    print(f"{name} {'strict' if strict else 'fast'} capacity 8: {len(cases)} cases, differing words {bad[:8]}")
+    assert not bad
