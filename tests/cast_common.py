@@ -113,14 +113,136 @@ def cloud_scene():
     return grid_layout("cloud")[0]
 
 
+# ---- the tangent pair: an equal t met from two cells of the grid
+TANGENT_A = ((0.75, 0.0, 1.0), 1.25)                 # the small sphere (centre, radius) ...
+TANGENT_B = ((6.0, 0.0, 8.0), 10.0)                  # ... and the large one it touches from inside at (0, 0, 0)
+TANGENT_FILLERS = 300
+# (origin, direction): both meet A and B at t = 1 exactly in float32 -- along x: b = -70, D = 36 and b = -112, D = 2304; along z: b = -20, D = 16
+# and b = -48, D = 1024 -- after a stretch inside B's box alone (5.5 units along x, 1.75 along z)
+TANGENT_EXACT = (((-8.0, 0.0, 0.0), (8.0, 0.0, 0.0)), ((0.0, 0.0, -4.0), (0.0, 0.0, 4.0)))
+TANGENT_SHIFT = (3.0, 12.0, 5.0)                     # moves the whole construction; every term above stays exact
+TANGENT_VARIANTS = {"tangent": {}, "tangent_opaque": dict(glass=False), "tangent_swapped": dict(swapped=True),
+                    "tangent_shifted": dict(shift=TANGENT_SHIFT)}
+
+
+def tangent_scene(glass=True, swapped=False, shift=(0.0, 0.0, 0.0)):
+    """Two spheres that touch internally where a ray meets them, so that both give the same t bits, with more than 256 spheres around them
+    so that the scene takes the uniform grid: the small sphere A at index 0 (glass, or opaque), the large B (opaque) at the last index --
+    `swapped`: the other way round, the control in which a cell's ascending order alone gives the answer.  B's box is (nearly) the grid's
+    bounds, so B is listed in every cell and a ray from outside A's box walks cells that list B alone before the cell of the hit, which
+    lists both: the walk holds B when it meets A, the LOWER index, at an equal t.  The fillers (r 0.1 .. 0.3, inside B's box, |y| >= 1.5) keep
+    off both exact rays; the floor lies below B's box, parallel to both."""
+    rng = np.random.default_rng(0x7A96)
+    n = TANGENT_FILLERS
+    sp = S.sphere_grid_scene(n + 2, 1).spheres.copy()          # plastic spheres with hashed colours: the geometry is overwritten
+    fill = rng.uniform([-3.7, 1.5, -1.7], [15.7, 9.7, 17.7], (n, 3))
+    fill[:, 1] *= rng.choice([-1.0, 1.0], n)
+    a, b = (n + 1, 0) if swapped else (0, n + 1)
+    sp["origin"][1:n + 1] = fill.astype(F)
+    sp["radius"][1:n + 1] = rng.uniform(0.1, 0.3, n).astype(F)
+    sp["origin"][a], sp["radius"][a] = TANGENT_A
+    sp["origin"][b], sp["radius"][b] = TANGENT_B
+    if glass:
+        g = S.glass()
+        for name in ("ambient", "diffuse", "specular", "shininess", "transperent", "dielectric", "n", "reflectivity"):
+            sp["material"][name][a] = g[name]
+    base = S.render_map_scene()
+    planes, li = base.planes[:1].copy(), base.lights.copy()
+    planes["normal"], planes["point_in_plane"] = (0.0, 1.0, 0.0), (0.0, -12.0, 0.0)
+    li["origin"] = [(3.0, 4.0, 2.0), (-2.0, 6.0, 9.0), (9.0, -3.0, 5.0)]
+    li["radius"] = (0.1, 0.08, 0.1)
+    shift = np.asarray(shift, F)
+    sp["origin"] += shift
+    li["origin"] += shift
+    planes["point_in_plane"] += shift
+    return S.Scene(sp, planes, li)
+
+
+def tangent_ids(name):
+    """(index of A, index of B) in a variant of the tangent scene"""
+    n = TANGENT_FILLERS
+    return (n + 1, 0) if TANGENT_VARIANTS[name].get("swapped") else (0, n + 1)
+
+
+def tangent_exact_rays(name):
+    """api.RAY_QUERY [5 * len(TANGENT_EXACT)]: each exact ray as it stands, ignoring A, ignoring B, ending at tmax = 1 and at nextafter(1, 0)"""
+    shift = np.asarray(TANGENT_VARIANTS[name].get("shift", (0.0, 0.0, 0.0)), F)
+    a, b = tangent_ids(name)
+    rays = np.zeros(5 * len(TANGENT_EXACT), api.RAY_QUERY)
+    rays["tmax"], rays["ignore"] = np.inf, ID_NONE
+    for k, (o, d) in enumerate(TANGENT_EXACT):
+        rays["origin"][5 * k:5 * k + 5] = np.asarray(o, F) + shift
+        rays["dir"][5 * k:5 * k + 5] = d
+        rays["ignore"][5 * k + 1], rays["ignore"][5 * k + 2] = a, b
+        rays["tmax"][5 * k + 3], rays["tmax"][5 * k + 4] = F(1), np.nextafter(F(1), F(0))
+    return rays
+
+
+def tangent_rays(name, seed, n=N_HOST):
+    """-> (api.RAY_QUERY [n + 10], where the exact rays sit): make_rays' set of the scene with the exact rays spread among it, so that their
+    lanes share waves with rays of other walk lengths"""
+    base = make_rays(scene_of(name), n, seed)[0]
+    exact = tangent_exact_rays(name)
+    at = (np.arange(exact.size) * (n // exact.size) + 7).astype(np.int64)      # positions in `base` in front of which they go
+    rays = np.insert(base, at, exact)
+    where = at + np.arange(exact.size)
+    assert rays[where].tobytes() == exact.tobytes()
+    rays.setflags(write=False)
+    return rays, where
+
+
+def tangent_cells(name, reg_pad=0.0):
+    """The premise of the tangent scenes on the grid the library builds for them (grid_common.build_grid, the shim's density and `reg_pad`):
+    per exact ray -> (cells the ray is in before the cell of the hit that list B and not A, whether the cell of the hit lists both).  The
+    cells are taken from points 1 / 64 of a unit apart along the ray, in float64: a cell crossed for less than that may be missed, which can
+    only lose a B-only cell, never invent one."""
+    import grid_common as gridc
+    sc = scene_of(name)
+    G = gridc.build_grid(sc.spheres, reg_pad)
+    gridc.check_grid(sc.spheres["origin"], sc.spheres["radius"], reg_pad, G)
+    a, b = tangent_ids(name)
+    res, gmin, cell = G["res"], G["gmin"].astype(np.float64), G["cell"].astype(np.float64)
+    shift = np.asarray(TANGENT_VARIANTS[name].get("shift", (0.0, 0.0, 0.0)), np.float64)
+
+    def listed(p):
+        k = np.floor((p - gmin) / cell).astype(np.int64)
+        if (k < 0).any() or (k >= res).any():
+            return None, None
+        c = int((k[2] * res[1] + k[1]) * res[0] + k[0])
+        return c, set(G["items"][G["start"][c]:G["start"][c + 1]].tolist())
+    out = []
+    for o, d in TANGENT_EXACT:
+        o, d = np.asarray(o, np.float64) + shift, np.asarray(d, np.float64)
+        hit_cell, at_hit = listed(o + d)
+        steps = int(np.linalg.norm(d) * 64)
+        before = {}
+        for t in np.arange(steps) / steps:
+            c, items = listed(o + t * d)
+            if c is not None and c != hit_cell:
+                before[c] = items
+        out.append((sorted(c for c, items in before.items() if b in items and a not in items), a in at_hit and b in at_hit))
+    return out, G
+
+
 SCENES = {"planes": lambda: small_scene(spheres=False), "spheres": lambda: small_scene(planes=False), "small": small_scene, "ns257": ns257_scene,
-          "cloud": cloud_scene}
+          "cloud": cloud_scene, "tangent": tangent_scene}
 _scenes = {}
 
 
+GRID_SCENES = ("giants", "coincident", "touching", "tower")      # fuzz_scenes.grid_layout: more than 256 spheres each
+
+
 def scene_of(name):
+    """a scene of SCENES, a variant of the tangent scene (TANGENT_VARIANTS) or a grid layout (GRID_SCENES), built once"""
     if name not in _scenes:
-        _scenes[name] = SCENES[name]()
+        if name in SCENES:
+            _scenes[name] = SCENES[name]()
+        elif name in TANGENT_VARIANTS:
+            _scenes[name] = tangent_scene(**TANGENT_VARIANTS[name])
+        else:
+            from fuzz_scenes import grid_layout
+            assert name in GRID_SCENES, name
+            _scenes[name] = grid_layout(name)[0]
     return _scenes[name]
 
 

@@ -10,7 +10,7 @@ from example_gui_opencl_raytracer_amd import scene as S
 F = np.float32
 K_MAX = 8
 K_ALL = tuple(range(1, K_MAX + 1))
-GRID_SCENES = ("giants", "coincident", "touching", "tower")      # fuzz_scenes.grid_layout: more than 256 spheres each
+GRID_SCENES = cc.GRID_SCENES                                      # fuzz_scenes.grid_layout: more than 256 spheres each
 TIE_SCENES = ("small", "stack", "coincident")                     # built with coincident spheres: two ids at one t
 TRUNCATES_AT_8 = ("stack", "cloud", "coincident", "touching", "tower")      # some ray has more than 8 candidates; elsewhere more than K <= 4
 
@@ -94,7 +94,7 @@ _scenes = {}
 
 
 def scene_of(name):
-    if name in cc.SCENES:
+    if name in cc.SCENES or name in cc.TANGENT_VARIANTS or name in cc.GRID_SCENES:
         return cc.scene_of(name)
     if name not in _scenes:
         _scenes[name] = SCENES[name]()

@@ -133,6 +133,49 @@ def test_coincident_spheres_the_lower_index_wins():
     assert (again["id"][sel] == 3).all() and np.array_equal(again["t"][sel], hits["t"][sel])
 
 
+@pytest.mark.parametrize("reg_pad", [0.0, 0.1])
+@pytest.mark.parametrize("name", list(cc.TANGENT_VARIANTS))
+def test_the_tangent_pair_ties_across_cells(name, reg_pad):
+    """The premise of the GPU tests of the tie rule (test_gpu_cast.py, test_gpu_layers.py: wt_sink_nearest::grid_take takes an equal t only from
+    a lower index): A and B give the same t bits, the definition keeps the lower index, and on the grid the library builds -- without a pad
+    and with the pad of the scene's lights -- the ray is in a cell that lists B and not A before it is in the cell of the hit, which lists
+    both.  Without that cell the walk would meet the pair in one cell's ascending order and the GPU tests would prove nothing."""
+    import layers_common as lc
+    sc = cc.scene_of(name)
+    a, b = cc.tangent_ids(name)
+    lo, hi = min(a, b), max(a, b)
+    assert len(sc.spheres) == cc.TANGENT_FILLERS + 2 > 256
+    assert bool(sc.spheres["material"]["transperent"][a]) == cc.TANGENT_VARIANTS[name].get("glass", True) and not sc.spheres["material"]["transperent"][b]
+    rays = cc.tangent_exact_rays(name)
+    one, below = F(1), np.nextafter(F(1), F(0))
+    for only in (a, b):                                                  # each alone: t = 1, bit for bit
+        h = api.cast_rays_host(rays[0::5], cc.SPHERES, sc.spheres[only:only + 1], None, None)
+        assert (h["id"] == 0).all() and np.array_equal(h["t"].view(np.uint32), np.full(len(h), one).view(np.uint32)), only
+    for flags, planes, lights in ((cc.SPHERES, None, None), (cc.SPHERES | cc.PLANES, sc.planes, sc.lights), (cc.KINDS, sc.planes, sc.lights)):
+        hits = api.cast_rays_host(rays, flags, sc.spheres, planes, lights)
+        model = cc.cast_model(rays, flags, sc.spheres, planes, lights)[0]
+        assert hits.tobytes() == model.tobytes()
+        for k in range(len(cc.TANGENT_EXACT)):
+            h = hits[5 * k:5 * k + 5]
+            assert h["id"].tolist() == [lo, b, a, lo, cc.ID_NONE], (name, flags, k, h["id"])      # plain, ignore A, ignore B, tmax 1, tmax below 1
+            assert h["t"][:4].tolist() == [1.0] * 4 and np.isposinf(h["t"][4])
+        two = api.cast_layers_host(rays, flags, 2, sc.spheres, planes, lights)
+        assert two["id"][:, 0::5].T.tolist() == [[lo, hi]] * len(cc.TANGENT_EXACT) and (two["t"][:, 0::5] == one).all()
+        t, ids, count = lc.candidates(rays, flags, sc.spheres, planes, lights)
+        assert np.array_equal(two["id"], lc.layers_of(t, ids, 2)["id"])
+    opaque = api.cast_rays_host(rays, cc.SPHERES | cc.OPAQUE, sc.spheres, None, None)
+    assert opaque["id"][0] == (b if sc.spheres["material"]["transperent"][a] else lo)
+    assert rays["tmax"][4] == below and below < one
+    cells, G = cc.tangent_cells(name, reg_pad)
+    print(f"{name} pad {reg_pad}: grid {G['res'].tolist()} cells of {G['cell'].tolist()}; cells before the hit that list B alone: {[len(c) for c, _ in cells]}")
+    assert (G["res"] > 1).all()
+    for k, (b_only, both_at_hit) in enumerate(cells):
+        assert both_at_hit, (name, k)
+        if k == 0:                       # the ray along x: 5.5 units of B's box before A's
+            assert len(b_only) >= 2, (name, reg_pad, b_only)
+        # (the ray along z has 1.75 units of B's box before A's, about one cell: it rides along, and decides where it finds such a cell)
+
+
 # ------------------------------------------------------------------ 4. closed forms with dyadic values
 def test_closed_forms():
     sc = cc.scene_of("small")

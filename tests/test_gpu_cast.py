@@ -16,6 +16,9 @@ WT_V_GEOM_GLOBAL = 1                     # csrc/launch_plan.h: geometry read fro
 SIZES = (1, 63, 64, 65, 193, 4099)      # one lane, a ragged wave, a whole one, one and a lane, several workgroups, many with a ragged tail
 S, P, L, O = cc.SPHERES, cc.PLANES, cc.LIGHTS, cc.OPAQUE
 FLAG_SETS = {"planes": (P, P | L), "spheres": (S | O, S | L), "small": (S | P, S | P | L | O), "ns257": (S | P, S | P | L), "cloud": (S | P | O, S | P | L)}
+# the grid layouts of fuzz_scenes.grid_layout but `offset` (make_rays draws origins up to three times the scene's bounds away: thousands of units
+# from the spheres, outside the domain where the float sphere test decides)
+FLAG_SETS.update({name: (S | P, S | P | L | O) for name in cc.GRID_SCENES})
 # name -> (setup of the wrapper, the geometry the pass must take: "lds" | "global" | "grid")
 UNIT_SCENES = {
     "planes": (None, "lds"),
@@ -27,6 +30,8 @@ UNIT_SCENES = {
     "cloud-grid": (None, "grid"),
     "cloud-linear": (lambda w: w.set_grid(0), "global"),
 }
+for _name in cc.GRID_SCENES:             # each walked and scanned: grid == linear == the definition
+    UNIT_SCENES.update({_name + "-grid": (None, "grid"), _name + "-linear": (lambda w: w.set_grid(0), "global")})
 _expected = {}
 
 
@@ -89,6 +94,68 @@ def test_casts_equal_the_definition(R, api, tex, sky, strict, name):
         took = "grid" if grid and grid["built"] and "linear" not in name else ("lds" if len(sc.spheres) <= gridc.GRID_MIN_SPHERES and "global" not in name else "global")
         assert took == geometry
     print(f"{name} {'strict' if strict else 'fast'}: {len(expected(name))} cases x nearest and any, differing bytes {sum(b[2] + b[3] for b in bad)} {bad[:8]}")
+    assert not bad
+
+
+# ------------------------------------------------------------------ 1b. an equal t met from two cells of the grid
+TANGENT_FLAGS = (S, S | P, S | P | L, S | O, S | P | L | O)
+_tangent = {}
+
+
+def tangent_expected(name):
+    """(rays, where the exact rays sit, {flags: (hits, blocked)}) of a variant of the tangent scene: the host definition, computed once"""
+    if name not in _tangent:
+        a, sc = api_mod(), cc.scene_of(name)
+        rays, where = cc.tangent_rays(name, seed=193)
+        want = {}
+        for flags in TANGENT_FLAGS:
+            hits = a.cast_rays_host(rays, flags, sc.spheres, sc.planes, sc.lights)
+            blocked = a.occluded_rays_host(rays, flags, sc.spheres, sc.planes, sc.lights)
+            hits.setflags(write=False)
+            blocked.setflags(write=False)
+            want[flags] = (hits, blocked)
+        _tangent[name] = (rays, where, want)
+    return _tangent[name]
+
+
+def assert_tangent_premise(name, grid):
+    """the pass took the grid, and on the grid of ITS pad the exact ray along x is in cells that list B alone before the cell that lists both.
+    The wrapper reports the pad the builder derived (scene_prep.c: wprep_grid_plan widens the one it is asked for), so the host builder is
+    asked for the pad the shim asks for -- the largest light radius of a paired walk, else none -- and must arrive at the reported one."""
+    assert grid and grid["built"], name
+    asked = float(np.abs(cc.scene_of(name).lights["radius"]).max()) if grid["pair"] else 0.0
+    cells, G = cc.tangent_cells(name, asked)
+    assert G["reg_pad"] == grid["reg_pad"] and (grid["reg_pad"] > 0) == bool(grid["pair"])
+    assert tuple(G["res"].tolist()) == grid["res"] and G["pairs"] == grid["pairs"], (G["res"], grid["res"], G["pairs"], grid["pairs"])
+    assert np.array_equal(bits(G["cell"]), bits(grid["cell"])) and np.array_equal(bits(G["gmin"]), bits(grid["gmin"]))
+    assert len(cells[0][0]) >= 2 and all(both for _, both in cells), (name, cells)
+
+
+@pytest.mark.parametrize("name", list(cc.TANGENT_VARIANTS))
+def test_an_equal_t_across_cells_keeps_the_lower_index(R, api, tex, sky, strict, name):
+    """wt_query_grid presents a cell's spheres in cell order and the cells in ray order, so the nearest sink meets the large sphere B, listed
+    in every cell, before the small sphere A at the same t: with A at the lower index the sink's rule for an equal t from a lower index
+    (wt_sink_nearest::grid_take) decides the id, with the indices swapped the rule must NOT fire.  The premise is asserted on the CPU
+    (test_cast_host.py: test_the_tangent_pair_ties_across_cells) and again here for the pad the wrapper reports."""
+    sc = cc.scene_of(name)
+    a, b = cc.tangent_ids(name)
+    rays, where, want = tangent_expected(name)
+    plain = want[S | P][0][where]
+    assert plain["id"][0::5].tolist() == [min(a, b)] * len(cc.TANGENT_EXACT) and plain["id"][1::5].tolist() == [b] * len(cc.TANGENT_EXACT)
+    bad = []
+    with rendering(R, sc, tex, sky, 8, 8, cam=None, strict=strict) as r:
+        for flags, (hits, blocked) in want.items():
+            got, got_blocked = r.w.cast_rays(rays, flags), r.w.occluded_rays(rays, flags)
+            d = (differing(got, hits), differing(got_blocked, blocked), differing(got[where], hits[where]))
+            print(f"{name} {'strict' if strict else 'fast'} flags {flags}: ids of the exact rays {got['id'][where].tolist()}")
+            if any(d):
+                bad.append((flags,) + d)
+        assert_tangent_premise(name, r.w.get_grid())
+    with rendering(R, sc, tex, sky, 8, 8, setup=lambda w: w.set_grid(0), cam=None, strict=strict) as r:      # ... and the linear scan agrees
+        for flags, (hits, blocked) in want.items():
+            if differing(r.w.cast_rays(rays, flags), hits) or differing(r.w.occluded_rays(rays, flags), blocked):
+                bad.append((flags, "linear"))
+    print(f"{name} {'strict' if strict else 'fast'}: {len(want)} flag sets x nearest and any, (flags, differing bytes: hits, blocked, hits of the exact rays) {bad}")
     assert not bad
 
 

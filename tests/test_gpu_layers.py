@@ -14,16 +14,17 @@ import layers_common as lc
 from conftest import CAM
 from render_common import R, api, bits, released, rendering  # noqa: F401  (R, api: the fixtures)
 from test_gpu_cast import FLAG_SETS as CAST_FLAG_SETS
-from test_gpu_cast import SIZES, UNIT_SCENES, WT_V_GEOM_GLOBAL, bare_scene_wrapper, read_framebuffer
+from test_gpu_cast import SIZES, WT_V_GEOM_GLOBAL, assert_tangent_premise, bare_scene_wrapper, read_framebuffer
+from test_gpu_cast import UNIT_SCENES as CAST_UNIT_SCENES
 
 pytestmark = pytest.mark.gpu
 
 S, P, L, O = cc.SPHERES, cc.PLANES, cc.LIGHTS, cc.OPAQUE
 K_EVERY_SIZE = (1, 4, 8)                 # the smaller kernel alone, full, the larger one full
 K_AT_193 = (2, 3, 5, 7)
-FLAG_SETS = dict(CAST_FLAG_SETS, stack=(S | P, S | P | L | O), **{name: (S | P, S | P | L | O) for name in lc.GRID_SCENES})
+FLAG_SETS = dict({name: sets for name, sets in CAST_FLAG_SETS.items() if name not in lc.GRID_SCENES}, stack=(S | P, S | P | L | O), **{name: (S | P, S | P | L | O) for name in lc.GRID_SCENES})
 # name -> (setup of the wrapper, the geometry the pass must take: "lds" | "global" | "grid")
-SCENES = dict(UNIT_SCENES)
+SCENES = {name: how for name, how in CAST_UNIT_SCENES.items() if name.split("-")[0] not in lc.GRID_SCENES}
 SCENES.update({"stack": (None, "lds"), "stack-global": (lambda w: w.set_variant(WT_V_GEOM_GLOBAL), "global")})
 for _name in lc.GRID_SCENES:             # each grid layout walked and scanned: grid == linear == the definition
     SCENES.update({_name + "-grid": (None, "grid"), _name + "-linear": (lambda w: w.set_grid(0), "global")})
@@ -106,6 +107,39 @@ def test_layers_equal_the_definition(R, api, tex, sky, strict, name):
         took = "grid" if grid and grid["built"] and "linear" not in name else ("lds" if len(sc.spheres) <= gridc.GRID_MIN_SPHERES and "global" not in name else "global")
         assert took == geometry
     print(f"{name} {'strict' if strict else 'fast'}: {len(expected(name))} cases, differing words {sum(b[3] for b in bad)} {bad[:8]}")
+    assert not bad
+
+
+# ------------------------------------------------------------------ 1b. an equal t met from two cells of the grid
+TANGENT_FLAGS = (S, S | P | L, S | P | L | O)
+TANGENT_K = (1, 2, 8)
+
+
+@pytest.mark.parametrize("name", list(cc.TANGENT_VARIANTS))
+def test_an_equal_t_across_cells_is_listed_in_id_order(R, api, tex, sky, strict, monkeypatch, name):
+    """test_gpu_cast.py's tangent pair under the list sink: the walk holds the large sphere B from the cells that list it alone when it meets
+    the small sphere A at the same t.  At K = 1 the list's worst entry is B itself and A, the lower index, must replace it (the rule
+    `t == worst_t && !(i < worst_i)` of wt_layers_insert); at K = 2 both are listed, lower index first; both compiled capacities."""
+    sc = cc.scene_of(name)
+    a, b = cc.tangent_ids(name)
+    rays, where = cc.tangent_rays(name, seed=193)
+    bad = []
+    with rendering(R, sc, tex, sky, 8, 8, cam=None, strict=strict) as r:
+        for capacity in (None, "8"):
+            if capacity:
+                monkeypatch.setenv("CLWRAP_LAYERS_CAPACITY", capacity)      # (read on every call)
+            for flags in TANGENT_FLAGS:
+                for K in TANGENT_K:
+                    want = api.cast_layers_host(rays, flags, K, sc.spheres, sc.planes, sc.lights)
+                    if not flags & O:
+                        assert want["id"][0][where[0::5]].tolist() == [min(a, b)] * len(cc.TANGENT_EXACT)
+                        assert K < 2 or want["id"][1][where[0::5]].tolist() == [max(a, b)] * len(cc.TANGENT_EXACT)
+                    got = r.w.cast_layers(rays, flags, K)
+                    d = differing(got, want)
+                    if d:
+                        bad.append((capacity, flags, K, d, got["id"][:, where[0::5]].tolist()))
+        assert_tangent_premise(name, r.w.get_grid())
+    print(f"{name} {'strict' if strict else 'fast'}: capacities 4 / 8 and 8 x {len(TANGENT_FLAGS)} flag sets x K {TANGENT_K}; (capacity, flags, K, differing words, ids of the exact rays) {bad}")
     assert not bad
 
 

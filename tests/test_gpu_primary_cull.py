@@ -1,17 +1,21 @@
 """The primary-ray cull table on the GPU (include/hip_wrap_ext.h: clw_host_primary_cull, clw_ext_read_primary_cull; csrc/whitted_cull.inc builds it,
 csrc/whitted_hit.inc reads it): a tile whose primary rays all fail the line test of every sphere / every light skips that group of tests in its
 first loop iteration.  Skipping a test that fails in every lane may not change a bit, so every frame here is compared with the frame of the same
-renderer under variant 32768 (no table), packed and float, fast and strict build; the device table is held to the host definition; and the
-launches that must not use a table are shown to run without one."""
+renderer under variant 32768 (no table), packed and float, fast and strict build (cull_common.on_and_off); the device table is held to the host
+definition; and the launches that must not use a table are shown to run without one.
+
+This module is about the table's life: when it is built, what it follows, which launches take none, strips and band shares.  Its views are
+render.map and one-sphere cuts of it, so of the 22 twin kernels `wt_trace_cull<FLAGS>` it launches five: the shaped twins of (4 spheres, 2 planes)
+and (1, 2), the strict LDS twin (flag word 4) and the two counting twins (word 5 of either build).  tests/test_gpu_cull_twins.py runs all 22."""
 import numpy as np
 import pytest
 
 from conftest import CAM
-from render_common import R, api, assert_same_frames, released, rendering, take  # noqa: F401
+from cull_common import NO_CULL, no_table, on_and_off
+from render_common import R, api, released, rendering, take  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-NO_CULL = 32768
 SIZES = [(64, 40), (72, 44)]      # the second has tiles cut by the right and the bottom edge
 
 
@@ -41,31 +45,6 @@ def scenes(api, demo_scene, W, H):
         "inside glass": (one_sphere(demo_scene, (0.8, 2.3, -7.6), 1.5, scene.glass()), CAM),
         "light in view": (demo_scene, dict(origin=(2.0, 1.5, -2.5), look=(0.0, 0.0, 1.0), fov=60.0, focal=1.0)),
     }
-
-
-def no_table(w, builds):
-    """the last whole-range trace launch had no table, and the builder has run `builds` times"""
-    table, n = w.read_primary_cull()
-    return table is None and n == builds
-
-
-def on_and_off(r, what, expect_table=True):
-    """the first frame of a view (no table yet: a view is built for when it comes twice in a row), a frame with the table, a frame without it
-    (variant 32768), a frame with it again: all the same bits -> (frame, table)"""
-    first = r.render().copy()      # (one trace launch; a frame of `take` is two: the float output is read behind a launch of its own)
-    assert no_table(r.w, 0), what
-    on = take(r, 1)[0]
-    table, _ = r.w.read_primary_cull()
-    assert (table is not None) == expect_table, what
-    r.w.set_variant(NO_CULL)
-    off = take(r, 1)[0]
-    assert r.w.read_primary_cull()[0] is None, what
-    r.w.set_variant(0)
-    again = take(r, 1)[0]
-    assert r.w.read_primary_cull()[1] == (1 if expect_table else 0), what      # the table built once serves the view again
-    assert np.array_equal(first, off[0]), what
-    assert_same_frames([on, again], off[0], off[1], what)
-    return off, table
 
 
 @pytest.mark.parametrize("strict", [False, True], ids=["fast", "strict"])

@@ -18,89 +18,10 @@ import numpy as np
 import pytest
 
 from conftest import CAM
-from oracle.oracle_py import Camera
+from cull_common import check_case, disc32, disc64_rel, launch_rays, oracle_camera, shares, tile_any, tile_max  # noqa: F401
 from example_gui_opencl_raytracer_amd import api, scene
 
 F = np.float32
-
-
-def oracle_camera(cam):
-    return Camera.from_buffer_copy(bytes(cam))
-
-
-def disc32(o, d, c, r):
-    """D of the oracle's intersect_sphere (oracle/whitted_oracle.c; primitives.cl:170-195), float32 operation by operation; d: [n, 3]"""
-    dot = lambda a, b: a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1] + a[..., 2] * b[..., 2]
-    v = (o - c).astype(F)
-    a = dot(d, d)
-    b = dot(v * F(2), d)
-    cc = dot(v, v) - r * r
-    return b * b - F(4) * a * cc
-
-
-def disc64_rel(o, d, c, r):
-    """D / 4 over |c - o|^2 for the float32 directions taken as exact, in float64 and with a = 1: sin^2 alpha - sin^2 phi of the header"""
-    o, d, c, r = (np.asarray(x, np.float64) for x in (o, d, c, r))
-    v = o - c
-    L2 = (v * v).sum()
-    if not L2 > 0:      # the origin is the centre: every line passes
-        return np.full(d.shape[0], np.inf)
-    d = d / np.sqrt((d * d).sum(-1, keepdims=True))
-    b = (d * v).sum(-1)
-    return (b * b - (L2 - r * r)) / L2
-
-
-def tile_any(flag, W, rows):
-    """per-pixel flags [rows * W] -> [tile rows, tiles per row]: any pixel of the tile"""
-    trows, tpr = (rows + 7) // 8, (W + 7) // 8
-    pad = np.zeros((trows * 8, tpr * 8), bool)
-    pad[:rows, :W] = flag.reshape(rows, W)
-    return pad.reshape(trows, 8, tpr, 8).any(axis=(1, 3))
-
-
-def tile_max(val, W, rows):
-    trows, tpr = (rows + 7) // 8, (W + 7) // 8
-    pad = np.full((trows * 8, tpr * 8), -np.inf)
-    pad[:rows, :W] = val.reshape(rows, W)
-    return pad.reshape(trows, 8, tpr, 8).max(axis=(1, 3))
-
-
-def launch_rays(oracle, cam, rows, row_offset, bands):
-    """origins and directions of the launch's pixels in local row order, as the trace kernel maps them"""
-    W = int(cam.width)
-    rays = oracle.raygen(oracle_camera(cam))
-    if bands:
-        stride, phase = bands
-        y = np.arange(rows)
-        gy = ((y >> 3) * stride + phase) * 8 + (y & 7)
-    else:
-        gy = row_offset + np.arange(rows)
-    ids = (gy[:, None] * W + np.arange(W)[None, :]).reshape(-1)
-    return rays[ids, 0:3], rays[ids, 4:7]
-
-
-def check_case(oracle, cam, sc, rows=None, row_offset=0, bands=None):
-    """-> (table, per-tile 'some pixel passes the line test' for spheres and lights); asserts soundness and the margin"""
-    rows = int(cam.height) if rows is None else rows
-    W = int(cam.width)
-    table = api.host_primary_cull(cam, sc.spheres, sc.lights, rows=rows, row_offset=row_offset, band_stride=bands[0] if bands else 1,
-                                  band_phase=bands[1] if bands else 0)
-    o, d = launch_rays(oracle, cam, rows, row_offset, bands)
-    out = []
-    for bit, prims in ((api.CULL_SPHERES, sc.spheres), (api.CULL_LIGHTS, sc.lights)):
-        passes = np.zeros((table.shape[0], table.shape[1]), bool)
-        worst = np.full(table.shape, -np.inf)
-        for p in prims:
-            c, r = p["origin"].astype(F), F(p["radius"])
-            D = disc32(o[0], d, c, r)
-            passes |= tile_any(~(D < 0), W, rows)
-            worst = np.maximum(worst, tile_max(disc64_rel(o[0], d, c, r), W, rows))
-        set_ = (table & bit) != 0
-        assert not (set_ & passes).any(), ("a set bit over a tile with D >= 0", bit, np.argwhere(set_ & passes)[:4])
-        if len(prims):
-            assert (worst[set_] <= -4e-6).all(), ("margin", bit, worst[set_].max())
-        out.append(passes)
-    return table, out[0], out[1]
 
 
 def rand_scene(rng, o, look, ns, behind=False):
@@ -126,13 +47,6 @@ def rand_camera(rng, W, H):
     look = rng.normal(size=3)
     look[1] *= 0.3      # (the reference rejects a view straight up)
     return o, look, api.perspective(tuple(o), tuple(look), float(rng.choice([40.0, 60.0, 90.0, 110.0])), 1.0, W, H)
-
-
-def shares(name, tables):
-    t = np.concatenate([x.reshape(-1) for x in tables])
-    s0, s1 = float(((t & 1) != 0).mean()), float(((t & 2) != 0).mean())
-    print(f"{name}: {t.size} tiles, bit 0 (spheres) set in {100 * s0:.1f} %, bit 1 (lights) set in {100 * s1:.1f} %")
-    return s0, s1
 
 
 FRAMES = [(64, 40), (72, 44), (37, 29), (50, 23)]      # width x height; the last three have tiles cut by the frame edge
