@@ -26,39 +26,6 @@ CL_MEM_WRITE_ONLY = 1 << 1
 CL_MEM_READ_ONLY = 1 << 2
 CL_MEM_COPY_HOST_PTR = 1 << 5
 
-# every symbol include/*.h declares (checked by the CPU test-suite)
-SYMBOLS = [
-    "cl_wrap_init", "cl_wrap_load_global_data", "cl_wrap_load_single_data", "cl_wrap_load_images",
-    "cl_wrap_output", "cl_wrap_release",
-    "clw_ext_set_depth", "clw_ext_get_depth", "clw_ext_set_strict", "clw_ext_set_fuse",
-    "clw_ext_set_id_offset", "clw_ext_set_row_bands", "clw_ext_set_async", "clw_ext_sync", "clw_ext_set_stream",
-    "clw_ext_timing_reset", "clw_ext_timing_get", "clw_ext_set_timing_every", "clw_ext_set_pipeline", "clw_ext_load_images_raw",
-    "clw_ext_bind_device_buffer", "clw_ext_device_ptr", "clw_ext_set_debug_rgb",
-    "clw_ext_enable_counters", "clw_ext_read_counters", "clw_ext_set_tile_sched", "clw_ext_read_tile_costs", "clw_ext_unit", "clw_ext_set_grid", "clw_ext_set_variant",
-    "clw_ext_last_trace_flags", "clw_ext_set_shadow_through", "clw_ext_set_tpt", "clw_ext_invalidate_scene", "clw_ext_read_counters_ex", "clw_ext_unit_scene",
-    "clw_host_perspective", "clw_host_write_png", "clw_host_write_png_rgba", "clw_host_read_png",
-    "clw_host_free", "clw_ext_version",
-    "clw_ext_set_supersample", "clw_ext_get_supersample",
-    "clw_ext_set_sample_cameras", "clw_ext_get_sample_cameras", "clw_ext_set_lens", "clw_host_lens_cameras", "clw_host_shutter_cameras",
-    "clw_ext_set_sphere_motion", "clw_ext_get_sample_times", "clw_host_sample_times", "clw_host_spheres_at",
-    "clw_ext_set_adaptive", "clw_ext_get_adaptive", "clw_ext_read_refine_mask", "clw_host_refine_mask",
-    "clw_ext_set_seed_offset", "clw_ext_get_seed_offset", "clw_ext_set_accumulate", "clw_ext_get_accumulated", "clw_ext_reset_accumulation",
-    "clw_host_frame_seed", "clw_host_jitter_camera",
-    "clw_ext_set_split", "clw_ext_get_split", "clw_ext_get_tpt", "clw_ext_read_tile_order", "clw_ext_unit_sched",
-    "clw_ext_render_gbuffer", "clw_ext_read_gbuffer", "clw_ext_gbuffer_device_ptr", "clw_ext_pick",
-    "clw_ext_get_grid", "clw_ext_set_grid_pair",
-    "clw_host_overlay", "clw_ext_render_overlay", "clw_ext_read_overlay", "clw_ext_overlay_device_ptr", "clw_ext_unit_overlay",
-    "clw_host_object_stats", "clw_host_merge_object_stats", "clw_ext_object_stats", "clw_ext_unit_object_stats",
-    "clw_host_projection_rays", "clw_host_projection_tables", "clw_host_ortho_camera",
-    "clw_ext_set_projection", "clw_ext_get_projection", "clw_ext_unit_projection",
-    "clw_host_ao_dirs", "clw_host_ao_open", "clw_host_ao_resolve", "clw_ext_render_ao", "clw_ext_read_ao", "clw_ext_ao_device_ptr",
-    "clw_ext_unit_ao_open", "clw_ext_unit_ao_resolve",
-    "clw_host_cast_rays", "clw_host_occluded_rays", "clw_ext_cast_rays", "clw_ext_occluded_rays", "clw_ext_cast_rays_device",
-    "clw_host_primary_cull", "clw_ext_read_primary_cull",
-    "clw_host_cast_layers", "clw_host_camera_rays", "clw_ext_cast_layers", "clw_ext_cast_layers_device", "clw_ext_camera_rays",
-    "clw_ext_camera_rays_device", "clw_ext_render_layers", "clw_ext_read_layers", "clw_ext_layers_device_ptr", "clw_ext_pick_layers",
-]
-
 # the channels of the primary-hit pass (hip_wrap_ext.h: CLW_GB_*), the id of a miss and the pass's id in the timing log
 GB_DEPTH, GB_ID, GB_NORMAL, GB_POINT, GB_ALBEDO, GB_ALL = 1, 2, 4, 8, 16, 31
 ID_NONE = 0xFFFFFFFF
@@ -71,9 +38,7 @@ GB_CHANNELS = {"depth": (GB_DEPTH, np.float32, 1), "id": (GB_ID, np.uint32, 1), 
 OV_OUTLINE, OV_FILL, OV_EDGES, OV_ALL = 1, 2, 4, 7
 TIMING_OVERLAY = 0x4F564C59
 
-# the visible-object table (hip_wrap_ext.h: clw_object_stat): a record as a numpy dtype, and the pass's id in the timing log
-OBJECT_STAT = np.dtype([("id", np.uint32), ("pixels", np.uint32), ("x0", np.uint32), ("y0", np.uint32), ("x1", np.uint32), ("y1", np.uint32),
-                        ("depth_min", np.float32), ("depth_max", np.float32), ("sum_x", np.uint64), ("sum_y", np.uint64)])
+# the visible-object table (hip_wrap_ext.h: clw_object_stat; OBJECT_STAT below is a record as a numpy dtype): the pass's id in the timing log
 TIMING_OBJECTS = 0x4F424A53
 
 # the camera models (hip_wrap_ext.h: CLW_PROJ_*)
@@ -86,17 +51,14 @@ AO_FRAME, AO_COUNTS = 0, 1
 TIMING_AO = 0x414F5452
 TIMING_AO_RESOLVE = 0x414F5253
 
-# ray queries (hip_wrap_ext.h: clw_ray, clw_hit, CLW_CAST_*): a ray and a hit as numpy dtypes (32 bytes each), the kinds a query tests, and
-# the kernel's id in the timing log
-RAY_QUERY = np.dtype([("origin", np.float32, 3), ("tmax", np.float32), ("dir", np.float32, 3), ("ignore", np.uint32)])
-HIT = np.dtype([("t", np.float32), ("id", np.uint32), ("normal", np.float32, 3), ("point", np.float32, 3)])
+# ray queries (hip_wrap_ext.h: clw_ray, clw_hit, CLW_CAST_*; RAY_QUERY and HIT below are a ray and a hit as numpy dtypes): the kinds a query
+# tests, and the kernel's id in the timing log
 CAST_SPHERES, CAST_PLANES, CAST_LIGHTS, CAST_KINDS, CAST_OPAQUE = 1, 2, 4, 7, 8
 CAST_KIND_NAMES = {"sphere": CAST_SPHERES, "plane": CAST_PLANES, "light": CAST_LIGHTS}
 TIMING_CAST = 0x43415354
 
-# layered ray queries (hip_wrap_ext.h: clw_layer, clw_host_cast_layers): one entry of a ray's list as a numpy dtype (8 bytes), the largest K,
-# what clw_ext_read_layers reads, and the two kernels' ids in the timing log
-LAYER = np.dtype([("t", np.float32), ("id", np.uint32)])
+# layered ray queries (hip_wrap_ext.h: clw_layer, clw_host_cast_layers; LAYER below is one entry of a ray's list as a numpy dtype): the
+# largest K, what clw_ext_read_layers reads, and the two kernels' ids in the timing log
 LAYERS_MAX = 8
 LAYERS_T, LAYERS_ID = 0, 1
 TIMING_LAYERS = 0x4C415952
@@ -116,6 +78,12 @@ def id_index(ids):
 def make_id(kind, index):
     """kind << 30 | index, as the id channel stores it."""
     return (np.asarray(kind, np.uint32) << np.uint32(30)) | np.asarray(index, np.uint32)
+
+
+def id_entry(word, **more) -> dict:
+    """{"id", "kind", "index"} of one id word as Python ints, then `more`: what ``Renderer.pick`` and ``pick_through`` answer per object."""
+    word = int(word)
+    return dict(id=word, kind=word >> 30, index=word & 0x3FFFFFFF, **more)
 
 
 def library_version() -> str:
@@ -210,220 +178,166 @@ class clw_grid_info(C.Structure):
                 ("cell", C.c_float * 3), ("gmin", C.c_float * 3), ("reg_pad", C.c_float)]
 
 
+# the records that travel in arrays, as numpy dtypes: derived from their Structure, so each layout is written once (32, 32, 8 and 48 bytes)
+RAY_QUERY, HIT, LAYER, OBJECT_STAT = np.dtype(clw_ray), np.dtype(clw_hit), np.dtype(clw_layer), np.dtype(clw_object_stat)
+
+_int, _u32, _u64, _sz, _f32, _vp, _str = C.c_int, C.c_uint32, C.c_uint64, C.c_size_t, C.c_float, C.c_void_p, C.c_char_p
+_f3, _pu32 = C.c_float * 3, C.POINTER(C.c_uint32)
+_W, _CAM, _PROJ, _OV, _AO = C.POINTER(cl_wrap), C.POINTER(clw_camera), C.POINTER(clw_projection), C.POINTER(clw_overlay), C.POINTER(clw_ao)
+_RECT, _SUM = C.POINTER(clw_rect), C.POINTER(clw_object_summary)
+
+# THE prototype table: every function include/opencl_wrap.h and include/hip_wrap_ext.h declare, name -> (return type, argument types), in the
+# headers' order.  None as the return type is `void`; None as the argument types is a variadic function, whose callers convert each argument
+# themselves.  tests/test_api_prototypes_host.py holds every line to its header prototype.  A new entry point is its header prototype, one
+# line here and its method below.
+PROTOTYPES = {
+    "cl_wrap_init": (None, None),
+    "cl_wrap_load_global_data": (None, [_W, _u32, _u32, _vp, _sz, _u64]),
+    "cl_wrap_load_single_data": (None, [_W, _u32, _u32, _vp, _sz]),
+    "cl_wrap_load_images": (None, None),
+    "cl_wrap_output": (None, [_W, _sz, _sz, _u32, _u32, C.c_int32, _vp]),
+    "cl_wrap_release": (None, [_W]),
+    "clw_ext_set_depth": (None, [_W, _int]),
+    "clw_ext_get_depth": (_int, [_W]),
+    "clw_ext_set_strict": (None, [_W, _int]),
+    "clw_ext_set_fuse": (None, [_W, _int]),
+    "clw_ext_set_id_offset": (None, [_W, _u64]),
+    "clw_ext_set_row_bands": (None, [_W, _u32, _u32]),
+    "clw_ext_set_async": (None, [_W, _int]),
+    "clw_ext_sync": (None, [_W]),
+    "clw_ext_set_stream": (None, [_W, _vp]),
+    "clw_ext_timing_reset": (None, [_W]),
+    "clw_ext_timing_get": (None, [_W, _u32, _pu32, C.POINTER(C.c_double)]),
+    "clw_ext_set_pipeline": (None, [_W, _int]),
+    "clw_ext_set_timing_every": (None, [_W, _u32]),
+    "clw_ext_load_images_raw": (None, [_W, _u32, _u32, _vp, _u32, _u32, _u32]),
+    "clw_ext_bind_device_buffer": (None, [_W, _u32, _u32, _vp, _sz]),
+    "clw_ext_invalidate_scene": (None, [_W]),
+    "clw_ext_device_ptr": (_vp, [_W, _u32, _u32]),
+    "clw_ext_set_debug_rgb": (None, [_W, _vp]),
+    "clw_ext_set_supersample": (None, [_W, _int]),
+    "clw_ext_get_supersample": (_int, [_W]),
+    "clw_ext_set_sample_cameras": (None, [_W, _vp, _u32]),
+    "clw_ext_get_sample_cameras": (_u32, [_W, _vp, _u32]),
+    "clw_ext_set_lens": (None, [_W, _f32, _f32]),
+    "clw_ext_set_sphere_motion": (None, [_W, _vp, _u32, _vp, _u32]),
+    "clw_ext_get_sample_times": (_u32, [_W, _vp, _u32]),
+    "clw_ext_set_adaptive": (None, [_W, _int]),
+    "clw_ext_get_adaptive": (_int, [_W]),
+    "clw_ext_read_refine_mask": (_u32, [_W, _vp, _u32]),
+    "clw_ext_set_seed_offset": (None, [_W, _u32]),
+    "clw_ext_get_seed_offset": (_u32, [_W]),
+    "clw_ext_set_accumulate": (None, [_W, _int, _int]),
+    "clw_ext_get_accumulated": (_u32, [_W]),
+    "clw_ext_reset_accumulation": (None, [_W]),
+    "clw_ext_render_gbuffer": (_u32, [_W, _u32]),
+    "clw_ext_read_gbuffer": (_u32, [_W, _u32, _vp, _u32]),
+    "clw_ext_gbuffer_device_ptr": (_vp, [_W, _u32]),
+    "clw_ext_pick": (_int, [_W, _u32, _u32, C.POINTER(clw_pick)]),
+    "clw_host_overlay": (_int, [_vp, _vp, _u32, _u32, _OV, _vp, _u32, _vp]),
+    "clw_ext_render_overlay": (_u32, [_W, _OV, _vp, _u32]),
+    "clw_ext_read_overlay": (_u32, [_W, _vp, _u32]),
+    "clw_ext_overlay_device_ptr": (_vp, [_W]),
+    "clw_ext_unit_overlay": (_u32, [_W, _vp, _vp, _u32, _u32, _OV, _vp, _u32, _vp]),
+    "clw_host_object_stats": (_int, [_vp, _vp, _u32, _u32, _u32, _RECT, _vp, _vp, _u32, _SUM]),
+    "clw_host_merge_object_stats": (_u32, [_vp, _u32, _vp, _u32, _vp, _u32]),
+    "clw_ext_object_stats": (_int, [_W, _RECT, _vp, _u32, _SUM]),
+    "clw_ext_unit_object_stats": (_int, [_W, _vp, _vp, _u32, _u32, _u32, _RECT, _vp, _vp, _u32, _SUM]),
+    "clw_host_projection_rays": (_int, [_CAM, _PROJ, _u64, _u64, _vp]),
+    "clw_host_projection_tables": (_int, [_CAM, _PROJ, _vp, _vp]),
+    "clw_host_ortho_camera": (_int, [_f3, _f3, _f32, _u32, _u32, _CAM, _PROJ]),
+    "clw_ext_set_projection": (None, [_W, _PROJ]),
+    "clw_ext_get_projection": (None, [_W, _PROJ]),
+    "clw_ext_unit_projection": (_int, [_W, _CAM, _PROJ, _u64, _u64, _vp]),
+    "clw_host_ao_dirs": (_int, [_u32, _vp]),
+    "clw_host_ao_open": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _AO, _vp, _vp]),
+    "clw_host_ao_resolve": (_int, [_vp, _vp, _vp, _u32, _u32, _AO, _vp]),
+    "clw_ext_render_ao": (_u32, [_W, _AO]),
+    "clw_ext_read_ao": (_u32, [_W, _u32, _vp, _u32]),
+    "clw_ext_ao_device_ptr": (_vp, [_W, _u32]),
+    "clw_ext_unit_ao_open": (_u32, [_W, _vp, _vp, _vp, _u32, _u32, _u32, _AO, _vp]),
+    "clw_ext_unit_ao_resolve": (_u32, [_W, _vp, _vp, _vp, _u32, _u32, _AO, _vp]),
+    "clw_host_cast_rays": (_int, [_vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "clw_host_occluded_rays": (_int, [_vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "clw_ext_cast_rays": (_u32, [_W, _vp, _u32, _u32, _vp]),
+    "clw_ext_occluded_rays": (_u32, [_W, _vp, _u32, _u32, _vp]),
+    "clw_ext_cast_rays_device": (_u32, [_W, _vp, _u32, _u32, _vp, _vp]),
+    "clw_host_cast_layers": (_int, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
+    "clw_host_camera_rays": (_int, [_CAM, _PROJ, _u64, _u64, _vp]),
+    "clw_ext_cast_layers": (_u32, [_W, _vp, _u32, _u32, _u32, _vp, _vp]),
+    "clw_ext_cast_layers_device": (_u32, [_W, _vp, _u32, _u32, _u32, _vp, _vp]),
+    "clw_ext_camera_rays": (_u32, [_W, _vp, _u32]),
+    "clw_ext_camera_rays_device": (_u32, [_W, _vp, _u32]),
+    "clw_ext_render_layers": (_u32, [_W, _u32, _u32]),
+    "clw_ext_read_layers": (_u32, [_W, _u32, _vp, _u32]),
+    "clw_ext_layers_device_ptr": (_vp, [_W, _u32]),
+    "clw_ext_pick_layers": (_int, [_W, _u32, _u32, _u32, _u32, _vp]),
+    "clw_ext_enable_counters": (None, [_W, _int]),
+    "clw_ext_read_counters": (None, [_W, C.POINTER(_u64 * 8)]),
+    "clw_ext_read_counters_ex": (None, [_W, C.POINTER(_u64 * 32), _u32]),
+    "clw_ext_set_shadow_through": (None, [_W, _f32]),
+    "clw_ext_set_grid": (None, [_W, _int]),
+    "clw_ext_get_grid": (_int, [_W, C.POINTER(clw_grid_info)]),
+    "clw_ext_set_grid_pair": (None, [_W, _int]),
+    "clw_ext_set_tile_sched": (None, [_W, _int]),
+    "clw_ext_read_tile_costs": (_u32, [_W, _vp, _u32]),
+    "clw_ext_unit": (None, [_W, _int, _vp, _u32, _vp, _u32, _u32, _u32]),
+    "clw_ext_unit_sched": (_u32, [_W, _vp, _u32, _u32, _int, _u32, _u32, _u32, _u32, _vp, _u32]),
+    "clw_ext_read_tile_order": (_u32, [_W, _vp, _u32, _pu32]),
+    "clw_ext_set_split": (None, [_W, _int, _int]),
+    "clw_ext_get_split": (None, [_W, _pu32, _pu32, _pu32]),
+    "clw_ext_unit_scene": (None, [_W, _u32, _int, _vp, _u32, _vp, _u32, _u32]),
+    "clw_ext_set_variant": (None, [_W, _int]),
+    "clw_ext_last_trace_flags": (_int, [_W]),
+    "clw_host_primary_cull": (_u32, [_CAM, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "clw_ext_read_primary_cull": (_u32, [_W, _vp, _u32, C.POINTER(_u64)]),
+    "clw_ext_set_tpt": (None, [_W, _int, _int, _int]),
+    "clw_ext_get_tpt": (None, [_W, _pu32, _pu32, _pu32]),
+    "clw_host_perspective": (_int, [_f3, _f3, _f32, _f32, _u32, _u32, _CAM]),
+    "clw_host_lens_cameras": (_int, [_CAM, _f32, _f32, _u32, _vp]),
+    "clw_host_shutter_cameras": (_int, [_CAM, _CAM, _u32, _vp]),
+    "clw_host_sample_times": (_int, [_u32, _vp]),
+    "clw_host_spheres_at": (_int, [_vp, _u32, _vp, _f32, _vp]),
+    "clw_host_frame_seed": (_u32, [_u32]),
+    "clw_host_jitter_camera": (_int, [_CAM, _u32, _u32, _CAM]),
+    "clw_host_refine_mask": (_int, [_vp, _u32, _u32, _u32, _int, _vp]),
+    "clw_host_write_png": (_int, [_str, _vp, _u32, _u32]),
+    "clw_host_write_png_rgba": (_int, [_str, _vp, _u32, _u32]),
+    "clw_host_read_png": (_int, [_str, _pu32, _pu32, C.POINTER(_vp)]),
+    "clw_host_free": (None, [_vp]),
+    "clw_ext_version": (_str, []),
+}
+SYMBOLS = list(PROTOTYPES)
+
+
+def bind_prototypes(L, may_be_missing: bool, table=PROTOTYPES):
+    """Give every function of `table` its types on the loaded library `L`.  A symbol `L` lacks ends the binding with the AttributeError ctypes
+    raises, which names it -- unless `may_be_missing` (an A/B build of another commit): then it is skipped and stays unbound, so
+    `hasattr(L, name)` still tells whether the library has it."""
+    for name, (restype, argtypes) in table.items():
+        if may_be_missing and not hasattr(L, name):
+            continue
+        f = getattr(L, name)
+        f.restype = restype
+        if argtypes is not None:
+            f.argtypes = argtypes
+    return L
+
+
 _lib = None
 
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
-    """Load the HIP shim.  Fails loudly if it has not been built."""
+    """Load the HIP shim.  Fails loudly if it has not been built, and -- unless CLWRAP_LIB names the library, for an A/B run against a build of
+    another commit -- if it lacks a symbol of the table."""
     global _lib
     if _lib is not None:
         return _lib
     if not os.path.exists(path):
         raise ImportError(f"{path} is missing: run `python -m example_gui_opencl_raytracer_amd.build` "
                           "(there is no CPU fallback for the trace path)")
-    L = C.CDLL(path)
-    vp, u32, sz = C.c_void_p, C.c_uint32, C.c_size_t
-    W = C.POINTER(cl_wrap)
-    L.cl_wrap_load_global_data.argtypes = [W, u32, u32, vp, sz, C.c_uint64]
-    L.cl_wrap_load_single_data.argtypes = [W, u32, u32, vp, sz]
-    L.cl_wrap_output.argtypes = [W, sz, sz, u32, u32, C.c_int32, vp]
-    L.cl_wrap_release.argtypes = [W]
-    L.clw_ext_set_depth.argtypes = [W, C.c_int]
-    L.clw_ext_get_depth.argtypes = [W]
-    L.clw_ext_get_depth.restype = C.c_int
-    for name in ("clw_ext_set_strict", "clw_ext_set_fuse", "clw_ext_set_async", "clw_ext_enable_counters",
-                 "clw_ext_set_variant", "clw_ext_set_tile_sched", "clw_ext_set_grid"):
-        getattr(L, name).argtypes = [W, C.c_int]
-    L.clw_ext_set_shadow_through.argtypes = [W, C.c_float]
-    if hasattr(L, "clw_ext_last_trace_flags") or not os.environ.get("CLWRAP_LIB"):   # (an older A/B build may lack it)
-        L.clw_ext_last_trace_flags.argtypes = [W]
-        L.clw_ext_last_trace_flags.restype = C.c_int
-    if hasattr(L, "clw_ext_set_tpt") or not os.environ.get("CLWRAP_LIB"):      # (an older A/B build may lack it)
-        L.clw_ext_set_tpt.argtypes = [W, C.c_int, C.c_int, C.c_int]
-    L.clw_ext_set_id_offset.argtypes = [W, C.c_uint64]
-    L.clw_ext_set_row_bands.argtypes = [W, u32, u32]
-    L.clw_ext_sync.argtypes = [W]
-    L.clw_ext_set_stream.argtypes = [W, vp]
-    L.clw_ext_timing_reset.argtypes = [W]
-    L.clw_ext_set_timing_every.argtypes = [W, u32]
-    L.clw_ext_set_pipeline.argtypes = [W, C.c_int]
-    L.clw_ext_timing_get.argtypes = [W, u32, C.POINTER(u32), C.POINTER(C.c_double)]
-    L.clw_ext_load_images_raw.argtypes = [W, u32, u32, vp, u32, u32, u32]
-    L.clw_ext_bind_device_buffer.argtypes = [W, u32, u32, vp, sz]
-    L.clw_ext_device_ptr.argtypes = [W, u32, u32]
-    L.clw_ext_device_ptr.restype = vp
-    L.clw_ext_set_debug_rgb.argtypes = [W, vp]
-    if hasattr(L, "clw_ext_set_supersample") or not os.environ.get("CLWRAP_LIB"):      # (an older A/B build may lack it)
-        L.clw_ext_set_supersample.argtypes = [W, C.c_int]
-        L.clw_ext_get_supersample.argtypes = [W]
-        L.clw_ext_get_supersample.restype = C.c_int
-    if hasattr(L, "clw_ext_set_sample_cameras") or not os.environ.get("CLWRAP_LIB"):      # (an older A/B build may lack them)
-        L.clw_ext_set_sample_cameras.argtypes = [W, vp, u32]
-        L.clw_ext_get_sample_cameras.argtypes = [W, vp, u32]
-        L.clw_ext_get_sample_cameras.restype = u32
-        L.clw_ext_set_lens.argtypes = [W, C.c_float, C.c_float]
-        L.clw_host_lens_cameras.argtypes = [C.POINTER(clw_camera), C.c_float, C.c_float, u32, vp]
-        L.clw_host_lens_cameras.restype = C.c_int
-        L.clw_host_shutter_cameras.argtypes = [C.POINTER(clw_camera), C.POINTER(clw_camera), u32, vp]
-        L.clw_host_shutter_cameras.restype = C.c_int
-    if hasattr(L, "clw_ext_set_sphere_motion") or not os.environ.get("CLWRAP_LIB"):       # (an older A/B build may lack them)
-        L.clw_ext_set_sphere_motion.argtypes = [W, vp, u32, vp, u32]
-        L.clw_ext_get_sample_times.argtypes = [W, vp, u32]
-        L.clw_ext_get_sample_times.restype = u32
-        L.clw_host_sample_times.argtypes = [u32, vp]
-        L.clw_host_sample_times.restype = C.c_int
-        L.clw_host_spheres_at.argtypes = [vp, u32, vp, C.c_float, vp]
-        L.clw_host_spheres_at.restype = C.c_int
-    if hasattr(L, "clw_ext_set_adaptive") or not os.environ.get("CLWRAP_LIB"):            # (an older A/B build may lack them)
-        L.clw_ext_set_adaptive.argtypes = [W, C.c_int]
-        L.clw_ext_get_adaptive.argtypes = [W]
-        L.clw_ext_get_adaptive.restype = C.c_int
-        L.clw_ext_read_refine_mask.argtypes = [W, vp, u32]
-        L.clw_ext_read_refine_mask.restype = u32
-        L.clw_host_refine_mask.argtypes = [vp, u32, u32, u32, C.c_int, vp]
-        L.clw_host_refine_mask.restype = C.c_int
-    if hasattr(L, "clw_ext_set_accumulate") or not os.environ.get("CLWRAP_LIB"):          # (an older A/B build may lack them)
-        L.clw_ext_set_seed_offset.argtypes = [W, u32]
-        L.clw_ext_get_seed_offset.argtypes = [W]
-        L.clw_ext_get_seed_offset.restype = u32
-        L.clw_ext_set_accumulate.argtypes = [W, C.c_int, C.c_int]
-        L.clw_ext_get_accumulated.argtypes = [W]
-        L.clw_ext_get_accumulated.restype = u32
-        L.clw_ext_reset_accumulation.argtypes = [W]
-        L.clw_host_frame_seed.argtypes = [u32]
-        L.clw_host_frame_seed.restype = u32
-        L.clw_host_jitter_camera.argtypes = [C.POINTER(clw_camera), u32, u32, C.POINTER(clw_camera)]
-        L.clw_host_jitter_camera.restype = C.c_int
-    if hasattr(L, "clw_ext_render_gbuffer") or not os.environ.get("CLWRAP_LIB"):          # (an older A/B build may lack them)
-        L.clw_ext_render_gbuffer.argtypes = [W, u32]
-        L.clw_ext_render_gbuffer.restype = u32
-        L.clw_ext_read_gbuffer.argtypes = [W, u32, vp, u32]
-        L.clw_ext_read_gbuffer.restype = u32
-        L.clw_ext_gbuffer_device_ptr.argtypes = [W, u32]
-        L.clw_ext_gbuffer_device_ptr.restype = vp
-        L.clw_ext_pick.argtypes = [W, u32, u32, C.POINTER(clw_pick)]
-        L.clw_ext_pick.restype = C.c_int
-    if hasattr(L, "clw_ext_get_grid") or not os.environ.get("CLWRAP_LIB"):                # (an older A/B build may lack them)
-        L.clw_ext_get_grid.argtypes = [W, C.POINTER(clw_grid_info)]
-        L.clw_ext_get_grid.restype = C.c_int
-        L.clw_ext_set_grid_pair.argtypes = [W, C.c_int]
-    if hasattr(L, "clw_ext_render_overlay") or not os.environ.get("CLWRAP_LIB"):          # (an older A/B build may lack them)
-        OV = C.POINTER(clw_overlay)
-        L.clw_host_overlay.argtypes = [vp, vp, u32, u32, OV, vp, u32, vp]
-        L.clw_host_overlay.restype = C.c_int
-        L.clw_ext_render_overlay.argtypes = [W, OV, vp, u32]
-        L.clw_ext_render_overlay.restype = u32
-        L.clw_ext_read_overlay.argtypes = [W, vp, u32]
-        L.clw_ext_read_overlay.restype = u32
-        L.clw_ext_overlay_device_ptr.argtypes = [W]
-        L.clw_ext_overlay_device_ptr.restype = vp
-        L.clw_ext_unit_overlay.argtypes = [W, vp, vp, u32, u32, OV, vp, u32, vp]
-        L.clw_ext_unit_overlay.restype = u32
-    if hasattr(L, "clw_ext_object_stats") or not os.environ.get("CLWRAP_LIB"):            # (an older A/B build may lack them)
-        RC, SM = C.POINTER(clw_rect), C.POINTER(clw_object_summary)
-        L.clw_host_object_stats.argtypes = [vp, vp, u32, u32, u32, RC, vp, vp, u32, SM]
-        L.clw_host_object_stats.restype = C.c_int
-        L.clw_host_merge_object_stats.argtypes = [vp, u32, vp, u32, vp, u32]
-        L.clw_host_merge_object_stats.restype = u32
-        L.clw_ext_object_stats.argtypes = [W, RC, vp, u32, SM]
-        L.clw_ext_object_stats.restype = C.c_int
-        L.clw_ext_unit_object_stats.argtypes = [W, vp, vp, u32, u32, u32, RC, vp, vp, u32, SM]
-        L.clw_ext_unit_object_stats.restype = C.c_int
-    if hasattr(L, "clw_ext_set_projection") or not os.environ.get("CLWRAP_LIB"):          # (an older A/B build may lack them)
-        CM, PR = C.POINTER(clw_camera), C.POINTER(clw_projection)
-        L.clw_host_projection_rays.argtypes = [CM, PR, C.c_uint64, C.c_uint64, vp]
-        L.clw_host_projection_rays.restype = C.c_int
-        L.clw_host_projection_tables.argtypes = [CM, PR, vp, vp]
-        L.clw_host_projection_tables.restype = C.c_int
-        L.clw_host_ortho_camera.argtypes = [C.c_float * 3, C.c_float * 3, C.c_float, u32, u32, CM, PR]
-        L.clw_host_ortho_camera.restype = C.c_int
-        L.clw_ext_set_projection.argtypes = [W, PR]
-        L.clw_ext_get_projection.argtypes = [W, PR]
-        L.clw_ext_unit_projection.argtypes = [W, CM, PR, C.c_uint64, C.c_uint64, vp]
-        L.clw_ext_unit_projection.restype = C.c_int
-    if hasattr(L, "clw_ext_render_ao") or not os.environ.get("CLWRAP_LIB"):               # (an older A/B build may lack them)
-        AO = C.POINTER(clw_ao)
-        L.clw_host_ao_dirs.argtypes = [u32, vp]
-        L.clw_host_ao_dirs.restype = C.c_int
-        L.clw_host_ao_open.argtypes = [vp, vp, vp, u32, u32, u32, vp, u32, vp, u32, AO, vp, vp]
-        L.clw_host_ao_open.restype = C.c_int
-        L.clw_host_ao_resolve.argtypes = [vp, vp, vp, u32, u32, AO, vp]
-        L.clw_host_ao_resolve.restype = C.c_int
-        L.clw_ext_render_ao.argtypes = [W, AO]
-        L.clw_ext_render_ao.restype = u32
-        L.clw_ext_read_ao.argtypes = [W, u32, vp, u32]
-        L.clw_ext_read_ao.restype = u32
-        L.clw_ext_ao_device_ptr.argtypes = [W, u32]
-        L.clw_ext_ao_device_ptr.restype = vp
-        L.clw_ext_unit_ao_open.argtypes = [W, vp, vp, vp, u32, u32, u32, AO, vp]
-        L.clw_ext_unit_ao_open.restype = u32
-        L.clw_ext_unit_ao_resolve.argtypes = [W, vp, vp, vp, u32, u32, AO, vp]
-        L.clw_ext_unit_ao_resolve.restype = u32
-    if hasattr(L, "clw_ext_cast_rays") or not os.environ.get("CLWRAP_LIB"):               # (an older A/B build may lack them)
-        L.clw_host_cast_rays.argtypes = [vp, u32, u32, vp, u32, vp, u32, vp, u32, vp]
-        L.clw_host_cast_rays.restype = C.c_int
-        L.clw_host_occluded_rays.argtypes = [vp, u32, u32, vp, u32, vp, u32, vp, u32, vp]
-        L.clw_host_occluded_rays.restype = C.c_int
-        L.clw_ext_cast_rays.argtypes = [W, vp, u32, u32, vp]
-        L.clw_ext_cast_rays.restype = u32
-        L.clw_ext_occluded_rays.argtypes = [W, vp, u32, u32, vp]
-        L.clw_ext_occluded_rays.restype = u32
-        L.clw_ext_cast_rays_device.argtypes = [W, vp, u32, u32, vp, vp]
-        L.clw_ext_cast_rays_device.restype = u32
-    if hasattr(L, "clw_ext_read_primary_cull") or not os.environ.get("CLWRAP_LIB"):       # (an older A/B build may lack them)
-        L.clw_host_primary_cull.argtypes = [C.POINTER(clw_camera), u32, u32, u32, u32, vp, u32, vp, u32, vp]
-        L.clw_host_primary_cull.restype = u32
-        L.clw_ext_read_primary_cull.argtypes = [W, vp, u32, C.POINTER(C.c_uint64)]
-        L.clw_ext_read_primary_cull.restype = u32
-    if hasattr(L, "clw_ext_cast_layers") or not os.environ.get("CLWRAP_LIB"):             # (an older A/B build may lack them)
-        L.clw_host_cast_layers.argtypes = [vp, u32, u32, u32, vp, u32, vp, u32, vp, u32, vp, vp]
-        L.clw_host_cast_layers.restype = C.c_int
-        L.clw_host_camera_rays.argtypes = [C.POINTER(clw_camera), C.POINTER(clw_projection), C.c_uint64, C.c_uint64, vp]
-        L.clw_host_camera_rays.restype = C.c_int
-        L.clw_ext_cast_layers.argtypes = [W, vp, u32, u32, u32, vp, vp]
-        L.clw_ext_cast_layers.restype = u32
-        L.clw_ext_cast_layers_device.argtypes = [W, vp, u32, u32, u32, vp, vp]
-        L.clw_ext_cast_layers_device.restype = u32
-        L.clw_ext_camera_rays.argtypes = [W, vp, u32]
-        L.clw_ext_camera_rays.restype = u32
-        L.clw_ext_camera_rays_device.argtypes = [W, vp, u32]
-        L.clw_ext_camera_rays_device.restype = u32
-        L.clw_ext_render_layers.argtypes = [W, u32, u32]
-        L.clw_ext_render_layers.restype = u32
-        L.clw_ext_read_layers.argtypes = [W, u32, vp, u32]
-        L.clw_ext_read_layers.restype = u32
-        L.clw_ext_layers_device_ptr.argtypes = [W, u32]
-        L.clw_ext_layers_device_ptr.restype = vp
-        L.clw_ext_pick_layers.argtypes = [W, u32, u32, u32, u32, vp]
-        L.clw_ext_pick_layers.restype = C.c_int
-    L.clw_ext_unit.argtypes = [W, C.c_int, vp, u32, vp, u32, u32, u32]
-    L.clw_ext_read_tile_costs.argtypes = [W, vp, u32]
-    L.clw_ext_read_tile_costs.restype = u32
-    L.clw_ext_set_split.argtypes = [W, C.c_int, C.c_int]
-    L.clw_ext_get_split.argtypes = [W, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
-    L.clw_ext_get_tpt.argtypes = [W, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
-    L.clw_ext_read_tile_order.argtypes = [W, vp, u32, C.POINTER(u32)]
-    L.clw_ext_read_tile_order.restype = u32
-    L.clw_ext_unit_sched.argtypes = [W, vp, u32, u32, C.c_int, u32, u32, u32, u32, vp, u32]
-    L.clw_ext_unit_sched.restype = u32
-    L.clw_ext_read_counters.argtypes = [W, C.POINTER(C.c_uint64 * 8)]
-    L.clw_ext_read_counters_ex.argtypes = [W, C.POINTER(C.c_uint64 * 32), u32]
-    L.clw_ext_invalidate_scene.argtypes = [W]
-    L.clw_ext_unit_scene.argtypes = [W, u32, C.c_int, vp, u32, vp, u32, u32]
-    L.clw_host_perspective.argtypes = [C.c_float * 3, C.c_float * 3, C.c_float, C.c_float, u32, u32,
-                                       C.POINTER(clw_camera)]
-    L.clw_host_perspective.restype = C.c_int
-    L.clw_host_write_png.argtypes = [C.c_char_p, vp, u32, u32]
-    L.clw_host_write_png.restype = C.c_int
-    L.clw_host_write_png_rgba.argtypes = [C.c_char_p, vp, u32, u32]
-    L.clw_host_write_png_rgba.restype = C.c_int
-    L.clw_host_read_png.argtypes = [C.c_char_p, C.POINTER(u32), C.POINTER(u32), C.POINTER(vp)]
-    L.clw_host_read_png.restype = C.c_int
-    L.clw_host_free.argtypes = [vp]
-    L.clw_ext_version.restype = C.c_char_p
-    _lib = L
-    return L
-
+    _lib = bind_prototypes(C.CDLL(path), may_be_missing=bool(os.environ.get("CLWRAP_LIB")))
+    return _lib
 
 def _ptr(a):
     if a is None:
@@ -431,6 +345,37 @@ def _ptr(a):
     if isinstance(a, np.ndarray):
         return a.ctypes.data_as(C.c_void_p)
     return C.cast(a, C.c_void_p)
+
+
+def _fits_u32(*values) -> bool:
+    """Whether every value can be passed as a uint32_t (ctypes would wrap a larger or a negative one silently)."""
+    return all(0 <= int(v) < 2 ** 32 for v in values)
+
+
+def _flat(a, dtype) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype).reshape(-1)
+
+
+def _frame_channels(width, rows, *channels, optional=()):
+    """The channels -- (array, dtype, entries per pixel) each -- of a width x rows frame -> (width, rows, [the arrays, contiguous and flat]), the
+    `optional` ones (None = left out, and stays None) after the others; None when there is no such frame or a channel has not its entries."""
+    width, rows = int(width), int(rows)
+    given = [(_flat(a, dtype), per) for a, dtype, per in channels] + [(a if a is None else _flat(a, dtype), per) for a, dtype, per in optional]
+    if width <= 0 or rows <= 0 or any(a is not None and a.size != per * width * rows for a, per in given):
+        return None
+    return width, rows, [a for a, _ in given]
+
+
+def _read_counted(read, dtype, unit: int | None = None) -> np.ndarray:
+    """Something the library holds, of a length only it knows: `read(out, capacity)` is asked for the count with no room at all, then again with
+    an array that holds it -> that array, flat; empty when the count is 0.  The count and the capacity are in units of `unit` bytes (None = in
+    entries of `dtype`)."""
+    itemsize = np.dtype(dtype).itemsize
+    n = int(read(None, 0))
+    out = np.zeros(n * (unit or itemsize) // itemsize, dtype)
+    if n:
+        assert read(_ptr(out), n) == n
+    return out
 
 
 def perspective(origin, look, fov, focal, width, height) -> clw_camera:
@@ -484,10 +429,10 @@ def spheres_at(spheres: np.ndarray, disp, t: float) -> np.ndarray:
 def refine_mask(xrgb, width: int, rows: int, n: int, threshold: int) -> np.ndarray:
     """clw_host_refine_mask: the blocks of b x b pixels (b = 8 / n) of a packed width x rows frame that adaptive supersampling refines at this
     contrast threshold -> uint8 [ceil(rows / b), ceil(width / b)] of 0 / 1."""
-    xrgb = np.ascontiguousarray(xrgb, np.uint32).reshape(-1)
-    width, rows, n = int(width), int(rows), int(n)
-    if n not in (2, 4, 8) or width <= 0 or rows <= 0 or xrgb.size != width * rows:
+    got, n = _frame_channels(width, rows, (xrgb, np.uint32, 1)), int(n)
+    if n not in (2, 4, 8) or got is None:
         raise ValueError("clw_host_refine_mask rejects these arguments (n in 2, 4, 8; a frame of width * rows pixels)")
+    width, rows, (xrgb,) = got
     b = 8 // n
     out = np.zeros((-(-rows // b), -(-width // b)), np.uint8)
     if not load_library().clw_host_refine_mask(_ptr(xrgb), width, rows, n, int(threshold), _ptr(out)):
@@ -501,17 +446,16 @@ def overlay_style(flags: int, radius: int = 2, outline: int = 0xFFFF00, fill: in
 
 
 def _selection(sel) -> np.ndarray:
-    return np.ascontiguousarray(np.atleast_1d(np.asarray(sel, np.uint32) if sel is not None else np.zeros(0, np.uint32)).reshape(-1))
+    return _flat(np.zeros(0, np.uint32) if sel is None else sel, np.uint32)
 
 
 def overlay(frame, ids, width: int, rows: int, style: clw_overlay, sel) -> np.ndarray:
     """clw_host_overlay: the selection overlay of a packed width x rows frame and its id channel, on the host -- THE definition the device pass is
     held to -> uint32 [width * rows].  `sel`: the selected ids (at most 64 words, or None)."""
-    frame = np.ascontiguousarray(frame, np.uint32).reshape(-1)
-    ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
-    width, rows = int(width), int(rows)
-    if width <= 0 or rows <= 0 or frame.size != width * rows or ids.size != width * rows:
+    got = _frame_channels(width, rows, (frame, np.uint32, 1), (ids, np.uint32, 1))
+    if got is None:
         raise ValueError("clw_host_overlay rejects these arguments (a frame and ids of width * rows words each)")
+    width, rows, (frame, ids) = got
     sel = _selection(sel)
     out = np.empty(width * rows, np.uint32)
     if not load_library().clw_host_overlay(_ptr(frame), _ptr(ids), width, rows, C.byref(style), _ptr(sel) if sel.size else None, sel.size, _ptr(out)):
@@ -527,7 +471,7 @@ def ao_params(rays: int = 8, radius: float = 1.0, strength: int = 256, filter: b
 def ao_dirs(rays: int) -> np.ndarray:
     """clw_host_ao_dirs: the direction table of K rays per pixel -> float32 [16, K, 4] (pattern, ray, {x, y, z, 0})."""
     out = np.empty((16, max(int(rays), 0), 4), np.float32)
-    if not 0 <= int(rays) < 2 ** 32 or not load_library().clw_host_ao_dirs(int(rays), _ptr(out)):
+    if not _fits_u32(rays) or not load_library().clw_host_ao_dirs(int(rays), _ptr(out)):
         raise ValueError("clw_host_ao_dirs rejects this number of rays (1..32)")
     return out
 
@@ -535,12 +479,10 @@ def ao_dirs(rays: int) -> np.ndarray:
 def ao_open(point, normal, ids, width: int, rows: int, first_row: int, spheres, planes, ao: clw_ao, dirs=None) -> np.ndarray:
     """clw_host_ao_open: the open rays of every pixel of a range of whole rows, on the host -- THE definition the device pass is held to ->
     uint8 [width * rows].  point, normal: float32 [n, 3]; ids: uint32 [n]; spheres, planes: the scene's record arrays (or None)."""
-    width, rows = int(width), int(rows)
-    point = np.ascontiguousarray(point, np.float32).reshape(-1)
-    normal = np.ascontiguousarray(normal, np.float32).reshape(-1)
-    ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
-    if width <= 0 or rows <= 0 or ids.size != width * rows or point.size != 3 * ids.size or normal.size != 3 * ids.size:
+    got = _frame_channels(width, rows, (point, np.float32, 3), (normal, np.float32, 3), (ids, np.uint32, 1))
+    if got is None:
         raise ValueError("clw_host_ao_open rejects these arguments (point and normal of 3, ids of 1 entry per pixel of width * rows)")
+    width, rows, (point, normal, ids) = got
     if dirs is None:
         dirs = ao_dirs(ao.rays)
     dirs = np.ascontiguousarray(dirs, np.float32)
@@ -556,13 +498,10 @@ def ao_open(point, normal, ids, width: int, rows: int, first_row: int, spheres, 
 def ao_resolve(open_u8, ids, frame, width: int, rows: int, ao: clw_ao) -> np.ndarray:
     """clw_host_ao_resolve: open-ray counts -> packed pixels, on the host -- THE definition the device pass is held to -> uint32 [width * rows].
     `frame` (read with AO_COMPOSE only) may be None without it."""
-    width, rows = int(width), int(rows)
-    open_u8 = np.ascontiguousarray(open_u8, np.uint8).reshape(-1)
-    ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
-    if frame is not None:
-        frame = np.ascontiguousarray(frame, np.uint32).reshape(-1)
-    if width <= 0 or rows <= 0 or open_u8.size != width * rows or ids.size != width * rows or (frame is not None and frame.size != width * rows):
+    got = _frame_channels(width, rows, (open_u8, np.uint8, 1), (ids, np.uint32, 1), optional=[(frame, np.uint32, 1)])
+    if got is None:
         raise ValueError("clw_host_ao_resolve rejects these arguments (counts, ids and frame of width * rows entries each)")
+    width, rows, (open_u8, ids, frame) = got
     out = np.empty(width * rows, np.uint32)
     if not load_library().clw_host_ao_resolve(_ptr(open_u8), _ptr(ids), _ptr(frame), width, rows, C.byref(ao), _ptr(out)):
         raise ValueError("clw_host_ao_resolve rejects these parameters (rays in 1..32, radius > 0, strength in 0..256, known flags, a frame with AO_COMPOSE)")
@@ -592,7 +531,7 @@ def make_rays(origins, dirs, tmax=np.inf, ignore=None) -> np.ndarray:
 
 
 def _cast_args(rays, spheres, planes, lights):
-    rays = np.ascontiguousarray(rays, RAY_QUERY).reshape(-1)
+    rays = _flat(rays, RAY_QUERY)
     arrs = [None if a is None else np.ascontiguousarray(a) for a in (spheres, planes, lights)]
     counts = [0 if a is None else int(a.shape[0]) for a in arrs]
     return rays, arrs, counts
@@ -602,7 +541,7 @@ def cast_rays_host(rays, flags: int, spheres, planes, lights=None) -> np.ndarray
     """clw_host_cast_rays: the nearest hit of every ray, on the host -- THE definition the device pass is held to -> HIT [n]."""
     rays, (s, p, l), (ns, np_, nl) = _cast_args(rays, spheres, planes, lights)
     out = np.empty(rays.size, HIT)
-    if not 0 <= int(flags) < 2 ** 32 or not load_library().clw_host_cast_rays(_ptr(rays), rays.size, int(flags), _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, _ptr(out)):
+    if not _fits_u32(flags) or not load_library().clw_host_cast_rays(_ptr(rays), rays.size, int(flags), _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, _ptr(out)):
         raise ValueError("clw_host_cast_rays rejects these arguments (at least one ray, fewer than 2^30, a kind bit and only CAST_* bits in flags)")
     return out
 
@@ -611,7 +550,7 @@ def occluded_rays_host(rays, flags: int, spheres, planes, lights=None) -> np.nda
     """clw_host_occluded_rays: whether every ray meets anything within its tmax, on the host -- THE definition -> uint8 [n] of 0 / 1."""
     rays, (s, p, l), (ns, np_, nl) = _cast_args(rays, spheres, planes, lights)
     out = np.empty(rays.size, np.uint8)
-    if not 0 <= int(flags) < 2 ** 32 or not load_library().clw_host_occluded_rays(_ptr(rays), rays.size, int(flags), _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, _ptr(out)):
+    if not _fits_u32(flags) or not load_library().clw_host_occluded_rays(_ptr(rays), rays.size, int(flags), _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, _ptr(out)):
         raise ValueError("clw_host_occluded_rays rejects these arguments (at least one ray, fewer than 2^30, a kind bit and only CAST_* bits in flags)")
     return out
 
@@ -622,7 +561,7 @@ def cast_layers_host(rays, flags: int, K: int, spheres, planes, lights=None) -> 
     rays, (s, p, l), (ns, np_, nl) = _cast_args(rays, spheres, planes, lights)
     K = int(K)
     t, ids = np.empty((max(K, 0), rays.size), np.float32), np.empty((max(K, 0), rays.size), np.uint32)
-    if not 0 <= int(flags) < 2 ** 32 or not 0 <= K < 2 ** 32 or not load_library().clw_host_cast_layers(
+    if not _fits_u32(flags, K) or not load_library().clw_host_cast_layers(
             _ptr(rays), rays.size, int(flags), K, _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, _ptr(t), _ptr(ids)):
         raise ValueError("clw_host_cast_layers rejects these arguments (at least one ray, fewer than 2^30, a kind bit and only CAST_* bits in flags, K in 1..8)")
     return {"t": t, "id": ids}
@@ -690,15 +629,15 @@ def object_stats(ids, depth, width: int, rows: int, counts, first_row: int = 0, 
     """clw_host_object_stats: the visible-object table of a width x rows range of an id channel (and its depth channel, or None) whose first row
     is row `first_row` of the frame, on the host -- THE definition the device pass is held to -> (OBJECT_STAT [objects], {"objects", "pixels",
     "foreign"}).  counts = (spheres, planes, lights); rect = (x, y, width, height) in frame pixels, None = the whole frame."""
-    ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
-    width, rows = int(width), int(rows)
-    if width <= 0 or rows <= 0 or ids.size != width * rows:
+    got = _frame_channels(width, rows, (ids, np.uint32, 1))
+    if got is None:
         raise ValueError("clw_host_object_stats rejects these arguments (an id channel of width * rows words)")
-    if depth is not None:
-        depth = np.ascontiguousarray(depth, np.float32).reshape(-1)
-        if depth.size != ids.size:
-            raise ValueError("clw_host_object_stats rejects these arguments (a depth channel of width * rows words)")
-    counts = np.ascontiguousarray(counts, np.uint32).reshape(3)
+    width, rows, (ids,) = got
+    got = _frame_channels(width, rows, optional=[(depth, np.float32, 1)])
+    if got is None:
+        raise ValueError("clw_host_object_stats rejects these arguments (a depth channel of width * rows words)")
+    depth = got[2][0]
+    counts = _flat(counts, np.uint32).reshape(3)
     L = load_library()
     got = _object_table(lambda out, cap, s: L.clw_host_object_stats(_ptr(ids), _ptr(depth), width, rows, int(first_row), _rect(rect), _ptr(counts),
                                                                     out, cap, s))
@@ -709,7 +648,7 @@ def object_stats(ids, depth, width: int, rows: int, counts, first_row: int = 0, 
 
 def merge_object_stats(a, b) -> np.ndarray:
     """clw_host_merge_object_stats: two tables sorted by id -> the table of both (the tables of two strips of a frame -> the frame's)."""
-    a, b = np.ascontiguousarray(a, OBJECT_STAT).reshape(-1), np.ascontiguousarray(b, OBJECT_STAT).reshape(-1)
+    a, b = _flat(a, OBJECT_STAT), _flat(b, OBJECT_STAT)
     out = np.zeros(a.size + b.size or 1, OBJECT_STAT)
     n = load_library().clw_host_merge_object_stats(_ptr(a), a.size, _ptr(b), b.size, _ptr(out), out.size)
     return out[:n].copy()
@@ -867,31 +806,21 @@ class ClWrap:
         return out
 
     def read_tile_costs(self) -> np.ndarray:
-        n = self.L.clw_ext_read_tile_costs(C.byref(self.w), None, 0)
-        out = np.zeros(n, np.uint32)
-        if n:
-            self.L.clw_ext_read_tile_costs(C.byref(self.w), _ptr(out), n)
-        return out
+        return _read_counted(lambda p, cap: self.L.clw_ext_read_tile_costs(C.byref(self.w), p, cap), np.uint32)
 
     def read_tile_order(self):
         """(order words [8 * per_share_cap], per_share_cap) the last tiled launch read; (empty, 0) = it ran in the default order."""
-        cap = C.c_uint32()
-        n = self.L.clw_ext_read_tile_order(C.byref(self.w), None, 0, C.byref(cap))
-        out = np.zeros(n, np.uint32)
-        if n:
-            self.L.clw_ext_read_tile_order(C.byref(self.w), _ptr(out), n, C.byref(cap))
-        return out, int(cap.value)
+        share = C.c_uint32()
+        out = _read_counted(lambda p, cap: self.L.clw_ext_read_tile_order(C.byref(self.w), p, cap, C.byref(share)), np.uint32)
+        return out, int(share.value)
 
     def unit_sched(self, cost: np.ndarray, tpr: int, trows: int, clamp_outliers: int, per_share_cap: int, split_slots: int, min_quota: int,
                    max_lg: int) -> np.ndarray:
         """Run wt_sched_build once on a cost table (see clw_ext_unit_sched) -> the whole sentinel-filled buffer, uint32."""
-        cost = np.ascontiguousarray(cost, np.uint32).reshape(-1)
+        cost = _flat(cost, np.uint32)
         assert cost.size == tpr * trows
         a = (int(tpr), int(trows), int(clamp_outliers), int(per_share_cap), int(split_slots), int(min_quota), int(max_lg))
-        n = self.L.clw_ext_unit_sched(C.byref(self.w), _ptr(cost), *a, None, 0)
-        out = np.zeros(n, np.uint32)
-        self.L.clw_ext_unit_sched(C.byref(self.w), _ptr(cost), *a, _ptr(out), n)
-        return out
+        return _read_counted(lambda p, words: self.L.clw_ext_unit_sched(C.byref(self.w), _ptr(cost), *a, p, words), np.uint32)
 
     def get_split(self):
         """(split_slots, min_quota, extra entries per share of a launch that may split) in effect."""
@@ -930,12 +859,8 @@ class ClWrap:
         """clw_ext_read_primary_cull -> (the cull table the last whole-range trace launch was given as uint8 [tiles], or None when it had
         none; how often the builder has run)."""
         builds = C.c_uint64()
-        n = self.L.clw_ext_read_primary_cull(C.byref(self.w), None, 0, C.byref(builds))
-        if n == 0:
-            return None, int(builds.value)
-        out = np.empty(n, np.uint8)
-        self.L.clw_ext_read_primary_cull(C.byref(self.w), _ptr(out), n, C.byref(builds))
-        return out, int(builds.value)
+        out = _read_counted(lambda p, cap: self.L.clw_ext_read_primary_cull(C.byref(self.w), p, cap, C.byref(builds)), np.uint8)
+        return (out if out.size else None), int(builds.value)
     def set_tpt(self, max_lanes=-1, min_paths=-1, pool_mb=-1): self.L.clw_ext_set_tpt(C.byref(self.w), int(max_lanes), int(min_paths), int(pool_mb))
     def timing_reset(self): self.L.clw_ext_timing_reset(C.byref(self.w))
     def set_timing_every(self, n): self.L.clw_ext_set_timing_every(C.byref(self.w), int(n))
@@ -971,12 +896,8 @@ class ClWrap:
         return int(self.L.clw_ext_render_gbuffer(C.byref(self.w), int(channels)))
 
     def _read_pass(self, read, dtype) -> np.ndarray:
-        """What a range pass left on the device: `read(out, capacity_bytes)` is asked for the byte count, then again with an array that holds it."""
-        nbytes = int(read(None, 0))
-        out = np.zeros(nbytes // np.dtype(dtype).itemsize, dtype)
-        if nbytes:
-            assert read(_ptr(out), nbytes) == nbytes
-        return out
+        """What a range pass left on the device: the counted read-back whose `read(out, capacity_bytes)` counts in bytes."""
+        return _read_counted(read, dtype, unit=1)
 
     def read_gbuffer(self, channel) -> np.ndarray:
         """One channel (a GB_* bit) of the last pass -> float32 [n] / uint32 [n] / float32 [n, 3]; empty for a channel it did not write."""
@@ -1008,8 +929,7 @@ class ClWrap:
 
     def unit_overlay(self, frame, ids, width: int, rows: int, style: clw_overlay, sel):
         """clw_ext_unit_overlay: the device pass on a synthetic frame and id channel -> uint32 [width * rows], or None when it is refused."""
-        frame = np.ascontiguousarray(frame, np.uint32).reshape(-1)
-        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        frame, ids = _flat(frame, np.uint32), _flat(ids, np.uint32)
         assert frame.size == int(width) * int(rows) == ids.size
         sel = _selection(sel)
         out = np.empty(frame.size, np.uint32)
@@ -1025,12 +945,12 @@ class ClWrap:
     def unit_object_stats(self, ids, depth, width: int, rows: int, counts, first_row: int = 0, rect=None):
         """clw_ext_unit_object_stats: the device pass on a synthetic id channel (and depth channel, or None) -> (records, summary), or None when
         it is refused."""
-        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        ids = _flat(ids, np.uint32)
         assert ids.size == int(width) * int(rows)
         if depth is not None:
-            depth = np.ascontiguousarray(depth, np.float32).reshape(-1)
+            depth = _flat(depth, np.float32)
             assert depth.size == ids.size
-        counts = np.ascontiguousarray(counts, np.uint32).reshape(3)
+        counts = _flat(counts, np.uint32).reshape(3)
         return _object_table(lambda out, cap, s: self.L.clw_ext_unit_object_stats(C.byref(self.w), _ptr(ids), _ptr(depth), int(width), int(rows), int(first_row),
                                                                                   _rect(rect), _ptr(counts), out, cap, s),
                              first_capacity=max(1024, min(ids.size, int(counts.astype(np.uint64).sum()) + 1)))
@@ -1050,18 +970,18 @@ class ClWrap:
     def cast_rays(self, rays, flags: int = CAST_SPHERES | CAST_PLANES):
         """clw_ext_cast_rays: the nearest hit of every ray (RAY_QUERY [n]) against the bound scene, on the device -> HIT [n], or None when it is
         refused (no scene bound, no ray, unknown flag bits, no kind)."""
-        rays = np.ascontiguousarray(rays, RAY_QUERY).reshape(-1)
+        rays = _flat(rays, RAY_QUERY)
         out = np.empty(rays.size, HIT)
-        if rays.size >= 2 ** 32 or not 0 <= int(flags) < 2 ** 32:
+        if not _fits_u32(rays.size, flags):
             return None
         n = self.L.clw_ext_cast_rays(C.byref(self.w), _ptr(rays), rays.size, int(flags), _ptr(out))
         return out if n == rays.size and n else None
 
     def occluded_rays(self, rays, flags: int = CAST_SPHERES | CAST_PLANES):
         """clw_ext_occluded_rays: whether every ray meets anything within its tmax, on the device -> uint8 [n] of 0 / 1, or None when it is refused."""
-        rays = np.ascontiguousarray(rays, RAY_QUERY).reshape(-1)
+        rays = _flat(rays, RAY_QUERY)
         out = np.empty(rays.size, np.uint8)
-        if rays.size >= 2 ** 32 or not 0 <= int(flags) < 2 ** 32:
+        if not _fits_u32(rays.size, flags):
             return None
         n = self.L.clw_ext_occluded_rays(C.byref(self.w), _ptr(rays), rays.size, int(flags), _ptr(out))
         return out if n == rays.size and n else None
@@ -1069,7 +989,7 @@ class ClWrap:
     def cast_rays_device(self, rays_ptr: int, n: int, flags: int = CAST_SPHERES | CAST_PLANES, hits_ptr: int | None = None, blocked_ptr: int | None = None) -> int:
         """clw_ext_cast_rays_device: the query over the caller's device memory (integer addresses: n RAY_QUERY records; n HIT records or n bytes --
         exactly one of the two), on the wrapper's stream, without waiting -> n, or 0 when it is refused."""
-        if not 0 <= int(n) < 2 ** 32 or not 0 <= int(flags) < 2 ** 32:
+        if not _fits_u32(n, flags):
             return 0
         return int(self.L.clw_ext_cast_rays_device(C.byref(self.w), C.c_void_p(rays_ptr or None), int(n), int(flags), C.c_void_p(hits_ptr or None),
                                                    C.c_void_p(blocked_ptr or None)))
@@ -1077,8 +997,8 @@ class ClWrap:
     def cast_layers(self, rays, flags: int = CAST_SPHERES | CAST_PLANES, K: int = 4):
         """clw_ext_cast_layers: the K nearest listed candidates of every ray (RAY_QUERY [n]) against the bound scene, on the device ->
         {"t": float32 [K, n], "id": uint32 [K, n]}, or None when it is refused (no scene bound, no ray, unknown flag bits, no kind, K outside 1..8)."""
-        rays = np.ascontiguousarray(rays, RAY_QUERY).reshape(-1)
-        if rays.size >= 2 ** 32 or not 0 <= int(flags) < 2 ** 32 or not 0 <= int(K) < 2 ** 32:
+        rays = _flat(rays, RAY_QUERY)
+        if not _fits_u32(rays.size, flags, K):
             return None
         t, ids = np.empty((int(K), rays.size), np.float32), np.empty((int(K), rays.size), np.uint32)
         n = self.L.clw_ext_cast_layers(C.byref(self.w), _ptr(rays), rays.size, int(flags), int(K), _ptr(t), _ptr(ids))
@@ -1087,7 +1007,7 @@ class ClWrap:
     def cast_layers_device(self, rays_ptr: int, n: int, flags: int, K: int, t_ptr: int, id_ptr: int) -> int:
         """clw_ext_cast_layers_device: the layered query over the caller's device memory (integer addresses: n RAY_QUERY records; K * n floats;
         K * n words, layer-major), on the wrapper's stream, without waiting -> n, or 0 when it is refused."""
-        if not 0 <= int(n) < 2 ** 32 or not 0 <= int(flags) < 2 ** 32 or not 0 <= int(K) < 2 ** 32:
+        if not _fits_u32(n, flags, K):
             return 0
         return int(self.L.clw_ext_cast_layers_device(C.byref(self.w), C.c_void_p(rays_ptr or None), int(n), int(flags), int(K), C.c_void_p(t_ptr or None),
                                                      C.c_void_p(id_ptr or None)))
@@ -1105,7 +1025,7 @@ class ClWrap:
 
     def render_layers(self, flags: int = CAST_SPHERES | CAST_PLANES, K: int = 4) -> int:
         """clw_ext_render_layers: the K layers of the launch camera's rays over the wrapper's range, on the device -> work-items (0 = refused)."""
-        if not 0 <= int(flags) < 2 ** 32 or not 0 <= int(K) < 2 ** 32:
+        if not _fits_u32(flags, K):
             return 0
         return int(self.L.clw_ext_render_layers(C.byref(self.w), int(flags), int(K)))
 
@@ -1120,16 +1040,14 @@ class ClWrap:
     def pick_layers(self, x, y, flags: int = CAST_SPHERES | CAST_PLANES, K: int = 8):
         """clw_ext_pick_layers: the K layers under frame pixel (x, y) -> LAYER [K], or None (no camera latched, the pixel is not one of this
         wrapper's, refused flags or K)."""
-        if not 0 <= int(flags) < 2 ** 32 or not 1 <= int(K) <= LAYERS_MAX:
+        if not _fits_u32(flags) or not 1 <= int(K) <= LAYERS_MAX:
             return None
         out = np.zeros(int(K), LAYER)
         return out if self.L.clw_ext_pick_layers(C.byref(self.w), int(x), int(y), int(flags), int(K), _ptr(out)) else None
 
     def unit_ao_open(self, point, normal, ids, width: int, rows: int, first_row: int, ao: clw_ao):
         """clw_ext_unit_ao_open: wt_ao_trace on synthetic channels against the bound scene -> uint8 [width * rows], or None when it is refused."""
-        point = np.ascontiguousarray(point, np.float32).reshape(-1)
-        normal = np.ascontiguousarray(normal, np.float32).reshape(-1)
-        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        point, normal, ids = _flat(point, np.float32), _flat(normal, np.float32), _flat(ids, np.uint32)
         assert ids.size == int(width) * int(rows) and point.size == normal.size == 3 * ids.size
         out = np.empty(ids.size, np.uint8)
         n = self.L.clw_ext_unit_ao_open(C.byref(self.w), _ptr(point), _ptr(normal), _ptr(ids), int(width), int(rows), int(first_row), C.byref(ao), _ptr(out))
@@ -1137,10 +1055,9 @@ class ClWrap:
 
     def unit_ao_resolve(self, open_u8, ids, frame, width: int, rows: int, ao: clw_ao):
         """clw_ext_unit_ao_resolve: wt_ao_resolve on synthetic counts, ids and frame (or None) -> uint32 [width * rows], or None when it is refused."""
-        open_u8 = np.ascontiguousarray(open_u8, np.uint8).reshape(-1)
-        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        open_u8, ids = _flat(open_u8, np.uint8), _flat(ids, np.uint32)
         if frame is not None:
-            frame = np.ascontiguousarray(frame, np.uint32).reshape(-1)
+            frame = _flat(frame, np.uint32)
         assert open_u8.size == int(width) * int(rows) == ids.size
         out = np.empty(ids.size, np.uint32)
         n = self.L.clw_ext_unit_ao_resolve(C.byref(self.w), _ptr(open_u8), _ptr(ids), _ptr(frame), int(width), int(rows), C.byref(ao), _ptr(out))
@@ -1167,11 +1084,7 @@ class ClWrap:
 
     def read_refine_mask(self) -> np.ndarray:
         """The block mask of the last trace launch if it was adaptive -> uint8 [blocks], row-major (empty = it was not)."""
-        n = self.L.clw_ext_read_refine_mask(C.byref(self.w), None, 0)
-        out = np.zeros(n, np.uint8)
-        if n:
-            self.L.clw_ext_read_refine_mask(C.byref(self.w), _ptr(out), n)
-        return out
+        return _read_counted(lambda p, cap: self.L.clw_ext_read_refine_mask(C.byref(self.w), p, cap), np.uint8)
 
     def set_sample_cameras(self, cams):
         """float32 [n*n, 12] ({im_corner, origin, up, right} per sample, sy * n + sx order), copied; None / empty = no table."""
@@ -1184,11 +1097,8 @@ class ClWrap:
 
     def get_sample_cameras(self) -> np.ndarray:
         """The table the last trace launch used -> float32 [count, 12] (count 0 = none)."""
-        n = self.L.clw_ext_get_sample_cameras(C.byref(self.w), None, 0)
-        out = np.zeros((n, 12), np.float32)
-        if n:
-            self.L.clw_ext_get_sample_cameras(C.byref(self.w), _ptr(out), n)
-        return out
+        cams = _read_counted(lambda p, cap: self.L.clw_ext_get_sample_cameras(C.byref(self.w), p, cap), np.float32, unit=C.sizeof(clw_sample_camera))
+        return cams.reshape(-1, 12)
 
     def set_lens(self, aperture, focus): self.L.clw_ext_set_lens(C.byref(self.w), float(aperture), float(focus))
 
@@ -1199,16 +1109,12 @@ class ClWrap:
             self.L.clw_ext_set_sphere_motion(C.byref(self.w), None, 0, None, 0)
             return
         disp = np.ascontiguousarray(disp, np.float32).reshape(-1, 3)
-        times = None if times is None else np.ascontiguousarray(times, np.float32).reshape(-1)
+        times = None if times is None else _flat(times, np.float32)
         self.L.clw_ext_set_sphere_motion(C.byref(self.w), _ptr(disp), disp.shape[0], None if times is None else _ptr(times), 0 if times is None else times.size)
 
     def get_sample_times(self) -> np.ndarray:
         """The sample times the last trace launch used -> float32 [count] (count 0 = the scene stood still)."""
-        n = self.L.clw_ext_get_sample_times(C.byref(self.w), None, 0)
-        out = np.zeros(n, np.float32)
-        if n:
-            self.L.clw_ext_get_sample_times(C.byref(self.w), _ptr(out), n)
-        return out
+        return _read_counted(lambda p, cap: self.L.clw_ext_get_sample_times(C.byref(self.w), p, cap), np.float32)
 
     def enable_counters(self, on): self.L.clw_ext_enable_counters(C.byref(self.w), int(on))
 

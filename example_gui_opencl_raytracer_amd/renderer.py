@@ -241,12 +241,16 @@ class Renderer:
     def reset_accumulation(self) -> None:
         self.w.reset_accumulation()
 
+    def _latch_camera(self) -> None:
+        """Ahead of every inspection pass: the raygen launch latches the camera set last (in fused mode it does nothing else)."""
+        if self._camera_set:
+            self.w.output(self.pixels, 0, 0, 0, 0, None)
+
     # ---- the primary-hit pass
     def gbuffer(self, channels: int = api.GB_ALL) -> dict:
         """{"depth": [n], "id": [n], "normal": [n, 3], "point": [n, 3], "albedo": [n, 3]} of the requested channels (api.GB_*) for the n work-items
-        of this renderer, through the camera set last.  The raygen launch latches it (in fused mode it does nothing else)."""
-        if self._camera_set:
-            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        of this renderer, through the camera set last."""
+        self._latch_camera()
         if self.w.render_gbuffer(channels) != self.pixels:
             raise RuntimeError("the primary-hit pass did not cover this renderer's range (is a camera set, is `channels` a mask of api.GB_*?)")
         return {name: self.w.read_gbuffer(bit) for name, (bit, _, _) in api.GB_CHANNELS.items() if channels & bit}
@@ -254,13 +258,12 @@ class Renderer:
     def pick(self, x: int, y: int) -> dict | None:
         """What lies under pixel (x, y) of the frame: {"id", "kind", "index", "depth", "point", "normal", "albedo"} -- the entries of that pixel in
         ``gbuffer()``, bit for bit -- or None when the pixel is not one of this renderer's rows (or no camera has been set)."""
-        if self._camera_set:
-            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        self._latch_camera()
         p = self.w.pick(x, y)
         if p is None:
             return None
-        return dict(id=int(p.id), kind=int(p.id) >> 30, index=int(p.id) & 0x3FFFFFFF, depth=np.float32(p.depth), point=np.array(p.point[:], np.float32),
-                    normal=np.array(p.normal[:], np.float32), albedo=np.array(p.albedo[:], np.float32))
+        return api.id_entry(p.id, depth=np.float32(p.depth), point=np.array(p.point[:], np.float32), normal=np.array(p.normal[:], np.float32),
+                            albedo=np.array(p.albedo[:], np.float32))
 
     # ---- the selection overlay
     def highlight(self, ids, *, outline: int | None = 0xFFFF00, radius: int = 2, fill: int | None = None, alpha: int = 96,
@@ -270,8 +273,7 @@ class Renderer:
         weight alpha / 256, None = none; edges: colour of a line along every boundary between two objects, None = none.  Colours are 0x00RRGGBB."""
         flags = (api.OV_OUTLINE if outline is not None else 0) | (api.OV_FILL if fill is not None else 0) | (api.OV_EDGES if edges is not None else 0)
         style = api.overlay_style(flags, radius, outline or 0, fill or 0, alpha, edges or 0)
-        if self._camera_set:
-            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        self._latch_camera()
         if self.w.render_overlay(style, ids) != self.pixels:
             raise RuntimeError("the selection overlay was refused (a camera set and a frame rendered? at most 64 ids, radius in 1..4, alpha in "
                                "0..256, something to draw, no row bands?)")
@@ -284,8 +286,7 @@ class Renderer:
         (0..256) scales how much of the occlusion shows; `filter` averages the 4 x 4 interleaved ray patterns away among pixels of the same
         object; `compose` multiplies the frame of the last ``render()`` by the result instead."""
         ao = api.ao_params(rays, radius, strength, filter, compose)
-        if self._camera_set:
-            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        self._latch_camera()
         if self.w.render_ao(ao) != self.pixels:
             raise RuntimeError("the ambient occlusion pass was refused (a camera set? rays in 1..32, radius > 0, strength in 0..256, no row bands, "
                                "with compose a frame rendered?)")
@@ -350,8 +351,7 @@ class Renderer:
     def camera_rays(self) -> np.ndarray:
         """The rays of this renderer's pixels through the camera set last, under the camera model, as query rays -> api.RAY_QUERY [pixels]
         (tmax = inf, ignore = api.ID_NONE): what ``cast_rays`` / ``cast_layers`` take.  Not available with row bands."""
-        if self._camera_set:
-            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        self._latch_camera()
         got = self.w.camera_rays(self.pixels)
         if got is None or got.size != self.pixels:
             raise RuntimeError("the camera rays were refused (a camera set? no row bands? a projection that resolves?)")
@@ -361,8 +361,7 @@ class Renderer:
         """What lies behind every pixel, in depth order -> {"t": float32 [K, rows, width], "id": uint32 [K, rows, width]}: the K nearest surfaces
         along the pixel's camera ray (``camera_rays()`` through ``cast_layers``, both on the device).  Layer 0 is what ``gbuffer()`` sees where
         the kinds agree; t is in units of the ray's direction (unit for the pinhole and the panorama)."""
-        if self._camera_set:
-            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        self._latch_camera()
         if self.w.render_layers(api.cast_flags(kinds, opaque_only), K) != self.pixels:
             raise RuntimeError("the layers pass was refused (a camera set? at least one kind, K in 1..8, no row bands?)")
         shape = (int(K), self.rows, self.width)
@@ -372,21 +371,18 @@ class Renderer:
         """Everything under pixel (x, y) of the frame, nearest first -> a list of {"id", "kind", "index", "depth"} of at most K entries (click
         again to select the object behind: the next entry), empty where the ray meets nothing; None when the pixel is not one of this
         renderer's rows (or no camera has been set)."""
-        if self._camera_set:
-            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        self._latch_camera()
         got = self.w.pick_layers(x, y, api.cast_flags(kinds, opaque_only), K)
         if got is None:
             return None
-        return [dict(id=int(e["id"]), kind=int(e["id"]) >> 30, index=int(e["id"]) & 0x3FFFFFFF, depth=np.float32(e["t"])) for e in got
-                if int(e["id"]) != api.ID_NONE]
+        return [api.id_entry(e["id"], depth=np.float32(e["t"])) for e in got if int(e["id"]) != api.ID_NONE]
 
     # ---- the visible-object table
     def objects(self, rect=None) -> np.ndarray:
         """Which objects show inside `rect` = (x, y, width, height) in frame pixels (None = the whole frame) on this renderer's rows, through the
         camera set last -> api.OBJECT_STAT [objects], sorted by id: id, pixels, the inclusive bounding box x0, y0, x1, y1 in frame coordinates,
         depth_min, depth_max, and sum_x, sum_y (centroid = sum / pixels).  Reduced on the device: only the records travel."""
-        if self._camera_set:
-            self.w.output(self.pixels, 0, 0, 0, 0, None)
+        self._latch_camera()
         got = self.w.object_stats(rect)
         if got is None:
             raise RuntimeError("the visible-object table was refused (a camera set? a rectangle of at least one pixel? no row bands?)")

@@ -444,6 +444,42 @@ def test_scene_arrays_are_snapshotted_until_invalidated(R, oracle, demo_scene, t
     assert np.array_equal(second, want) and not np.array_equal(second, first)
 
 
+def test_counted_readers_before_and_after_a_launch(R, demo_scene, tex, sky):
+    """Every reader of the "ask for the count, allocate, ask again" kind: its documented empty value on a wrapper that has no scene, no camera
+    and no launch (the shim returns 0 before it touches device memory), and its size and dtype after one 16 x 16 depth-1 frame -- 2 x 2 tiles,
+    the smallest frame with more than one tile row and column -- and one run of each inspection pass."""
+    from example_gui_opencl_raytracer_amd import api
+
+    def shaped(a, dtype, *shape):
+        return isinstance(a, np.ndarray) and a.dtype == np.dtype(dtype) and a.shape == shape
+
+    with released(api.ClWrap()) as cw:
+        assert shaped(cw.read_tile_costs(), np.uint32, 0)
+        order, cap = cw.read_tile_order()
+        assert shaped(order, np.uint32, 0) and cap == 0 and type(cap) is int
+        assert shaped(cw.read_refine_mask(), np.uint8, 0)
+        assert shaped(cw.get_sample_cameras(), np.float32, 0, 12)
+        assert shaped(cw.get_sample_times(), np.float32, 0)
+        table, builds = cw.read_primary_cull()
+        assert table is None and builds == 0 and type(builds) is int
+        assert shaped(cw.read_gbuffer(api.GB_NORMAL), np.float32, 0, 3)
+        assert shaped(cw.read_overlay(), np.uint32, 0) and shaped(cw.read_ao(api.AO_FRAME), np.uint32, 0)
+        assert shaped(cw.read_ao(api.AO_COUNTS), np.uint8, 0)
+        assert shaped(cw.read_layers(api.LAYERS_T), np.float32, 0) and shaped(cw.read_layers(api.LAYERS_ID), np.uint32, 0)
+    w = h = 16
+    with rendering(R, demo_scene, tex, sky, w, h, depth=1) as r:
+        assert shaped(r.render(), np.uint32, w * h)
+        ids = r.gbuffer()["id"]
+        r.ambient_occlusion(rays=1)
+        r.highlight([int(ids[ids != api.ID_NONE][0])])
+        r.layers(K=1)
+        assert shaped(r.w.read_tile_costs(), np.uint32, 4)
+        assert shaped(r.w.read_gbuffer(api.GB_NORMAL), np.float32, w * h, 3)
+        assert shaped(r.w.read_overlay(), np.uint32, w * h) and shaped(r.w.read_ao(api.AO_FRAME), np.uint32, w * h)
+        assert shaped(r.w.read_ao(api.AO_COUNTS), np.uint8, w * h)
+        assert shaped(r.w.read_layers(api.LAYERS_T), np.float32, w * h) and shaped(r.w.read_layers(api.LAYERS_ID), np.uint32, w * h)
+
+
 def test_traced_ray_counter(R, oracle, demo_scene, tex, sky):
     """clw_ext_read_counters_ex: word 8 = the shadow rays really traced; the reference casts 2 per light per shaded hit,
     the kernel elides those of surfaces whose specular and diffuse coefficients are both zero (glass)."""
