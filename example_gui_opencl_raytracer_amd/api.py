@@ -291,6 +291,9 @@ PROTOTYPES = {
     "clw_ext_last_trace_flags": (_int, [_W]),
     "clw_host_primary_cull": (_u32, [_CAM, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
     "clw_ext_read_primary_cull": (_u32, [_W, _vp, _u32, C.POINTER(_u64)]),
+    "clw_host_bounce_cull": (_u32, [_CAM, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _u32, _vp]),
+    "clw_ext_read_bounce_cull": (_u32, [_W, _vp, _u32]),
+    "clw_ext_set_bounce_cull": (None, [_W, _int]),
     "clw_ext_set_tpt": (None, [_W, _int, _int, _int]),
     "clw_ext_get_tpt": (None, [_W, _pu32, _pu32, _pu32]),
     "clw_host_perspective": (_int, [_f3, _f3, _f32, _f32, _u32, _u32, _CAM]),
@@ -597,6 +600,27 @@ def host_primary_cull(cam: clw_camera, spheres, lights, rows: int | None = None,
     return out[:n].reshape(trows, tpr)
 
 
+BC_SHADOW, BC_REFL_SPHERES, BC_REFL_LIGHTS = 15, 16, 32      # the bits of a bounce cull table's bytes (hip_wrap_ext.h: clw_host_bounce_cull)
+BC_PART_SHADOW, BC_PART_REFL = 1, 2                          # its parts (clw_ext_set_bounce_cull)
+
+
+def host_bounce_cull(cam: clw_camera, spheres, planes, lights, depth: int = 4, parts: int = 3, rows: int | None = None, row_offset: int = 0,
+                     band_stride: int = 1, band_phase: int = 0) -> np.ndarray:
+    """clw_host_bounce_cull: THE definition of the bounce cull table of a launch (the ranges of host_primary_cull) -> uint8 [tile rows, tiles per
+    row], bits 0-3 = the first shade's shadow rays miss the line test of every sphere i with i % 4 = the bit, bit 4 / 5 = the second iteration's
+    rays miss every sphere / every light."""
+    rows = int(cam.height) if rows is None else int(rows)
+    s, p, l = (None if a is None else np.ascontiguousarray(a) for a in (spheres, planes, lights))
+    ns, npl, nl = (0 if a is None else int(a.shape[0]) for a in (s, p, l))
+    trows, tpr = (rows + 7) // 8, (int(cam.width) + 7) // 8
+    out = np.empty(max(trows * tpr, 1), np.uint8)
+    n = load_library().clw_host_bounce_cull(C.byref(cam), int(row_offset), rows, int(band_stride), int(band_phase), _ptr(s), ns, _ptr(p), npl,
+                                            _ptr(l), nl, int(depth), int(parts), _ptr(out))
+    if n != trows * tpr or n == 0:
+        raise ValueError("clw_host_bounce_cull rejects these arguments (a frame with tiles, band_phase below band_stride)")
+    return out[:n].reshape(trows, tpr)
+
+
 def _rect(rect):
     """None (the whole frame), a clw_rect or (x, y, width, height) -> what ctypes passes for a `const clw_rect*`"""
     if rect is None:
@@ -861,6 +885,15 @@ class ClWrap:
         builds = C.c_uint64()
         out = _read_counted(lambda p, cap: self.L.clw_ext_read_primary_cull(C.byref(self.w), p, cap, C.byref(builds)), np.uint8)
         return (out if out.size else None), int(builds.value)
+
+    def read_bounce_cull(self):
+        """clw_ext_read_bounce_cull -> the bounce cull table the last whole-range trace launch was given as uint8 [tiles], or None"""
+        out = _read_counted(lambda p, cap: self.L.clw_ext_read_bounce_cull(C.byref(self.w), p, cap), np.uint8)
+        return out if out.size else None
+
+    def set_bounce_cull(self, parts=3):
+        """clw_ext_set_bounce_cull: which parts the tables built from now on carry (BC_PART_*; 0 = the primary bits only).  Same image."""
+        self.L.clw_ext_set_bounce_cull(C.byref(self.w), int(parts))
     def set_tpt(self, max_lanes=-1, min_paths=-1, pool_mb=-1): self.L.clw_ext_set_tpt(C.byref(self.w), int(max_lanes), int(min_paths), int(pool_mb))
     def timing_reset(self): self.L.clw_ext_timing_reset(C.byref(self.w))
     def set_timing_every(self, n): self.L.clw_ext_set_timing_every(C.byref(self.w), int(n))

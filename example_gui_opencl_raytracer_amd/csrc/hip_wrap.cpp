@@ -536,12 +536,14 @@ const unsigned char* bind_primary_cull(Impl* I, Impl::Cull& C, const wt_plan_in&
     V.width = P.width; V.rows = P.rows; V.row_offset = P.row_offset; V.band_stride = P.band_stride; V.band_phase = P.band_phase;
     if (!wt_cull_view_ok(&V)) return nullptr;      /* a camera term that is not finite: no bit could be set */
     const uint32_t tiles = plan.trows * plan.tpr;
-    const size_t bytes = ((size_t)tiles + 3u) & ~(size_t)3u;
-    const bool current = C.valid && C.scene == I->scene_generation && C.tiles == tiles && !memcmp(&C.view, &V, sizeof V);
+    const size_t bytes = (2u * (size_t)tiles + 3u) & ~(size_t)3u;      /* two bytes per tile: the primary byte, the bounce byte */
+    /* (the bounce byte also depends on the launch depth -- it names the second iteration -- and on the parts asked for) */
+    const bool current = C.valid && C.scene == I->scene_generation && C.tiles == tiles && C.depth == P.depth && C.parts == I->bounce_parts && !memcmp(&C.view, &V, sizeof V);
     if (!current) {
-        /* A table pays when it is read more than once: the builder's launch costs the frame 4.7 us of wall time and saves it 1 us of kernel
-         * time (1920x1080, demo scene).  So a view is built for when it is seen the SECOND time in a row: a camera that moves every frame
-         * never builds (its launches test everything, as before), a still view builds once, behind its first frame. */
+        /* A table pays when it is read more than once: the builder's launch runs 30 us (1920x1080, demo scene: both bytes of a tile, in
+         * double precision) and the table saves a frame 5.6 us of kernel time; when the builder wrote the primary byte alone it ran 7 us, cost
+         * a frame 4.7 us of wall time and saved it 1 us.  So a view is built for when it is seen the SECOND time in a row: a camera that
+         * moves every frame never builds (its launches test everything, as before), a still view builds once, behind its first frame. */
         const bool again = C.seen && C.seen_scene == I->scene_generation && C.seen_tiles == tiles && !memcmp(&C.seen_view, &V, sizeof V);
         C.valid = false;
         if (!again) { C.seen = true; C.seen_view = V; C.seen_scene = I->scene_generation; C.seen_tiles = tiles; return nullptr; }
@@ -553,8 +555,8 @@ const unsigned char* bind_primary_cull(Impl* I, Impl::Cull& C, const wt_plan_in&
         C.bytes = bytes;
     }
     if (!current) {
-        if (wt_fast_launch_cull(&P, C.table, I->stream) != hipSuccess) die("Couldn't run the kernel");
-        C.view = V; C.scene = I->scene_generation; C.tiles = tiles; C.valid = true; C.builds++;
+        if (wt_fast_launch_cull(&P, I->bounce_parts, C.table, I->stream) != hipSuccess) die("Couldn't run the kernel");
+        C.view = V; C.scene = I->scene_generation; C.tiles = tiles; C.depth = P.depth; C.parts = I->bounce_parts; C.valid = true; C.builds++;
     }
     I->tables_in_flight = true;
     C.last_used = true;
@@ -867,6 +869,7 @@ void cl_wrap_init(cl_wrap* wrap, cl_device_type type, ...) {
     I->tpt_pool_mb = (unsigned)env_int("CLWRAP_TPT_POOL_MB", (int)WT_TPT_POOL_MB);
     I->split_min_quota = (unsigned)env_int("CLWRAP_SPLIT_MIN_QUOTA", (int)WT_SPLIT_MIN_QUOTA);
     I->tpt_clock = env_int("CLWRAP_TPT_CLOCK", 0) ? 1 : 0;
+    I->bounce_parts = (uint32_t)env_int("CLWRAP_BOUNCE_CULL", 3) & 3u;      /* A/B runs: clw_ext_set_bounce_cull */
     I->split_slots = (unsigned)std::max(1, env_int("CLWRAP_SPLIT_SLOTS", (int)WT_SPLIT_SLOTS));
 
     wrap->impl = I;
@@ -1171,6 +1174,12 @@ void clw_ext_set_grid_pair(cl_wrap* wrap, int on) {
 void clw_ext_set_tile_sched(cl_wrap* wrap, int on) { Impl* I = impl_of(wrap); I->sched = on ? 1 : 0; for (auto& sc : I->scheds) sc.reset(); }
 void clw_ext_set_variant(cl_wrap* wrap, int variant) { impl_of(wrap)->variant = variant; }
 int clw_ext_last_trace_flags(cl_wrap* wrap) { return impl_of(wrap)->last_trace_flags; }
+/* byte `which` (0 = primary, 1 = bounce) of every tile's entry of a slot's table -> out[tiles] */
+static void read_cull_bytes(const Impl::Cull& C, unsigned which, uint8_t* out) {
+    std::vector<uint8_t> both(2u * (size_t)C.tiles);
+    HIP_OK(hipMemcpy(both.data(), C.table, both.size(), hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
+    for (uint32_t t = 0; t < C.tiles; t++) out[t] = both[2u * (size_t)t + which];
+}
 uint32_t clw_ext_read_primary_cull(cl_wrap* wrap, uint8_t* out, uint32_t capacity, uint64_t* builds) {
     Impl* I = impl_of(wrap);
     use_device(I);
@@ -1178,8 +1187,23 @@ uint32_t clw_ext_read_primary_cull(cl_wrap* wrap, uint8_t* out, uint32_t capacit
     const Impl::Cull& C = I->culls[0];
     if (builds) *builds = C.builds;
     if (!C.last_used || !C.table) return 0;
-    if (out && capacity >= C.tiles) HIP_OK(hipMemcpy(out, C.table, C.tiles, hipMemcpyDeviceToHost), "Failed to transfer device memory to host");
+    if (out && capacity >= C.tiles) read_cull_bytes(C, 0, out);
     return C.tiles;
+}
+uint32_t clw_ext_read_bounce_cull(cl_wrap* wrap, uint8_t* out, uint32_t capacity) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    finish(I);
+    const Impl::Cull& C = I->culls[0];
+    if (!C.last_used || !C.table) return 0;
+    if (out && capacity >= C.tiles) read_cull_bytes(C, 1, out);
+    return C.tiles;
+}
+void clw_ext_set_bounce_cull(cl_wrap* wrap, int parts) {
+    if (parts < 0 || parts > 3) die("The bounce cull parts must be 0 (none), 1 (shadow), 2 (reflected) or 3 (both)");
+    Impl* I = impl_of(wrap);
+    I->bounce_parts = (uint32_t)parts;
+    for (auto& c : I->culls) c.valid = false;      /* the view's next launch builds its table again */
 }
 void clw_ext_set_tpt(cl_wrap* wrap, int max_lanes, int min_paths, int pool_mb) {
     Impl* I = impl_of(wrap);

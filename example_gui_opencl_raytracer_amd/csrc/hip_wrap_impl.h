@@ -26,6 +26,7 @@
 #include "objects_host.h"
 #include "overlay_host.h"
 #include "png_codec.h"
+#include "bounce_cull_host.h"
 #include "primary_cull_host.h"
 #include "projection_host.h"
 #include "scene_prep.h"
@@ -325,10 +326,11 @@ struct Impl {
      * now come twice in a row, so a still view pays for it once and a camera that moves every frame never.  It is written and read in stream
      * order (the tables fence covers a change of stream). */
     struct Cull {
-        unsigned char* table = nullptr; size_t bytes = 0;   /* a byte per tile, rounded up to whole words */
-        bool valid = false;                                  /* `table` holds the table of `view` and `scene` */
+        unsigned char* table = nullptr; size_t bytes = 0;   /* two bytes per tile (primary, bounce: bounce_cull_host.h), rounded up to whole words */
+        bool valid = false;                                  /* `table` holds the table of `view`, `scene`, `depth` and `parts` */
         wt_cull_view view{}; uint64_t scene = 0;
         uint32_t tiles = 0;
+        int32_t depth = 0; uint32_t parts = 0;               /* what the bounce bytes were built for: the launch depth, WT_BC_PART_* */
         bool seen = false;                                   /* the key of the slot's last launch that could read a table: a view is built for when it comes twice in a row */
         wt_cull_view seen_view{}; uint64_t seen_scene = 0; uint32_t seen_tiles = 0;
         uint64_t builds = 0;                                 /* builder launches so far (clw_ext_read_primary_cull) */
@@ -336,6 +338,7 @@ struct Impl {
         void free_all() { if (table) (void)hipFree(table); table = nullptr; bytes = 0; valid = false; last_used = false; tiles = 0; }
     };
     Cull culls[1 + MAX_CHUNKS];
+    uint32_t bounce_parts = WT_BC_PART_SHADOW | WT_BC_PART_REFL;   /* CLWRAP_BOUNCE_CULL, clw_ext_set_bounce_cull: the parts of the bounce byte that tables carry */
     /* pipelined read-back (cl_wrap_output of a large frame): strips rendered back to back, each copied to the host
      * while the next one renders */
     int pipeline = 1;

@@ -12,7 +12,7 @@
 #define WT_FAST_ONLY(ret, name, args) extern "C" ret wt_fast_##name args;
 
 WT_BOTH(hipError_t, launch_trace, (const whitted_params* P, const unsigned char* tile_cull, int flags, unsigned grid, size_t dyn_lds, hipStream_t s))
-WT_FAST_ONLY(hipError_t, launch_cull, (const whitted_params* P, unsigned char* table, hipStream_t s))
+WT_FAST_ONLY(hipError_t, launch_cull, (const whitted_params* P, unsigned parts, unsigned char* table, hipStream_t s))
 WT_BOTH(int, has_trace, (int flags))
 WT_BOTH(hipError_t, launch_raygen, (const raygen_params* P, hipStream_t s))
 WT_BOTH(hipError_t, launch_raygen_proj, (const raygen_params* P, const wt_projection* T, hipStream_t s))

@@ -3,7 +3,7 @@
  * whitted_ao.inc, the ray queries of whitted_cast.inc, the layered ray queries of whitted_layers.inc, the selection overlay of
  * whitted_overlay.inc, the visible-object table of whitted_objects.inc and the builder of the primary-ray cull table of whitted_cull.inc) in
  * namespace WT_NS and exports the C launchers the shim calls. */
-#include "primary_cull_host.h"
+#include "bounce_cull_host.h"      /* (and through it primary_cull_host.h) */
 namespace WT_NS {
 #include "whitted_trace.inc"
 #include "whitted_gbuffer.inc"
@@ -90,16 +90,20 @@ WT_LAUNCHER(trace)(const whitted_params* P, const unsigned char* tile_cull, int 
 }
 
 #if !WT_STRICT   /* double-precision work that is the same in both builds: one copy, in the fast unit */
-/* the primary-ray cull table (whitted_cull.inc) of the tiled launch `P` describes, into `table`: a byte per tile, trows x tpr of them */
-WT_LAUNCHER(cull)(const whitted_params* P, unsigned char* table, hipStream_t s) {
+/* the cull table (whitted_cull.inc) of the tiled launch `P` describes, into `table`: two bytes per tile -- the primary byte, the bounce byte with
+ * the parts `parts` (WT_BC_PART_*) --, trows x tpr of them */
+WT_LAUNCHER(cull)(const whitted_params* P, unsigned parts, unsigned char* table, hipStream_t s) {
     const unsigned long long tpr = (P->width + 7ull) / 8ull, trows = (P->rows + 7ull) / 8ull;
-    if (!P->tiled || P->width == 0u || P->rows == 0u || tpr * trows >= (1ull << 31) || !table || !P->geom) return hipErrorInvalidValue;
+    if (!P->tiled || P->width == 0u || P->rows == 0u || tpr * trows >= (1ull << 30) || !table || !P->geom) return hipErrorInvalidValue;
     WT_NS::wt_cull_args A = {};
     for (int a = 0; a < 3; a++) { A.V.corner[a] = P->corner[a]; A.V.origin[a] = P->origin[a]; A.V.up[a] = P->up[a]; A.V.right[a] = P->right[a]; }
     A.V.w_factor = P->w_factor; A.V.h_factor = P->h_factor;
     A.V.width = P->width; A.V.rows = P->rows; A.V.row_offset = P->row_offset; A.V.band_stride = P->band_stride; A.V.band_phase = P->band_phase;
-    A.spheres = P->geom; A.lights = P->geom + 4 * ((size_t)P->ns + 2 * (size_t)P->np);
-    A.ns = P->ns; A.nl = P->nl; A.tiles = (unsigned)(tpr * trows); A.tpr = (unsigned)tpr; A.table = table;
+    A.S.spheres = P->geom; A.S.planes = P->geom + 4 * (size_t)P->ns; A.S.lights = P->geom + 4 * ((size_t)P->ns + 2 * (size_t)P->np);
+    A.S.planes_raw = (const uint32_t*)P->planes_raw;
+    A.S.ns = P->ns; A.S.np = P->np; A.S.nl = P->nl; A.S.depth = P->depth > 0 ? (unsigned)P->depth : 0u;
+    if (A.S.np > 0u && !A.S.planes_raw) parts = 0u;      /* (no raw records to read the planes' materials from: the primary byte alone) */
+    A.tiles = (unsigned)(tpr * trows); A.tpr = (unsigned)tpr; A.parts = parts; A.table = table;
     hipLaunchKernelGGL(WT_NS::wt_primary_cull_build, dim3((A.tiles + 255u) / 256u), dim3(256), 0, s, A);
     return hipGetLastError();
 }

@@ -145,9 +145,11 @@ typedef struct {
 } whitted_params;
 
 /* What wt_trace_cull receives, the twin of wt_trace that a launch WITH a primary-ray cull table runs (a launch without one runs wt_trace on the
- * whitted_params alone): the parameters, and behind them the table (primary_cull_host.h): one byte per tile, indexed like tile_cost, bit 0 = no primary ray of the tile can meet the line test of any sphere, bit 1 = of any
- * light sphere; the first loop iteration of the tile's wave skips the group (whitted_hit.inc).  Read as whole words: the allocation is a
- * multiple of four bytes.  The pointer travels BEHIND whitted_params, not inside it: the struct is embedded in the planner's wt_plan_out, whose
+ * whitted_params alone): the parameters, and behind them the table: TWO bytes per tile, indexed like tile_cost.  The first is the primary byte
+ * (primary_cull_host.h): bit 0 = no primary ray of the tile can meet the line test of any sphere, bit 1 = of any light sphere; the first loop
+ * iteration of the tile's wave skips the group (whitted_hit.inc).  The second is the bounce byte (bounce_cull_host.h): the sphere classes the
+ * first shade's shadow batch skips, and the two groups again for the second iteration.  Read as whole words: the allocation is a multiple of
+ * four bytes.  The pointer travels BEHIND whitted_params, not inside it: the struct is embedded in the planner's wt_plan_out, whose
  * layout the planner's tests mirror field by field, and the planner has nothing to say about a device pointer.  Only shallow fused tiled
  * launches of the pinhole camera without sample cameras, moving spheres, supersampling or a grid get a table (launch_plan.h: wt_plan_cull). */
 typedef struct {

@@ -147,8 +147,10 @@
                 }
                 WT_STAMP(WT_ST_LIGHTS);
                 /* (not in the high-occupancy deep flavour: its register cap turns the table's four values into spills, +3 % at C3) */
+                /* (wt_trace_cull: in a tile's first iteration `cullb` carries the sphere classes no shadow ray of this shade can meet) */
                 if (any_sample)
-                    wt_shadow_batch<GEOM_LDS, NR, !(DEEP && wt_cfg<FLAGS>::occ), SPHCULL, FLAGS>(P, sg, g_pln, ip, rd, tl, a4, a2, op, LCH == 3 ? lb / 3u : ~0u, dl, cand, WT_MOTION);
+                    wt_shadow_batch<GEOM_LDS, NR, !(DEEP && wt_cfg<FLAGS>::occ), SPHCULL, FLAGS, CULL>(P, sg, g_pln, ip, rd, tl, a4, a2, op, LCH == 3 ? lb / 3u : ~0u, dl, cand, WT_MOTION,
+                                                                                                    CULL ? (cullb >> WT_CULLB_SHADOW_SHIFT) & 15u : 0u);
                 WT_STAMP(WT_ST_SHADOW);
 #pragma unroll
                 for (int k = 0; k < LCH; k++) {

@@ -1203,12 +1203,14 @@ __device__ __forceinline__ unsigned long long wt_sphere_candidates(const whitted
  * light sphere lie on the same side of the plane, with margins ten times the rounding involved, so the reference's
  * predicate `b != 0 && 0 < num/b < tl` (primitives.cl:422-437) is false whatever the sample.  In render.map no plane
  * ever lies between a surface and a light: 12 of the 36 tests of a shaded hit go. */
-template <bool GEOM_LDS, int NR, bool CULL, bool MASKED = false, int SHF = 0>
+template <bool GEOM_LDS, int NR, bool CULL, bool MASKED = false, int SHF = 0, bool SKIP = false>
 __device__ __forceinline__ void wt_shadow_batch(const whitted_params& P, const float4* sg, unsigned g_pln, f3 ip,
                                                 const f3 (&rd)[NR], const float (&tl)[NR], const float (&a4)[NR],
                                                 const float (&a2)[NR], float (&op)[NR], unsigned chunk,
                                                 const float (&dlc)[NR / WT_SOFT], const unsigned long long cand = ~0ull,
-                                                const wt_motion mv = wt_motion{false, 0.0f, 0u}) {
+                                                const wt_motion mv = wt_motion{false, 0.0f, 0u}, const unsigned skip = 0u) {
+    /* `skip` (SKIP: wt_trace_cull only; wave-uniform): bit k set = no ray of this batch, from any lane, can pass the line test of a sphere i
+     * with i mod 4 = k (the bounce cull table, bounce_cull_host.h): the plain loop does not test those spheres. */
     /* `cand` (wave-uniform; scenes of <= 64 spheres): bit i clear = no ray of this batch, from any lane, can meet sphere i in front of its
      * sample (wt_sphere_candidates): the sphere is not tested.  Which spheres are tested never changes a factor: a skipped test could only fail. */
     typedef wt_shape<SHF> SH;                                /* SHF: the caller's FLAGS (compile-time counts, wt_shape) */
@@ -1247,6 +1249,7 @@ __device__ __forceinline__ void wt_shadow_batch(const whitted_params& P, const f
             for (int q = 0; q < NR; q++) live |= __float_as_uint(op[q]);
             if (__builtin_amdgcn_ballot_w64(live != 0u) == 0) break;
         }
+        if (SKIP && ((skip >> (i & 3u)) & 1u)) continue;          /* wave-uniform */
         const float4 s = wt_sphere_at<GEOM_LDS>(P, sg, i, mv);
         const sph_pre pre = wt_shadow_pre(ip, s);
         const float through = (__float_as_uint(s.w) >> 31) ? P.through : 0.0f;   /* x0.8 or blocked */
@@ -1375,6 +1378,12 @@ __device__ __forceinline__ void wt_acc_fold(float* __restrict__ s, const float s
 typedef const __attribute__((address_space(4))) whitted_params* wt_kparams_t;
 /* the flavours that have a twin reading the primary-ray cull table (wt_trace_cull): shallow, 1 sample, rays generated in the kernel, linear scan */
 constexpr bool wt_cull_flavour(int flags) { return (flags & (WT_F_DEEP | WT_F_GRID | WT_F_RAYS | WT_F_SS)) == 0; }
+/* a tile's 16-bit entry of the table (whitted_params.h: whitted_kargs): the primary byte, and the bounce byte (bounce_cull_host.h) above it */
+#define WT_CULLB_SHADOW_SHIFT 8u        /* bits 8-11: WT_BC_SHADOW << k */
+#define WT_CULLB_REFL_SHIFT 12u         /* bits 12-13: WT_BC_REFL_SPHERES, WT_BC_REFL_LIGHTS, in the order of WT_CULL_SPHERES, WT_CULL_LIGHTS */
+#define WT_CULLB_MASK 0x3F03u
+static_assert(WT_BC_REFL_SPHERES << 8 == WT_CULL_SPHERES << WT_CULLB_REFL_SHIFT && WT_BC_REFL_LIGHTS << 8 == WT_CULL_LIGHTS << WT_CULLB_REFL_SHIFT &&
+              WT_BC_EPS == WT_EPSILON, "the bounce byte as wt_trace_body reads it");
 /* TABLE: the body of wt_trace_cull -- `Pk` then points at a whitted_kargs (the parameters first, the table's pointer behind them); false: the
  * body of wt_trace, `Pk` points at the whitted_params alone and nothing of the table is compiled */
 template <int FLAGS, bool TABLE>
@@ -1440,7 +1449,9 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
     unsigned x = 0, y = 0;  /* position inside this launch's row range (fused mode) */
     unsigned tile = 0xFFFFFFFFu;   /* row-major tile index (tiled mode) */
     unsigned part_lg = 0u, part = 0u; /* this wave serves part `part` of 2^part_lg of the tile */
-    unsigned cullb = 0u;    /* wave-uniform: the groups of tests the FIRST loop iteration skips (WT_CULL_*), cleared after it */
+    /* wave-uniform: the tile's entry of the cull table in the FIRST loop iteration -- bits 0-1 the groups of tests it skips (WT_CULL_*), bits 8-11
+     * the sphere classes its shade's shadow batch skips --, in the second the two group bits again (from the entry's bits 12-13), then 0 */
+    unsigned cullb = 0u;
     if (P.tiled) {
         /* workgroups are dealt to XCDs round-robin (b % 8): XCD k owns the tile rows r = 8m + k, so a
          * framebuffer line is written by one L2 and per-XCD work stays balanced.  Within an XCD's share
@@ -1466,12 +1477,12 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
          * 2^lg owns 64 >> lg of its pixels, the other lanes only help in the tree-parallel tail, which such a wave enters at once */
         valid = (tile != 0xFFFFFFFFu) && (x < P.width) && (y < P.rows) && ((lane >> (6u - part_lg)) == part);
         item = y * P.width + x;
-        /* the tile's byte of the cull table: a scalar load of the word that holds it, issued here, first needed at the light probe */
+        /* the tile's two bytes of the cull table: a scalar load of the word that holds them, issued here, first needed at the light probe */
         if (CULL) {
             typedef const __attribute__((address_space(1))) unsigned* wt_gwords_t;
             const uint8_t* tc = ((const __attribute__((address_space(4))) whitted_kargs*)Pk)->tile_cull;
             if (tc && tile != 0xFFFFFFFFu && trow * 8u < P.rows)      /* (the default order's grid is rounded up to 8 tile rows: those lie beyond the table) */
-                cullb = (unsigned)__builtin_amdgcn_readfirstlane((int)((((wt_gwords_t)tc)[tile >> 2] >> ((tile & 3u) * 8u)) & 3u));
+                cullb = (unsigned)__builtin_amdgcn_readfirstlane((int)((((wt_gwords_t)tc)[tile >> 1] >> ((tile & 1u) * 16u)) & WT_CULLB_MASK));
         }
     } else {
         item = wg * WT_BLOCK + tid;
@@ -1598,7 +1609,10 @@ __device__ __forceinline__ void wt_trace_body(const wt_kparams_t Pk, const unsig
 #include "whitted_pop.inc"
             WT_STAMP(WT_ST_POP);
         }
-        if (CULL) cullb = 0u;      /* the table speaks of primary rays: every live lane has just traced its own */
+        /* the table's low byte speaks of primary rays and of their shade: every live lane has just traced its own.  Its reflected bits move into
+         * the two group bits for the second iteration (every live lane then traces the reflection off the tile's plane: bounce_cull_host.h), and
+         * the same shift leaves 0 behind that one */
+        if (CULL) cullb = (cullb >> WT_CULLB_REFL_SHIFT) & (WT_CULL_SPHERES | WT_CULL_LIGHTS);
     }
     if (!TPT || __builtin_amdgcn_ballot_w64(active) == 0) break;
     {

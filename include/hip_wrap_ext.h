@@ -809,6 +809,29 @@ uint32_t clw_host_primary_cull(const struct clw_camera* cam, uint32_t row_offset
                                uint32_t ns, const void* lights, uint32_t nl, uint8_t* out);
 uint32_t clw_ext_read_primary_cull(cl_wrap* wrap, uint8_t* out, uint32_t capacity, uint64_t* builds);
 
+/* The bounce cull table: a second byte per tile, one segment further.  Where bit 0 of the primary byte is set and ONE plane is the first hit of
+ * every primary ray of the tile (decided at the four corner pixels and the centre: between two planes "nearer" is linear in the unnormalised
+ * direction; a tile in which two planes meet, a grazing view or a normal that is not unit to 1e-6 carries nothing), the shading points of the
+ * tile lie in a ball around the four corner hits, and
+ *   bits 0-3  bit k: no line through that ball and a light sphere (any light) passes the line test of a scene sphere i with i mod 4 = k -- the
+ *             shadow batch of the tile's FIRST shade skips those spheres (an empty class has its bit set)
+ *   bit 4     no ray of the tile's SECOND loop iteration passes the line test of any scene sphere     bit 5  the same for every light sphere
+ *             -- the plane's material is not transparent and depth >= 2, so those rays are the primary rays' mirror images and leave a
+ *             virtual pinhole, the camera origin mirrored in the plane: the primary table's cone rule from there, every radius enlarged by
+ *             the kernel's offset of the hit point.
+ * clw_host_bounce_cull is THE definition (csrc/bounce_cull_host.h states the rule and justifies its margins); the arguments are
+ * clw_host_primary_cull's, with the 96-byte rplane array, the launch depth and `parts` (1 = bits 0-3, 2 = bits 4-5, 3 = both; other bits of the
+ * byte are 0).  Conservative like the primary table: a set bit implies D < 0 in the kernel's float32 for every test it stands for.
+ * The device builder writes both bytes of a tile (one 16-bit entry, which the trace kernel loads where it loaded the primary byte) under the
+ * primary table's when-to-build rule; a change of the launch depth or of the parts also builds again.
+ * clw_ext_read_bounce_cull: the bounce bytes of the table the LAST whole-range trace launch was given, as clw_ext_read_primary_cull reads the
+ * primary ones.  clw_ext_set_bounce_cull: the parts that tables built from now on carry (default 3, or CLWRAP_BOUNCE_CULL); same image whatever
+ * the parts; the next launch of a still view builds its table again.  For tests and A/B runs. */
+uint32_t clw_host_bounce_cull(const struct clw_camera* cam, uint32_t row_offset, uint32_t rows, uint32_t band_stride, uint32_t band_phase, const void* spheres,
+                              uint32_t ns, const void* planes, uint32_t np, const void* lights, uint32_t nl, uint32_t depth, uint32_t parts, uint8_t* out);
+uint32_t clw_ext_read_bounce_cull(cl_wrap* wrap, uint8_t* out, uint32_t capacity);
+void clw_ext_set_bounce_cull(cl_wrap* wrap, int parts);
+
 /* The tree-parallel tail of deep launches (depth > 4; csrc/whitted_tpt.inc): once at most `max_lanes` lanes of a tile's wavefront are
  * alive and they hold at least `min_paths` pending paths (current segments + continuations on their stacks), the rest of the tile is
  * traced by the whole wavefront as one pool of segments kept in a slot of a device pool of `pool_mb` MiB (8 192 slots).
