@@ -64,6 +64,14 @@ LAYERS_T, LAYERS_ID = 0, 1
 TIMING_LAYERS = 0x4C415952
 TIMING_CAMRAYS = 0x43524159
 
+# path queries (hip_wrap_ext.h: CLW_PATH_*, clw_host_cast_paths): the two flags beside the ray queries', the largest number of segments, why a
+# path ended (the high half of its status byte; the low half is the count of recorded hits), and the kernel's id in the timing log
+PATH_TRANSMIT, PATH_ALL_SURFACES = 16, 32
+PATH_MAX_BOUNCES = 8
+PATH_REASON_BOUNCES, PATH_REASON_MISSED, PATH_REASON_ENDED = 0, 1, 2
+PATH_EPSILON = np.float32(0.001)      # the reference's EPSILON: a segment starts at point + normal * EPSILON of the hit before it
+TIMING_PATHS = 0x50415448
+
 
 def id_kind(ids):
     """Kind of the entries of an id channel (0 sphere, 1 plane, 2 light; 3 for ID_NONE)."""
@@ -272,6 +280,10 @@ PROTOTYPES = {
     "clw_ext_read_layers": (_u32, [_W, _u32, _vp, _u32]),
     "clw_ext_layers_device_ptr": (_vp, [_W, _u32]),
     "clw_ext_pick_layers": (_int, [_W, _u32, _u32, _u32, _u32, _vp]),
+    "clw_host_cast_paths": (_int, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "clw_ext_cast_paths": (_u32, [_W, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "clw_ext_cast_paths_device": (_u32, [_W, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "clw_ext_pick_path": (_int, [_W, _u32, _u32, _u32, _u32, _vp, _vp]),
     "clw_ext_enable_counters": (None, [_W, _int]),
     "clw_ext_read_counters": (None, [_W, C.POINTER(_u64 * 8)]),
     "clw_ext_read_counters_ex": (None, [_W, C.POINTER(_u64 * 32), _u32]),
@@ -568,6 +580,31 @@ def cast_layers_host(rays, flags: int, K: int, spheres, planes, lights=None) -> 
             _ptr(rays), rays.size, int(flags), K, _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, _ptr(t), _ptr(ids)):
         raise ValueError("clw_host_cast_layers rejects these arguments (at least one ray, fewer than 2^30, a kind bit and only CAST_* bits in flags, K in 1..8)")
     return {"t": t, "id": ids}
+
+
+def path_flags(kinds=("sphere", "plane", "light"), opaque_only: bool = False, transmit: bool = False, all_surfaces: bool = False) -> int:
+    """The flag word of a path query: cast_flags(kinds, opaque_only), PATH_TRANSMIT, PATH_ALL_SURFACES."""
+    return cast_flags(kinds, opaque_only) | (PATH_TRANSMIT if transmit else 0) | (PATH_ALL_SURFACES if all_surfaces else 0)
+
+
+def paths_result(hits, status, nxt) -> dict:
+    """What a path query answers, from its three arrays (HIT [B, n], uint8 [n], RAY_QUERY [n]) -> {"t", "id", "normal", "point"} as [B, n]
+    (normal and point [B, n, 3]; entries from a path's count on are misses), "count" and "reason" as uint8 [n] (PATH_REASON_*), "next" as
+    RAY_QUERY [n], and the arrays themselves as "hits" and "status"."""
+    return {"t": hits["t"], "id": hits["id"], "normal": hits["normal"], "point": hits["point"], "count": status & np.uint8(15),
+            "reason": status >> np.uint8(4), "next": nxt, "hits": hits, "status": status}
+
+
+def cast_paths_host(rays, flags: int, bounces: int, spheres, planes, lights=None) -> dict:
+    """clw_host_cast_paths: the path of every ray -- its hit, the reference's reflected or refracted ray from there, that ray's hit ... for up
+    to `bounces` segments --, on the host: THE definition the device pass is held to -> paths_result()."""
+    rays, (s, p, l), (ns, np_, nl) = _cast_args(rays, spheres, planes, lights)
+    B = int(bounces)
+    hits, status, nxt = np.empty((max(B, 0), rays.size), HIT), np.empty(rays.size, np.uint8), np.empty(rays.size, RAY_QUERY)
+    if not _fits_u32(flags, B) or not load_library().clw_host_cast_paths(
+            _ptr(rays), rays.size, int(flags), B, _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, _ptr(hits), _ptr(status), _ptr(nxt)):
+        raise ValueError("clw_host_cast_paths rejects these arguments (at least one ray, fewer than 2^30, a kind bit and only CAST_* and PATH_* bits in flags, bounces in 1..8)")
+    return paths_result(hits, status, nxt)
 
 
 def camera_rays_host(cam: clw_camera, proj: clw_projection | None = None, id_begin: int = 0, id_end: int | None = None) -> np.ndarray:
@@ -1077,6 +1114,33 @@ class ClWrap:
             return None
         out = np.zeros(int(K), LAYER)
         return out if self.L.clw_ext_pick_layers(C.byref(self.w), int(x), int(y), int(flags), int(K), _ptr(out)) else None
+
+    def cast_paths(self, rays, flags: int = CAST_KINDS, bounces: int = 4):
+        """clw_ext_cast_paths: the path of every ray (RAY_QUERY [n]) through the bound scene, on the device, in one launch -> paths_result(), or
+        None when it is refused (no scene bound, no ray, unknown flag bits, no kind, bounces outside 1..8)."""
+        rays = _flat(rays, RAY_QUERY)
+        if not _fits_u32(rays.size, flags, bounces) or int(bounces) < 1:
+            return None
+        hits, status, nxt = np.empty((int(bounces), rays.size), HIT), np.empty(rays.size, np.uint8), np.empty(rays.size, RAY_QUERY)
+        n = self.L.clw_ext_cast_paths(C.byref(self.w), _ptr(rays), rays.size, int(flags), int(bounces), _ptr(hits), _ptr(status), _ptr(nxt))
+        return paths_result(hits, status, nxt) if n == rays.size and n else None
+
+    def cast_paths_device(self, rays_ptr: int, n: int, flags: int, bounces: int, hits_ptr: int, status_ptr: int, next_ptr: int | None = None) -> int:
+        """clw_ext_cast_paths_device: the path query over the caller's device memory (integer addresses: n RAY_QUERY records; bounces * n HIT
+        records, segment-major; n bytes; n RAY_QUERY records or None), on the wrapper's stream, without waiting -> n, or 0 when it is refused."""
+        if not _fits_u32(n, flags, bounces):
+            return 0
+        return int(self.L.clw_ext_cast_paths_device(C.byref(self.w), C.c_void_p(rays_ptr or None), int(n), int(flags), int(bounces),
+                                                    C.c_void_p(hits_ptr or None), C.c_void_p(status_ptr or None), C.c_void_p(next_ptr or None)))
+
+    def pick_path(self, x, y, bounces: int = 4, flags: int = CAST_KINDS):
+        """clw_ext_pick_path: the path of the camera ray of frame pixel (x, y) -> (HIT [bounces], status byte), or None (no camera latched, the
+        pixel is not one of this wrapper's, refused flags or bounces, no scene bound)."""
+        if not _fits_u32(flags) or not 1 <= int(bounces) <= PATH_MAX_BOUNCES:
+            return None
+        hits, status = np.zeros(int(bounces), HIT), np.zeros(1, np.uint8)
+        ok = self.L.clw_ext_pick_path(C.byref(self.w), int(x), int(y), int(bounces), int(flags), _ptr(hits), _ptr(status))
+        return (hits, int(status[0])) if ok else None
 
     def unit_ao_open(self, point, normal, ids, width: int, rows: int, first_row: int, ao: clw_ao):
         """clw_ext_unit_ao_open: wt_ao_trace on synthetic channels against the bound scene -> uint8 [width * rows], or None when it is refused."""

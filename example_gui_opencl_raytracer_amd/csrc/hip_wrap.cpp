@@ -1006,6 +1006,7 @@ void cl_wrap_release(cl_wrap* wrap) {
     I->ao.release();
     I->cast.free_buffers();
     I->layers.release();
+    I->paths.release();
     I->ptab.free_all();
     I->adapt.free_all();
     if (I->tables_fence) (void)hipEventDestroy(I->tables_fence);

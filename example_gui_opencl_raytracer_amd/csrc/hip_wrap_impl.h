@@ -22,6 +22,7 @@
 #include "ao_host.h"
 #include "cast_host.h"
 #include "layers_host.h"
+#include "paths_host.h"
 #include "launch_plan.h"
 #include "objects_host.h"
 #include "overlay_host.h"
@@ -273,6 +274,15 @@ struct Impl {
         }
         void release() { free_range(); h_rays.release(); h_t.release(); h_id.release(); if (pick) (void)hipFree(pick); pick = nullptr; drop_done(); }
     } layers;
+    /* path queries (clw_ext_cast_paths / clw_ext_pick_path; whitted_paths.inc): the buffers of the host-array entry point -- the rays as uploaded,
+     * the hits, the status bytes, the outgoing rays -- each grown to the largest size so far (DeviceGrow); that call waits for its own work.  A
+     * pick is the camera-ray kernel and the path kernel on a one-pixel range into `pick`: the ray, then 8 hits, the outgoing ray and the status
+     * byte's word.  The device entry point works on the caller's memory and owns nothing. */
+    struct Paths {
+        DeviceGrow rays, hits, status, next;
+        uint32_t* pick = nullptr;
+        void release() { rays.release(); hits.release(); status.release(); next.release(); if (pick) (void)hipFree(pick); pick = nullptr; }
+    } paths;
     /* prepared scene cache */
     const Buffer *prep_s = nullptr, *prep_p = nullptr, *prep_l = nullptr;
     uint32_t prep_ns = 0, prep_np = 0, prep_nl = 0;

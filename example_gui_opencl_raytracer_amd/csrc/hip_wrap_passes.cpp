@@ -1,6 +1,6 @@
 /*
  * hip_wrap_passes.cpp -- the passes beside the trace launch (include/hip_wrap_ext.h): the primary-hit pass and the pick, the selection
- * overlay, the visible-object table, ambient occlusion, the ray queries and the layered ray queries.  Same conventions as hip_wrap.cpp; the shared internals are
+ * overlay, the visible-object table, ambient occlusion, the ray queries, the layered ray queries and the path queries.  Same conventions as hip_wrap.cpp; the shared internals are
  * hip_wrap_impl.h's.
  */
 #include "hip_wrap_impl.h"
@@ -169,6 +169,28 @@ void launch_layers(Impl* I, const whitted_params& P, const wt_cast_class& cc, co
     const unsigned capacity = ((want == 4 || want == 8) && (uint32_t)want >= K) ? (unsigned)want : 0u;
     LaunchTimer tm(I, CLW_TIMING_LAYERS, timed);
     hipError_t e = WT_LAUNCH(I, cast_layers)(&P, cc.flags, cc.dyn_lds, rays, n, flags, K, capacity, t, id, I->stream);
+    if (e != hipSuccess) die("Couldn't run the kernel");
+    tm.done();
+}
+
+/* ---- path queries -------------------------------------------------------------------------------------------------------------------- */
+/* The scene side of a path query of n rays: a ray query's (cast_params), and the bound sphere and plane arrays themselves, from which
+ * wt_cast_paths reads the winner's material.  false as cast_params. */
+bool paths_params(cl_wrap* w, Impl* I, uint32_t n, whitted_params& P, wt_cast_class& cc) {
+    if (!cast_params(w, I, n, P, cc)) return false;
+    const int kid = raytracer_kernel(I);
+    Buffer* bs = (Buffer*)w->buffers[kid][1];
+    Buffer* bp = (Buffer*)w->buffers[kid][2];
+    ensure_allocated(I, bs); ensure_allocated(I, bp);
+    P.spheres_raw = (const uint8_t*)bs->dptr; P.planes_raw = (const uint8_t*)bp->dptr;
+    return true;
+}
+
+/* wt_cast_paths over device memory on the launch stream: bounces * n hits, n status bytes, n outgoing rays (next may be null) */
+void launch_paths(Impl* I, const whitted_params& P, const wt_cast_class& cc, const void* rays, uint32_t n, uint32_t flags, uint32_t bounces, void* hits,
+                  uint8_t* status, void* next, bool timed) {
+    LaunchTimer tm(I, CLW_TIMING_PATHS, timed);
+    hipError_t e = WT_LAUNCH(I, cast_paths)(&P, cc.flags, cc.dyn_lds, rays, n, flags, bounces, hits, status, next, I->stream);
     if (e != hipSuccess) die("Couldn't run the kernel");
     tm.done();
 }
@@ -635,6 +657,69 @@ int clw_ext_pick_layers(cl_wrap* wrap, uint32_t x, uint32_t y, uint32_t flags, u
     if (hipMemcpyAsync(h, dt, sizeof h, hipMemcpyDeviceToHost, I->stream) != hipSuccess) die("Failed to transfer device memory to host");
     finish(I);
     for (uint32_t k = 0; k < K; k++) { memcpy(&out[k].t, &h[k], 4); out[k].id = h[WT_LAYERS_MAX + k]; }
+    return 1;
+}
+
+uint32_t clw_ext_cast_paths(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uint32_t flags, uint32_t bounces, clw_hit* hits, uint8_t* status,
+                            clw_ray* next) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    if (!wt_paths_check(n, flags, bounces) || !rays || !hits || !status) return 0;
+    whitted_params P{};
+    wt_cast_class cc;
+    if (!paths_params(wrap, I, n, P, cc)) return 0;
+    Impl::Paths& B = I->paths;
+    const size_t ray_bytes = (size_t)n * sizeof(clw_ray), hit_bytes = (size_t)bounces * n * sizeof(clw_hit);
+    void* d_rays = B.rays.reserve(ray_bytes);
+    void* d_hits = B.hits.reserve(hit_bytes);
+    uint8_t* d_status = (uint8_t*)B.status.reserve(n);
+    void* d_next = next ? B.next.reserve(ray_bytes) : nullptr;
+    HIP_OK(hipMemcpyAsync(d_rays, rays, ray_bytes, hipMemcpyHostToDevice, I->stream), "Couldn't transfer the data from host to the device");
+    launch_paths(I, P, cc, d_rays, n, flags, bounces, d_hits, d_status, d_next, true);
+    HIP_OK(hipMemcpyAsync(hits, d_hits, hit_bytes, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    HIP_OK(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    if (next) HIP_OK(hipMemcpyAsync(next, d_next, ray_bytes, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    finish(I);
+    return n;
+}
+
+uint32_t clw_ext_cast_paths_device(cl_wrap* wrap, const void* d_rays, uint32_t n, uint32_t flags, uint32_t bounces, void* d_hits, void* d_status,
+                                   void* d_next) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    if (!wt_paths_check(n, flags, bounces) || !d_rays || !d_hits || !d_status) return 0;
+    whitted_params P{};
+    wt_cast_class cc;
+    if (!paths_params(wrap, I, n, P, cc)) return 0;
+    launch_paths(I, P, cc, d_rays, n, flags, bounces, d_hits, (uint8_t*)d_status, d_next, true);
+    return n;
+}
+
+int clw_ext_pick_path(cl_wrap* wrap, uint32_t x, uint32_t y, uint32_t bounces, uint32_t flags, clw_hit* out_hits, uint8_t* out_status) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    CameraRange R;
+    if (!out_hits || !out_status || !wt_paths_check(1u, flags, bounces) || !camera_range(wrap, I, R)) return 0;
+    if (x >= R.P.width || y >= R.P.height) return 0;
+    const uint64_t pixel = (uint64_t)y * R.P.width + x;      /* is the pixel one of the wrapper's work-items? */
+    if (pixel < R.P.id_offset || pixel - R.P.id_offset >= R.P.n_items) return 0;
+    whitted_params P{};
+    wt_cast_class cc;
+    if (!paths_params(wrap, I, 1u, P, cc)) return 0;
+    /* the camera-ray kernel on the one-pixel range [pixel, pixel + 1), then that ray's path */
+    R.P.id_offset = pixel; R.P.n_items = 1; R.P.tiled = 0; R.P.rows = 0; R.P.row_offset = y;
+    Impl::Paths& B = I->paths;
+    constexpr uint32_t RAY_WORDS = sizeof(clw_ray) / 4, HIT_WORDS = sizeof(clw_hit) / 4, WORDS = RAY_WORDS + WT_PATHS_MAX * HIT_WORDS + 1;
+    if (!B.pick) HIP_OK(hipMalloc((void**)&B.pick, WORDS * 4), "Couldn't allocate device memory");
+    uint32_t* d_hits = B.pick + RAY_WORDS;
+    uint32_t* d_status = d_hits + WT_PATHS_MAX * HIT_WORDS;
+    launch_camera_rays(I, R, B.pick, false);
+    launch_paths(I, P, cc, B.pick, 1u, flags, bounces, d_hits, (uint8_t*)d_status, nullptr, false);      /* (n = 1: segment k is record k) */
+    uint32_t h[WT_PATHS_MAX * HIT_WORDS + 1];
+    if (hipMemcpyAsync(h, d_hits, sizeof h, hipMemcpyDeviceToHost, I->stream) != hipSuccess) die("Failed to transfer device memory to host");
+    finish(I);
+    memcpy(out_hits, h, (size_t)bounces * sizeof(clw_hit));
+    *out_status = (uint8_t)(h[WT_PATHS_MAX * HIT_WORDS] & 0xFFu);      /* (the byte the kernel wrote: the word's lowest) */
     return 1;
 }
 

@@ -1,6 +1,6 @@
 /* whitted_launch.inc -- instantiates the kernels of whitted_trace.inc (and the primary-hit pass of whitted_gbuffer.inc, built from its
  * pieces, the camera models of whitted_projection.inc, the queries' shared scan of whitted_query.inc, the ambient occlusion pass of
- * whitted_ao.inc, the ray queries of whitted_cast.inc, the layered ray queries of whitted_layers.inc, the selection overlay of
+ * whitted_ao.inc, the ray queries of whitted_cast.inc, the layered ray queries of whitted_layers.inc, the path queries of whitted_paths.inc, the selection overlay of
  * whitted_overlay.inc, the visible-object table of whitted_objects.inc and the builder of the primary-ray cull table of whitted_cull.inc) in
  * namespace WT_NS and exports the C launchers the shim calls. */
 #include "bounce_cull_host.h"      /* (and through it primary_cull_host.h) */
@@ -12,6 +12,7 @@ namespace WT_NS {
 #include "whitted_ao.inc"
 #include "whitted_cast.inc"
 #include "whitted_layers.inc"
+#include "whitted_paths.inc"
 #include "whitted_overlay.inc"
 #include "whitted_objects.inc"
 #include "whitted_cull.inc"
@@ -320,6 +321,22 @@ WT_LAUNCHER(cast_layers)(const whitted_params* P, int flags, size_t dyn_lds, con
     const dim3 g((n + 63u) / 64u), block(WT_BLOCK);
     if (capacity == 4u) WT_LAUNCH_FLAVOUR(wt_cast_layers, WT_TAIL(4), flags, g, block, 0, dyn_lds, 0, s, *P, A);
     else WT_LAUNCH_FLAVOUR(wt_cast_layers, WT_TAIL(8), flags, g, block, 0, dyn_lds, 0, s, *P, A);
+    return hipGetLastError();
+}
+
+/* path queries (whitted_paths.inc): wt_cast_paths over `n` rays (2 float4 each) on the device, one workgroup of one wave per 64 rays, geometry
+ * as the caller's plan chose it (launch_plan.c: wt_plan_cast -- flags as the gbuffer launcher); P carries the bound sphere and plane arrays
+ * (spheres_raw, planes_raw) the materials are read from.  `hits` receives bounces * n records of 2 float4, segment-major, `status` n bytes,
+ * `next` (may be null) n rays.  The caller has checked n, path_flags and bounces (csrc/paths_host.h: wt_paths_check) */
+WT_LAUNCHER(cast_paths)(const whitted_params* P, int flags, size_t dyn_lds, const void* rays, unsigned n, unsigned path_flags, unsigned bounces,
+                        void* hits, unsigned char* status, void* next, hipStream_t s) {
+    if (n == 0u || n >= (1u << 30) || !(path_flags & 7u) || (path_flags & ~63u) || bounces == 0u || bounces > 8u || !rays || !hits || !status ||
+        (P->ns > 0u && !P->spheres_raw) || (P->np > 0u && !P->planes_raw) || dyn_lds > 48u * 1024u)
+        return hipErrorInvalidValue;
+    WT_NS::wt_paths_args A = {};
+    A.rays = (const float4*)rays; A.hits = (float4*)hits; A.status = status; A.next = (float4*)next; A.n = n; A.flags = path_flags; A.bounces = bounces;
+    const dim3 g((n + 63u) / 64u), block(WT_BLOCK);
+    WT_LAUNCH_FLAVOUR(wt_cast_paths, /* no tail */, flags, g, block, 0, dyn_lds, 0, s, *P, A);
     return hipGetLastError();
 }
 

@@ -57,6 +57,11 @@ anything within ``tmax``.  Directions are not normalised: t is in units of their
 caller's rays, along every pixel's camera ray, or under one pixel (click again to select the object behind).  ``camera_rays()`` returns the
 launch camera's rays as query rays.  Nothing else the renderer holds is touched; not available with row bands.
 
+``cast_paths(origins, dirs, bounces, ...)`` / ``cast_paths_device(...)`` / ``pick_path(x, y)``: path queries (clw_ext_cast_paths) -- where a
+ray GOES: its hit, the reference's reflected (with ``transmit``, through glass: refracted) ray from there, that ray's hit, and so on for up
+to 8 segments in one launch; ``pick_path`` answers what a pixel shows and what is reflected in that.  Nothing else the renderer holds is
+touched; ``pick_path`` is not available with row bands.
+
 ``projection=...`` / ``set_projection(model, ...)`` / ``look_ortho`` / ``look_panorama``: the camera models beside the pinhole
 (clw_ext_set_projection) -- ``'ortho'``: parallel rays from the image plane, the top / front / side view of an editor; ``'equirect'``: a
 latitude-longitude panorama of up to 360 x 180 degrees around the camera origin.  ``render()``, ``read_rays()``, ``gbuffer()``, ``pick``,
@@ -376,6 +381,45 @@ class Renderer:
         if got is None:
             return None
         return [api.id_entry(e["id"], depth=np.float32(e["t"])) for e in got if int(e["id"]) != api.ID_NONE]
+
+    # ---- path queries
+    def cast_paths(self, origins, dirs, bounces: int = 4, transmit: bool = False, all_surfaces: bool = False, tmax=np.inf, ignore=None,
+                   kinds=("sphere", "plane", "light"), opaque_only: bool = False) -> dict:
+        """Where every ray GOES (arguments as ``cast_rays``; dirs should be unit: the refraction rule takes them for unit) -> {"t", "id",
+        "normal", "point"} as [bounces, n] arrays (normal and point [bounces, n, 3]): segment 0 is ``cast_rays`` of the ray, segment k + 1 the
+        hit of the reference's reflected ray -- with `transmit`, through a transparent surface, of its refracted ray -- from segment k's hit;
+        "count" [n]: the hits recorded, entries past it are misses; "reason" [n]: api.PATH_REASON_BOUNCES (all `bounces` recorded),
+        _MISSED (the last ray met nothing) or _ENDED (on a light, or on a surface that is neither reflective, dielectric nor transparent --
+        `all_surfaces` reflects off those too); "next" api.RAY_QUERY [n]: the ray the path would go on with (after _MISSED the ray that
+        missed: look the sky up with it; after _ENDED a zero direction).  One launch whatever `bounces` (1..8) is; tmax bounds each segment."""
+        got = self.w.cast_paths(api.make_rays(origins, dirs, tmax, ignore), api.path_flags(kinds, opaque_only, transmit, all_surfaces), bounces)
+        if got is None:
+            raise RuntimeError("the path query was refused (at least one ray, at least one kind, bounces in 1..8?)")
+        return got
+
+    def cast_paths_device(self, rays_ptr: int, n: int, hits_ptr: int, status_ptr: int, next_ptr: int | None = None, bounces: int = 4,
+                          transmit: bool = False, all_surfaces: bool = False, kinds=("sphere", "plane", "light"), opaque_only: bool = False) -> int:
+        """The path query over the caller's device memory, by integer device address (``tensor.data_ptr()``): n api.RAY_QUERY records in,
+        bounces * n api.HIT records (segment-major), n status bytes and, if `next_ptr` is given, n api.RAY_QUERY records out.  Launched on the
+        wrapper's stream (``w.set_stream``) without waiting -> n."""
+        got = self.w.cast_paths_device(rays_ptr, n, api.path_flags(kinds, opaque_only, transmit, all_surfaces), bounces, hits_ptr, status_ptr, next_ptr)
+        if got != n:
+            raise RuntimeError("the path query was refused (at least one ray, at least one kind, bounces in 1..8, the three addresses?)")
+        return got
+
+    def pick_path(self, x: int, y: int, bounces: int = 4, transmit: bool = False) -> list | None:
+        """What pixel (x, y) of the frame shows and what shows in THAT: the objects along the path of the pixel's camera ray -> a list of
+        {"id", "kind", "index", "depth", "point", "normal"} of at most `bounces` entries -- the first is what ``pick(x, y)`` answers (a light
+        behind a transparent sphere aside: the path meets the sphere), the second the object reflected in it (with `transmit`: seen through
+        it), ...; depth is the segment's t, point the point shading uses (moved by EPSILON along the normal, where the next segment starts).
+        Empty where the ray meets nothing; None when the pixel is not one of this renderer's rows (or no camera has been set)."""
+        self._latch_camera()
+        got = self.w.pick_path(x, y, bounces, api.path_flags(transmit=transmit))
+        if got is None:
+            return None
+        hits, status = got
+        return [api.id_entry(h["id"], depth=np.float32(h["t"]), point=h["point"] + h["normal"] * api.PATH_EPSILON, normal=h["normal"].copy())
+                for h in hits[:status & 15]]
 
     # ---- the visible-object table
     def objects(self, rect=None) -> np.ndarray:

@@ -659,6 +659,68 @@ int      clw_ext_pick_layers(cl_wrap* wrap, uint32_t x, uint32_t y, uint32_t fla
 #define CLW_TIMING_LAYERS  0x4C415952u
 #define CLW_TIMING_CAMRAYS 0x43524159u
 
+/* Path queries: where a ray GOES -- what shows in a mirror, what a glass sphere refracts into view, where a beam ends after four bounces -- in
+ * ONE launch, where hits read back, a bounce step and another cast cost a launch per bounce and a caller's own copy of the reference's
+ * refraction rule.  clw_host_cast_paths is THE definition; the device pass (wt_cast_paths: csrc/whitted_paths.inc) equals it bit for bit in both
+ * builds.  The arithmetic regime is the ray queries': float32, one rounding per operation, never fused, IEEE square root and divide, dot products
+ * left to right.  Rays, the kinds that take part, `ignore`, CLW_CAST_OPAQUE and the tests are those of clw_host_cast_rays above.
+ * Per ray, a path of up to B = `bounces` (1..8) segments; the path's refractive index n1 starts at 1 (the reference's DEFAULT_N).  Segment k:
+ *   - THE HIT of segment k is exactly what clw_host_cast_rays answers for the segment's ray {origin, tmax, dir, ignore}: segment 0 is the
+ *     caller's ray as given (its direction NOT normalised, its own `ignore`); every later segment has the path's outgoing ray, the caller's
+ *     tmax and ignore = CLW_ID_NONE.  tmax bounds every segment on its own.
+ *   - A miss ends the path (reason 1); it is not recorded.  A hit is recorded: count = k + 1.
+ *   - A light that is hit (kind 2) ends the path (reason 2).
+ *   - The winner's material is read from its 96-byte record: the words transperent, dielectric (u32), n, reflectivity (f32) at byte 64.  Unless
+ *     CLW_PATH_ALL_SURFACES is set, a surface with reflectivity == 0 && !dielectric && !transperent ends the path (reason 2): the reference sends
+ *     nothing on from it.
+ *   - The outgoing ray is the reference's (raytracing.cl:139-179), operation for operation, with N = the hit's normal, D = the segment's
+ *     direction and P = point + N * EPSILON per component (EPSILON = 0.001f; the product, then the sum -- the point shading uses):
+ *       reflect(D, N) = D + N * (2 * c), c = -(N.D) -- every path continues so unless it is transmitted: origin = P, dir = reflect(D, N).
+ *       With CLW_PATH_TRANSMIT and transperent != 0: n2 = (n1 == 1) ? material n : 1; if n1 < n2 the origin is P - N * (2 * EPSILON) (inside
+ *       the surface), otherwise N is negated and the origin stays P; with e = n1 / n2, c = -(N.D), s = e * e * (1 - c * c): s > 1 gives a NaN
+ *       direction, else dir = D * e + N * (e * c - sqrtf(1 - s)); the path's n1 becomes n2.  A direction whose x is NaN (total internal
+ *       reflection) falls back to the reflected ray from P with n1 unchanged: that is where the reference's light goes.
+ *     refract assumes a UNIT direction, as in the reference; nothing here normalises one.
+ *   - After segment B - 1 the path ends with reason 0.
+ * Output: hits[k * n + i] = the hit of segment k of ray i (layer-major as the layered query); entries from `count` on hold the miss record of
+ * clw_host_cast_rays {+inf, CLW_ID_NONE, 0, 0}.  status[i] = count | reason << 4 (CLW_PATH_COUNT / CLW_PATH_REASON).  next (optional, n
+ * records): after reason 0 the outgoing ray of the last hit, after reason 1 the ray that missed (its `ignore` included) -- a caller can look the
+ * sky up --, after reason 2 {P of the last hit, tmax, dir = 0, CLW_ID_NONE}: a zero direction meets nothing.
+ * Refused (0 returned, nothing written): whatever clw_host_cast_rays refuses for flags & (CLW_CAST_KINDS | CLW_CAST_OPAQUE); a flag bit beside
+ * those and the two below; bounces == 0 or > 8; a NULL hits or status. */
+#define CLW_PATH_TRANSMIT     16u   /* a transparent surface is passed through (refracted), not reflected off */
+#define CLW_PATH_ALL_SURFACES 32u   /* a diffuse surface reflects the path on instead of ending it */
+#define CLW_PATH_MAX_BOUNCES  8u
+#define CLW_PATH_REASON_BOUNCES 0u  /* `bounces` segments recorded */
+#define CLW_PATH_REASON_MISSED  1u  /* the last segment met nothing */
+#define CLW_PATH_REASON_ENDED   2u  /* the last hit was a light, or a surface that sends nothing on */
+#define CLW_PATH_COUNT(status)  ((status) & 15u)
+#define CLW_PATH_REASON(status) ((status) >> 4)
+int clw_host_cast_paths(const clw_ray* rays, uint32_t n, uint32_t flags, uint32_t bounces, const void* spheres, uint32_t ns, const void* planes,
+                        uint32_t np, const void* lights, uint32_t nl, clw_hit* hits /* bounces * n */, uint8_t* status /* n */,
+                        clw_ray* next /* n, or NULL */);   /* 1 = done, 0 = refused */
+/* On the device, against the wrapper's bound scene, with the conventions of the clw_ext_cast_layers* calls: the scene is prepared if needed and
+ * read staged in LDS, from global memory or through the uniform grid as wt_plan_cast decides for the ray queries; the materials are read from
+ * the bound sphere and plane arrays themselves; 0 is returned and nothing launched for what the definition refuses and when no scene is bound.
+ * clw_ext_cast_paths takes HOST arrays (n rays; bounces * n hits; n bytes; n rays or NULL), waits and returns n; its staging buffers are
+ * allocated at first use, grown at need and freed by cl_wrap_release.  clw_ext_cast_paths_device takes the caller's DEVICE memory of the same
+ * sizes (d_next may be NULL), launches on the wrapper's stream -- the caller's after clw_ext_set_stream --, does not wait and returns n.
+ * clw_ext_pick_path: the camera-ray kernel on the one-pixel range of frame pixel (x, y) under the wrapper's camera model, then the path of that
+ * ray; out_hits[k], k < bounces, and *out_status as above.  1, or 0 as clw_ext_pick_layers (no latched camera, a pixel that is not one of the
+ * wrapper's work-items, row bands, a NULL output, refused flags or bounces, no scene bound).  It does not restart an accumulating view.
+ * All three leave alone the framebuffer, the buffers of clw_ext_render_gbuffer, the overlay, the object table, the AO pass, the ray queries and
+ * the layers, an accumulating view and its count, the tile order and clw_ext_last_trace_flags.  Launches are logged under CLW_TIMING_PATHS in
+ * clw_ext_timing_get (a pick's are not).
+ * Not built: per-ray flags; a bound on the total path length instead of the per-segment tmax; Schlick-weighted branching (a path follows one
+ * ray, the reference's trace follows both at a dielectric). */
+uint32_t clw_ext_cast_paths(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uint32_t flags, uint32_t bounces, clw_hit* hits, uint8_t* status,
+                            clw_ray* next);   /* host arrays; waits */
+uint32_t clw_ext_cast_paths_device(cl_wrap* wrap, const void* d_rays, uint32_t n, uint32_t flags, uint32_t bounces, void* d_hits, void* d_status,
+                                   void* d_next);   /* no wait */
+int      clw_ext_pick_path(cl_wrap* wrap, uint32_t x, uint32_t y, uint32_t bounces, uint32_t flags, clw_hit* out_hits /* bounces */,
+                           uint8_t* out_status);
+#define CLW_TIMING_PATHS 0x50415448u
+
 /* Work counters of the trace kernel.  enable=1 selects the counting build of the kernel
  * for subsequent launches (slower); read returns and clears
  *   out[0] path segments  out[1] shadow rays  out[2] light probes  out[3] skybox fetches
