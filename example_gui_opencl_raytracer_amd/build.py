@@ -25,7 +25,7 @@ HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc
 CC = os.environ.get("CC") or "gcc"
 
 DEVICE_DEPS = ["whitted_trace.inc", "whitted_hit.inc", "whitted_shade.inc", "whitted_bounce.inc", "whitted_pop.inc", "whitted_tpt.inc", "whitted_terms.inc",
-               "whitted_gbuffer.inc", "whitted_projection.inc", "whitted_query.inc", "whitted_ao.inc", "whitted_cast.inc", "whitted_layers.inc", "whitted_paths.inc", "whitted_overlay.inc", "whitted_objects.inc", "whitted_cull.inc", "primary_cull_host.h", "bounce_cull_host.h", "whitted_launch.inc", "whitted_launch.h", "whitted_params.h",
+               "whitted_gbuffer.inc", "whitted_projection.inc", "whitted_query.inc", "whitted_ao.inc", "whitted_cast.inc", "whitted_layers.inc", "whitted_paths.inc", "whitted_overlay.inc", "whitted_objects.inc", "whitted_cull.inc", "primary_cull_host.h", "bounce_cull_host.h", "ref_tests.h", "whitted_launch.inc", "whitted_launch.h", "whitted_params.h",
                "projection_host.h"]
 SHIM_FLAGS = ["-O2", "-std=c++17", "-Wall"]
 SHIM_DEPS = ["hip_wrap_impl.h", "whitted_params.h", "whitted_launch.h", "launch_plan.h", "scene_prep.h", "ao_host.h", "cast_host.h", "layers_host.h", "paths_host.h", "overlay_host.h", "objects_host.h", "projection_host.h",
@@ -58,7 +58,7 @@ UNITS = [
     ("bounce_cull_host.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra", "-D_DEFAULT_SOURCE"],
      ["bounce_cull_host.h", "primary_cull_host.h", "scene_prep.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
     ("projection_host.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra", "-D_DEFAULT_SOURCE"],
-     ["projection_host.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
+     ["projection_host.h", "ref_tests.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
     ("launch_plan.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra"],
      ["launch_plan.h", "whitted_params.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
     ("host_camera.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra", "-D_DEFAULT_SOURCE"],

@@ -1,7 +1,8 @@
 /* ao_host.c -- THE definition of the ambient occlusion pass (include/hip_wrap_ext.h: clw_host_ao_dirs, clw_host_ao_open, clw_host_ao_resolve):
  * the device pass (wt_ao_trace, wt_ao_resolve: whitted_ao.inc) is held to it bit for bit.  Written for reading, not for speed: every pixel on
- * its own, every ray against every primitive, the rules in the header's order.  Built with -ffp-contract=off: every float32 operation below
- * is rounded once. */
+ * its own, every ray against every primitive, the rules in the header's order.  The arithmetic -- the two hit tests, the basis of a normal,
+ * a ray's direction, the integers of the resolve -- is ref_tests.h, the one text the device pass is compiled from too.  Built with
+ * -ffp-contract=off: every float32 operation is rounded once. */
 #include "ao_host.h"
 
 #include <math.h>
@@ -45,7 +46,6 @@ int clw_host_ao_dirs(uint32_t K, float* dirs4) {
 }
 
 /* ---- (b) the open rays of every pixel ----------------------------------------------------------------------------------------------- */
-/* the two hit tests: ref_tests.h (ref_sphere, ref_plane), the one copy */
 int clw_host_ao_open(const float* point, const float* normal, const uint32_t* ids, uint32_t width, uint32_t rows, uint32_t first_row,
                      const void* spheres, uint32_t ns, const void* planes, uint32_t np, const clw_ao* ao, const float* dirs4,
                      uint8_t* open_u8) {
@@ -66,25 +66,20 @@ int clw_host_ao_open(const float* point, const float* normal, const uint32_t* id
             const size_t p = (size_t)y * width + x;
             const uint32_t id = ids[p], kind = id >> 30, index = id & 0x3FFFFFFFu;
             if (!((kind == 0u && index < ns) || (kind == 1u && index < np))) { open_u8[p] = (uint8_t)K; continue; }
-            const float* o = point + 3 * p;
-            const float* n = normal + 3 * p;
-            const float sg = copysignf(1.0f, n[2]);
-            const float a = -1.0f / (sg + n[2]);
-            const float b = n[0] * n[1] * a;
-            const float t[3] = {1.0f + sg * n[0] * n[0] * a, sg * b, -sg * n[0]};
-            const float u[3] = {b, sg + n[1] * n[1] * a, -n[1]};
+            const ref_v3 o = ref_ld(point + 3 * p), n = ref_ld(normal + 3 * p);
+            ref_v3 t, u;
+            ref_ao_basis(n, &t, &u);
             const uint32_t j = (x & 3u) | (((first_row + y) & 3u) << 2);
             uint32_t open = 0u;
             for (uint32_t i = 0; i < K; i++) {
                 const float* l = dirs4 + 4 * ((size_t)j * K + i);
-                float d[3];
-                for (int k = 0; k < 3; k++) d[k] = t[k] * l[0] + u[k] * l[1] + n[k] * l[2];
+                const ref_v3 d = ref_ao_dir(t, u, n, l[0], l[1], l[2]);
                 int occluded = 0;
                 float th;
                 for (uint32_t s = 0; s < ns; s++)
-                    if (ref_sphere(o, d, geom + 4 * (size_t)s, &th) && th <= radius) occluded = 1;
+                    if (ref_sphere(o, d, ref_ld(geom + 4 * (size_t)s), geom[4 * (size_t)s + 3], &th) && th <= radius) occluded = 1;
                 for (uint32_t q = 0; q < np; q++)
-                    if (ref_plane(o, d, pl + 8 * (size_t)q, pl + 8 * (size_t)q + 4, &th) && th <= radius) occluded = 1;
+                    if (ref_plane(o, d, ref_ld(pl + 8 * (size_t)q), ref_ld(pl + 8 * (size_t)q + 4), &th) && th <= radius) occluded = 1;
                 if (!occluded) open++;
             }
             open_u8[p] = (uint8_t)open;
@@ -114,14 +109,8 @@ int clw_host_ao_resolve(const uint8_t* open_u8, const uint32_t* ids, const uint3
                         if (ids[q] == ids[p]) { S += open_u8[q]; m++; }
                     }
             }
-            const uint32_t v = (255u * S + ((m * K) >> 1)) / (m * K);
-            const uint32_t vs = 255u - (((255u - v) * ao->strength + 128u) >> 8);
-            uint32_t c = vs * 0x010101u;
-            if (ao->flags & CLW_AO_COMPOSE) {
-                c = 0u;
-                for (int shift = 0; shift < 24; shift += 8) c |= ((((frame[p] >> shift) & 255u) * vs + 127u) / 255u) << shift;
-            }
-            out_u32[p] = c;
+            const uint32_t vs = ref_ao_level(S, m, K, ao->strength);
+            out_u32[p] = (ao->flags & CLW_AO_COMPOSE) ? ref_ao_compose(frame[p], vs) : ref_ao_grey(vs);
         }
     }
     return 1;

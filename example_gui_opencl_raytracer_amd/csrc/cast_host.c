@@ -1,8 +1,8 @@
 /* cast_host.c -- THE definition of the ray queries (include/hip_wrap_ext.h: clw_host_cast_rays, clw_host_occluded_rays): the device pass
  * (wt_cast: whitted_cast.inc) is held to it bit for bit.  Written for reading, not for speed: every ray on its own against every primitive that
  * takes part, the rules in the header's order.  wt_cast_enumerate is the one copy of that rule: the queries here and the layered ones
- * (layers_host.c) differ only in what they do with a candidate.  Built with -ffp-contract=off: every float32 operation below, and of the two
- * hit tests (ref_tests.h), is rounded once. */
+ * (layers_host.c) differ only in what they do with a candidate.  The arithmetic -- the two hit tests, the winner's point and normal -- is
+ * ref_tests.h, the one text the device pass is compiled from too.  Built with -ffp-contract=off: every float32 operation is rounded once. */
 #include "cast_host.h"
 
 #include <math.h>
@@ -30,8 +30,7 @@ int wt_cast_enumerate(const clw_ray* rays, uint32_t n, uint32_t flags, const voi
     wprep_build((const uint8_t*)spheres, ns, (const uint8_t*)planes, np, (const uint8_t*)lights, nl, geom, ptex);
     const wt_cast_geom g = {geom, geom + 4 * (size_t)ns, geom + 4 * (size_t)ns + 8 * (size_t)np};
     for (uint32_t k = 0; k < n; k++) {
-        const float* o = rays[k].origin;
-        const float* d = rays[k].dir;
+        const ref_v3 o = ref_ld(rays[k].origin), d = ref_ld(rays[k].dir);
         const float tmax = rays[k].tmax;
         const uint32_t ignore = rays[k].ignore;
         float t;
@@ -40,17 +39,18 @@ int wt_cast_enumerate(const clw_ray* rays, uint32_t n, uint32_t flags, const voi
             for (uint32_t i = 0; i < ns; i++) {
                 const float* s = g.spheres + 4 * (size_t)i;
                 if (i == ignore || ((flags & CLW_CAST_OPAQUE) && sign_bit(s[3]))) continue;
-                if (ref_sphere(o, d, s, &t) && t <= tmax) v->take(v->ctx, t, i);
+                if (ref_sphere(o, d, ref_ld(s), s[3], &t) && t <= tmax) v->take(v->ctx, t, i);
             }
         if (flags & CLW_CAST_PLANES)
             for (uint32_t i = 0; i < np; i++) {
                 if (((1u << 30) | i) == ignore) continue;
-                if (ref_plane(o, d, g.planes + 8 * (size_t)i, g.planes + 8 * (size_t)i + 4, &t) && t <= tmax) v->take(v->ctx, t, (1u << 30) | i);
+                if (ref_plane(o, d, ref_ld(g.planes + 8 * (size_t)i), ref_ld(g.planes + 8 * (size_t)i + 4), &t) && t <= tmax) v->take(v->ctx, t, (1u << 30) | i);
             }
         if (flags & CLW_CAST_LIGHTS)
             for (uint32_t i = 0; i < nl; i++) {
                 if (((2u << 30) | i) == ignore) continue;
-                if (ref_sphere(o, d, g.lights + 8 * (size_t)i, &t) && t <= tmax) v->take(v->ctx, t, (2u << 30) | i);
+                const float* l = g.lights + 8 * (size_t)i;
+                if (ref_sphere(o, d, ref_ld(l), l[3], &t) && t <= tmax) v->take(v->ctx, t, (2u << 30) | i);
             }
         v->ray_done(v->ctx, k, rays + k, &g);
     }
@@ -84,16 +84,12 @@ static void nearest_done(void* ctx, uint32_t k, const clw_ray* ray, const wt_cas
     h->id = best;
     for (int a = 0; a < 3; a++) { h->normal[a] = 0.0f; h->point[a] = 0.0f; }
     if (best == CLW_ID_NONE) return;
-    for (int a = 0; a < 3; a++) h->point[a] = ray->dir[a] * tbest + ray->origin[a];
     const uint32_t kind = best >> 30, index = best & 0x3FFFFFFFu;
-    if (kind == 1u) {
-        for (int a = 0; a < 3; a++) h->normal[a] = g->planes[8 * (size_t)index + a];
-    } else {
-        const float* c = kind == 0u ? g->spheres + 4 * (size_t)index : g->lights + 8 * (size_t)index;
-        const float w[3] = {h->point[0] - c[0], h->point[1] - c[1], h->point[2] - c[2]};
-        const float len = sqrtf(dot3(w, w));
-        for (int a = 0; a < 3; a++) h->normal[a] = w[a] / len;
-    }
+    /* the plane's normal, or the centre of the sphere or light */
+    const float* w = kind == 1u ? g->planes + 8 * (size_t)index : kind == 0u ? g->spheres + 4 * (size_t)index : g->lights + 8 * (size_t)index;
+    const ref_v3 point = ref_hit_point(ref_ld(ray->origin), ref_ld(ray->dir), tbest);
+    ref_st(h->point, point);
+    ref_st(h->normal, ref_hit_normal(kind == 1u, point, ref_ld(w)));
 }
 
 static int cast(const clw_ray* rays, uint32_t n, uint32_t flags, const void* spheres, uint32_t ns, const void* planes, uint32_t np,

@@ -4,14 +4,17 @@
  *
  * A projection is resolved ONCE per (camera, frame, projection) into scalar terms and, for the panorama, two small tables; everything
  * transcendental or double happens there, on the host.  The ray of a pixel is then a handful of float operations, one rounding each, no
- * contraction, IEEE square root and divide -- wt_projection_ray here, wt_proj_ray in csrc/whitted_projection.inc: the same operations in
- * the same order on the same terms, so host and device agree to the bit.  Built with -ffp-contract=off, like host_camera.c.
+ * contraction, IEEE square root and divide -- wt_projection_ray here, wt_proj_ray in csrc/whitted_projection.inc: each with its own table
+ * addressing around the one text of the arithmetic (ref_tests.h), so host and device agree to the bit.  Built with -ffp-contract=off, like
+ * host_camera.c.
  */
 #include "projection_host.h"
 
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include "ref_tests.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -128,23 +131,21 @@ int clw_host_projection_tables(const clw_camera* cam, const clw_projection* proj
 }
 
 void wt_projection_ray(const wt_projection* T, const float* col, const float* row, uint32_t x, uint32_t y, float o[3], float d[3]) {
-    float v[3];
+    ref_v3 v;
     if (T->model == CLW_PROJ_EQUIRECT) {
-        const float* c = col + 4 * (size_t)x;
         const float* r = row + 4 * (size_t)y;
-        for (int k = 0; k < 3; k++) { v[k] = c[k] * r[0] + r[1 + k]; o[k] = T->origin[k]; }
+        v = ref_madd(ref_ld(col + 4 * (size_t)x), r[0], ref_ld(r + 1));
     } else {
         /* the image-plane vector of the pinhole raygen (raygen.cl:13-17), the operations of wt_primary_dir_xy before its sqrtf, in that order */
-        const float w = (float)x, h = (float)y;
-        for (int k = 0; k < 3; k++) v[k] = T->corner[k] + T->right[k] * T->w_factor * w - T->up[k] * T->h_factor * h;
+        v = ref_image_plane(ref_ld(T->corner), ref_ld(T->right), ref_ld(T->up), T->w_factor, T->h_factor, x, y);
         if (T->model == CLW_PROJ_ORTHO) {      /* parallel rays from the image plane: it is the near plane */
-            for (int k = 0; k < 3; k++) { o[k] = T->origin[k] + v[k]; d[k] = T->dir[k]; }
+            ref_st(o, ref_add(ref_ld(T->origin), v));
+            ref_st(d, ref_ld(T->dir));
             return;
         }
-        for (int k = 0; k < 3; k++) o[k] = T->origin[k];
     }
-    const float len = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    for (int k = 0; k < 3; k++) d[k] = v[k] / len;
+    ref_st(o, ref_ld(T->origin));
+    ref_st(d, ref_normalize(v));
 }
 
 int clw_host_projection_rays(const clw_camera* cam, const clw_projection* proj, uint64_t id_begin, uint64_t id_end, float* rays16) {

@@ -1,8 +1,8 @@
 /* whitted_ao.inc -- ray-traced ambient occlusion over the primary-hit buffers (hip_wrap_ext.h: clw_ao, clw_ext_render_ao): wt_ao_trace counts,
  * for every pixel of a range of whole rows, how many of K short any-hit rays over the hemisphere of its normal stay open; wt_ao_resolve turns
  * the counts into pixels.  Included by whitted_launch.inc behind whitted_query.inc, so both exist in the fast and the strict unit.
- * csrc/ao_host.c is their definition: the arithmetic below is that file's, operation for operation -- wt_gb_ref_dot's sums, IEEE square root
- * and divide, no fused operation (`#pragma clang fp contract(off)` wherever a float is computed) -- so both builds give the host's bits.
+ * csrc/ao_host.c is their definition: its arithmetic and this file's are csrc/ref_tests.h, the one text both are compiled from -- IEEE square
+ * root and divide, no fused operation -- so both builds give the host's bits.
  *
  * wt_ao_trace: one wave = one 8 x 8 tile = one workgroup, tiles row-major over the range (8 x 8 holds each of the 16 interleave patterns four
  * times).  The scene is staged by wt_stage_scene or read from global memory as in wt_gbuffer; the 16 K directions of the table follow it in LDS
@@ -34,18 +34,14 @@ struct wt_ao_args {
     float radius;               /* > 0, +inf = unlimited */
 };
 
-/* the definition's sphere test with the invariants already taken (whitted_query.inc: wt_query_sphere, the one copy): is it met at t <= radius? */
-__device__ __forceinline__ bool wt_ao_sphere(f3 v, float cc, f3 d, float a, float radius) {
+/* the definition's two tests with the origin's invariants already taken (ref_tests.h: ref_sphere_query, ref_plane_rest): met at t <= radius? */
+__device__ __forceinline__ bool wt_ao_sphere(ref_v3 v, float cc, f3 d, float a, float radius) {
     float t;
-    return wt_query_sphere(v, cc, d, a, radius, t);
+    return ref_sphere_query(v, cc, rv3(d), a, radius, &t);
 }
-
-/* the definition's plane test, num = (p0 - o).n taken: the operations of wt_gb_ref_plane in its order */
-__device__ __forceinline__ bool wt_ao_plane(float num, f3 nn, f3 d, float radius) {
-#pragma clang fp contract(off)
-    const float b = wt_gb_ref_dot(d, nn);
-    const float t = num / b;
-    return !(b == 0) && !(t <= 0) && t <= radius;
+__device__ __forceinline__ bool wt_ao_plane(float num, float4 pn, f3 d, float radius) {
+    float t;
+    return ref_plane_rest(num, rv3(pn), rv3(d), &t) && t <= radius;
 }
 
 /* is some sphere met at t <= radius?  The walk of wt_grid_occluded, ended where the cells lie beyond `radius`: a sphere met at t <= radius is
@@ -55,8 +51,8 @@ __device__ __forceinline__ bool wt_ao_grid_spheres(const whitted_params& P, f3 o
         bool hit = false;
         for (unsigned i = 0; i < P.ns; i++) {
             const float4 s = ((const float4*)P.geom)[i];
-            const f3 v = o - mk3(s.x, s.y, s.z);
-            if (wt_ao_sphere(v, wt_gb_ref_dot(v, v) - fabsf(s.w), d, a, radius)) hit = true;
+            const ref_v3 v = ref_sub(rv3(o), rv3(s));
+            if (wt_ao_sphere(v, ref_sphere_cc(v, s.w), d, a, radius)) hit = true;
         }
         return hit;
     }
@@ -71,8 +67,8 @@ __device__ __forceinline__ bool wt_ao_grid_spheres(const whitted_params& P, f3 o
         if (more) nxt = wt_grid_range(P, wt_grid_cell(P, nw));           /* in flight while this cell is tested */
         for (unsigned k = cur.b; k < cur.e; k++) {
             const float4 s = ((const float4*)P.grid_geom)[k];
-            const f3 v = o - mk3(s.x, s.y, s.z);
-            if (wt_ao_sphere(v, wt_gb_ref_dot(v, v) - fabsf(s.w), d, a, radius)) return true;
+            const ref_v3 v = ref_sub(rv3(o), rv3(s));
+            if (wt_ao_sphere(v, ref_sphere_cc(v, s.w), d, a, radius)) return true;
         }
         if (!more) return false;
         w = nw; cur = nxt;
@@ -96,15 +92,8 @@ __global__ void __launch_bounds__(WT_BLOCK) wt_ao_trace(const whitted_params P, 
     const bool surface = valid && ((kind == 0u && index < P.ns) || (kind == 1u && index < P.np));
     const f3 o = mk3(A.point[3 * p], A.point[3 * p + 1], A.point[3 * p + 2]);
     const f3 n = mk3(A.normal[3 * p], A.normal[3 * p + 1], A.normal[3 * p + 2]);
-    f3 bt, bu;
-    {
-#pragma clang fp contract(off)
-        const float sgn = copysignf(1.0f, n.z);
-        const float a = -1.0f / (sgn + n.z);
-        const float b = n.x * n.y * a;
-        bt = mk3(1.0f + sgn * n.x * n.x * a, sgn * b, -sgn * n.x);
-        bu = mk3(b, sgn + n.y * n.y * a, -n.y);
-    }
+    ref_v3 bt, bu;
+    ref_ao_basis(rv3(n), &bt, &bu);
     const float4* ld = s_dirs + ((x & 3u) | (((A.first_row + y) & 3u) << 2)) * A.K;
     const float radius = A.radius;
     const unsigned g_pln = P.ns;
@@ -114,22 +103,16 @@ __global__ void __launch_bounds__(WT_BLOCK) wt_ao_trace(const whitted_params P, 
         /* a ray at a time: a walk shares nothing with the lane's other rays, and a batch's 32 registers are better left to the walk */
 #pragma unroll 1
         for (unsigned i = 0; i < A.K; i++) {
-            f3 d;
-            float a;
-            {
-#pragma clang fp contract(off)
-                const float4 l = ld[i];
-                d = mk3(bt.x * l.x + bu.x * l.y + n.x * l.z, bt.y * l.x + bu.y * l.y + n.y * l.z, bt.z * l.x + bu.z * l.y + n.z * l.z);
-                a = wt_gb_ref_dot(d, d);
-            }
+            const float4 l = ld[i];
+            const f3 d = fv3(ref_ao_dir(bt, bu, rv3(n), l.x, l.y, l.z));
+            const float a = wt_ref_dot(d, d);
             bool hit = false;
             if (surface) {
                 hit = wt_ao_grid_spheres(P, o, d, a, radius);
                 for (unsigned k = 0; k < P.np && !hit; k++) {
                     const float4 pn = ((const float4*)P.geom)[g_pln + 2 * k];
                     const float4 p0 = ((const float4*)P.geom)[g_pln + 2 * k + 1];
-                    const f3 nn = mk3(pn.x, pn.y, pn.z);
-                    hit = wt_ao_plane(wt_gb_ref_dot(mk3(p0.x, p0.y, p0.z) - o, nn), nn, d, radius);
+                    hit = wt_ao_plane(ref_plane_num(rv3(o), rv3(pn), rv3(p0)), pn, d, radius);
                 }
             }
             open += hit ? 0u : 1u;
@@ -142,10 +125,9 @@ __global__ void __launch_bounds__(WT_BLOCK) wt_ao_trace(const whitted_params P, 
         float amax = 0.0f;      /* the largest d.d of the batch (a NaN one is left out: such a ray is never occluded) */
 #pragma unroll
         for (int r = 0; r < WT_AO_BATCH; r++) {
-#pragma clang fp contract(off)
             const float4 l = ld[base + ((unsigned)r < nb ? (unsigned)r : 0u)];
-            d[r] = mk3(bt.x * l.x + bu.x * l.y + n.x * l.z, bt.y * l.x + bu.y * l.y + n.y * l.z, bt.z * l.x + bu.z * l.y + n.z * l.z);
-            a[r] = wt_gb_ref_dot(d[r], d[r]);
+            d[r] = fv3(ref_ao_dir(bt, bu, rv3(n), l.x, l.y, l.z));
+            a[r] = wt_ref_dot(d[r], d[r]);
             if ((unsigned)r < nb && a[r] > amax) amax = a[r];
         }
         unsigned live = surface ? (1u << nb) - 1u : 0u;      /* bit r: ray base + r is not occluded yet */
@@ -156,13 +138,8 @@ __global__ void __launch_bounds__(WT_BLOCK) wt_ao_trace(const whitted_params P, 
             for (unsigned i = 0; i < P.ns; i++) {
                 if (__builtin_amdgcn_ballot_w64(live != 0u) == 0ull) break;      /* nobody has an open ray left */
                 const float4 s = wt_geom<GEOM_LDS>(P, sg, i);
-                const f3 v = o - mk3(s.x, s.y, s.z);
-                float vv, cc;
-                {
-#pragma clang fp contract(off)
-                    vv = wt_gb_ref_dot(v, v);
-                    cc = vv - fabsf(s.w);
-                }
+                const ref_v3 v = ref_sub(rv3(o), rv3(s));
+                const float vv = ref_dot(v, v), cc = ref_sphere_cc(v, s.w);      /* (v.v is taken once: the same operations on the same words) */
                 /* The reach check: can a ray of this lane, of length <= radius, touch the sphere at all?  With r = the radius and |v| the
                  * distance of its centre, a ray that meets it does so no nearer than |v| - r, so it cannot when |v| - r > R.  The verdict
                  * skipped is the FLOAT test's, whose t carries rounding: v.v, v.d, d.d and v.v - r r are each within a few ulp of |v|^2
@@ -193,18 +170,17 @@ __global__ void __launch_bounds__(WT_BLOCK) wt_ao_trace(const whitted_params P, 
             if (__builtin_amdgcn_ballot_w64(live != 0u) == 0ull) break;
             const float4 pn = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * i);
             const float4 p0 = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * i + 1);
-            const f3 nn = mk3(pn.x, pn.y, pn.z);
-            const float num = wt_gb_ref_dot(mk3(p0.x, p0.y, p0.z) - o, nn);
+            const float num = ref_plane_num(rv3(o), rv3(pn), rv3(p0));
 #pragma unroll
             for (int r = 0; r < WT_AO_BATCH; r++)
-                if (((live >> r) & 1u) && wt_ao_plane(num, nn, d[r], radius)) live &= ~(1u << r);
+                if (((live >> r) & 1u) && wt_ao_plane(num, pn, d[r], radius)) live &= ~(1u << r);
         }
         open += (unsigned)__builtin_popcount(live);
     }
     if (valid) A.open[p] = (unsigned char)(surface ? open : A.K);
 }
 
-/* ---- counts -> pixels: integers only, the same bits in both units (csrc/ao_host.c: clw_host_ao_resolve) --------------------------------
+/* ---- counts -> pixels: integers only (ref_tests.h: ref_ao_level, _grey, _compose), as in csrc/ao_host.c: clw_host_ao_resolve --------------------------------
  * One work-item per pixel, a workgroup of 256 per tile of 32 x 8 pixels as the overlay's.  With FILTER the counts and ids of the tile and of
  * its halo -- 2 to the left and above, 1 to the right and below: 35 x 11 entries -- are staged in LDS, an absent pixel as WT_AO_ABSENT in the
  * count plane; a pixel then sums the entries of its 4 x 4 window that are present and carry its id.  Without it a pixel reads its own count. */
@@ -253,14 +229,6 @@ __global__ void __launch_bounds__(WT_AO_TILE_W * WT_AO_TILE_H) wt_ao_resolve(con
     } else {
         S = A.open[p]; m = 1u;
     }
-    const unsigned v = (255u * S + ((m * A.K) >> 1)) / (m * A.K);
-    const unsigned vs = 255u - (((255u - v) * A.strength + 128u) >> 8);
-    unsigned c = vs * 0x010101u;
-    if (A.compose) {
-        const unsigned f = A.frame[p];
-        c = 0u;
-#pragma unroll
-        for (int shift = 0; shift < 24; shift += 8) c |= ((((f >> shift) & 255u) * vs + 127u) / 255u) << shift;
-    }
-    A.out[p] = c;
+    const unsigned vs = ref_ao_level(S, m, A.K, A.strength);
+    A.out[p] = A.compose ? ref_ao_compose(A.frame[p], vs) : ref_ao_grey(vs);
 }

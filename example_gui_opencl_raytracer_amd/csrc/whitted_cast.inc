@@ -43,13 +43,22 @@ struct wt_sink_any {
     __device__ __forceinline__ bool grid_done(float) const { return false; }      /* (a walk that goes on has met nothing) */
 };
 
+/* the winner's point and normal (ref_tests.h: ref_hit_point, ref_hit_normal -- wt_gbuffer's, without the EPSILON offset): one fetch of the
+ * plane's normal or the centre of the sphere or light */
+template <bool GEOM_LDS>
+__device__ __forceinline__ void wt_query_winner(const whitted_params& P, const float4* sg, const wt_query_ray& r, float t, unsigned id, f3& ip, f3& nrm) {
+    const unsigned kind = id >> 30, index = id & 0x3FFFFFFFu;
+    const float4 g = wt_geom<GEOM_LDS>(P, sg, kind == 0u ? index : P.ns + 2 * index + (kind == 1u ? 0u : 2 * P.np));
+    ip = wt_ref_hit_point(r.o, r.d, t);
+    nrm = fv3(ref_hit_normal(kind == 1u, rv3(ip), rv3(g)));
+}
+
 template <bool GEOM_LDS, bool GRID, bool ANY>
 __global__ void __launch_bounds__(WT_BLOCK) wt_cast(const whitted_params P, const wt_cast_args A) {
     extern __shared__ float4 s_geom[];
     if (GEOM_LDS) wt_stage_scene(P, s_geom, threadIdx.x, WT_BLOCK);
     const float4* sg = s_geom;
     const unsigned lane = threadIdx.x & 63u;
-    const unsigned g_pln = P.ns, g_lgt = P.ns + 2 * P.np;
 
     for (unsigned bt = 0; bt < A.batches; bt++) {      /* (wave-uniform) */
         const unsigned base = (blockIdx.x * A.batches + bt) * 64u;      /* (the launcher keeps groups * batches * 64 below 2^31) */
@@ -64,17 +73,7 @@ __global__ void __launch_bounds__(WT_BLOCK) wt_cast(const whitted_params P, cons
         if constexpr (ANY) { A.blocked[k] = B.any ? 1 : 0; continue; }
         else {
             f3 ip = mk3(0, 0, 0), nrm = mk3(0, 0, 0);
-            if (B.id != WT_GB_ID_NONE) {      /* the winner's point and normal: wt_gbuffer's, without the EPSILON offset */
-                const unsigned kind = B.id >> 30, index = B.id & 0x3FFFFFFFu;
-                ip = wt_gb_ref_madd(r.d, B.t, r.o);
-                if (kind == 1u) {
-                    const float4 pn = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * index);
-                    nrm = mk3(pn.x, pn.y, pn.z);      /* never flipped toward the ray */
-                } else {
-                    const float4 s = wt_geom<GEOM_LDS>(P, sg, kind == 0u ? index : g_lgt + 2 * index);
-                    nrm = wt_gb_ref_normalize(ip - mk3(s.x, s.y, s.z));
-                }
-            }
+            if (B.id != WT_GB_ID_NONE) wt_query_winner<GEOM_LDS>(P, sg, r, B.t, B.id, ip, nrm);
             A.hits[2 * (size_t)k] = make_float4(B.t, __uint_as_float(B.id), nrm.x, nrm.y);
             A.hits[2 * (size_t)k + 1] = make_float4(nrm.z, ip.x, ip.y, ip.z);
         }

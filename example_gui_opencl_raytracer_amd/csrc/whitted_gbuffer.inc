@@ -9,7 +9,7 @@
  * skybox fetch, no random numbers, no tile costs.
  * WHICH primitive wins is decided by that search, in the build's own arithmetic: the pass names the object the trace launch of the same build
  * shades.  WHERE it is hit -- depth, point, normal, a light's colour -- is then evaluated once more for the winner alone in the reference's
- * arithmetic (wt_gb_ref_*: IEEE divide and square root, no fused operation), the same in both builds: D/4 = b b - c cancels near a silhouette
+ * arithmetic (csrc/ref_tests.h: IEEE divide and square root, no fused operation), the same in both builds: D/4 = b b - c cancels near a silhouette
  * and from afar, where the fast build's fused products move t by 1e-4 and more and a light's (1 / d) * d by an ulp, and a consumer of the buffers
  * (a focus distance, a denoiser's normals) should not see which build made them.  In the strict build these are the search's own values.
  * The pass sees the launch camera at pixel centres and the scene as it stands: no sample cameras, no sphere motion, no jitter, no seed.
@@ -32,41 +32,16 @@ struct wt_gbuffer_out {
     float* albedo;       /* 3 */
 };
 
-/* ---- the reference's arithmetic for ONE primitive (primitives.cl:170-215 as wt_sphere_* / wt_plane evaluate them in the strict build: b/2 and
- *      D/4, see whitted_trace.inc), spelled out so that the fast unit computes the same bits: both units are compiled without contraction and
- *      with correctly rounded divide and square root ---- */
-__device__ __forceinline__ float wt_gb_ref_dot(f3 a, f3 b) {
-#pragma clang fp contract(off)
-    return a.x * b.x + a.y * b.y + a.z * b.z;
-}
-__device__ __forceinline__ f3 wt_gb_ref_madd(f3 a, float s, f3 b) {      /* a * s + b */
-#pragma clang fp contract(off)
-    return mk3(a.x * s + b.x, a.y * s + b.y, a.z * s + b.z);
-}
-__device__ __forceinline__ f3 wt_gb_ref_normalize(f3 v) {
-#pragma clang fp contract(off)
-    const float len = sqrtf(wt_gb_ref_dot(v, v));
-    return mk3(v.x / len, v.y / len, v.z / len);
-}
-__device__ __forceinline__ bool wt_gb_ref_sphere(f3 o, f3 d, float4 s, float& t) {
-#pragma clang fp contract(off)
-    const float a = wt_gb_ref_dot(d, d);
-    const f3 v = o - mk3(s.x, s.y, s.z);
-    const float c = wt_gb_ref_dot(v, v) - fabsf(s.w);
-    const float b = wt_gb_ref_dot(v, d);
-    const float D = b * b + (-(a * c));
-    const float sD = sqrtf(D);
-    const float t0 = (-b - sD) / a;
-    t = (t0 < 0) ? (-b + sD) / a : t0;
-    return !(D < 0) && !(t <= 0);
-}
-__device__ __forceinline__ bool wt_gb_ref_plane(f3 o, f3 d, float4 n, float4 p0, float& t) {
-#pragma clang fp contract(off)
-    const float num = wt_gb_ref_dot(mk3(p0.x, p0.y, p0.z) - o, mk3(n.x, n.y, n.z));
-    const float b = wt_gb_ref_dot(d, mk3(n.x, n.y, n.z));
-    t = num / b;
-    return !(b == 0) && !(t <= 0);
-}
+/* ---- the reference's arithmetic (primitives.cl:170-215) is csrc/ref_tests.h, the one text the host definitions are compiled from too: both
+ *      units are compiled without contraction and with correctly rounded divide and square root, so the fast unit computes the same bits.
+ *      Here only the adapters between the kernels' f3 / float4 and its ref_v3: no arithmetic ---- */
+static_assert(REF_EPSILON == WT_EPSILON, "the point shading uses");
+__device__ __forceinline__ ref_v3 rv3(f3 a) { return ref_mk(a.x, a.y, a.z); }
+__device__ __forceinline__ ref_v3 rv3(float4 a) { return ref_mk(a.x, a.y, a.z); }
+__device__ __forceinline__ f3 fv3(ref_v3 a) { return mk3(a.x, a.y, a.z); }
+__device__ __forceinline__ float wt_ref_dot(f3 a, f3 b) { return ref_dot(rv3(a), rv3(b)); }
+__device__ __forceinline__ f3 wt_ref_hit_point(f3 o, f3 d, float t) { return fv3(ref_hit_point(rv3(o), rv3(d), t)); }
+__device__ __forceinline__ f3 wt_ref_hit_offset(f3 point, f3 n) { return fv3(ref_hit_offset(rv3(point), rv3(n))); }
 
 __device__ __forceinline__ void wt_gb_store3(float* __restrict__ p, unsigned item, f3 v) {
     if (p) { float* q = p + 3 * (size_t)item; q[0] = v.x; q[1] = v.y; q[2] = v.z; }
@@ -163,9 +138,9 @@ __global__ void __launch_bounds__(WT_BLOCK) wt_gbuffer(const whitted_params P, c
         const float4 l0 = wt_geom<GEOM_LDS>(P, sg, g_lgt + 2 * li);
         const float4 l1 = wt_geom<GEOM_LDS>(P, sg, g_lgt + 2 * li + 1);
         float tr;
-        if (wt_gb_ref_sphere(o, d, l0, tr)) tl = tr;
-        const f3 hp = wt_gb_ref_madd(d, tl, o);
-        const float dist = sqrtf(wt_gb_ref_dot(o - hp, o - hp));
+        if (ref_sphere(rv3(o), rv3(d), rv3(l0), l0.w, &tr)) tl = tr;
+        const f3 hp = wt_ref_hit_point(o, d, tl);
+        const float dist = ref_length(ref_sub(rv3(o), rv3(hp)));
         depth = tl; id = WT_GB_KIND_LIGHT | li;
         alb = mk3(l1.x, l1.y, l1.z) * (1 / dist * dist);      /* "(1/d*d)" = (1/d)*d, not inverse-square: kept (primitives.cl:287) */
     } else {
@@ -201,17 +176,17 @@ __global__ void __launch_bounds__(WT_BLOCK) wt_gbuffer(const whitted_params P, c
             float tr;
             if (prim < P.ns) {
                 const float4 s = wt_geom<GEOM_LDS>(P, sg, prim);
-                if (wt_gb_ref_sphere(o, d, s, tr)) tbest = tr;
-                ip = wt_gb_ref_madd(d, tbest, o);
-                nrm = wt_gb_ref_normalize(ip - mk3(s.x, s.y, s.z));
+                if (ref_sphere(rv3(o), rv3(d), rv3(s), s.w, &tr)) tbest = tr;
+                ip = wt_ref_hit_point(o, d, tbest);
+                nrm = fv3(ref_hit_normal(0, rv3(ip), rv3(s)));
                 id = prim;
             } else {
                 const unsigned pi = prim - P.ns;
                 const float4 n = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * pi);
                 const float4 p0 = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * pi + 1);
-                if (wt_gb_ref_plane(o, d, n, p0, tr)) tbest = tr;
-                ip = wt_gb_ref_madd(d, tbest, o);
-                nrm = mk3(n.x, n.y, n.z);                    /* never flipped toward the ray */
+                if (ref_plane(rv3(o), rv3(d), rv3(n), rv3(p0), &tr)) tbest = tr;
+                ip = wt_ref_hit_point(o, d, tbest);
+                nrm = fv3(ref_hit_normal(1, rv3(ip), rv3(n)));
                 id = WT_GB_KIND_PLANE | pi;
                 if (n.w != 0.0f && G.albedo) {               /* texture_id >= 0: the texel of the pre-offset point (primitives.cl:377) */
                     texpx = wt_plane_texel_fetch(P, pi, ip);
@@ -223,7 +198,7 @@ __global__ void __launch_bounds__(WT_BLOCK) wt_gbuffer(const whitted_params P, c
                 alb = textured ? wt_texel_rgb(texpx) : mk3(a_.x, a_.y, a_.z);
             }
             depth = tbest;
-            ip = wt_gb_ref_madd(nrm, WT_EPSILON, ip);        /* the point shading uses */
+            ip = wt_ref_hit_offset(ip, nrm);                 /* the point shading uses */
         }
     }
     if (G.depth) G.depth[item] = depth;

@@ -4,6 +4,7 @@
  * whitted_overlay.inc, the visible-object table of whitted_objects.inc and the builder of the primary-ray cull table of whitted_cull.inc) in
  * namespace WT_NS and exports the C launchers the shim calls. */
 #include "bounce_cull_host.h"      /* (and through it primary_cull_host.h) */
+#include "ref_tests.h"             /* the reference arithmetic of the passes beside the trace launch: one text, host and device */
 namespace WT_NS {
 #include "whitted_trace.inc"
 #include "whitted_gbuffer.inc"

@@ -2,36 +2,26 @@
  * and the equirectangular panorama.  Included by whitted_launch.inc behind whitted_gbuffer.inc, so it exists in the fast and the strict unit.
  * THE definition of a model's rays is the host's (projection_host.c: clw_host_projection_rays); the host resolves a projection once per
  * (camera, frame, projection) into the scalar terms of wt_projection and, for the panorama, a column and a row table -- every sine, cosine and
- * double operation happens there -- and wt_proj_ray below performs the float operations of wt_projection_ray on them, in the same order, one
- * rounding each (no contraction, IEEE square root and divide, in both units): host and device agree to the bit.
+ * double operation happens there -- and wt_proj_ray below performs on them the float operations wt_projection_ray performs, both compiled from
+ * the one text of csrc/ref_tests.h, one rounding each (no contraction, IEEE square root and divide, in both units): host and device agree to
+ * the bit.
  * A projected launch is never fused: wt_raygen_proj writes the 64-byte records the ray-buffer flavours (WT_F_RAYS) of wt_trace read, and the
  * primary-hit pass (wt_gbuffer) calls wt_proj_ray where it calls wt_primary_dir(_xy) for the pinhole.  The trace kernels know nothing of it. */
 
-/* the ray of pixel (x, y) of the frame: wt_projection_ray of projection_host.c, operation for operation (T.model != CLW_PROJ_PERSPECTIVE) */
+/* the ray of pixel (x, y) of the frame (T.model != CLW_PROJ_PERSPECTIVE): wt_projection_ray of projection_host.c with the device's table
+ * addressing, the arithmetic being the one text of both (ref_tests.h) */
 __device__ __forceinline__ void wt_proj_ray(const wt_projection& T, unsigned x, unsigned y, f3& o, f3& d) {
-#pragma clang fp contract(off)
-    float vx, vy, vz;
     if (T.model == CLW_PROJ_EQUIRECT) {
         /* (an index past a table cannot be: the shim sizes both for the frame the ids come from; the clamp keeps a stray id inside them) */
         const float4 c = ((const float4*)T.col)[x < T.width ? x : T.width - 1u];      /* coalesced along a row of the frame */
         const float4 r = ((const float4*)T.row)[y < T.height ? y : T.height - 1u];    /* one entry per lane; a block spans few rows */
-        vx = c.x * r.x + r.y;
-        vy = c.y * r.x + r.z;
-        vz = c.z * r.x + r.w;
-        o = mk3(T.origin[0], T.origin[1], T.origin[2]);
+        o = fv3(ref_ld(T.origin));
+        d = fv3(ref_normalize(ref_madd(rv3(c), r.x, ref_mk(r.y, r.z, r.w))));
     } else {
-        /* ORTHO: the image-plane vector the pinhole raygen would normalise (wt_primary_dir_xy before its sqrtf) is the origin's offset */
-        const float w = (float)x;
-        const float h = (float)y;
-        vx = T.corner[0] + T.right[0] * T.w_factor * w - T.up[0] * T.h_factor * h;
-        vy = T.corner[1] + T.right[1] * T.w_factor * w - T.up[1] * T.h_factor * h;
-        vz = T.corner[2] + T.right[2] * T.w_factor * w - T.up[2] * T.h_factor * h;
-        o = mk3(T.origin[0] + vx, T.origin[1] + vy, T.origin[2] + vz);
-        d = mk3(T.dir[0], T.dir[1], T.dir[2]);
-        return;
+        /* ORTHO: the image-plane vector the pinhole raygen would normalise is the origin's offset */
+        o = fv3(ref_add(ref_ld(T.origin), ref_image_plane(ref_ld(T.corner), ref_ld(T.right), ref_ld(T.up), T.w_factor, T.h_factor, x, y)));
+        d = fv3(ref_ld(T.dir));
     }
-    const float len = sqrtf(vx * vx + vy * vy + vz * vz);
-    d = mk3(vx / len, vy / len, vz / len);
 }
 
 /* ---- the twin of wt_raygen for the two models: the same work-item -> id mapping (id offset, row bands), the same transposition through LDS,

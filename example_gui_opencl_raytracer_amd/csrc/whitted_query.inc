@@ -1,8 +1,7 @@
 /* whitted_query.inc -- what the ray queries share: the one candidate scan of wt_cast (whitted_cast.inc) and wt_cast_layers
  * (whitted_layers.inc), and the sphere test that the ambient occlusion pass (whitted_ao.inc) makes too.  Included by whitted_launch.inc ahead of
- * those three, so it exists in the fast and the strict unit.  The arithmetic is the host definitions' (csrc/ref_tests.h, cast_host.c),
- * operation for operation -- wt_gb_ref_dot's sums, IEEE square root and divide, no fused operation (`#pragma clang fp contract(off)` wherever a
- * float is computed) -- so both builds give the host's bits.
+ * those three, so it exists in the fast and the strict unit.  The arithmetic is csrc/ref_tests.h, the one text the host definitions
+ * (cast_host.c) are compiled from too -- IEEE square root and divide, no fused operation -- so both builds give the host's bits.
  *
  * A query kernel loads a lane's ray (wt_query_load), hands it to wt_query_scan with a SINK, and stores what the sink holds.  The scan
  * enumerates the ray's candidates -- a primitive that takes part, is not `ignore`, is hit, and at t <= tmax -- and the sink decides what becomes
@@ -24,18 +23,11 @@
 #define WT_CAST_LIGHTS 4u
 #define WT_CAST_OPAQUE 8u
 
-/* the definition's sphere test, the invariants of the origin (v = o - c, cc = v.v - |r r|) and of the direction (a = d.d) already taken: the
- * operations of wt_gb_ref_sphere in its order.  true = a candidate (hit && t <= tmax), its parameter in t.  D < 0 leaves before the roots:
- * wt_gb_ref_sphere's verdict is then `no hit` whatever t is. */
-__device__ __forceinline__ bool wt_query_sphere(f3 v, float cc, f3 d, float a, float tmax, float& t) {
-#pragma clang fp contract(off)
-    const float b = wt_gb_ref_dot(v, d);
-    const float D = b * b + (-(a * cc));
-    if (D < 0) return false;
-    const float sD = sqrtf(D);
-    const float t0 = (-b - sD) / a;
-    t = (t0 < 0) ? (-b + sD) / a : t0;
-    return !(t <= 0) && t <= tmax;
+/* the definition's sphere test of the ray (o, d), a = d.d already taken, against {c, +-r r} = s: ref_sphere_query over the origin's invariants.
+ * true = a candidate (hit && t <= tmax), its parameter in t. */
+__device__ __forceinline__ bool wt_query_sphere(f3 o, float4 s, f3 d, float a, float tmax, float& t) {
+    const ref_v3 v = ref_sub(rv3(o), rv3(s));
+    return ref_sphere_query(v, ref_sphere_cc(v, s.w), rv3(d), a, tmax, &t);
 }
 
 struct wt_query_ray { f3 o, d; float tmax; unsigned ignore; float a; };      /* a = d.d */
@@ -47,7 +39,7 @@ __device__ __forceinline__ wt_query_ray wt_query_load(const float4* rays, unsign
     r.o = mk3(r0.x, r0.y, r0.z); r.d = mk3(r1.x, r1.y, r1.z);
     r.tmax = r0.w;
     r.ignore = __float_as_uint(r1.w);
-    r.a = wt_gb_ref_dot(r.d, r.d);
+    r.a = wt_ref_dot(r.d, r.d);
     return r;
 }
 
@@ -83,9 +75,8 @@ __device__ __forceinline__ void wt_query_grid(const whitted_params& P, const wt_
         for (unsigned i = 0; i < P.ns; i++) {
             const float4 s = ((const float4*)P.geom)[i];
             if (i == r.ignore || (opaque && (__float_as_uint(s.w) >> 31))) continue;
-            const f3 v = o - mk3(s.x, s.y, s.z);
             float t;
-            if (wt_query_sphere(v, wt_gb_ref_dot(v, v) - fabsf(s.w), d, r.a, r.tmax, t)) S.take(t, i);
+            if (wt_query_sphere(o, s, d, r.a, r.tmax, t)) S.take(t, i);
         }
         return;
     }
@@ -102,9 +93,8 @@ __device__ __forceinline__ void wt_query_grid(const whitted_params& P, const wt_
         for (unsigned k = cur.b; k < cur.e; k++) {
             const float4 s = ((const float4*)P.grid_geom)[k];
             if (opaque && (__float_as_uint(s.w) >> 31)) continue;
-            const f3 v = o - mk3(s.x, s.y, s.z);
             float t;
-            if (wt_query_sphere(v, wt_gb_ref_dot(v, v) - fabsf(s.w), d, r.a, r.tmax, t) && S.grid_wants(t)) {
+            if (wt_query_sphere(o, s, d, r.a, r.tmax, t) && S.grid_wants(t)) {
                 const unsigned i = P.grid_items[k];      /* (fetched for a candidate the sink can use only) */
                 if (i == r.ignore) continue;
                 S.grid_take(t, i);
@@ -138,23 +128,14 @@ __device__ __forceinline__ void wt_query_scan(const whitted_params& P, const flo
         for (unsigned i = 0; !GRID && i < P.ns; i++) {
             if (SINK::FIRST && __builtin_amdgcn_ballot_w64(live) == 0ull) break;      /* everybody is settled */
             const float4 s = wt_geom<GEOM_LDS>(P, sg, i);
-            const f3 v = o - mk3(s.x, s.y, s.z);
-            bool ok;
+            const ref_v3 v = ref_sub(rv3(o), rv3(s));
             float b, D;
-            {
-#pragma clang fp contract(off)
-                const float cc = wt_gb_ref_dot(v, v) - fabsf(s.w);
-                b = wt_gb_ref_dot(v, d);
-                D = b * b + (-(a * cc));
-                ok = live && i != ignore && !(opaque && (__float_as_uint(s.w) >> 31)) && !(D < 0);
-            }
+            const bool met = ref_sphere_disc(v, ref_sphere_cc(v, s.w), rv3(d), a, &b, &D);
+            const bool ok = live && i != ignore && !(opaque && (__float_as_uint(s.w) >> 31)) && met;
             if (__builtin_amdgcn_ballot_w64(ok) == 0ull) continue;      /* nobody's line meets this one */
-            if (ok) {      /* (wt_query_sphere's second half) */
-#pragma clang fp contract(off)
-                const float sD = sqrtf(D);
-                const float t0 = (-b - sD) / a;
-                const float t = (t0 < 0) ? (-b + sD) / a : t0;
-                if (!(t <= 0) && t <= tmax) { S.take(t, i); if (SINK::FIRST) live = false; }
+            if (ok) {      /* (ref_sphere_query's second half) */
+                const float t = ref_sphere_root(b, D, a);
+                if (ref_candidate(t, tmax)) { S.take(t, i); if (SINK::FIRST) live = false; }
             }
         }
     }
@@ -164,7 +145,7 @@ __device__ __forceinline__ void wt_query_scan(const whitted_params& P, const flo
             const float4 pn = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * i);
             const float4 p0 = wt_geom<GEOM_LDS>(P, sg, g_pln + 2 * i + 1);
             float t;
-            if (live && (WT_GB_KIND_PLANE | i) != ignore && wt_gb_ref_plane(o, d, pn, p0, t) && t <= tmax) {
+            if (live && (WT_GB_KIND_PLANE | i) != ignore && ref_plane(rv3(o), rv3(d), rv3(pn), rv3(p0), &t) && t <= tmax) {
                 S.take(t, WT_GB_KIND_PLANE | i);      /* (kind 1 ids follow every sphere's) */
                 if (SINK::FIRST) live = false;
             }
@@ -174,9 +155,8 @@ __device__ __forceinline__ void wt_query_scan(const whitted_params& P, const flo
         for (unsigned i = 0; i < P.nl; i++) {
             if (SINK::FIRST && __builtin_amdgcn_ballot_w64(live) == 0ull) break;
             const float4 l0 = wt_geom<GEOM_LDS>(P, sg, g_lgt + 2 * i);
-            const f3 v = o - mk3(l0.x, l0.y, l0.z);
             float t;
-            if (live && (WT_GB_KIND_LIGHT | i) != ignore && wt_query_sphere(v, wt_gb_ref_dot(v, v) - fabsf(l0.w), d, a, tmax, t)) {
+            if (live && (WT_GB_KIND_LIGHT | i) != ignore && wt_query_sphere(o, l0, d, a, tmax, t)) {
                 S.take(t, WT_GB_KIND_LIGHT | i);
                 if (SINK::FIRST) live = false;
             }

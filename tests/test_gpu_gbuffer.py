@@ -8,7 +8,7 @@ edge may take the neighbour: the bar of test_find_solid_intersection).
 Measured on the MI355X: both builds meet every bound.  strict: 0 ids and 0 bits differ in all cases, depth included.  fast: 0 or 1 id per case
 differs, and on the pixels with equal ids depth, point and normal have the expected BITS (largest error 0): the pass decides the winner in the
 build's own arithmetic but evaluates the winner's depth, point, normal and a light's colour in the reference's (csrc/whitted_gbuffer.inc,
-wt_gb_ref_*).  Evaluated in the fast build's own fused arithmetic the same quantities miss these bounds -- D/4 = b*b - c cancels near a
+csrc/ref_tests.h). Evaluated in the fast build's own fused arithmetic the same quantities miss these bounds -- D/4 = b*b - c cancels near a
 silhouette and from afar: normals off by up to 7.9e-5 (case A, 21 pixels above 1e-5) and 2.4e-3 (D0, 83 pixels), a light colour of 16.01 off by
 an ulp of 1.9e-6 on 2 % of case C1 -- which is why they are not."""
 import ctypes as C
