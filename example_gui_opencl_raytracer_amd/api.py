@@ -72,6 +72,10 @@ PATH_REASON_BOUNCES, PATH_REASON_MISSED, PATH_REASON_ENDED = 0, 1, 2
 PATH_EPSILON = np.float32(0.001)      # the reference's EPSILON: a segment starts at point + normal * EPSILON of the hit before it
 TIMING_PATHS = 0x50415448
 
+# proximity queries (hip_wrap_ext.h: clw_probe, clw_host_nearest_surface; PROBE below is a probe as a numpy dtype): the kernel's id in the
+# timing log
+TIMING_NEAR = 0x4E454152
+
 
 def id_kind(ids):
     """Kind of the entries of an id channel (0 sphere, 1 plane, 2 light; 3 for ID_NONE)."""
@@ -157,6 +161,11 @@ class clw_layer(C.Structure):
     _fields_ = [("t", C.c_float), ("id", C.c_uint32)]
 
 
+class clw_probe(C.Structure):
+    """One probe of a proximity query (16 bytes): a point and how far it reaches (inf = unlimited; negative = only penetrations that deep)."""
+    _fields_ = [("point", C.c_float * 3), ("reach", C.c_float)]
+
+
 class clw_rect(C.Structure):
     """A rectangle in frame pixels (16 bytes)."""
     _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32)]
@@ -186,8 +195,9 @@ class clw_grid_info(C.Structure):
                 ("cell", C.c_float * 3), ("gmin", C.c_float * 3), ("reg_pad", C.c_float)]
 
 
-# the records that travel in arrays, as numpy dtypes: derived from their Structure, so each layout is written once (32, 32, 8 and 48 bytes)
+# the records that travel in arrays, as numpy dtypes: derived from their Structure, so each layout is written once (32, 32, 8, 48 and 16 bytes)
 RAY_QUERY, HIT, LAYER, OBJECT_STAT = np.dtype(clw_ray), np.dtype(clw_hit), np.dtype(clw_layer), np.dtype(clw_object_stat)
+PROBE = np.dtype(clw_probe)
 
 _int, _u32, _u64, _sz, _f32, _vp, _str = C.c_int, C.c_uint32, C.c_uint64, C.c_size_t, C.c_float, C.c_void_p, C.c_char_p
 _f3, _pu32 = C.c_float * 3, C.POINTER(C.c_uint32)
@@ -284,6 +294,14 @@ PROTOTYPES = {
     "clw_ext_cast_paths": (_u32, [_W, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
     "clw_ext_cast_paths_device": (_u32, [_W, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
     "clw_ext_pick_path": (_int, [_W, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "clw_host_nearest_surface": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "clw_host_within_reach": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "clw_host_near_surfaces": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp]),
+    "clw_ext_nearest_surface": (_u32, [_W, _vp, _vp, _u32, _u32, _vp]),
+    "clw_ext_within_reach": (_u32, [_W, _vp, _vp, _u32, _u32, _vp]),
+    "clw_ext_near_surfaces": (_u32, [_W, _vp, _vp, _u32, _u32, _u32, _vp, _vp]),
+    "clw_ext_probe_device": (_u32, [_W, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "clw_ext_near_surfaces_device": (_u32, [_W, _vp, _vp, _u32, _u32, _u32, _vp, _vp]),
     "clw_ext_enable_counters": (None, [_W, _int]),
     "clw_ext_read_counters": (None, [_W, C.POINTER(_u64 * 8)]),
     "clw_ext_read_counters_ex": (None, [_W, C.POINTER(_u64 * 32), _u32]),
@@ -605,6 +623,61 @@ def cast_paths_host(rays, flags: int, bounces: int, spheres, planes, lights=None
             _ptr(rays), rays.size, int(flags), B, _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, _ptr(hits), _ptr(status), _ptr(nxt)):
         raise ValueError("clw_host_cast_paths rejects these arguments (at least one ray, fewer than 2^30, a kind bit and only CAST_* and PATH_* bits in flags, bounces in 1..8)")
     return paths_result(hits, status, nxt)
+
+
+def make_probes(points, reach=np.inf) -> np.ndarray:
+    """PROBE [n] from points of [n, 3]; reach is scalar or per probe."""
+    points = np.asarray(points, np.float32).reshape(-1, 3)
+    probes = np.empty(points.shape[0], PROBE)
+    probes["point"] = points
+    probes["reach"] = np.asarray(reach, np.float32)
+    return probes
+
+
+def _near_args(probes, ignore, spheres, planes, lights):
+    """The probes (PROBE [n]) and their ignore words (uint32 [n], a scalar for all, or None = nothing is ignored), flat, and the scene arrays."""
+    probes = _flat(probes, PROBE)
+    if ignore is not None:
+        ignore = np.ascontiguousarray(np.broadcast_to(np.asarray(ignore, np.uint32).reshape(-1), probes.shape))
+    arrs = [None if a is None else np.ascontiguousarray(a) for a in (spheres, planes, lights)]
+    counts = [0 if a is None else int(a.shape[0]) for a in arrs]
+    return probes, ignore, arrs, counts
+
+
+_NEAR_REJECTS = "rejects these arguments (at least one probe, fewer than 2^30, a kind bit and only CAST_* bits in flags"
+
+
+def nearest_surface_host(probes, flags: int, spheres, planes, lights=None, ignore=None) -> np.ndarray:
+    """clw_host_nearest_surface: the nearest surface within reach of every probe, on the host -- THE definition the device pass is held to ->
+    HIT [n] with t = the signed distance (negative inside a sphere)."""
+    probes, ignore, (s, p, l), (ns, np_, nl) = _near_args(probes, ignore, spheres, planes, lights)
+    out = np.empty(probes.size, HIT)
+    if not _fits_u32(flags) or not load_library().clw_host_nearest_surface(
+            _ptr(probes), _ptr(ignore), probes.size, int(flags), _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, _ptr(out)):
+        raise ValueError("clw_host_nearest_surface " + _NEAR_REJECTS + ")")
+    return out
+
+
+def within_reach_host(probes, flags: int, spheres, planes, lights=None, ignore=None) -> np.ndarray:
+    """clw_host_within_reach: whether any surface lies within reach of every probe, on the host -- THE definition -> uint8 [n] of 0 / 1."""
+    probes, ignore, (s, p, l), (ns, np_, nl) = _near_args(probes, ignore, spheres, planes, lights)
+    out = np.empty(probes.size, np.uint8)
+    if not _fits_u32(flags) or not load_library().clw_host_within_reach(
+            _ptr(probes), _ptr(ignore), probes.size, int(flags), _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, _ptr(out)):
+        raise ValueError("clw_host_within_reach " + _NEAR_REJECTS + ")")
+    return out
+
+
+def near_surfaces_host(probes, flags: int, K: int, spheres, planes, lights=None, ignore=None) -> dict:
+    """clw_host_near_surfaces: the K nearest surfaces within reach of every probe, on the host -- THE definition the device pass is held to ->
+    {"d": float32 [K, n], "id": uint32 [K, n]}, nearest first, empty entries {inf, ID_NONE}."""
+    probes, ignore, (s, p, l), (ns, np_, nl) = _near_args(probes, ignore, spheres, planes, lights)
+    K = int(K)
+    d, ids = np.empty((max(K, 0), probes.size), np.float32), np.empty((max(K, 0), probes.size), np.uint32)
+    if not _fits_u32(flags, K) or not load_library().clw_host_near_surfaces(
+            _ptr(probes), _ptr(ignore), probes.size, int(flags), _ptr(s), ns, _ptr(p), np_, _ptr(l), nl, K, _ptr(d), _ptr(ids)):
+        raise ValueError("clw_host_near_surfaces " + _NEAR_REJECTS + ", K in 1..8)")
+    return {"d": d, "id": ids}
 
 
 def camera_rays_host(cam: clw_camera, proj: clw_projection | None = None, id_begin: int = 0, id_end: int | None = None) -> np.ndarray:
@@ -1081,6 +1154,60 @@ class ClWrap:
             return 0
         return int(self.L.clw_ext_cast_layers_device(C.byref(self.w), C.c_void_p(rays_ptr or None), int(n), int(flags), int(K), C.c_void_p(t_ptr or None),
                                                      C.c_void_p(id_ptr or None)))
+
+    def _probes(self, probes, ignore):
+        probes = _flat(probes, PROBE)
+        if ignore is not None:
+            ignore = np.ascontiguousarray(np.broadcast_to(np.asarray(ignore, np.uint32).reshape(-1), probes.shape))
+        return probes, ignore
+
+    def nearest_surface(self, probes, flags: int = CAST_SPHERES | CAST_PLANES, ignore=None):
+        """clw_ext_nearest_surface: the nearest surface within reach of every probe (PROBE [n]; ignore: uint32 [n], a scalar, or None) against
+        the bound scene, on the device -> HIT [n] with t = the signed distance, or None when it is refused (no scene bound, no probe, unknown
+        flag bits, no kind)."""
+        probes, ignore = self._probes(probes, ignore)
+        out = np.empty(probes.size, HIT)
+        if not _fits_u32(probes.size, flags):
+            return None
+        n = self.L.clw_ext_nearest_surface(C.byref(self.w), _ptr(probes), _ptr(ignore), probes.size, int(flags), _ptr(out))
+        return out if n == probes.size and n else None
+
+    def within_reach(self, probes, flags: int = CAST_SPHERES | CAST_PLANES, ignore=None):
+        """clw_ext_within_reach: whether any surface lies within reach of every probe, on the device -> uint8 [n] of 0 / 1, or None when it is
+        refused."""
+        probes, ignore = self._probes(probes, ignore)
+        out = np.empty(probes.size, np.uint8)
+        if not _fits_u32(probes.size, flags):
+            return None
+        n = self.L.clw_ext_within_reach(C.byref(self.w), _ptr(probes), _ptr(ignore), probes.size, int(flags), _ptr(out))
+        return out if n == probes.size and n else None
+
+    def near_surfaces(self, probes, flags: int = CAST_SPHERES | CAST_PLANES, K: int = 4, ignore=None):
+        """clw_ext_near_surfaces: the K nearest surfaces within reach of every probe, on the device -> {"d": float32 [K, n], "id": uint32
+        [K, n]}, or None when it is refused (as nearest_surface; K outside 1..8)."""
+        probes, ignore = self._probes(probes, ignore)
+        if not _fits_u32(probes.size, flags, K):
+            return None
+        d, ids = np.empty((int(K), probes.size), np.float32), np.empty((int(K), probes.size), np.uint32)
+        n = self.L.clw_ext_near_surfaces(C.byref(self.w), _ptr(probes), _ptr(ignore), probes.size, int(flags), int(K), _ptr(d), _ptr(ids))
+        return {"d": d, "id": ids} if n == probes.size and n else None
+
+    def probe_device(self, probes_ptr: int, n: int, flags: int = CAST_SPHERES | CAST_PLANES, ignore_ptr: int | None = None, hits_ptr: int | None = None,
+                     within_ptr: int | None = None) -> int:
+        """clw_ext_probe_device: the nearest or the within query over the caller's device memory (integer addresses: n PROBE records; n ignore
+        words or None; n HIT records or n bytes -- exactly one of the two), on the wrapper's stream, without waiting -> n, or 0 when it is refused."""
+        if not _fits_u32(n, flags):
+            return 0
+        return int(self.L.clw_ext_probe_device(C.byref(self.w), C.c_void_p(probes_ptr or None), C.c_void_p(ignore_ptr or None), int(n), int(flags),
+                                               C.c_void_p(hits_ptr or None), C.c_void_p(within_ptr or None)))
+
+    def near_surfaces_device(self, probes_ptr: int, n: int, flags: int, K: int, d_ptr: int, id_ptr: int, ignore_ptr: int | None = None) -> int:
+        """clw_ext_near_surfaces_device: the K-nearest query over the caller's device memory (integer addresses: n PROBE records; K * n floats;
+        K * n words, layer-major; n ignore words or None), on the wrapper's stream, without waiting -> n, or 0 when it is refused."""
+        if not _fits_u32(n, flags, K):
+            return 0
+        return int(self.L.clw_ext_near_surfaces_device(C.byref(self.w), C.c_void_p(probes_ptr or None), C.c_void_p(ignore_ptr or None), int(n), int(flags),
+                                                       int(K), C.c_void_p(d_ptr or None), C.c_void_p(id_ptr or None)))
 
     def camera_rays(self, capacity: int):
         """clw_ext_camera_rays: the query rays of the range the next trace launch would cover -> RAY_QUERY [n], or None when it is refused (no

@@ -3,7 +3,7 @@
   libopencl_wrap_hip.so  = hip_wrap.cpp + hip_wrap_passes.cpp (C-ABI shim: the reference's entry points and the trace path; the passes beside
                            it; shared internals in hip_wrap_impl.h) + whitted_fast.hip + whitted_strict.hip
                            (gfx950 kernels) + launch_plan.c (the launch planner) + scene_prep.c + overlay_host.c (the selection
-                           overlay's host model) + ao_host.c (the ambient occlusion pass's definition) + cast_host.c (the ray queries') + layers_host.c (the layered ray queries') + paths_host.c (the path queries') + objects_host.c (the visible-object table's) + primary_cull_host.c (the primary-ray cull table's) + bounce_cull_host.c (the bounce cull table's) + projection_host.c (the camera models beside the
+                           overlay's host model) + ao_host.c (the ambient occlusion pass's definition) + cast_host.c (the ray queries') + layers_host.c (the layered ray queries') + near_host.c (the proximity queries') + paths_host.c (the path queries') + objects_host.c (the visible-object table's) + primary_cull_host.c (the primary-ray cull table's) + bounce_cull_host.c (the bounce cull table's) + projection_host.c (the camera models beside the
                            pinhole: THE definition of their rays) + host_camera.c + png_codec.c
 Usage: python -m example_gui_opencl_raytracer_amd.build [--force]
 """
@@ -25,10 +25,10 @@ HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc
 CC = os.environ.get("CC") or "gcc"
 
 DEVICE_DEPS = ["whitted_trace.inc", "whitted_hit.inc", "whitted_shade.inc", "whitted_bounce.inc", "whitted_pop.inc", "whitted_tpt.inc", "whitted_terms.inc",
-               "whitted_gbuffer.inc", "whitted_projection.inc", "whitted_query.inc", "whitted_ao.inc", "whitted_cast.inc", "whitted_layers.inc", "whitted_paths.inc", "whitted_overlay.inc", "whitted_objects.inc", "whitted_cull.inc", "primary_cull_host.h", "bounce_cull_host.h", "ref_tests.h", "whitted_launch.inc", "whitted_launch.h", "whitted_params.h",
+               "whitted_gbuffer.inc", "whitted_projection.inc", "whitted_query.inc", "whitted_ao.inc", "whitted_cast.inc", "whitted_layers.inc", "whitted_near.inc", "whitted_paths.inc", "whitted_overlay.inc", "whitted_objects.inc", "whitted_cull.inc", "primary_cull_host.h", "bounce_cull_host.h", "ref_tests.h", "whitted_launch.inc", "whitted_launch.h", "whitted_params.h",
                "projection_host.h"]
 SHIM_FLAGS = ["-O2", "-std=c++17", "-Wall"]
-SHIM_DEPS = ["hip_wrap_impl.h", "whitted_params.h", "whitted_launch.h", "launch_plan.h", "scene_prep.h", "ao_host.h", "cast_host.h", "layers_host.h", "paths_host.h", "overlay_host.h", "objects_host.h", "projection_host.h",
+SHIM_DEPS = ["hip_wrap_impl.h", "whitted_params.h", "whitted_launch.h", "launch_plan.h", "scene_prep.h", "ao_host.h", "cast_host.h", "layers_host.h", "near_host.h", "paths_host.h", "overlay_host.h", "objects_host.h", "projection_host.h",
              "primary_cull_host.h", "bounce_cull_host.h", "png_codec.h", "../../include/opencl_wrap.h", "../../include/hip_wrap_ext.h"]
 UNITS = [
     # (source, compiler, flags, extra deps)
@@ -49,6 +49,8 @@ UNITS = [
      ["cast_host.h", "ref_tests.h", "scene_prep.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
     ("layers_host.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra", "-D_DEFAULT_SOURCE"],
      ["layers_host.h", "cast_host.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
+    ("near_host.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra", "-D_DEFAULT_SOURCE"],
+     ["near_host.h", "cast_host.h", "layers_host.h", "ref_tests.h", "scene_prep.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
     ("paths_host.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra", "-D_DEFAULT_SOURCE"],
      ["paths_host.h", "cast_host.h", "ref_tests.h", "../../include/hip_wrap_ext.h", "../../include/opencl_wrap.h"]),
     ("objects_host.c", "c", ["-O2", "-std=c99", "-ffp-contract=off", "-Wall", "-Wextra"],

@@ -255,7 +255,7 @@ void prepare_scene(Impl* I, Buffer* s, uint32_t ns, Buffer* p, uint32_t np, Buff
     /* uniform grid over the spheres for big scenes */
     for (uint32_t** q : {&I->d_grid_start, &I->d_grid_items, &I->d_grid_box}) { if (*q) { (void)hipFree(*q); *q = nullptr; } }
     if (I->d_grid_geom) { (void)hipFree(I->d_grid_geom); I->d_grid_geom = nullptr; }
-    I->grid_ok = false;
+    I->grid_ok = false; I->near_grid_ok = false;
     if (ns > (uint32_t)env_int("CLWRAP_GRID_MIN", (int)WT_GRID_MIN_SPHERES)) {   /* CLWRAP_GRID_MIN: tuning knob */
         const char* dens = getenv("CLWRAP_GRID_DENSITY");   /* tuning knob: average spheres per cell */
         /* the two soft-shadow samples of a light share one walk (wt_grid_shadow_pair) when spheres are listed a light radius beyond their
@@ -287,6 +287,9 @@ void prepare_scene(Impl* I, Buffer* s, uint32_t ns, Buffer* p, uint32_t np, Buff
             HIP_OK(hipMemcpy(I->d_grid_geom, cg.data(), cg.size() * 4, hipMemcpyHostToDevice), "Couldn't transfer the data from host to the device");
             I->grid_ok = true;
             I->grid_pairs = pairs;
+            /* the proximity queries' box through the grid needs every prepared r * r word finite (whitted_near.inc) */
+            I->near_grid_ok = true;
+            for (uint32_t i = 0; i < ns; i++) if (!std::isfinite(geom[4 * (size_t)i + 3])) I->near_grid_ok = false;
         }
     }
     I->geom_f4 = f4;
@@ -1007,6 +1010,7 @@ void cl_wrap_release(cl_wrap* wrap) {
     I->cast.free_buffers();
     I->layers.release();
     I->paths.release();
+    I->near.release();
     I->ptab.free_all();
     I->adapt.free_all();
     if (I->tables_fence) (void)hipEventDestroy(I->tables_fence);

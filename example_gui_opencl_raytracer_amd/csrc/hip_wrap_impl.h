@@ -22,6 +22,7 @@
 #include "ao_host.h"
 #include "cast_host.h"
 #include "layers_host.h"
+#include "near_host.h"
 #include "paths_host.h"
 #include "launch_plan.h"
 #include "objects_host.h"
@@ -283,6 +284,14 @@ struct Impl {
         uint32_t* pick = nullptr;
         void release() { rays.release(); hits.release(); status.release(); next.release(); if (pick) (void)hipFree(pick); pick = nullptr; }
     } paths;
+    /* proximity queries (clw_ext_nearest_surface / clw_ext_within_reach / clw_ext_near_surfaces; whitted_near.inc): the buffers of the host-array
+     * entry points -- the probes and the ignore words as uploaded, the hits or the within bytes, the K planar layers of d and id -- each grown to
+     * the largest size so far (DeviceGrow); those calls wait for their own work.  The device entry points work on the caller's memory and own
+     * nothing. */
+    struct Near {
+        DeviceGrow probes, ignore, out, d, id;
+        void release() { probes.release(); ignore.release(); out.release(); d.release(); id.release(); }
+    } near;
     /* prepared scene cache */
     const Buffer *prep_s = nullptr, *prep_p = nullptr, *prep_l = nullptr;
     uint32_t prep_ns = 0, prep_np = 0, prep_nl = 0;
@@ -292,7 +301,7 @@ struct Impl {
     uint64_t scene_generation = 0;   /* bumped every time the prepared scene is rebuilt (device pointers can be reused) */
     uint32_t *d_grid_start = nullptr, *d_grid_items = nullptr, *d_grid_box = nullptr;
     float* d_grid_geom = nullptr;
-    wprep_grid grid{}; bool grid_ok = false, grid_pair = false; int use_grid = 1;
+    wprep_grid grid{}; bool grid_ok = false, grid_pair = false, near_grid_ok = false; int use_grid = 1;
     size_t grid_pairs = 0;                       /* cell-list entries of the grid built (clw_ext_get_grid) */
     int grid_pair_req = -1;                      /* clw_ext_set_grid_pair: -1 = env CLWRAP_GRID_PAIR (default on), 0 / 1 */
     unsigned long long* d_counters = nullptr;

@@ -173,6 +173,59 @@ void launch_layers(Impl* I, const whitted_params& P, const wt_cast_class& cc, co
     tm.done();
 }
 
+/* ---- proximity queries ---------------------------------------------------------------------------------------------------------------- */
+/* The scene side of a proximity query of n probes: a ray query's (cast_params) under the plan wt_plan_near -- the grid only where every prepared
+ * r * r word is finite.  CLWRAP_NEAR_BOX_CELLS: the cap on a probe's box, for tests and A/B runs.  false as cast_params. */
+bool near_params(cl_wrap* w, Impl* I, uint32_t n, whitted_params& P, wt_near_class& nc) {
+    wt_cast_class cc;
+    if (!cast_params(w, I, n, P, cc)) return false;      /* (prepares the scene; its geometry class is chosen again below) */
+    nc = wt_plan_near(I->variant, I->prep_ns, (uint32_t)I->geom_f4, I->grid_ok && I->use_grid && I->near_grid_ok, n, env_int("CLWRAP_NEAR_BOX_CELLS", -1));
+    if (nc.groups == 0u) return false;
+    P = whitted_params{};
+    bind_geometry(I, P, nc.flags);
+    return true;
+}
+
+/* wt_near over device memory on the launch stream; exactly one of hits / within / (d and id) */
+void launch_near(Impl* I, const whitted_params& P, const wt_near_class& nc, const void* probes, const void* ignore, uint32_t n, uint32_t flags, uint32_t K,
+                 void* hits, void* within, void* d, void* id) {
+    LaunchTimer t(I, CLW_TIMING_NEAR, true);
+    hipError_t e = WT_LAUNCH(I, near)(&P, nc.flags, nc.dyn_lds, nc.box_cells, probes, (const unsigned*)ignore, n, flags, K, hits, (unsigned char*)within,
+                                      (float*)d, (unsigned*)id, I->stream);
+    if (e != hipSuccess) die("Couldn't run the kernel");
+    t.done();
+}
+
+/* the three host-array entry points: upload, launch, read back, all in the order of the launch stream, then wait.  K = 0: hits or within */
+uint32_t near_host_arrays(cl_wrap* wrap, const clw_probe* probes, const uint32_t* ignore, uint32_t n, uint32_t flags, uint32_t K, clw_hit* hits,
+                          uint8_t* within, float* d, uint32_t* id) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    static_assert(sizeof(clw_probe) == 16, "the proximity queries' ABI");
+    if (!(K ? wt_near_list_check(n, flags, K) : wt_near_check(n, flags)) || !probes) return 0;
+    whitted_params P{};
+    wt_near_class nc;
+    if (!near_params(wrap, I, n, P, nc)) return 0;
+    Impl::Near& B = I->near;
+    const size_t words = (size_t)K * n;
+    void* d_probes = B.probes.reserve((size_t)n * sizeof(clw_probe));
+    void* d_ignore = ignore ? B.ignore.reserve((size_t)n * 4) : nullptr;
+    void* d_out = K ? nullptr : B.out.reserve(hits ? (size_t)n * sizeof(clw_hit) : (size_t)n);
+    void* d_d = K ? B.d.reserve(words * 4) : nullptr;
+    void* d_id = K ? B.id.reserve(words * 4) : nullptr;
+    HIP_OK(hipMemcpyAsync(d_probes, probes, (size_t)n * sizeof(clw_probe), hipMemcpyHostToDevice, I->stream), "Couldn't transfer the data from host to the device");
+    if (ignore) HIP_OK(hipMemcpyAsync(d_ignore, ignore, (size_t)n * 4, hipMemcpyHostToDevice, I->stream), "Couldn't transfer the data from host to the device");
+    launch_near(I, P, nc, d_probes, d_ignore, n, flags, K, hits ? d_out : nullptr, within ? d_out : nullptr, d_d, d_id);
+    if (hits) HIP_OK(hipMemcpyAsync(hits, d_out, (size_t)n * sizeof(clw_hit), hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    else if (within) HIP_OK(hipMemcpyAsync(within, d_out, (size_t)n, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    else {
+        HIP_OK(hipMemcpyAsync(d, d_d, words * 4, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+        HIP_OK(hipMemcpyAsync(id, d_id, words * 4, hipMemcpyDeviceToHost, I->stream), "Failed to transfer device memory to host");
+    }
+    finish(I);
+    return n;
+}
+
 /* ---- path queries -------------------------------------------------------------------------------------------------------------------- */
 /* The scene side of a path query of n rays: a ray query's (cast_params), and the bound sphere and plane arrays themselves, from which
  * wt_cast_paths reads the winner's material.  false as cast_params. */
@@ -658,6 +711,45 @@ int clw_ext_pick_layers(cl_wrap* wrap, uint32_t x, uint32_t y, uint32_t flags, u
     finish(I);
     for (uint32_t k = 0; k < K; k++) { memcpy(&out[k].t, &h[k], 4); out[k].id = h[WT_LAYERS_MAX + k]; }
     return 1;
+}
+
+uint32_t clw_ext_nearest_surface(cl_wrap* wrap, const clw_probe* probes, const uint32_t* ignore, uint32_t n, uint32_t flags, clw_hit* out) {
+    if (!out) return 0;
+    return near_host_arrays(wrap, probes, ignore, n, flags, 0u, out, nullptr, nullptr, nullptr);
+}
+
+uint32_t clw_ext_within_reach(cl_wrap* wrap, const clw_probe* probes, const uint32_t* ignore, uint32_t n, uint32_t flags, uint8_t* within) {
+    if (!within) return 0;
+    return near_host_arrays(wrap, probes, ignore, n, flags, 0u, nullptr, within, nullptr, nullptr);
+}
+
+uint32_t clw_ext_near_surfaces(cl_wrap* wrap, const clw_probe* probes, const uint32_t* ignore, uint32_t n, uint32_t flags, uint32_t K, float* d,
+                               uint32_t* id) {
+    if (K == 0u || !d || !id) return 0;
+    return near_host_arrays(wrap, probes, ignore, n, flags, K, nullptr, nullptr, d, id);
+}
+
+uint32_t clw_ext_probe_device(cl_wrap* wrap, const void* d_probes, const void* d_ignore, uint32_t n, uint32_t flags, void* d_hits, void* d_within) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    if (!wt_near_check(n, flags) || !d_probes || (d_hits != nullptr) == (d_within != nullptr)) return 0;
+    whitted_params P{};
+    wt_near_class nc;
+    if (!near_params(wrap, I, n, P, nc)) return 0;
+    launch_near(I, P, nc, d_probes, d_ignore, n, flags, 0u, d_hits, d_within, nullptr, nullptr);
+    return n;
+}
+
+uint32_t clw_ext_near_surfaces_device(cl_wrap* wrap, const void* d_probes, const void* d_ignore, uint32_t n, uint32_t flags, uint32_t K, void* d_d,
+                                      void* d_id) {
+    Impl* I = impl_of(wrap);
+    use_device(I);
+    if (!wt_near_list_check(n, flags, K) || !d_probes || !d_d || !d_id) return 0;
+    whitted_params P{};
+    wt_near_class nc;
+    if (!near_params(wrap, I, n, P, nc)) return 0;
+    launch_near(I, P, nc, d_probes, d_ignore, n, flags, K, nullptr, nullptr, d_d, d_id);
+    return n;
 }
 
 uint32_t clw_ext_cast_paths(cl_wrap* wrap, const clw_ray* rays, uint32_t n, uint32_t flags, uint32_t bounces, clw_hit* hits, uint8_t* status,

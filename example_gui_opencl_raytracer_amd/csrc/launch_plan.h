@@ -165,6 +165,18 @@ wt_geom_class wt_plan_geometry(int strict, int variant, uint32_t ns, uint32_t np
 enum { WT_CAST_BATCHES_LDS = 1, WT_CAST_BATCHES_MAX = 64 };
 typedef struct { int32_t flags; uint32_t dyn_lds, groups, batches; } wt_cast_class;
 wt_cast_class wt_plan_cast(int variant, uint32_t ns, uint32_t geom_f4, int grid_usable, uint32_t n, uint32_t batches_req);
+/* how a proximity query (whitted_near.inc: wt_near) of `n` probes reads the scene and how it is launched: the geometry class by wt_plan_cast's
+ * rules, one wave per workgroup, one batch of 64 probes each (groups = 0: n is not a count the queries accept).  `grid_usable` here also asks
+ * that every prepared r * r word is finite (the box proof of whitted_near.inc needs it; the shim checks when it builds the grid).
+ * box_cells: on the grid, the most cells a probe's box may cover before the probe scans every sphere instead -- `box_cells_req` >= 0
+ * overrides it (the tuning knob CLWRAP_NEAR_BOX_CELLS; 0 = every probe scans), else WT_NEAR_BOX_CELLS.  A probe with a box of c cells pays c
+ * cell-range fetches and the tests of the spheres listed there; one that scans pays ns tests.  At about 1.6 spheres per cell and 2-3 cells
+ * per sphere, c cells hold about 4 c entries, so the two meet near c = ns / 4; below a cap, a wave waits for its largest box, above it for
+ * the scan.  WT_NEAR_BOX_CELLS is a provisional constant of that order for the scenes that get a grid at all (more than 256 spheres); the sweep
+ * that should choose it (tools/near_times.py --cap-sweep) has not been run yet. */
+enum { WT_NEAR_BOX_CELLS = 512 };
+typedef struct { int32_t flags; uint32_t dyn_lds, groups, box_cells; } wt_near_class;
+wt_near_class wt_plan_near(int variant, uint32_t ns, uint32_t geom_f4, int grid_usable, uint32_t n, int32_t box_cells_req);
 
 /* Which tile order a tiled launch reads and which builds it must wait for (hip_wrap.cpp: Impl::Sched).  Trace k writes its tile costs into
  * cost[wr]; when the signature changed, order[wr] is built from them on a side stream behind it, while trace k + 1 already runs with the

@@ -11,13 +11,10 @@
 
 int wt_layers_check(uint32_t n, uint32_t flags, uint32_t K) { return wt_cast_check(n, flags) && K >= 1u && K <= (uint32_t)WT_LAYERS_MAX; }
 
-/* a ray's list: the K smallest keys (t, id) met so far, ascending; entries past `count` are not read */
-typedef struct { clw_layer e[WT_LAYERS_MAX]; uint32_t count, K; } layer_list;
-
 static int key_before(float t, uint32_t id, const clw_layer* e) { return t < e->t || (t == e->t && id < e->id); }
 
 /* a candidate (hit && t <= tmax) of the ray: listed iff t < +inf; kept iff it is among the K smallest keys */
-static void list_candidate(layer_list* L, float t, uint32_t id) {
+void wt_layers_candidate(wt_layer_list* L, float t, uint32_t id) {
     if (!(t < INFINITY)) return;
     uint32_t at = L->count;
     while (at > 0u && key_before(t, id, &L->e[at - 1u])) at--;
@@ -29,11 +26,11 @@ static void list_candidate(layer_list* L, float t, uint32_t id) {
 }
 
 /* the visitor of cast_host.c's wt_cast_enumerate: the list of the ray under way, and where a finished one goes */
-typedef struct { layer_list L; float* t_out; uint32_t* id_out; uint32_t n; } layers_out;
+typedef struct { wt_layer_list L; float* t_out; uint32_t* id_out; uint32_t n; } layers_out;
 
 static void layers_begin(void* ctx) { ((layers_out*)ctx)->L.count = 0u; }
 
-static void layers_take(void* ctx, float t, uint32_t id) { list_candidate(&((layers_out*)ctx)->L, t, id); }
+static void layers_take(void* ctx, float t, uint32_t id) { wt_layers_candidate(&((layers_out*)ctx)->L, t, id); }
 
 static void layers_done(void* ctx, uint32_t k, const clw_ray* ray, const wt_cast_geom* g) {
     layers_out* s = (layers_out*)ctx;

@@ -1,7 +1,7 @@
 /* ref_tests.h -- the reference arithmetic of every pass beside the trace launch, as ONE text: the hit tests, a hit's point and normal, the
- * outgoing ray of a path, the ambient occlusion basis and resolve, a projected pixel's ray.  Compiled twice from this one text, as
- * primary_cull_host.h is: by the C compiler into the host definitions (cast_host.c, layers_host.c, paths_host.c, ao_host.c, projection_host.c)
- * and by the device compiler into the passes held to them bit for bit (whitted_gbuffer/query/cast/layers/paths/ao/projection.inc, in the fast
+ * outgoing ray of a path, a point's distance from a surface, the ambient occlusion basis and resolve, a projected pixel's ray.  Compiled twice from this one text, as
+ * primary_cull_host.h is: by the C compiler into the host definitions (cast_host.c, layers_host.c, near_host.c, paths_host.c, ao_host.c, projection_host.c)
+ * and by the device compiler into the passes held to them bit for bit (whitted_gbuffer/query/cast/layers/near/paths/ao/projection.inc, in the fast
  * and the strict unit).  Only + - * / sqrt, fabs, copysign and comparisons on float32, each rounded once: no fused operation anywhere
  * (`#pragma clang fp contract(off)` in every function that computes a float; the host C files are built with -ffp-contract=off as well), and
  * both device units are built with correctly rounded divide and square root.  So the per-ray arithmetic of host and device is equal by
@@ -95,6 +95,22 @@ REF_FN int ref_plane(ref_v3 o, ref_v3 d, ref_v3 n, ref_v3 p0, float* t) { return
 REF_FN ref_v3 ref_hit_point(ref_v3 o, ref_v3 d, float t) { return ref_madd(d, t, o); }
 REF_FN ref_v3 ref_hit_normal(int plane, ref_v3 point, ref_v3 g) { return plane ? g : ref_normalize(ref_sub(point, g)); }
 REF_FN ref_v3 ref_hit_offset(ref_v3 point, ref_v3 n) { return ref_madd(n, REF_EPSILON, point); }
+
+/* ---- proximity: how far a point p is from a surface, and the surface's nearest point (the proximity queries: near_host.c, whitted_near.inc) ---- */
+/* the sphere or light {c, q = +-r r}, v = p - c: d = |v| - sqrt(|q|), signed, negative inside */
+REF_FN float ref_near_sphere(ref_v3 v, float q) { REF_FP return ref_length(v) - sqrtf(fabsf(q)); }
+/* the plane of normal n through p0, a two-sided sheet: s = (p - p0).n, d = |s| */
+REF_FN float ref_near_plane_s(ref_v3 p, ref_v3 n, ref_v3 p0) { return ref_dot(ref_sub(p, p0), n); }
+/* a surface at distance d is a candidate of a probe that reaches `reach` (a NaN on either side is none) */
+REF_FN int ref_near_candidate(float d, float reach) { return d <= reach; }
+/* the sphere's normal toward p, N = v / |v|, and its nearest point c + N r; at the centre both are the NaNs this computes */
+REF_FN void ref_near_sphere_point(ref_v3 p, ref_v3 c, float q, ref_v3* N, ref_v3* point) {
+    REF_FP
+    *N = ref_normalize(ref_sub(p, c));
+    *point = ref_madd(*N, sqrtf(fabsf(q)), c);
+}
+/* the plane's nearest point p - n s (n taken for unit, as the reference's shading takes it) */
+REF_FN ref_v3 ref_near_plane_point(ref_v3 p, ref_v3 n, float s) { REF_FP return ref_mk(p.x - n.x * s, p.y - n.y * s, p.z - n.z * s); }
 
 /* ---- paths: what becomes of a hit (raytracing.cl:139-179 without the weights) ---- */
 /* the four words of a 96-byte sphere or plane record that decide where a path goes: byte 64 = offset 32 of its material */

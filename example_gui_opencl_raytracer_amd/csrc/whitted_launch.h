@@ -39,6 +39,8 @@ WT_BOTH(hipError_t, launch_cast, (const whitted_params* P, int flags, unsigned g
                                   unsigned cast_flags, void* hits, unsigned char* blocked, hipStream_t s))
 WT_BOTH(hipError_t, launch_cast_layers, (const whitted_params* P, int flags, size_t dyn_lds, const void* rays, unsigned n, unsigned cast_flags, unsigned K,
                                          unsigned capacity, float* t, unsigned* id, hipStream_t s))
+WT_BOTH(hipError_t, launch_near, (const whitted_params* P, int flags, size_t dyn_lds, unsigned box_cells, const void* probes, const unsigned* ignore,
+                                  unsigned n, unsigned cast_flags, unsigned K, void* hits, unsigned char* within, float* d, unsigned* id, hipStream_t s))
 WT_BOTH(hipError_t, launch_cast_paths, (const whitted_params* P, int flags, size_t dyn_lds, const void* rays, unsigned n, unsigned path_flags,
                                         unsigned bounces, void* hits, unsigned char* status, void* next, hipStream_t s))
 WT_BOTH(hipError_t, launch_camera_rays, (const whitted_params* P, const wt_projection* T, void* rays, hipStream_t s))

@@ -1,6 +1,6 @@
 /* whitted_launch.inc -- instantiates the kernels of whitted_trace.inc (and the primary-hit pass of whitted_gbuffer.inc, built from its
  * pieces, the camera models of whitted_projection.inc, the queries' shared scan of whitted_query.inc, the ambient occlusion pass of
- * whitted_ao.inc, the ray queries of whitted_cast.inc, the layered ray queries of whitted_layers.inc, the path queries of whitted_paths.inc, the selection overlay of
+ * whitted_ao.inc, the ray queries of whitted_cast.inc, the layered ray queries of whitted_layers.inc, the proximity queries of whitted_near.inc, the path queries of whitted_paths.inc, the selection overlay of
  * whitted_overlay.inc, the visible-object table of whitted_objects.inc and the builder of the primary-ray cull table of whitted_cull.inc) in
  * namespace WT_NS and exports the C launchers the shim calls. */
 #include "bounce_cull_host.h"      /* (and through it primary_cull_host.h) */
@@ -13,6 +13,7 @@ namespace WT_NS {
 #include "whitted_ao.inc"
 #include "whitted_cast.inc"
 #include "whitted_layers.inc"
+#include "whitted_near.inc"
 #include "whitted_paths.inc"
 #include "whitted_overlay.inc"
 #include "whitted_objects.inc"
@@ -322,6 +323,28 @@ WT_LAUNCHER(cast_layers)(const whitted_params* P, int flags, size_t dyn_lds, con
     const dim3 g((n + 63u) / 64u), block(WT_BLOCK);
     if (capacity == 4u) WT_LAUNCH_FLAVOUR(wt_cast_layers, WT_TAIL(4), flags, g, block, 0, dyn_lds, 0, s, *P, A);
     else WT_LAUNCH_FLAVOUR(wt_cast_layers, WT_TAIL(8), flags, g, block, 0, dyn_lds, 0, s, *P, A);
+    return hipGetLastError();
+}
+
+/* proximity queries (whitted_near.inc): wt_near over `n` probes (1 float4 each; `ignore` a word each, or null) on the device, one workgroup of
+ * one wave per 64 probes, geometry as the caller's plan chose it (launch_plan.c: wt_plan_near -- flags as the gbuffer launcher, `box_cells` the
+ * cap on a probe's box on the grid).  Exactly one output is given: `hits` (the nearest: 2 float4 per probe), `within` (a byte per probe), or
+ * `d` and `id` together with K in 1..8 (K * n words each, layer-major; the list capacity run is the smallest of 4 and 8 that holds K).  The
+ * caller has checked n, cast_flags and K (csrc/near_host.h: wt_near_check, wt_near_list_check) */
+WT_LAUNCHER(near)(const whitted_params* P, int flags, size_t dyn_lds, unsigned box_cells, const void* probes, const unsigned* ignore, unsigned n,
+                  unsigned cast_flags, unsigned K, void* hits, unsigned char* within, float* d, unsigned* id, hipStream_t s) {
+    const int outputs = (hits != nullptr) + (within != nullptr) + (d != nullptr || id != nullptr);
+    if (n == 0u || n >= (1u << 30) || !(cast_flags & 7u) || (cast_flags & ~15u) || !probes || outputs != 1 || ((d != nullptr) != (id != nullptr)) ||
+        (d && (K == 0u || K > 8u)) || dyn_lds > 48u * 1024u)
+        return hipErrorInvalidValue;
+    WT_NS::wt_near_args A = {};
+    A.probes = (const float4*)probes; A.ignore = ignore; A.hits = (float4*)hits; A.within = within; A.d = d; A.id = id;
+    A.n = n; A.flags = cast_flags; A.K = K; A.box_cells = box_cells;
+    const dim3 g((n + 63u) / 64u), block(WT_BLOCK);
+    if (hits) WT_LAUNCH_FLAVOUR(wt_near, WT_TAIL(0), flags, g, block, 0, dyn_lds, 0, s, *P, A);
+    else if (within) WT_LAUNCH_FLAVOUR(wt_near, WT_TAIL(1), flags, g, block, 0, dyn_lds, 0, s, *P, A);
+    else if (K <= 4u) WT_LAUNCH_FLAVOUR(wt_near, WT_TAIL(4), flags, g, block, 0, dyn_lds, 0, s, *P, A);
+    else WT_LAUNCH_FLAVOUR(wt_near, WT_TAIL(8), flags, g, block, 0, dyn_lds, 0, s, *P, A);
     return hipGetLastError();
 }
 

@@ -62,6 +62,12 @@ ray GOES: its hit, the reference's reflected (with ``transmit``, through glass: 
 to 8 segments in one launch; ``pick_path`` answers what a pixel shows and what is reflected in that.  Nothing else the renderer holds is
 touched; ``pick_path`` is not available with row bands.
 
+``nearest_surface(points, reach)`` / ``within_reach(points, reach)`` / ``near_surfaces(points, K, reach)`` / ``probe_device(...)`` /
+``near_surfaces_device(...)`` / ``touching_spheres(margin, K)``: proximity queries (clw_ext_nearest_surface) -- what lies AROUND a point, no
+direction involved: the nearest surface within ``reach`` (signed distance, id, normal, nearest point; a point inside a sphere has a negative
+distance), whether a ball of that radius touches anything, or the K (1..8) nearest surfaces in order; ``touching_spheres`` asks it of every
+sphere of the scene.  Nothing else the renderer holds is touched.
+
 ``projection=...`` / ``set_projection(model, ...)`` / ``look_ortho`` / ``look_panorama``: the camera models beside the pinhole
 (clw_ext_set_projection) -- ``'ortho'``: parallel rays from the image plane, the top / front / side view of an editor; ``'equirect'``: a
 latitude-longitude panorama of up to 360 x 180 degrees around the camera origin.  ``render()``, ``read_rays()``, ``gbuffer()``, ``pick``,
@@ -334,6 +340,67 @@ class Renderer:
         a = np.asarray(a, np.float32).reshape(-1, 3)
         b = np.asarray(b, np.float32).reshape(-1, 3)
         return ~self.cast_rays(a, b - a, tmax=1.0, opaque_only=opaque_only, any_hit=True)
+
+    # ---- proximity queries
+    def nearest_surface(self, points, reach=np.inf, ignore=None, kinds=("sphere", "plane"), opaque_only: bool = False) -> np.ndarray:
+        """The surface nearest to every point (array of [n, 3]) among those within `reach` of it -> api.HIT [n]: t = the distance (signed for a
+        sphere or light: negative inside; inf = nothing within reach), id (api.ID_NONE = nothing), the surface's normal toward the point and its
+        nearest point.  reach and ignore (the id word of the one primitive a probe does not test; None = none) are scalar or per point; a
+        negative reach asks for penetrations at least that deep; kinds and opaque_only as ``cast_rays``.  Needs no camera."""
+        got = self.w.nearest_surface(api.make_probes(points, reach), api.cast_flags(kinds, opaque_only), ignore)
+        if got is None:
+            raise RuntimeError("the proximity query was refused (at least one point, at least one kind?)")
+        return got
+
+    def within_reach(self, points, reach, ignore=None, kinds=("sphere", "plane"), opaque_only: bool = False) -> np.ndarray:
+        """Does a ball of radius `reach` placed at every point touch anything? -> bool [n] (arguments as ``nearest_surface``)."""
+        got = self.w.within_reach(api.make_probes(points, reach), api.cast_flags(kinds, opaque_only), ignore)
+        if got is None:
+            raise RuntimeError("the proximity query was refused (at least one point, at least one kind?)")
+        return got.astype(bool)
+
+    def near_surfaces(self, points, K: int = 4, reach=np.inf, ignore=None, kinds=("sphere", "plane"), opaque_only: bool = False) -> dict:
+        """The K nearest surfaces within `reach` of every point (arguments as ``nearest_surface``) -> {"d": float32 [K, n], "id": uint32 [K, n]}:
+        entry k of point i at [k, i], ordered by (d, id word), every primitive at most once, entries past a point's candidates {inf,
+        api.ID_NONE}.  K is 1..8; there is no total count: a full K-th row means "ask for more"."""
+        got = self.w.near_surfaces(api.make_probes(points, reach), api.cast_flags(kinds, opaque_only), K, ignore)
+        if got is None:
+            raise RuntimeError("the proximity query was refused (at least one point, at least one kind, K in 1..8?)")
+        return got
+
+    @staticmethod
+    def _address(buffer):
+        """the device address of a torch tensor (``data_ptr()``), or the integer address itself; None stays None"""
+        return buffer if buffer is None else int(buffer.data_ptr() if hasattr(buffer, "data_ptr") else buffer)
+
+    def probe_device(self, probes, n: int, hits=None, within=None, ignore=None, kinds=("sphere", "plane"), opaque_only: bool = False) -> int:
+        """The nearest-surface or the within-reach query over the caller's device memory -- torch tensors or integer device addresses: n
+        api.PROBE records in (float32 [n, 4]: point, reach), optionally n uint32 ignore words, n api.HIT records (`hits`: float32 [n, 8]) or n
+        bytes (`within`) out -- exactly one of the two.  Launched on the wrapper's stream (``w.set_stream``) without waiting -> n."""
+        got = self.w.probe_device(self._address(probes), n, api.cast_flags(kinds, opaque_only), self._address(ignore), self._address(hits),
+                                  self._address(within))
+        if got != n:
+            raise RuntimeError("the proximity query was refused (at least one point, at least one kind, exactly one of hits and within?)")
+        return got
+
+    def near_surfaces_device(self, probes, n: int, K: int, d, ids, ignore=None, kinds=("sphere", "plane"), opaque_only: bool = False) -> int:
+        """The K-nearest query over the caller's device memory (torch tensors or integer device addresses): n api.PROBE records in, K * n floats
+        and K * n id words out, layer-major.  Launched on the wrapper's stream without waiting -> n."""
+        got = self.w.near_surfaces_device(self._address(probes), n, api.cast_flags(kinds, opaque_only), K, self._address(d), self._address(ids),
+                                          self._address(ignore))
+        if got != n:
+            raise RuntimeError("the proximity query was refused (at least one point, at least one kind, K in 1..8, all three addresses?)")
+        return got
+
+    def touching_spheres(self, margin: float = 0.0, K: int = 8):
+        """Which spheres of the scene touch each other (or come within `margin`)?  Probe i sits at sphere i's centre, reaches |r_i| + margin
+        (float32) and ignores sphere i; only spheres take part -> (id uint32 [K, ns], gap float32 [K, ns]): the up to K spheres nearest to
+        sphere i's surface in order, gap = their distance from it (d - |r_i|, float32; negative = they overlap), empty entries {api.ID_NONE,
+        inf}.  A full K-th row means "ask for more"."""
+        s = self.scene.spheres
+        r = np.abs(s["radius"].astype(np.float32))
+        got = self.near_surfaces(s["origin"], K, reach=r + np.float32(margin), ignore=np.arange(len(s), dtype=np.uint32), kinds=("sphere",))
+        return got["id"], got["d"] - r[None, :]
 
     # ---- layered ray queries
     def cast_layers(self, origins, dirs, K: int = 4, tmax=np.inf, ignore=None, kinds=("sphere", "plane"), opaque_only: bool = False) -> dict:

@@ -721,6 +721,64 @@ int      clw_ext_pick_path(cl_wrap* wrap, uint32_t x, uint32_t y, uint32_t bounc
                            uint8_t* out_status);
 #define CLW_TIMING_PATHS 0x50415448u
 
+/* ---- proximity queries: what lies around a point -- the nearest surface, whether anything is within reach, the K nearest surfaces.  The
+ * questions that have no direction: how far is this point from the nearest object and which one is it, does a ball of radius R placed here
+ * touch anything, which spheres touch each other.  clw_host_nearest_surface, clw_host_within_reach and clw_host_near_surfaces are THE
+ * definition; the device pass (wt_near: csrc/whitted_near.inc) equals them bit for bit in both builds.  The regime is the ray queries': float32,
+ * one rounding per operation, never fused, IEEE square root and divide, dot products left to right, the scene read through the prepared words
+ * {c, +-r * r}, {n}, {p0} the device reads.  flags are CLW_CAST_SPHERES | PLANES | LIGHTS | OPAQUE with their meaning above; the primitives take
+ * part in the same order (spheres, planes, lights, ascending index); a primitive whose id word equals ignore[k] is skipped (`ignore` NULL, or
+ * the word CLW_ID_NONE: nothing is); with CLW_CAST_OPAQUE a sphere whose prepared word has its sign bit set is skipped.
+ *   Probe k = {p, reach} against
+ *   - a sphere or light {c, q}: v = p - c, m = sqrtf(v.v), r = sqrtf(|q|), d = m - r -- signed, negative inside.  Normal N = v / m per
+ *     component, nearest point c + N * r per component (the product, then the sum).  At the centre m = 0: N and the point are the NaNs this
+ *     computes and d = -r; they are stored as computed.
+ *   - a plane {n, p0}: s = (p - p0).n, d = fabsf(s) -- the two-sided sheet the tracer shades.  Nearest point p - n * s per component (the
+ *     product, then the difference); normal = the stored n, never flipped and taken for unit.
+ *   CANDIDATE iff d <= reach.  So a NaN point or a NaN reach meets nothing, reach = +inf is unlimited, and a negative reach is legal: only
+ *   penetrations at least that deep.
+ *   - nearest: the smallest key (d, id word) -- a candidate replaces the best iff d < best, so an equal d keeps the earlier primitive -- as a
+ *     clw_hit {t = d, id, normal, point}.  No candidate: the miss record of clw_host_cast_rays.  A candidate at d = +inf raises `within` but
+ *     keeps the miss record.
+ *   - within: within[k] = 1 iff probe k has a candidate, else 0.
+ *   - K nearest (1..8): exactly the list rules of clw_host_cast_layers with d for t -- listed iff d < +inf, ordered by (d, id), every
+ *     primitive at most once, planar and layer-major d[k * n + i], id[k * n + i], empty entries {+inf, CLW_ID_NONE}.  K is a prefix of K + 1,
+ *     and layer 0 is {d, id} of the nearest query wherever that is finite.
+ *   Refused (0 returned, nothing written): whatever clw_host_cast_rays refuses for n, flags and NULL arrays; K == 0 or K > 8; a NULL output. */
+typedef struct clw_probe { float point[3]; float reach; } clw_probe;   /* 16 bytes */
+int clw_host_nearest_surface(const clw_probe* probes, const uint32_t* ignore /* n words, or NULL */, uint32_t n, uint32_t flags,
+                             const void* spheres, uint32_t ns, const void* planes, uint32_t np, const void* lights, uint32_t nl,
+                             clw_hit* out);                     /* 1 = done, 0 = refused */
+int clw_host_within_reach(const clw_probe* probes, const uint32_t* ignore, uint32_t n, uint32_t flags, const void* spheres, uint32_t ns,
+                          const void* planes, uint32_t np, const void* lights, uint32_t nl, uint8_t* within);      /* 0 / 1 per probe */
+int clw_host_near_surfaces(const clw_probe* probes, const uint32_t* ignore, uint32_t n, uint32_t flags, const void* spheres, uint32_t ns,
+                           const void* planes, uint32_t np, const void* lights, uint32_t nl, uint32_t K, float* d /* K * n */,
+                           uint32_t* id /* K * n */);
+/* On the device, against the wrapper's bound scene, with the conventions of the clw_ext_cast_* calls: the scene is prepared if needed (a call
+ * after clw_ext_invalidate_scene sees the rewritten scene) and read staged in LDS, from global memory or through the uniform grid as
+ * wt_plan_near decides -- on the grid a probe tests the spheres listed in the cells of the box its reach spans (csrc/whitted_near.inc states
+ * and proves the box); a probe whose box covers more than a cap of cells (CLWRAP_NEAR_BOX_CELLS in the environment overrides the built-in
+ * cap) or whose reach is not finite scans every sphere.  Same answer either way.
+ * clw_ext_nearest_surface / clw_ext_within_reach / clw_ext_near_surfaces take HOST arrays (n probes; n ignore words or NULL), wait and return
+ * n; their staging buffers are allocated at first use, grown at need and freed by cl_wrap_release.  clw_ext_probe_device and
+ * clw_ext_near_surfaces_device take the caller's DEVICE memory of the same sizes (d_ignore may be NULL; exactly one of d_hits / d_within is
+ * non-NULL), launch on the wrapper's stream -- the caller's after clw_ext_set_stream --, do not wait and return n.
+ * 0 is returned and nothing launched for what the definition refuses, when no scene is bound and, for clw_ext_probe_device, when both or
+ * neither output is given.  The framebuffer, the buffers of clw_ext_render_gbuffer, the overlay, the object table, the AO pass, the ray,
+ * layered and path queries, an accumulating view and its count, the tile order and clw_ext_last_trace_flags are left alone.  Launches are
+ * logged under CLW_TIMING_NEAR in clw_ext_timing_get.
+ * Not built: swept balls; an expanding search for an unlimited reach on the grid (such a probe scans every sphere); per-probe flags; a
+ * clearance view over the primary-hit point channel. */
+uint32_t clw_ext_nearest_surface(cl_wrap* wrap, const clw_probe* probes, const uint32_t* ignore, uint32_t n, uint32_t flags, clw_hit* out);     /* host arrays; waits */
+uint32_t clw_ext_within_reach(cl_wrap* wrap, const clw_probe* probes, const uint32_t* ignore, uint32_t n, uint32_t flags, uint8_t* within);    /* host arrays; waits */
+uint32_t clw_ext_near_surfaces(cl_wrap* wrap, const clw_probe* probes, const uint32_t* ignore, uint32_t n, uint32_t flags, uint32_t K, float* d,
+                               uint32_t* id);     /* host arrays; waits */
+uint32_t clw_ext_probe_device(cl_wrap* wrap, const void* d_probes, const void* d_ignore, uint32_t n, uint32_t flags, void* d_hits,
+                              void* d_within);   /* exactly one output; no wait */
+uint32_t clw_ext_near_surfaces_device(cl_wrap* wrap, const void* d_probes, const void* d_ignore, uint32_t n, uint32_t flags, uint32_t K, void* d_d,
+                                      void* d_id);   /* no wait */
+#define CLW_TIMING_NEAR 0x4E454152u
+
 /* Work counters of the trace kernel.  enable=1 selects the counting build of the kernel
  * for subsequent launches (slower); read returns and clears
  *   out[0] path segments  out[1] shadow rays  out[2] light probes  out[3] skybox fetches
